@@ -539,6 +539,36 @@ def timed_region(args, torch, dist, world, dev, step, gloo):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write what the timed path computed in its last step, {name: host array of
+    log-posteriors}, as finite arrays that restore it exactly:
+      DIR/<name>_rejected.npy  float32, the array's shape: 1 where the path returned -inf (a walker outside
+                               the prior's support or with a non-finite likelihood, psfMC/models.py:208-241)
+      DIR/<name>.npy           float64, the other entries in row-major order (a NaN or +inf would be a
+                               fault and stays here, in plain sight)
+    Past 64 MB in all, every array is first cut to the same fixed, seeded sample of its flattened elements
+    (DIR/<name>_index.npy holds the flat indices taken).  The inputs depend on the command line alone, so two
+    builds run with the same arguments can be compared file for file."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n_all = sum(v.size for v in arrays.values())
+    # bytes per element: 8 value + 4 mask, and 8 more for the index when sampled; 1 % left for the headers
+    sample = n_all * 12 > 0.99 * DUMP_LIMIT_BYTES
+    frac = min(1.0, 0.99 * DUMP_LIMIT_BYTES / (n_all * 20)) if sample else 1.0
+    for name, val in arrays.items():
+        if sample:
+            keep = max(1, int(val.size * frac))
+            idx = np.sort(np.random.RandomState(1234).choice(val.size, keep, replace=False))
+            np.save(os.path.join(directory, name + '_index.npy'), idx.astype(np.float64))
+            val = val.reshape(-1)[idx]
+        rejected = val == -np.inf
+        np.save(os.path.join(directory, name + '_rejected.npy'), rejected.astype(np.float32))
+        np.save(os.path.join(directory, name + '.npy'), val[~rejected])
+
+
 def fields_mcmc_rates(args, probs, merged, n_iter=60):
     """Config 5 as a FIT (psfMC/fitting.py:56-86 for every field): stretch-move iterations per second
     with the fields' ensembles stepped TOGETHER in the shared context (`FieldSetSampler`) and one after
@@ -619,6 +649,9 @@ def many_fields(args, torch, dist, world, rank, local, dev, gloo):
                 eng.logpost_theta_device(args.walkers, t.data_ptr(), 0, o.data_ptr(), None)
 
     elapsed = timed_region(args, torch, dist, world, dev, step, gloo)
+    if args.dump_outputs and rank == 0:      # this rank's fields, before the check below reuses `outs`
+        last = all_out.view(args.fields, args.walkers) if merged is not None else torch.stack(outs)
+        dump_outputs(args.dump_outputs, {'logpost': last.cpu().numpy()})
     finite = int(sum(int(torch.isfinite(o).sum().item()) for o in outs))
     agree = None
     if merged is not None:
@@ -962,7 +995,13 @@ def main():
     ap.add_argument('--extras-timeout', type=float, default=420.0,
                     help='N > 1: seconds the multi_gpu side figures may take before rank 0 prints the headline line '
                          'without them and every rank leaves')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the log-posteriors of the last step (one row per resident '
+                         'set of walkers, or per field) as DIR/logpost_rejected.npy (1 where -inf) and '
+                         'DIR/logpost.npy (the other values, float64); see dump_outputs')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.cpu_worker >= 0:
         return cpu_worker(args)
     env_world = os.environ.get('WORLD_SIZE')
@@ -1069,6 +1108,10 @@ def main():
                 gathered[b] = sharded.evaluate_device(theta_dev[b])
 
     elapsed = timed_region(args, torch, dist, world, dev, step, gloo)
+    if args.dump_outputs and rank == 0:
+        # the last step wrote every resident set once; taken before the checks and side figures below reuse `out`
+        last = out if sharded is None else torch.stack([gathered[b] for b in range(n_sets)])
+        dump_outputs(args.dump_outputs, {'logpost': last.cpu().numpy()})
     sharded_check = None
     if world > 1:
         # every rank holds every block: this rank's own block evaluated alone must be what the gather put in
