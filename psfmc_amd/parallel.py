@@ -166,24 +166,46 @@ class ShardedLogPosterior(object):
         that device with every rank's block in place.  Nothing crosses the host: the rank evaluates its
         contiguous block (`psfmc_eval_theta_device`) and the blocks are exchanged by the one all-gather
         (`RankGroup.all_gather_blocks`).  Needs a `MultiComponentModel` whose priors all have a device
-        form.  The result is ordered on the stream of `RankGroup.on_stream()`: synchronise the device (or
-        that stream) before reading it elsewhere."""
+        form.  The work runs on the stream of `RankGroup.on_stream()`, ordered after what the caller's
+        current stream has enqueued so far (a `theta_dev` still being written there included); the
+        caller's current stream then waits for it, so the result may be used there directly (it is
+        `record_stream`ed for that stream).  Any other stream synchronises first."""
         if self.model is None:
             raise ValueError('evaluate_device needs a MultiComponentModel')
+        rg = self.ranks
+        torch = rg.torch
+        # the library reads the tensor through its raw pointer as [W, num_params] float64
+        if not isinstance(theta_dev, torch.Tensor):
+            raise ValueError('theta_dev must be a torch tensor, got {}'.format(type(theta_dev).__name__))
+        if theta_dev.dtype != torch.float64:
+            raise ValueError('theta_dev must be float64, got {}'.format(theta_dev.dtype))
+        if theta_dev.dim() != 2 or theta_dev.shape[1] != self.model.num_params:
+            raise ValueError('theta_dev must be [W, {}], got {}'.format(self.model.num_params,
+                                                                     tuple(theta_dev.shape)))
+        if not theta_dev.is_contiguous():
+            raise ValueError('theta_dev must be contiguous')
+        if theta_dev.device != rg.device:
+            raise ValueError('theta_dev must be on {}, got {}'.format(rg.device, theta_dev.device))
         eng = self.model.engine                                     # creates context + layout
         if self.model._host_priors:
             raise ValueError('evaluate_device needs a model whose priors all have a device form')
-        rg = self.ranks
-        torch = rg.torch
         n_w = int(theta_dev.shape[0])
         lo, hi = rg.block(n_w)
+        caller = torch.cuda.current_stream(rg.device) if rg.device.type == 'cuda' else None
         with rg.on_stream():
+            side = torch.cuda.current_stream(rg.device) if caller is not None else None
+            if side is not None and side != caller:
+                side.wait_stream(caller)
             stream = rg.stream_ptr()
             send = torch.full((max(rg.slot(n_w), 1),), float('nan'), dtype=torch.float64, device=rg.device)
             for a in range(lo, hi, eng.max_walkers):                # larger blocks go through in slices
                 b = min(a + eng.max_walkers, hi)
                 eng.logpost_theta_device(b - a, theta_dev[a:b].data_ptr(), 0, send[a - lo:].data_ptr(), stream)
-            return rg.all_gather_blocks(send, n_w)
+            out = rg.all_gather_blocks(send, n_w)
+            if side is not None and side != caller:
+                caller.wait_stream(side)
+                out.record_stream(caller)
+            return out
 
     def __call__(self, theta):
         theta = np.ascontiguousarray(theta, dtype=np.float64)
