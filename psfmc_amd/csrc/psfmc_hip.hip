@@ -368,7 +368,7 @@ struct psfmc_ctx {
     bool rows3_fwd = false, rows3_inv = false;
     long long speculated_runs = 0;   // psfmc_stretch_run calls that took the whole-iteration route
     int speculate = -1;       // device sampler: ensembles of up to 2 x this many walkers run ONE pipeline pass per iteration (0 = never, -1 = the default rule)
-    int cols3 = 1;            // column kernel on the wave-wide three-stage engines: 0 never, 1 the defaults (k_cols3f at 512 / 1536 / 2048, k_cols3 at 1024, k_cols3g at the other sides of fft3g_pick), 2 k_cols3g at those four as well, 3 round 3's k_cols3 at 512 / 1024, 4 k_cols3f at 1024 too
+    int cols3 = 1;            // column kernel (set_option "cols3", launch_cols): 0 the two-stage k_cols (sides <= 1024 only), 1 the defaults (k_cols3f at 512 / 1024 / 1536 / 2048, k_cols3g at the other sides of fft3g_pick), 2 k_cols3g at those four as well, 3 round 3's k_cols3 at 512 / 1024 (elsewhere as 2), 4 the same as 1
     bool use_graph = false;   // psfmc_stretch_run replays a captured iteration (set_option "graph"; measured: no gain,
                               // the iteration is kernel-time- not launch-bound)
     long long graph_launches = 0;
@@ -1488,6 +1488,12 @@ extern "C" int psfmc_set_option(psfmc_ctx* c, const char* key, double value) {
         return PSFMC_OK;
     }
     if (!strcmp(key, "cols3")) {
+        // refused here, not at the next evaluation: only the engines launch_cols knows, and k_cols only where the
+        // transform's column side has a two-stage kernel
+        if (!(value >= 0 && value <= 4) || value != (double)(int)value)
+            return fail(PSFMC_EINVAL, "cols3 must be one of 0, 1, 2, 3, 4 (got %g)", value);
+        if (value == 0 && c->backend == PSFMC_BACKEND_FUSED && !two_stage_side(c->ny))
+            return fail(PSFMC_EINVAL, "cols3 = 0: transform side %d has only the three-stage column kernels", c->ny);
         c->cols3 = (int)value;
         return PSFMC_OK;
     }
@@ -1556,6 +1562,7 @@ extern "C" double psfmc_get_option(const psfmc_ctx* cc, const char* key) {
     if (!strcmp(key, "streams")) return c->n_streams;
     if (!strcmp(key, "stagger")) return c->stagger;
     if (!strcmp(key, "exclusive")) return c->exclusive;
+    if (!strcmp(key, "cols3")) return c->cols3;
     if (!strcmp(key, "linear_accumulation")) return c->linear_acc ? 1.0 : 0.0;
     return NAN;
 }

@@ -501,7 +501,8 @@ def test_schedule_paths_cover_every_family():
 def test_schedule_invariance_across_kernel_families(path):
     """A distinct-walker batch gives the same bits under every schedule: streams 1 ... 4, passes of 1, 3, 5
     walkers and the default, a single pass split over two streams (min_split), a permuted batch, single-walker and
-    pass-straddling sub-batches, and the device sampler with and without graph replay.  A missing event between
+    pass-straddling sub-batches, every `exclusive` chaining with and without `stagger`, and the device sampler with
+    and without graph replay.  A missing event between
     lanes or a pass offset applied twice would change some walker's value."""
     from psfmc_amd import DeviceEnsembleSampler
     shape, col, rows3, group, embedded = path
@@ -516,6 +517,7 @@ def test_schedule_invariance_across_kernel_families(path):
     transform = (int(eng.get_option('transform_ny')), int(eng.get_option('transform_nx')))
     assert (transform != shape) == embedded, transform
     default = int(eng.get_option('chunk_walkers'))
+    default_stagger = int(eng.get_option('stagger'))
     base = model.log_posterior_batch(theta)
     inside = np.isfinite(model.log_priors_batch(theta))
     assert np.isfinite(base[inside]).all() and np.all(base[~inside] == -np.inf)
@@ -542,6 +544,24 @@ def test_schedule_invariance_across_kernel_families(path):
         eng.set_option('min_split', 1 << 30)
         assert eng.pass_size(n_w) == n_w
         same('min_split off')
+        # the measurement knobs (psfmc_hip.hip run_pipeline): kernels of the kinds in `exclusive` (bits 0 ... 2) of
+        # one pass wait for those of the pass before, on two streams; `stagger` delays the second lane by one
+        # forward-row kernel from 8 passes on -- eight walkers (walker 0 twice) in passes of one
+        eight, want8 = np.vstack([theta, theta[:1]]), np.concatenate([base, base[:1]])
+        for stagger in (0, 1):
+            eng.set_option('stagger', stagger)
+            for exclusive in range(8):
+                eng.set_option('exclusive', exclusive)
+                assert (eng.get_option('stagger'), eng.get_option('exclusive')) == (stagger, exclusive)
+                for streams in (2, 4):
+                    eng.set_option('streams', streams)
+                    for chunk in (1, default):
+                        eng.set_option('chunk_walkers', chunk)
+                        same(('stagger', stagger, 'exclusive', exclusive, streams, chunk))
+                        assert np.array_equal(model.log_posterior_batch(eight), want8), (shape, stagger, exclusive)
+        eng.set_option('stagger', default_stagger)
+        eng.set_option('exclusive', 0)
+        eng.set_option('streams', 2)
         eng.set_option('chunk_walkers', default)
         perm = np.random.RandomState(shape[0]).permutation(n_w)
         assert np.array_equal(model.log_posterior_batch(theta[perm]), base[perm]), shape
@@ -561,6 +581,8 @@ def test_schedule_invariance_across_kernel_families(path):
         eng.set_option('min_split', 1 << 30)
         eng.set_option('streams', 2)
         eng.set_option('chunk_walkers', default)
+        eng.set_option('stagger', default_stagger)
+        eng.set_option('exclusive', 0)
     model.close()
 
 
