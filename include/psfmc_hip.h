@@ -152,6 +152,7 @@ int psfmc_eval_images(psfmc_ctx* ctx, int W, const double* rows,
  * Prior families per vector column: 0 = evaluated by the host (passed per walker in
  * `extra_lnprior`), 1 uniform(loc=p0, scale=p1), 2 normal(loc=p0, scale=p1),
  * 3 weibull_min(c=p0, loc=p1, scale=p2), 4 randint(low=p0, high=p1) on the rounded value.
+ * psfmc_set_layout accepts families 0-4 only; psfmc_set_priors then replaces the whole table.
  */
 #define PSFMC_PRIOR_HOST         0
 #define PSFMC_PRIOR_UNIFORM      1
@@ -162,6 +163,42 @@ int psfmc_set_layout(psfmc_ctx* ctx, int n_sky, int n_params, const int* slot_co
                      const double* slot_const, const int* ps_method, const int* sersic_degrees,
                      double mag_zeropoint, const int* family, const double* p0, const double* p1,
                      const double* p2);
+/*
+ * The full prior table of field `field` (0 for a one-field context), after psfmc_set_layout[_field]:
+ * family [n_params], params [n_params][PSFMC_PRIOR_NPAR] = the scipy.stats arguments in the order below,
+ * unused trailing entries ignored.  Each column's log-density is scipy's frozen logpdf (logpmf for
+ * randint) of the column's value: the same support, closed or open as scipy's (lognorm and invgamma
+ * open, the rest closed), so that the support's edges and the values one ulp on either side give scipy's
+ * result (-inf, a finite value or +inf); NaN gives NaN, and the walker is skipped.
+ *    0 host                                   1 uniform (loc, scale)
+ *    2 norm (loc, scale)                      3 weibull_min (c, loc, scale)
+ *    4 randint (low, high) -- a location is folded in: (low + loc, high + loc)
+ *    5 truncnorm (a, b, loc, scale)           6 lognorm (s, loc, scale)
+ *    7 halfnorm (loc, scale)                  8 expon (loc, scale)
+ *    9 laplace (loc, scale)                  10 cauchy (loc, scale)
+ *   11 halfcauchy (loc, scale)               12 logistic (loc, scale)
+ *   13 t (df, loc, scale)                    14 beta (a, b, loc, scale)
+ *   15 reciprocal = loguniform (a, b, loc, scale)
+ *   16 weibull_max (c, loc, scale)           17 invgamma (a, loc, scale)
+ * PSFMC_EINVAL, with the previous table kept, for an unknown code, parameters scipy rejects (scale <= 0,
+ * a shape <= 0, a >= b for truncnorm / reciprocal, randint bounds not integers with low < high) or that
+ * are not finite (truncnorm's a, b may be infinite), n_params other than the layout's, or no layout yet.
+ */
+#define PSFMC_PRIOR_NPAR         4
+#define PSFMC_PRIOR_TRUNCNORM    5
+#define PSFMC_PRIOR_LOGNORM      6
+#define PSFMC_PRIOR_HALFNORM     7
+#define PSFMC_PRIOR_EXPON        8
+#define PSFMC_PRIOR_LAPLACE      9
+#define PSFMC_PRIOR_CAUCHY      10
+#define PSFMC_PRIOR_HALFCAUCHY  11
+#define PSFMC_PRIOR_LOGISTIC    12
+#define PSFMC_PRIOR_T           13
+#define PSFMC_PRIOR_BETA        14
+#define PSFMC_PRIOR_RECIPROCAL  15
+#define PSFMC_PRIOR_WEIBULL_MAX 16
+#define PSFMC_PRIOR_INVGAMMA    17
+int psfmc_set_priors(psfmc_ctx* ctx, int field, int n_params, const int* family, const double* params);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -228,8 +265,8 @@ int psfmc_debug_theta_rows(psfmc_ctx* ctx, int W, const double* theta, double* r
  * (the sampler the reference drives, psfMC/fitting.py:56-86; algorithm restated in
  * SURVEY.md Appendix A).  The caller supplies the random numbers in emcee's draw order
  * (per half-step: z, partner index, ln u), so a run reproduces the host-side sampler;
- * nothing is copied to the host between iterations.  Needs psfmc_set_layout with every
- * prior on the device (no PSFMC_PRIOR_HOST column).
+ * nothing is copied to the host between iterations.  Needs psfmc_set_layout (and psfmc_set_priors)
+ * with every prior on the device (no PSFMC_PRIOR_HOST column).
  *   pos [W][P], lnprob [W]      in/out (host); lnprob is computed first if !lnprob_valid
  *   lz, log_u [n_iter][2][W/2]  (P-1) ln z and ln u;  z [n_iter][2][W/2]
  *   partner [n_iter][2][W/2]    index into the complementary half-ensemble
@@ -295,6 +332,8 @@ int psfmc_group_set_layout(psfmc_group* group, int n_sky, int n_params, const in
                            const double* slot_const, const int* ps_method, const int* sersic_degrees,
                            double mag_zeropoint, const int* family, const double* p0, const double* p1,
                            const double* p2);
+/* psfmc_set_priors on every device of the group */
+int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, const double* params);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,
                            double* loglike);
 int psfmc_group_eval_theta(psfmc_group* group, int W, const double* theta, const double* extra_lnprior,

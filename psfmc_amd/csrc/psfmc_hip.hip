@@ -1940,7 +1940,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     HIP_TRY(hipDeviceSynchronize());
     // pack everything into one device allocation (8-byte units)
     const size_t n_int = (size_t)ns + c->n_ps + c->n_sersic + n_params;
-    const size_t n_dbl = (size_t)ns + 4 * (size_t)n_params;
+    const size_t n_dbl = (size_t)ns + 5 * (size_t)n_params;         // slot constants, pa, pb, pc, pd (0 here), pk
     const size_t int_bytes = (n_int * sizeof(int) + 7) / 8 * 8;
     std::vector<unsigned char> blob(int_bytes + n_dbl * sizeof(double));
     int* ip = reinterpret_cast<int*>(blob.data());
@@ -1954,7 +1954,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
         memcpy(dp + ns, p0, n_params * sizeof(double));
         memcpy(dp + ns + n_params, p1, n_params * sizeof(double));
         memcpy(dp + ns + 2 * n_params, p2, n_params * sizeof(double));
-        for (int i = 0; i < n_params; ++i) dp[ns + 3 * n_params + i] = prior_log_norm(family[i], p0[i], p1[i], p2[i]);
+        for (int i = 0; i < n_params; ++i) dp[ns + 4 * n_params + i] = prior_log_norm(family[i], p0[i], p1[i], p2[i]);
     }
     if (field > 0 && c->more_layouts.size() < (size_t)c->n_fields - 1) {
         c->more_layouts.resize(c->n_fields - 1);
@@ -1973,7 +1973,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.slot_col = dip; L.ps_method = dip + ns; L.sersic_deg = dip + ns + c->n_ps;
     L.family = dip + ns + c->n_ps + c->n_sersic;
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
-    L.pk = ddp + ns + 3 * n_params;
+    L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
     if (c->n_fields > 1) {
         if (!c->d_field_layouts) HIP_TRY(hipMalloc(&c->d_field_layouts, (size_t)c->n_fields * sizeof(ThetaLayout)));
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
@@ -2002,6 +2002,43 @@ extern "C" int psfmc_set_layout(psfmc_ctx* c, int n_sky, int n_params, const int
                                 const double* p1, const double* p2) {
     return set_layout_impl(c, 0, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees, mag_zeropoint,
                            family, p0, p1, p2);
+}
+
+// Replace field `field`'s prior table: family [n_params], params [n_params][PSFMC_PRIOR_NPAR] (scipy's
+// arguments in order).  Everything is checked before anything is written, so a refused table leaves the
+// previous one in force.  The tables sit in the layout blob (L.family, and L.pa ... L.pk back to back),
+// which keeps its place: the device copies of the layouts stay valid.
+static_assert(kPriorNpar == PSFMC_PRIOR_NPAR && PRIOR_TRUNCNORM == PSFMC_PRIOR_TRUNCNORM &&
+              PRIOR_INVGAMMA == PSFMC_PRIOR_INVGAMMA && PRIOR_N_FAMILIES == PSFMC_PRIOR_INVGAMMA + 1,
+              "prior codes of include/psfmc_hip.h");
+extern "C" int psfmc_set_priors(psfmc_ctx* c, int field, int n_params, const int* family, const double* params) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    const bool has = field == 0 ? c->has_layout
+                                : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    if (n_params != L.n_params)
+        return fail(PSFMC_EINVAL, "%d prior columns for a layout of %d", n_params, L.n_params);
+    if (n_params == 0) return PSFMC_OK;
+    if (!family || !params) return fail(PSFMC_EINVAL, "NULL prior table");
+    std::vector<double> tab(5 * (size_t)n_params);          // pa | pb | pc | pd | pk
+    for (int i = 0; i < n_params; ++i) {
+        const double* p = params + (size_t)kPriorNpar * i;
+        if (family[i] < 0 || family[i] >= PRIOR_N_FAMILIES)
+            return fail(PSFMC_EINVAL, "unknown prior family %d for column %d", family[i], i);
+        if (!prior_params_ok(family[i], p))
+            return fail(PSFMC_EINVAL, "column %d: parameters (%g, %g, %g, %g) invalid for prior family %d", i, p[0],
+                        p[1], p[2], p[3], family[i]);
+        double e[5];
+        prior_prepare(family[i], p, e);
+        for (int j = 0; j < 5; ++j) tab[(size_t)j * n_params + i] = e[j];
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                          // no launch may read the tables being replaced
+    HIP_TRY(hipMemcpy(const_cast<int*>(L.family), family, n_params * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(const_cast<double*>(L.pa), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    return PSFMC_OK;
 }
 
 // the layout of one field of a psfmc_ctx_create_fields context (field 0 first; the same slot / column
@@ -2972,6 +3009,12 @@ extern "C" int psfmc_group_set_layout(psfmc_group* g, int n_sky, int n_params, c
     for (psfmc_ctx* c : g->ctx)
         RC_TRY(psfmc_set_layout(c, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees,
                                 mag_zeropoint, family, p0, p1, p2));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_priors(psfmc_group* g, int n_params, const int* family, const double* params) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_priors(c, 0, n_params, family, params));
     return PSFMC_OK;
 }
 

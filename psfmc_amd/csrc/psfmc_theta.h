@@ -15,7 +15,11 @@
 namespace psfmc {
 
 enum PriorFamily { PRIOR_HOST = 0, PRIOR_UNIFORM = 1, PRIOR_NORMAL = 2, PRIOR_WEIBULL_MIN = 3,
-                   PRIOR_RANDINT = 4 };
+                   PRIOR_RANDINT = 4, PRIOR_TRUNCNORM = 5, PRIOR_LOGNORM = 6, PRIOR_HALFNORM = 7,
+                   PRIOR_EXPON = 8, PRIOR_LAPLACE = 9, PRIOR_CAUCHY = 10, PRIOR_HALFCAUCHY = 11,
+                   PRIOR_LOGISTIC = 12, PRIOR_T = 13, PRIOR_BETA = 14, PRIOR_RECIPROCAL = 15,
+                   PRIOR_WEIBULL_MAX = 16, PRIOR_INVGAMMA = 17, PRIOR_N_FAMILIES = 18 };
+constexpr int kPriorNpar = 4;           // parameters per column in psfmc_set_priors
 
 // slots of a model, in this order: n_sky x [adu] | n_ps x [mag, x, y] |
 // n_sersic x [angle, index, mag, reff, reff_b, x, y] | [psf_index]
@@ -34,8 +38,9 @@ struct ThetaLayout {
     const double* pa;           // [n_params] loc / c / low
     const double* pb;           // [n_params] scale / loc / high
     const double* pc;           // [n_params] - / scale / -
-    const double* pk;           // [n_params] the family's constant log term (prior_log_norm),
-                                //            filled by psfmc_set_layout
+    const double* pd;           // [n_params] families 5..: see prior_prepare
+    const double* pk;           // [n_params] the family's constant log term (prior_log_norm,
+                                //            prior_prepare), filled by psfmc_set_layout / _priors
 };
 
 // ---------------------------------------------------------------------------
@@ -124,6 +129,115 @@ __host__ inline double prior_log_norm(int fam, double a, double b, double c) {
     }
 }
 
+// log Phi(x), the standard normal CDF: erfc on the side away from zero, and below -20 the asymptotic
+// series of the Mills ratio (Abramowitz & Stegun 26.2.12; the tenth term is < 1e-20 there)
+__host__ inline double prior_log_ndtr(double x) {
+    if (x >= 0.0) return log1p(-0.5 * erfc(x * 0.70710678118654752440));
+    if (x > -20.0) return log(0.5 * erfc(-x * 0.70710678118654752440));
+    const double r = 1.0 / (x * x);
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k <= 10; ++k) {
+        term *= -(2.0 * k - 1.0) * r;
+        sum += term;
+    }
+    return -0.5 * x * x - log(-x) - 0.91893853320467274178 + log(sum);
+}
+
+// log(Phi(b) - Phi(a)), a < b: both bounds in the left tail, mirrored when both are in the right one
+__host__ inline double prior_log_gauss_mass(double a, double b) {
+    if (b <= 0.0 || a > 0.0) {
+        const double hi = b <= 0.0 ? prior_log_ndtr(b) : prior_log_ndtr(-a);
+        const double lo = b <= 0.0 ? prior_log_ndtr(a) : prior_log_ndtr(-b);
+        return hi + log1p(-exp(lo - hi));
+    }
+    return log1p(-0.5 * erfc(-a * 0.70710678118654752440) - 0.5 * erfc(b * 0.70710678118654752440));
+}
+
+// Would scipy.stats accept these parameters?  (`_argcheck`, scale > 0; randint: integer low < high.)
+// p = the family's scipy arguments in order (include/psfmc_hip.h PSFMC_PRIOR_*).  Locations, scales and
+// shapes must also be finite, and truncnorm's bounds not NaN (an infinite bound is allowed).
+__host__ inline bool prior_params_ok(int fam, const double* p) {
+    auto fin = [](double v) { return std::isfinite(v); };
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    switch (fam) {
+        case PRIOR_HOST: return true;
+        case PRIOR_UNIFORM: case PRIOR_NORMAL: return fin(p[0]) && pos(p[1]);
+        case PRIOR_WEIBULL_MIN: case PRIOR_WEIBULL_MAX: case PRIOR_LOGNORM: case PRIOR_T: case PRIOR_INVGAMMA:
+            return pos(p[0]) && fin(p[1]) && pos(p[2]);
+        case PRIOR_RANDINT:
+            return fin(p[0]) && fin(p[1]) && p[0] == rint(p[0]) && p[1] == rint(p[1]) && p[0] < p[1];
+        case PRIOR_TRUNCNORM:
+            return !std::isnan(p[0]) && !std::isnan(p[1]) && p[0] < p[1] && fin(p[2]) && pos(p[3]);
+        case PRIOR_HALFNORM: case PRIOR_EXPON: case PRIOR_LAPLACE: case PRIOR_CAUCHY: case PRIOR_HALFCAUCHY:
+        case PRIOR_LOGISTIC:
+            return fin(p[0]) && pos(p[1]);
+        case PRIOR_BETA: return pos(p[0]) && pos(p[1]) && fin(p[2]) && pos(p[3]);
+        case PRIOR_RECIPROCAL: return pos(p[0]) && fin(p[1]) && p[1] > p[0] && fin(p[2]) && pos(p[3]);
+        default: return false;
+    }
+}
+
+// The per-column table entry {pa, pb, pc, pd, pk} of one prior (p as for prior_params_ok, already
+// checked).  Families 1-4 keep psfmc_set_layout's form.  Families 5.. hold pa = loc, pb = scale, two
+// shape terms pc, pd and in pk every x-independent term, -log(scale) included, so that the device
+// works out y = (x - loc) / scale and at most a log, a log1p and one exp per column.
+__host__ inline void prior_prepare(int fam, const double* p, double* out) {
+    const double log_pi = 1.14472988584940017414, half_log_2pi = 0.91893853320467274178;
+    double pa = 0.0, pb = 0.0, pc = 0.0, pd = 0.0, pk = 0.0;
+    switch (fam) {
+        case PRIOR_UNIFORM: case PRIOR_NORMAL: case PRIOR_WEIBULL_MIN: case PRIOR_RANDINT:
+            pa = p[0]; pb = p[1]; pc = fam == PRIOR_WEIBULL_MIN ? p[2] : 0.0;
+            pk = prior_log_norm(fam, pa, pb, pc);
+            break;
+        case PRIOR_TRUNCNORM:                      // pc, pd = the bounds a, b
+            pa = p[2]; pb = p[3]; pc = p[0]; pd = p[1];
+            pk = -half_log_2pi - prior_log_gauss_mass(p[0], p[1]) - log(pb);
+            break;
+        case PRIOR_LOGNORM:                        // pd = 2 s^2
+            pa = p[1]; pb = p[2]; pc = p[0]; pd = 2.0 * (p[0] * p[0]);
+            pk = -log(p[0] * 2.50662827463100050242) - log(pb);
+            break;
+        case PRIOR_HALFNORM: case PRIOR_EXPON: case PRIOR_LAPLACE: case PRIOR_CAUCHY: case PRIOR_HALFCAUCHY:
+        case PRIOR_LOGISTIC:
+            pa = p[0]; pb = p[1];
+            pk = -log(pb);
+            if (fam == PRIOR_HALFNORM) pk = 0.5 * log(2.0 / M_PI) - log(pb);
+            if (fam == PRIOR_CAUCHY) pk = -log_pi - log(pb);
+            if (fam == PRIOR_HALFCAUCHY) pk = log(2.0 / M_PI) - log(pb);
+            break;
+        case PRIOR_T: {                            // pc = df, pd = (df + 1) / 2
+            const long double h = 0.5L * (long double)p[0];
+            pa = p[1]; pb = p[2]; pc = p[0]; pd = (p[0] + 1.0) / 2.0;
+            pk = (double)(lgammal(h + 0.5L) - lgammal(h)) - 0.5 * (log(p[0]) + log_pi) - log(pb);
+            break;
+        }
+        case PRIOR_BETA: {                         // pc = a - 1, pd = b - 1
+            const long double a = p[0], b = p[1];
+            pa = p[2]; pb = p[3]; pc = p[0] - 1.0; pd = p[1] - 1.0;
+            pk = -(double)(lgammal(a) + lgammal(b) - lgammal(a + b)) - log(pb);
+            break;
+        }
+        case PRIOR_RECIPROCAL:                     // pc, pd = the bounds a, b
+            pa = p[2]; pb = p[3]; pc = p[0]; pd = p[1];
+            pk = -log(log(p[1]) - log(p[0])) - log(pb);
+            break;
+        case PRIOR_WEIBULL_MAX:                    // pc = c, pd = c - 1
+            pa = p[1]; pb = p[2]; pc = p[0]; pd = p[0] - 1.0;
+            pk = log(p[0]) - log(pb);
+            break;
+        case PRIOR_INVGAMMA:                       // pc = a + 1
+            pa = p[1]; pb = p[2]; pc = p[0] + 1.0;
+            pk = -(double)lgammal((long double)p[0]) - log(pb);
+            break;
+        default: break;
+    }
+    out[0] = pa; out[1] = pb; out[2] = pc; out[3] = pd; out[4] = pk;
+}
+
+// log-density of one column: families 1-4 with set_layout's parameters here, families 5.. in
+// prior_logp_more as scipy's `_logpdf(y) - log(scale)` in scipy's own form (its lazywhere branches and
+// support masks: closed, or open for lognorm and invgamma), so that the edges of the support give scipy's
+// value.  NaN in, NaN out.
 __device__ inline double prior_logp(int fam, double x, double a, double b, double c, double k) {
     const double ninf = -INFINITY;
     switch (fam) {
@@ -144,6 +258,65 @@ __device__ inline double prior_logp(int fam, double x, double a, double b, doubl
         case PRIOR_RANDINT: {                                 // low a, high b (exclusive); x already rounded
             return (x >= a && x <= b - 1.0) ? k : ninf;
         }
+        default:
+            return 0.0;
+    }
+}
+
+// families 5..: loc a, scale b.  `fam` is the same in every lane (one column at a time): the dispatch is
+// scalar, and families 1-4 never reach it (theta_log_prior)
+__device__ inline double prior_logp_more(int fam, double x, double a, double b, double c, double d, double k) {
+    const double ninf = -INFINITY;
+    const double y = (x - a) / b;
+    switch (__builtin_amdgcn_readfirstlane(fam)) {
+        case PRIOR_TRUNCNORM:                                 // [c, d]
+            if (!(y >= c && y <= d)) return y == y ? ninf : y;
+            return -0.5 * y * y + k;
+        case PRIOR_LOGNORM: {                                 // (0, inf); d = 2 s^2
+            if (!(y > 0.0 && y < INFINITY)) return y == y ? ninf : y;
+            const double l = log(y);
+            return -(l * l) / d - l + k;
+        }
+        case PRIOR_HALFNORM:                                  // [0, inf]
+            if (!(y >= 0.0)) return y == y ? ninf : y;
+            return -0.5 * y * y + k;
+        case PRIOR_EXPON:
+            if (!(y >= 0.0)) return y == y ? ninf : y;
+            return -y + k;
+        case PRIOR_LAPLACE:                                   // scipy: log(pdf), which underflows past |y| ~ 745
+            return log(0.5 * exp(-fabs(y))) + k;
+        case PRIOR_CAUCHY: {
+            const double ay = fabs(y);
+            if (ay < 1.0) return -log1p(ay * ay) + k;
+            const double r = 1.0 / ay;
+            return -(2.0 * log(ay) + log1p(r * r)) + k;
+        }
+        case PRIOR_HALFCAUCHY:
+            if (!(y >= 0.0)) return y == y ? ninf : y;
+            return -log1p(y * y) + k;
+        case PRIOR_LOGISTIC: {
+            const double t = -fabs(y);
+            return t - 2.0 * log1p(exp(t)) + k;
+        }
+        case PRIOR_T:                                         // c = df, d = (df + 1) / 2
+            return -d * log1p(y * y / c) + k;
+        case PRIOR_BETA: {                                    // [0, 1]; c = a - 1, d = b - 1 (xlogy, xlog1py)
+            if (!(y >= 0.0 && y <= 1.0)) return y == y ? ninf : y;
+            const double t1 = d == 0.0 ? 0.0 : d * log1p(-y);
+            const double t2 = c == 0.0 ? 0.0 : c * log(y);
+            return (t1 + t2) + k;
+        }
+        case PRIOR_RECIPROCAL:                                // [c, d]
+            if (!(y >= c && y <= d)) return y == y ? ninf : y;
+            return -log(y) + k;
+        case PRIOR_WEIBULL_MAX: {                             // [-inf, 0]; c = shape, d = c - 1
+            if (!(y <= 0.0)) return y == y ? ninf : y;
+            const double u = -y;
+            return (k + (d == 0.0 ? 0.0 : d * log(u))) - pow(u, c);
+        }
+        case PRIOR_INVGAMMA:                                  // (0, inf); c = a + 1
+            if (!(y > 0.0 && y < INFINITY)) return y == y ? ninf : y;
+            return (-c * log(y) - 1.0 / y) + k;
         default:
             return 0.0;
     }
@@ -171,7 +344,8 @@ __device__ inline double theta_log_prior(const ThetaLayout& L, const double* __r
         const int fam = L.family[p];
         if (fam == PRIOR_HOST) continue;
         const double x = fam == PRIOR_RANDINT ? rint(theta[p]) : theta[p];
-        lp += prior_logp(fam, x, L.pa[p], L.pb[p], L.pc[p], L.pk[p]);
+        if (fam <= PRIOR_RANDINT) lp += prior_logp(fam, x, L.pa[p], L.pb[p], L.pc[p], L.pk[p]);
+        else lp += prior_logp_more(fam, x, L.pa[p], L.pb[p], L.pc[p], L.pd[p], L.pk[p]);
     }
     // Sersic axis-ratio constraint (Sersic.py:41-45)
     for (int k = 0; k < L.n_sersic; ++k) {
@@ -278,7 +452,7 @@ __host__ inline int theta_task_waves(int n_ps, int n_sersic) {
 __host__ inline size_t theta_prep_lds_bytes(int n_sky, int n_ps, int n_sersic, int n_params) {
     const size_t ns = n_slots(n_sky, n_ps, n_sersic);
     const size_t n_int = ((ns + n_ps + n_sersic + n_params + 1) / 2) * 2;           // 8-byte multiple
-    const size_t n_dbl = ns + 4 * (size_t)n_params;
+    const size_t n_dbl = ns + 5 * (size_t)n_params;
     return n_int * sizeof(int) +
            (n_dbl + (size_t)kThetaThreads * (n_params + row_len(n_ps, n_sersic) + n_ps + 3 * n_sersic)) *
                sizeof(double);
@@ -312,7 +486,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
     }
     const int ns = n_slots(G.n_sky, G.n_ps, G.n_sersic);
     const int n_int = ((ns + G.n_ps + G.n_sersic + G.n_params + 1) / 2) * 2;
-    const int n_dbl = ns + 4 * G.n_params;
+    const int n_dbl = ns + 5 * G.n_params;
     const int rlen = row_len(G.n_ps, G.n_sersic);
     const int P = G.n_params;
     int* li = reinterpret_cast<int*>(lds_raw);
@@ -321,7 +495,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
     double* row_tile = th_tile + (size_t)kThetaThreads * P;
     double* peak_tile = row_tile + (size_t)kThetaThreads * rlen;       // [component][walker]
     const int tid = threadIdx.y * kThetaThreads + threadIdx.x, nthr = kThetaThreads * blockDim.y;
-    // The four int tables and the four double tables are contiguous in the blob.  The layout
+    // The four int tables and the six double tables are contiguous in the blob.  The layout
     // tables and the parameter tile are independent: every thread first ISSUES its (first) load
     // of each, then stores them to LDS -- one memory round trip instead of three in a row (the
     // kernel is a chain of latencies: 16 us for a 128-walker half-step whatever the batch).
@@ -397,7 +571,8 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
     ThetaLayout L = G;
     L.slot_col = li; L.ps_method = li + ns; L.sersic_deg = li + ns + G.n_ps;
     L.family = li + ns + G.n_ps + G.n_sersic;
-    L.slot_const = ld; L.pa = ld + ns; L.pb = ld + ns + P; L.pc = ld + ns + 2 * P; L.pk = ld + ns + 3 * P;
+    L.slot_const = ld; L.pa = ld + ns; L.pb = ld + ns + P; L.pc = ld + ns + 2 * P; L.pd = ld + ns + 3 * P;
+    L.pk = ld + ns + 4 * P;
     const int lw = threadIdx.x, w = w0 + lw;
     const bool active = w < W;
     const double* th = th_tile + (size_t)lw * P;

@@ -167,6 +167,8 @@ def load_library():
     lib.psfmc_set_layout.restype = ci
     lib.psfmc_set_layout.argtypes = [vp, ci, ci, ip, _c_double_p, ip, ip, cd, ip, _c_double_p,
                                      _c_double_p, _c_double_p]
+    lib.psfmc_set_priors.restype = ci
+    lib.psfmc_set_priors.argtypes = [vp, ci, ci, ip, _c_double_p]
     lib.psfmc_eval_theta.restype = ci
     lib.psfmc_eval_theta.argtypes = [vp, ci, _c_double_p, _c_double_p, _c_double_p]
     lib.psfmc_eval_theta_device.restype = ci
@@ -232,6 +234,8 @@ def load_library():
     lib.psfmc_group_set_layout.restype = ci
     lib.psfmc_group_set_layout.argtypes = [vp, ci, ci, ip, _c_double_p, ip, ip, cd, ip, _c_double_p,
                                            _c_double_p, _c_double_p]
+    lib.psfmc_group_set_priors.restype = ci
+    lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
     lib.psfmc_group_eval_batch.argtypes = [vp, ci, _c_double_p, _c_u8_p, _c_double_p]
     lib.psfmc_group_eval_theta.restype = ci
@@ -250,6 +254,21 @@ def load_library():
 
 def _dp(arr):
     return arr.ctypes.data_as(_c_double_p)
+
+
+PRIOR_NPAR = 4          # include/psfmc_hip.h PSFMC_PRIOR_NPAR
+
+
+def _prior_table(family, params):
+    """(family [P] int32, params [P, PRIOR_NPAR] float64) for psfmc_set_priors; `params` may have fewer
+    columns (the rest is 0)."""
+    family = np.ascontiguousarray(family, dtype=np.int32).ravel()
+    params = np.asarray(params, dtype=np.float64).reshape(len(family), -1)
+    if params.shape[1] > PRIOR_NPAR:
+        raise ValueError('at most {} parameters per prior'.format(PRIOR_NPAR))
+    table = np.zeros((len(family), PRIOR_NPAR))
+    table[:, :params.shape[1]] = params
+    return family, table, family.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(table)
 
 
 def _f64(arr):
@@ -432,6 +451,12 @@ class Context(object):
             self._ctx, int(n_sky), int(n_params), ipt(slot_col), _dp(slot_const), ipt(ps_method),
             ipt(sersic_degrees), float(mag_zeropoint), ipt(family), _dp(p0), _dp(p1), _dp(p2)))
         self.n_params = int(n_params)
+
+    def set_priors(self, family, params):
+        """Replace the prior table of the layout (after `set_layout`): family [P] codes of
+        include/psfmc_hip.h (0 = host), params [P, <= 4] their scipy.stats arguments in order."""
+        fam, tab, fp, tp = _prior_table(family, params)
+        self._check(self._lib.psfmc_set_priors(self._ctx, 0, len(fam), fp, tp))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -665,6 +690,10 @@ class FieldSetContext(object):
                 if owner.n_params not in (None, int(n_params)):
                     raise ValueError('every field must have the same number of free parameters')
                 owner.n_params = int(n_params)
+
+            def set_priors(self, family, params):
+                fam, tab, fp, tp = _prior_table(family, params)
+                owner._check(owner._lib.psfmc_set_priors(owner._ctx, int(field), len(fam), fp, tp))
         return _Proxy()
 
     @staticmethod
@@ -902,6 +931,11 @@ class ContextGroup(object):
             self._grp, int(n_sky), int(n_params), ipt(slot_col), _dp(slot_const), ipt(ps_method),
             ipt(sersic_degrees), float(mag_zeropoint), ipt(family), _dp(p0), _dp(p1), _dp(p2)))
         self.n_params = int(n_params)
+
+    def set_priors(self, family, params):
+        """`Context.set_priors` on every device of the group."""
+        fam, tab, fp, tp = _prior_table(family, params)
+        self._check(self._lib.psfmc_group_set_priors(self._grp, len(fam), fp, tp))
 
     def loglike(self, rows, skip=None):
         rows = _f64(rows)

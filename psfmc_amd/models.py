@@ -23,9 +23,46 @@ from . import engine
 IMAGE_KINDS = engine.Context.IMAGE_KINDS
 
 
+# scipy.stats name -> (include/psfmc_hip.h PSFMC_PRIOR_* code, number of shape arguments); the
+# device takes the shapes, then loc and scale (randint: low and high with the location folded in)
+_DEVICE_FAMILIES = {
+    'uniform': (1, 0), 'norm': (2, 0), 'weibull_min': (3, 1), 'randint': (4, 2),
+    'truncnorm': (5, 2), 'lognorm': (6, 1), 'halfnorm': (7, 0), 'expon': (8, 0), 'laplace': (9, 0),
+    'cauchy': (10, 0), 'halfcauchy': (11, 0), 'logistic': (12, 0), 't': (13, 1), 'beta': (14, 2),
+    'reciprocal': (15, 2), 'loguniform': (15, 2), 'weibull_max': (16, 1), 'invgamma': (17, 1),
+}
+_FIRST_NEW_FAMILY = 5           # psfmc_set_layout takes families 0-4; the rest go through psfmc_set_priors
+
+
+def _device_params_ok(code, params):
+    """What psfmc_set_priors accepts (psfmc_theta.h prior_params_ok): the parameters scipy accepts, finite
+    (truncnorm's bounds may be infinite), for every element."""
+    p = [np.asarray(v, dtype=np.float64) for v in params]
+    fin = lambda v: np.isfinite(v)
+    pos = lambda v: np.isfinite(v) & (v > 0)
+    if code in (1, 2):
+        ok = fin(p[0]) & pos(p[1])
+    elif code in (3, 6, 13, 16, 17):
+        ok = pos(p[0]) & fin(p[1]) & pos(p[2])
+    elif code == 4:
+        ok = fin(p[0]) & fin(p[1]) & (p[0] == np.rint(p[0])) & (p[1] == np.rint(p[1])) & (p[0] < p[1])
+    elif code == 5:
+        ok = (p[0] < p[1]) & fin(p[2]) & pos(p[3])
+    elif code in (7, 8, 9, 10, 11, 12):
+        ok = fin(p[0]) & pos(p[1])
+    elif code == 14:
+        ok = pos(p[0]) & pos(p[1]) & fin(p[2]) & pos(p[3])
+    elif code == 15:
+        ok = pos(p[0]) & fin(p[1]) & (p[1] > p[0]) & fin(p[2]) & pos(p[3])
+    else:
+        return False
+    return bool(np.all(ok))
+
+
 def _device_prior(prior, width):
-    """(family, p0, p1, p2) if the library evaluates this prior itself
-    (include/psfmc_hip.h PSFMC_PRIOR_*), else None."""
+    """(family, p0, p1, p2, p3) if the library evaluates this prior itself
+    (include/psfmc_hip.h PSFMC_PRIOR_*: the scipy.stats arguments in order, each a scalar or one value
+    per element of a vector parameter), else None: an unknown family, or parameters scipy rejects."""
     rv = getattr(prior, 'rv_frozen', None)
     if rv is None:
         return None
@@ -35,17 +72,21 @@ def _device_prior(prior, width):
         return None
     name = rv.dist.name
     ok_size = all(np.size(v) in (1, width) for v in (loc, scale) + tuple(shapes))
-    if not ok_size:
+    if not ok_size or name not in _DEVICE_FAMILIES:
         return None
-    if name == 'uniform':
-        return 1, loc, scale, 0.0
-    if name == 'norm':
-        return 2, loc, scale, 0.0
-    if name == 'weibull_min':
-        return 3, shapes[0], loc, scale
-    if name == 'randint' and np.all(np.asarray(loc) == 0):
-        return 4, shapes[0], shapes[1], 0.0
-    return None
+    code, n_shapes = _DEVICE_FAMILIES[name]
+    if len(shapes) != n_shapes:
+        return None
+    if code == 4:                   # randint: an integer location moves the bounds
+        loc = np.asarray(loc, dtype=np.float64)
+        if not np.all(np.isfinite(loc) & (loc == np.rint(loc))):
+            return None
+        params = (shapes[0] + loc, shapes[1] + loc)
+    else:
+        params = tuple(shapes) + (loc, scale)
+    if not _device_params_ok(code, params):
+        return None
+    return (code,) + tuple(params) + (0.0,) * (4 - len(params))
 
 
 class MultiComponentModel(object):
@@ -142,10 +183,11 @@ class MultiComponentModel(object):
     def _register_layout(self, eng):
         """Hand the parameter layout and the priors to the library so that raw
         emcee vectors can be evaluated without host arithmetic.  Priors of
-        families the library does not know stay on the host (`_host_priors`)."""
+        families the library does not know, and parameters scipy rejects, stay on the host
+        (`_host_priors`)."""
         col_of = {}                                   # (component id, attr, element) -> column
         family = np.zeros(self.num_params, dtype=np.int32)
-        p0, p1, p2 = (np.zeros(self.num_params) for _ in range(3))
+        params = np.zeros((self.num_params, engine.PRIOR_NPAR))
         self._host_priors = []                        # (prior, column slice)
         for comp, span in zip(self.components, self._spans):
             pos = span.start
@@ -158,8 +200,7 @@ class MultiComponentModel(object):
                     col_of[(id(comp), name, j)] = pos + j
                     if desc is not None:
                         family[pos + j] = desc[0]
-                        p0[pos + j], p1[pos + j], p2[pos + j] = (np.ravel(v)[j if np.size(v) > 1 else 0]
-                                                                 for v in desc[1:])
+                        params[pos + j] = [np.ravel(v)[j if np.size(v) > 1 else 0] for v in desc[1:]]
                 pos += width
         slot_col, slot_const = [], []
 
@@ -180,10 +221,17 @@ class MultiComponentModel(object):
                 add(c, name)
             add(c, 'xy', 0); add(c, 'xy', 1)
         add(self.config.psf_selector, 'psf_index')
+        # families 0-4 as psfmc_set_layout takes them, the newer ones as host columns there; the full
+        # table follows only where a newer family exists (a model of families 1-4 makes the same calls
+        # as before they did)
+        new = family >= _FIRST_NEW_FAMILY
+        base = np.where(new[:, None], 0.0, params)
         eng.set_layout(len(self._sky), self.num_params, slot_col, slot_const,
                        [SHIFT_METHODS[c.shift_method] for c in self._ps],
                        [int(bool(c.angle_degrees)) for c in self._sersic],
-                       self.config.mag_zeropoint, family, p0, p1, p2)
+                       self.config.mag_zeropoint, np.where(new, 0, family), base[:, 0], base[:, 1], base[:, 2])
+        if new.any():
+            eng.set_priors(family, params)
 
     def device_group(self, devices, max_walkers=None):
         """A `engine.ContextGroup`: this model's field on several GPUs driven by this one
