@@ -16,7 +16,10 @@ ranks as a CHILD process (before this process touches the GPU) and relays its ou
 the driver's own `torch.distributed.run ... bench.py --gpus N` form runs the ranks
 directly.  One process per GPU; weak scaling (per-GPU batch fixed).
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the headline (`value`, `ms_per_step`, ...) with `roofline` = the whole step by measured bytes (the committed PMC
+table x evals/s, no run of its own); nothing else is measured or checked.  `--full` adds, as separate runs after
+the timed steps,
   roofline       the dominant kernel (k_cols): its algorithmic bytes per launch (read +
                  write of the transposed half-spectra, = the column pass's share of SURVEY
                  section 8(d)'s per-evaluation figure) over its live HIP-event-timed launch
@@ -26,7 +29,11 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
                  `algorithmic_equiv_GBps` is SURVEY section 8(d)'s 96 N^2 + 64 N bytes x
                  evals/s -- an equivalent rate of an unfused design, not a fraction of peak
   cpu_baseline   the numpy oracle (a port of the reference algorithm) timed on this host,
-                 one walker per call like the reference
+                 one walker per call like the reference; check_vs_cpu_rel: the timed batch against it
+  side figures   likelihood from rows, the Python entry point, small ensembles, the default-ensemble sampler,
+                 the sweep and VALU ceilings, the storage_f32 option, the example model
+  checks         (N > 1) every rank's gathered block against its own evaluation; (--fields > 1) the shared
+                 batch against every field's own context, bit for bit
   configs        (N = 1) the other single-GPU workloads of BASELINE.json, each timed for >= 1 s after the
                  headline: config 3 (512^2, 2 Sersic, 1024 walkers), config 4's per-GPU share (1024^2, 4
                  Sersic, 256 walkers), config 5's share (8 fields x 256 walkers: evaluations and stretch-move
@@ -656,6 +663,7 @@ def many_fields(args, torch, dist, world, rank, local, dev, gloo):
     agree = None
     if merged is not None:
         finite = int(torch.isfinite(all_out).sum().item())
+    if merged is not None and args.full:
         # the shared batch against each field's own context, bit for bit
         for eng, t, o in zip(engs, thetas, outs):
             eng.logpost_theta_device(args.walkers, t.data_ptr(), 0, o.data_ptr(), None)
@@ -951,7 +959,9 @@ def multi_gpu_extras(args, torch, dist, world, rank, local, dev, gloo):
     return out if rank == 0 else None
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  Without --full every side figure and check is switched off (the --no-* options all
+    set): a plain run sets up, warms up, times the steps, dumps and prints the headline line."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -999,9 +1009,22 @@ def main():
                     help='after the timed steps, write the log-posteriors of the last step (one row per resident '
                          'set of walkers, or per field) as DIR/logpost_rejected.npy (1 where -inf) and '
                          'DIR/logpost.npy (the other values, float64); see dump_outputs')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline: the per-kernel profile and its '
+                         'roofline, the side figures, the other single-GPU configs, the sharded paths, the example '
+                         'model, the CPU baselines and the checks against the CPU oracle and between ranks or '
+                         'contexts (the --no-* options trim it); without it the run times the headline steps and '
+                         'nothing else')
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        args.no_cpu = args.no_example = args.no_extras = args.no_configs = args.no_multi = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.cpu_worker >= 0:
         return cpu_worker(args)
     env_world = os.environ.get('WORLD_SIZE')
@@ -1113,7 +1136,7 @@ def main():
         last = out if sharded is None else torch.stack([gathered[b] for b in range(n_sets)])
         dump_outputs(args.dump_outputs, {'logpost': last.cpu().numpy()})
     sharded_check = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank holds every block: this rank's own block evaluated alone must be what the gather put in
         # its place, and (rank 0) 64 walkers of the LAST rank's block evaluated here must equal what that rank sent
         # (per-walker results do not depend on the batch: same bits)
@@ -1138,7 +1161,7 @@ def main():
         n_finite = int(sum(int(torch.isfinite(g).sum().item()) for g in gathered.values()))
 
     kernels = []
-    if rank == 0 and args.backend == 'fused':
+    if rank == 0 and args.backend == 'fused' and args.full:
         kernels = kernel_profile(eng, args, one_batch, torch, dev, max(2, min(args.steps, 5)))
     line = None
     if rank == 0:

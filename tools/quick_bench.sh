@@ -7,7 +7,7 @@ CONFIGS=${CONFIGS:-"256:1:4096 512:2:1024 1024:4:256"}
 mkdir -p $R/gpurun_out
 for cfg in $CONFIGS; do
   IFS=: read size sersic walkers <<< "$cfg"
-  python3 $R/bench.py --size $size --sersic $sersic --walkers $walkers --no-cpu --no-example --steps 10 --warmup 2 "$@" 2>/dev/null | python3 -c "
+  python3 $R/bench.py --size $size --sersic $sersic --walkers $walkers --full --no-cpu --no-example --steps 10 --warmup 2 "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 n=d['config']['image']; t4=4*2*(n//2+1)*n*16
