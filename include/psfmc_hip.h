@@ -207,14 +207,25 @@ int psfmc_eval_theta_device(psfmc_ctx* ctx, int W, const double* d_theta, const 
                             double* d_lnprob, void* stream);
 
 /*
- * Several observed fields of ONE shape in one context (fused back end).  The reference fits one
- * field per process (psfMC/fitting.py:13-113 builds one MultiComponentModel per model file); a
- * survey of many small fields -- BASELINE config 5: independent 256 x 256 fields x 256 walkers each
- * -- then makes many small batches, each paying the fixed cost of a call.  Here the fields' walkers
- * share the batches: every walker's record carries (field * n_psf + PSF) as its kernel-spectrum index,
- * the row kernels pick the field's pixels from it, and 8 x 256 walkers run at the rate of one 2048-walker
- * ensemble.
- *   sci / obs_var / bad_px  [n_fields][ny][nx];  psf / psf_var  [n_fields][n_psf][psf_ny][psf_nx]
+ * Several observed fields in one context (fused back end).  The reference fits one field per process
+ * (psfMC/fitting.py:13-113 builds one MultiComponentModel per model file); a survey of many small fields --
+ * BASELINE config 5: independent 256 x 256 fields x 256 walkers each -- then makes many small batches, each
+ * paying the fixed cost of a call.  Here the fields' walkers share the batches: every walker's record carries
+ * (field * n_psf + PSF) as its kernel-spectrum index, the row kernels pick the field's pixels (and, embedded,
+ * its image's place in the transform) from it, and 8 x 256 walkers run at the rate of one 2048-walker ensemble.
+ * psfmc_ctx_create_fields_shaped: field f is an image of ny[f] x nx[f] pixels (even sides) with n_psf[f] PSFs
+ *   of psf_ny[f] x psf_nx[f] (no larger than the image); n_psf[f] is the same for every field.
+ *   sci / obs_var / bad_px  the fields' [ny[f]][nx[f]] arrays concatenated in field order;
+ *   psf / psf_var           the fields' [n_psf][psf_ny[f]][psf_nx[f]] arrays concatenated in field order.
+ *   The fields share ONE transform shape: per axis the fields' common side if it is built, else the cheapest
+ *   built side (<= 2048) that every field either has or holds with its wrap-around margin (side + PSF side - 1).
+ *   EVERY FIELD PAYS FOR THAT TRANSFORM: a 96 x 96 field in a set with a 256 x 256 one costs what a 256 x 256
+ *   walker costs.  Grouping fields of very different sizes into separate sets is the caller's choice.
+ *   get_option "transform_ny" / "transform_nx" report the shared transform, psfmc_field_shape a field's own
+ *   image sides -- the shape of every pixel array of that field at this ABI (psfmc_eval_images_field,
+ *   psfmc_get_accumulated_field).  Arguments are checked (naming the field) before any device is touched.
+ * psfmc_ctx_create_fields: the same with every field of one shape: sci / obs_var / bad_px [n_fields][ny][nx],
+ *   psf / psf_var [n_fields][n_psf][psf_ny][psf_nx].
  *   the same component counts (n_ps, n_sersic) and parameter layout structure for every field;
  *   psfmc_set_layout (= field 0) first, then psfmc_set_layout_field for fields 1..: own constants, priors
  *   psfmc_eval_theta[_device]_fields: segment i = seg_count[i] consecutive walkers of field seg_field[i];
@@ -231,9 +242,14 @@ int psfmc_eval_theta_device(psfmc_ctx* ctx, int W, const double* d_theta, const 
  * psfmc_reset_accumulated clears every field's sums, psfmc_reset_accumulated_field one field's.  The raw-sum exchange for sharded ranks
  * (psfmc_get/set_accumulated_sums) and the half-step API (psfmc_stretch_open ...) serve one-field contexts.
  */
+int psfmc_ctx_create_fields_shaped(psfmc_ctx** out, int device, int n_fields, const int* ny, const int* nx,
+                                   const double* sci, const double* obs_var, const uint8_t* bad_px, const int* n_psf,
+                                   const int* psf_ny, const int* psf_nx, const double* psf, const double* psf_var,
+                                   int n_ps, int n_sersic, int max_walkers);
 int psfmc_ctx_create_fields(psfmc_ctx** out, int device, int ny, int nx, int n_fields, const double* sci,
                             const double* obs_var, const uint8_t* bad_px, int n_psf, int psf_ny, int psf_nx,
                             const double* psf, const double* psf_var, int n_ps, int n_sersic, int max_walkers);
+int psfmc_field_shape(psfmc_ctx* ctx, int field, int* ny, int* nx);
 int psfmc_set_layout_field(psfmc_ctx* ctx, int field, int n_sky, int n_params, const int* slot_col,
                            const double* slot_const, const int* ps_method, const int* sersic_degrees,
                            double mag_zeropoint, const int* family, const double* p0, const double* p1,

@@ -460,11 +460,19 @@ __device__ __forceinline__ double fast_exp2_poly(double r) {
 // length L (utils.py:25-32) on the pixels [a, a + L), which are the only ones the likelihood looks at
 // (overlap-save: every output there only reaches back over pixels that hold what the periodic image
 // holds).  a = Pk - 1 - c, c = the kernel's origin inside the padded PSF (psfmc_hip.hip embed_axis).
-// l = 0: no embedding on this axis.
+// An axis that is not embedded has l = e = M, a = 0 (the identity).
 struct WrapDesc {
     int lx, ax, ex;     // image side, margin before the image, extent of the filled pixels (lx + Pk - 1)
     int ly, ay, ey;
 };
+// The rasterising kernels of an embedded context read the descriptor of the walker's field from a device table
+// with one entry per kernel spectrum (field * PSFs per field + PSF: the index the walker's record carries), so
+// that the fields of one context may differ in image and PSF size.  The index is made provably wave-uniform:
+// the descriptor then arrives through scalar loads (no waterfall loop).  Only a record that is not skipped
+// holds a valid index.
+__device__ __forceinline__ WrapDesc walker_wrap(const WrapDesc* __restrict__ tab, const double* __restrict__ wprep) {
+    return tab[__builtin_amdgcn_readfirstlane((int)wprep[kPrepPsfIdx])];
+}
 // the image's own [ly][lx] window at (ay, ax) of a transform-shaped [..][nx] pixel array (the whole of it
 // unless the image is embedded)
 struct ImgWindow { int nx, ly, lx, ay, ax; };

@@ -273,13 +273,13 @@ __global__ void k_pack_field(const double* __restrict__ sci, const double* __res
 // raw_out (optional): [n][ny][nx] copy of the raw model (psfmc_eval_images)
 // ---------------------------------------------------------------------------
 // WRAP: the image is embedded in a larger transform size (psfmc_device.h WrapDesc); ny, NX are the
-// transform's sides
+// transform's sides, wrap_tab the context's descriptors per kernel spectrum (walker_wrap)
 template <int NX, bool FROM_IMAGE, typename TS = cd, bool FAST = FftShape<NX>::kPlain, bool WRAP = false>
 __global__ void __launch_bounds__((row_threads<NX, FAST>()), (fused_row_min_waves<NX, false, WRAP>()))
 k_rows_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
            const cd* __restrict__ twx, TS* __restrict__ Tbuf, int n_ps, int n_sersic, int ny,
            int ps_only, const double* __restrict__ img, const double* __restrict__ img_scale,
-           double* __restrict__ raw_out, WrapDesc wr, int pow_mode) {
+           double* __restrict__ raw_out, const WrapDesc* __restrict__ wrap_tab, int pow_mode) {
     using S = FftShape<NX>;
     constexpr int P = S::P, T = S::T, R = S::R, RG = row_group<NX>();
     constexpr int NXH = NX / 2 + 1;
@@ -325,6 +325,8 @@ k_rows_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
         const double* wprep = prep + (size_t)w * prep_len(n_ps, n_sersic);   // wave-uniform
         const double mu = wprep[kPrepMu];
         if (skipped) return;                          // a skipped walker's record may hold anything
+        WrapDesc wr{0, 0, 0, 0, 0, 0};
+        if constexpr (WRAP) wr = walker_wrap(wrap_tab, wprep);      // (its field's; scalar loads)
         // the rasteriser's tables borrow the start of the wave's transform region (exchange area and
         // twiddle table), which is idle until the transform begins
         static_assert(fused_row_wave_lds_doubles<NX>() >= (pow_tabs_side(NX) ? (size_t)kRasterLdsDoubles : (size_t)kLogTabBytes / 8),
@@ -1520,7 +1522,7 @@ template <int NX, bool WRAP = false>
 __global__ void __launch_bounds__(64) k_raster_sums(const double* __restrict__ prep, int plen, int n_w, int group_size,
                                                     int n_ps, int n_sersic, int ny, int n_psf,
                                                     double* __restrict__ part, int per_field, int f0, int npf,
-                                                    WrapDesc wr) {
+                                                    const WrapDesc* __restrict__ wrap_tab) {
     using S = RasterShape<NX>;
     constexpr int T = S::T, RG = S::TPW;
     static_assert(S::P % raster_seg<S::P>() == 0, "segment");
@@ -1536,6 +1538,9 @@ __global__ void __launch_bounds__(64) k_raster_sums(const double* __restrict__ p
     const size_t Spx = (size_t)ny * NX;
     const int psf0 = per_field > 0 ? (f0 + w0 / per_field) * npf : 0;      // (wave-uniform)
     const int n_here = per_field > 0 ? npf : n_psf;
+    // the group's walkers and kernel spectra belong to ONE field (per_field > 0; or the only one): its descriptor
+    WrapDesc wr{0, 0, 0, 0, 0, 0};
+    if constexpr (WRAP) wr = wrap_tab[__builtin_amdgcn_readfirstlane(psf0)];
     for (int p = 0; p < n_here; ++p)
         raster_sums_all<NX, 0, WRAP>(prep, plen, w0, w1, psf0 + p, n_ps, n_sersic, t, row_on ? iy : 0, row_on, log_tab,
                                      part + ((size_t)g * n_here + p) * 3 * Spx, Spx, wr);

@@ -305,12 +305,13 @@ struct psfmc_ctx {
     int device = 0;
     int ny = 0, nx = 0, nxh = 0, S = 0, F = 0;
     int nyp = 0;                  // column length of the T layout: ny rounded up to whole row groups
-    // An image side the transforms are not built for is EMBEDDED in the next built side >= side + PSF side - 1
-    // (psfmc_device.h WrapDesc): ny, nx above are then the TRANSFORM's sides, ly, lx the image's; every pixel
-    // array that crosses the C ABI has the image's shape, every internal one the transform's.
-    bool embed = false;
-    int ly = 0, lx = 0;           // the image's own sides (= ny, nx without embedding)
-    WrapDesc wrap{0, 0, 0, 0, 0, 0};
+    // An image side the transforms are not built for is EMBEDDED in a built side >= side + PSF side - 1
+    // (psfmc_device.h WrapDesc): ny, nx above are then the TRANSFORM's sides, each field's wraps[f].ly, .lx its
+    // image's; every pixel array that crosses the C ABI has its field's image shape, every internal one the
+    // transform's.  The fields of one context may differ in image and PSF size: they share the transform.
+    bool embed = false;           // some field's descriptor is not the identity
+    std::vector<WrapDesc> wraps;  // [n_fields] each field's image inside the transform (identity: l = e = side, a = 0)
+    WrapDesc* d_wrap = nullptr;   // [n_psf] the same per kernel spectrum (embedded contexts: walker_wrap)
     int n_psf = 0, n_ps = 0, n_sersic = 0;   // n_psf: kernel spectra in all (fields x PSFs per field)
     int n_fields = 1, n_psf_field = 0;       // observed fields of this context (psfmc_ctx_create_fields), PSFs of each
     size_t field_len = 0;                    // packed pixels (FieldPx) of one field
@@ -396,6 +397,7 @@ struct psfmc_ctx {
     std::vector<char> more_has;
     size_t theta_lds = 0;
     ThetaLayout* d_field_layouts = nullptr;  // [n_fields] device copies of the layouts (launches that span several fields)
+    int* d_field_sides = nullptr;            // [n_fields][2] each field's image sides (ly, lx), for the same launches
     void* d_layout_blob = nullptr;           // one allocation behind the layout's pointers
     double *d_theta = nullptr, *d_extra = nullptr, *d_lnprior = nullptr;
     double* d_acc = nullptr;  // [n_fields][4][S] sums: raw, conv, model variance, PS-only conv
@@ -427,8 +429,13 @@ struct psfmc_ctx {
     } stretch;
 };
 
-// the image's window inside the transform-shaped pixel arrays (all of them unless the image is embedded)
-static ImgWindow img_window(const psfmc_ctx* c) { return ImgWindow{c->nx, c->ly, c->lx, c->wrap.ay, c->wrap.ax}; }
+// a field's image window inside the transform-shaped pixel arrays (all of them unless the image is embedded)
+static ImgWindow img_window(const psfmc_ctx* c, int field) {
+    const WrapDesc& w = c->wraps[field];
+    return ImgWindow{c->nx, w.ly, w.lx, w.ay, w.ax};
+}
+// pixels of a field's own image (the shape of its arrays at the C ABI)
+static size_t img_pixels(const psfmc_ctx* c, int field) { return (size_t)c->wraps[field].ly * c->wraps[field].lx; }
 
 // samples in the posterior-image sums of one field
 static long long& acc_n(psfmc_ctx* c, int field) { return field == 0 ? c->acc_count : c->acc_more[field - 1]; }
@@ -465,7 +472,7 @@ static int launch_rows3_fwd_kernel(psfmc_ctx* c, int n, const double* prep, cons
         return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
     hipLaunchKernelGGL((k_rows3_fwd<NX, FROM_IMAGE, WRAP>), dim3((c->ny + rows3_waves(NX) - 1) / rows3_waves(NX), n),
                        dim3(rows3_threads(NX)), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic, c->ny, ps_only, img,
-                       img_scale, raw_out, c->wrap, c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
+                       img_scale, raw_out, c->d_wrap, c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
     return PSFMC_OK;
 }
 template <int NX, bool FROM_IMAGE>
@@ -528,7 +535,7 @@ static int launch_rows_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const
         return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
     hipLaunchKernelGGL((k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP>), dim3((c->nblk + waves - 1) / waves, n),
                        dim3((row_threads<NX, FAST>())), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic,
-                       c->ny, ps_only, img, img_scale, raw_out, c->wrap,
+                       c->ny, ps_only, img, img_scale, raw_out, c->d_wrap,
                        c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
     return PSFMC_OK;
 }
@@ -781,12 +788,12 @@ static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int group
     if (c->embed) {
         hipLaunchKernelGGL((k_raster_sums<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
                            c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
-                           f0, c->n_psf_field, c->wrap);
+                           f0, c->n_psf_field, c->d_wrap);
         return PSFMC_OK;
     }
     hipLaunchKernelGGL((k_raster_sums<NX, false>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep, c->plen, n,
                        group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field, f0,
-                       c->n_psf_field, c->wrap);
+                       c->n_psf_field, c->d_wrap);
     return PSFMC_OK;
 }
 
@@ -1109,8 +1116,9 @@ extern "C" int psfmc_abi_version(void) { return 1; }
 
 extern "C" const char* psfmc_last_error(void) { return g_err.c_str(); }
 
+// psf / psf_var: every field's [n_psf_field][psf_ny[f]][psf_nx[f]] block, in field order
 static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, const uint8_t* bad_px,
-                    int psf_ny, int psf_nx, const double* psf, const double* psf_var) {
+                    const int* psf_ny, const int* psf_nx, const double* psf, const double* psf_var) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     for (int i = 0; i < psfmc_ctx::kMaxStreams; ++i) HIP_TRY(hipEventCreateWithFlags(&c->ev_stagger[i], hipEventDisableTiming));
@@ -1132,6 +1140,24 @@ static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, cons
     HIP_TRY(hipMalloc(&c->d_like, (size_t)c->max_walkers * sizeof(double)));
     HIP_TRY(hipMalloc(&c->d_skip, (size_t)c->max_walkers));
     HIP_TRY(hipMalloc(&c->d_partial, (size_t)c->max_walkers * c->nblk * sizeof(double)));
+    // the fields' image sides (multi-field record derivation) and, embedded, the descriptor of every kernel spectrum
+    std::vector<int> sides(2 * (size_t)c->n_fields);
+    std::vector<WrapDesc> wrap_tab(c->n_psf);
+    for (int f = 0; f < c->n_fields; ++f) {
+        sides[2 * f] = c->wraps[f].ly;
+        sides[2 * f + 1] = c->wraps[f].lx;
+        for (int p = 0; p < c->n_psf_field; ++p) wrap_tab[(size_t)f * c->n_psf_field + p] = c->wraps[f];
+    }
+    HIP_TRY(hipMalloc(&c->d_field_sides, sides.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(c->d_field_sides, sides.data(), sides.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (c->embed) {
+        HIP_TRY(hipMalloc(&c->d_wrap, wrap_tab.size() * sizeof(WrapDesc)));
+        HIP_TRY(hipMemcpy(c->d_wrap, wrap_tab.data(), wrap_tab.size() * sizeof(WrapDesc), hipMemcpyHostToDevice));
+    }
+    // where field f's PSF block starts in psf / psf_var
+    std::vector<size_t> psf_off(c->n_fields + 1, 0);
+    for (int f = 0; f < c->n_fields; ++f)
+        psf_off[f + 1] = psf_off[f] + (size_t)c->n_psf_field * psf_ny[f] * psf_nx[f];
 
     if (c->backend == PSFMC_BACKEND_FUSED) {
         const std::vector<cd> tx = twiddle_table(c->nx), ty = twiddle_table(c->ny);
@@ -1142,10 +1168,12 @@ static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, cons
         // rho[p] = 2^-round(log2(sum of the variance map)): brings the variance
         // channel of the packed complex transforms up to the model channel's scale
         std::vector<double> rho(c->n_psf, 1.0);
-        const size_t small_n = (size_t)psf_ny * psf_nx;
         for (int p = 0; p < c->n_psf; ++p) {
+            const int f = p / c->n_psf_field;
+            const size_t small_n = (size_t)psf_ny[f] * psf_nx[f];
+            const double* pv = psf_var + psf_off[f] + (size_t)(p % c->n_psf_field) * small_n;
             double tot = 0.0;
-            for (size_t i = 0; i < small_n; ++i) tot += psf_var[(size_t)p * small_n + i];
+            for (size_t i = 0; i < small_n; ++i) tot += pv[i];
             if (tot > 0.0 && std::isfinite(tot)) {
                 int e;
                 (void)frexp(tot, &e);
@@ -1169,12 +1197,15 @@ static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, cons
         }
     }
 
-    // centre-padded canvases, interleaved (psf0, var0, psf1, var1, ...)
-    const size_t small = (size_t)psf_ny * psf_nx;
-    std::vector<double> inter((size_t)2 * c->n_psf * small);
+    // centre-padded canvases, interleaved (psf0, var0, psf1, var1, ...), each field's at its own PSF shape
+    std::vector<double> inter(2 * psf_off[c->n_fields]);
     for (int p = 0; p < c->n_psf; ++p) {
-        memcpy(&inter[(size_t)(2 * p) * small], psf + (size_t)p * small, small * sizeof(double));
-        memcpy(&inter[(size_t)(2 * p + 1) * small], psf_var + (size_t)p * small, small * sizeof(double));
+        const int f = p / c->n_psf_field;
+        const size_t small = (size_t)psf_ny[f] * psf_nx[f];
+        const size_t src = psf_off[f] + (size_t)(p % c->n_psf_field) * small;
+        const size_t dst = 2 * psf_off[f] + (size_t)(2 * (p % c->n_psf_field)) * small;
+        memcpy(&inter[dst], psf + src, small * sizeof(double));
+        memcpy(&inter[dst + small], psf_var + src, small * sizeof(double));
     }
     double *d_small = nullptr, *d_canvas = nullptr;
     HIP_TRY(hipMalloc(&d_small, inter.size() * sizeof(double)));
@@ -1185,8 +1216,10 @@ static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, cons
         hipMemcpy(d_small, inter.data(), inter.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(PSFMC_EHIP, "hipMemcpy(psf) failed");
     if (rc == PSFMC_OK) {
-        hipLaunchKernelGGL(k_pad, dim3(256), dim3(256), 0, c->stream, d_small, d_canvas, 2 * c->n_psf,
-                           psf_ny, psf_nx, c->ny, c->nx);
+        for (int f = 0; f < c->n_fields; ++f)
+            hipLaunchKernelGGL(k_pad, dim3(256), dim3(256), 0, c->stream, d_small + 2 * psf_off[f],
+                               d_canvas + (size_t)2 * f * c->n_psf_field * c->S, 2 * c->n_psf_field, psf_ny[f], psf_nx[f],
+                               c->ny, c->nx);
         rc = c->backend == PSFMC_BACKEND_FUSED ? spectra_fused(c, d_canvas) : spectra_hipfft(c, d_canvas);
     }
     (void)hipStreamSynchronize(c->stream);
@@ -1212,35 +1245,54 @@ static void embed_axis_at(int l, int pk, int m, int* a, int* e) {
     *e = l + pk - 1;
 }
 
-// The transform shape of an image with unbuilt sides.  Every built side >= l + pk - 1 would do; the kernels of
-// the built sides differ by up to 2x per pixel (radix mix, lanes per transform, registers), so the smallest
-// is often not the cheapest: the pair (my, mx) with the least ny nx (rows(nx) + cols(ny)) of the measured table
-// psfmc_side_costs.h wins, if it beats the smallest pair by 4 % (the table's noise).  A built axis stays as it is.
-static bool choose_embedding(int ly, int lx, int pky, int pkx, int* my, int* mx) {
+// The transform shape of a context's fields (image sides ly[f] x lx[f], PSF sides pky[f] x pkx[f]), per axis:
+// an axis on which every field has one built side keeps it; otherwise a built side m serves if every field
+// either has that side (it is not embedded on the axis) or fits with its wrap-around margin, m >= l + pk - 1
+// (embedded).  The kernels of the built sides differ by up to 2x per pixel (radix mix, lanes per transform,
+// registers), so the smallest pair is often not the cheapest: the pair (my, mx) with the least
+// ny nx (rows(nx) + cols(ny)) of the measured table psfmc_side_costs.h wins, if it beats the smallest pair by
+// 4 % (the table's noise).  One field (or fields of one shape) get the choice of an image of their own.
+// false: no built side serves every field on an axis; *bad = a field the largest built side does not serve.
+static bool choose_embedding(int n, const int* ly, const int* lx, const int* pky, const int* pkx, int* my, int* mx,
+                             int* bad) {
     auto cost_of = [](int side) -> const SideCost* {
         for (const SideCost& sc : kSideCosts)
             if (sc.side == side) return &sc;
         return nullptr;
     };
-    const bool fix_y = fused_side(ly), fix_x = fused_side(lx);
-    const int need_y = fix_y ? ly : ly + pky - 1, need_x = fix_x ? lx : lx + pkx - 1;
+    auto fixed_side = [n](const int* l) {            // the axis's side if every field has it and it is built
+        for (int f = 1; f < n; ++f)
+            if (l[f] != l[0]) return 0;
+        return fused_side(l[0]) ? l[0] : 0;
+    };
+    const int fix_y = fixed_side(ly), fix_x = fixed_side(lx);
+    auto misfit = [n](int m, int fix, const int* l, const int* pk) {   // the first field m does not serve, or -1
+        if (fix) return m == fix ? -1 : 0;
+        for (int f = 0; f < n; ++f)
+            if (l[f] != m && m < l[f] + pk[f] - 1) return f;
+        return -1;
+    };
     int small_y = 0, small_x = 0;
     for (int v : kFusedSides) {
-        if (!small_y && v >= need_y) small_y = v;
-        if (!small_x && v >= need_x) small_x = v;
+        if (!small_y && misfit(v, fix_y, ly, pky) < 0) small_y = v;
+        if (!small_x && misfit(v, fix_x, lx, pkx) < 0) small_x = v;
     }
-    if (!small_y || !small_x) return false;
+    if (!small_y || !small_x) {
+        const int kLargest = kFusedSides[sizeof(kFusedSides) / sizeof(kFusedSides[0]) - 1];
+        *bad = !small_y ? misfit(kLargest, fix_y, ly, pky) : misfit(kLargest, fix_x, lx, pkx);
+        return false;
+    }
     *my = small_y; *mx = small_x;
     const SideCost *sy0 = cost_of(small_y), *sx0 = cost_of(small_x);
     if (!sy0 || !sx0) return true;
     const double base = (double)small_y * small_x * (sx0->rows_ps + sy0->cols_ps);
     double best = base * 0.96;
     for (int vy : kFusedSides) {
-        if (fix_y ? vy != ly : vy < need_y) continue;
+        if (misfit(vy, fix_y, ly, pky) >= 0) continue;
         const SideCost* sy = cost_of(vy);
         if (!sy) continue;
         for (int vx : kFusedSides) {
-            if (fix_x ? vx != lx : vx < need_x) continue;
+            if (misfit(vx, fix_x, lx, pkx) >= 0) continue;
             const SideCost* sx = cost_of(vx);
             if (!sx) continue;
             const double cst = (double)vy * vx * (sx->rows_ps + sy->cols_ps);
@@ -1250,57 +1302,70 @@ static bool choose_embedding(int ly, int lx, int pky, int pkx, int* my, int* mx)
     return true;
 }
 
-static int ctx_create_impl(psfmc_ctx** out, int device, int ny, int nx, int n_fields, const double* sci,
-                           const double* obs_var, const uint8_t* bad_px, int n_psf,
-                           int psf_ny, int psf_nx, const double* psf, const double* psf_var,
+// Every context is made here: n_fields fields, field f an image of ny[f] x nx[f] pixels with n_psf PSFs of
+// psf_ny[f] x psf_nx[f]; the pixel arrays are the fields' own arrays concatenated in field order.
+static int ctx_create_impl(psfmc_ctx** out, int device, int n_fields, const int* ny_f, const int* nx_f,
+                           const double* sci, const double* obs_var, const uint8_t* bad_px, int n_psf,
+                           const int* psf_ny, const int* psf_nx, const double* psf, const double* psf_var,
                            int n_ps, int n_sersic, int max_walkers, int backend) {
     if (!out) return fail(PSFMC_EINVAL, "out is NULL");
+    *out = nullptr;
     if (n_fields < 1 || n_fields > 4096) return fail(PSFMC_EINVAL, "n_fields out of range");
     if (n_fields > 1 && backend != PSFMC_BACKEND_FUSED)
         return fail(PSFMC_EINVAL, "several fields per context need the fused back end");
-    *out = nullptr;
+    if (!ny_f || !nx_f || !psf_ny || !psf_nx) return fail(PSFMC_EINVAL, "NULL shape array");
     if (!sci || !obs_var || !bad_px || !psf || !psf_var) return fail(PSFMC_EINVAL, "NULL input array");
-    if (ny < 2 || nx < 2 || (ny & 1) || (nx & 1))
-        return fail(PSFMC_EINVAL, "image sides must be even (got %d x %d)", ny, nx);
-    if (n_psf < 1 || psf_ny < 1 || psf_nx < 1 || psf_ny > ny || psf_nx > nx)
-        return fail(PSFMC_EINVAL, "PSF larger than the observation is not supported (%d x %d in %d x %d)",
-                    psf_ny, psf_nx, ny, nx);
+    for (int f = 0; f < n_fields; ++f) {
+        if (ny_f[f] < 2 || nx_f[f] < 2 || (ny_f[f] & 1) || (nx_f[f] & 1))
+            return fail(PSFMC_EINVAL, "field %d: image sides must be even (got %d x %d)", f, ny_f[f], nx_f[f]);
+        if (psf_ny[f] < 1 || psf_nx[f] < 1 || psf_ny[f] > ny_f[f] || psf_nx[f] > nx_f[f])
+            return fail(PSFMC_EINVAL, "field %d: PSF larger than the observation is not supported (%d x %d in %d x %d)",
+                        f, psf_ny[f], psf_nx[f], ny_f[f], nx_f[f]);
+    }
+    if (n_psf < 1) return fail(PSFMC_EINVAL, "n_psf must be >= 1");
     if (n_ps < 0 || n_sersic < 0 || n_ps > 16 || n_sersic > 16)
         return fail(PSFMC_EINVAL, "component counts out of range (n_ps=%d n_sersic=%d)", n_ps, n_sersic);
     if (max_walkers < 1) return fail(PSFMC_EINVAL, "max_walkers must be >= 1");
     if (backend != PSFMC_BACKEND_HIPFFT && backend != PSFMC_BACKEND_FUSED)
         return fail(PSFMC_EINVAL, "unknown backend %d", backend);
+    int ny = ny_f[0], nx = nx_f[0];                   // the transform's sides
     int row_tiles = 0;
     bool rows3_fwd = false, rows3_inv = false;
     RowShape rs{};
-    const int ly = ny, lx = nx;                       // the image's own sides
-    WrapDesc wrap{0, 0, 0, 0, 0, 0};
+    // every field's image inside the transform: the identity unless it is embedded
+    std::vector<WrapDesc> wraps(n_fields);
+    for (int f = 0; f < n_fields; ++f) wraps[f] = WrapDesc{nx_f[f], 0, nx_f[f], ny_f[f], 0, ny_f[f]};
     bool embed = false;
     std::vector<double> pad_sci, pad_var;
     std::vector<uint8_t> pad_bad;
     if (backend == PSFMC_BACKEND_FUSED) {
-        if (!fused_side(ny) || !fused_side(nx)) {
-            // embed the axes the transforms are not built for (a built axis stays as it is: a = 0, e = l = m)
-            embed = true;
-            wrap = WrapDesc{lx, 0, lx, ly, 0, ly};
-            if (!choose_embedding(ly, lx, psf_ny, psf_nx, &ny, &nx))
-                return fail(PSFMC_EINVAL, "fused backend: image %d x %d + PSF %d x %d - 1 exceeds the largest built "
-                            "side (2048)", ly, lx, psf_ny, psf_nx);
-            if (nx != lx) embed_axis_at(lx, psf_nx, nx, &wrap.ax, &wrap.ex);
-            if (ny != ly) embed_axis_at(ly, psf_ny, ny, &wrap.ay, &wrap.ey);
-            // the field arrays in transform coordinates: the image at (ay, ax), every other pixel excluded
-            const size_t S_t = (size_t)ny * nx, S_l = (size_t)ly * lx;
+        int bad = 0;
+        if (!choose_embedding(n_fields, ny_f, nx_f, psf_ny, psf_nx, &ny, &nx, &bad))
+            return fail(PSFMC_EINVAL, "fused backend: field %d: image %d x %d + PSF %d x %d - 1 exceeds the largest "
+                        "built side (2048)%s", bad, ny_f[bad], nx_f[bad], psf_ny[bad], psf_nx[bad],
+                        n_fields > 1 ? " where the transform shared by the fields needs it" : "");
+        // embed the axes on which a field's side is not the transform's (an axis that is stays as it is)
+        for (int f = 0; f < n_fields; ++f) {
+            if (nx != nx_f[f]) embed_axis_at(nx_f[f], psf_nx[f], nx, &wraps[f].ax, &wraps[f].ex);
+            if (ny != ny_f[f]) embed_axis_at(ny_f[f], psf_ny[f], ny, &wraps[f].ay, &wraps[f].ey);
+            embed = embed || nx != nx_f[f] || ny != ny_f[f];
+        }
+        if (embed) {
+            // the field arrays in transform coordinates: each image at its (ay, ax), every other pixel excluded
+            const size_t S_t = (size_t)ny * nx;
             pad_sci.assign((size_t)n_fields * S_t, 0.0);
             pad_var.assign((size_t)n_fields * S_t, 1.0);
             pad_bad.assign((size_t)n_fields * S_t, 1);
-            for (int f = 0; f < n_fields; ++f)
-                for (int y = 0; y < ly; ++y) {
-                    const size_t dst = (size_t)f * S_t + (size_t)(y + wrap.ay) * nx + wrap.ax;
-                    const size_t src = (size_t)f * S_l + (size_t)y * lx;
-                    memcpy(&pad_sci[dst], sci + src, (size_t)lx * sizeof(double));
-                    memcpy(&pad_var[dst], obs_var + src, (size_t)lx * sizeof(double));
-                    memcpy(&pad_bad[dst], bad_px + src, (size_t)lx);
+            size_t src = 0;
+            for (int f = 0; f < n_fields; ++f) {
+                const WrapDesc& w = wraps[f];
+                for (int y = 0; y < w.ly; ++y, src += w.lx) {
+                    const size_t dst = (size_t)f * S_t + (size_t)(y + w.ay) * nx + w.ax;
+                    memcpy(&pad_sci[dst], sci + src, (size_t)w.lx * sizeof(double));
+                    memcpy(&pad_var[dst], obs_var + src, (size_t)w.lx * sizeof(double));
+                    memcpy(&pad_bad[dst], bad_px + src, (size_t)w.lx);
                 }
+            }
             sci = pad_sci.data(); obs_var = pad_var.data(); bad_px = pad_bad.data();
         }
         const char* env3 = getenv("PSFMC_ROWS3");
@@ -1328,7 +1393,7 @@ static int ctx_create_impl(psfmc_ctx** out, int device, int ny, int nx, int n_fi
     psfmc_ctx* c = new psfmc_ctx;
     c->device = device;
     c->ny = ny; c->nx = nx; c->nxh = nx / 2 + 1; c->S = ny * nx; c->F = ny * c->nxh;
-    c->ly = ly; c->lx = lx; c->embed = embed; c->wrap = wrap;
+    c->embed = embed; c->wraps = wraps;
     c->n_fields = n_fields; c->n_psf_field = n_psf;
     c->acc_more.assign(n_fields - 1, 0);
     c->n_psf = n_fields * n_psf; c->n_ps = n_ps; c->n_sersic = n_sersic;
@@ -1380,20 +1445,55 @@ extern "C" int psfmc_ctx_create(psfmc_ctx** out, int device, int ny, int nx, con
                                 const double* obs_var, const uint8_t* bad_px, int n_psf,
                                 int psf_ny, int psf_nx, const double* psf, const double* psf_var,
                                 int n_ps, int n_sersic, int max_walkers, int backend) {
-    return ctx_create_impl(out, device, ny, nx, 1, sci, obs_var, bad_px, n_psf, psf_ny, psf_nx, psf, psf_var, n_ps,
+    return ctx_create_impl(out, device, 1, &ny, &nx, sci, obs_var, bad_px, n_psf, &psf_ny, &psf_nx, psf, psf_var, n_ps,
                            n_sersic, max_walkers, backend);
 }
 
-// Several observed fields of one shape in ONE context (fused back end): their walkers share the
-// batches of psfmc_eval_theta_device_fields, so many small ensembles run at the rate of one large one
-// (BASELINE config 5: independent fields x 256 walkers each).  sci / obs_var / bad_px: [n_fields][ny][nx];
-// psf / psf_var: [n_fields][n_psf][psf_ny][psf_nx]; the same component counts for every field.
+// Several observed fields in ONE context (fused back end): their walkers share the batches of
+// psfmc_eval_theta_device_fields, so many small ensembles run at the rate of one large one (BASELINE config 5:
+// independent fields x 256 walkers each).  Field f is an image of ny[f] x nx[f] pixels with n_psf[f] PSFs of
+// psf_ny[f] x psf_nx[f] (n_psf[f] the same for every field); sci / obs_var / bad_px and psf / psf_var are the
+// fields' own arrays concatenated in field order; the same component counts for every field.  The fields share
+// one transform shape (choose_embedding), which every one of them pays for.
+extern "C" int psfmc_ctx_create_fields_shaped(psfmc_ctx** out, int device, int n_fields, const int* ny, const int* nx,
+                                              const double* sci, const double* obs_var, const uint8_t* bad_px,
+                                              const int* n_psf, const int* psf_ny, const int* psf_nx, const double* psf,
+                                              const double* psf_var, int n_ps, int n_sersic, int max_walkers) {
+    if (!out) return fail(PSFMC_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (n_fields < 1 || n_fields > 4096) return fail(PSFMC_EINVAL, "n_fields out of range");
+    if (!n_psf) return fail(PSFMC_EINVAL, "NULL shape array");
+    for (int f = 1; f < n_fields; ++f)
+        if (n_psf[f] != n_psf[0])
+            return fail(PSFMC_EINVAL, "field %d: %d PSFs where field 0 has %d (every field needs the same number)", f,
+                        n_psf[f], n_psf[0]);
+    return ctx_create_impl(out, device, n_fields, ny, nx, sci, obs_var, bad_px, n_psf[0], psf_ny, psf_nx, psf, psf_var,
+                           n_ps, n_sersic, max_walkers, PSFMC_BACKEND_FUSED);
+}
+
+// the same with every field of one shape: sci / obs_var / bad_px [n_fields][ny][nx], psf / psf_var
+// [n_fields][n_psf][psf_ny][psf_nx]
 extern "C" int psfmc_ctx_create_fields(psfmc_ctx** out, int device, int ny, int nx, int n_fields,
                                        const double* sci, const double* obs_var, const uint8_t* bad_px,
                                        int n_psf, int psf_ny, int psf_nx, const double* psf,
                                        const double* psf_var, int n_ps, int n_sersic, int max_walkers) {
-    return ctx_create_impl(out, device, ny, nx, n_fields, sci, obs_var, bad_px, n_psf, psf_ny, psf_nx, psf, psf_var,
-                           n_ps, n_sersic, max_walkers, PSFMC_BACKEND_FUSED);
+    if (!out) return fail(PSFMC_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (n_fields < 1 || n_fields > 4096) return fail(PSFMC_EINVAL, "n_fields out of range");
+    const std::vector<int> ys(n_fields, ny), xs(n_fields, nx), ks(n_fields, n_psf), pys(n_fields, psf_ny),
+        pxs(n_fields, psf_nx);
+    return psfmc_ctx_create_fields_shaped(out, device, n_fields, ys.data(), xs.data(), sci, obs_var, bad_px, ks.data(),
+                                          pys.data(), pxs.data(), psf, psf_var, n_ps, n_sersic, max_walkers);
+}
+
+// a field's own image sides (the shape of its pixel arrays at the C ABI; get_option "transform_ny" / "_nx" gives
+// the transform's, shared by every field)
+extern "C" int psfmc_field_shape(psfmc_ctx* c, int field, int* ny, int* nx) {
+    if (!c || !ny || !nx) return fail(PSFMC_EINVAL, "NULL argument");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    *ny = c->wraps[field].ly;
+    *nx = c->wraps[field].lx;
+    return PSFMC_OK;
 }
 
 extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
@@ -1409,7 +1509,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_like, c->d_skip, c->d_partial, c->d_real,  c->d_spec,  c->d_Ts[0], c->d_Kraw,
                     c->d_Kt,   c->d_twx,  c->d_twy,     c->d_img0,  c->d_img1, c->d_rho,   c->d_field, c->d_Ts[1], c->d_acc, c->d_lin, c->d_linpart,
                     c->d_layout_blob, c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
-                    c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
+                    c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag};
     for (void* p : bufs)
@@ -1727,7 +1827,8 @@ static int eval_device(psfmc_ctx* c, int W, const double* d_rows, const uint8_t*
                        double* d_like, hipStream_t st, int field = -1) {
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, d_rows, c->d_prep, W, c->n_ps,
-                       c->n_sersic, c->ly, c->lx, c->d_rho, field < 0 ? c->n_psf : c->n_psf_field,
+                       c->n_sersic, c->wraps[field < 0 ? 0 : field].ly, c->wraps[field < 0 ? 0 : field].lx, c->d_rho,
+                       field < 0 ? c->n_psf : c->n_psf_field,
                        field < 0 ? 0 : field * c->n_psf_field);
     launch_pow_tables(c, W, 0, d_skip, st);
     RC_TRY(run_pipeline(c, W, d_skip, st));
@@ -1747,13 +1848,14 @@ static void launch_theta_prep(psfmc_ctx* c, int W, const double* d_theta, const 
                               double* d_rows, hipStream_t st, const StretchIn& sp, int field = 0, int w_off = 0,
                               int n_seg = 1) {
     const ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    FieldSegs segs{nullptr, 0};
-    if (n_seg > 1) segs = FieldSegs{c->d_field_layouts + field, c->n_psf_field};
+    FieldSegs segs{nullptr, nullptr, 0};
+    if (n_seg > 1) segs = FieldSegs{c->d_field_layouts + field, c->d_field_sides + 2 * field, c->n_psf_field};
     if (w_off == 0) c->prep_tabs_valid = false;       // d_prep is being rewritten (w_off > 0: a further piece of one batch)
     hipLaunchKernelGGL(k_theta_prep, dim3((W + kThetaThreads - 1) / kThetaThreads, n_seg),
                        dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
                        L, d_theta, d_extra, d_rows, c->d_prep + (size_t)w_off * c->plen, c->d_lnprior + w_off,
-                       c->d_skip + w_off, W, c->ly, c->lx, c->d_rho, sp, field * c->n_psf_field, segs);
+                       c->d_skip + w_off, W, c->wraps[field].ly, c->wraps[field].lx, c->d_rho, sp, field * c->n_psf_field,
+                       segs);
     launch_pow_tables(c, W * n_seg, w_off, c->d_skip + w_off, st);
 }
 
@@ -1838,12 +1940,12 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const bool fused = c->backend == PSFMC_BACKEND_FUSED;
-    const size_t S_img = (size_t)c->ly * c->lx;                 // pixels of a host image
+    const size_t S_img = img_pixels(c, field);                  // pixels of a host image (the field's own shape)
     const size_t img = S_img * sizeof(double);
     HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
-                       c->n_sersic, c->ly, c->lx, c->d_rho, c->n_psf_field, field * c->n_psf_field);
+                       c->n_sersic, c->wraps[field].ly, c->wraps[field].lx, c->d_rho, c->n_psf_field, field * c->n_psf_field);
     launch_pow_tables(c, W, 0, nullptr, st);
     RC_TRY(ensure_image_staging(c));
     double *d_out = nullptr, *d_rawdev = nullptr;     // [chunk] staging for derived images / the raw models (transform shape)
@@ -1862,7 +1964,7 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
         auto emit = [&](double* host, const double* src, int strd, int comp, int op) -> int {
             if (!host) return PSFMC_OK;
             hipLaunchKernelGGL(k_image_out, dim3(64, n), dim3(256), 0, st, src, f_sci, f_var, d_out,
-                               c->S, strd, comp, op, img_window(c));
+                               c->S, strd, comp, op, img_window(c, field));
             HIP_TRY(hipMemcpyAsync(host + (size_t)w0 * S_img, d_out, (size_t)n * img,
                                    hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -2429,7 +2531,7 @@ extern "C" int psfmc_accumulate_images(psfmc_ctx* c, int W, const double* rows) 
     HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
-                       c->n_sersic, c->ly, c->lx, c->d_rho, c->n_psf, 0);
+                       c->n_sersic, c->wraps[0].ly, c->wraps[0].lx, c->d_rho, c->n_psf, 0);
     launch_pow_tables(c, W, 0, nullptr, st);
     rc = accumulate_from_prep(c, W, st);
     (void)hipStreamSynchronize(st);
@@ -2840,7 +2942,8 @@ extern "C" int psfmc_get_accumulated_sums(psfmc_ctx* c, double* sums, long long*
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(flush_linear_sums(c));
     *count = c->acc_count;
-    const size_t S_img = (size_t)c->ly * c->lx;
+    const WrapDesc& wr = c->wraps[0];
+    const size_t S_img = img_pixels(c, 0);
     if (!c->d_acc) { memset(sums, 0, 4 * S_img * sizeof(double)); return PSFMC_OK; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!c->embed) {
@@ -2850,9 +2953,9 @@ extern "C" int psfmc_get_accumulated_sums(psfmc_ctx* c, double* sums, long long*
     std::vector<double> full((size_t)4 * c->S);              // transform shape -> the image's window
     HIP_TRY(hipMemcpy(full.data(), c->d_acc, full.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; ++k)
-        for (int y = 0; y < c->ly; ++y)
-            memcpy(sums + k * S_img + (size_t)y * c->lx,
-                   &full[(size_t)k * c->S + (size_t)(y + c->wrap.ay) * c->nx + c->wrap.ax], (size_t)c->lx * sizeof(double));
+        for (int y = 0; y < wr.ly; ++y)
+            memcpy(sums + k * S_img + (size_t)y * wr.lx,
+                   &full[(size_t)k * c->S + (size_t)(y + wr.ay) * c->nx + wr.ax], (size_t)wr.lx * sizeof(double));
     return PSFMC_OK;
 }
 
@@ -2866,12 +2969,13 @@ extern "C" int psfmc_set_accumulated_sums(psfmc_ctx* c, const double* sums, long
     if (!c->embed) {
         HIP_TRY(hipMemcpy(c->d_acc, sums, (size_t)4 * c->S * sizeof(double), hipMemcpyHostToDevice));
     } else {
-        const size_t S_img = (size_t)c->ly * c->lx;
+        const WrapDesc& wr = c->wraps[0];
+        const size_t S_img = img_pixels(c, 0);
         std::vector<double> full((size_t)4 * c->S, 0.0);     // only the image's window is ever read back
         for (int k = 0; k < 4; ++k)
-            for (int y = 0; y < c->ly; ++y)
-                memcpy(&full[(size_t)k * c->S + (size_t)(y + c->wrap.ay) * c->nx + c->wrap.ax],
-                       sums + k * S_img + (size_t)y * c->lx, (size_t)c->lx * sizeof(double));
+            for (int y = 0; y < wr.ly; ++y)
+                memcpy(&full[(size_t)k * c->S + (size_t)(y + wr.ay) * c->nx + wr.ax],
+                       sums + k * S_img + (size_t)y * wr.lx, (size_t)wr.lx * sizeof(double));
         HIP_TRY(hipMemcpy(c->d_acc, full.data(), full.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     c->acc_count = count;
@@ -2888,7 +2992,7 @@ static int get_accumulated_impl(psfmc_ctx* c, int field, double* raw, double* co
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(flush_linear_sums(c));
     double* d_out = nullptr;
-    const size_t S_img = (size_t)c->ly * c->lx;
+    const size_t S_img = img_pixels(c, field);              // the field's own image shape
     HIP_TRY(hipMalloc(&d_out, S_img * sizeof(double)));
     const double inv_n = 1.0 / (double)n;
     const size_t px = (size_t)field * c->S;                 // this field's pixels in d_sci / d_var
@@ -2899,7 +3003,7 @@ static int get_accumulated_impl(psfmc_ctx* c, int field, double* raw, double* co
         if (!o.host) continue;
         hipLaunchKernelGGL(k_accumulated_out, dim3(256), dim3(256), 0, c->stream,
                            c->d_acc + ((size_t)field * 4 + o.slot) * c->S, c->d_sci + px, c->d_var + px, d_out,
-                           inv_n, o.op, img_window(c));
+                           inv_n, o.op, img_window(c, field));
         if (hipMemcpyAsync(o.host, d_out, S_img * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
                 hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
             rc = fail(PSFMC_EHIP, "accumulated image copy failed");
@@ -2924,7 +3028,7 @@ extern "C" int psfmc_get_accumulated_field(psfmc_ctx* c, int field, double* raw,
 extern "C" int psfmc_get_spectra(psfmc_ctx* c, double* psf_spec, double* var_spec) {
     if (!c || !psf_spec || !var_spec) return fail(PSFMC_EINVAL, "NULL argument");
     if (c->embed) return fail(PSFMC_EINVAL, "the image is embedded in a %d x %d transform: its kernel spectra are not "
-                              "those of the %d x %d image", c->ny, c->nx, c->ly, c->lx);
+                              "those of the %d x %d image", c->ny, c->nx, c->wraps[0].ly, c->wraps[0].lx);
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n_psf * c->F * sizeof(double2);
     if (c->backend == PSFMC_BACKEND_HIPFFT) {

@@ -212,7 +212,8 @@ template <int NX, bool FROM_IMAGE, bool WRAP = false, class S = typename Rows3<N
 __global__ void __launch_bounds__((rows3_threads(NX)), (rows3_min_waves<S, false>()))
 k_rows3_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip, const cd* __restrict__ twx,
             cd* __restrict__ Tbuf, int n_ps, int n_sersic, int ny, int ps_only, const double* __restrict__ img,
-            const double* __restrict__ img_scale, double* __restrict__ raw_out, WrapDesc wr, int pow_mode) {
+            const double* __restrict__ img_scale, double* __restrict__ raw_out, const WrapDesc* __restrict__ wrap_tab,
+            int pow_mode) {
     static_assert(pow_tabs_side(NX), "the three-stage row kernels rasterise with the power tables");
     static_assert(rows3_lds_fits<S>(), "a workgroup's LDS");
     constexpr int R1 = S::R1, R2 = S::R2, R3 = S::R3, L = S::L, NB3 = S::NB3;
@@ -253,6 +254,8 @@ k_rows3_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip, c
 #pragma unroll
         for (int k = 0; k < R1; ++k) v[k] = cd{0.0, 0.0};
         if (row_in) {
+            WrapDesc wr{0, 0, 0, 0, 0, 0};
+            if constexpr (WRAP) wr = walker_wrap(wrap_tab, wprep);  // (its field's; the walker is not skipped)
             // the rasteriser's tables borrow the wave's transform region, idle until the transform begins
             if (!ps_only && n_sersic > 0) load_a_table(wave_lds, t);
             double r[R1];

@@ -425,10 +425,11 @@ struct StretchIn {
     int spec;
 };
 
-// the fields of one k_theta_prep launch (gridDim.y > 1): field f takes layouts[f], walkers
-// [f W, (f + 1) W) of every per-walker array, kernel spectra from f * psf_stride on
+// the fields of one k_theta_prep launch (gridDim.y > 1): field f takes layouts[f], image sides sides[2 f],
+// sides[2 f + 1], walkers [f W, (f + 1) W) of every per-walker array, kernel spectra from f * psf_stride on
 struct FieldSegs {
     const ThetaLayout* layouts;   // device array [gridDim.y], or nullptr: one field, the layout passed by value
+    const int* sides;             // device array [gridDim.y][2] (fields may differ in image size)
     int psf_stride;
 };
 
@@ -469,6 +470,8 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
     if (segs.layouts) {                                 // (wave-uniform) this workgroup's field
         const int f = blockIdx.y;
         G = segs.layouts[f];
+        ny = segs.sides[2 * f];
+        nx = segs.sides[2 * f + 1];
         const size_t first = (size_t)f * W;             // its first walker in the per-walker arrays
         if (theta) theta += first * G.n_params;
         if (extra) extra += first;

@@ -177,6 +177,11 @@ def load_library():
     lib.psfmc_ctx_create_fields.restype = ci
     lib.psfmc_ctx_create_fields.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, _c_double_p, _c_double_p, _c_u8_p,
                                             ci, ci, ci, _c_double_p, _c_double_p, ci, ci, ci]
+    lib.psfmc_ctx_create_fields_shaped.restype = ci
+    lib.psfmc_ctx_create_fields_shaped.argtypes = [ctypes.POINTER(vp), ci, ci, ip, ip, _c_double_p, _c_double_p,
+                                                   _c_u8_p, ip, ip, ip, _c_double_p, _c_double_p, ci, ci, ci]
+    lib.psfmc_field_shape.restype = ci
+    lib.psfmc_field_shape.argtypes = [vp, ci, ip, ip]
     lib.psfmc_set_layout_field.restype = ci
     lib.psfmc_set_layout_field.argtypes = [vp, ci, ci, ci, ip, _c_double_p, ip, ip, ctypes.c_double, ip,
                                            _c_double_p, _c_double_p, _c_double_p]
@@ -618,12 +623,16 @@ class Context(object):
 
 
 class FieldSetContext(object):
-    """Several observed fields of ONE shape resident on one GPU in one context (wraps
-    `psfmc_ctx_create_fields`): their walkers share the batches, so many small ensembles run at the
-    rate of one large one -- log-posteriors, the device-resident sampler (every field's ensemble stepped
-    together), posterior-image sums and per-sample images.
+    """Several observed fields resident on one GPU in one context (wraps `psfmc_ctx_create_fields_shaped`):
+    their walkers share the batches, so many small ensembles run at the rate of one large one --
+    log-posteriors, the device-resident sampler (every field's ensemble stepped together), posterior-image
+    sums and per-sample images.  The fields may differ in image and PSF size.  They share one transform
+    shape (`get_option('transform_ny' / 'transform_nx')`), and every field costs what a walker of that
+    shape costs: a 96 x 96 field in a set with a 256 x 256 one costs a 256 x 256 walker.  Fields of very
+    different sizes are cheaper in separate sets.
 
-    fields: sequence of (sci, obs_var, bad_px, psfs [n_psf, py, px], psf_vars) with the same shapes."""
+    fields: sequence of (sci, obs_var, bad_px, psfs [n_psf, py, px], psf_vars), every field with its own
+    image and PSF shape and the same number of PSFs.  `shapes[f]` is field f's image shape."""
 
     def __init__(self, fields, n_ps, n_sersic, max_walkers=4096, device=0):
         self._lib = load_library()
@@ -631,26 +640,47 @@ class FieldSetContext(object):
         fields = list(fields)
         if not fields:
             raise ValueError('no field')
-        sci = _f64(np.stack([_f64(f[0]) for f in fields]))
-        var = _f64(np.stack([_f64(f[1]) for f in fields]))
-        bad = np.ascontiguousarray(np.stack([np.asarray(f[2]).astype(bool) for f in fields]), dtype=np.uint8)
-        psfs = _f64(np.stack([_f64(f[3]) for f in fields]))
-        pvar = _f64(np.stack([_f64(f[4]) for f in fields]))
-        if sci.ndim != 3 or var.shape != sci.shape or bad.shape != sci.shape:
-            raise ValueError('every field needs sci / obs_var / bad_px of one 2-D shape')
-        if psfs.ndim != 4 or pvar.shape != psfs.shape:
-            raise ValueError('every field needs psfs / psf_vars of one [n_psf, py, px] shape')
-        self.n_fields, self.shape, self.n_psf = len(fields), sci.shape[1:], psfs.shape[1]
+        sci, var, bad, psfs, pvar = [], [], [], [], []
+        for f, fld in enumerate(fields):
+            sci.append(_f64(fld[0]))
+            var.append(_f64(fld[1]))
+            bad.append(np.ascontiguousarray(np.asarray(fld[2]).astype(bool), dtype=np.uint8))
+            psfs.append(_f64(fld[3]))
+            pvar.append(_f64(fld[4]))
+            if sci[f].ndim != 2 or var[f].shape != sci[f].shape or bad[f].shape != sci[f].shape:
+                raise ValueError('field {}: sci / obs_var / bad_px need one 2-D shape'.format(f))
+            if psfs[f].ndim != 3 or pvar[f].shape != psfs[f].shape:
+                raise ValueError('field {}: psfs / psf_vars need one [n_psf, py, px] shape'.format(f))
+            if len(psfs[f]) != len(psfs[0]):
+                raise ValueError('field {} has {} PSFs and field 0 has {}: every field of a set needs the same '
+                                 'number of PSFs'.format(f, len(psfs[f]), len(psfs[0])))
+        self.n_fields, self.n_psf = len(fields), psfs[0].shape[0]
+        self.shapes = [tuple(a.shape) for a in sci]
+        # the one image shape of a set whose fields all have it; None for a mixed set (see `shapes`)
+        self.shape = self.shapes[0] if len(set(self.shapes)) == 1 else None
         self.n_ps, self.n_sersic = int(n_ps), int(n_sersic)
         self.max_walkers, self.device = int(max_walkers), int(device)
         self.n_params = None
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        ny, nx = i32([sh[0] for sh in self.shapes]), i32([sh[1] for sh in self.shapes])
+        kn = i32([len(p) for p in psfs])
+        py, px = i32([p.shape[1] for p in psfs]), i32([p.shape[2] for p in psfs])
+        cat = lambda arrs: np.ascontiguousarray(np.concatenate([a.ravel() for a in arrs]))
+        sci, var, bad, psfs, pvar = cat(sci), cat(var), cat(bad), cat(psfs), cat(pvar)
         handle = ctypes.c_void_p()
-        rc = self._lib.psfmc_ctx_create_fields(
-            ctypes.byref(handle), self.device, sci.shape[1], sci.shape[2], self.n_fields, _dp(sci), _dp(var),
-            bad.ctypes.data_as(_c_u8_p), self.n_psf, psfs.shape[2], psfs.shape[3], _dp(psfs), _dp(pvar),
+        rc = self._lib.psfmc_ctx_create_fields_shaped(
+            ctypes.byref(handle), self.device, self.n_fields, ipt(ny), ipt(nx), _dp(sci), _dp(var),
+            bad.ctypes.data_as(_c_u8_p), ipt(kn), ipt(py), ipt(px), _dp(psfs), _dp(pvar),
             self.n_ps, self.n_sersic, self.max_walkers)
         self._check(rc)
         self._ctx = handle
+
+    def field_shape(self, field):
+        """Field `field`'s image shape as the library reports it (the shape of its images and sums)."""
+        ny, nx = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.psfmc_field_shape(self._ctx, int(field), ctypes.byref(ny), ctypes.byref(nx)))
+        return ny.value, nx.value
 
     def _check(self, rc):
         if rc != 0:
@@ -772,8 +802,8 @@ class FieldSetContext(object):
             self._check(self._lib.psfmc_accumulate_theta_field(self._ctx, int(field), len(part), _dp(part)))
 
     def accumulated(self, field):
-        """(dict kind -> mean image, sample count) of one field's posterior sums."""
-        bufs = {k: np.empty(self.shape, dtype=np.float64) for k in self.IMAGE_KINDS}
+        """(dict kind -> mean image, sample count) of one field's posterior sums, at the field's own shape."""
+        bufs = {k: np.empty(self.shapes[field], dtype=np.float64) for k in self.IMAGE_KINDS}
         count = ctypes.c_longlong(0)
         self._check(self._lib.psfmc_get_accumulated_field(
             self._ctx, int(field), *[_dp(bufs[k]) for k in self.IMAGE_KINDS], ctypes.byref(count)))
@@ -813,7 +843,7 @@ class FieldSetContext(object):
         bufs, args = {}, []
         for k in self.IMAGE_KINDS:
             if k in kinds:
-                bufs[k] = np.empty((n_w,) + tuple(self.shape), dtype=np.float64)
+                bufs[k] = np.empty((n_w,) + tuple(self.shapes[field]), dtype=np.float64)
                 args.append(_dp(bufs[k]))
             else:
                 args.append(None)
@@ -831,7 +861,7 @@ class FieldView(object):
 
     def __init__(self, owner, field):
         self.owner, self.field = owner, int(field)
-        self.shape, self.n_psf = tuple(owner.shape), owner.n_psf
+        self.shape, self.n_psf = tuple(owner.shapes[self.field]), owner.n_psf
         self.max_walkers, self.device = owner.max_walkers, owner.device
 
     def close(self):                       # the FieldSet owns the context

@@ -162,7 +162,8 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
 def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetypes, iterations=0, burn=0,
                       chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
                       device=0, random_states=None, start_positions=None, accumulate=True, quiet=False):
-    """`model_galaxy_mcmc` for SEVERAL fields of one image shape and one model structure at once, in
+    """`model_galaxy_mcmc` for SEVERAL fields of one model structure at once (their image and PSF sizes may
+    differ: each field's database and posterior images have its own shape), in
     one GPU context (`models.FieldSet`): every field is fitted exactly as its own `model_galaxy_mcmc`
     run would fit it -- its own ensemble of `chains` walkers, its own random stream, burn-in, sampling
     with posterior images accumulated, convergence check, trace database `<output_name>_db.fits` and

@@ -519,8 +519,10 @@ class MultiComponentModel(object):
 
 
 class FieldSet(object):
-    """Several fields of one image shape and one model structure (the same component lists, their own
-    data, constants and priors) evaluated in shared GPU batches: `engine.FieldSetContext`.  The
+    """Several fields of one model structure (the same component lists; their own data, image and PSF
+    sizes, constants and priors) evaluated in shared GPU batches: `engine.FieldSetContext`.  Every
+    field's images and posterior images have its own shape; the fields share one transform shape, which
+    each of them pays for (a small field in a set with a large one costs a large field's walker).  The
     reference has no counterpart (one `MultiComponentModel` per model file and process,
     psfMC/fitting.py:13-113); this is for surveys of many small fields, where a batch per field would
     be dominated by its fixed cost (BASELINE config 5).
