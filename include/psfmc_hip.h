@@ -270,6 +270,36 @@ int psfmc_eval_theta_fields(psfmc_ctx* ctx, int n_seg, const int* seg_field, con
 int psfmc_eval_theta_device_fields(psfmc_ctx* ctx, int n_seg, const int* seg_field, const int* seg_count,
                                    const double* d_theta, const double* d_extra_lnprior, double* d_lnprob,
                                    void* stream);
+/*
+ * Joint fits: several exposures of ONE object (dithers, visits, filters; each field its own data, PSFs,
+ * constants and zeropoint) fitted with ONE parameter vector per walker, its log-posterior
+ *   lnp(theta) = ((ll_0(theta_0) + ll_1(theta_1)) + ... + ll_{F-1}(theta_{F-1})) + lnprior(theta),
+ * theta_f = field f's values read from theta through its own slot -> column map.  A column read by several
+ * fields is a shared parameter; a column read by one field only is a per-field one.  -inf when the joint
+ * log-prior is not finite, when some field's Sersic component has reff_b > reff, or when the summed
+ * log-likelihood is not finite.  A walker's value does not depend on the rest of its batch.
+ *   psfmc_set_layout / psfmc_set_layout_field  every field's layout with n_params = the JOINT column count,
+ *                                 slot_col into the joint columns; the fields' own prior tables are ignored
+ *   psfmc_set_joint_priors        the joint prior table [n_params] (codes and checks of psfmc_set_priors;
+ *                                 every column a device family, not PSFMC_PRIOR_HOST), each column counted
+ *                                 ONCE.  Valid after every field has its layout; a later layout call
+ *                                 invalidates it (call it again).
+ *   psfmc_eval_theta_joint[_device]  theta [W][n_params] -> lnprob [W]
+ *   psfmc_stretch_run_joint       psfmc_stretch_run's arrays for ONE ensemble of W joint walkers (pos
+ *                                 [W][n_params] ...); accumulate: every field's posterior-image sums get the
+ *                                 current positions (psfmc_get_accumulated_field)
+ * Capacity: each walker is n_fields field records, so n_fields x W <= max_walkers for an evaluation and for
+ * the sampler (its start positions and image sums are n_fields x W records).  Beyond it a call returns
+ * PSFMC_EINVAL naming max_walkers before any device work is enqueued.  Fused back end only (the contexts of
+ * psfmc_ctx_create_fields[_shaped], one field included).
+ */
+int psfmc_set_joint_priors(psfmc_ctx* ctx, int n_params, const int* family, const double* params);
+int psfmc_eval_theta_joint(psfmc_ctx* ctx, int W, const double* theta, double* lnprob);
+/* device buffers, enqueued on `stream` (NULL = the context's stream), not synchronised */
+int psfmc_eval_theta_joint_device(psfmc_ctx* ctx, int W, const double* d_theta, double* d_lnprob, void* stream);
+int psfmc_stretch_run_joint(psfmc_ctx* ctx, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                            const double* z, const double* lz, const int* partner, const double* log_u,
+                            double* chain, double* lnprob_chain, long long* naccepted, int accumulate);
 /* test hook: the derived rows [W][row_len], log-priors [W] and skip flags [W] the device
  * computes for W vectors */
 int psfmc_debug_theta_rows(psfmc_ctx* ctx, int W, const double* theta, double* rows, double* lnprior,

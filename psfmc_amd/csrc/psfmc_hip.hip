@@ -399,6 +399,15 @@ struct psfmc_ctx {
     ThetaLayout* d_field_layouts = nullptr;  // [n_fields] device copies of the layouts (launches that span several fields)
     int* d_field_sides = nullptr;            // [n_fields][2] each field's image sides (ly, lx), for the same launches
     void* d_layout_blob = nullptr;           // one allocation behind the layout's pointers
+    // joint fits (psfmc_set_joint_priors): one parameter vector per walker for every field
+    struct Joint {
+        bool ready = false;                  // set by psfmc_set_joint_priors, cleared by a new field layout
+        ThetaLayout prior{};                 // the joint prior table (n_params columns, no slots)
+        std::vector<ThetaLayout> fields;     // each field's layout with every prior column PRIOR_HOST
+        std::vector<void*> blobs;            // [0]: the prior table's, [1 + f]: field f's copy of its layout blob
+        ThetaLayout* d_fields = nullptr;     // device copies of `fields`
+        double* d_lp = nullptr;              // [max_walkers] joint log-priors (k_joint_prior)
+    } joint;
     double *d_theta = nullptr, *d_extra = nullptr, *d_lnprior = nullptr;
     double* d_acc = nullptr;  // [n_fields][4][S] sums: raw, conv, model variance, PS-only conv
     // fused path: samples are first added to three LINEAR sums per PSF -- raw, raw^2, PS-only raw --
@@ -1496,6 +1505,16 @@ extern "C" int psfmc_field_shape(psfmc_ctx* c, int field, int* ny, int* nx) {
     return PSFMC_OK;
 }
 
+static void free_joint(psfmc_ctx* c) {
+    for (void* b : c->joint.blobs)
+        if (b) (void)hipFree(b);
+    c->joint.blobs.clear();
+    c->joint.fields.clear();
+    if (c->joint.d_fields) (void)hipFree(c->joint.d_fields);
+    c->joint.d_fields = nullptr;
+    c->joint.ready = false;
+}
+
 extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
     if (!c) return PSFMC_OK;
     (void)hipSetDevice(c->device);
@@ -1524,6 +1543,8 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
     }
     for (void* b : c->more_blobs)
         if (b) (void)hipFree(b);
+    free_joint(c);
+    if (c->joint.d_lp) (void)hipFree(c->joint.d_lp);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     for (int i = 0; i < psfmc_ctx::kMaxStreams; ++i)
         if (c->ev_stagger[i]) (void)hipEventDestroy(c->ev_stagger[i]);
@@ -1865,7 +1886,7 @@ static int eval_theta_device(psfmc_ctx* c, int W, const double* d_theta, const d
     launch_theta_prep(c, W, d_theta, d_extra, nullptr, st, StretchIn{});
     RC_TRY(run_pipeline(c, W, c->d_skip, st));
     hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial, c->d_skip,
-                       c->d_lnprior, d_lnprob, W, c->nblk);
+                       c->d_lnprior, d_lnprob, W, c->nblk, 1, 0);
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;
 }
@@ -2040,6 +2061,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
             return fail(PSFMC_EINVAL, "unknown prior family %d for column %d", family[i], i);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
+    c->joint.ready = false;                  // (the joint layouts are copies of the fields' layouts)
     // pack everything into one device allocation (8-byte units)
     const size_t n_int = (size_t)ns + c->n_ps + c->n_sersic + n_params;
     const size_t n_dbl = (size_t)ns + 5 * (size_t)n_params;         // slot constants, pa, pb, pc, pd (0 here), pk
@@ -2113,18 +2135,10 @@ extern "C" int psfmc_set_layout(psfmc_ctx* c, int n_sky, int n_params, const int
 static_assert(kPriorNpar == PSFMC_PRIOR_NPAR && PRIOR_TRUNCNORM == PSFMC_PRIOR_TRUNCNORM &&
               PRIOR_INVGAMMA == PSFMC_PRIOR_INVGAMMA && PRIOR_N_FAMILIES == PSFMC_PRIOR_INVGAMMA + 1,
               "prior codes of include/psfmc_hip.h");
-extern "C" int psfmc_set_priors(psfmc_ctx* c, int field, int n_params, const int* family, const double* params) {
-    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    const bool has = field == 0 ? c->has_layout
-                                : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    if (n_params != L.n_params)
-        return fail(PSFMC_EINVAL, "%d prior columns for a layout of %d", n_params, L.n_params);
-    if (n_params == 0) return PSFMC_OK;
+// the checked device form of a prior table: tab = pa | pb | pc | pd | pk, n_params each
+static int prior_table(int n_params, const int* family, const double* params, std::vector<double>& tab) {
     if (!family || !params) return fail(PSFMC_EINVAL, "NULL prior table");
-    std::vector<double> tab(5 * (size_t)n_params);          // pa | pb | pc | pd | pk
+    tab.assign(5 * (size_t)n_params, 0.0);
     for (int i = 0; i < n_params; ++i) {
         const double* p = params + (size_t)kPriorNpar * i;
         if (family[i] < 0 || family[i] >= PRIOR_N_FAMILIES)
@@ -2136,6 +2150,21 @@ extern "C" int psfmc_set_priors(psfmc_ctx* c, int field, int n_params, const int
         prior_prepare(family[i], p, e);
         for (int j = 0; j < 5; ++j) tab[(size_t)j * n_params + i] = e[j];
     }
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_set_priors(psfmc_ctx* c, int field, int n_params, const int* family, const double* params) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    const bool has = field == 0 ? c->has_layout
+                                : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    if (n_params != L.n_params)
+        return fail(PSFMC_EINVAL, "%d prior columns for a layout of %d", n_params, L.n_params);
+    if (n_params == 0) return PSFMC_OK;
+    std::vector<double> tab;
+    RC_TRY(prior_table(n_params, family, params, tab));
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());                          // no launch may read the tables being replaced
     HIP_TRY(hipMemcpy(const_cast<int*>(L.family), family, n_params * sizeof(int), hipMemcpyHostToDevice));
@@ -2200,7 +2229,7 @@ extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int
     }
     RC_TRY(run_pipeline(c, (int)W, c->d_skip, st));
     hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks((int)W)), dim3(kFinishThreads), 0, st, c->d_partial,
-                       c->d_skip, c->d_lnprior, d_lnprob, (int)W, c->nblk);
+                       c->d_skip, c->d_lnprior, d_lnprob, (int)W, c->nblk, 1, 0);
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;
 }
@@ -2692,7 +2721,7 @@ static void stretch_accept(psfmc_ctx* c, int it, int h, const double* d_newlnp, 
                        c->d_skip, c->d_lnprior, c->nblk, d_newlnp, S.pos, S.lnp, S.q, S.rand + n_rand,
                        S.rand + 2 * n_rand, S.nacc, S.store ? S.chain : nullptr, S.store ? S.lnchain : nullptr,
                        graph_iter ? S.iter : nullptr, it, S.n_iter, half, h, c->layout.n_params, per_field,
-                       acc_out, acc_in, S.partner);
+                       acc_out, acc_in, S.partner, 1, 0);
 }
 
 // a whole iteration's proposals in one launch (StretchIn::spec): 3 half walkers
@@ -2721,7 +2750,7 @@ static int stretch_eval_positions(psfmc_ctx* c, hipStream_t st) {
     launch_theta_prep(c, S.W, S.pos, nullptr, nullptr, st, StretchIn{}, 0, 0, S.F);
     RC_TRY(run_pipeline(c, S.W * S.F, c->d_skip, st));
     hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(S.W * S.F)), dim3(kFinishThreads), 0, st, c->d_partial,
-                       c->d_skip, c->d_lnprior, S.lnp, S.W * S.F, c->nblk);
+                       c->d_skip, c->d_lnprior, S.lnp, S.W * S.F, c->nblk, 1, 0);
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;
 }
@@ -2852,6 +2881,193 @@ extern "C" int psfmc_stretch_run_fields(psfmc_ctx* c, int W, int n_iter, double*
 }
 
 // ---------------------------------------------------------------------------
+// Joint fits: ONE parameter vector per walker for every field of the context (several exposures of one
+// object, some parameters shared and some per field).  A walker is F field records -- field f's copy at
+// f W + w of the per-walker arrays, an ordinary multi-field pass of the pipeline -- all derived from the
+// same row of theta through each field's own slot -> column map.  Its log-posterior is
+// ((ll_0 + ll_1) + ... + ll_{F-1}) + the joint log-prior, which k_joint_prior evaluates once per walker
+// from the joint table (psfmc_set_joint_priors) and every field's axis-ratio rule; the fields' records
+// take it as their `extra` from layouts whose own prior columns are all PRIOR_HOST (joint.fields), so a
+// walker outside the joint support is skipped in every field and no prior is counted twice.
+// ---------------------------------------------------------------------------
+extern "C" int psfmc_set_joint_priors(psfmc_ctx* c, int n_params, const int* family, const double* params) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    for (int f = 0; f < c->n_fields; ++f) {
+        const bool has = f == 0 ? c->has_layout : (size_t)f <= c->more_has.size() && c->more_has[f - 1];
+        const ThetaLayout& L = f == 0 ? c->layout : c->more_layouts[f - 1];
+        if (!has || L.n_params != n_params)
+            return fail(PSFMC_EINVAL, "field %d has no layout of %d columns (psfmc_set_layout[_field] first)", f,
+                        n_params);
+    }
+    if (n_params < 1) return fail(PSFMC_EINVAL, "a joint fit needs at least one free parameter");
+    std::vector<double> tab;
+    RC_TRY(prior_table(n_params, family, params, tab));
+    for (int i = 0; i < n_params; ++i)
+        if (family[i] == PRIOR_HOST)
+            return fail(PSFMC_EINVAL, "column %d: a joint prior needs a device family (PSFMC_PRIOR_UNIFORM ...)", i);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                          // no launch may read the tables being replaced
+    free_joint(c);
+    psfmc_ctx::Joint& J = c->joint;
+    const int P = n_params;
+    // the prior table: family | pa | pb | pc | pd | pk
+    const size_t fam_bytes = ((size_t)P * sizeof(int) + 7) / 8 * 8;
+    void* blob = nullptr;
+    HIP_TRY(hipMalloc(&blob, fam_bytes + tab.size() * sizeof(double)));
+    J.blobs.push_back(blob);
+    HIP_TRY(hipMemcpy(blob, family, P * sizeof(int), hipMemcpyHostToDevice));
+    double* dp = reinterpret_cast<double*>(static_cast<unsigned char*>(blob) + fam_bytes);
+    HIP_TRY(hipMemcpy(dp, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    J.prior = ThetaLayout{};
+    J.prior.n_params = P;
+    J.prior.family = static_cast<const int*>(blob);
+    J.prior.pa = dp; J.prior.pb = dp + P; J.prior.pc = dp + 2 * P; J.prior.pd = dp + 3 * P; J.prior.pk = dp + 4 * P;
+    // each field's layout blob (set_layout_impl: int tables from slot_col on, then the double tables) copied,
+    // its prior families set to PRIOR_HOST
+    const int ns = n_slots(c->layout.n_sky, c->n_ps, c->n_sersic);
+    const size_t int_bytes = (((size_t)ns + c->n_ps + c->n_sersic + P) * sizeof(int) + 7) / 8 * 8;
+    const size_t bytes = int_bytes + ((size_t)ns + 5 * (size_t)P) * sizeof(double);
+    for (int f = 0; f < c->n_fields; ++f) {
+        const ThetaLayout& L = f == 0 ? c->layout : c->more_layouts[f - 1];
+        const unsigned char* old_base = reinterpret_cast<const unsigned char*>(L.slot_col);
+        void* copy = nullptr;
+        HIP_TRY(hipMalloc(&copy, bytes));
+        J.blobs.push_back(copy);
+        unsigned char* base = static_cast<unsigned char*>(copy);
+        HIP_TRY(hipMemcpy(copy, old_base, bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemset(base + (reinterpret_cast<const unsigned char*>(L.family) - old_base), 0, P * sizeof(int)));
+        auto at = [&](const void* p) { return base + (static_cast<const unsigned char*>(p) - old_base); };
+        ThetaLayout G = L;
+        G.slot_col = reinterpret_cast<const int*>(at(L.slot_col));
+        G.ps_method = reinterpret_cast<const int*>(at(L.ps_method));
+        G.sersic_deg = reinterpret_cast<const int*>(at(L.sersic_deg));
+        G.family = reinterpret_cast<const int*>(at(L.family));
+        G.slot_const = reinterpret_cast<const double*>(at(L.slot_const));
+        G.pa = reinterpret_cast<const double*>(at(L.pa));
+        G.pb = reinterpret_cast<const double*>(at(L.pb));
+        G.pc = reinterpret_cast<const double*>(at(L.pc));
+        G.pd = reinterpret_cast<const double*>(at(L.pd));
+        G.pk = reinterpret_cast<const double*>(at(L.pk));
+        J.fields.push_back(G);
+    }
+    HIP_TRY(hipMalloc(&J.d_fields, (size_t)c->n_fields * sizeof(ThetaLayout)));
+    HIP_TRY(hipMemcpy(J.d_fields, J.fields.data(), (size_t)c->n_fields * sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    if (!J.d_lp) HIP_TRY(hipMalloc(&J.d_lp, (size_t)c->max_walkers * sizeof(double)));
+    J.ready = true;
+    return PSFMC_OK;
+}
+
+// W walkers' vectors d_theta [W][P] -> the prep records, skip flags and log-priors of their F field
+// records (field-major).  d_extra: the joint log-priors (k_joint_prior), or nullptr where only the records
+// are needed (posterior-image sums)
+static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
+                                    hipStream_t st) {
+    const int F = c->n_fields;
+    const FieldSegs segs = F > 1 ? FieldSegs{c->joint.d_fields, c->d_field_sides, c->n_psf_field, 1}
+                                 : FieldSegs{nullptr, nullptr, 0, 0};
+    c->prep_tabs_valid = false;
+    hipLaunchKernelGGL(k_theta_prep, dim3((W + kThetaThreads - 1) / kThetaThreads, F),
+                       dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
+                       c->joint.fields[0], d_theta, d_extra, nullptr, c->d_prep, c->d_lnprior, c->d_skip, W,
+                       c->wraps[0].ly, c->wraps[0].lx, c->d_rho, StretchIn{}, 0, segs);
+    launch_pow_tables(c, W * F, 0, c->d_skip, st);
+}
+
+static int joint_check(psfmc_ctx* c, int W) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (!c->joint.ready)
+        return fail(PSFMC_EINVAL, "psfmc_set_joint_priors has not been called since the last field layout");
+    if (W < 0 || (long long)W * c->n_fields > c->max_walkers)
+        return fail(PSFMC_EINVAL, "n_fields x W = %d x %d exceeds max_walkers=%d", c->n_fields, W, c->max_walkers);
+    return PSFMC_OK;
+}
+
+static int eval_theta_joint(psfmc_ctx* c, int W, const double* d_theta, double* d_lnprob, hipStream_t st) {
+    const int F = c->n_fields;
+    hipLaunchKernelGGL(k_joint_prior, dim3((W + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields, F,
+                       d_theta, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp, W);
+    launch_theta_prep_joint(c, W, d_theta, c->joint.d_lp, st);
+    RC_TRY(run_pipeline(c, W * F, c->d_skip, st));
+    hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       c->d_skip, c->d_lnprior, d_lnprob, W, c->nblk, F, W);
+    HIP_TRY(hipGetLastError());
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_eval_theta_joint_device(psfmc_ctx* c, int W, const double* d_theta, double* d_lnprob,
+                                             void* stream) {
+    RC_TRY(joint_check(c, W));
+    if (W == 0) return PSFMC_OK;
+    if (!d_theta || !d_lnprob) return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    return eval_theta_joint(c, W, d_theta, d_lnprob, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int psfmc_eval_theta_joint(psfmc_ctx* c, int W, const double* theta, double* lnprob) {
+    RC_TRY(joint_check(c, W));
+    if (W == 0) return PSFMC_OK;
+    if (!theta || !lnprob) return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+    RC_TRY(eval_theta_joint(c, W, c->d_theta, c->d_like, st));
+    HIP_TRY(hipMemcpyAsync(lnprob, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PSFMC_OK;
+}
+
+// The stretch-move sampler of psfmc_stretch_run for ONE ensemble of W joint walkers: every half-step's
+// proposals (formed by k_joint_prior) are F W / 2 field records in one pipeline pass; k_stretch_finish sums
+// each proposal's fields.  Plain half-steps only (no whole-iteration launches, no hipGraph): the chain is
+// the one of psfmc_stretch_run's rules either way.  accumulate: after every iteration, each field's
+// posterior-image sums get the current positions mapped to that field.
+extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
+                                       int lnprob_valid, const double* z, const double* lz, const int* partner,
+                                       const double* log_u, double* chain, double* lnprob_chain,
+                                       long long* naccepted, int accumulate) {
+    RC_TRY(joint_check(c, W));
+    if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
+    if (n_iter < 0 || !pos || !lnprob || !naccepted || (n_iter && (!z || !lz || !partner || !log_u)))
+        return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    const int F = c->n_fields, half = W / 2, P = c->layout.n_params;
+    hipStream_t st = c->stream;
+    psfmc_ctx::Stretch& S = c->stretch;
+    RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
+                          chain != nullptr, st));
+    S.spec = false;
+    int rc = PSFMC_OK;
+    if (!lnprob_valid) rc = eval_theta_joint(c, W, S.pos, S.lnp, st);
+    if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
+    const size_t n_rand = (size_t)n_iter * W;                  // per random array (S.rand: z | lz | log u)
+    for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
+        for (int h = 0; h < 2 && rc == PSFMC_OK; ++h) {
+            hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
+                               c->joint.d_fields, F, nullptr, S.pos, S.q, S.rand, S.partner, it, half, h,
+                               c->joint.d_lp, half);
+            launch_theta_prep_joint(c, half, S.q, c->joint.d_lp, st);
+            rc = run_pipeline(c, half * F, c->d_skip, st);
+            if (rc != PSFMC_OK) break;
+            hipLaunchKernelGGL(k_stretch_finish, dim3(finish_blocks(half)), dim3(kFinishThreads), 0, st, c->d_partial,
+                               c->d_skip, c->d_lnprior, c->nblk, nullptr, S.pos, S.lnp, S.q, S.rand + n_rand,
+                               S.rand + 2 * n_rand, S.nacc, S.store ? S.chain : nullptr,
+                               S.store ? S.lnchain : nullptr, nullptr, it, n_iter, half, h, P, (size_t)0, nullptr,
+                               nullptr, S.partner, F, half);
+        }
+        if (rc == PSFMC_OK && accumulate) {
+            launch_theta_prep_joint(c, W, S.pos, nullptr, st);
+            rc = accumulate_from_prep(c, W * F, st, 0, F, W);
+        }
+    }
+    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
+    (void)hipStreamSynchronize(st);
+    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
+    S.open = false;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
 // The same sampler, one half-step at a time, for walkers sharded over several GPUs: every
 // rank holds ALL walkers and the same random numbers, evaluates the log-posterior of ITS
 // block of each half-step's proposals, the blocks are all-gathered by the caller (RCCL /
@@ -2892,7 +3108,7 @@ extern "C" int psfmc_stretch_half_eval(psfmc_ctx* c, int it, int h, int lo, int 
         RC_TRY(run_pipeline(c, n, c->d_skip, st, lo));
         hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st,
                            c->d_partial + (size_t)lo * c->nblk, c->d_skip + lo, c->d_lnprior + lo,
-                           d_newlnp_block, n, c->nblk);
+                           d_newlnp_block, n, c->nblk, 1, 0);
     }
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;

@@ -338,6 +338,15 @@ __device__ inline double theta_slot(const ThetaLayout& L, const double* __restri
     return col >= 0 ? theta[col] : L.slot_const[s];
 }
 
+// Sersic axis-ratio constraint (Sersic.py:41-45): -inf if some component has reff_b > reff, else lp
+__device__ inline double theta_axis_ratio(const ThetaLayout& L, const double* __restrict__ theta, double lp) {
+    for (int k = 0; k < L.n_sersic; ++k) {
+        const int s0 = L.n_sky + 3 * L.n_ps + 7 * k;
+        if (theta_slot(L, theta, s0 + 4) > theta_slot(L, theta, s0 + 3)) lp = -INFINITY;
+    }
+    return lp;
+}
+
 __device__ inline double theta_log_prior(const ThetaLayout& L, const double* __restrict__ theta, double extra) {
     double lp = extra;
     for (int p = 0; p < L.n_params; ++p) {
@@ -347,12 +356,7 @@ __device__ inline double theta_log_prior(const ThetaLayout& L, const double* __r
         if (fam <= PRIOR_RANDINT) lp += prior_logp(fam, x, L.pa[p], L.pb[p], L.pc[p], L.pk[p]);
         else lp += prior_logp_more(fam, x, L.pa[p], L.pb[p], L.pc[p], L.pd[p], L.pk[p]);
     }
-    // Sersic axis-ratio constraint (Sersic.py:41-45)
-    for (int k = 0; k < L.n_sersic; ++k) {
-        const int s0 = L.n_sky + 3 * L.n_ps + 7 * k;
-        if (theta_slot(L, theta, s0 + 4) > theta_slot(L, theta, s0 + 3)) lp = -INFINITY;
-    }
-    return lp;
+    return theta_axis_ratio(L, theta, lp);
 }
 
 // row pieces (the caller-row layout of include/psfmc_hip.h)
@@ -431,6 +435,7 @@ struct FieldSegs {
     const ThetaLayout* layouts;   // device array [gridDim.y], or nullptr: one field, the layout passed by value
     const int* sides;             // device array [gridDim.y][2] (fields may differ in image size)
     int psf_stride;
+    int shared_theta;             // 1 (joint fits): every field reads the same W vectors of theta / extra
 };
 
 __device__ inline double stretch_point(double s, double c, double z) {
@@ -473,8 +478,9 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
         ny = segs.sides[2 * f];
         nx = segs.sides[2 * f + 1];
         const size_t first = (size_t)f * W;             // its first walker in the per-walker arrays
-        if (theta) theta += first * G.n_params;
-        if (extra) extra += first;
+        const size_t first_in = segs.shared_theta ? 0 : first;
+        if (theta) theta += first_in * G.n_params;
+        if (extra) extra += first_in;
         if (rows) rows += first * row_len(G.n_ps, G.n_sersic);
         prep += first * prep_len(G.n_ps, G.n_sersic);
         lnprior += first;
@@ -646,24 +652,31 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
 #endif
 
 // lnprob = loglike + lnprior, non-finite likelihood -> -inf (models.py:238-243); all
-// lanes of the walker's wave get the value
+// lanes of the walker's wave get the value.
+// Joint fits (nf > 1 fields, records of field f at w + f fstride): loglike = ((ll_0 + ll_1) + ...) +
+// ll_{nf-1}, each ll_f the one-field sum; -inf if any field's record is skipped.  lnprior[w] (field 0's
+// record) is the joint log-prior.
 __device__ inline double walker_lnprob(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
-                                       const double* __restrict__ lnprior, int nblk, int w, int lane) {
-    if (skip[w]) return -INFINITY;
-    const double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+                                       const double* __restrict__ lnprior, int nblk, int w, int lane,
+                                       int nf = 1, int fstride = 0) {
+    for (int f = 0; f < nf; ++f)
+        if (skip[w + (size_t)f * fstride]) return -INFINITY;
+    double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+    for (int f = 1; f < nf; ++f)
+        ll += -0.5 * wave_sum_partials(partial + (w + (size_t)f * fstride) * nblk, nblk, lane);
     const bool fin = ll == ll && fabs(ll) != INFINITY;
     return fin ? ll + lnprior[w] : -INFINITY;
 }
 
-// one wave per walker (launch: finish_blocks(W) x kFinishThreads)
+// one wave per walker (launch: finish_blocks(W) x kFinishThreads); nf, fstride: see walker_lnprob
 #if PSFMC_PART == 0          /* not a template: defined in the API part only */
 __global__ void k_finish_posterior(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
                                    const double* __restrict__ lnprior, double* __restrict__ lnprob,
-                                   int W, int nblk) {
+                                   int W, int nblk, int nf, int fstride) {
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
     if (w >= W) return;
-    const double lp = walker_lnprob(partial, skip, lnprior, nblk, w, lane);
+    const double lp = walker_lnprob(partial, skip, lnprior, nblk, w, lane, nf, fstride);
     if (lane == 0) lnprob[w] = lp;
 }
 #endif
@@ -678,6 +691,8 @@ __global__ void k_finish_posterior(const double* __restrict__ partial, const uin
 // `newlnp_in` (multi-GPU): the proposals' log-posteriors were evaluated in blocks on several
 // ranks and gathered; they are read from it instead of being summed here -- the values are the
 // ones k_finish_posterior produced from the same partial sums, so the chain is the same bit for bit.
+// Joint fits (psfmc_stretch_run_joint; one ensemble, gridDim.y = 1): each proposal is nf field records,
+// summed as k_finish_posterior sums them (nf, fstride = half).
 // ---------------------------------------------------------------------------
 #if PSFMC_PART == 0          /* not a template: defined in the API part only */
 __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
@@ -689,7 +704,8 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
                                  double* __restrict__ chain, double* __restrict__ lnchain,
                                  const int* __restrict__ d_iter, int it_val, int n_iter, int half, int h,
                                  int P, size_t rand_stride, uint8_t* __restrict__ acc_out,
-                                 const uint8_t* __restrict__ acc_in, const int* __restrict__ partner) {
+                                 const uint8_t* __restrict__ acc_in, const int* __restrict__ partner,
+                                 int nf, int fstride) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
@@ -717,7 +733,7 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
     // partner's outcome selects -- half + w if the partner moved, 2 half + w if it stayed
     int row = w;
     if (acc_in) row = w + (acc_in[partner[off + w]] ? half : 2 * half);
-    const double newlnp = newlnp_in ? newlnp_in[w] : walker_lnprob(partial, skip, lnprior, nblk, row, lane);
+    const double newlnp = newlnp_in ? newlnp_in[w] : walker_lnprob(partial, skip, lnprior, nblk, row, lane, nf, fstride);
     const int g = h * half + w;
     double lp = lnprob[g];
     const double diff = (lz[off + w] + newlnp) - lp;
@@ -741,6 +757,41 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
         }
         if (chain) lnchain[(size_t)g * n_iter + it] = lp;
     }
+}
+#endif
+
+// ---------------------------------------------------------------------------
+// joint fits (psfmc_eval_theta_joint, psfmc_stretch_run_joint): the joint log-prior of W parameter vectors,
+// ONCE per walker -- every column's prior from the joint table J (J.n_sersic = 0: no slots), then the
+// Sersic axis-ratio rule of every field from that field's own slots (fields[f]).  k_theta_prep then
+// takes it as `extra`, with every field's own prior columns PRIOR_HOST, so that a walker outside the joint
+// support is skipped in every field.  With pos set, the vectors are the stretch proposals of half h at
+// iteration it, formed here (stretch_point: the roundings of k_theta_prep's proposals) and written to q.
+// One lane per walker (launch: ceil(W / 64) x 64).
+// ---------------------------------------------------------------------------
+#if PSFMC_PART == 0          /* not a template: defined in the API part only */
+__global__ void __launch_bounds__(64)
+k_joint_prior(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields, const double* __restrict__ theta,
+              const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
+              const int* __restrict__ partner, int it, int half, int h, double* __restrict__ lnprior, int W) {
+    const int w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= W) return;
+    const int P = J.n_params;
+    const double* th;
+    if (!pos) {
+        th = theta + (size_t)w * P;
+    } else {
+        const size_t off = ((size_t)it * 2 + h) * half;
+        const double* s = pos + (size_t)(h * half + w) * P;
+        const double* c = pos + (size_t)((1 - h) * half + partner[off + w]) * P;
+        const double zz = z[off + w];
+        double* qw = q + (size_t)w * P;
+        for (int d = 0; d < P; ++d) qw[d] = stretch_point(s[d], c[d], zz);
+        th = qw;
+    }
+    double lp = theta_log_prior(J, th, 0.0);
+    for (int f = 0; f < n_fields; ++f) lp = theta_axis_ratio(fields[f], th, lp);
+    lnprior[w] = lp;
 }
 #endif
 

@@ -17,6 +17,7 @@ _COMMENTS = {'MCITER': 'number of retained samples',
              'MCCHAINS': 'number of walkers run',
              'MCWALKRS': 'number of walkers run',
              'MCCONVRG': 'Has MCMC sampler converged?',
+             'MCFIELDS': 'number of fields fitted jointly',
              'MCACCEPT': 'Acceptance fraction (avg of all walkers)',
              'MAPWLKR': 'Walker index of maximum posterior model',
              'MAPSAMP': 'Sample index of maximum posterior model',

@@ -200,6 +200,14 @@ def load_library():
     llp = ctypes.POINTER(ctypes.c_longlong)
     lib.psfmc_stretch_run_fields.restype = ci
     lib.psfmc_stretch_run_fields.argtypes = lib.psfmc_stretch_run.argtypes
+    lib.psfmc_set_joint_priors.restype = ci
+    lib.psfmc_set_joint_priors.argtypes = [vp, ci, ip, _c_double_p]
+    lib.psfmc_eval_theta_joint.restype = ci
+    lib.psfmc_eval_theta_joint.argtypes = [vp, ci, _c_double_p, _c_double_p]
+    lib.psfmc_eval_theta_joint_device.restype = ci
+    lib.psfmc_eval_theta_joint_device.argtypes = [vp, ci, vp, vp, vp]
+    lib.psfmc_stretch_run_joint.restype = ci
+    lib.psfmc_stretch_run_joint.argtypes = lib.psfmc_stretch_run.argtypes
     lib.psfmc_accumulate_theta_field.restype = ci
     lib.psfmc_accumulate_theta_field.argtypes = [vp, ci, ci, _c_double_p]
     lib.psfmc_reset_accumulated_field.restype = ci
@@ -792,6 +800,53 @@ class FieldSetContext(object):
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
         return pos, lnp, chain, lnchain
 
+    # -- joint fits: one parameter vector per walker for every field (include/psfmc_hip.h psfmc_*_joint) --
+    def set_joint_priors(self, family, params):
+        """The joint prior table (every field's layout registered first, with n_params joint columns)."""
+        fam, tab, fp, tp = _prior_table(family, params)
+        self._check(self._lib.psfmc_set_joint_priors(self._ctx, len(fam), fp, tp))
+
+    def logpost_theta_joint(self, theta):
+        """[W, n_params] joint vectors -> [W] joint log-posteriors; n_fields x W <= max_walkers."""
+        theta = _f64(theta)
+        if theta.ndim != 2 or theta.shape[1] != self.n_params:
+            raise ValueError('theta must be [W, {}]'.format(self.n_params))
+        out = np.empty(len(theta))
+        if len(theta):
+            self._check(self._lib.psfmc_eval_theta_joint(self._ctx, len(theta), _dp(theta), _dp(out)))
+        return out
+
+    def logpost_theta_joint_device(self, n_w, d_theta, d_out, stream=None):
+        self._check(self._lib.psfmc_eval_theta_joint_device(
+            self._ctx, int(n_w), ctypes.c_void_p(d_theta), ctypes.c_void_p(d_out),
+            ctypes.c_void_p(stream) if stream else None))
+
+    def stretch_run_joint(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True, accumulate=False):
+        """`Context.stretch_run` for ONE ensemble of joint walkers (psfmc_stretch_run_joint): pos [W, P],
+        lnprob [W] or None, z / lz / log_u / partner [n_iter, 2, W/2], naccepted int64 [W] (updated).
+        accumulate: every field's posterior sums get the positions after every iteration."""
+        pos = np.array(pos, dtype=np.float64, order='C')
+        n_w, n_p = pos.shape
+        n_iter = int(np.shape(z)[0])
+        have = lnprob is not None
+        lnp = np.array(lnprob, dtype=np.float64) if have else np.empty(n_w)
+        z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_w // 2) for a in (z, lz, log_u))
+        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
+        if naccepted.dtype != np.int64 or naccepted.shape != (n_w,) or not naccepted.flags.c_contiguous:
+            raise ValueError('naccepted must be a contiguous int64 [W]')
+        chain = np.empty((n_w, n_iter, n_p)) if store and n_iter else None
+        lnchain = np.empty((n_w, n_iter)) if store and n_iter else None
+        self._check(self._lib.psfmc_stretch_run_joint(
+            self._ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(z), _dp(lz),
+            partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(log_u),
+            _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
+            naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
+        return pos, lnp, chain, lnchain
+
+    def joint_view(self):
+        """The interface a `JointModel` and `DeviceEnsembleSampler` use: `JointView`."""
+        return JointView(self)
+
     def accumulate_theta(self, field, theta):
         """Add the images of [W, P] raw parameter vectors of one field to its posterior sums."""
         theta = _f64(theta)
@@ -816,9 +871,11 @@ class FieldSetContext(object):
         else:
             self._check(self._lib.psfmc_reset_accumulated_field(self._ctx, int(field)))
 
-    def view(self, field):
-        """The part of `Context`'s interface a `MultiComponentModel` uses, for ONE field of this context."""
-        return FieldView(self, field)
+    def view(self, field, columns=None):
+        """The part of `Context`'s interface a `MultiComponentModel` uses, for ONE field of this context.
+        columns (joint fits): the joint column of each of the field's own columns -- the view takes the
+        field's own vectors and places them there."""
+        return FieldView(self, field, columns)
 
     def loglike(self, field, rows, skip=None):
         """[W] log-likelihoods of derived rows of one field (`Context.loglike` for a field of this context)."""
@@ -859,10 +916,20 @@ class FieldView(object):
 
     IMAGE_KINDS = Context.IMAGE_KINDS
 
-    def __init__(self, owner, field):
+    def __init__(self, owner, field, columns=None):
         self.owner, self.field = owner, int(field)
         self.shape, self.n_psf = tuple(owner.shapes[self.field]), owner.n_psf
         self.max_walkers, self.device = owner.max_walkers, owner.device
+        self.columns = None if columns is None else np.asarray(columns, dtype=np.int64)
+
+    def _own_to_layout(self, theta):
+        """The field's own [W, P_f] vectors as the [W, n_params] vectors its layout reads."""
+        if self.columns is None:
+            return theta
+        theta = _f64(theta)
+        full = np.zeros((theta.shape[0], self.owner.n_params))
+        full[:, self.columns] = theta
+        return full
 
     def close(self):                       # the FieldSet owns the context
         pass
@@ -874,6 +941,9 @@ class FieldView(object):
         return self.owner.get_option(key)
 
     def logpost_theta(self, theta, extra_lnprior=None):
+        if self.columns is not None:
+            raise NotImplementedError('field {} is part of a joint fit: its log-posterior is the JointModel\'s '
+                                      '(log_posterior_batch)'.format(self.field))
         if extra_lnprior is not None:
             raise ValueError('a FieldSet evaluates priors on the GPU only')
         thetas = [None] * self.owner.n_fields
@@ -901,13 +971,59 @@ class FieldView(object):
         raise AttributeError(name)
 
     def accumulate_theta(self, theta):
-        self.owner.accumulate_theta(self.field, theta)
+        self.owner.accumulate_theta(self.field, self._own_to_layout(theta))
 
     def accumulated(self):
         return self.owner.accumulated(self.field)
 
     def reset_accumulated(self):
         self.owner.reset_accumulated(self.field)
+
+
+class JointView(object):
+    """A `FieldSetContext` whose fields are fitted jointly (`models.JointModel`), behind the part of a
+    one-field `Context`'s interface that `DeviceEnsembleSampler` uses: `stretch_run` is the joint run
+    (psfmc_stretch_run_joint), `logpost_theta` the joint log-posterior."""
+
+    IMAGE_KINDS = Context.IMAGE_KINDS
+
+    def __init__(self, owner):
+        self.owner = owner
+        self.max_walkers, self.device = owner.max_walkers, owner.device
+
+    def close(self):                       # the JointModel owns the context
+        pass
+
+    def set_option(self, key, value):
+        self.owner.set_option(key, value)
+
+    def get_option(self, key):
+        return self.owner.get_option(key)
+
+    def logpost_theta(self, theta, extra_lnprior=None):
+        if extra_lnprior is not None:
+            raise ValueError('a joint fit evaluates priors on the GPU only')
+        return self.owner.logpost_theta_joint(theta)
+
+    def stretch_run(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True, accumulate=False):
+        return self.owner.stretch_run_joint(pos, lnprob, z, lz, partner, log_u, naccepted, store=store,
+                                            accumulate=accumulate)
+
+    def accumulated(self, field):
+        return self.owner.accumulated(field)
+
+    def reset_accumulated(self, field=None):
+        self.owner.reset_accumulated(field)
+
+    def __getattr__(self, name):
+        # the half-step API of sharded runs and the one-field raw-sum exchange have no joint form
+        if callable(getattr(Context, name, None)):
+            def _unsupported(*args, **kwargs):
+                raise NotImplementedError(
+                    "'{}' is not available for a joint fit: it runs on one GPU (no sharding over ranks) "
+                    "and its images are per field (JointModel.field_models)".format(name))
+            return _unsupported
+        raise AttributeError(name)
 
 
 class ContextGroup(object):

@@ -13,8 +13,8 @@ from warnings import warn
 import numpy as np
 
 from .analysis import check_convergence_autocorr, save_posterior_images, default_filetypes
-from .database import save_database, load_database
-from .models import MultiComponentModel
+from .database import Table, save_database, load_database
+from .models import JointModel, MultiComponentModel
 from .sampler import EnsembleSampler, DeviceEnsembleSampler
 from .utils import print_progress
 
@@ -41,6 +41,38 @@ def _rank_group(group, device):
             return None
         raise
     return None if ranks.single else ranks
+
+
+def _burn_and_sample(sampler, model, param_vec, burn, iterations, max_iterations, convergence_check,
+                     host_acc, device_acc, quiet):
+    """The reference's sampling flow (psfMC/fitting.py:56-86): burn-in, reset, sampling with posterior
+    images accumulated (on the device inside the sampler if `device_acc`, else from the current positions
+    after every iteration if `host_acc`), until `convergence_check` passes or `max_iterations` rounds.
+    Returns whether it converged."""
+    lnprob = None
+    for step, result in enumerate(sampler.sample(param_vec, iterations=burn)):
+        param_vec, lnprob = result[0], result[1]
+        sampler.clear_blobs()
+        if not quiet:
+            print_progress(step, burn, 'Burning')
+    sampler.reset()
+
+    if device_acc:              # images are summed inside the device sampling loop
+        sampler.accumulate = True
+    for sampling_iter in range(max_iterations):
+        for step, result in enumerate(sampler.sample(param_vec, lnprob0=lnprob,
+                                                     iterations=iterations)):
+            param_vec, lnprob = result[0], result[1]
+            if host_acc and not device_acc:   # current positions, summed on the GPU
+                model.accumulate_samples(param_vec)
+            sampler.clear_blobs()
+            if not quiet:
+                print_progress(step, iterations, 'Sampling')
+        if convergence_check(sampler):
+            return True
+        warn('Not yet converged after {:d} iterations:'.format((sampling_iter + 1) * iterations))
+        convergence_check(sampler, verbose=0 if quiet else 1)
+    return False
 
 
 def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes, iterations=0,
@@ -112,32 +144,8 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
         param_vec = mc_model.init_params_from_priors(chains)
         if ranks is not None:
             param_vec = ranks.broadcast_object(param_vec)
-        lnprob = None
-        for step, result in enumerate(sampler.sample(param_vec, iterations=burn)):
-            param_vec, lnprob = result[0], result[1]
-            sampler.clear_blobs()
-            if not quiet:
-                print_progress(step, burn, 'Burning')
-        sampler.reset()
-
-        converged = False
-        if device_acc:              # images are summed inside the device sampling loop
-            sampler.accumulate = True
-        for sampling_iter in range(max_iterations):
-            for step, result in enumerate(sampler.sample(param_vec, lnprob0=lnprob,
-                                                         iterations=iterations)):
-                param_vec, lnprob = result[0], result[1]
-                if accumulate and not device_acc and writer:   # current positions, summed on the GPU
-                    mc_model.accumulate_samples(param_vec)
-                sampler.clear_blobs()
-                if not quiet:
-                    print_progress(step, iterations, 'Sampling')
-            if convergence_check(sampler):
-                converged = True
-                break
-            warn('Not yet converged after {:d} iterations:'.format((sampling_iter + 1) * iterations))
-            convergence_check(sampler, verbose=0 if quiet else 1)
-
+        converged = _burn_and_sample(sampler, mc_model, param_vec, burn, iterations, max_iterations,
+                                     convergence_check, accumulate and writer, device_acc, quiet)
         if device_acc:
             mc_model.reduce_accumulated(ranks)
         meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
@@ -258,3 +266,67 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
     for m, db, out in zip(models, databases, output_names):
         save_posterior_images(m, db, output_name=out, filetypes=write_fits)
     return list(zip(models, databases))
+
+
+def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=default_filetypes, iterations=0,
+                     burn=0, chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
+                     device=0, random_state=None, accumulate=True, quiet=False):
+    """`model_galaxy_mcmc` for ONE model fitted jointly to several exposures of the same object
+    (`models.JointModel`: each field its own data, PSFs, constants and zeropoint; the parameters not named
+    in `per_field` shared).  The reference's flow -- burn-in, reset, sampling with posterior images
+    accumulated, convergence loop, metadata -- on the device sampler, one ensemble of `chains` walkers
+    (default 2 P_joint + 2) in the joint parameters.  The reference has no counterpart (one model file per
+    process, psfMC/fitting.py:13-113).
+
+    Outputs: ONE trace database `<output_name>_db.fits` with the joint columns (metadata MCFIELDS = number
+    of fields), and each field's posterior images `<output_name>_f<k>_<type>.fits` at that field's shape
+    (what `save_posterior_images` writes for the field's model and the database's rows mapped to the
+    field's own parameter names).  An existing database skips sampling.  Returns (JointModel, database)."""
+    if output_name is None:
+        output_name = 'out_joint_' + str(model_files[0]).replace('.py', '')
+    joint = model_files if isinstance(model_files, JointModel) else None
+    if joint is None:
+        # room for the image recomputation's batches (as model_galaxy_mcmc), F field records per walker
+        n_f = len(model_files)
+        joint = JointModel(model_files, per_field=per_field, device=device,
+                           max_walkers=n_f * max(chains or 0, 1024))
+    n_f = len(joint.field_models)
+    if chains is None:
+        chains = 2 * joint.num_params + 2
+    if chains < 2 or chains % 2:
+        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
+                         'two halves'.format(chains))
+    if chains * n_f > joint._max_walkers:
+        raise ValueError('{} fields x {} chains exceed max_walkers={}'.format(n_f, chains, joint._max_walkers))
+    sampler = DeviceEnsembleSampler(chains, joint)
+    if random_state is not None:
+        if isinstance(random_state, (int, np.integer)):
+            random_state = np.random.RandomState(int(random_state)).get_state()
+        sampler.random_state = random_state
+
+    db_name = output_name + '_db.fits'
+    if not os.path.exists(db_name):
+        param_vec = joint.init_params_from_priors(chains)
+        converged = _burn_and_sample(sampler, joint, param_vec, burn, iterations, max_iterations,
+                                     convergence_check, False, accumulate, quiet)
+        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
+                            ('MCCONVRG', bool(converged)),
+                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f)])
+        database = save_database(sampler, joint, db_name, meta_dict=meta)
+    else:
+        if not quiet:
+            print('Database already contains sampled chains, skipping sampling')
+        database = load_database(db_name)
+
+    theta = database.param_matrix(joint.param_names)
+    for f, m in enumerate(joint.field_models):
+        own = joint.field_theta(theta, f)
+        cols, pos = OrderedDict(), 0
+        for name, width in zip(m.param_names, m.param_lens):
+            cols[name] = own[:, pos:pos + width]
+            pos += width
+        for name in ('lnprobability', 'walker', 'sample'):
+            cols[name] = database[name]
+        save_posterior_images(m, Table(cols, database.meta), output_name='{}_f{}_{{}}'.format(output_name, f),
+                              filetypes=write_fits)
+    return joint, database

@@ -180,11 +180,12 @@ class MultiComponentModel(object):
             self._register_layout(self._engine)
         return self._engine
 
-    def _register_layout(self, eng):
+    def _register_layout(self, eng, columns=None, n_params=None):
         """Hand the parameter layout and the priors to the library so that raw
         emcee vectors can be evaluated without host arithmetic.  Priors of
         families the library does not know, and parameters scipy rejects, stay on the host
-        (`_host_priors`)."""
+        (`_host_priors`).  Joint fits (`JointModel`): this model's column c is column columns[c] of
+        n_params joint columns, and its prior table is left to the joint one (psfmc_set_joint_priors)."""
         col_of = {}                                   # (component id, attr, element) -> column
         family = np.zeros(self.num_params, dtype=np.int32)
         params = np.zeros((self.num_params, engine.PRIOR_NPAR))
@@ -221,6 +222,14 @@ class MultiComponentModel(object):
                 add(c, name)
             add(c, 'xy', 0); add(c, 'xy', 1)
         add(self.config.psf_selector, 'psf_index')
+        if columns is not None:
+            slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
+            zero = np.zeros(n_params)
+            eng.set_layout(len(self._sky), n_params, slot_col, slot_const,
+                           [SHIFT_METHODS[c.shift_method] for c in self._ps],
+                           [int(bool(c.angle_degrees)) for c in self._sersic],
+                           self.config.mag_zeropoint, np.zeros(n_params, dtype=np.int32), zero, zero, zero)
+            return
         # families 0-4 as psfmc_set_layout takes them, the newer ones as host columns there; the full
         # table follows only where a newer family exists (a model of families 1-4 makes the same calls
         # as before they did)
@@ -569,3 +578,267 @@ class FieldSet(object):
         for m in self.models:
             m._engine = None               # (views of the context just closed)
 
+
+
+def _same_prior(a, b):
+    """The same scipy family with the same args and kwds (vector arguments equal element by element)."""
+    ra, rb = getattr(a, 'rv_frozen', None), getattr(b, 'rv_frozen', None)
+    if ra is None or rb is None:
+        return a is b
+    if ra.dist.name != rb.dist.name or len(ra.args) != len(rb.args) or set(ra.kwds) != set(rb.kwds):
+        return False
+    same = lambda x, y: np.shape(x) == np.shape(y) and np.array_equal(np.asarray(x), np.asarray(y))
+    return (all(same(x, y) for x, y in zip(ra.args, rb.args)) and
+            all(same(ra.kwds[k], rb.kwds[k]) for k in ra.kwds))
+
+
+class JointModel(object):
+    """ONE model fitted jointly to several exposures of the same object (dithered frames, visits,
+    filters): every field keeps its own data, PSFs, noise map, constants and zeropoint, and the
+    log-posterior of a joint vector theta is
+
+        ((ll_0(theta_0) + ll_1(theta_1)) + ... + ll_{F-1}(theta_{F-1})) + lnprior(theta)
+
+    with theta_f field f's own vector taken from theta's columns.  The reference has no counterpart (one
+    model file per process, psfMC/fitting.py:13-113).
+
+    models     F >= 1 model files or `MultiComponentModel`s with the same component lists (so the same
+               `param_names` / `param_lens`) and the same number of PSFs; image and PSF sizes may differ
+    per_field  names of `param_names` that each field fits on its own: each becomes F column blocks
+               `<name>_f<k>`.  Every other parameter is SHARED (one block, the same value in every field,
+               and the same prior in every field).  A PSF index is always per field.
+
+    Joint column order: field 0's `param_names` in order, a shared name once, a per-field name as its F
+    blocks in field order.  Every joint column's prior counts once; the Sersic axis-ratio rule applies in
+    every field.  Every prior needs a device form.  The linking is checked here without touching the GPU;
+    the shared context (`engine.FieldSetContext`, fused back end, f64 storage) is made on first use.
+    Capacity: a walker is F field records, so F x W <= max_walkers per batch."""
+
+    def __init__(self, models, per_field=(), max_walkers=4096, device=0):
+        models = list(models)
+        if not models:
+            raise ValueError('a joint fit needs at least one field')
+        for m in models:
+            if isinstance(m, MultiComponentModel) and (m._storage != 'f64' or m._backend != 'fused'):
+                raise ValueError("a joint fit runs on the fused back end with storage='f64' (got backend={!r}, "
+                                 "storage={!r})".format(m._backend, m._storage))
+        # shallow copies (as FieldSet makes): a model handed in stays what it was
+        self.field_models = [copy.copy(m) if isinstance(m, MultiComponentModel) else
+                             MultiComponentModel(m, device=device, backend='fused', max_walkers=1) for m in models]
+        first = self.field_models[0]
+        names, lens = first.param_names, first.param_lens
+        n_psf = len(first.config.psf_selector.psf_data)
+        for f, m in enumerate(self.field_models):
+            if (m.param_names != names or m.param_lens != lens or
+                    (len(m._ps), len(m._sersic), len(m._sky)) != (len(first._ps), len(first._sersic), len(first._sky))):
+                raise ValueError('field {}: the fields of a joint fit need the same component lists and free '
+                                 'parameters ({} against field 0\'s {})'.format(f, m.param_names, names))
+            if len(m.config.psf_selector.psf_data) != n_psf:
+                raise ValueError('field {} has {} PSFs and field 0 has {}: every field needs the same number of '
+                                 'PSFs'.format(f, len(m.config.psf_selector.psf_data), n_psf))
+        per_field = set(per_field)
+        unknown = sorted(per_field - set(names))
+        if unknown:
+            raise ValueError('per_field names {} are not parameters of the model ({})'.format(unknown, names))
+        psf_names = [n for c in first.components if isinstance(c, PSFSelector) for n in c.stochastic_names()]
+        per_field |= set(psf_names)
+        n_f = len(self.field_models)
+        self.per_field = sorted(per_field)
+        # each field's priors by parameter name, with their device forms
+        priors = []
+        for f, m in enumerate(self.field_models):
+            by_name = {}
+            for comp in m.components:
+                for attr in comp.free_names():
+                    prior = comp._priors[attr]
+                    desc = _device_prior(prior, prior.size)
+                    if desc is None:
+                        raise ValueError('field {}: the prior of {} has no device form; a joint fit evaluates '
+                                         'priors on the GPU only'.format(f, prior.name))
+                    by_name[prior.name] = (prior, desc)
+            priors.append(by_name)
+        # joint columns
+        own_start = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(int)
+        self._columns = [np.zeros(first.num_params, dtype=np.int64) for _ in range(n_f)]
+        self._blocks = []                          # (prior, joint slice, device description)
+        j_names, j_lens, pos = [], [], 0
+        for name, width, start in zip(names, lens, own_start):
+            own = slice(start, start + width)
+            if name in per_field:
+                for f in range(n_f):
+                    prior, desc = priors[f][name]
+                    j_names.append('{}_f{}'.format(name, f))
+                    j_lens.append(width)
+                    self._columns[f][own] = np.arange(pos, pos + width)
+                    self._blocks.append((prior, slice(pos, pos + width), desc))
+                    pos += width
+            else:
+                prior, desc = priors[0][name]
+                for f in range(1, n_f):
+                    if not _same_prior(prior, priors[f][name][0]):
+                        raise ValueError('shared parameter {}: field {} has the prior {!r}, field 0 has {!r}; a '
+                                         'shared parameter needs the same prior in every field (or make it '
+                                         'per_field)'.format(name, f, priors[f][name][0], prior))
+                j_names.append(name)
+                j_lens.append(width)
+                for f in range(n_f):
+                    self._columns[f][own] = np.arange(pos, pos + width)
+                self._blocks.append((prior, slice(pos, pos + width), desc))
+                pos += width
+        self._param_names, self._param_lens, self._num_params = j_names, j_lens, pos
+        self._family = np.zeros(pos, dtype=np.int32)
+        self._prior_params = np.zeros((pos, engine.PRIOR_NPAR))
+        for prior, cols, desc in self._blocks:
+            width = cols.stop - cols.start
+            self._family[cols] = desc[0]
+            for j in range(width):
+                self._prior_params[cols.start + j] = [np.ravel(v)[j if np.size(v) > 1 else 0] for v in desc[1:]]
+        self._device, self._max_walkers = int(device), int(max_walkers)
+        self._context = None
+        self._host_priors = []             # (DeviceEnsembleSampler: every prior is on the device)
+
+    # -- the shared context ------------------------------------------------------
+    @property
+    def engine(self):
+        """A `engine.JointView` of the fields' shared context, created on first use."""
+        if self._context is None:
+            fields = []
+            for m in self.field_models:
+                sel = m.config.psf_selector
+                fields.append((m.config.obs_data, m.config.obs_var, m.config.bad_px, np.stack(sel.psf_data),
+                               np.stack(sel.psf_var)))
+            first = self.field_models[0]
+            ctx = engine.FieldSetContext(fields, n_ps=len(first._ps), n_sersic=len(first._sersic),
+                                         max_walkers=self._max_walkers, device=self._device)
+            try:
+                for f, m in enumerate(self.field_models):
+                    m._register_layout(ctx.layout_of(f), columns=self._columns[f], n_params=self._num_params)
+                ctx.set_joint_priors(self._family, self._prior_params)
+            except Exception:
+                ctx.close()
+                raise
+            for f, m in enumerate(self.field_models):
+                # the field's images and posterior sums go through ITS field of the shared context
+                m._engine = ctx.view(f, self._columns[f])
+                m.posterior_images = dict(m.posterior_images)
+                m._param_vector = m._param_vector.copy()
+                m._max_walkers = self._max_walkers
+            self._context = ctx
+        return self._context.joint_view()
+
+    @property
+    def context(self):
+        """The shared `engine.FieldSetContext` (created on first use)."""
+        self.engine
+        return self._context
+
+    def close(self):
+        if self._context is not None:
+            self._context.close()
+            self._context = None
+            for m in self.field_models:
+                m._engine = None           # (views of the context just closed)
+
+    # -- parameter vector -----------------------------------------------------------
+    @property
+    def num_params(self):
+        return self._num_params
+
+    @property
+    def param_names(self):
+        return list(self._param_names)
+
+    @property
+    def param_lens(self):
+        return list(self._param_lens)
+
+    @property
+    def param_fits_abbrs(self):
+        return list(self._param_names)
+
+    @property
+    def obs_header(self):
+        return self.field_models[0].obs_header
+
+    def field_columns(self, f):
+        """[P_f] joint column of each of field f's own columns."""
+        return self._columns[f].copy()
+
+    def _theta(self, theta):
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim == 1:
+            theta = theta[None, :]
+        if theta.ndim != 2 or theta.shape[1] != self.num_params:
+            raise ValueError('expected [W, {}] joint parameter vectors, got {}'.format(self.num_params, theta.shape))
+        return theta
+
+    def field_theta(self, theta, f):
+        """[W, P_joint] joint vectors -> [W, P_f] field f's own vectors."""
+        return np.ascontiguousarray(self._theta(theta)[:, self._columns[f]])
+
+    def init_params_from_priors(self, nwalkers):
+        """Start positions: every joint column block drawn from its prior, redrawn until every field's
+        component priors (the axis-ratio rule included) are finite."""
+        out = np.zeros((nwalkers, self.num_params))
+        for w in range(nwalkers):
+            while True:
+                for prior, cols, _ in self._blocks:
+                    out[w, cols] = np.ravel(prior.random())
+                if np.isfinite(self.log_priors_batch(out[w:w + 1])[0]):
+                    break
+        return out
+
+    # -- priors and posterior ----------------------------------------------------------
+    def log_priors_batch(self, theta):
+        """[W] joint log-priors with scipy: each joint column's prior once, then every field's Sersic
+        axis-ratio rule."""
+        theta = self._theta(theta)
+        total = np.zeros(theta.shape[0])
+        with np.errstate(all='ignore'):
+            for prior, cols, _ in self._blocks:
+                total = total + prior.logp_batch(theta[:, cols])
+            for f, m in enumerate(self.field_models):
+                th = theta[:, self._columns[f]]
+                for comp, span in zip(m.components, m._spans):
+                    if isinstance(comp, Sersic):
+                        v = comp.values_batch(th[:, span])
+                        total = np.where(v['reff_b'] > v['reff'], -np.inf, total)
+        return total
+
+    def log_posterior_batch(self, theta):
+        """[W] joint log-posteriors, everything on the device, in slices of max_walkers // F walkers."""
+        theta = self._theta(theta)
+        eng = self.engine
+        cap = max(self._max_walkers // len(self.field_models), 1)
+        parts = [eng.logpost_theta(theta[lo:lo + cap]) for lo in range(0, theta.shape[0], cap)]
+        return np.concatenate(parts) if parts else np.zeros(0)
+
+    # -- posterior-image bookkeeping: the device sampler counts samples on the model, every field's sums
+    # get each of them -------------------------------------------------------------------
+    @property
+    def accumulated_samples(self):
+        return self.field_models[0].accumulated_samples
+
+    @accumulated_samples.setter
+    def accumulated_samples(self, n):
+        step = n - self.field_models[0].accumulated_samples
+        for m in self.field_models:
+            m.accumulated_samples += step
+
+    @property
+    def _device_samples(self):
+        return self.field_models[0]._device_samples
+
+    @_device_samples.setter
+    def _device_samples(self, n):
+        step = n - self.field_models[0]._device_samples
+        for m in self.field_models:
+            m._device_samples += step
+
+    def reset_images(self):
+        for m in self.field_models:
+            m.reset_images()
+
+    def collect_posterior_images(self):
+        """One dict kind -> image per field (`MultiComponentModel.collect_posterior_images`)."""
+        return [m.collect_posterior_images() for m in self.field_models]
