@@ -432,6 +432,8 @@ int psfmc_get_spectra(psfmc_ctx* ctx, double* psf_spec, double* var_spec);
  * bound, -1 (default) n = 3e6 / transform pixels, the measured break-even; needs max_walkers >= 1.5 W.
  * get_option only: "pow_tabs" (1: this context's rasterising kernels take (rho^2)^p from per-walker power tables --
  * transforms of more than 256 pixels per row --, 0: log2 + exp2 per pixel; a property of the transform shape),
+ * "pow_tabs_built" (1: the last batch's forward rows read the tables k_pow_tables built in memory, 0: its row waves
+ * formed the entries themselves -- small batches, psfmc_hip.hip launch_pow_tables -- or the context has no tables),
  * "transform_ny" / "transform_nx" (the transform shape: the image's own, or the built sides an
  * image of unbuilt sides is embedded in), "speculated_runs", "graph_launches", "row_group",
  * "partials_per_walker", "cols3", "column_engine" (the column kernel this context launches now: 0 k_cols, 1 k_cols3, 2

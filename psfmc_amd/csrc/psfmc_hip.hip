@@ -1670,6 +1670,7 @@ extern "C" double psfmc_get_option(const psfmc_ctx* cc, const char* key) {
     }
     if (!strcmp(key, "speculate")) return c->speculate;
     if (!strcmp(key, "pow_tabs")) return c->use_pow_tabs ? 1.0 : 0.0;
+    if (!strcmp(key, "pow_tabs_built")) return c->prep_tabs_built ? 1.0 : 0.0;   // the last batch read k_pow_tables' output
     if (!strcmp(key, "speculated_runs")) return (double)c->speculated_runs;
     if (!strcmp(key, "transform_ny")) return c->ny;        // the transform shape (the image's own, or the one it is embedded in)
     if (!strcmp(key, "transform_nx")) return c->nx;

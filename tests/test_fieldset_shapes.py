@@ -82,3 +82,34 @@ def test_fieldset_context_refuses_odd_side_naming_the_field():
     with pytest.raises(engine.NativeError) as err:
         engine.FieldSetContext(fields, n_ps=1, n_sersic=1, max_walkers=8)
     assert err.value.code == -1 and 'field 1' in str(err.value) and 'even' in str(err.value)
+
+
+def test_mixed_sets_cover_the_issue():
+    """tests/test_gpu_mixed_paths.py's sets reach every kernel family a mixed set can land on (each set's test
+    asserts the family the library reports)."""
+    from test_gpu_mixed_paths import MIXED_SETS
+    from test_gpu_variants import K_COLS, K_COLS3F, K_COLS3G, ROWS3_SIDES
+    code = {'k_cols': K_COLS, 'k_cols3g': K_COLS3G, 'k_cols3f': K_COLS3F}
+    for s in MIXED_SETS:
+        ty, tx = s.transform
+        assert code[engine.column_engine(ty)[0]] == s.column_engine, s.name
+        assert ty in engine.FUSED_SIDES and tx in engine.FUSED_SIDES, s.name
+        for ly, lx, pk in s.fields:
+            # an embedded axis holds the image and its wrap-around margin
+            assert all(t == l or t >= l + pk - 1 for t, l in ((ty, ly), (tx, lx))), (s.name, ly, lx, pk)
+    assert {s.column_engine for s in MIXED_SETS} == {K_COLS, K_COLS3G, K_COLS3F}
+    assert any(s.rows3 & 2 and s.transform[1] in ROWS3_SIDES for s in MIXED_SETS)
+    assert any(s.rows3 == 3 and min(s.transform) > 1024 for s in MIXED_SETS)
+    rows = {s.transform[1] for s in MIXED_SETS}
+    assert 256 in rows and any(256 < n <= 300 for n in rows) and min(rows) <= 64
+    assert any(s.row_group == 8 for s in MIXED_SETS) and any(s.row_group == 1 for s in MIXED_SETS)
+    assert any(s.transform[0] != s.transform[1] for s in MIXED_SETS)
+    fields = [(s, fld) for s in MIXED_SETS for fld in s.fields]
+    embedded = [((fld[0] != s.transform[0]), (fld[1] != s.transform[1])) for s, fld in fields]
+    assert (True, False) in embedded and (False, True) in embedded and (True, True) in embedded
+    assert any(fld[:2] == s.transform for s, fld in fields)
+    exact = [(s.name, axis) for s, fld in fields for axis in (0, 1)
+             if fld[axis] != s.transform[axis] and fld[axis] + fld[2] - 1 == s.transform[axis]]
+    assert {name for name, _ in exact} >= {'B', 'C', 'D', 'G', 'H'}
+    assert {axis for _, axis in exact} == {0, 1}
+    assert any(s.n_psf > 1 for s in MIXED_SETS) and {len(s.fields) for s in MIXED_SETS} == {2, 3}

@@ -586,17 +586,19 @@ def test_schedule_invariance_across_kernel_families(path):
     model.close()
 
 
-def edge_case(seed, shape, psf_shape, comps=None, n_walkers=5):
-    """A random field (`random_case`) with one PSF of the given shape and, if given, these components; in the
-    free-parameter form."""
+def edge_case(seed, shape, psf_shape, comps=None, n_walkers=5, n_psf=1):
+    """A random field (`random_case`) with n_psf PSFs of the given shape (each wider than the one before; with
+    several, the PSF index is free) and, if given, these components; in the free-parameter form."""
     case = random_case(seed, shape)
     rng = np.random.RandomState(seed + 1)
     py, px = psf_shape
     yy, xx = np.mgrid[0:py, 0:px].astype(float)
-    core = (1 + ((xx - px // 2) ** 2 + (yy - py // 2 + 0.1) ** 2) / 2.0 ** 2) ** -2.5 * 300
-    var = 0.01 + core / 40.0
-    case['psfs'] = [(core + rng.normal(size=core.shape) * np.sqrt(var)).astype(np.float32)]
-    case['pivms'] = [(1.0 / var).astype(np.float32)]
+    case['psfs'], case['pivms'] = [], []
+    for k in range(n_psf):
+        core = (1 + ((xx - px // 2) ** 2 + (yy - py // 2 + 0.1) ** 2) / (2.0 + 0.6 * k) ** 2) ** -2.5 * 300
+        var = 0.01 + core / 40.0
+        case['psfs'].append((core + rng.normal(size=core.shape) * np.sqrt(var)).astype(np.float32))
+        case['pivms'].append((1.0 / var).astype(np.float32))
     case['psf_index'] = 0
     if comps is not None:
         case['comps'] = comps
