@@ -327,6 +327,43 @@ int psfmc_stretch_run(psfmc_ctx* ctx, int W, int n_iter, double* pos, double* ln
                       long long* naccepted, int accumulate);
 
 /*
+ * Parallel tempering (no reference counterpart; the contract is psfmc_amd/sampler.py's
+ * TemperedEnsembleSampler, which these calls reproduce bit for bit).  One-field contexts with every prior
+ * on the device; multi-field and joint contexts and PSFMC_PRIOR_HOST columns return PSFMC_EINVAL.
+ * psfmc_eval_theta_split: psfmc_eval_theta's evaluation with the two terms apart -- lnlike [W] (-inf when
+ *   the walker is skipped or its log-likelihood is not finite) and lnprior [W] (the device log-prior plus
+ *   extra_lnprior), the values psfmc_pt_run works with.
+ * psfmc_pt_run: n_iter tempered iterations, nothing copied to the host in between.  T ensembles of W walkers
+ *   sample beta_t lnL + lnpi on the ladder betas [T] (1 = beta_0 > ... > beta_{T-1} = 0; T = 1: betas = {1}).
+ *   A walker's lnp is beta lnL + lnpi, that product then that sum; lnL = lnp = -inf where lnpi or lnL is not
+ *   finite.  Per iteration: the stretch half-steps h = 0, 1 of every rung (one proposal launch, one pipeline
+ *   pass over T W/2 records, one accept launch each; random numbers in the host sampler's order, rung-major
+ *   within a half-step), then ONE swap launch: for t = T-1 ... 1, walker swap_i[k] of rung t and swap_j[k] of
+ *   rung t-1 exchange positions, lnL and lnpi when swap_log_u[k] < (beta_{t-1} - beta_t)(lnL_t - lnL_{t-1}).
+ *     pos [T][W][P], lnlike [T][W], lnprior [T][W]   in/out; lnlike / lnprior are evaluated first unless
+ *                                 state_valid
+ *     z, lz, log_u, partner [n_iter][2][T][W/2]      psfmc_stretch_run's, per rung (partner in [0, W/2))
+ *     swap_i, swap_j, swap_log_u [n_iter][T-1][W]    entry t-1 is the rung pair (t-1, t); swap_i and swap_j
+ *                                 permutations of [0, W) (checked)
+ *     chain [T][W][n_iter][P]     every rung's positions after each iteration's swaps, the beta = 1 rung
+ *                                 first: its first W n_iter P entries are the beta = 1 chain (may be NULL)
+ *     lnprob_chain [W][n_iter]    lnp of the beta = 1 rung (may be NULL)
+ *     lnlike_chain, lnprior_chain [T][W][n_iter]     every rung's lnL and lnpi (may be NULL): with chain, a
+ *                                 state to resume from after any iteration
+ *     naccepted [T][W], nswap [T-1]                  in/out counters (nswap: accepted swaps per rung pair)
+ *     accumulate                  nonzero: after every iteration add the images of the beta = 1 rung's W
+ *                                 positions to the posterior sums
+ *   PSFMC_EINVAL for T W > max_walkers, an odd W, a bad ladder, a host prior or a context of several fields.
+ */
+int psfmc_eval_theta_split(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
+                           double* lnlike, double* lnprior);
+int psfmc_pt_run(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos, double* lnlike,
+                 double* lnprior, int state_valid, const double* z, const double* lz, const int* partner,
+                 const double* log_u, const int* swap_i, const int* swap_j, const double* swap_log_u,
+                 double* chain, double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                 long long* naccepted, long long* nswap, int accumulate);
+
+/*
  * The same sampler one half-step at a time, for walkers sharded over several GPUs (one
  * process per GPU).  Every rank opens the SAME ensemble with the SAME
  * random numbers; per half-step each rank calls psfmc_stretch_half_eval for its contiguous

@@ -4,12 +4,14 @@ brightness modelling.  Public names mirror the reference package `psfMC`.
 """
 from .models import MultiComponentModel, FieldSet, JointModel
 from .batch import BatchLogPosterior
-from .sampler import EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler
+from .sampler import (EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler, TemperedEnsembleSampler,
+                      DeviceTemperedSampler, default_betas)
 from .parallel import RankGroup, ShardedLogPosterior
-from .fitting import model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc
+from .fitting import model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc
 from .database import load_database
 
 __version__ = '0.1.0'
 __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior', 'EnsembleSampler',
-           'DeviceEnsembleSampler', 'FieldSetSampler', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc',
-           'model_fields_mcmc', 'model_joint_mcmc', 'load_database']
+           'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler', 'DeviceTemperedSampler',
+           'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
+           'model_joint_mcmc', 'model_galaxy_ptmcmc', 'load_database']

@@ -436,6 +436,9 @@ struct psfmc_ctx {
         int F = 1;                // ensembles in the run (psfmc_stretch_run_fields: one per field)
         bool store = false, open = false;
     } stretch;
+    // parallel-tempering state (psfmc_pt_run): one grow-only allocation carved per call
+    unsigned char* pt_blob = nullptr;
+    size_t pt_cap = 0;
 };
 
 // a field's image window inside the transform-shaped pixel arrays (all of them unless the image is embedded)
@@ -1530,7 +1533,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_layout_blob, c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
-                    c->stretch.nacc, c->stretch.accflag};
+                    c->stretch.nacc, c->stretch.accflag, c->pt_blob};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2879,6 +2882,167 @@ extern "C" int psfmc_stretch_run_fields(psfmc_ctx* c, int W, int n_iter, double*
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     return stretch_run_impl(c, c->n_fields, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, chain,
                             lnprob_chain, naccepted, accumulate);
+}
+
+// ---------------------------------------------------------------------------
+// parallel tempering (include/psfmc_hip.h psfmc_eval_theta_split, psfmc_pt_run)
+// ---------------------------------------------------------------------------
+extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, const double* extra,
+                                      double* lnlike, double* lnprior) {
+    if (c && c->n_fields > 1) return fail(PSFMC_EINVAL, "this entry point serves contexts of one field");
+    int rc = check_theta_call(c, W, theta, lnlike);
+    if (rc != PSFMC_OK || W == 0) return rc;
+    if (!lnprior) return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (c->layout.n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+                               hipMemcpyHostToDevice, st));
+    if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_theta_prep(c, W, c->d_theta, extra ? c->d_extra : nullptr, nullptr, st, StretchIn{});
+    RC_TRY(run_pipeline(c, W, c->d_skip, st));
+    hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial, c->d_skip,
+                       c->nblk, c->d_like, W);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lnlike, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lnprior, c->d_lnprior, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                            double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                            const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
+                            const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
+                            double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (T < 1 || W < 0 || (long long)T * W > c->max_walkers)
+        return fail(PSFMC_EINVAL, "T=%d temperatures x W=%d walkers outside [1, max_walkers=%d]", T, W, c->max_walkers);
+    RC_TRY(stretch_check(c, W, 1));               // one field, a layout, W even, every prior on the device
+    const bool swaps = T > 1 && n_iter > 0;
+    if (n_iter < 0 || !betas || !pos || !lnlike || !lnprior || !naccepted || (T > 1 && !nswap) ||
+        (n_iter && (!z || !lz || !partner || !log_u)) || (swaps && (!swap_i || !swap_j || !swap_log_u)))
+        return fail(PSFMC_EINVAL, "NULL buffer");
+    // the ladder: finite, beta_0 = 1, strictly decreasing, the last rung 0 (the evidence needs the prior rung)
+    for (int t = 0; t < T; ++t)
+        if (!std::isfinite(betas[t]) || (t == 0 && betas[t] != 1.0) || (t > 0 && !(betas[t] < betas[t - 1])))
+            return fail(PSFMC_EINVAL, "bad temperature ladder at rung %d", t);
+    if (T > 1 && betas[T - 1] != 0.0) return fail(PSFMC_EINVAL, "the last rung of the ladder must be beta = 0");
+    const int half = W / 2, P = c->layout.n_params;
+    const size_t TW = (size_t)T * W, n_rand = (size_t)n_iter * TW, n_swap = swaps ? (size_t)n_iter * (T - 1) * W : 0;
+    // every index is checked here: the kernels address walkers by them
+    for (size_t i = 0; i < n_rand; ++i)
+        if (partner[i] < 0 || partner[i] >= half) return fail(PSFMC_EINVAL, "partner index %d outside [0, %d)", partner[i], half);
+    for (size_t i = 0; i < n_swap; ++i)
+        if (swap_i[i] < 0 || swap_i[i] >= W || swap_j[i] < 0 || swap_j[i] >= W)
+            return fail(PSFMC_EINVAL, "swap index outside [0, %d)", W);
+    // swap pairs must form a matching (the swap kernel gives each pair its own thread)
+    if (n_swap) {
+        std::vector<int> seen((size_t)2 * W, -1);
+        for (size_t r = 0; r < n_swap / W; ++r)
+            for (int k = 0; k < W; ++k) {
+                const int a = swap_i[r * W + k], b = W + swap_j[r * W + k];
+                if (seen[a] == (int)r || seen[b] == (int)r) return fail(PSFMC_EINVAL, "swap indices are not permutations");
+                seen[a] = seen[b] = (int)r;
+            }
+    }
+    // one allocation: doubles, then long longs, then ints, each piece 256-byte aligned
+    size_t bytes = 0;
+    auto take = [&](size_t n, size_t elem) { const size_t at = bytes; bytes += (n * elem + 255) / 256 * 256; return at; };
+    const size_t o_beta = take(T, 8), o_pos = take(TW * P, 8), o_lnL = take(TW, 8), o_lnpi = take(TW, 8),
+                 o_lnp = take(TW, 8), o_q = take((size_t)T * half * P, 8), o_rand = take(3 * n_rand, 8),
+                 o_slu = take(n_swap, 8), o_chain = take(chain ? TW * n_iter * P : 0, 8),
+                 o_lnpc = take(lnprob_chain ? (size_t)W * n_iter : 0, 8),
+                 o_lnlc = take(lnlike_chain ? TW * n_iter : 0, 8), o_lnqc = take(lnprior_chain ? TW * n_iter : 0, 8),
+                 o_nacc = take(TW, 8), o_nswap = take(T, 8),
+                 o_partner = take(n_rand, 4), o_si = take(n_swap, 4), o_sj = take(n_swap, 4);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));            // a previous call may still use the blob
+    RC_TRY(grow(&c->pt_blob, &c->pt_cap, bytes));
+    unsigned char* base = c->pt_blob;
+    double* d_beta = reinterpret_cast<double*>(base + o_beta);
+    double* d_pos = reinterpret_cast<double*>(base + o_pos);
+    double* d_lnL = reinterpret_cast<double*>(base + o_lnL);
+    double* d_lnpi = reinterpret_cast<double*>(base + o_lnpi);
+    double* d_lnp = reinterpret_cast<double*>(base + o_lnp);
+    double* d_q = reinterpret_cast<double*>(base + o_q);
+    double* d_z = reinterpret_cast<double*>(base + o_rand);
+    double* d_lz = d_z + n_rand;
+    double* d_logu = d_z + 2 * n_rand;
+    double* d_slu = reinterpret_cast<double*>(base + o_slu);
+    double* d_chain = chain ? reinterpret_cast<double*>(base + o_chain) : nullptr;
+    double* d_lnpc = lnprob_chain ? reinterpret_cast<double*>(base + o_lnpc) : nullptr;
+    double* d_lnlc = lnlike_chain ? reinterpret_cast<double*>(base + o_lnlc) : nullptr;
+    double* d_lnqc = lnprior_chain ? reinterpret_cast<double*>(base + o_lnqc) : nullptr;
+    long long* d_nacc = reinterpret_cast<long long*>(base + o_nacc);
+    long long* d_nswap = reinterpret_cast<long long*>(base + o_nswap);
+    int* d_partner = reinterpret_cast<int*>(base + o_partner);
+    int* d_si = reinterpret_cast<int*>(base + o_si);
+    int* d_sj = reinterpret_cast<int*>(base + o_sj);
+    auto up = [&](void* dst, const void* src, size_t n) -> int {
+        if (n) HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st));
+        return PSFMC_OK;
+    };
+    RC_TRY(up(d_beta, betas, T * sizeof(double)));
+    RC_TRY(up(d_pos, pos, TW * P * sizeof(double)));
+    RC_TRY(up(d_nacc, naccepted, TW * sizeof(long long)));
+    if (T > 1) RC_TRY(up(d_nswap, nswap, (T - 1) * sizeof(long long)));
+    RC_TRY(up(d_z, z, n_rand * sizeof(double)));
+    RC_TRY(up(d_lz, lz, n_rand * sizeof(double)));
+    RC_TRY(up(d_logu, log_u, n_rand * sizeof(double)));
+    RC_TRY(up(d_partner, partner, n_rand * sizeof(int)));
+    RC_TRY(up(d_si, swap_i, n_swap * sizeof(int)));
+    RC_TRY(up(d_sj, swap_j, n_swap * sizeof(int)));
+    RC_TRY(up(d_slu, swap_log_u, n_swap * sizeof(double)));
+    if (state_valid) {
+        RC_TRY(up(d_lnL, lnlike, TW * sizeof(double)));
+        RC_TRY(up(d_lnpi, lnprior, TW * sizeof(double)));
+    } else {                                      // every rung's start positions in one batch
+        launch_theta_prep(c, (int)TW, d_pos, nullptr, nullptr, st, StretchIn{});
+        RC_TRY(run_pipeline(c, (int)TW, c->d_skip, st));
+        hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks((int)TW)), dim3(kFinishThreads), 0, st, c->d_partial,
+                           c->d_skip, c->nblk, d_lnL, (int)TW);
+        HIP_TRY(hipMemcpyAsync(d_lnpi, c->d_lnprior, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    hipLaunchKernelGGL(k_pt_tempered, dim3(((int)TW + 255) / 256), dim3(256), 0, st, d_beta, d_lnL, d_lnpi, d_lnp,
+                       (int)TW, W);
+    if (accumulate) RC_TRY(stretch_prepare_accumulation(c));
+    // one iteration is seven launches whatever T is: per half-step the T rungs' proposals (one k_theta_prep),
+    // one pipeline pass over T half records, one accept kernel; then one swap kernel
+    for (int it = 0; it < n_iter; ++it) {
+        for (int h = 0; h < 2; ++h) {
+            StretchIn sp{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T};
+            launch_theta_prep(c, T * half, nullptr, nullptr, nullptr, st, sp);
+            RC_TRY(run_pipeline(c, T * half, c->d_skip, st));
+            hipLaunchKernelGGL(k_pt_finish, dim3(finish_blocks(T * half)), dim3(kFinishThreads), 0, st, c->d_partial,
+                               c->d_skip, c->d_lnprior, c->nblk, d_beta, d_pos, d_lnL, d_lnpi, d_lnp, d_q, d_lz,
+                               d_logu, d_nacc, it, T, half, h, P);
+        }
+        hipLaunchKernelGGL(k_pt_swap, dim3(1), dim3(kPtSwapThreads), 0, st, d_beta, d_pos, d_lnL, d_lnpi, d_lnp,
+                           d_si, d_sj, d_slu, d_nswap, d_chain, d_lnpc, d_lnlc, d_lnqc, it, n_iter, T, W, P);
+        if (accumulate) {                         // the beta = 1 rung: the first W walkers
+            launch_theta_prep(c, W, d_pos, nullptr, nullptr, st, StretchIn{});
+            RC_TRY(accumulate_from_prep(c, W, st, 0, 1, W));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    auto down = [&](void* dst, const void* src, size_t n) -> int {
+        if (n) HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st));
+        return PSFMC_OK;
+    };
+    RC_TRY(down(pos, d_pos, TW * P * sizeof(double)));
+    RC_TRY(down(lnlike, d_lnL, TW * sizeof(double)));
+    RC_TRY(down(lnprior, d_lnpi, TW * sizeof(double)));
+    RC_TRY(down(naccepted, d_nacc, TW * sizeof(long long)));
+    if (T > 1) RC_TRY(down(nswap, d_nswap, (T - 1) * sizeof(long long)));
+    if (chain) RC_TRY(down(chain, d_chain, TW * n_iter * P * sizeof(double)));
+    if (lnprob_chain) RC_TRY(down(lnprob_chain, d_lnpc, (size_t)W * n_iter * sizeof(double)));
+    if (lnlike_chain) RC_TRY(down(lnlike_chain, d_lnlc, TW * n_iter * sizeof(double)));
+    if (lnprior_chain) RC_TRY(down(lnprior_chain, d_lnqc, TW * n_iter * sizeof(double)));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hipGetLastError() != hipSuccess) return fail(PSFMC_EHIP, "kernel launch failed");
+    return PSFMC_OK;
 }
 
 // ---------------------------------------------------------------------------

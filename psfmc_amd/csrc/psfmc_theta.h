@@ -427,6 +427,11 @@ struct StretchIn {
     // The accept step of the second half picks the row its partner's outcome selects (k_stretch_finish), so the
     // chain is the one of two half-steps run after each other, bit for bit, at one pipeline pass per iteration.
     int spec;
+    // n_ens > 0 (parallel tempering, psfmc_pt_run): the launch's records are the half-step proposals of n_ens
+    // ensembles of 2 half walkers that share field 0, flattened -- record r belongs to ensemble t = r / half,
+    // whose walkers are rows [t 2 half, (t + 1) 2 half) of pos; the random numbers are [n_iter][2][n_ens][half],
+    // so record r reads entry ((it 2 + h) n_ens) half + r.  0 everywhere else.
+    int n_ens;
 };
 
 // the fields of one k_theta_prep launch (gridDim.y > 1): field f takes layouts[f], image sides sides[2 f],
@@ -537,11 +542,12 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
         soff = (size_t)it * 2 * sp.half;
     } else if (sp.pos) {                                            // propose into the tile
         const int it = sp.d_iter ? *sp.d_iter : sp.it;
-        soff = ((size_t)it * 2 + sp.h) * sp.half;
+        soff = ((size_t)it * 2 + sp.h) * sp.half * (sp.n_ens ? sp.n_ens : 1);
         if (tid < n_tile) {
             const int lw = tid / P, d = tid - lw * P, w = w0 + lw;
-            s_own = sp.pos[(size_t)(sp.h * sp.half + w) * P + d];
-            c_other = sp.pos[(size_t)((1 - sp.h) * sp.half + sp.partner[soff + w]) * P + d];
+            const int e = sp.n_ens ? (w / sp.half) * sp.half : 0;   // (n_ens) ensemble t = w / half: t half
+            s_own = sp.pos[(size_t)(e + sp.h * sp.half + w) * P + d];
+            c_other = sp.pos[(size_t)(2 * e + (1 - sp.h) * sp.half + sp.partner[soff + w]) * P + d];
             zz = sp.z[soff + w];
         }
     } else if (tid < n_tile) {
@@ -565,8 +571,9 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
         }
         for (int i = tid + nthr; i < n_tile; i += nthr) {
             const int lw = i / P, d = i - lw * P, w = w0 + lw;
-            const double s = sp.pos[(size_t)(sp.h * sp.half + w) * P + d];
-            const double c = sp.pos[(size_t)((1 - sp.h) * sp.half + sp.partner[soff + w]) * P + d];
+            const int e = sp.n_ens ? (w / sp.half) * sp.half : 0;
+            const double s = sp.pos[(size_t)(e + sp.h * sp.half + w) * P + d];
+            const double c = sp.pos[(size_t)(2 * e + (1 - sp.h) * sp.half + sp.partner[soff + w]) * P + d];
             const double q = stretch_point(s, c, sp.z[soff + w]);
             th_tile[i] = q;
             sp.q[(size_t)w0 * P + i] = q;
@@ -756,6 +763,149 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
             nacc[g] += 1;
         }
         if (chain) lnchain[(size_t)g * n_iter + it] = lp;
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------
+// parallel tempering (psfmc_eval_theta_split, psfmc_pt_run; the contract is sampler.py's
+// TemperedEnsembleSampler).  A walker carries its log-likelihood lnL, its log-prior lnpi and its tempered
+// log-posterior lnp = beta lnL + lnpi -- exactly that product, then that sum.  A walker whose lnpi or lnL is
+// not finite has lnL = lnp = -inf at every beta (no 0 * inf = NaN on the beta = 0 rung).
+// ---------------------------------------------------------------------------
+// the log-likelihood of walker w: walker_lnprob's sum without the prior, -inf if skipped or not finite
+__device__ inline double walker_loglike(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
+                                        int nblk, int w, int lane) {
+    if (skip[w]) return -INFINITY;
+    const double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+    return ll == ll && fabs(ll) != INFINITY ? ll : -INFINITY;
+}
+
+__device__ inline double tempered_lnp(double beta, double ll, double lp) {
+#pragma clang fp contract(off)
+    const bool ok = ll == ll && fabs(ll) != INFINITY && lp == lp && fabs(lp) != INFINITY;
+    const double bl = beta * ll;
+    return ok ? bl + lp : -INFINITY;
+}
+
+#if PSFMC_PART == 0          /* not a template: defined in the API part only */
+// log-likelihoods of W walkers whose partial sums are in `partial` (their log-priors stay in d_lnprior).
+// One wave per walker (launch: finish_blocks(W) x kFinishThreads).
+__global__ void k_split_finish(const double* __restrict__ partial, const uint8_t* __restrict__ skip, int nblk,
+                               double* __restrict__ lnlike, int W) {
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
+    if (w >= W) return;
+    const double ll = walker_loglike(partial, skip, nblk, w, lane);
+    if (lane == 0) lnlike[w] = ll;
+}
+
+// the start state of T W walkers (rung t = walkers [t W, (t + 1) W)): lnL made -inf where lnpi or lnL is not
+// finite, lnp at each walker's beta.  One thread per walker.
+__global__ void k_pt_tempered(const double* __restrict__ betas, double* __restrict__ lnL,
+                              const double* __restrict__ lnpi, double* __restrict__ lnp, int TW, int W) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= TW) return;
+    const double v = tempered_lnp(betas[i / W], lnL[i], lnpi[i]);
+    if (v == -INFINITY) lnL[i] = -INFINITY;
+    lnp[i] = v;
+}
+
+// accept / move of one tempered half-step: record r = t half + w is walker h half + w of rung t's ensemble,
+// its proposal q[r] (formed by k_theta_prep with StretchIn::n_ens = T); random numbers [n_iter][2][T][half].
+// Acceptance as k_stretch_finish's, ((P - 1) ln z + lnp_new) - lnp > ln u, with the tempered lnp.  No chain
+// entry here: k_pt_swap writes the iteration's.  One wave per proposal (launch: finish_blocks(T half) x
+// kFinishThreads).
+__global__ void k_pt_finish(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
+                            const double* __restrict__ lnprior, int nblk, const double* __restrict__ betas,
+                            double* __restrict__ pos, double* __restrict__ lnL, double* __restrict__ lnpi,
+                            double* __restrict__ lnp, const double* __restrict__ q, const double* __restrict__ lz,
+                            const double* __restrict__ log_u, long long* __restrict__ nacc, int it, int T,
+                            int half, int h, int P) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
+    if (r >= T * half) return;                               // wave-uniform
+    const int t = r / half, w = r - t * half;
+    const size_t off = ((size_t)it * 2 + h) * T * half + r;
+    const double ll = walker_loglike(partial, skip, nblk, r, lane);
+    const double lp = lnprior[r];
+    const double newlnp = tempered_lnp(betas[t], ll, lp);
+    const size_t g = (size_t)t * 2 * half + (size_t)h * half + w;
+    const double diff = (lz[off] + newlnp) - lnp[g];
+    if (!(diff > log_u[off])) return;                        // the same in every lane
+    for (int d = lane; d < P; d += 64) pos[g * P + d] = q[(size_t)r * P + d];
+    if (lane == 0) {
+        lnL[g] = newlnp == -INFINITY ? -INFINITY : ll;
+        lnpi[g] = lp;
+        lnp[g] = newlnp;
+        nacc[g] += 1;
+    }
+}
+
+// the swaps of one iteration, hottest pair first: for t = T-1 ... 1, pair k exchanges walker i[k] of rung t with
+// walker j[k] of rung t-1 when ln u[k] < (beta_{t-1} - beta_t) (lnL[t, i[k]] - lnL[t-1, j[k]]) -- positions, lnL
+// and lnpi; lnp is recomputed at each walker's new beta.  i and j are permutations, so the pairs of a rung are a
+// matching: no two threads touch one walker.  Rungs run one after another (a barrier between them); the rung
+// pair's accepted swaps are reduced in LDS and added to nswap[t-1] by one thread.  Then the iteration's chain
+// entries: every rung's positions, lnL and lnpi (the host yields a resumable state per iteration), lnp of the
+// beta = 1 rung.  ONE workgroup (launch: 1 x kPtSwapThreads).
+// swap_i / swap_j / swap_log_u: [n_iter][T-1][W], entry t-1 the pair (t-1, t).
+constexpr int kPtSwapThreads = 256;
+__global__ void __launch_bounds__(kPtSwapThreads)
+k_pt_swap(const double* __restrict__ betas, double* __restrict__ pos, double* __restrict__ lnL,
+          double* __restrict__ lnpi, double* __restrict__ lnp, const int* __restrict__ swap_i,
+          const int* __restrict__ swap_j, const double* __restrict__ swap_log_u, long long* __restrict__ nswap,
+          double* __restrict__ chain, double* __restrict__ lnprob_chain, double* __restrict__ lnlike_chain,
+          double* __restrict__ lnprior_chain, int it, int n_iter, int T, int W, int P) {
+#pragma clang fp contract(off)
+    __shared__ int count[kPtSwapThreads];
+    const int tid = threadIdx.x;
+    for (int t = T - 1; t >= 1; --t) {
+        const size_t roff = ((size_t)it * (T - 1) + (t - 1)) * W;
+        const double b_hot = betas[t], b_cold = betas[t - 1];
+        const double dbeta = b_cold - b_hot;
+        int mine = 0;
+        for (int k = tid; k < W; k += kPtSwapThreads) {
+            const size_t a = (size_t)t * W + swap_i[roff + k];
+            const size_t b = (size_t)(t - 1) * W + swap_j[roff + k];
+            const double dl = lnL[a] - lnL[b];
+            const double lr = dbeta * dl;
+            if (swap_log_u[roff + k] < lr) {
+                for (int d = 0; d < P; ++d) {
+                    const double x = pos[a * P + d];
+                    pos[a * P + d] = pos[b * P + d];
+                    pos[b * P + d] = x;
+                }
+                const double la = lnL[b], pa = lnpi[b], lb = lnL[a], pb = lnpi[a];
+                lnL[a] = la;
+                lnpi[a] = pa;
+                lnp[a] = tempered_lnp(b_hot, la, pa);
+                lnL[b] = lb;
+                lnpi[b] = pb;
+                lnp[b] = tempered_lnp(b_cold, lb, pb);
+                ++mine;
+            }
+        }
+        count[tid] = mine;
+        __syncthreads();
+        for (int s = kPtSwapThreads / 2; s > 0; s >>= 1) {
+            if (tid < s) count[tid] += count[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) nswap[t - 1] += count[0];
+        __syncthreads();                                     // rung t-1 is final; count is free again
+    }
+    if (chain)
+        for (int i = tid; i < T * W * P; i += kPtSwapThreads) {
+            const int w = i / P, d = i - w * P;
+            chain[((size_t)w * n_iter + it) * P + d] = pos[i];
+        }
+    if (lnprob_chain)
+        for (int w = tid; w < W; w += kPtSwapThreads) lnprob_chain[(size_t)w * n_iter + it] = lnp[w];
+    for (int i = tid; i < T * W; i += kPtSwapThreads) {
+        if (lnlike_chain) lnlike_chain[(size_t)i * n_iter + it] = lnL[i];
+        if (lnprior_chain) lnprior_chain[(size_t)i * n_iter + it] = lnpi[i];
     }
 }
 #endif

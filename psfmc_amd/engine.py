@@ -200,6 +200,12 @@ def load_library():
     llp = ctypes.POINTER(ctypes.c_longlong)
     lib.psfmc_stretch_run_fields.restype = ci
     lib.psfmc_stretch_run_fields.argtypes = lib.psfmc_stretch_run.argtypes
+    lib.psfmc_eval_theta_split.restype = ci
+    lib.psfmc_eval_theta_split.argtypes = [vp, ci, _c_double_p, _c_double_p, _c_double_p, _c_double_p]
+    lib.psfmc_pt_run.restype = ci
+    lib.psfmc_pt_run.argtypes = [vp, ci, ci, ci, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ci,
+                                 _c_double_p, _c_double_p, ip, _c_double_p, ip, ip, _c_double_p,
+                                 _c_double_p, _c_double_p, _c_double_p, _c_double_p, llp, llp, ci]
     lib.psfmc_set_joint_priors.restype = ci
     lib.psfmc_set_joint_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_eval_theta_joint.restype = ci
@@ -536,6 +542,67 @@ class Context(object):
             _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
         return pos, lnp, chain, lnchain
+
+    def loglike_prior_theta(self, theta, extra_lnprior=None):
+        """[W, P] raw parameter vectors -> (lnlike [W], lnprior [W]) as the device computes them
+        (psfmc_eval_theta_split): lnlike -inf outside the priors or where it is not finite."""
+        theta = self._theta(theta)
+        n_w = theta.shape[0]
+        ll, lp = np.empty(n_w), np.empty(n_w)
+        if n_w == 0:
+            return ll, lp
+        extra = None
+        if extra_lnprior is not None:
+            extra = _f64(extra_lnprior)
+            if extra.shape != (n_w,):
+                raise ValueError('extra_lnprior must be [W]')
+        self._check(self._lib.psfmc_eval_theta_split(self._ctx, n_w, _dp(theta),
+                                                     _dp(extra) if extra is not None else None, _dp(ll), _dp(lp)))
+        return ll, lp
+
+    def pt_run(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+               naccepted, nswap, store=True, accumulate=False):
+        """Run z.shape[0] parallel-tempered iterations on the device (include/psfmc_hip.h psfmc_pt_run).
+        betas [T], pos [T,W,P], lnlike / lnprior [T,W] or None (then evaluated first), z/lz/log_u/partner
+        [n_iter,2,T,W/2], swap_i/swap_j/swap_log_u [n_iter,T-1,W], naccepted int64 [T,W], nswap int64 [T-1].
+        Returns (pos, lnlike, lnprior, chain [T,W,n_iter,P] (every rung, beta = 1 first), lnprob_chain [W,n_iter]
+        (beta = 1), lnlike_chain [T,W,n_iter], lnprior_chain [T,W,n_iter]) -- the chains None unless `store`;
+        naccepted and nswap are updated."""
+        betas = _f64(betas)
+        pos = np.array(pos, dtype=np.float64, order='C')
+        if pos.ndim != 3 or betas.shape != (pos.shape[0],):
+            raise ValueError('pos must be [T, W, P] with betas [T]')
+        n_t, n_w, n_p = pos.shape
+        if n_p != self.n_params:
+            raise ValueError('pos must have {} parameters'.format(self.n_params))
+        if n_t * n_w > self.max_walkers:
+            raise ValueError('T x W = {} exceeds max_walkers={}'.format(n_t * n_w, self.max_walkers))
+        n_iter = int(np.shape(z)[0])
+        have = lnlike is not None and lnprior is not None
+        ll = np.array(lnlike, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
+        lp = np.array(lnprior, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
+        z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_t, n_w // 2) for a in (z, lz, log_u))
+        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_t, n_w // 2)
+        n_sw = max(n_t - 1, 0)
+        swap_i, swap_j = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, n_sw, n_w) for a in (swap_i, swap_j))
+        swap_log_u = _f64(swap_log_u).reshape(n_iter, n_sw, n_w)
+        if naccepted.dtype != np.int64 or naccepted.shape != (n_t, n_w) or not naccepted.flags.c_contiguous:
+            raise ValueError('naccepted must be int64 [T, W]')
+        if nswap.dtype != np.int64 or nswap.shape != (n_sw,):
+            raise ValueError('nswap must be int64 [T-1]')
+        store = store and n_iter > 0
+        chain = np.empty((n_t, n_w, n_iter, n_p)) if store else None
+        lnchain = np.empty((n_w, n_iter)) if store else None
+        llchain = np.empty((n_t, n_w, n_iter)) if store else None
+        lpchain = np.empty((n_t, n_w, n_iter)) if store else None
+        ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        lpt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        opt = lambda a: _dp(a) if a is not None else None
+        self._check(self._lib.psfmc_pt_run(
+            self._ctx, n_t, n_w, n_iter, _dp(betas), _dp(pos), _dp(ll), _dp(lp), int(have), _dp(z), _dp(lz),
+            ipt(partner), _dp(log_u), ipt(swap_i), ipt(swap_j), _dp(swap_log_u), opt(chain), opt(lnchain),
+            opt(llchain), opt(lpchain), lpt(naccepted), lpt(nswap) if n_sw else None, int(bool(accumulate))))
+        return pos, ll, lp, chain, lnchain, llchain, lpchain
 
     # -- the sampler one half-step at a time (walkers sharded over ranks) -----
     def stretch_open(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True):

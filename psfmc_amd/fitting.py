@@ -330,3 +330,70 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
         save_posterior_images(m, Table(cols, database.meta), output_name='{}_f{}_{{}}'.format(output_name, f),
                               filetypes=write_fits)
     return joint, database
+
+
+def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetypes, iterations=0, burn=0,
+                        chains=None, ntemps=16, tmax=1e6, betas=None, device=0, backend='auto', random_state=None,
+                        accumulate=True, quiet=False):
+    """`model_galaxy_mcmc` on the parallel-tempered device sampler (`sampler.DeviceTemperedSampler`), for the
+    Bayesian evidence of the model: burn-in, reset and `iterations` sampling iterations as the reference runs
+    them, then the beta = 1 rung's database and posterior images exactly as `model_galaxy_mcmc` writes them, with
+    the header keys MCNTEMPS (rungs), MCLNZ / MCLNZERR (`log_evidence()` of the sampling iterations) and MCTSWAP
+    (mean swap acceptance).  The ladder is `betas`, or `default_betas(ntemps, tmax)` (defaults: DESIGN.md
+    section 13).  One-field models with every prior on the device.  Returns (model, database, (lnZ, err))."""
+    from .sampler import DeviceTemperedSampler, default_betas
+    if output_name is None:
+        output_name = 'out_' + model_file.replace('.py', '')
+    output_name += '_{}'
+    betas = default_betas(ntemps, tmax) if betas is None else np.asarray(betas, dtype=np.float64)
+    n_t = len(betas)
+    mc_model = model_file if isinstance(model_file, MultiComponentModel) else None
+    if mc_model is None:
+        n_hint = max(chains or 0, 1024)
+        n_chains = chains if chains is not None else 0
+        mc_model = MultiComponentModel(model_file, device=device, backend=backend,
+                                       max_walkers=max(n_hint, n_t * n_chains))
+    if chains is None:
+        chains = 2 * mc_model.num_params + 2
+    if n_t * chains > mc_model._max_walkers:
+        if isinstance(model_file, MultiComponentModel):
+            raise ValueError('model was built for at most {} walkers; {} temperatures x {} walkers need more'
+                             .format(mc_model._max_walkers, n_t, chains))
+        mc_model.close()
+        mc_model = MultiComponentModel(model_file, device=device, backend=backend, max_walkers=n_t * chains)
+    mc_model.engine
+    sampler = DeviceTemperedSampler(chains, mc_model, betas=betas)
+    if random_state is not None:
+        if isinstance(random_state, (int, np.integer)):
+            random_state = np.random.RandomState(int(random_state)).get_state()
+        sampler.random_state = random_state
+
+    db_name = output_name.format('db') + '.fits'
+    evidence = (float('nan'), float('nan'))
+    if not os.path.exists(db_name):
+        pos = np.stack([mc_model.init_params_from_priors(chains) for _ in range(n_t)])
+        lnlike = lnprior = None
+        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, iterations=burn)):
+            if not quiet:
+                print_progress(step, burn, 'Burning')
+        sampler.reset()
+        sampler.accumulate = bool(accumulate)
+        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, lnlike, lnprior,
+                                                                        iterations=iterations)):
+            if not quiet:
+                print_progress(step, iterations, 'Sampling')
+        sampler.accumulate = False
+        evidence = sampler.log_evidence(fburnin=0.0) if n_t > 1 and iterations > 0 else evidence
+        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
+                            ('MCCHAINS', chains), ('MCCONVRG', bool(check_convergence_autocorr(sampler))),
+                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())),
+                            ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
+                            ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+        database = save_database(sampler, mc_model, db_name, meta_dict=meta)
+    else:
+        print('Database already contains sampled chains, skipping sampling')
+        database = load_database(db_name)
+        if 'MCLNZ' in database.meta:
+            evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
+    save_posterior_images(mc_model, database, output_name=output_name, filetypes=write_fits)
+    return mc_model, database, evidence

@@ -397,6 +397,20 @@ class MultiComponentModel(object):
                  for lo in range(0, theta.shape[0], cap)]
         return np.concatenate(parts) if parts else np.zeros(0)
 
+    def log_likelihood_and_prior_batch(self, theta):
+        """(lnL [W], lnprior [W]) of W parameter vectors from ONE device evaluation, the two terms of
+        `log_posterior_batch` apart (psfmc_eval_theta_split): lnL is -inf outside the priors and where it is
+        not finite.  The tempered samplers work with these values (sampler.TemperedEnsembleSampler)."""
+        theta = self._theta(theta)
+        eng = self.engine
+        extra = self._host_prior_sum(theta)
+        cap = self._max_walkers
+        parts = [eng.loglike_prior_theta(theta[lo:lo + cap], None if extra is None else extra[lo:lo + cap])
+                 for lo in range(0, theta.shape[0], cap)]
+        if not parts:
+            return np.zeros(0), np.zeros(0)
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
     def log_posterior_batch_host(self, theta):
         """The same through host-side priors and derived rows (scipy.stats /
         scipy.special exactly as the reference calls them); the device only runs the

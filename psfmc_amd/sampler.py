@@ -24,7 +24,8 @@ import threading
 
 import numpy as np
 
-__all__ = ['EnsembleSampler', 'DeviceEnsembleSampler', 'FieldSetSampler', 'AutocorrError', 'integrated_time']
+__all__ = ['EnsembleSampler', 'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler',
+           'DeviceTemperedSampler', 'default_betas', 'AutocorrError', 'integrated_time']
 
 
 class AutocorrError(Exception):
@@ -542,4 +543,370 @@ class FieldSetSampler(object):
             for j in range(n):
                 yield [(chain[i][:, j, :].copy(), lnchain[i][:, j].copy(), block_states[i][j])
                        for i in range(n_f)]
+            done += n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Parallel tempering
+# ---------------------------------------------------------------------------------------------------------------------
+def default_betas(ntemps, tmax):
+    """The default inverse-temperature ladder of `ntemps` rungs: ntemps - 1 geometric rungs from 1 down to
+    1 / tmax, then beta = 0 (the prior, which the evidence needs).  ntemps = 1: (1,), plain sampling."""
+    ntemps = int(ntemps)
+    if ntemps < 1:
+        raise ValueError('ntemps must be at least 1')
+    if ntemps == 1:
+        return np.ones(1)
+    tmax = float(tmax)
+    if not (np.isfinite(tmax) and tmax > 1.0):
+        raise ValueError('tmax must be finite and greater than 1')
+    betas = np.concatenate([np.geomspace(1.0, 1.0 / tmax, ntemps - 1), [0.0]])
+    betas[0] = 1.0
+    return betas
+
+
+def check_betas(betas):
+    """A user ladder as float64 [T], or ValueError: finite, beta_0 = 1, strictly decreasing, and (T > 1) the last
+    rung 0 -- every device prior family is proper, so beta = 0 samples a proper prior."""
+    b = np.array(betas, dtype=np.float64).ravel()
+    if b.size < 1 or not np.all(np.isfinite(b)):
+        raise ValueError('the temperature ladder must be a non-empty list of finite betas')
+    if b[0] != 1.0:
+        raise ValueError('the first rung of the ladder must be beta = 1')
+    if np.any(np.diff(b) >= 0):
+        raise ValueError('the ladder must be strictly decreasing')
+    if b.size > 1 and b[-1] != 0.0:
+        raise ValueError('the last rung of the ladder must be beta = 0 (the evidence needs the prior rung)')
+    return b
+
+
+def _tempered(beta, lnlike, lnprior):
+    """beta lnL + lnpi -- that product, then that sum -- and -inf where lnL or lnpi is not finite."""
+    with np.errstate(invalid='ignore', over='ignore'):
+        v = beta * lnlike + lnprior
+    return np.where(np.isfinite(lnlike) & np.isfinite(lnprior), v, -np.inf)
+
+
+def _logsumexp(x):
+    m = np.max(x)
+    if not np.isfinite(m):
+        return m
+    return m + np.log(np.sum(np.exp(x - m)))
+
+
+def _stepping_stone(betas, lnlike):
+    """ln Z = sum_k [logsumexp((beta_k - beta_{k+1}) lnL^(k+1)) - ln N], lnlike [T, N] the samples of each rung."""
+    total = 0.0
+    for k in range(len(betas) - 1):
+        x = (betas[k] - betas[k + 1]) * lnlike[k + 1]
+        total += _logsumexp(x) - np.log(x.size)
+    return total
+
+
+class TemperedEnsembleSampler(object):
+    """Parallel-tempered stretch-move sampler: T copies of an ensemble of `nwalkers` walkers sample the tempered
+    posteriors beta_t lnL + lnpi on the ladder `betas` (1 = beta_0 > ... > beta_{T-1} = 0), and neighbouring
+    rungs swap walkers.  The stored lnL samples of every rung give the Bayesian evidence (`log_evidence`).
+
+    This numpy implementation is the contract: `DeviceTemperedSampler` reproduces it bit for bit.  It is NOT a
+    port of emcee 2's PTSampler (another z distribution and another split of the ensemble; emcee is not
+    available here to pin anything against).  Per iteration:
+      * the two half-steps of `EnsembleSampler.sample` (contiguous halves, h = 0 then 1); in each, for every rung
+        t = 0 ... T-1 in turn: z = ((a-1) rand(half) + 1)^2 / a, partner = randint(half, size=half) (the same
+        rung's other half), log_u = log(rand(half)); then ONE `like_prior_fn` call evaluates the T half proposals;
+        accept where ((P-1) ln z + lnp_new) - lnp > log_u, lnp = beta_t lnL + lnpi;
+      * swaps: for t = T-1 down to 1: i = permutation(W), j = permutation(W), log_u = log(rand(W)); pair k swaps
+        walker i[k] of rung t with walker j[k] of rung t-1 when log_u[k] < (beta_{t-1} - beta_t) (lnL[t, i[k]] -
+        lnL[t-1, j[k]]): positions, lnL and lnpi are exchanged, lnp recomputed at the new beta;
+      * then storage.
+    A walker whose lnpi or lnL is not finite has lnL = lnp = -inf at every beta.  With T = 1 (betas = (1,)) the
+    chain is `EnsembleSampler`'s, bit for bit.
+
+    like_prior_fn(theta [N, P]) -> (lnL [N], lnpi [N]), e.g. `model.log_likelihood_and_prior_batch`.
+    Stored: `chain` [W, n, P] and `lnprobability` [W, n] of the beta = 1 rung (what `save_database` and
+    `check_convergence_autocorr` read), `lnlikelihood` [T, W, n] of every rung; counters `naccepted_t` [T, W],
+    `nswap` [T-1]."""
+
+    def __init__(self, nwalkers, dim, betas, like_prior_fn, a=2.0):
+        if nwalkers % 2 or nwalkers < 2:
+            raise ValueError('The number of walkers must be even.')
+        self.k, self.dim, self.a = int(nwalkers), int(dim), float(a)
+        self.betas = check_betas(betas)
+        self.ntemps = len(self.betas)
+        self.like_prior_fn = like_prior_fn
+        self._random = np.random.mtrand.RandomState()
+        self.reset()
+
+    def reset(self):
+        self.iterations = 0
+        self.naccepted_t = np.zeros((self.ntemps, self.k))
+        self.nswap = np.zeros(max(self.ntemps - 1, 0))
+        self._chain = np.empty((self.k, 0, self.dim))
+        self._lnprob = np.empty((self.k, 0))
+        self._lnlike = np.empty((self.ntemps, self.k, 0))
+
+    clear_chain = reset
+
+    def clear_blobs(self):
+        pass
+
+    random_state = EnsembleSampler.random_state
+
+    @property
+    def naccepted(self):
+        return self.naccepted_t[0]
+
+    @property
+    def chain(self):
+        return self._chain
+
+    @property
+    def flatchain(self):
+        s = self._chain.shape
+        return self._chain.reshape(s[0] * s[1], s[2])
+
+    @property
+    def lnprobability(self):
+        return self._lnprob
+
+    @property
+    def flatlnprobability(self):
+        return self._lnprob.flatten()
+
+    @property
+    def lnlikelihood(self):
+        return self._lnlike
+
+    @property
+    def acceptance_fraction(self):
+        return self.naccepted_t[0] / max(self.iterations, 1)
+
+    @property
+    def temperature_acceptance_fraction(self):
+        return self.naccepted_t / max(self.iterations, 1)
+
+    @property
+    def tswap_acceptance_fraction(self):
+        return self.nswap / (max(self.iterations, 1) * self.k)
+
+    get_autocorr_time = EnsembleSampler.get_autocorr_time
+    acor = EnsembleSampler.acor
+
+    def log_evidence(self, fburnin=0.1):
+        """(ln Z, err): the stepping-stone estimate from the stored lnL samples of every rung after the first
+        `fburnin` of the stored iterations, ln Z = sum_k [logsumexp((beta_k - beta_{k+1}) lnL^(k+1)) - ln N];
+        err = |ln Z - the same estimate on every other rung| (rungs 0, 2, 4, ... and always the beta = 0 one).
+        Z is relative to the prior's normalisation over its support, the walkers' beta = 0 distribution."""
+        if self.ntemps < 2:
+            raise ValueError('the evidence needs a ladder of at least two rungs (beta = 1 ... beta = 0)')
+        n = self._lnlike.shape[2]
+        first = int(fburnin * n)
+        if n - first < 1:
+            raise ValueError('no stored samples after the burn-in')
+        samples = self._lnlike[:, :, first:].reshape(self.ntemps, -1)
+        lnz = _stepping_stone(self.betas, samples)
+        coarse = list(range(0, self.ntemps, 2))
+        if coarse[-1] != self.ntemps - 1:
+            coarse.append(self.ntemps - 1)
+        err = abs(lnz - _stepping_stone(self.betas[coarse], samples[coarse]))
+        return lnz, err
+
+    # -- state ----------------------------------------------------------------------------------------------------
+    def _start(self, p0):
+        p = np.array(p0, dtype=np.float64)
+        if p.shape != (self.ntemps, self.k, self.dim):
+            raise ValueError('p0 must have shape ({}, {}, {})'.format(self.ntemps, self.k, self.dim))
+        if np.any(~np.isfinite(p)):
+            raise ValueError('At least one parameter value was infinite or NaN.')
+        return p
+
+    def _like_prior(self, theta):
+        ll, lp = self.like_prior_fn(theta)
+        ll, lp = np.array(ll, dtype=np.float64), np.array(lp, dtype=np.float64)
+        ll[~(np.isfinite(ll) & np.isfinite(lp))] = -np.inf
+        return ll, lp
+
+    def _grow_storage(self, iterations, thin, storechain):
+        i0 = self._chain.shape[1]
+        if storechain:
+            n_keep = int(iterations // thin)
+            self._chain = np.concatenate((self._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
+            self._lnprob = np.concatenate((self._lnprob, np.zeros((self.k, n_keep))), axis=1)
+            self._lnlike = np.concatenate((self._lnlike, np.zeros((self.ntemps, self.k, n_keep))), axis=2)
+        return i0
+
+    def sample(self, p0, lnlike0=None, lnprior0=None, rstate0=None, iterations=1, thin=1, storechain=True):
+        """Generator: p0 [T, W, P] start positions (lnlike0 / lnprior0 [T, W] or None: evaluated); yields
+        (pos [T, W, P], lnL [T, W], lnpi [T, W], rstate) after every iteration -- a state to resume from."""
+        if rstate0 is not None:
+            self.random_state = rstate0
+        n_t, n_w, n_p = self.ntemps, self.k, self.dim
+        p = self._start(p0)
+        if lnlike0 is None or lnprior0 is None:
+            ll, lp = self._like_prior(p.reshape(n_t * n_w, n_p))
+            ll, lp = ll.reshape(n_t, n_w), lp.reshape(n_t, n_w)
+        else:
+            ll = np.array(lnlike0, dtype=np.float64).reshape(n_t, n_w)
+            lp = np.array(lnprior0, dtype=np.float64).reshape(n_t, n_w)
+            ll[~(np.isfinite(ll) & np.isfinite(lp))] = -np.inf
+        beta = self.betas[:, None]
+        lnp = _tempered(beta, ll, lp)
+        i0 = self._grow_storage(iterations, thin, storechain)
+        half = n_w // 2
+        rs = self._random
+        for i in range(int(iterations)):
+            self.iterations += 1
+            for s0, s1 in ((slice(0, half), slice(half, n_w)), (slice(half, n_w), slice(0, half))):
+                z = np.empty((n_t, half))
+                lu = np.empty((n_t, half))
+                q = np.empty((n_t, half, n_p))
+                for t in range(n_t):
+                    z[t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
+                    rint = rs.randint(half, size=(half,))
+                    lu[t] = np.log(rs.rand(half))
+                    c = p[t, s1][rint]
+                    q[t] = c - z[t][:, np.newaxis] * (c - p[t, s0])
+                nl, npri = self._like_prior(q.reshape(n_t * half, n_p))
+                nl, npri = nl.reshape(n_t, half), npri.reshape(n_t, half)
+                newlnp = _tempered(beta, nl, npri)
+                with np.errstate(invalid='ignore'):
+                    acc = (self.dim - 1.0) * np.log(z) + newlnp - lnp[:, s0] > lu
+                if np.any(acc):
+                    p[:, s0][acc] = q[acc]
+                    ll[:, s0][acc] = nl[acc]
+                    lp[:, s0][acc] = npri[acc]
+                    lnp[:, s0][acc] = newlnp[acc]
+                    self.naccepted_t[:, s0][acc] += 1
+            for t in range(n_t - 1, 0, -1):
+                ii = rs.permutation(n_w)
+                jj = rs.permutation(n_w)
+                lu = np.log(rs.rand(n_w))
+                with np.errstate(invalid='ignore'):
+                    acc = lu < (self.betas[t - 1] - self.betas[t]) * (ll[t, ii] - ll[t - 1, jj])
+                if np.any(acc):
+                    a, b = ii[acc], jj[acc]
+                    for arr in (p, ll, lp):
+                        arr[t, a], arr[t - 1, b] = arr[t - 1, b].copy(), arr[t, a].copy()
+                    lnp[t, a] = _tempered(self.betas[t], ll[t, a], lp[t, a])
+                    lnp[t - 1, b] = _tempered(self.betas[t - 1], ll[t - 1, b], lp[t - 1, b])
+                    self.nswap[t - 1] += int(np.count_nonzero(acc))
+            if storechain and i % thin == 0:
+                ind = i0 + int(i // thin)
+                self._chain[:, ind, :] = p[0]
+                self._lnprob[:, ind] = lnp[0]
+                self._lnlike[:, :, ind] = ll
+            yield p.copy(), ll.copy(), lp.copy(), self.random_state
+
+    def run_mcmc(self, pos0, N, lnlike0=None, lnprior0=None, rstate0=None, **kwargs):
+        results = None
+        for results in self.sample(pos0, lnlike0, lnprior0, rstate0, iterations=N, **kwargs):
+            pass
+        return results
+
+
+class DeviceTemperedSampler(TemperedEnsembleSampler):
+    """`TemperedEnsembleSampler` with every rung resident on the GPU (`psfmc_pt_run`): proposals of all T rungs
+    in one launch per half-step, one pipeline pass over T W/2 records, the tempered accept, the swaps and the
+    chain entries on the device.  The host draws the random numbers from the same `RandomState` in the same
+    order (the next block while the GPU runs the current one), so both samplers produce the same chain bit for
+    bit given lnL / lnpi as the device computes them (`model.log_likelihood_and_prior_batch`).  `block`
+    iterations per library call; `sample()` yields once per iteration with a resumable state, while the counters
+    and the stored chain advance a block at a time.
+
+    The ladder is `betas`, or `default_betas(ntemps, tmax)`.  The defaults (ntemps=16, tmax=1e6) are argued in
+    DESIGN.md section 13.  One-field `MultiComponentModel` only, every prior on the device; its `max_walkers`
+    must hold ntemps x nwalkers.  `accumulate`: posterior images of the beta = 1 rung after every iteration."""
+
+    def __init__(self, nwalkers, model, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
+        from .models import MultiComponentModel
+        from .engine import Context
+        if not isinstance(model, MultiComponentModel):
+            raise ValueError('the tempered device sampler serves one-field MultiComponentModel fits; FieldSets and '
+                             'joint fits are not supported')
+        if betas is None:
+            betas = default_betas(ntemps, tmax)
+        super(DeviceTemperedSampler, self).__init__(nwalkers, model.num_params, betas,
+                                                    model.log_likelihood_and_prior_batch, a=a)
+        self.model = model
+        self.block = int(block)
+        self.accumulate = bool(accumulate)
+        if self.ntemps * self.k > model._max_walkers:
+            raise ValueError('model was built for at most {} walkers; {} temperatures x {} walkers need more'
+                             .format(model._max_walkers, self.ntemps, self.k))
+        eng = model.engine
+        if type(eng) is not Context:
+            raise ValueError('the tempered device sampler serves one-field models only')
+        if model._host_priors:
+            raise ValueError('priors {} are evaluated on the host: the tempered device sampler cannot be '
+                             'used'.format([p.name for p, _ in model._host_priors]))
+
+    _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
+
+    def _draw(self, n_iter):
+        """Random numbers of n_iter iterations in the host sampler's order."""
+        n_t, n_w, half = self.ntemps, self.k, self.k // 2
+        n_s = max(n_t - 1, 0)
+        z = np.empty((n_iter, 2, n_t, half))
+        partner = np.empty((n_iter, 2, n_t, half), dtype=np.int32)
+        log_u = np.empty((n_iter, 2, n_t, half))
+        si = np.empty((n_iter, n_s, n_w), dtype=np.int32)
+        sj = np.empty((n_iter, n_s, n_w), dtype=np.int32)
+        slu = np.empty((n_iter, n_s, n_w))
+        rs = self._random
+        states = []
+        snap = self._state_snapshotter()
+        for it in range(n_iter):
+            for h in range(2):
+                for t in range(n_t):
+                    z[it, h, t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
+                    partner[it, h, t] = rs.randint(half, size=(half,))
+                    log_u[it, h, t] = np.log(rs.rand(half))
+            for t in range(n_t - 1, 0, -1):
+                si[it, t - 1] = rs.permutation(n_w)
+                sj[it, t - 1] = rs.permutation(n_w)
+                slu[it, t - 1] = np.log(rs.rand(n_w))
+            states.append(snap())
+        return (z, (self.dim - 1.0) * np.log(z), partner, log_u, si, sj, slu), states
+
+    def sample(self, p0, lnlike0=None, lnprior0=None, rstate0=None, iterations=1, thin=1, storechain=True):
+        if rstate0 is not None:
+            self.random_state = rstate0
+        p = self._start(p0)
+        ll = lp = None
+        if lnlike0 is not None and lnprior0 is not None:
+            ll, lp = np.array(lnlike0, dtype=np.float64), np.array(lnprior0, dtype=np.float64)
+        i0 = self._grow_storage(iterations, thin, storechain)
+        nacc = self.naccepted_t.astype(np.int64)
+        nsw = self.nswap.astype(np.int64)
+        eng = self.model.engine
+        done = 0
+        # the next block's random numbers are drawn while the GPU runs the current one (DeviceEnsembleSampler)
+        draws, states = self._draw(min(self.block, iterations)) if iterations > 0 else (None, None)
+        while done < iterations:
+            n = min(self.block, iterations - done)
+            n_next = min(self.block, iterations - done - n)
+            block_states = states
+            job = _run_async(eng.pt_run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
+                             accumulate=self.accumulate)
+            try:
+                draws, states = self._draw(n_next) if n_next > 0 else (None, None)
+            finally:
+                p, ll, lp, chain, lnchain, llchain, lpchain = job()
+            if self.accumulate:
+                self.model._device_samples += n * self.k
+                self.model.accumulated_samples += n * self.k
+            if storechain:
+                first = (-done) % thin
+                if first < n:
+                    count = (n - first + thin - 1) // thin
+                    dst = i0 + (done + first) // thin
+                    self._chain[:, dst:dst + count, :] = chain[0, :, first::thin, :]
+                    self._lnprob[:, dst:dst + count] = lnchain[:, first::thin]
+                    self._lnlike[:, :, dst:dst + count] = llchain[:, :, first::thin]
+            self.naccepted_t = nacc.astype(np.float64)
+            self.nswap = nsw.astype(np.float64)
+            self.iterations += n
+            for j in range(n):
+                yield (chain[:, :, j, :].copy(), llchain[:, :, j].copy(), lpchain[:, :, j].copy(),
+                       block_states[j])
             done += n
