@@ -199,6 +199,19 @@ int psfmc_set_layout(psfmc_ctx* ctx, int n_sky, int n_params, const int* slot_co
 #define PSFMC_PRIOR_WEIBULL_MAX 16
 #define PSFMC_PRIOR_INVGAMMA    17
 int psfmc_set_priors(psfmc_ctx* ctx, int field, int n_params, const int* family, const double* params);
+/*
+ * Pixel-integrated Sersic components (not the reference's profile): integrate[k] != 0 makes Sersic component k
+ * (model-file order among the Sersics) of observed field `field` (0 in an ordinary context) the PIXEL-INTEGRATED
+ * profile -- the plain profile times its full two-dimensional second-order term, midpoint grids in a box of
+ * pixels around the centre, recursive refinement of the pixel(s) that hold the centre (definition:
+ * psfmc_amd/ModelComponents/Sersic.py Sersic.integrated_image; kernels: csrc/psfmc_integrated.h) -- in every entry
+ * point that rasterises: rows and raw vectors, log-likelihoods, images, posterior sums, the device samplers, on both
+ * back ends and with either storage.  It is finite where the centre is a pixel centre (the default profile is NaN
+ * there).  The fields of one context keep their own flags.  A context that never receives a non-zero flag
+ * allocates nothing, launches nothing more and computes what it did without this call; the first non-zero flag
+ * allocates max_walkers images of the transform's size.  Call between batches (it waits for the context's stream).
+ */
+int psfmc_set_sersic_integrate(psfmc_ctx* ctx, int field, int n_sersic, const int* integrate);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -417,6 +430,8 @@ int psfmc_group_set_layout(psfmc_group* group, int n_sky, int n_params, const in
                            const double* p2);
 /* psfmc_set_priors on every device of the group */
 int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, const double* params);
+/* psfmc_set_sersic_integrate (field 0) on every device of the group */
+int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,
                            double* loglike);
 int psfmc_group_eval_theta(psfmc_group* group, int W, const double* theta, const double* extra_lnprior,

@@ -4,10 +4,27 @@ from scipy.special import gamma, gammaincinv
 from .ComponentBase import ComponentBase, StochasticProperty
 
 
+# Constants of the pixel-integrated profile (`integrate=True`); fixed per build, the same on the device
+# (csrc/psfmc_integrated.h).  DESIGN.md section "Pixel-integrated Sersic profile" says how they were chosen.
+INTEG_HALF_BOX = 3        # H: midpoint grids in the (2H+1)^2 pixels around the pixel nearest the centre
+INTEG_GRID_NEAR = 8       # s x s samples per pixel at Chebyshev distance <= INTEG_NEAR_RING ...
+INTEG_NEAR_RING = 1
+INTEG_GRID_FAR = 4        # ... and further out in the box
+INTEG_SPLIT = 4           # s0: a cell that holds the centre is split s0 x s0
+INTEG_LEVELS = 8          # L: the sub-cell(s) holding the centre are split again, L times
+INTEG_SUB = 4             # midpoint grid of every sub-cell that is not split (even: see integrated_image)
+
+
 class Sersic(ComponentBase):
     """Elliptical Sersic profile (reference: ModelComponents/Sersic.py:16-45).
     `reff` / `reff_b` are the semi-major / semi-minor effective radii, `angle`
-    the position angle (CCW of up; radians unless `angle_degrees`)."""
+    the position angle (CCW of up; radians unless `angle_degrees`).
+
+    The default profile is the reference's: the profile at the pixel centre times a one-dimensional
+    centroid correction, which is NaN in the pixel whose centre is the component's centre (0/0), so that
+    such a walker's log-posterior is -inf.  `integrate=True` asks for the PIXEL-INTEGRATED profile instead
+    (`Sersic.integrated_image`; not the reference's): finite everywhere, an on-pixel centre included, and
+    several times closer to GALFIT's rendering in the core."""
     device_kind = 'sersic'
     _fits_abbrs = [('Sersic', 'SER'), ('reff_b', 'REB'), ('reff', 'RE'),
                    ('index', 'N'), ('angle', 'ANG')]
@@ -20,7 +37,7 @@ class Sersic(ComponentBase):
     angle = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
-                 angle=None, angle_degrees=False):
+                 angle=None, angle_degrees=False, integrate=False):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -29,6 +46,12 @@ class Sersic(ComponentBase):
         self.index = index
         self.angle = angle
         self.angle_degrees = angle_degrees
+        self.integrate = bool(integrate)
+
+    def header_flags(self, count):
+        """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
+        when it is the pixel-integrated profile, nothing otherwise."""
+        return {'{:d}SERINT'.format(count): True} if self.integrate else {}
 
     # axis-ratio constraint: reff_b <= reff (Sersic.py:41-45)
     def log_priors(self):
@@ -53,3 +76,114 @@ class Sersic(ComponentBase):
         return flux_tot / (np.pi * reff * reff_b * 2 * index *
                            np.exp(kappa + np.log(kappa) * -2 * index) *
                            gamma(2 * index))
+
+    # -- host meaning of the profile ---------------------------------------------------------------
+    def derived_row(self, mag_zp):
+        """The nine scalars the rasterisers work from (include/psfmc_hip.h, Sersic block of a row) for this
+        component's current values: x0, y0, the rows of the inverse ellipse matrix, kappa, 1/(2n), Sigma_e."""
+        angle = np.deg2rad(self.angle) if self.angle_degrees else self.angle
+        sin_t, cos_t = np.sin(angle + 0.5 * np.pi), np.cos(angle + 0.5 * np.pi)
+        kappa = Sersic.kappa(self.index)
+        flux = 10 ** (-0.4 * (self.mag - mag_zp))
+        xy = np.ravel(self.xy)
+        return np.array([xy[0], xy[1], cos_t / self.reff, sin_t / self.reff, -sin_t / self.reff_b,
+                         cos_t / self.reff_b, kappa, 0.5 / self.index,
+                         Sersic.sb_eff(flux, self.index, self.reff, self.reff_b, kappa)], dtype=np.float64)
+
+    def add_to_array(self, arr, mag_zp):
+        """Add this component (current values) to `arr` on the host: the reference's formula, or the
+        pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
+        row = self.derived_row(mag_zp)
+        arr += (Sersic.integrated_image(row, arr.shape) if self.integrate
+                else Sersic.reference_image(row, arr.shape))
+        return arr
+
+    @staticmethod
+    def _plain(row, x, y):
+        """Sigma_e exp(-kappa (rho^(1/n) - 1)) at the points (x, y); at rho = 0 its finite peak Sigma_e e^kappa.
+        Returns (f, u, v, q = rho^2, t = q^p)."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        dx, dy = x - x0, y - y0
+        u = m00 * dx + m01 * dy
+        v = m10 * dx + m11 * dy
+        q = u * u + v * v
+        with np.errstate(all='ignore'):
+            t = np.where(q > 0, np.exp(np.log(q) * p), 0.0)
+            return sbeff * np.exp(-kappa * (t - 1)), u, v, q, t
+
+    @staticmethod
+    def reference_image(row, shape):
+        """The reference's profile (Sersic.py:98-153) from a derived row: NaN where the centre is a pixel centre."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+        f, _, _, q, t = Sersic._plain(row, xx, yy)
+        with np.errstate(all='ignore'):
+            g = -2 * kappa * p * t / np.sqrt(q)
+            return f * (1 + g * (q / ((xx - x0) ** 2 + (yy - y0) ** 2) / 12 * g))
+
+    @staticmethod
+    def integrated_image(row, shape, half_box=INTEG_HALF_BOX, grid=None, split=INTEG_SPLIT, levels=INTEG_LEVELS,
+                         sub=INTEG_SUB):
+        """The pixel-integrated profile of one component on a `shape` image, from its derived row.  This numpy
+        text is the DEFINITION the device kernels are held to.
+
+        1. Every pixel: f (1 + lap f / (24 f)) with f the plain profile at the pixel centre -- the full
+           two-dimensional second-order term of the mean over the pixel.
+        2. The (2H+1)^2 pixels around (px, py) = floor(centre + 1/2), clipped to the image: the mean of f over an
+           s x s midpoint grid, s = `grid(d)` of the Chebyshev distance d from (px, py).
+        3. Every pixel whose closed square holds the centre (one, two on an edge, four on a corner): on the
+           global grid of pitch h_l = split^-l (l = 0: the pixels), the cells that hold the centre in their closed
+           square are split `split` x `split`; a sub-cell that is itself such a cell of level l + 1 is left to
+           that level (l < levels), every other one adds (h_l / split)^2 times the mean of f over its `sub` x `sub`
+           midpoint grid.  At the last level every sub-cell is sampled.  `sub` is even, so a sample never falls on
+           its cell's centre, edges or corners; should the centre coincide with a sample all the same, f there is
+           its finite peak Sigma_e e^kappa (`_plain`).  "Holds" is decided on g = (centre + 1/2) split^l: cell
+           floor(g) always, cell floor(g) - 1 as well where g is an integer."""
+        if grid is None:
+            grid = lambda d: INTEG_GRID_NEAR if d <= INTEG_NEAR_RING else INTEG_GRID_FAR
+        if sub % 2:
+            raise ValueError('sub must be even')
+        ny, nx = shape
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        yy, xx = np.mgrid[0:ny, 0:nx].astype(np.float64)
+        f, u, v, q, t = Sersic._plain(row, xx, yy)
+        ie2, ib2 = m00 * m00 + m01 * m01, m10 * m10 + m11 * m11          # 1 / r_e^2, 1 / r_b^2
+        with np.errstate(all='ignore'):
+            tt = kappa * p * t / q
+            lap = (tt * tt - tt * (p - 1) / q) * 4 * (u * u * ie2 + v * v * ib2) - 2 * tt * (ie2 + ib2)
+            img = f * (1 + lap / 24)
+        gx, gy = x0 + 0.5, y0 + 0.5
+        if not (np.isfinite(gx) and np.isfinite(gy)) or abs(gx) > 2.0 ** 30 or abs(gy) > 2.0 ** 30:
+            return img                                                  # (no pixel of any image is near)
+        px, py = int(np.floor(gx)), int(np.floor(gy))
+
+        def held(g, scale):               # indices of the pitch-1/scale cells holding the centre along one axis
+            a = np.floor(g * scale)
+            return ([int(a) - 1] if g * scale == a else []) + [int(a)]
+        for j in range(max(py - half_box, 0), min(py + half_box + 1, ny)):
+            for i in range(max(px - half_box, 0), min(px + half_box + 1, nx)):
+                if i in held(gx, 1.0) and j in held(gy, 1.0):
+                    img[j, i] = 0.0                                     # part 3 below
+                    continue
+                s = grid(max(abs(i - px), abs(j - py)))
+                o = (np.arange(s) + 0.5) / s - 0.5
+                sx, sy = np.meshgrid(i + o, j + o)
+                img[j, i] = Sersic._plain(row, sx, sy)[0].mean()
+        o = (np.arange(sub) + 0.5) / sub
+        for l in range(levels + 1):
+            scale = float(split) ** l
+            cw = 1.0 / (scale * split)                                  # sub-cell pitch of this level
+            nxt_x, nxt_y = held(gx, scale * split), held(gy, scale * split)
+            for cy in held(gy, scale):
+                for cx in held(gx, scale):
+                    i, j = int(np.floor(cx / scale)), int(np.floor(cy / scale))      # the pixel of this cell
+                    if not (0 <= i < nx and 0 <= j < ny):
+                        continue
+                    for b in range(split):
+                        for a in range(split):
+                            ix, iy = cx * split + a, cy * split + b
+                            if l < levels and ix in nxt_x and iy in nxt_y:
+                                continue
+                            sx, sy = np.meshgrid(ix * cw - 0.5 + o * cw, iy * cw - 0.5 + o * cw)
+                            img[j, i] += cw * cw * Sersic._plain(row, sx, sy)[0].mean()
+        return img

@@ -274,7 +274,11 @@ __global__ void k_pack_field(const double* __restrict__ sci, const double* __res
 // ---------------------------------------------------------------------------
 // WRAP: the image is embedded in a larger transform size (psfmc_device.h WrapDesc); ny, NX are the
 // transform's sides, wrap_tab the context's descriptors per kernel spectrum (walker_wrap)
-template <int NX, bool FROM_IMAGE, typename TS = cd, bool FAST = FftShape<NX>::kPlain, bool WRAP = false>
+// EXTRA (rasterising instantiations only; its own instantiation, so that the kernels of a model without the
+// keyword are the same code as before): `img` is [n][ny][NX], per walker the sum of its pixel-integrated Sersic
+// components at model coordinates (psfmc_integrated.h), added to the rasterised row unless ps_only
+template <int NX, bool FROM_IMAGE, typename TS = cd, bool FAST = FftShape<NX>::kPlain, bool WRAP = false,
+          bool EXTRA = false>
 __global__ void __launch_bounds__((row_threads<NX, FAST>()), (fused_row_min_waves<NX, false, WRAP>()))
 k_rows_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
            const cd* __restrict__ twx, TS* __restrict__ Tbuf, int n_ps, int n_sersic, int ny,
@@ -348,6 +352,23 @@ k_rows_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
             // form spilled or lost a wave -- embedded 586^2 -17 %, 698^2 -21 % whole step)
             raster_row<P, T, 0, WRAP, WRAP ? 1 : raster_group<NX>()>(wprep, n_ps, n_sersic, t, iy, ps_only != 0, log_tab, r,
                                                                     wr, pow_mode);
+        }
+        if constexpr (EXTRA) {
+            if (!ps_only && row_on) {
+                const double* ex = img + (size_t)w * Spx;
+                if constexpr (WRAP) {
+                    // (as raster_row: transform pixel -> model pixel; zeros beyond the wrap-around margin)
+                    const double* exr = ex + (size_t)wrap_coord(iy, wr.ay, wr.ly) * NX;
+                    if (iy < wr.ey) {
+#pragma unroll
+                        for (int k = 0; k < P; ++k)
+                            if (T * k + t < wr.ex) r[k] += exr[wrap_coord(T * k + t, wr.ax, wr.lx)];
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < P; ++k) r[k] += ex[(size_t)iy * NX + T * k + t];
+                }
+            }
         }
         wave_lds_sync();
 #pragma unroll
@@ -1463,11 +1484,12 @@ template <int NX> struct RasterShape<NX, false> {
 
 template <int P> constexpr int raster_seg() { return P <= 16 ? P : (P % 16 == 0 ? 16 : P % 15 == 0 ? 15 : P % 12 == 0 ? 12 : P % 10 == 0 ? 10 : P % 9 == 0 ? 9 : P % 7 == 0 ? 7 : P % 5 == 0 ? 5 : P); }
 
-template <int NX, int K0, int SEG, bool WRAP>
+// extra (EXTRA instantiations): [n_w][ny][NX] the walkers' pixel-integrated components (psfmc_integrated.h)
+template <int NX, int K0, int SEG, bool WRAP, bool EXTRA>
 __device__ __forceinline__ void raster_sums_segment(const double* __restrict__ prep, int plen, int w0, int w1, int psf,
                                                     int n_ps, int n_sersic, int t, int iy, bool row_on,
                                                     double* __restrict__ log_tab, double* __restrict__ out,
-                                                    size_t S, const WrapDesc& wr) {
+                                                    size_t S, const WrapDesc& wr, const double* __restrict__ extra) {
     constexpr int T = RasterShape<NX>::T;
     double a[SEG], b[SEG], cps[SEG];
 #pragma unroll
@@ -1479,6 +1501,22 @@ __device__ __forceinline__ void raster_sums_segment(const double* __restrict__ p
         // (log2 + exp2 form at every size: a segment is 7 ... 16 pixels per lane, and the power tables would be
         // fetched again for each -- 512^2, 256 walkers: 0.59 ms per iteration of image sums with them, 0.46 without)
         raster_row_logexp<SEG, T, K0, WRAP>(wprep, n_ps, n_sersic, t, iy, false, log_tab, r, wr);
+        if constexpr (EXTRA) {
+            if (row_on) {
+                const double* ex = extra + (size_t)w * S;
+                if constexpr (WRAP) {
+                    const double* exr = ex + (size_t)wrap_coord(iy, wr.ay, wr.ly) * NX;
+                    if (iy < wr.ey) {
+#pragma unroll
+                        for (int k = 0; k < SEG; ++k)
+                            if (T * (K0 + k) + t < wr.ex) r[k] += exr[wrap_coord(T * (K0 + k) + t, wr.ax, wr.lx)];
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < SEG; ++k) r[k] += ex[(size_t)iy * NX + T * (K0 + k) + t];
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < SEG; ++k) {
             a[k] += r[k];
@@ -1501,16 +1539,17 @@ __device__ __forceinline__ void raster_sums_segment(const double* __restrict__ p
     }
 }
 
-template <int NX, int K0, bool WRAP>
+template <int NX, int K0, bool WRAP, bool EXTRA>
 __device__ __forceinline__ void raster_sums_all(const double* __restrict__ prep, int plen, int w0, int w1, int psf,
                                                 int n_ps, int n_sersic, int t, int iy, bool row_on,
                                                 double* __restrict__ log_tab, double* __restrict__ out, size_t S,
-                                                const WrapDesc& wr) {
+                                                const WrapDesc& wr, const double* __restrict__ extra) {
     constexpr int P = RasterShape<NX>::P, SEG = raster_seg<P>();
     if constexpr (K0 < P) {
-        raster_sums_segment<NX, K0, SEG, WRAP>(prep, plen, w0, w1, psf, n_ps, n_sersic, t, iy, row_on, log_tab, out, S,
-                                               wr);
-        raster_sums_all<NX, K0 + SEG, WRAP>(prep, plen, w0, w1, psf, n_ps, n_sersic, t, iy, row_on, log_tab, out, S, wr);
+        raster_sums_segment<NX, K0, SEG, WRAP, EXTRA>(prep, plen, w0, w1, psf, n_ps, n_sersic, t, iy, row_on, log_tab, out,
+                                                      S, wr, extra);
+        raster_sums_all<NX, K0 + SEG, WRAP, EXTRA>(prep, plen, w0, w1, psf, n_ps, n_sersic, t, iy, row_on, log_tab, out, S,
+                                                   wr, extra);
     }
 }
 
@@ -1518,11 +1557,14 @@ __device__ __forceinline__ void raster_sums_all(const double* __restrict__ prep,
 // field f0) and a group never straddles two fields: the group then only looks at its own field's npf
 // kernel spectra and writes part[group][npf][3][ny][NX] (k_sum_partials_fields adds a field's groups up).
 // per_field == 0: any mixture of kernel spectra, part[group][n_psf][3][ny][NX].
-template <int NX, bool WRAP = false>
-__global__ void __launch_bounds__(64) k_raster_sums(const double* __restrict__ prep, int plen, int n_w, int group_size,
-                                                    int n_ps, int n_sersic, int ny, int n_psf,
-                                                    double* __restrict__ part, int per_field, int f0, int npf,
-                                                    const WrapDesc* __restrict__ wrap_tab) {
+// EXTRA: `wrap_tab` is followed by the walkers' pixel-integrated images (its own instantiation and signature: the
+// kernel of a model without the keyword is the code it was)
+template <int NX, bool WRAP, bool EXTRA>
+__device__ __forceinline__ void raster_sums_body(const double* __restrict__ prep, int plen, int n_w, int group_size,
+                                                 int n_ps, int n_sersic, int ny, int n_psf,
+                                                 double* __restrict__ part, int per_field, int f0, int npf,
+                                                 const WrapDesc* __restrict__ wrap_tab,
+                                                 const double* __restrict__ extra) {
     using S = RasterShape<NX>;
     constexpr int T = S::T, RG = S::TPW;
     static_assert(S::P % raster_seg<S::P>() == 0, "segment");
@@ -1542,8 +1584,25 @@ __global__ void __launch_bounds__(64) k_raster_sums(const double* __restrict__ p
     WrapDesc wr{0, 0, 0, 0, 0, 0};
     if constexpr (WRAP) wr = wrap_tab[__builtin_amdgcn_readfirstlane(psf0)];
     for (int p = 0; p < n_here; ++p)
-        raster_sums_all<NX, 0, WRAP>(prep, plen, w0, w1, psf0 + p, n_ps, n_sersic, t, row_on ? iy : 0, row_on, log_tab,
-                                     part + ((size_t)g * n_here + p) * 3 * Spx, Spx, wr);
+        raster_sums_all<NX, 0, WRAP, EXTRA>(prep, plen, w0, w1, psf0 + p, n_ps, n_sersic, t, row_on ? iy : 0, row_on,
+                                            log_tab, part + ((size_t)g * n_here + p) * 3 * Spx, Spx, wr, extra);
+}
+template <int NX, bool WRAP = false>
+__global__ void __launch_bounds__(64) k_raster_sums(const double* __restrict__ prep, int plen, int n_w, int group_size,
+                                                    int n_ps, int n_sersic, int ny, int n_psf,
+                                                    double* __restrict__ part, int per_field, int f0, int npf,
+                                                    const WrapDesc* __restrict__ wrap_tab) {
+    raster_sums_body<NX, WRAP, false>(prep, plen, n_w, group_size, n_ps, n_sersic, ny, n_psf, part, per_field, f0, npf,
+                                      wrap_tab, nullptr);
+}
+template <int NX, bool WRAP = false>
+__global__ void __launch_bounds__(64) k_raster_sums_extra(const double* __restrict__ prep, int plen, int n_w,
+                                                          int group_size, int n_ps, int n_sersic, int ny, int n_psf,
+                                                          double* __restrict__ part, int per_field, int f0, int npf,
+                                                          const WrapDesc* __restrict__ wrap_tab,
+                                                          const double* __restrict__ extra) {
+    raster_sums_body<NX, WRAP, true>(prep, plen, n_w, group_size, n_ps, n_sersic, ny, n_psf, part, per_field, f0, npf,
+                                     wrap_tab, extra);
 }
 
 // lin[i] += part[0][i] + part[1][i] + ... (fixed order)

@@ -31,6 +31,9 @@
 #include "psfmc_fused_path.h"
 #include "psfmc_rows3_path.h"
 #include "psfmc_theta.h"
+#if PSFMC_PART == 0
+#include "psfmc_integrated.h"
+#endif
 
 using namespace psfmc;
 
@@ -439,7 +442,20 @@ struct psfmc_ctx {
     // parallel-tempering state (psfmc_pt_run): one grow-only allocation carved per call
     unsigned char* pt_blob = nullptr;
     size_t pt_cap = 0;
+    // pixel-integrated Sersic components (psfmc_set_sersic_integrate, psfmc_integrated.h); nothing is allocated and
+    // no kernel changes until a flag is set
+    bool integ_any = false;
+    std::vector<uint8_t> integ_flags;    // [n_fields][n_sersic]
+    uint8_t* d_integ_flags = nullptr;
+    double* d_integ_par = nullptr;       // [max_walkers][n_sersic][9] the integrated components' real blocks
+    double* d_integ_img = nullptr;       // [max_walkers][S] sum of a walker's integrated components, model coordinates
 };
+
+// the integrated-components image of the walker whose record `prep` points at (nullptr: none to add)
+static const double* integ_image_of(const psfmc_ctx* c, const double* prep) {
+    if (!c->integ_any || !prep) return nullptr;
+    return c->d_integ_img + (size_t)((prep - c->d_prep) / c->plen) * c->S;
+}
 
 // a field's image window inside the transform-shaped pixel arrays (all of them unless the image is embedded)
 static ImgWindow img_window(const psfmc_ctx* c, int field) {
@@ -467,22 +483,28 @@ template <int N> constexpr bool plain_side() {
 template <int N, typename TS> constexpr bool storage_built() { return sizeof(TS) == sizeof(cd) || plain_side<N>(); }
 
 // ---- the three-stage row kernels (psfmc_rows3_path.h) ----
-template <int NX, bool FROM_IMAGE, bool WRAP>
+template <int NX, bool FROM_IMAGE, bool WRAP, bool EXTRA = false>
 static int launch_rows3_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, cd* Tbuf, int ps_only,
                                    const double* img, const double* img_scale, double* raw_out, hipStream_t st) {
     using S = typename Rows3<NX>::S;
     constexpr size_t lds = rows3_lds_bytes<S>();
+    if constexpr (!FROM_IMAGE && !EXTRA) {
+        // pixel-integrated components: the same kernel with their image added (its own instantiation)
+        if (const double* extra = ps_only ? nullptr : integ_image_of(c, prep))
+            return launch_rows3_fwd_kernel<NX, false, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra, img_scale, raw_out,
+                                                                  st);
+    }
     if constexpr (lds > 64 * 1024) {
         static thread_local int attr_device = -1;
         if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows3_fwd<NX, FROM_IMAGE, WRAP>),
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows3_fwd<NX, FROM_IMAGE, WRAP, S, EXTRA>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr_device = c->device;
         }
     }
     if (!FROM_IMAGE && !c->prep_tabs_valid)
         return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
-    hipLaunchKernelGGL((k_rows3_fwd<NX, FROM_IMAGE, WRAP>), dim3((c->ny + rows3_waves(NX) - 1) / rows3_waves(NX), n),
+    hipLaunchKernelGGL((k_rows3_fwd<NX, FROM_IMAGE, WRAP, S, EXTRA>), dim3((c->ny + rows3_waves(NX) - 1) / rows3_waves(NX), n),
                        dim3(rows3_threads(NX)), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic, c->ny, ps_only, img,
                        img_scale, raw_out, c->d_wrap, c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
     return PSFMC_OK;
@@ -529,15 +551,21 @@ static int launch_rows3_inv(psfmc_ctx* c, int n, const cd* Tbuf, const double* p
     }
 }
 
-template <int NX, bool FROM_IMAGE, typename TS, bool FAST, bool WRAP>
+template <int NX, bool FROM_IMAGE, typename TS, bool FAST, bool WRAP, bool EXTRA = false>
 static int launch_rows_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, TS* Tbuf,
                                   int ps_only, const double* img, const double* img_scale, double* raw_out,
                                   hipStream_t st) {
     constexpr size_t lds = fused_row_lds_bytes<NX, FAST>();
+    if constexpr (!FROM_IMAGE && !EXTRA) {
+        // pixel-integrated components: the same kernel with their image added (its own instantiation)
+        if (const double* extra = ps_only ? nullptr : integ_image_of(c, prep))
+            return launch_rows_fwd_kernel<NX, false, TS, FAST, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra,
+                                                                           img_scale, raw_out, st);
+    }
     if constexpr (lds > 64 * 1024) {
         static thread_local int attr_device = -1;
         if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP>),
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP, EXTRA>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr_device = c->device;
         }
@@ -545,7 +573,7 @@ static int launch_rows_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const
     constexpr int waves = row_waves<NX, FAST>();
     if (!FROM_IMAGE && !c->prep_tabs_valid)
         return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
-    hipLaunchKernelGGL((k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP>), dim3((c->nblk + waves - 1) / waves, n),
+    hipLaunchKernelGGL((k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP, EXTRA>), dim3((c->nblk + waves - 1) / waves, n),
                        dim3((row_threads<NX, FAST>())), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic,
                        c->ny, ps_only, img, img_scale, raw_out, c->d_wrap,
                        c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
@@ -797,6 +825,17 @@ template <int NX>
 static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int groups, int group_size, hipStream_t st,
                               int per_field, int f0) {
     constexpr int RG = RasterShape<NX>::TPW;
+    if (const double* extra = integ_image_of(c, prep)) {      // pixel-integrated components: their image is added
+        if (c->embed)
+            hipLaunchKernelGGL((k_raster_sums_extra<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
+                               c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
+                               f0, c->n_psf_field, c->d_wrap, extra);
+        else
+            hipLaunchKernelGGL((k_raster_sums_extra<NX, false>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
+                               c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
+                               f0, c->n_psf_field, c->d_wrap, extra);
+        return PSFMC_OK;
+    }
     if (c->embed) {
         hipLaunchKernelGGL((k_raster_sums<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
                            c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
@@ -1533,7 +1572,8 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_layout_blob, c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
-                    c->stretch.nacc, c->stretch.accflag, c->pt_blob};
+                    c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
+                    c->d_integ_img};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1700,7 +1740,7 @@ static int hipfft_convolve(psfmc_ctx* c, int n, const double* d_prep, const uint
     const size_t lds = (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double);
     RC_TRY(use_plans(c, 2 * n));
     hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256), lds, st, d_prep, d_skip,
-                       c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, ps_only);
+                       c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, ps_only, integ_image_of(c, d_prep));
     FFT_TRY(hipfftSetStream(c->plan_fwd, st));
     FFT_TRY(hipfftSetStream(c->plan_inv, st));
     FFT_TRY(hipfftExecD2Z(c->plan_fwd, c->d_real, (hipfftDoubleComplex*)c->d_spec));
@@ -1827,6 +1867,22 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
     const double p = rec[kPrepHead + kPrepPs * n_ps + kPrepSersic * k + 7];
     build_pow_table(p, rec + prep_rec_len(n_ps, n_sersic) + (size_t)k * kPowTab, lane);
 }
+// Pixel-integrated Sersic components (psfmc_integrated.h): after every kernel that writes prep records, same
+// stream, the walkers' integrated images are formed and the components' blocks made neutral for the rasterisers.
+static void launch_integrated(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
+    if (!c->integ_any || n <= 0) return;
+    double* prep = c->d_prep + (size_t)w_off * c->plen;
+    double* ipar = c->d_integ_par + (size_t)w_off * c->n_sersic * kPrepSersic;
+    double* img = c->d_integ_img + (size_t)w_off * c->S;
+    const int items = n * c->n_sersic;
+    hipLaunchKernelGGL(k_integ_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen, skip, ipar,
+                       c->d_integ_flags, c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
+    hipLaunchKernelGGL(k_integ_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, ipar,
+                       c->d_integ_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
+    hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
+                       c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
+}
+
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
 // function, same bits; ~400 instructions per wave and component) -- a kernel boundary plus a one-wave-per-pair
 // kernel are 4 ... 5 us of a small ensemble's half-step.  "Small" = up to this many (row wave, component) pairs in
@@ -1835,7 +1891,9 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 constexpr int kInWavePowTabWaves = 8192;
 // walkers [w_off, w_off + n) of c->d_prep; after the kernel that wrote their records, same stream.
 // (Only the forward row kernels read the tables: k_raster_sums keeps the log2 + exp2 form at every size.)
+static void launch_integrated(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st);
 static void launch_pow_tables(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
+    launch_integrated(c, n, w_off, skip, st);         // (before the tables: it rewrites the integrated components' blocks)
     c->prep_tabs_valid = true;
     if (c->backend != PSFMC_BACKEND_FUSED || c->n_sersic == 0 || n <= 0 || !c->use_pow_tabs) return;
     const int pairs = n * c->n_sersic;
@@ -2005,7 +2063,8 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
         if (raw && !fused) {   // raw model before the inverse transform overwrites it
             hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256),
                                (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double), st, prep,
-                               (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0);
+                               (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0,
+                               integ_image_of(c, prep));
             rc = emit(raw, c->d_real, 2, 0, IMG_COPY);
             if (rc != PSFMC_OK) break;
         }
@@ -2154,6 +2213,30 @@ static int prior_table(int n_params, const int* family, const double* params, st
         prior_prepare(family[i], p, e);
         for (int j = 0; j < 5; ++j) tab[(size_t)j * n_params + i] = e[j];
     }
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_set_sersic_integrate(psfmc_ctx* c, int field, int n_sersic, const int* integrate) {
+    if (!c || !integrate) return fail(PSFMC_EINVAL, "NULL argument");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->integ_flags.empty()) c->integ_flags.assign((size_t)c->n_fields * c->n_sersic, 0);
+    for (int k = 0; k < n_sersic; ++k) c->integ_flags[(size_t)field * n_sersic + k] = integrate[k] ? 1 : 0;
+    bool any = false;
+    for (uint8_t f : c->integ_flags) any = any || f;
+    if (any && !c->d_integ_img) {
+        HIP_TRY(hipMalloc(&c->d_integ_flags, c->integ_flags.size()));
+        HIP_TRY(hipMalloc(&c->d_integ_par, (size_t)c->max_walkers * c->n_sersic * kPrepSersic * sizeof(double)));
+        if (hipMalloc(&c->d_integ_img, (size_t)c->max_walkers * c->S * sizeof(double)) != hipSuccess)
+            return fail(PSFMC_ENOMEM, "hipMalloc (integrated-profile images: %d walkers x %d pixels)", c->max_walkers,
+                        c->S);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (no batch in flight reads the flags)
+    if (c->d_integ_flags)
+        HIP_TRY(hipMemcpy(c->d_integ_flags, c->integ_flags.data(), c->integ_flags.size(), hipMemcpyHostToDevice));
+    c->integ_any = any;
+    c->prep_tabs_valid = false;                        // records written under the old flags are not to be rasterised
     return PSFMC_OK;
 }
 
@@ -2535,7 +2618,8 @@ static int accumulate_from_prep(psfmc_ctx* c, int W, hipStream_t st, int f0 = 0,
         } else {
             hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256),
                                (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double), st, prep,
-                               (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0);
+                               (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0,
+                               integ_image_of(c, prep));
             acc(c->d_real, 2, 0, 0, n);
             RC_TRY(hipfft_convolve(c, n, prep, nullptr, st, 0));
         }
@@ -3500,6 +3584,12 @@ extern "C" int psfmc_group_set_layout(psfmc_group* g, int n_sky, int n_params, c
 extern "C" int psfmc_group_set_priors(psfmc_group* g, int n_params, const int* family, const double* params) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_priors(c, 0, n_params, family, params));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_sersic_integrate(psfmc_group* g, int n_sersic, const int* integrate) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_sersic_integrate(c, 0, n_sersic, integrate));
     return PSFMC_OK;
 }
 

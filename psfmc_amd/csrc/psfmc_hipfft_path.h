@@ -18,11 +18,12 @@ __global__ void k_prep(const double* __restrict__ rows, double* __restrict__ pre
                prep + (size_t)w * prep_len(n_ps, n_sersic), n_ps, n_sersic, ny, nx, rho, n_psf, psf_base);
 }
 
-// raw model and its square: real[(2w)][S] = raw, real[(2w+1)][S] = raw^2
+// raw model and its square: real[(2w)][S] = raw, real[(2w+1)][S] = raw^2; extra (optional): [W][S] added to raw
 // (models.py:213, :277).  grid (ceil(S / (256*4)), W)
 __global__ void __launch_bounds__(256)
 k_raster(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
-         double* __restrict__ real, int n_ps, int n_sersic, int ny, int nx, int ps_only) {
+         double* __restrict__ real, int n_ps, int n_sersic, int ny, int nx, int ps_only,
+         const double* __restrict__ extra) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     extern __shared__ double s_prep[];
@@ -38,7 +39,9 @@ k_raster(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
         const int idx = base + j * 256;
         if (idx < S) {
             const int iy = idx / nx, ix = idx - iy * nx;
-            const double v = raster_pixel(s_prep, n_ps, n_sersic, ix, iy, ps_only != 0);
+            double v = raster_pixel(s_prep, n_ps, n_sersic, ix, iy, ps_only != 0);
+            // the walker's pixel-integrated Sersic components (psfmc_integrated.h); nullptr: none
+            if (extra && !ps_only) v += extra[(size_t)w * S + idx];
             raw[idx] = v;
             raw2[idx] = v * v;
         }

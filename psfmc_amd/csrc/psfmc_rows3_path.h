@@ -208,7 +208,8 @@ __device__ __forceinline__ void rows3_fill_table(cd* __restrict__ tab, const cd*
 // rows3_fwd.  grid (ceil(ny / 4), n_walkers), 4 waves per workgroup, wave = row of the layout group.
 // Arguments as k_rows_fwd.
 // ---------------------------------------------------------------------------
-template <int NX, bool FROM_IMAGE, bool WRAP = false, class S = typename Rows3<NX>::S>
+// EXTRA: as k_rows_fwd's (`img` holds the walkers' pixel-integrated components)
+template <int NX, bool FROM_IMAGE, bool WRAP = false, class S = typename Rows3<NX>::S, bool EXTRA = false>
 __global__ void __launch_bounds__((rows3_threads(NX)), (rows3_min_waves<S, false>()))
 k_rows3_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip, const cd* __restrict__ twx,
             cd* __restrict__ Tbuf, int n_ps, int n_sersic, int ny, int ps_only, const double* __restrict__ img,
@@ -266,6 +267,22 @@ k_rows3_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip, c
             raster_row<R1, L, 0, WRAP, WRAP ? 1 : PSFMC_ROWS3_RASTER_GROUP, PSFMC_ROWS3_PREFETCH != 0>(
                 wprep, n_ps, n_sersic, tl, iy, ps_only != 0, wave_lds, r, wr, pow_mode);
 #endif
+            if constexpr (EXTRA) {
+                if (!ps_only && lane_in) {
+                    const double* ex = img + (size_t)w * Spx;
+                    if constexpr (WRAP) {
+                        const double* exr = ex + (size_t)wrap_coord(iy, wr.ay, wr.ly) * NX;
+                        if (iy < wr.ey) {
+#pragma unroll
+                            for (int k = 0; k < R1; ++k)
+                                if (L * k + tl < wr.ex) r[k] += exr[wrap_coord(L * k + tl, wr.ax, wr.lx)];
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < R1; ++k) r[k] += ex[(size_t)iy * NX + L * k + tl];
+                    }
+                }
+            }
             wave_lds_sync();
 #pragma unroll
             for (int k = 0; k < R1; ++k) v[k] = cd{r[k], mu * r[k] * r[k]};

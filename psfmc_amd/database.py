@@ -22,6 +22,7 @@ _COMMENTS = {'MCITER': 'number of retained samples',
              'MAPWLKR': 'Walker index of maximum posterior model',
              'MAPSAMP': 'Sample index of maximum posterior model',
              'PSFIMG': 'PSF image of maximum posterior model'}
+_INTEGRATE_COMMENT = 'pixel-integrated Sersic (not the reference profile)'
 
 
 class Table(object):
@@ -89,6 +90,10 @@ def save_database(sampler, model, db_name, meta_dict=None, sample_index='referen
     best = int(np.argmax(cols['lnprobability']))
     meta['MAPWLKR'] = int(cols['walker'][best])
     meta['MAPSAMP'] = int(cols['sample'][best])
+    # components fitted with the pixel-integrated profile say so (<n>SERINT beside the component's <n>SER_* keys);
+    # a model without the keyword writes the header it always wrote
+    for key, val in getattr(model, 'header_flags', dict)().items():
+        meta[key] = (val, _INTEGRATE_COMMENT)
     fits_io.write_table(db_name, cols, annotate_metadata(meta))
     return load_database(db_name)
 

@@ -253,6 +253,10 @@ def load_library():
     lib.psfmc_group_set_layout.restype = ci
     lib.psfmc_group_set_layout.argtypes = [vp, ci, ci, ip, _c_double_p, ip, ip, cd, ip, _c_double_p,
                                            _c_double_p, _c_double_p]
+    lib.psfmc_set_sersic_integrate.restype = ci
+    lib.psfmc_set_sersic_integrate.argtypes = [vp, ci, ci, ip]
+    lib.psfmc_group_set_sersic_integrate.restype = ci
+    lib.psfmc_group_set_sersic_integrate.argtypes = [vp, ci, ip]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -476,6 +480,13 @@ class Context(object):
         include/psfmc_hip.h (0 = host), params [P, <= 4] their scipy.stats arguments in order."""
         fam, tab, fp, tp = _prior_table(family, params)
         self._check(self._lib.psfmc_set_priors(self._ctx, 0, len(fam), fp, tp))
+
+    def set_sersic_integrate(self, flags):
+        """Which Sersic components (model-file order) are the pixel-integrated profile
+        (psfmc_set_sersic_integrate).  A context that never gets a true flag is what it was without the call."""
+        flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+        self._check(self._lib.psfmc_set_sersic_integrate(
+            self._ctx, 0, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -799,6 +810,11 @@ class FieldSetContext(object):
             def set_priors(self, family, params):
                 fam, tab, fp, tp = _prior_table(family, params)
                 owner._check(owner._lib.psfmc_set_priors(owner._ctx, int(field), len(fam), fp, tp))
+
+            def set_sersic_integrate(self, flags):
+                flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+                owner._check(owner._lib.psfmc_set_sersic_integrate(
+                    owner._ctx, int(field), len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return _Proxy()
 
     @staticmethod
@@ -1149,6 +1165,12 @@ class ContextGroup(object):
         """`Context.set_priors` on every device of the group."""
         fam, tab, fp, tp = _prior_table(family, params)
         self._check(self._lib.psfmc_group_set_priors(self._grp, len(fam), fp, tp))
+
+    def set_sersic_integrate(self, flags):
+        """`Context.set_sersic_integrate` on every device of the group."""
+        flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+        self._check(self._lib.psfmc_group_set_sersic_integrate(
+            self._grp, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
 
     def loglike(self, rows, skip=None):
         rows = _f64(rows)

@@ -186,6 +186,10 @@ class MultiComponentModel(object):
         families the library does not know, and parameters scipy rejects, stay on the host
         (`_host_priors`).  Joint fits (`JointModel`): this model's column c is column columns[c] of
         n_params joint columns, and its prior table is left to the joint one (psfmc_set_joint_priors)."""
+        # which Sersic components are the pixel-integrated profile: a property of the model, sent once like the
+        # point sources' shift methods (nothing is sent, and nothing changes, for a model without the keyword)
+        if any(self.sersic_integrate):
+            eng.set_sersic_integrate(self.sersic_integrate)
         col_of = {}                                   # (component id, attr, element) -> column
         family = np.zeros(self.num_params, dtype=np.int32)
         params = np.zeros((self.num_params, engine.PRIOR_NPAR))
@@ -241,6 +245,18 @@ class MultiComponentModel(object):
                        self.config.mag_zeropoint, np.where(new, 0, family), base[:, 0], base[:, 1], base[:, 2])
         if new.any():
             eng.set_priors(family, params)
+
+    @property
+    def sersic_integrate(self):
+        """[n_sersic] which Sersic components (model-file order) were given `integrate=True`."""
+        return [bool(getattr(c, 'integrate', False)) for c in self._sersic]
+
+    def header_flags(self):
+        """Header keys of the components that are not the reference's profile (`Sersic.header_flags`)."""
+        out = {}
+        for count, comp in enumerate(self.components):
+            out.update(getattr(comp, 'header_flags', lambda n: {})(count))
+        return out
 
     def device_group(self, devices, max_walkers=None):
         """A `engine.ContextGroup`: this model's field on several GPUs driven by this one
@@ -773,6 +789,16 @@ class JointModel(object):
     @property
     def obs_header(self):
         return self.field_models[0].obs_header
+
+    def header_flags(self):
+        """`MultiComponentModel.header_flags` over the fields: a key's value is T where every field integrates the
+        component, else one letter per field ('TF': field 0 only)."""
+        per = [m.header_flags() for m in self.field_models]
+        out = {}
+        for key in sorted(set().union(*per)):
+            marks = ''.join('T' if key in p else 'F' for p in per)
+            out[key] = True if 'F' not in marks else marks
+        return out
 
     def field_columns(self, f):
         """[P_f] joint column of each of field f's own columns."""
