@@ -44,12 +44,9 @@ typedef struct psfmc_ctx psfmc_ctx;
 
 /* convolution back ends (both run entirely on the GPU) */
 #define PSFMC_BACKEND_FUSED   0  /* hand-written LDS FFT fused with rasteriser / spectral multiply / chi^2.
-                                    BUILT sides: the powers of two 64..1024 and the even 5-smooth sides 96 100 120
-                                    144 150 160 180 192 200 240 250 288 300 320 360 384 400 480 500 576 600
-                                    640 720 768 800 900 960 and, with a factor 7, 84 98 112 126 140 168 196
-                                    210 224 252 280 294 336 350 392 420 448 504 560 630 672 700 784 840 896,
-                                    with a factor 11 or 13: 88 104 110 130 132 156 176 208 220 260 264 286 308 312
-                                    330 352 364 390 416 440 484 520 528 572 616 624 650 660 676 704 728 780 832
+                                    BUILT sides: the rows of psfmc_amd/csrc/psfmc_sides.h (the powers of two
+                                    64..2048, 1152, 1280, 1536 and the even sides up to 960 with factors 3, 5, 7, 11
+                                    and 13 listed there; psfmc_amd/engine.py FUSED_SIDES is the same list)
                                     (nx and ny independently, any combination).  Any OTHER even side is EMBEDDED
                                     (round 3): it runs on the kernels of a built side >= side + PSF side - 1 of
                                     that axis (overlap-save; every array at this boundary keeps the image's own

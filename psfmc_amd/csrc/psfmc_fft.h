@@ -25,6 +25,7 @@
 
 #include "psfmc_trig_table.h"
 #include "psfmc_device.h"
+#include "psfmc_sides.h"
 
 namespace psfmc {
 
@@ -90,11 +91,11 @@ template <int N> struct FftShape;
         static constexpr bool kFull = (TPW * T_ == 64);     /* every lane of a wave works */        \
         static constexpr bool kPlain = kExact && kFull;     /* the power-of-two shapes */           \
     };
-PSFMC_FFT_SHAPE(64, 8, 8)
-PSFMC_FFT_SHAPE(128, 16, 8)
-PSFMC_FFT_SHAPE(256, 16, 16)
-PSFMC_FFT_SHAPE(512, 32, 16)
-PSFMC_FFT_SHAPE(1024, 32, 32)
+// The shapes (P, T) are the rows of psfmc_sides.h: every power of two 64 ... 1024 and the even sides with factors 3, 5
+// (any even side of the list runs on the fused kernels), 7, 11 and 13 (round 2: the same rules).  The
+// shapes keep R = max(P, ceil(P/T) T) small -- registers, hence waves per SIMD, are what the
+// memory-bound column kernel lives on -- at the price of a few idle lanes (T = 10, 15, 20, 30
+// use 60 of a wave's 64 lanes, T = 18 54, T = 24 48, T = 25 50) or idle stage-2 slots (P < T).
 // Round 4, a survey of the shapes that leave many lanes idle (tools/side_costs.py with the alternative shape against
 // this table, same box; profiles/r4_shape_survey*_{base,alt}.jsonl): where the COLUMNS of a side run on the three-stage
 // engine anyway (fft3g_pick) the two-stage shape only serves the row kernels, and more lanes beat fewer registers --
@@ -104,98 +105,10 @@ PSFMC_FFT_SHAPE(1024, 32, 32)
 // lanes) -> 24 x 12 (60): +4.6 %, 18 x 16 (64 lanes, 32 registers): +0 % (profiles/r4_shape_288.txt).  Measured and left alone: 384, 390, 448, 480, 504, 576, 600, 672 (-8 ... +3 %), every small
 // side tried (110 ... 288: -1 ... -44 %: their two-stage COLUMN kernel pays for the registers) and the R = 40 shapes of 440,
 // 500, 520, 560 (-13 ... -14 %).
-// sides with factors 3 and 5 (any even side of this list runs on the fused kernels).  The
-// shapes keep R = max(P, ceil(P/T) T) small -- registers, hence waves per SIMD, are what the
-// memory-bound column kernel lives on -- at the price of a few idle lanes (T = 10, 15, 20, 30
-// use 60 of a wave's 64 lanes, T = 18 54, T = 24 48, T = 25 50) or idle stage-2 slots (P < T).
-PSFMC_FFT_SHAPE(96, 12, 8)
-PSFMC_FFT_SHAPE(100, 10, 10)
-PSFMC_FFT_SHAPE(120, 15, 8)
-PSFMC_FFT_SHAPE(144, 12, 12)
-PSFMC_FFT_SHAPE(150, 10, 15)
-PSFMC_FFT_SHAPE(160, 10, 16)
-PSFMC_FFT_SHAPE(180, 12, 15)
-PSFMC_FFT_SHAPE(192, 12, 16)
-PSFMC_FFT_SHAPE(200, 20, 10)
-PSFMC_FFT_SHAPE(240, 15, 16)
-PSFMC_FFT_SHAPE(250, 25, 10)
-PSFMC_FFT_SHAPE(288, 24, 12)
-PSFMC_FFT_SHAPE(300, 15, 20)
-PSFMC_FFT_SHAPE(320, 16, 20)
-PSFMC_FFT_SHAPE(360, 18, 20)
-PSFMC_FFT_SHAPE(384, 16, 24)
-PSFMC_FFT_SHAPE(400, 20, 20)
-PSFMC_FFT_SHAPE(480, 20, 24)
-PSFMC_FFT_SHAPE(500, 20, 25)
-PSFMC_FFT_SHAPE(576, 24, 24)
-PSFMC_FFT_SHAPE(600, 24, 25)
-PSFMC_FFT_SHAPE(640, 20, 32)
-PSFMC_FFT_SHAPE(720, 24, 30)
-PSFMC_FFT_SHAPE(768, 24, 32)
-PSFMC_FFT_SHAPE(800, 25, 32)
-PSFMC_FFT_SHAPE(900, 30, 30)
-PSFMC_FFT_SHAPE(960, 30, 32)
-// sides with a factor 7 (round 2): the same rules
-PSFMC_FFT_SHAPE(84, 7, 12)
-PSFMC_FFT_SHAPE(98, 7, 14)
-PSFMC_FFT_SHAPE(112, 14, 8)
-PSFMC_FFT_SHAPE(126, 9, 14)
-PSFMC_FFT_SHAPE(140, 10, 14)
-PSFMC_FFT_SHAPE(168, 12, 14)
-PSFMC_FFT_SHAPE(196, 14, 14)
-PSFMC_FFT_SHAPE(210, 14, 15)
-PSFMC_FFT_SHAPE(224, 14, 16)
-PSFMC_FFT_SHAPE(252, 14, 18)
-PSFMC_FFT_SHAPE(280, 14, 20)
-PSFMC_FFT_SHAPE(294, 14, 21)
-PSFMC_FFT_SHAPE(336, 16, 21)
-PSFMC_FFT_SHAPE(350, 25, 14)
-PSFMC_FFT_SHAPE(392, 14, 28)
-PSFMC_FFT_SHAPE(420, 20, 21)
-PSFMC_FFT_SHAPE(448, 16, 28)
-PSFMC_FFT_SHAPE(504, 21, 24)
-PSFMC_FFT_SHAPE(560, 20, 28)
-PSFMC_FFT_SHAPE(630, 21, 30)
-PSFMC_FFT_SHAPE(672, 24, 28)
-PSFMC_FFT_SHAPE(700, 25, 28)
-PSFMC_FFT_SHAPE(784, 28, 28)
-PSFMC_FFT_SHAPE(840, 28, 30)
-PSFMC_FFT_SHAPE(896, 28, 32)
-// sides with a factor 11 or 13 (round 2): the same rules
-PSFMC_FFT_SHAPE(88, 11, 8)
-PSFMC_FFT_SHAPE(104, 13, 8)
-PSFMC_FFT_SHAPE(110, 10, 11)
-PSFMC_FFT_SHAPE(130, 10, 13)
-PSFMC_FFT_SHAPE(132, 11, 12)
-PSFMC_FFT_SHAPE(156, 12, 13)
-PSFMC_FFT_SHAPE(176, 11, 16)
-PSFMC_FFT_SHAPE(208, 13, 16)
-PSFMC_FFT_SHAPE(220, 11, 20)
-PSFMC_FFT_SHAPE(260, 13, 20)
-PSFMC_FFT_SHAPE(264, 22, 12)
-PSFMC_FFT_SHAPE(286, 22, 13)
-PSFMC_FFT_SHAPE(308, 11, 28)
-PSFMC_FFT_SHAPE(312, 24, 13)
-PSFMC_FFT_SHAPE(330, 22, 15)
-PSFMC_FFT_SHAPE(352, 22, 16)
-PSFMC_FFT_SHAPE(364, 13, 28)
-PSFMC_FFT_SHAPE(390, 15, 26)
-PSFMC_FFT_SHAPE(416, 26, 16)
-PSFMC_FFT_SHAPE(440, 20, 22)
-PSFMC_FFT_SHAPE(484, 22, 22)
-PSFMC_FFT_SHAPE(520, 20, 26)
-PSFMC_FFT_SHAPE(528, 22, 24)
-PSFMC_FFT_SHAPE(572, 22, 26)
-PSFMC_FFT_SHAPE(616, 22, 28)
-PSFMC_FFT_SHAPE(624, 24, 26)
-PSFMC_FFT_SHAPE(650, 25, 26)
-PSFMC_FFT_SHAPE(660, 22, 30)
-PSFMC_FFT_SHAPE(676, 26, 26)
-PSFMC_FFT_SHAPE(704, 22, 32)
-PSFMC_FFT_SHAPE(728, 26, 28)
-PSFMC_FFT_SHAPE(780, 26, 30)
-PSFMC_FFT_SHAPE(832, 26, 32)
+#define PSFMC_NO_FFT_SHAPE(N_)      /* sides above 1024: no two-stage shape, FftShape<N> stays undefined */
+PSFMC_SIDES(PSFMC_FFT_SHAPE, PSFMC_NO_FFT_SHAPE)
 #undef PSFMC_FFT_SHAPE
+#undef PSFMC_NO_FFT_SHAPE
 
 // the output index lane t holds in register e, and whether that register holds one at all
 template <int N> __device__ __forceinline__ constexpr int fft_k_of(int t, int e) {
@@ -827,6 +740,16 @@ constexpr Fft3gPick fft3g_pick(int n) {
         default: return {0, 0};
     }
 }
+// (R2, R3) splits a side N = R1 R2 R3 on R2 R3 <= 64 lanes with 4 <= R1 <= 32 registers: checked here for every pick,
+// not only where a part instantiates Fft3gShape<N>
+constexpr bool fft3g_shape_ok(int n, Fft3gPick p) {
+    return p.r2 > 0 && p.r3 > 0 && n % (p.r2 * p.r3) == 0 && p.r2 * p.r3 <= 64 && n / (p.r2 * p.r3) >= 4 &&
+           n / (p.r2 * p.r3) <= 32;
+}
+static_assert(for_all_lengths([](int n) { return fft3g_pick(n).r2 == 0 || fused_side(n); }),
+              "fft3g_pick names a side psfmc_sides.h does not list");
+static_assert(for_all_lengths([](int n) { return fft3g_pick(n).r2 == 0 || fft3g_shape_ok(n, fft3g_pick(n)); }),
+              "fft3g_pick: N = R1 R2 R3 with R2 R3 <= 64 and 4 <= R1 <= 32");
 template <int N, int R2_ = fft3g_pick(N).r2, int R3_ = fft3g_pick(N).r3> struct Fft3gShape {
     static constexpr bool kBuilt = R2_ > 0;
     static constexpr int kN = N;

@@ -166,6 +166,8 @@ template <int N> constexpr int fused_min_waves() {
 constexpr bool row_two_waves_side(int n) {
     return n == 630 || n == 650 || n == 660 || n == 676 || n == 700 || n == 720 || n == 780;
 }
+static_assert(for_all_lengths([](int n) { return !row_two_waves_side(n) || fused_side_has_two_stage_shape(n); }),
+              "row_two_waves_side names a side without two-stage row kernels (psfmc_sides.h)");
 // Sides whose row kernels sit 2 ... 8 registers above an occupancy step (130 vector registers: three waves per
 // SIMD instead of four; 172 ... 176: two instead of three), bounded to the next step where that measured faster
 // (same box, kernel time): the forward kernel of 84, 98, 132, 160, 176 (-3 ... -6 %), the inverse kernel of 220, 260,

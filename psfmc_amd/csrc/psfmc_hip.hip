@@ -21,6 +21,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -81,225 +82,41 @@ int psfmc_fail_(int code, const char* fmt, ...) {
         if (rc_ != PSFMC_OK) return rc_; \
     } while (0)
 
-// sides the fused kernels are instantiated for (FftShape in psfmc_fft.h): every power of two
-// 64..1024 and the even sides with factors 3, 5, 7, 11, 13 listed there
-#define PSFMC_FUSED_SIDES "64 84 88 96 98 100 104 110 112 120 126 128 130 132 140 144 150 156 160 168 176 180 192 196 200 208 210 220 224 240 250 252 256 260 264 280 286 288 294 300 308 312 320 330 336 350 352 360 364 384 390 392 400 416 420 440 448 480 484 500 504 512 520 528 560 572 576 600 616 624 630 640 650 660 672 676 700 704 720 728 768 780 784 800 832 840 896 900 960 1024 1152 1280 1536 2048"
-// run BODY with `N_` a compile-time copy of the length n; in a split build only for this part's sides
-// (side i of the list belongs to part i mod PSFMC_NPARTS)
-#if PSFMC_NPARTS == 1
-#define DISPATCH_LEN(n, BODY) \
-    switch (n) { \
-        case 64: { constexpr int N_ = 64; BODY; } break; \
-        case 84: { constexpr int N_ = 84; BODY; } break; \
-        case 88: { constexpr int N_ = 88; BODY; } break; \
-        case 96: { constexpr int N_ = 96; BODY; } break; \
-        case 98: { constexpr int N_ = 98; BODY; } break; \
-        case 100: { constexpr int N_ = 100; BODY; } break; \
-        case 104: { constexpr int N_ = 104; BODY; } break; \
-        case 110: { constexpr int N_ = 110; BODY; } break; \
-        case 112: { constexpr int N_ = 112; BODY; } break; \
-        case 120: { constexpr int N_ = 120; BODY; } break; \
-        case 126: { constexpr int N_ = 126; BODY; } break; \
-        case 128: { constexpr int N_ = 128; BODY; } break; \
-        case 130: { constexpr int N_ = 130; BODY; } break; \
-        case 132: { constexpr int N_ = 132; BODY; } break; \
-        case 140: { constexpr int N_ = 140; BODY; } break; \
-        case 144: { constexpr int N_ = 144; BODY; } break; \
-        case 150: { constexpr int N_ = 150; BODY; } break; \
-        case 156: { constexpr int N_ = 156; BODY; } break; \
-        case 160: { constexpr int N_ = 160; BODY; } break; \
-        case 168: { constexpr int N_ = 168; BODY; } break; \
-        case 176: { constexpr int N_ = 176; BODY; } break; \
-        case 180: { constexpr int N_ = 180; BODY; } break; \
-        case 192: { constexpr int N_ = 192; BODY; } break; \
-        case 196: { constexpr int N_ = 196; BODY; } break; \
-        case 200: { constexpr int N_ = 200; BODY; } break; \
-        case 208: { constexpr int N_ = 208; BODY; } break; \
-        case 210: { constexpr int N_ = 210; BODY; } break; \
-        case 220: { constexpr int N_ = 220; BODY; } break; \
-        case 224: { constexpr int N_ = 224; BODY; } break; \
-        case 240: { constexpr int N_ = 240; BODY; } break; \
-        case 250: { constexpr int N_ = 250; BODY; } break; \
-        case 252: { constexpr int N_ = 252; BODY; } break; \
-        case 256: { constexpr int N_ = 256; BODY; } break; \
-        case 260: { constexpr int N_ = 260; BODY; } break; \
-        case 264: { constexpr int N_ = 264; BODY; } break; \
-        case 280: { constexpr int N_ = 280; BODY; } break; \
-        case 286: { constexpr int N_ = 286; BODY; } break; \
-        case 288: { constexpr int N_ = 288; BODY; } break; \
-        case 294: { constexpr int N_ = 294; BODY; } break; \
-        case 300: { constexpr int N_ = 300; BODY; } break; \
-        case 308: { constexpr int N_ = 308; BODY; } break; \
-        case 312: { constexpr int N_ = 312; BODY; } break; \
-        case 320: { constexpr int N_ = 320; BODY; } break; \
-        case 330: { constexpr int N_ = 330; BODY; } break; \
-        case 336: { constexpr int N_ = 336; BODY; } break; \
-        case 350: { constexpr int N_ = 350; BODY; } break; \
-        case 352: { constexpr int N_ = 352; BODY; } break; \
-        case 360: { constexpr int N_ = 360; BODY; } break; \
-        case 364: { constexpr int N_ = 364; BODY; } break; \
-        case 384: { constexpr int N_ = 384; BODY; } break; \
-        case 390: { constexpr int N_ = 390; BODY; } break; \
-        case 392: { constexpr int N_ = 392; BODY; } break; \
-        case 400: { constexpr int N_ = 400; BODY; } break; \
-        case 416: { constexpr int N_ = 416; BODY; } break; \
-        case 420: { constexpr int N_ = 420; BODY; } break; \
-        case 440: { constexpr int N_ = 440; BODY; } break; \
-        case 448: { constexpr int N_ = 448; BODY; } break; \
-        case 480: { constexpr int N_ = 480; BODY; } break; \
-        case 484: { constexpr int N_ = 484; BODY; } break; \
-        case 500: { constexpr int N_ = 500; BODY; } break; \
-        case 504: { constexpr int N_ = 504; BODY; } break; \
-        case 512: { constexpr int N_ = 512; BODY; } break; \
-        case 520: { constexpr int N_ = 520; BODY; } break; \
-        case 528: { constexpr int N_ = 528; BODY; } break; \
-        case 560: { constexpr int N_ = 560; BODY; } break; \
-        case 572: { constexpr int N_ = 572; BODY; } break; \
-        case 576: { constexpr int N_ = 576; BODY; } break; \
-        case 600: { constexpr int N_ = 600; BODY; } break; \
-        case 616: { constexpr int N_ = 616; BODY; } break; \
-        case 624: { constexpr int N_ = 624; BODY; } break; \
-        case 630: { constexpr int N_ = 630; BODY; } break; \
-        case 640: { constexpr int N_ = 640; BODY; } break; \
-        case 650: { constexpr int N_ = 650; BODY; } break; \
-        case 660: { constexpr int N_ = 660; BODY; } break; \
-        case 672: { constexpr int N_ = 672; BODY; } break; \
-        case 676: { constexpr int N_ = 676; BODY; } break; \
-        case 700: { constexpr int N_ = 700; BODY; } break; \
-        case 704: { constexpr int N_ = 704; BODY; } break; \
-        case 720: { constexpr int N_ = 720; BODY; } break; \
-        case 728: { constexpr int N_ = 728; BODY; } break; \
-        case 768: { constexpr int N_ = 768; BODY; } break; \
-        case 780: { constexpr int N_ = 780; BODY; } break; \
-        case 784: { constexpr int N_ = 784; BODY; } break; \
-        case 800: { constexpr int N_ = 800; BODY; } break; \
-        case 832: { constexpr int N_ = 832; BODY; } break; \
-        case 840: { constexpr int N_ = 840; BODY; } break; \
-        case 896: { constexpr int N_ = 896; BODY; } break; \
-        case 900: { constexpr int N_ = 900; BODY; } break; \
-        case 960: { constexpr int N_ = 960; BODY; } break; \
-        case 1024: { constexpr int N_ = 1024; BODY; } break; \
-        case 1152: { constexpr int N_ = 1152; BODY; } break; \
-        case 1280: { constexpr int N_ = 1280; BODY; } break; \
-        case 1536: { constexpr int N_ = 1536; BODY; } break; \
-        case 2048: { constexpr int N_ = 2048; BODY; } break; \
-        default: return fail(PSFMC_EINVAL, "fused backend: side %d is not one of " PSFMC_FUSED_SIDES, n); \
+// the built sides, as the error messages list them (psfmc_sides.h: the one list everything here derives from)
+#define PSFMC_SIDE_STR_(N, ...) " " #N
+#define PSFMC_FUSED_SIDES PSFMC_SIDES(PSFMC_SIDE_STR_, PSFMC_SIDE_STR_)
+#define PSFMC_UNKNOWN_SIDE(n) fail(PSFMC_EINVAL, "fused backend: side %d is not one of" PSFMC_FUSED_SIDES, n)
+
+// Run BODY with `N_` a compile-time copy of the length n; in a split build only for this part's sides: side i of
+// the list belongs to part i mod PSFMC_NPARTS, a side of another part answers PSFMC_NOT_MINE.  BODY sits in a generic
+// lambda and the switch in a template on the part, so that a part instantiates the launchers -- hence the kernels --
+// of its own sides only (in a plain function a discarded `if constexpr` branch is still instantiated).
+template <int PART, class Body> static int dispatch_side(int n, Body& body) {
+    switch (n) {
+#define PSFMC_SIDE_CASE_(N, ...)                                                                                   \
+    case N:                                                                                                        \
+        if constexpr (fused_side_index(N) % PSFMC_NPARTS == PART) return body(std::integral_constant<int, N>{});  \
+        else return PSFMC_NOT_MINE;
+        PSFMC_SIDES(PSFMC_SIDE_CASE_, PSFMC_SIDE_CASE_)
+#undef PSFMC_SIDE_CASE_
+        default: return PSFMC_NPARTS == 1 ? PSFMC_UNKNOWN_SIDE(n) : PSFMC_NOT_MINE;
     }
-#elif PSFMC_PART == 0
-#define DISPATCH_LEN(n, BODY) \
-    switch (n) { \
-        case 64: { constexpr int N_ = 64; BODY; } break; \
-        case 98: { constexpr int N_ = 98; BODY; } break; \
-        case 112: { constexpr int N_ = 112; BODY; } break; \
-        case 130: { constexpr int N_ = 130; BODY; } break; \
-        case 150: { constexpr int N_ = 150; BODY; } break; \
-        case 176: { constexpr int N_ = 176; BODY; } break; \
-        case 200: { constexpr int N_ = 200; BODY; } break; \
-        case 224: { constexpr int N_ = 224; BODY; } break; \
-        case 256: { constexpr int N_ = 256; BODY; } break; \
-        case 286: { constexpr int N_ = 286; BODY; } break; \
-        case 308: { constexpr int N_ = 308; BODY; } break; \
-        case 336: { constexpr int N_ = 336; BODY; } break; \
-        case 364: { constexpr int N_ = 364; BODY; } break; \
-        case 400: { constexpr int N_ = 400; BODY; } break; \
-        case 448: { constexpr int N_ = 448; BODY; } break; \
-        case 504: { constexpr int N_ = 504; BODY; } break; \
-        case 560: { constexpr int N_ = 560; BODY; } break; \
-        case 616: { constexpr int N_ = 616; BODY; } break; \
-        case 650: { constexpr int N_ = 650; BODY; } break; \
-        case 700: { constexpr int N_ = 700; BODY; } break; \
-        case 768: { constexpr int N_ = 768; BODY; } break; \
-        case 832: { constexpr int N_ = 832; BODY; } break; \
-        case 960: { constexpr int N_ = 960; BODY; } break; \
-        case 1536: { constexpr int N_ = 1536; BODY; } break; \
-        default: return PSFMC_NOT_MINE; \
-    }
-#elif PSFMC_PART == 1
-#define DISPATCH_LEN(n, BODY) \
-    switch (n) { \
-        case 84: { constexpr int N_ = 84; BODY; } break; \
-        case 100: { constexpr int N_ = 100; BODY; } break; \
-        case 120: { constexpr int N_ = 120; BODY; } break; \
-        case 132: { constexpr int N_ = 132; BODY; } break; \
-        case 156: { constexpr int N_ = 156; BODY; } break; \
-        case 180: { constexpr int N_ = 180; BODY; } break; \
-        case 208: { constexpr int N_ = 208; BODY; } break; \
-        case 240: { constexpr int N_ = 240; BODY; } break; \
-        case 260: { constexpr int N_ = 260; BODY; } break; \
-        case 288: { constexpr int N_ = 288; BODY; } break; \
-        case 312: { constexpr int N_ = 312; BODY; } break; \
-        case 350: { constexpr int N_ = 350; BODY; } break; \
-        case 384: { constexpr int N_ = 384; BODY; } break; \
-        case 416: { constexpr int N_ = 416; BODY; } break; \
-        case 480: { constexpr int N_ = 480; BODY; } break; \
-        case 512: { constexpr int N_ = 512; BODY; } break; \
-        case 572: { constexpr int N_ = 572; BODY; } break; \
-        case 624: { constexpr int N_ = 624; BODY; } break; \
-        case 660: { constexpr int N_ = 660; BODY; } break; \
-        case 704: { constexpr int N_ = 704; BODY; } break; \
-        case 780: { constexpr int N_ = 780; BODY; } break; \
-        case 840: { constexpr int N_ = 840; BODY; } break; \
-        case 1024: { constexpr int N_ = 1024; BODY; } break; \
-        case 2048: { constexpr int N_ = 2048; BODY; } break; \
-        default: return PSFMC_NOT_MINE; \
-    }
-#elif PSFMC_PART == 2
-#define DISPATCH_LEN(n, BODY) \
-    switch (n) { \
-        case 88: { constexpr int N_ = 88; BODY; } break; \
-        case 104: { constexpr int N_ = 104; BODY; } break; \
-        case 126: { constexpr int N_ = 126; BODY; } break; \
-        case 140: { constexpr int N_ = 140; BODY; } break; \
-        case 160: { constexpr int N_ = 160; BODY; } break; \
-        case 192: { constexpr int N_ = 192; BODY; } break; \
-        case 210: { constexpr int N_ = 210; BODY; } break; \
-        case 250: { constexpr int N_ = 250; BODY; } break; \
-        case 264: { constexpr int N_ = 264; BODY; } break; \
-        case 294: { constexpr int N_ = 294; BODY; } break; \
-        case 320: { constexpr int N_ = 320; BODY; } break; \
-        case 352: { constexpr int N_ = 352; BODY; } break; \
-        case 390: { constexpr int N_ = 390; BODY; } break; \
-        case 420: { constexpr int N_ = 420; BODY; } break; \
-        case 484: { constexpr int N_ = 484; BODY; } break; \
-        case 520: { constexpr int N_ = 520; BODY; } break; \
-        case 576: { constexpr int N_ = 576; BODY; } break; \
-        case 630: { constexpr int N_ = 630; BODY; } break; \
-        case 672: { constexpr int N_ = 672; BODY; } break; \
-        case 720: { constexpr int N_ = 720; BODY; } break; \
-        case 784: { constexpr int N_ = 784; BODY; } break; \
-        case 896: { constexpr int N_ = 896; BODY; } break; \
-        case 1152: { constexpr int N_ = 1152; BODY; } break; \
-        default: return PSFMC_NOT_MINE; \
-    }
-#elif PSFMC_PART == 3
-#define DISPATCH_LEN(n, BODY) \
-    switch (n) { \
-        case 96: { constexpr int N_ = 96; BODY; } break; \
-        case 110: { constexpr int N_ = 110; BODY; } break; \
-        case 128: { constexpr int N_ = 128; BODY; } break; \
-        case 144: { constexpr int N_ = 144; BODY; } break; \
-        case 168: { constexpr int N_ = 168; BODY; } break; \
-        case 196: { constexpr int N_ = 196; BODY; } break; \
-        case 220: { constexpr int N_ = 220; BODY; } break; \
-        case 252: { constexpr int N_ = 252; BODY; } break; \
-        case 280: { constexpr int N_ = 280; BODY; } break; \
-        case 300: { constexpr int N_ = 300; BODY; } break; \
-        case 330: { constexpr int N_ = 330; BODY; } break; \
-        case 360: { constexpr int N_ = 360; BODY; } break; \
-        case 392: { constexpr int N_ = 392; BODY; } break; \
-        case 440: { constexpr int N_ = 440; BODY; } break; \
-        case 500: { constexpr int N_ = 500; BODY; } break; \
-        case 528: { constexpr int N_ = 528; BODY; } break; \
-        case 600: { constexpr int N_ = 600; BODY; } break; \
-        case 640: { constexpr int N_ = 640; BODY; } break; \
-        case 676: { constexpr int N_ = 676; BODY; } break; \
-        case 728: { constexpr int N_ = 728; BODY; } break; \
-        case 800: { constexpr int N_ = 800; BODY; } break; \
-        case 900: { constexpr int N_ = 900; BODY; } break; \
-        case 1280: { constexpr int N_ = 1280; BODY; } break; \
-        default: return PSFMC_NOT_MINE; \
-    }
-#endif
+}
+#define DISPATCH_LEN(n, BODY)                                                                                    \
+    do {                                                                                                         \
+        auto body_ = [&](auto n_) -> int { constexpr int N_ = decltype(n_)::value; BODY; return PSFMC_OK; };     \
+        const int rc_ = dispatch_side<PSFMC_PART>(n, body_);                                                     \
+        if (rc_ != PSFMC_OK) return rc_;                                                                         \
+    } while (0)
+
+// the measured cost table has exactly the built sides, in their order
+constexpr bool side_costs_match_sides() {
+    if (sizeof(kSideCosts) / sizeof(kSideCosts[0]) != (size_t)kNumFusedSides) return false;
+    for (int i = 0; i < kNumFusedSides; ++i)
+        if (kSideCosts[i].side != kFusedSides[i]) return false;
+    return true;
+}
+static_assert(side_costs_match_sides(), "psfmc_side_costs.h: regenerate it (tools/gen_side_costs.py) for the sides of psfmc_sides.h");
 
 // ---------------------------------------------------------------------------
 // context
@@ -945,7 +762,7 @@ static int size_call(int op, int side, SizeCall& a) {
         const int rc = fn(op, side, &a);
         if (rc != PSFMC_NOT_MINE) return rc;
     }
-    return fail(PSFMC_EINVAL, "fused backend: side %d is not one of " PSFMC_FUSED_SIDES, side);
+    return PSFMC_UNKNOWN_SIDE(side);
 #endif
 }
 
@@ -1035,14 +852,6 @@ static int fused_pass_walkers(const psfmc_ctx* c) {
     // (sides above 1024: 2 walkers per pass at 1536^2, ONE at 2048^2 -- 67 MB of T each, two passes in flight)
     return chunk < 1 ? 1 : chunk;
 }
-
-static bool fused_side(int n) {
-    static const int sides[] = {64,84,88,96,98,100,104,110,112,120,126,128,130,132,140,144,150,156,160,168,176,180,192,196,200,208,210,220,224,240,250,252,256,260,264,280,286,288,294,300,308,312,320,330,336,350,352,360,364,384,390,392,400,416,420,440,448,480,484,500,504,512,520,528,560,572,576,600,616,624,630,640,650,660,672,676,700,704,720,728,768,780,784,800,832,840,896,900,960,1024,1152,1280,1536,2048};
-    for (int v : sides)
-        if (v == n) return true;
-    return false;
-}
-
 
 // per-kernel timing: bracket a launch with events on its own stream
 enum { PROF_ROWS_FWD = 0, PROF_COLS = 1, PROF_ROWS_INV = 2 };
@@ -1282,9 +1091,6 @@ static int ctx_init(psfmc_ctx* c, const double* sci, const double* obs_var, cons
     return PSFMC_OK;
 }
 
-// the built sides in ascending order
-static const int kFusedSides[] = {64,84,88,96,98,100,104,110,112,120,126,128,130,132,140,144,150,156,160,168,176,180,192,196,200,208,210,220,224,240,250,252,256,260,264,280,286,288,294,300,308,312,320,330,336,350,352,360,364,384,390,392,400,416,420,440,448,480,484,500,504,512,520,528,560,572,576,600,616,624,630,640,650,660,672,676,700,704,720,728,768,780,784,800,832,840,896,900,960,1024,1152,1280,1536,2048};
-
 // One axis of an image whose side `l` the transforms are not built for: the smallest built side
 // m >= l + pk - 1 (pk the PSF's side on that axis), the margin a in front of the image and the extent e of
 // the filled transform pixels (psfmc_device.h WrapDesc).  The kernel's origin inside the centre-padded
@@ -1329,8 +1135,7 @@ static bool choose_embedding(int n, const int* ly, const int* lx, const int* pky
         if (!small_x && misfit(v, fix_x, lx, pkx) < 0) small_x = v;
     }
     if (!small_y || !small_x) {
-        const int kLargest = kFusedSides[sizeof(kFusedSides) / sizeof(kFusedSides[0]) - 1];
-        *bad = !small_y ? misfit(kLargest, fix_y, ly, pky) : misfit(kLargest, fix_x, lx, pkx);
+        *bad = !small_y ? misfit(kMaxFusedSide, fix_y, ly, pky) : misfit(kMaxFusedSide, fix_x, lx, pkx);
         return false;
     }
     *my = small_y; *mx = small_x;

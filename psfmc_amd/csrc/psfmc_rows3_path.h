@@ -116,7 +116,7 @@ constexpr Fft3gPick rows3_pick(int n) {
 #endif
     }
 }
-constexpr bool rows3_only_side(int n) { return n > 1024; }
+constexpr bool rows3_only_side(int n) { return fused_side(n) && !fused_side_has_two_stage_shape(n); }   // psfmc_sides.h THREE(n)
 // the inverse kernel is the default where it measured faster; the forward kernel only where there is no other
 // (the sides whose two-stage row shapes round 4 re-surveyed for lanes now hold 24 ... 32 complex registers per lane:
 // the inverse kernel there, profiles/r4_inv3_reshaped_sides.txt -- faster alone at 330 and 350 only (9.5 -> 8.0, 8.9 -> 7.3
@@ -129,6 +129,21 @@ constexpr bool rows3_inv_default(int n) {
     return rows3_only_side(n) || n == 676 || n == 720 || n == 728 || n == 780 || n == 784 || n == 840 || n == 900;
 }
 constexpr bool rows3_fwd_built(int n) { return rows3_pick(n).r2 > 0 && (rows3_only_side(n) || PSFMC_ROWS3_EXTRA); }
+// the picks against the list of built sides (psfmc_sides.h)
+static_assert(for_all_lengths([](int n) { return rows3_pick(n).r2 == 0 || (fused_side(n) && fft3g_shape_ok(n, rows3_pick(n))); }),
+              "rows3_pick names a side psfmc_sides.h does not list, or a shape that does not split it");
+// (the survey list of PSFMC_ROWS3_INV_MORE also names sides the build at hand may have no three-stage row kernel for)
+static_assert(for_all_lengths([](int n) {
+                  return !rows3_inv_default(n) || (fused_side(n) && (PSFMC_ROWS3_INV_MORE || rows3_pick(n).r2 > 0));
+              }),
+              "rows3_inv_default names a side without a three-stage row kernel");
+// every built side has row and column kernels: a two-stage shape (two_stage_side: the kernels of psfmc_fused_path.h),
+// or -- rows3_only_side, the sides above 1024 -- a three-stage shape for its rows and one for its columns
+static_assert(for_all_lengths([](int n) {
+                  return !fused_side(n) || (fused_side_has_two_stage_shape(n) == two_stage_side(n) &&
+                                            (!rows3_only_side(n) || (fft3g_pick(n).r2 > 0 && rows3_pick(n).r2 > 0)));
+              }),
+              "a side of psfmc_sides.h has neither a two-stage shape nor both three-stage picks");
 template <int NX> struct Rows3 {
     using S = Fft3gShape<NX, rows3_pick(NX).r2, rows3_pick(NX).r3>;
     static constexpr bool kBuilt = S::kBuilt;

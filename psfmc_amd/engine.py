@@ -14,7 +14,7 @@ BACKENDS = {'fused': BACKEND_FUSED, 'hipfft': BACKEND_HIPFFT}
 
 ROW_SKY, ROW_PS, ROW_SERSIC = 1, 4, 9
 
-# sides the fused kernels are built for (psfmc_amd/csrc/psfmc_fft.h FftShape)
+# sides the fused kernels are built for: the rows of psfmc_amd/csrc/psfmc_sides.h (tests/test_host_glue.py compares)
 FUSED_SIDES = (64, 84, 88, 96, 98, 100, 104, 110, 112, 120, 126, 128, 130, 132, 140, 144, 150, 156,
                160, 168, 176, 180, 192, 196, 200, 208, 210, 220, 224, 240, 250, 252, 256, 260, 264,
                280, 286, 288, 294, 300, 308, 312, 320, 330, 336, 350, 352, 360, 364, 384, 390, 392,

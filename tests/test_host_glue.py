@@ -220,18 +220,50 @@ def test_nearest_fused_sides():
 
 
 def test_side_tables_agree_between_python_and_the_kernels():
-    """The per-side tables exist in several places: the list of built sides (engine.FUSED_SIDES, two copies in
-    psfmc_hip.hip), the sides whose columns run on the general three-stage engine with their (R2, R3) split
-    (psfmc_fft.h fft3g_pick, mirrored by engine.column_engine), and the measured cost table the embedding ranks
-    candidate sides with (psfmc_side_costs.h).  They are parsed from the sources here and compared."""
+    """The built sides are listed once in the C++ -- the rows of psfmc_sides.h, TWO(N, P, T) or THREE(N) -- and once in
+    Python (engine.FUSED_SIDES); the kernels' per-side picks sit next to the kernels (psfmc_fft.h fft3g_pick, mirrored by
+    engine.column_engine; psfmc_rows3_path.h rows3_inv_default, mirrored by test_gpu_variants.ROWS3_SIDES) and the
+    measured cost table the embedding ranks candidate sides with is generated (psfmc_side_costs.h).  The compiler holds
+    the C++ picks and the cost table to the list (static_assert); the Python copies are parsed from the sources here.
+    No second full copy may grow back: outside psfmc_sides.h and the generated cost table no file of csrc/ holds more
+    than ten consecutive sides of the list as consecutive integer literals (`_longest_run_of_sides`: literals separated
+    by anything but digits and letters count as consecutive, and a literal that is not the next side ends the run.
+    On the sources before psfmc_sides.h existed this fails on psfmc_hip.hip: its two arrays and its list in the
+    error messages are runs of all 94, its `case N: { constexpr int N_ = N;` lines runs of at most one)."""
     import re
     from psfmc_amd import engine
     csrc = os.path.join(os.path.dirname(os.path.abspath(engine.__file__)), 'csrc')
-    hip = open(os.path.join(csrc, 'psfmc_hip.hip')).read()
-    lists = re.findall(r'static const int (?:sides|kFusedSides)\[\] = \{([0-9, ]+)\}', hip)
-    assert len(lists) == 2
-    for text in lists:
-        assert tuple(int(v) for v in text.split(',')) == tuple(engine.FUSED_SIDES)
+    def _longest_run_of_sides(text):
+        best = run = 0
+        nxt = None                                                        # index of the side that would extend the run
+        for tok in re.findall(r'[A-Za-z_0-9.]+', text):
+            if tok.isdigit() and int(tok) in engine.FUSED_SIDES:
+                i = engine.FUSED_SIDES.index(int(tok))
+                run = run + 1 if i == nxt else 1
+                nxt = i + 1
+            else:
+                run, nxt = 0, None
+            best = max(best, run)
+        return best
+    assert _longest_run_of_sides('{64,84,88,96, 98}; "100 104 110 112 120 126 128"') == 12
+    assert _longest_run_of_sides('case 64: { constexpr int N_ = 64; } case 84: TWO(88, 11, 8) TWO(96, 12, 8)') == 1
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith(('.h', '.hip', '.cpp', '.hpp')) and name not in ('psfmc_sides.h', 'psfmc_side_costs.h'):
+            assert _longest_run_of_sides(open(os.path.join(csrc, name)).read()) <= 10, name
+
+    table = open(os.path.join(csrc, 'psfmc_sides.h')).read()
+    table = table[table.index('#define PSFMC_SIDES(TWO, THREE)'):]
+    table = table[:table.index('\n\n')]
+    rows = re.findall(r'^\s*(?:TWO\((\d+), (\d+), (\d+)\)|THREE\((\d+)\))(?: \\)?$', table, re.M)
+    assert len(rows) == len(table.splitlines()) - 1                       # every line of the macro is a row
+    sides = tuple(int(r[0] or r[3]) for r in rows)
+    assert sides == tuple(engine.FUSED_SIDES)
+    for n, p, q, three in rows:
+        if three:
+            assert int(three) > 1024                                      # no P, T <= 32 reaches it
+        else:
+            assert int(p) * int(q) == int(n) and 1 <= int(p) <= 32 and 1 <= int(q) <= 32, n
+
     fft = open(os.path.join(csrc, 'psfmc_fft.h')).read()
     body = fft[fft.index('constexpr Fft3gPick fft3g_pick(int n)'):]
     body = body[:body.index('default:')]
@@ -254,3 +286,14 @@ def test_side_tables_agree_between_python_and_the_kernels():
     rows = re.findall(r'\{(\d+), ([0-9.]+)f, ([0-9.]+)f\}', costs)
     assert tuple(int(r[0]) for r in rows) == tuple(engine.FUSED_SIDES)
     assert all(5.0 < float(r[1]) < 40.0 and 3.0 < float(r[2]) < 30.0 for r in rows)      # picoseconds per pixel per walker
+
+    # the sides <= 1024 whose inverse row kernel is the three-stage one by default: the default build's last `return`
+    # of rows3_inv_default (the line above it belongs to a survey knob)
+    rows3 = open(os.path.join(csrc, 'psfmc_rows3_path.h')).read()
+    body = rows3[rows3.index('constexpr bool rows3_inv_default(int n) {'):]
+    body = body[:body.index('\n}')]
+    inv_default = [int(v) for v in re.findall(r'n == (\d+)', body.splitlines()[-1])]
+    assert 'rows3_only_side(n) ||' in body.splitlines()[-1] and inv_default and set(inv_default) <= set(sides)
+    variants = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'test_gpu_variants.py')).read()
+    listed = re.search(r'^ROWS3_SIDES = \[([0-9, ]+)\]', variants, re.M).group(1)
+    assert [int(v) for v in listed.split(',')] == sorted(v for v in inv_default if v <= 1024)
