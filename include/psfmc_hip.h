@@ -209,6 +209,34 @@ int psfmc_set_priors(psfmc_ctx* ctx, int field, int n_params, const int* family,
  * allocates max_walkers images of the transform's size.  Call between batches (it waits for the context's stream).
  */
 int psfmc_set_sersic_integrate(psfmc_ctx* ctx, int field, int n_sersic, const int* integrate);
+/*
+ * Auxiliary parameters: free parameters beyond the caller row, with the components that read them (not the
+ * reference's): a tilted sky (Sky(..., slope=(sx, sy))) and boxy / disky Sersic isophotes (Sersic(..., boxiness=c),
+ * GALFIT's C0).  Definitions: psfmc_amd/ModelComponents/Sky.py Sky.tilted_image and Sersic.py Sersic.general_image;
+ * kernels: csrc/psfmc_general.h.  Every walker carries an auxiliary vector of n_aux = 2 n_sky + n_sersic doubles:
+ * per Sky (model-file order) its slope d/dx, d/dy in ADU per pixel per pixel, then per Sersic its boxiness.
+ * aux_col[j] / aux_const[j] have the meaning of psfmc_set_layout's slot_col / slot_const (column of theta, or -1
+ * and a constant); a component without the keyword has -1 and 0.  sky_slope_flags [n_sky] and sersic_general_flags
+ * [n_sersic] say which components read their entries: a flagged Sky adds sx (x - (nx-1)/2) + sy (y - (ny-1)/2)
+ * over the field's own image shape, a flagged Sersic is rendered with rho^2 = (|u|^e + |v|^e)^(2/e), e = c + 2, and
+ * Sigma_e / A(c) (total magnitude kept); c <= -2 or not finite gives log-posterior -inf.  A flag on a pixel-
+ * integrated component is refused.  Call after the field's psfmc_set_layout[_field] (a new layout drops the
+ * field's aux layout) and, in joint fits, before psfmc_set_joint_priors.  n_aux = 0 removes the field's aux layout.
+ * The fields of one context keep their own flags and aux layouts.  A context that never receives an aux layout
+ * allocates nothing, launches nothing more and computes what it did without this call; the first one allocates
+ * max_walkers aux vectors and parameter blocks and (shared with the pixel-integrated profile) max_walkers images of
+ * the transform's size.  Every raw-vector entry point (log-posteriors, posterior sums, the device samplers, field
+ * sets, joint fits) derives the aux vectors on the device.
+ */
+int psfmc_set_aux_layout(psfmc_ctx* ctx, int field, int n_aux, const int* aux_col, const double* aux_const,
+                         const int* sky_slope_flags, const int* sersic_general_flags);
+/*
+ * Row-based entry points (psfmc_eval_batch[_field / _device], psfmc_eval_images[_field], psfmc_accumulate_images)
+ * take the auxiliary vectors of their W walkers from this companion call: aux [W][n_aux] (host) serves the NEXT
+ * row-based call of the context, which must have the same W; on a context with a flagged component such a call
+ * without its aux rows is refused (PSFMC_EINVAL), never evaluated without the terms.
+ */
+int psfmc_set_aux_rows(psfmc_ctx* ctx, int W, const double* aux);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -427,6 +455,10 @@ int psfmc_group_set_layout(psfmc_group* group, int n_sky, int n_params, const in
                            const double* p2);
 /* psfmc_set_priors on every device of the group */
 int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, const double* params);
+/* psfmc_set_aux_layout (field 0) on every device of the group (raw-vector entry points; the group's row-based
+ * psfmc_group_eval_batch has no aux rows and is refused on such a group) */
+int psfmc_group_set_aux_layout(psfmc_group* group, int n_aux, const int* aux_col, const double* aux_const,
+                               const int* sky_slope_flags, const int* sersic_general_flags);
 /* psfmc_set_sersic_integrate (field 0) on every device of the group */
 int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,

@@ -1,5 +1,5 @@
 import numpy as np
-from scipy.special import gamma, gammaincinv
+from scipy.special import gamma, gammaincinv, gammaln
 
 from .ComponentBase import ComponentBase, StochasticProperty
 
@@ -24,10 +24,18 @@ class Sersic(ComponentBase):
     centroid correction, which is NaN in the pixel whose centre is the component's centre (0/0), so that
     such a walker's log-posterior is -inf.  `integrate=True` asks for the PIXEL-INTEGRATED profile instead
     (`Sersic.integrated_image`; not the reference's): finite everywhere, an on-pixel centre included, and
-    several times closer to GALFIT's rendering in the core."""
+    several times closer to GALFIT's rendering in the core.
+
+    `boxiness=c` (a number or a prior; GALFIT's C0, not the reference's) generalises the isophotes to
+    superellipses |u|^(c+2) + |v|^(c+2) = const: boxy for c > 0, disky for c < 0, the plain ellipse at c = 0
+    (`Sersic.general_image`); `mag` stays the total magnitude.  c <= -2 or a non-finite c is outside the support
+    (log-prior -inf, like reff_b > reff).  None (the default) means absent: the component, its parameters and its
+    kernels are the plain profile's.  `boxiness` together with `integrate=True` is out of scope (the
+    pixel-integrated profile's second-order term and core refinement are derived for ellipses) and raises
+    ValueError."""
     device_kind = 'sersic'
     _fits_abbrs = [('Sersic', 'SER'), ('reff_b', 'REB'), ('reff', 'RE'),
-                   ('index', 'N'), ('angle', 'ANG')]
+                   ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')]
 
     xy = StochasticProperty()
     mag = StochasticProperty()
@@ -35,9 +43,10 @@ class Sersic(ComponentBase):
     reff_b = StochasticProperty()
     index = StochasticProperty()
     angle = StochasticProperty()
+    boxiness = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
-                 angle=None, angle_degrees=False, integrate=False):
+                 angle=None, angle_degrees=False, integrate=False, boxiness=None):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -47,21 +56,42 @@ class Sersic(ComponentBase):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = bool(integrate)
+        self.has_boxiness = boxiness is not None
+        if self.has_boxiness:
+            if self.integrate:
+                raise ValueError('Sersic: boxiness together with integrate=True is not supported (the '
+                                 'pixel-integrated profile is defined for elliptical isophotes)')
+            self.boxiness = boxiness
 
     def header_flags(self, count):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
-        when it is the pixel-integrated profile, nothing otherwise."""
-        return {'{:d}SERINT'.format(count): True} if self.integrate else {}
+        when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, nothing otherwise."""
+        out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
+        if self.has_boxiness:
+            out['{:d}SERBOX'.format(count)] = True
+        return out
 
-    # axis-ratio constraint: reff_b <= reff (Sersic.py:41-45)
+    @staticmethod
+    def _boxiness_ok(c):
+        """The support of the boxiness: finite and above -2 (e = c + 2 > 0)."""
+        c = np.asarray(c, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            return np.isfinite(c) & (c > -2)
+
+    # axis-ratio constraint: reff_b <= reff (Sersic.py:41-45); the boxiness has its support
     def log_priors(self):
         logp = super(Sersic, self).log_priors()
+        if self.has_boxiness and not np.all(Sersic._boxiness_ok(self.boxiness)):
+            return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
     def log_priors_batch(self, block):
         logp = super(Sersic, self).log_priors_batch(block)
         vals = self.values_batch(block)
-        return np.where(vals['reff_b'] > vals['reff'], -np.inf, logp)
+        logp = np.where(vals['reff_b'] > vals['reff'], -np.inf, logp)
+        if self.has_boxiness:
+            logp = np.where(Sersic._boxiness_ok(np.reshape(vals['boxiness'], (len(logp),))), logp, -np.inf)
+        return logp
 
     @staticmethod
     def kappa(index):
@@ -94,9 +124,45 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.has_boxiness:
+            arr += Sersic.general_image(row, float(np.ravel(self.boxiness)[0]), arr.shape)
+            return arr
         arr += (Sersic.integrated_image(row, arr.shape) if self.integrate
                 else Sersic.reference_image(row, arr.shape))
         return arr
+
+    @staticmethod
+    def superellipse_area_ratio(boxiness):
+        """A(c) = 4 Gamma(1 + 1/e)^2 / (pi Gamma(1 + 2/e)), e = c + 2: the area of the superellipse
+        |u|^e + |v|^e = 1 over the unit circle's (GALFIT's R(C0) is its reciprocal); A(0) = 1."""
+        e = np.asarray(boxiness, dtype=np.float64) + 2.0
+        return 4.0 / np.pi * np.exp(2.0 * gammaln(1.0 + 1.0 / e) - gammaln(1.0 + 2.0 / e))
+
+    @staticmethod
+    def general_image(row, boxiness, shape):
+        """The profile with boxy / disky isophotes on a `shape` image, from a derived row (`derived_row`: the plain
+        component's) and c = `boxiness`.  This numpy text is the DEFINITION the device kernels
+        (csrc/psfmc_general.h) are held to.  With e = c + 2,
+
+            u = m00 dx + m01 dy,  v = m10 dx + m11 dy,  rho^2 = (|u|^e + |v|^e)^(2/e)
+
+        and then the reference's formula unchanged: q = rho^2 / (dx^2 + dy^2), L = ln rho^2, g = -2 kappa p
+        exp(L (p - 1/2)), value = sb exp(-kappa expm1(L p)) (1 + g (q/12 g)), with sb = Sigma_e / A(c)
+        (`superellipse_area_ratio`), which keeps `mag` the total magnitude.  At c = 0 it is the reference's
+        profile in different bits; where the centre is a pixel centre it is NaN like that one."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        e = float(boxiness) + 2.0
+        yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+        dx, dy = xx - x0, yy - y0
+        u = m00 * dx + m01 * dy
+        v = m10 * dx + m11 * dy
+        with np.errstate(all='ignore'):
+            rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
+            q = rho2 / (dx ** 2 + dy ** 2)
+            L = np.log(rho2)
+            sb = sbeff / Sersic.superellipse_area_ratio(boxiness)
+            g = -2 * kappa * p * np.exp(L * (p - 0.5))
+            return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
 
     @staticmethod
     def _plain(row, x, y):

@@ -1,0 +1,146 @@
+// psfmc_general.h -- components with FREE PARAMETERS BEYOND THE ROW: boxy / disky Sersic isophotes
+// (`Sersic(..., boxiness=c)`, GALFIT's C0) and a tilted sky (`Sky(..., slope=(sx, sy))`).  Not the reference's.
+//
+// Definitions: psfmc_amd/ModelComponents/Sersic.py `Sersic.general_image` and Sky.py `Sky.tilted_image` (numpy);
+// these kernels are held to them.  The new parameters reach the device as a per-walker AUXILIARY VECTOR
+// aux[w][n_aux] = per Sky (sx, sy), then per Sersic its boxiness (k_theta_prep writes it from the walker's parameter
+// tile, psfmc_set_aux_rows from the host for row-based calls); caller rows and prep records keep their layouts.
+// Per walker the kernels write (or, behind the pixel-integrated profile's kernels, add to) the walker's EXTRA IMAGE
+// (psfmc_integrated.h: [ny][nx] doubles at model coordinates, added by the EXTRA instantiations of the rasterising
+// kernels).  A general Sersic component's block of the prep record is replaced by the neutral block, as an
+// integrated one's is, and its real block moves to gpar[w][k][kGenPar].
+//
+//   k_general_split   per (walker, component): move a flagged block to gpar with e = c + 2, 2 / e and Sigma_e / A(c),
+//                     A(c) = 4 Gamma(1 + 1/e)^2 / (pi Gamma(1 + 2/e)) (lgamma once per walker and component);
+//                     leave the neutral block; c <= -2 or not finite: the walker is skipped (log-posterior -inf)
+//   k_general_rows    a wave per image row over the field's own ly x lx pixels: the slope terms of the flagged skies
+//                     (the constant level stays in the record's head) plus every general component
+// The work per walker is fixed, each pixel is one lane's own sum in component order, there are no atomics: a
+// walker's bits do not depend on its batch.
+#pragma once
+#include "psfmc_device.h"
+#include "psfmc_integrated.h"
+
+namespace psfmc {
+
+constexpr int kGenPar = 12;          // the nine of a Sersic block (Sigma_e / A(c) in [8]), e, 2 / e, spare
+
+// aux[2 k], aux[2 k + 1]: Sky k's slope; aux[2 n_sky + k]: Sersic k's boxiness
+__host__ __device__ inline int aux_len(int n_sky, int n_sersic) { return 2 * n_sky + n_sersic; }
+
+// skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
+// component, and with it the walker's likelihood, NaN)
+__global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __restrict__ skip,
+                                double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
+                                const uint8_t* __restrict__ flags, int n_ps, int n_sersic, int n_psf, int n_psf_field,
+                                int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * n_sersic) return;
+    const int w = i / n_sersic, k = i - w * n_sersic;
+    // (skip[w] is not read here: sibling threads of the walker may set it in this launch, and every thread does the
+    // same work whatever they do -- a skipped walker's record is scratch, its PSF index is clamped below)
+    double* rec = prep + (size_t)w * plen;
+    int idx = (int)rec[kPrepPsfIdx];
+    idx = idx < 0 ? 0 : (idx >= n_psf ? n_psf - 1 : idx);
+    if (!flags[(idx / n_psf_field) * n_sersic + k]) return;
+    double* b = rec + kPrepHead + kPrepPs * n_ps + kPrepSersic * k;
+    double* o = gpar + (size_t)i * kGenPar;
+    const double c = aux[(size_t)w * aux_stride + 2 * n_sky + k];
+    const double e = c + 2.0;
+    const bool bad = !(c > -2.0) || !(c < INFINITY);
+    // 1 / A(c): the ellipse's area over the superellipse's
+    const double inv_a = 0.78539816339744830962 * exp(lgamma(1.0 + 2.0 / e) - 2.0 * lgamma(1.0 + 1.0 / e));
+    for (int j = 0; j < kPrepSersic - 1; ++j) o[j] = b[j];
+    o[8] = bad ? __builtin_nan("") : b[8] * inv_a;
+    o[9] = e;
+    o[10] = 2.0 / e;
+    o[11] = 0.0;
+    integ_neutral_block(b);
+    if (bad && skip) skip[w] = 1;
+}
+
+// one general component at one pixel: Sigma_e / A exp(-kappa (t - 1)) (1 + (2 kappa p t)^2 / (12 (dx^2 + dy^2))),
+// t = (|u|^e + |v|^e)^(2 p / e) -- the reference's formula with rho^2 = (|u|^e + |v|^e)^(2/e) (the elliptical radius of
+// its centroid term cancels as in raster_row), through the rasteriser's log2 / exp2
+struct GenPar { SersicPar s; double e, pe2, nkl, gk; };
+__device__ __forceinline__ GenPar load_general(const double* __restrict__ g) {
+    GenPar G;
+    G.s = load_sersic(g);
+    G.e = g[9];
+    G.pe2 = G.s.p * g[10];
+    G.nkl = -G.s.kappa * kIntegLog2e;
+    G.gk = -2.0 * G.s.kappa * G.s.p * 0.28867513459481288225;      // sqrt(1/12)
+    return G;
+}
+__device__ __forceinline__ double general_pixel(const GenPar& G, double x, double y) {
+    const double dx = x - G.s.x0, dy = y - G.s.y0;
+    const double u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
+    const double v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
+    const double au = fabs(u), av = fabs(v);
+    // |u| = 0 gives the term exactly 0 (not log2(0) e)
+    const double pu = au > 0.0 ? fast_exp2(G.e * fast_log2(au)) : 0.0;
+    const double pv = av > 0.0 ? fast_exp2(G.e * fast_log2(av)) : 0.0;
+    const double s = pu + pv;
+    const double t = s > 0.0 ? fast_exp2(G.pe2 * fast_log2(s)) : 0.0;
+    const double sb = G.s.sbeff * fast_exp2_floor(__builtin_fma(G.nkl, t, -G.nkl));
+    const double gt = G.gk * t;
+    const double val = sb * __builtin_fma(gt * gt, fast_rcp(__builtin_fma(dx, dx, dy * dy)), 1.0);
+    const double chk = (u + v) + (G.nkl + G.pe2);      // (the comparisons and the exponentials' clamps swallow a NaN)
+    return chk == chk ? val : chk;
+}
+
+// grid (ceil(ny / 4), n), 4 waves = 4 rows per workgroup.  add != 0: the pixel-integrated profile's kernels have
+// written the walkers' extra images, this one adds to them; else it writes them.
+// Only the field's own ly x lx corner of a walker's [ny][nx] slot is written (as k_integ_rows does); the EXTRA
+// readers clip to the same ly, lx from wrap_tab and never read beyond it.
+__global__ void __launch_bounds__(256)
+k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
+               const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
+               const uint8_t* __restrict__ sky_flags, const uint8_t* __restrict__ flags, int n_sersic, int n_psf,
+               int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
+               int add) {
+    const int w = blockIdx.y;
+    if (skip && skip[w]) return;
+    const int lane = threadIdx.x & 63;
+    const int iy = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int idx = integ_psf_index(prep + (size_t)w * plen, n_psf);
+    const int ly = wrap_tab ? wrap_tab[idx].ly : ny, lx = wrap_tab ? wrap_tab[idx].lx : nx;
+    if (iy >= ly || iy >= ny) return;
+    const int field = idx / n_psf_field;
+    const uint8_t* fl = flags + field * n_sersic;
+    const uint8_t* sfl = sky_flags + field * n_sky;
+    const double* a = aux + (size_t)w * aux_stride;
+    double* out = img + ((size_t)w * ny + iy) * nx;
+    const double y = (double)iy;
+    const double cx = 0.5 * (double)(lx - 1), cy = 0.5 * (double)(ly - 1);
+    const int xn = lx < nx ? lx : nx;
+    // what the row holds before the general components: the image the integrated kernels wrote (add) plus the skies'
+    // slope terms.  Each lane owns its pixels, so the passes below need no synchronisation.
+    auto base = [&](int ix) {
+        double acc = add ? out[ix] : 0.0;
+        for (int k = 0; k < n_sky; ++k) {
+            if (!sfl[k]) continue;                                     // wave-uniform
+            acc += __builtin_fma(a[2 * k], (double)ix - cx, a[2 * k + 1] * (y - cy));
+        }
+        return acc;
+    };
+    // components outermost: a component's parameters are loaded and its constants formed once per row, not per
+    // 64-pixel chunk; the first flagged component's pass starts from `base`, the later ones add to the row
+    bool first = true;
+    for (int k = 0; k < n_sersic; ++k) {
+        if (!fl[k]) continue;                                          // wave-uniform
+        const GenPar G = load_general(gpar + ((size_t)w * n_sersic + k) * kGenPar);
+        for (int x0 = 0; x0 < xn; x0 += 64) {
+            const int ix = x0 + lane;
+            if (ix < xn) out[ix] = (first ? base(ix) : out[ix]) + general_pixel(G, (double)ix, y);
+        }
+        first = false;
+    }
+    if (first)
+        for (int x0 = 0; x0 < xn; x0 += 64) {
+            const int ix = x0 + lane;
+            if (ix < xn) out[ix] = base(ix);
+        }
+}
+
+}  // namespace psfmc

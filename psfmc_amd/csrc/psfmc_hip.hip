@@ -34,6 +34,7 @@
 #include "psfmc_theta.h"
 #if PSFMC_PART == 0
 #include "psfmc_integrated.h"
+#include "psfmc_general.h"
 #endif
 
 using namespace psfmc;
@@ -265,13 +266,25 @@ struct psfmc_ctx {
     std::vector<uint8_t> integ_flags;    // [n_fields][n_sersic]
     uint8_t* d_integ_flags = nullptr;
     double* d_integ_par = nullptr;       // [max_walkers][n_sersic][9] the integrated components' real blocks
-    double* d_integ_img = nullptr;       // [max_walkers][S] sum of a walker's integrated components, model coordinates
+    // the walkers' EXTRA IMAGES, model coordinates: what the kernels of psfmc_integrated.h and psfmc_general.h
+    // produce and the EXTRA instantiations of the rasterising kernels add (one buffer, any producer)
+    double* d_extra_img = nullptr;       // [max_walkers][S]
+    // auxiliary parameters, general Sersic components and tilted skies (psfmc_set_aux_layout, psfmc_general.h);
+    // nothing is allocated and no kernel changes until a field registers an aux layout with a flag set
+    bool gen_any = false;
+    int aux_stride = 0, aux_n_sky = 0;   // doubles per walker of d_aux (2 n_sky + n_sersic), the same for every field
+    std::vector<uint8_t> gen_flags;      // [n_fields][n_sersic] general components, then [n_fields][n_sky] tilted skies
+    uint8_t* d_gen_flags = nullptr;
+    double* d_gen_par = nullptr;         // [max_walkers][n_sersic][kGenPar] the general components' real blocks
+    double* d_aux = nullptr;             // [max_walkers][aux_stride]
+    std::vector<void*> aux_blobs;        // [n_fields] the allocations behind the layouts' aux_col / aux_const
+    int aux_rows_w = -1;                 // walkers whose aux rows psfmc_set_aux_rows left in d_aux for the next row-based call
 };
 
-// the integrated-components image of the walker whose record `prep` points at (nullptr: none to add)
-static const double* integ_image_of(const psfmc_ctx* c, const double* prep) {
-    if (!c->integ_any || !prep) return nullptr;
-    return c->d_integ_img + (size_t)((prep - c->d_prep) / c->plen) * c->S;
+// the extra image of the walker whose record `prep` points at (nullptr: none to add)
+static const double* extra_image_of(const psfmc_ctx* c, const double* prep) {
+    if ((!c->integ_any && !c->gen_any) || !prep) return nullptr;
+    return c->d_extra_img + (size_t)((prep - c->d_prep) / c->plen) * c->S;
 }
 
 // a field's image window inside the transform-shaped pixel arrays (all of them unless the image is embedded)
@@ -307,7 +320,7 @@ static int launch_rows3_fwd_kernel(psfmc_ctx* c, int n, const double* prep, cons
     constexpr size_t lds = rows3_lds_bytes<S>();
     if constexpr (!FROM_IMAGE && !EXTRA) {
         // pixel-integrated components: the same kernel with their image added (its own instantiation)
-        if (const double* extra = ps_only ? nullptr : integ_image_of(c, prep))
+        if (const double* extra = ps_only ? nullptr : extra_image_of(c, prep))
             return launch_rows3_fwd_kernel<NX, false, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra, img_scale, raw_out,
                                                                   st);
     }
@@ -375,7 +388,7 @@ static int launch_rows_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const
     constexpr size_t lds = fused_row_lds_bytes<NX, FAST>();
     if constexpr (!FROM_IMAGE && !EXTRA) {
         // pixel-integrated components: the same kernel with their image added (its own instantiation)
-        if (const double* extra = ps_only ? nullptr : integ_image_of(c, prep))
+        if (const double* extra = ps_only ? nullptr : extra_image_of(c, prep))
             return launch_rows_fwd_kernel<NX, false, TS, FAST, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra,
                                                                            img_scale, raw_out, st);
     }
@@ -642,7 +655,7 @@ template <int NX>
 static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int groups, int group_size, hipStream_t st,
                               int per_field, int f0) {
     constexpr int RG = RasterShape<NX>::TPW;
-    if (const double* extra = integ_image_of(c, prep)) {      // pixel-integrated components: their image is added
+    if (const double* extra = extra_image_of(c, prep)) {      // pixel-integrated components: their image is added
         if (c->embed)
             hipLaunchKernelGGL((k_raster_sums_extra<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
                                c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
@@ -1378,8 +1391,10 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
-                    c->d_integ_img};
+                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux};
     for (void* p : bufs)
+        if (p) (void)hipFree(p);
+    for (void* p : c->aux_blobs)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     for (int i = 1; i < psfmc_ctx::kMaxStreams; ++i) {
@@ -1545,7 +1560,7 @@ static int hipfft_convolve(psfmc_ctx* c, int n, const double* d_prep, const uint
     const size_t lds = (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double);
     RC_TRY(use_plans(c, 2 * n));
     hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256), lds, st, d_prep, d_skip,
-                       c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, ps_only, integ_image_of(c, d_prep));
+                       c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, ps_only, extra_image_of(c, d_prep));
     FFT_TRY(hipfftSetStream(c->plan_fwd, st));
     FFT_TRY(hipfftSetStream(c->plan_inv, st));
     FFT_TRY(hipfftExecD2Z(c->plan_fwd, c->d_real, (hipfftDoubleComplex*)c->d_spec));
@@ -1672,20 +1687,46 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
     const double p = rec[kPrepHead + kPrepPs * n_ps + kPrepSersic * k + 7];
     build_pow_table(p, rec + prep_rec_len(n_ps, n_sersic) + (size_t)k * kPowTab, lane);
 }
-// Pixel-integrated Sersic components (psfmc_integrated.h): after every kernel that writes prep records, same
-// stream, the walkers' integrated images are formed and the components' blocks made neutral for the rasterisers.
-static void launch_integrated(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
-    if (!c->integ_any || n <= 0) return;
+// The walkers' extra images: pixel-integrated Sersic components (psfmc_integrated.h), then general Sersic components
+// and tilted skies (psfmc_general.h).  After every kernel that writes prep records, same stream, the images are
+// formed and the components' blocks made neutral for the rasterisers.  The integrated profile's kernels WRITE the
+// images, the general kernel then ADDS to them; alone it writes.
+static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
+    if ((!c->integ_any && !c->gen_any) || n <= 0) return;
     double* prep = c->d_prep + (size_t)w_off * c->plen;
-    double* ipar = c->d_integ_par + (size_t)w_off * c->n_sersic * kPrepSersic;
-    double* img = c->d_integ_img + (size_t)w_off * c->S;
+    double* img = c->d_extra_img + (size_t)w_off * c->S;
     const int items = n * c->n_sersic;
+    if (c->gen_any) {
+        // (the flags the context owns are writable: a boxiness outside its support skips the walker)
+        uint8_t* own_skip = (skip && skip >= c->d_skip && skip < c->d_skip + c->max_walkers) ? const_cast<uint8_t*>(skip)
+                                                                                           : nullptr;
+        double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
+        const double* aux = c->d_aux + (size_t)w_off * c->aux_stride;
+        const uint8_t* sky_flags = c->d_gen_flags + (size_t)c->n_fields * c->n_sersic;
+        if (items > 0)
+            hipLaunchKernelGGL(k_general_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen,
+                               skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
+                               c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
+        if (!c->integ_any) {
+            hipLaunchKernelGGL(k_general_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
+                               aux, c->aux_stride, c->aux_n_sky, sky_flags, c->d_gen_flags, c->n_sersic, c->n_psf,
+                               c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0);
+            return;
+        }
+    }
+    double* ipar = c->d_integ_par + (size_t)w_off * c->n_sersic * kPrepSersic;
     hipLaunchKernelGGL(k_integ_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen, skip, ipar,
                        c->d_integ_flags, c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
     hipLaunchKernelGGL(k_integ_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, ipar,
                        c->d_integ_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
+    if (c->gen_any)
+        hipLaunchKernelGGL(k_general_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip,
+                           c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
+                           c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
+                           c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, c->d_gen_flags, c->n_sersic, c->n_psf,
+                           c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -1696,9 +1737,9 @@ static void launch_integrated(psfmc_ctx* c, int n, int w_off, const uint8_t* ski
 constexpr int kInWavePowTabWaves = 8192;
 // walkers [w_off, w_off + n) of c->d_prep; after the kernel that wrote their records, same stream.
 // (Only the forward row kernels read the tables: k_raster_sums keeps the log2 + exp2 form at every size.)
-static void launch_integrated(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st);
+static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st);
 static void launch_pow_tables(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
-    launch_integrated(c, n, w_off, skip, st);         // (before the tables: it rewrites the integrated components' blocks)
+    launch_extra_images(c, n, w_off, skip, st);       // (before the tables: it rewrites the flagged components' blocks)
     c->prep_tabs_valid = true;
     if (c->backend != PSFMC_BACKEND_FUSED || c->n_sersic == 0 || n <= 0 || !c->use_pow_tabs) return;
     const int pairs = n * c->n_sersic;
@@ -1711,8 +1752,10 @@ static void launch_pow_tables(psfmc_ctx* c, int n, int w_off, const uint8_t* ski
 }
 
 // field < 0: the rows' PSF index counts over every kernel spectrum of the context; field >= 0: within that field
+static int take_aux_rows(psfmc_ctx* c, int W);
 static int eval_device(psfmc_ctx* c, int W, const double* d_rows, const uint8_t* d_skip,
                        double* d_like, hipStream_t st, int field = -1) {
+    RC_TRY(take_aux_rows(c, W));
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, d_rows, c->d_prep, W, c->n_ps,
                        c->n_sersic, c->wraps[field < 0 ? 0 : field].ly, c->wraps[field < 0 ? 0 : field].lx, c->d_rho,
@@ -1732,6 +1775,24 @@ static int eval_device(psfmc_ctx* c, int W, const double* d_rows, const uint8_t*
 // for the usual one-field context): its layout, its block of kernel spectra
 // `n_seg` > 1: ONE launch for the fields `field` .. `field + n_seg - 1`, W walkers each (blockIdx.y = field):
 // the same per-walker arrays with field f's block at offset f W, every field's own layout
+// where k_theta_prep writes the auxiliary vectors of the walkers from w_off on (nullptr: the context has none);
+// aux rows a caller left for a row-based call are gone
+static AuxOut aux_out(psfmc_ctx* c, int w_off) {
+    c->aux_rows_w = -1;
+    return AuxOut{c->d_aux ? c->d_aux + (size_t)w_off * c->aux_stride : nullptr, c->aux_stride};
+}
+// Row-based calls on a context with general components or tilted skies read the walkers' auxiliary vectors that
+// psfmc_set_aux_rows left in d_aux; they serve one call.
+static int take_aux_rows(psfmc_ctx* c, int W) {
+    if (!c->gen_any) return PSFMC_OK;
+    const int have = c->aux_rows_w;
+    c->aux_rows_w = -1;
+    if (have != W)
+        return fail(PSFMC_EINVAL, "this context has general Sersic components or tilted skies (boxiness / slope): call "
+                    "psfmc_set_aux_rows for the %d walkers of a row-based call first (aux rows of %d walkers are set)",
+                    W, have);
+    return PSFMC_OK;
+}
 static void launch_theta_prep(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
                               double* d_rows, hipStream_t st, const StretchIn& sp, int field = 0, int w_off = 0,
                               int n_seg = 1) {
@@ -1743,7 +1804,7 @@ static void launch_theta_prep(psfmc_ctx* c, int W, const double* d_theta, const 
                        dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
                        L, d_theta, d_extra, d_rows, c->d_prep + (size_t)w_off * c->plen, c->d_lnprior + w_off,
                        c->d_skip + w_off, W, c->wraps[field].ly, c->wraps[field].lx, c->d_rho, sp, field * c->n_psf_field,
-                       segs);
+                       segs, aux_out(c, w_off));
     launch_pow_tables(c, W * n_seg, w_off, c->d_skip + w_off, st);
 }
 
@@ -1830,6 +1891,7 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
     const bool fused = c->backend == PSFMC_BACKEND_FUSED;
     const size_t S_img = img_pixels(c, field);                  // pixels of a host image (the field's own shape)
     const size_t img = S_img * sizeof(double);
+    RC_TRY(take_aux_rows(c, W));
     HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
@@ -1869,7 +1931,7 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
             hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256),
                                (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double), st, prep,
                                (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0,
-                               integ_image_of(c, prep));
+                               extra_image_of(c, prep));
             rc = emit(raw, c->d_real, 2, 0, IMG_COPY);
             if (rc != PSFMC_OK) break;
         }
@@ -1917,6 +1979,10 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     if (field > 0 && (!c->has_layout || n_sky != c->layout.n_sky || n_params != c->layout.n_params))
         return fail(PSFMC_EINVAL, "set field 0's layout first; every field has the same slots and columns");
     if (n_sky < 0 || n_sky > 16 || n_params < 0 || n_params > 4096) return fail(PSFMC_EINVAL, "bad counts");
+    if (c->d_aux && n_sky != c->aux_n_sky)
+        return fail(PSFMC_EINVAL, "n_sky=%d: the context's auxiliary vectors were allocated for %d skies "
+                    "(psfmc_set_aux_layout); a layout with another number of skies needs a new context", n_sky,
+                    c->aux_n_sky);
     const int ns = n_slots(n_sky, c->n_ps, c->n_sersic);
     if (!slot_col || !slot_const || (c->n_ps && !ps_method) || (c->n_sersic && !sersic_degrees) ||
         (n_params && (!family || !p0 || !p1 || !p2)))
@@ -1966,6 +2032,19 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.family = dip + ns + c->n_ps + c->n_sersic;
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
+    // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again)
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr;
+    if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
+    if (!c->gen_flags.empty()) {
+        const size_t n_ser = c->n_sersic, n_sk = c->aux_n_sky;
+        for (size_t k = 0; k < n_ser; ++k) c->gen_flags[(size_t)field * n_ser + k] = 0;
+        for (size_t k = 0; k < n_sk; ++k) c->gen_flags[(size_t)c->n_fields * n_ser + (size_t)field * n_sk + k] = 0;
+        bool any = false;
+        for (uint8_t f : c->gen_flags) any = any || f;
+        if (c->d_gen_flags)
+            HIP_TRY(hipMemcpy(c->d_gen_flags, c->gen_flags.data(), c->gen_flags.size(), hipMemcpyHostToDevice));
+        c->gen_any = any;
+    }
     if (c->n_fields > 1) {
         if (!c->d_field_layouts) HIP_TRY(hipMalloc(&c->d_field_layouts, (size_t)c->n_fields * sizeof(ThetaLayout)));
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
@@ -2021,27 +2100,119 @@ static int prior_table(int n_params, const int* family, const double* params, st
     return PSFMC_OK;
 }
 
+static int ensure_extra_images(psfmc_ctx* c, const char* what);
 extern "C" int psfmc_set_sersic_integrate(psfmc_ctx* c, int field, int n_sersic, const int* integrate) {
     if (!c || !integrate) return fail(PSFMC_EINVAL, "NULL argument");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
     if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
     HIP_TRY(hipSetDevice(c->device));
+    for (int k = 0; k < n_sersic; ++k)
+        if (integrate[k] && !c->gen_flags.empty() && c->gen_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d has a boxiness: boxiness and integrate exclude each other", k,
+                        field);
     if (c->integ_flags.empty()) c->integ_flags.assign((size_t)c->n_fields * c->n_sersic, 0);
     for (int k = 0; k < n_sersic; ++k) c->integ_flags[(size_t)field * n_sersic + k] = integrate[k] ? 1 : 0;
     bool any = false;
     for (uint8_t f : c->integ_flags) any = any || f;
-    if (any && !c->d_integ_img) {
+    if (any && !c->d_integ_flags) {
         HIP_TRY(hipMalloc(&c->d_integ_flags, c->integ_flags.size()));
         HIP_TRY(hipMalloc(&c->d_integ_par, (size_t)c->max_walkers * c->n_sersic * kPrepSersic * sizeof(double)));
-        if (hipMalloc(&c->d_integ_img, (size_t)c->max_walkers * c->S * sizeof(double)) != hipSuccess)
-            return fail(PSFMC_ENOMEM, "hipMalloc (integrated-profile images: %d walkers x %d pixels)", c->max_walkers,
-                        c->S);
+        RC_TRY(ensure_extra_images(c, "integrated-profile"));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));          // (no batch in flight reads the flags)
     if (c->d_integ_flags)
         HIP_TRY(hipMemcpy(c->d_integ_flags, c->integ_flags.data(), c->integ_flags.size(), hipMemcpyHostToDevice));
     c->integ_any = any;
     c->prep_tabs_valid = false;                        // records written under the old flags are not to be rasterised
+    return PSFMC_OK;
+}
+
+// the extra images (and nothing else) of a context that just got its first integrated / general flag
+static int ensure_extra_images(psfmc_ctx* c, const char* what) {
+    if (c->d_extra_img) return PSFMC_OK;
+    if (hipMalloc(&c->d_extra_img, (size_t)c->max_walkers * c->S * sizeof(double)) != hipSuccess)
+        return fail(PSFMC_ENOMEM, "hipMalloc (%s images: %d walkers x %d pixels)", what, c->max_walkers, c->S);
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const int* aux_col, const double* aux_const,
+                                    const int* sky_slope_flags, const int* sersic_general_flags) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const int want = aux_len(L.n_sky, c->n_sersic);
+    if (n_aux != 0 && n_aux != want)
+        return fail(PSFMC_EINVAL, "n_aux=%d: a layout of %d skies and %d Sersics has 2 x %d + %d", n_aux, L.n_sky,
+                    c->n_sersic, L.n_sky, c->n_sersic);
+    if (n_aux && (!aux_col || !aux_const || (L.n_sky && !sky_slope_flags) || (c->n_sersic && !sersic_general_flags)))
+        return fail(PSFMC_EINVAL, "NULL aux array");
+    for (int j = 0; j < n_aux; ++j)
+        if (aux_col[j] < -1 || aux_col[j] >= L.n_params)
+            return fail(PSFMC_EINVAL, "aux value %d refers to column %d of %d", j, aux_col[j], L.n_params);
+    for (int k = 0; n_aux && k < c->n_sersic; ++k)
+        if (sersic_general_flags[k] && !c->integ_flags.empty() && c->integ_flags[(size_t)field * c->n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: boxiness and integrate exclude each other",
+                        k, field);
+    if (c->d_aux && n_aux && (want != c->aux_stride || L.n_sky != c->aux_n_sky))
+        return fail(PSFMC_EINVAL, "n_aux=%d: the context's auxiliary vectors were allocated with %d values per walker",
+                    n_aux, c->aux_stride);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and flags being replaced
+    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
+    const int n_sky = L.n_sky, n_ser = c->n_sersic;
+    const size_t n_flags = (size_t)c->n_fields * (n_ser + n_sky);
+    if (c->gen_flags.size() != n_flags) c->gen_flags.assign(n_flags, 0);
+    uint8_t* ser_fl = c->gen_flags.data() + (size_t)field * n_ser;
+    uint8_t* sky_fl = c->gen_flags.data() + (size_t)c->n_fields * n_ser + (size_t)field * n_sky;
+    for (int k = 0; k < n_ser; ++k) ser_fl[k] = n_aux && sersic_general_flags[k] ? 1 : 0;
+    for (int k = 0; k < n_sky; ++k) sky_fl[k] = n_aux && sky_slope_flags[k] ? 1 : 0;
+    bool any = false;
+    for (uint8_t f : c->gen_flags) any = any || f;
+    if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
+    if (c->aux_blobs[field]) { (void)hipFree(c->aux_blobs[field]); c->aux_blobs[field] = nullptr; }
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr;
+    if (n_aux) {
+        // aux_const first (8-byte units), then aux_col
+        std::vector<unsigned char> blob((size_t)n_aux * (sizeof(double) + sizeof(int)));
+        memcpy(blob.data(), aux_const, (size_t)n_aux * sizeof(double));
+        memcpy(blob.data() + (size_t)n_aux * sizeof(double), aux_col, (size_t)n_aux * sizeof(int));
+        HIP_TRY(hipMalloc(&c->aux_blobs[field], blob.size()));
+        HIP_TRY(hipMemcpy(c->aux_blobs[field], blob.data(), blob.size(), hipMemcpyHostToDevice));
+        L.n_aux = n_aux;
+        L.aux_const = static_cast<const double*>(c->aux_blobs[field]);
+        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(c->aux_blobs[field]) +
+                                                 (size_t)n_aux * sizeof(double));
+    }
+    if (c->n_fields > 1 && c->d_field_layouts)
+        HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    if (n_aux && !c->d_aux) {                          // (every layout with n_aux > 0 writes aux vectors)
+        c->aux_stride = want;
+        c->aux_n_sky = n_sky;
+        HIP_TRY(hipMalloc(&c->d_gen_flags, n_flags));
+        HIP_TRY(hipMalloc(&c->d_gen_par, ((size_t)c->max_walkers * n_ser * kGenPar + 1) * sizeof(double)));
+        HIP_TRY(hipMalloc(&c->d_aux, (size_t)c->max_walkers * want * sizeof(double)));
+        HIP_TRY(hipMemset(c->d_aux, 0, (size_t)c->max_walkers * want * sizeof(double)));
+    }
+    if (any) RC_TRY(ensure_extra_images(c, "general-component"));
+    if (c->d_gen_flags)
+        HIP_TRY(hipMemcpy(c->d_gen_flags, c->gen_flags.data(), n_flags, hipMemcpyHostToDevice));
+    c->gen_any = any;
+    c->aux_rows_w = -1;
+    c->prep_tabs_valid = false;                        // records written under the old flags are not to be rasterised
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (!c->gen_any) return fail(PSFMC_EINVAL, "the context has no auxiliary parameters (psfmc_set_aux_layout)");
+    if (W < 0 || W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%d outside [0, max_walkers=%d]", W, c->max_walkers);
+    if (W > 0 && !aux) return fail(PSFMC_EINVAL, "NULL aux rows");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (no batch in flight reads d_aux)
+    if (W) HIP_TRY(hipMemcpy(c->d_aux, aux, (size_t)W * c->aux_stride * sizeof(double), hipMemcpyHostToDevice));
+    c->aux_rows_w = W;
     return PSFMC_OK;
 }
 
@@ -2424,7 +2595,7 @@ static int accumulate_from_prep(psfmc_ctx* c, int W, hipStream_t st, int f0 = 0,
             hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256),
                                (size_t)prep_rec_len(c->n_ps, c->n_sersic) * sizeof(double), st, prep,
                                (const uint8_t*)nullptr, c->d_real, c->n_ps, c->n_sersic, c->ny, c->nx, 0,
-                               integ_image_of(c, prep));
+                               extra_image_of(c, prep));
             acc(c->d_real, 2, 0, 0, n);
             RC_TRY(hipfft_convolve(c, n, prep, nullptr, st, 0));
         }
@@ -2450,6 +2621,7 @@ extern "C" int psfmc_accumulate_images(psfmc_ctx* c, int W, const double* rows) 
     if (!c->d_acc) RC_TRY(psfmc_reset_accumulated(c));
     RC_TRY(ensure_linear_sums(c));
     hipStream_t st = c->stream;
+    RC_TRY(take_aux_rows(c, W));
     HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
     c->prep_tabs_valid = false;                       // d_prep is being rewritten
     hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
@@ -3023,7 +3195,7 @@ static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, 
     hipLaunchKernelGGL(k_theta_prep, dim3((W + kThetaThreads - 1) / kThetaThreads, F),
                        dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
                        c->joint.fields[0], d_theta, d_extra, nullptr, c->d_prep, c->d_lnprior, c->d_skip, W,
-                       c->wraps[0].ly, c->wraps[0].lx, c->d_rho, StretchIn{}, 0, segs);
+                       c->wraps[0].ly, c->wraps[0].lx, c->d_rho, StretchIn{}, 0, segs, aux_out(c, 0));
     launch_pow_tables(c, W * F, 0, c->d_skip, st);
 }
 
@@ -3389,6 +3561,14 @@ extern "C" int psfmc_group_set_layout(psfmc_group* g, int n_sky, int n_params, c
 extern "C" int psfmc_group_set_priors(psfmc_group* g, int n_params, const int* family, const double* params) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_priors(c, 0, n_params, family, params));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_aux_layout(psfmc_group* g, int n_aux, const int* aux_col, const double* aux_const,
+                                          const int* sky_slope_flags, const int* sersic_general_flags) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx)
+        RC_TRY(psfmc_set_aux_layout(c, 0, n_aux, aux_col, aux_const, sky_slope_flags, sersic_general_flags));
     return PSFMC_OK;
 }
 

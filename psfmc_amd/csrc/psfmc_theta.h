@@ -41,6 +41,19 @@ struct ThetaLayout {
     const double* pd;           // [n_params] families 5..: see prior_prepare
     const double* pk;           // [n_params] the family's constant log term (prior_log_norm,
                                 //            prior_prepare), filled by psfmc_set_layout / _priors
+    // auxiliary parameters (psfmc_set_aux_layout, psfmc_general.h): per Sky its two slope values, then per
+    // Sersic its boxiness; entries as slot_col / slot_const.  n_aux = 0: none (the layout of a model without
+    // the keywords).  These two tables stay in global memory.
+    int n_aux;
+    const int* aux_col;         // [n_aux] column of theta, or -1
+    const double* aux_const;    // [n_aux]
+};
+
+// where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
+// every field; a field whose layout has n_aux = 0 writes nothing)
+struct AuxOut {
+    double* aux;
+    int stride;
 };
 
 // ---------------------------------------------------------------------------
@@ -475,7 +488,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
              const double* __restrict__ extra, double* __restrict__ rows,
              double* __restrict__ prep, double* __restrict__ lnprior,
              uint8_t* __restrict__ skip, int W, int ny, int nx,
-             const double* __restrict__ rho, StretchIn sp, int psf_base, FieldSegs segs) {
+             const double* __restrict__ rho, StretchIn sp, int psf_base, FieldSegs segs, AuxOut ax) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     if (segs.layouts) {                                 // (wave-uniform) this workgroup's field
         const int f = blockIdx.y;
@@ -490,6 +503,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
         prep += first * prep_len(G.n_ps, G.n_sersic);
         lnprior += first;
         skip += first;
+        if (ax.aux) ax.aux += first * ax.stride;
         psf_base += f * segs.psf_stride;
         if (sp.pos) {
             sp.pos += (size_t)f * sp.pos_stride;
@@ -600,7 +614,18 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
     for (int task = threadIdx.y; task < n_tasks; task += blockDim.y) {      // wave-uniform
         if (!active) continue;
         if (task == 0) {
-            const double lp = theta_log_prior(L, th, extra ? extra[w] : 0.0);
+            double lp = theta_log_prior(L, th, extra ? extra[w] : 0.0);
+            if (G.n_aux > 0) {                                              // wave-uniform
+                // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
+                // reff_b > reff is)
+                double* a = ax.aux + (size_t)w * ax.stride;
+                for (int j = 0; j < G.n_aux; ++j) {
+                    const int col = G.aux_col[j];
+                    const double v = col >= 0 ? th[col] : G.aux_const[j];
+                    a[j] = v;
+                    if (j >= 2 * G.n_sky && (!(v > -2.0) || !(v < INFINITY))) lp = -INFINITY;
+                }
+            }
             ok = lp == lp && fabs(lp) != INFINITY;                          // finite
             lnprior[w] = lp;
             skip[w] = ok ? 0 : 1;

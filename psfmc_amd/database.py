@@ -23,6 +23,8 @@ _COMMENTS = {'MCITER': 'number of retained samples',
              'MAPSAMP': 'Sample index of maximum posterior model',
              'PSFIMG': 'PSF image of maximum posterior model'}
 _INTEGRATE_COMMENT = 'pixel-integrated Sersic (not the reference profile)'
+_FLAG_COMMENTS = {'SERINT': _INTEGRATE_COMMENT, 'SERBOX': 'Sersic with boxy/disky isophotes (boxiness)',
+                  'SKYSLP': 'tilted sky (slope)'}
 
 
 class Table(object):
@@ -93,7 +95,7 @@ def save_database(sampler, model, db_name, meta_dict=None, sample_index='referen
     # components fitted with the pixel-integrated profile say so (<n>SERINT beside the component's <n>SER_* keys);
     # a model without the keyword writes the header it always wrote
     for key, val in getattr(model, 'header_flags', dict)().items():
-        meta[key] = (val, _INTEGRATE_COMMENT)
+        meta[key] = (val, _FLAG_COMMENTS.get(key.lstrip('0123456789'), _INTEGRATE_COMMENT))
     fits_io.write_table(db_name, cols, annotate_metadata(meta))
     return load_database(db_name)
 

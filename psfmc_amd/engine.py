@@ -257,6 +257,12 @@ def load_library():
     lib.psfmc_set_sersic_integrate.argtypes = [vp, ci, ci, ip]
     lib.psfmc_group_set_sersic_integrate.restype = ci
     lib.psfmc_group_set_sersic_integrate.argtypes = [vp, ci, ip]
+    lib.psfmc_set_aux_layout.restype = ci
+    lib.psfmc_set_aux_layout.argtypes = [vp, ci, ci, ip, _c_double_p, ip, ip]
+    lib.psfmc_set_aux_rows.restype = ci
+    lib.psfmc_set_aux_rows.argtypes = [vp, ci, _c_double_p]
+    lib.psfmc_group_set_aux_layout.restype = ci
+    lib.psfmc_group_set_aux_layout.argtypes = [vp, ci, ip, _c_double_p, ip, ip]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -296,6 +302,28 @@ def _prior_table(family, params):
 
 def _f64(arr):
     return np.ascontiguousarray(arr, dtype=np.float64)
+
+
+def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
+    """The arrays of psfmc_set_aux_layout (kept alive by the caller's tuple) and their ctypes pointers."""
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
+    col, sky, ser = i32(aux_col), i32(np.asarray(sky_flags, dtype=bool)), i32(np.asarray(sersic_flags, dtype=bool))
+    const = _f64(aux_const).ravel()
+    if len(col) != len(const) or len(col) != 2 * len(sky) + len(ser):
+        raise ValueError('aux layout: 2 values per Sky and 1 per Sersic, got {} for {} + {}'.format(
+            len(col), len(sky), len(ser)))
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    return (col, const, sky, ser), (len(col), ipt(col), _dp(const), ipt(sky), ipt(ser))
+
+
+def _send_aux_rows(lib, ctx, check, aux, n_w):
+    """psfmc_set_aux_rows for the next row-based call of n_w walkers (aux None: nothing to send)."""
+    if aux is None:
+        return
+    aux = _f64(aux)
+    if aux.ndim != 2 or aux.shape[0] != n_w:
+        raise ValueError('aux rows must be [W, n_aux] with the rows\' W')
+    check(lib.psfmc_set_aux_rows(ctx, int(n_w), _dp(aux)))
 
 
 def debug_math(op, values, device=0):
@@ -419,9 +447,10 @@ class Context(object):
             self._check(rc)
         return rc
 
-    def loglike(self, rows, skip=None):
+    def loglike(self, rows, skip=None, aux=None):
         """[W, row_len] derived rows -> [W] log-likelihoods (NaN/inf preserved;
-        skipped walkers -inf)."""
+        skipped walkers -inf).  aux: the walkers' [W, n_aux] auxiliary vectors, for a context with an aux
+        layout (`set_aux_layout`)."""
         rows = self._rows(rows)
         n_w = rows.shape[0]
         out = np.empty(n_w, dtype=np.float64)
@@ -433,6 +462,7 @@ class Context(object):
             if skip.shape != (n_w,):
                 raise ValueError('skip must be [W]')
             skip_p = skip.ctypes.data_as(_c_u8_p)
+        _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
         self._check(self._lib.psfmc_eval_batch(self._ctx, n_w, _dp(rows), skip_p, _dp(out)))
         return out
 
@@ -443,8 +473,8 @@ class Context(object):
             ctypes.c_void_p(d_skip) if d_skip else None, ctypes.c_void_p(d_out),
             ctypes.c_void_p(stream) if stream else None))
 
-    def images(self, rows, kinds=None):
-        """dict kind -> [W, ny, nx] for the requested image kinds."""
+    def images(self, rows, kinds=None, aux=None):
+        """dict kind -> [W, ny, nx] for the requested image kinds (aux: as for `loglike`)."""
         rows = self._rows(rows)
         kinds = self.IMAGE_KINDS if kinds is None else tuple(kinds)
         n_w = rows.shape[0]
@@ -459,6 +489,7 @@ class Context(object):
         if unknown:
             raise ValueError('unknown image kinds: {}'.format(sorted(unknown)))
         if n_w:
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
             self._check(self._lib.psfmc_eval_images(self._ctx, n_w, _dp(rows), *args))
         return bufs
 
@@ -487,6 +518,13 @@ class Context(object):
         flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
         self._check(self._lib.psfmc_set_sersic_integrate(
             self._ctx, 0, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+
+    def set_aux_layout(self, aux_col, aux_const, sky_flags, sersic_flags):
+        """Auxiliary parameters (psfmc_set_aux_layout; after `set_layout`): per Sky two slope entries, per Sersic
+        one boxiness entry -- column of theta or -1 and a constant -- and which components read them.  A context
+        that never gets the call is what it was without it."""
+        keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
+        self._check(self._lib.psfmc_set_aux_layout(self._ctx, 0, *args))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -667,11 +705,12 @@ class Context(object):
             raise ValueError('sums must be [4, ny, nx]')
         self._check(self._lib.psfmc_set_accumulated_sums(self._ctx, _dp(sums), int(count)))
 
-    def accumulate(self, rows):
+    def accumulate(self, rows, aux=None):
         """Add the five images of every row's walker to the device-resident
-        posterior sums."""
+        posterior sums (aux: as for `loglike`)."""
         rows = self._rows(rows)
         if len(rows):
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, len(rows))
             self._check(self._lib.psfmc_accumulate_images(self._ctx, len(rows), _dp(rows)))
 
     def accumulate_theta(self, theta):
@@ -815,6 +854,10 @@ class FieldSetContext(object):
                 flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
                 owner._check(owner._lib.psfmc_set_sersic_integrate(
                     owner._ctx, int(field), len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+
+            def set_aux_layout(self, aux_col, aux_const, sky_flags, sersic_flags):
+                keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
+                owner._check(owner._lib.psfmc_set_aux_layout(owner._ctx, int(field), *args))
         return _Proxy()
 
     @staticmethod
@@ -960,7 +1003,7 @@ class FieldSetContext(object):
         field's own vectors and places them there."""
         return FieldView(self, field, columns)
 
-    def loglike(self, field, rows, skip=None):
+    def loglike(self, field, rows, skip=None, aux=None):
         """[W] log-likelihoods of derived rows of one field (`Context.loglike` for a field of this context)."""
         rows = _f64(rows)
         n_w = rows.shape[0]
@@ -972,10 +1015,11 @@ class FieldSetContext(object):
             skip = np.ascontiguousarray(np.asarray(skip).astype(bool), dtype=np.uint8)
             skip_p = skip.ctypes.data_as(_c_u8_p)
         if n_w:
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
             self._check(self._lib.psfmc_eval_batch_field(self._ctx, int(field), n_w, _dp(rows), skip_p, _dp(out)))
         return out
 
-    def images(self, field, rows, kinds=None):
+    def images(self, field, rows, kinds=None, aux=None):
         """dict kind -> [W, ny, nx] of the requested per-sample images for derived rows of one field."""
         rows = _f64(rows)
         kinds = self.IMAGE_KINDS if kinds is None else tuple(kinds)
@@ -988,6 +1032,7 @@ class FieldSetContext(object):
             else:
                 args.append(None)
         if n_w:
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
             self._check(self._lib.psfmc_eval_images_field(self._ctx, int(field), n_w, _dp(rows), *args))
         return bufs
 
@@ -1033,11 +1078,11 @@ class FieldView(object):
         thetas[self.field] = theta
         return self.owner.logpost_theta(thetas)[self.field]
 
-    def images(self, rows, kinds=None):
-        return self.owner.images(self.field, rows, kinds)
+    def images(self, rows, kinds=None, aux=None):
+        return self.owner.images(self.field, rows, kinds, aux=aux)
 
-    def loglike(self, rows, skip=None):
-        return self.owner.loglike(self.field, rows, skip)
+    def loglike(self, rows, skip=None, aux=None):
+        return self.owner.loglike(self.field, rows, skip, aux=aux)
 
     def __getattr__(self, name):
         # the rest of Context's interface (device-resident sampler, raw-sum exchange, device pointers, ...) has
@@ -1172,7 +1217,15 @@ class ContextGroup(object):
         self._check(self._lib.psfmc_group_set_sersic_integrate(
             self._grp, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
 
-    def loglike(self, rows, skip=None):
+    def set_aux_layout(self, aux_col, aux_const, sky_flags, sersic_flags):
+        """`Context.set_aux_layout` on every device of the group."""
+        keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
+        self._check(self._lib.psfmc_group_set_aux_layout(self._grp, *args))
+
+    def loglike(self, rows, skip=None, aux=None):
+        if aux is not None:
+            raise NotImplementedError('derived rows of a model with a Sky `slope` or a Sersic `boxiness` are not '
+                                      'split over a ContextGroup: use logpost_theta (raw vectors)')
         rows = _f64(rows)
         if rows.ndim != 2 or rows.shape[1] != self.row_len:
             raise ValueError('rows must be [W, {}]'.format(self.row_len))

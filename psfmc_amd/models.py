@@ -226,6 +226,27 @@ class MultiComponentModel(object):
                 add(c, name)
             add(c, 'xy', 0); add(c, 'xy', 1)
         add(self.config.psf_selector, 'psf_index')
+        # auxiliary parameters (Sky slope, Sersic boxiness): per Sky two values, per Sersic one, a component
+        # without the keyword a neutral constant; registered after the layout, and only by a model with a keyword
+        n_main = len(slot_col)
+        for c in self._sky:
+            if c.has_slope:
+                add(c, 'slope', 0); add(c, 'slope', 1)
+            else:
+                slot_col += [-1, -1]; slot_const += [0.0, 0.0]
+        for c in self._sersic:
+            if c.has_boxiness:
+                add(c, 'boxiness')
+            else:
+                slot_col.append(-1); slot_const.append(0.0)
+        aux_col, aux_const = slot_col[n_main:], slot_const[n_main:]
+        slot_col, slot_const = slot_col[:n_main], slot_const[:n_main]
+        if columns is not None:
+            aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
+
+        def register_aux():
+            if self.has_aux:
+                eng.set_aux_layout(aux_col, aux_const, self.sky_slope_flags, self.sersic_general_flags)
         if columns is not None:
             slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
             zero = np.zeros(n_params)
@@ -233,6 +254,7 @@ class MultiComponentModel(object):
                            [SHIFT_METHODS[c.shift_method] for c in self._ps],
                            [int(bool(c.angle_degrees)) for c in self._sersic],
                            self.config.mag_zeropoint, np.zeros(n_params, dtype=np.int32), zero, zero, zero)
+            register_aux()
             return
         # families 0-4 as psfmc_set_layout takes them, the newer ones as host columns there; the full
         # table follows only where a newer family exists (a model of families 1-4 makes the same calls
@@ -245,6 +267,48 @@ class MultiComponentModel(object):
                        self.config.mag_zeropoint, np.where(new, 0, family), base[:, 0], base[:, 1], base[:, 2])
         if new.any():
             eng.set_priors(family, params)
+        register_aux()
+
+    @property
+    def sky_slope_flags(self):
+        """[n_sky] which Sky components (model-file order) were given a `slope`."""
+        return [bool(getattr(c, 'has_slope', False)) for c in self._sky]
+
+    @property
+    def sersic_general_flags(self):
+        """[n_sersic] which Sersic components (model-file order) were given a `boxiness`."""
+        return [bool(getattr(c, 'has_boxiness', False)) for c in self._sersic]
+
+    @property
+    def has_aux(self):
+        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`)?"""
+        return any(self.sky_slope_flags) or any(self.sersic_general_flags)
+
+    def aux_rows(self, theta):
+        """[W, P] emcee vectors -> [W, 2 n_sky + n_sersic] auxiliary vectors (include/psfmc_hip.h
+        psfmc_set_aux_layout: per Sky its slope, per Sersic its boxiness; zeros for components without the
+        keyword), or None for a model without the keywords: the companion of `derived_rows`."""
+        if not self.has_aux:
+            return None
+        theta = self._theta(theta)
+        n_w = theta.shape[0]
+        cols = []
+        for c, s in zip(self.components, self._spans):
+            if isinstance(c, Sky):
+                sl = c.values_batch(theta[:, s])['slope'] if c.has_slope else np.zeros((n_w, 2))
+                sl = np.reshape(sl, (n_w, 2))
+                cols += [sl[:, 0], sl[:, 1]]
+        for c, s in zip(self.components, self._spans):
+            if isinstance(c, Sersic):
+                cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
+                            else np.zeros(n_w))
+        return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
+
+    @staticmethod
+    def _aux_kw(aux, lo, hi):
+        """Keyword for the engine's row-based calls: rows [lo, hi) of `aux_rows`' result, nothing for a model
+        without the keywords (whose calls are what they always were)."""
+        return {} if aux is None else {'aux': aux[lo:hi]}
 
     @property
     def sersic_integrate(self):
@@ -393,9 +457,10 @@ class MultiComponentModel(object):
     # -- the hot path -----------------------------------------------------------
     def log_likelihood_batch(self, theta, skip=None):
         """[W] Gaussian log-likelihoods from the GPU; non-finite -> -inf."""
-        rows = self.derived_rows(theta)
+        rows, aux = self.derived_rows(theta), self.aux_rows(theta)
         cap = self._max_walkers                  # larger batches go through in slices
-        parts = [self.engine.loglike(rows[lo:lo + cap], None if skip is None else skip[lo:lo + cap])
+        parts = [self.engine.loglike(rows[lo:lo + cap], None if skip is None else skip[lo:lo + cap],
+                                     **self._aux_kw(aux, lo, lo + cap))
                  for lo in range(0, len(rows), cap)]
         ll = np.concatenate(parts) if parts else np.zeros(0)
         return np.where(np.isfinite(ll), ll, -np.inf)
@@ -458,9 +523,10 @@ class MultiComponentModel(object):
     def sample_images(self, theta, kinds=None):
         """The per-sample images of models.py:222-226 for W vectors:
         dict kind -> [W, ny, nx]."""
-        rows = self.derived_rows(theta)
+        rows, aux = self.derived_rows(theta), self.aux_rows(theta)
         cap = self._max_walkers
-        parts = [self.engine.images(rows[lo:lo + cap], kinds) for lo in range(0, max(len(rows), 1), cap)]
+        parts = [self.engine.images(rows[lo:lo + cap], kinds, **self._aux_kw(aux, lo, lo + cap))
+                 for lo in range(0, max(len(rows), 1), cap)]
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
     def _one_image(self, kind):
@@ -791,8 +857,8 @@ class JointModel(object):
         return self.field_models[0].obs_header
 
     def header_flags(self):
-        """`MultiComponentModel.header_flags` over the fields: a key's value is T where every field integrates the
-        component, else one letter per field ('TF': field 0 only)."""
+        """`MultiComponentModel.header_flags` over the fields: a key's value is T where every field has the flag
+        (pixel-integrated, boxiness, sky slope), else one letter per field ('TF': field 0 only)."""
         per = [m.header_flags() for m in self.field_models]
         out = {}
         for key in sorted(set().union(*per)):

@@ -1,0 +1,99 @@
+"""Cost of the general components (`Sersic(..., boxiness=...)`, `Sky(..., slope=...)`): log-posterior evaluations per
+second of the same synthetic field (Sky + PS + 1 Sersic) with one general Sersic and a tilted sky and without the
+keywords, vectors resident on the device (psfmc_eval_theta_device, what bench.py times), at 256^2 with 4096 walkers
+(the headline shape) and at 128^2 with 22 walkers.  One JSON line per configuration, a table at the end.
+Usage: python tools/time_general.py [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+import synth_field                                      # noqa: E402
+from psfmc_amd import MultiComponentModel, fits_io      # noqa: E402
+
+
+SKY = ('Sky(adu=Normal(loc=0, scale=0.01))', 'Sky(adu=Normal(loc=0, scale=0.01), slope=Normal(loc=(0, 0), scale=(1e-4, 1e-4)))')
+
+
+def build(side, directory, max_walkers, general):
+    fld = synth_field.make_field(side, n_sersic=1, seed=0)
+    for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
+        fits_io.write_image(os.path.join(directory, name), fld[key])
+    text = synth_field.model_file_text(side, 1)
+    text = text.replace('PointSource(', SKY[general] + '\nPointSource(', 1)
+    if general:
+        text = text.replace('angle_degrees=True)', 'angle_degrees=True, boxiness=Uniform(loc=-1, scale=2))')
+    path = os.path.join(directory, 'model_%d.py' % general)
+    with open(path, 'w') as f:
+        f.write(text)
+    return MultiComponentModel(path, max_walkers=max_walkers), fld
+
+
+def evals_per_second(model, theta, seconds):
+    import torch
+    eng = model.engine
+    d_theta = torch.as_tensor(theta, dtype=torch.float64, device='cuda').contiguous()
+    d_out = torch.empty(len(theta), dtype=torch.float64, device='cuda')
+    call = lambda: eng.logpost_theta_device(len(theta), d_theta.data_ptr(), 0, d_out.data_ptr())
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    n, t0 = 0, time.perf_counter()
+    while True:
+        for _ in range(20):
+            call()
+        torch.cuda.synchronize()
+        n += 20
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            break
+    assert torch.isfinite(d_out).all()
+    return n * len(theta) / dt, d_out.cpu().numpy()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', nargs='+', default=['256:4096', '128:22'], help='side:walkers')
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    rows = []
+    for shape in args.shapes:
+        side, n_w = (int(v) for v in shape.split(':'))
+        with tempfile.TemporaryDirectory() as tmp:
+            rates = {}
+            for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
+                model, fld = build(side, tmp, n_w, general)
+                theta = synth_field.draw_walkers(side, 1, n_w, seed=2, near_truth=fld['truth'])
+                rng = np.random.RandomState(3)
+                theta = np.hstack([rng.normal(size=(n_w, 1)) * 1e-3, theta])            # the sky level
+                if general:                                                            # the slope, the boxiness
+                    theta = np.insert(theta, [1, 1, 5], np.c_[rng.normal(size=(n_w, 2)) * 1e-5,
+                                                              rng.uniform(-0.5, 0.5, n_w)], axis=1)
+                rate, _ = evals_per_second(model, theta, args.seconds)
+                rates[general] = max(rates.get(general, 0.0), rate)
+                model.close()
+            row = dict(side=side, walkers=n_w, default_evals_per_s=round(rates[0], 1),
+                       general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    lines = ['side     W   default evals/s     general evals/s  ratio']
+    for r in rows:
+        lines.append('%4d %5d %16.0f %19.0f %6.3f' % (r['side'], r['walkers'], r['default_evals_per_s'],
+                                                     r['general_evals_per_s'], r['ratio']))
+    print('\n'.join(lines))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
