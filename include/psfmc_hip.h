@@ -237,6 +237,29 @@ int psfmc_set_aux_layout(psfmc_ctx* ctx, int field, int n_aux, const int* aux_co
  * without its aux rows is refused (PSFMC_EINVAL), never evaluated without the terms.
  */
 int psfmc_set_aux_rows(psfmc_ctx* ctx, int W, const double* aux);
+/*
+ * Azimuthal Fourier modes on the isophotes of general Sersic components (Sersic(..., fourier={m: (a_m, phi_m)}),
+ * GALFIT's F1 ... F6; not the reference's).  Definition: psfmc_amd/ModelComponents/Sersic.py Sersic.fourier_image;
+ * kernels: csrc/psfmc_general.h.  mode_mask [n_sersic]: bit m - 1 set where Sersic component k (model-file order)
+ * has mode m, m = 1 ... PSFMC_FOURIER_MODES; col / konst [n_sersic][PSFMC_FOURIER_MODES][2] have the meaning of
+ * psfmc_set_layout's slot_col / slot_const for the amplitude and the phase of every mode (an absent mode has -1 and
+ * 0).  The call APPENDS these 12 n_sersic entries to the field's auxiliary table behind the 2 n_sky + n_sersic
+ * entries of psfmc_set_aux_layout, whose indexing does not change; from the first such call on, every walker's
+ * auxiliary vector of the context -- psfmc_set_aux_rows' rows included -- has 2 n_sky + 13 n_sersic doubles, the
+ * entries of a field without modes unused.  A component with modes is rendered with rho^2 = (|u|^e + |v|^e)^(2/e)
+ * (1 + eps)^2, eps = sum_m a_m cos(m (t + phi_m)), t the angle in the component's (u, v) frame, and Sigma_e /
+ * (A(c) Q) with Q the 128-point area ratio of the definition (total magnitude kept); phases are in degrees where
+ * the layout's sersic_degrees flag of the component is set.  A value that is not finite, or sum_m |a_m| >= 1,
+ * gives log-posterior -inf.  Call after the field's psfmc_set_aux_layout, which must flag the components that
+ * have modes as general (a new layout or aux layout drops the field's modes) and, in joint fits, before
+ * psfmc_set_joint_priors; an all-zero mask removes the field's modes.  Refused: a mode on a pixel-integrated or
+ * unflagged component, a mask bit above mode 6, a field without an aux layout.  The fields of one context keep
+ * their own masks, registered in any order.  A context that never receives a mode allocates nothing, launches
+ * nothing more and computes what it did without this call.
+ */
+#define PSFMC_FOURIER_MODES 6
+int psfmc_set_fourier_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* mode_mask, const int* col,
+                             const double* konst);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -460,6 +483,9 @@ int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, 
 int psfmc_group_set_aux_layout(psfmc_group* group, int n_aux, const int* aux_col, const double* aux_const,
                                const int* sky_slope_flags, const int* sersic_general_flags);
 /* psfmc_set_sersic_integrate (field 0) on every device of the group */
+/* psfmc_set_fourier_layout (field 0) on every device of the group */
+int psfmc_group_set_fourier_layout(psfmc_group* group, int n_sersic, const int* mode_mask, const int* col,
+                                   const double* konst);
 int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,
                            double* loglike);

@@ -32,10 +32,21 @@ class Sersic(ComponentBase):
     (log-prior -inf, like reff_b > reff).  None (the default) means absent: the component, its parameters and its
     kernels are the plain profile's.  `boxiness` together with `integrate=True` is out of scope (the
     pixel-integrated profile's second-order term and core refinement are derived for ellipses) and raises
-    ValueError."""
+    ValueError.
+
+    `fourier={m: (amplitude, phase), ...}` (numbers or priors, m in 1 ... 6; GALFIT's F1 ... F6, not the reference's)
+    bends the isophote radius by azimuthal modes, r = r0 (1 + sum_m a_m cos(m (theta + phi_m)))
+    (`Sersic.fourier_image`): m = 1 is lopsidedness, m = 3 and above pick up tails and arms; `mag` stays the total
+    magnitude.  The parameters are the attributes `f<m>_amp` and `f<m>_phase` (the phase in radians, or in degrees with
+    `angle_degrees`).  Amplitudes and phases must be finite and sum_m |a_m| < 1 (log-prior -inf otherwise).  A
+    component with `fourier` but without `boxiness` has c = 0; `fourier` with `integrate=True` raises ValueError."""
     device_kind = 'sersic'
-    _fits_abbrs = [('Sersic', 'SER'), ('reff_b', 'REB'), ('reff', 'RE'),
-                   ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')]
+    FOURIER_MODES = (1, 2, 3, 4, 5, 6)
+    FOURIER_POINTS = 128      # midpoint rule of the area ratio Q (`fourier_area_ratio`); fixed, the same on the device
+    _fits_abbrs = ([('Sersic', 'SER'), ('reff_b', 'REB'), ('reff', 'RE'),
+                    ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')] +
+                   [('f%d_amp' % m, 'F%dA' % m) for m in FOURIER_MODES] +
+                   [('f%d_phase' % m, 'F%dP' % m) for m in FOURIER_MODES])
 
     xy = StochasticProperty()
     mag = StochasticProperty()
@@ -44,9 +55,21 @@ class Sersic(ComponentBase):
     index = StochasticProperty()
     angle = StochasticProperty()
     boxiness = StochasticProperty()
+    f1_amp = StochasticProperty()
+    f1_phase = StochasticProperty()
+    f2_amp = StochasticProperty()
+    f2_phase = StochasticProperty()
+    f3_amp = StochasticProperty()
+    f3_phase = StochasticProperty()
+    f4_amp = StochasticProperty()
+    f4_phase = StochasticProperty()
+    f5_amp = StochasticProperty()
+    f5_phase = StochasticProperty()
+    f6_amp = StochasticProperty()
+    f6_phase = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
-                 angle=None, angle_degrees=False, integrate=False, boxiness=None):
+                 angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -62,14 +85,59 @@ class Sersic(ComponentBase):
                 raise ValueError('Sersic: boxiness together with integrate=True is not supported (the '
                                  'pixel-integrated profile is defined for elliptical isophotes)')
             self.boxiness = boxiness
+        self.fourier_modes = ()
+        if fourier is not None:
+            if self.integrate:
+                raise ValueError('Sersic: fourier together with integrate=True is not supported (the '
+                                 'pixel-integrated profile is defined for elliptical isophotes)')
+            modes = []
+            for m, entry in dict(fourier).items():
+                if isinstance(m, bool) or int(m) != m or int(m) not in Sersic.FOURIER_MODES:
+                    raise ValueError('Sersic: fourier mode numbers are integers in 1 ... 6, got {!r}'.format(m))
+                try:
+                    amp, phase = entry
+                except (TypeError, ValueError):
+                    raise ValueError('Sersic: fourier mode {} needs (amplitude, phase)'.format(m))
+                if int(m) in modes:
+                    raise ValueError('Sersic: fourier mode {} given twice'.format(int(m)))
+                modes.append(int(m))
+                setattr(self, 'f%d_amp' % int(m), amp)
+                setattr(self, 'f%d_phase' % int(m), phase)
+            self.fourier_modes = tuple(sorted(modes))
+        self.has_fourier = bool(self.fourier_modes)
+
+    @property
+    def is_general(self):
+        """Does the component run the general kernels (a `boxiness` or `fourier` keyword)?"""
+        return self.has_boxiness or self.has_fourier
 
     def header_flags(self, count):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
-        when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, nothing otherwise."""
+        when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, `<count>SERFOU` = the
+        comma-separated mode numbers when it has Fourier modes, nothing otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
             out['{:d}SERBOX'.format(count)] = True
+        if self.has_fourier:
+            out['{:d}SERFOU'.format(count)] = ','.join(str(m) for m in self.fourier_modes)
         return out
+
+    @staticmethod
+    def _fourier_ok(amps, phases):
+        """The support of the modes, amps / phases [..., n_modes]: every value finite and sum |a_m| < 1, so that
+        1 + eps > 0 at every angle."""
+        amps, phases = np.asarray(amps, dtype=np.float64), np.asarray(phases, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            return (np.all(np.isfinite(amps), axis=-1) & np.all(np.isfinite(phases), axis=-1) &
+                    (np.sum(np.abs(amps), axis=-1) < 1))
+
+    def _fourier_values(self, vals, n_w=None):
+        """(amps, phases in radians), each [n_modes] (n_w None: current values) or [n_w, n_modes]."""
+        shape = (len(self.fourier_modes),) if n_w is None else (n_w, len(self.fourier_modes))
+        get = (lambda k: np.reshape(vals[k], shape[:-1])) if n_w is not None else (lambda k: float(np.ravel(vals(k))[0]))
+        amps = np.stack([get('f%d_amp' % m) for m in self.fourier_modes], axis=-1).reshape(shape)
+        phases = np.stack([get('f%d_phase' % m) for m in self.fourier_modes], axis=-1).reshape(shape)
+        return amps, (np.deg2rad(phases) if self.angle_degrees else phases)
 
     @staticmethod
     def _boxiness_ok(c):
@@ -83,6 +151,8 @@ class Sersic(ComponentBase):
         logp = super(Sersic, self).log_priors()
         if self.has_boxiness and not np.all(Sersic._boxiness_ok(self.boxiness)):
             return -np.inf
+        if self.has_fourier and not Sersic._fourier_ok(*self._fourier_values(lambda k: getattr(self, k))):
+            return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
     def log_priors_batch(self, block):
@@ -91,6 +161,8 @@ class Sersic(ComponentBase):
         logp = np.where(vals['reff_b'] > vals['reff'], -np.inf, logp)
         if self.has_boxiness:
             logp = np.where(Sersic._boxiness_ok(np.reshape(vals['boxiness'], (len(logp),))), logp, -np.inf)
+        if self.has_fourier:
+            logp = np.where(Sersic._fourier_ok(*self._fourier_values(vals, len(logp))), logp, -np.inf)
         return logp
 
     @staticmethod
@@ -124,6 +196,11 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.has_fourier:
+            amps, phases = self._fourier_values(lambda k: getattr(self, k))
+            arr += Sersic.fourier_image(row, float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
+                                        list(zip(self.fourier_modes, amps, phases)), arr.shape)
+            return arr
         if self.has_boxiness:
             arr += Sersic.general_image(row, float(np.ravel(self.boxiness)[0]), arr.shape)
             return arr
@@ -161,6 +238,68 @@ class Sersic(ComponentBase):
             q = rho2 / (dx ** 2 + dy ** 2)
             L = np.log(rho2)
             sb = sbeff / Sersic.superellipse_area_ratio(boxiness)
+            g = -2 * kappa * p * np.exp(L * (p - 0.5))
+            return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
+
+    @staticmethod
+    def _fourier_eps(cos_t, sin_t, modes):
+        """eps = sum_m a_m (cos(m t) cos(m phi_m) - sin(m t) sin(m phi_m)): cos(m t), sin(m t) from
+        (cos t + i sin t)^m by repeated multiplication (no atan2)."""
+        eps = np.zeros(np.shape(cos_t))
+        todo = {int(m): (float(a), float(phi)) for m, a, phi in modes}
+        if len(todo) != len(list(modes)) or any(m < 1 or m > 6 for m in todo):
+            raise ValueError('fourier modes are distinct integers in 1 ... 6')
+        cm, sm = cos_t, sin_t
+        for m in range(1, max(todo) + 1 if todo else 1):
+            if m > 1:
+                cm, sm = cm * cos_t - sm * sin_t, sm * cos_t + cm * sin_t
+            if m in todo:
+                a, phi = todo[m]
+                eps = eps + a * (cm * np.cos(m * phi) - sm * np.sin(m * phi))
+        return eps
+
+    @staticmethod
+    def fourier_area_ratio(boxiness, modes, points=FOURIER_POINTS):
+        """Q: the area inside the perturbed isophote over the unperturbed one's, DEFINED as the midpoint sum
+            t_k = 2 pi (k + 1/2) / points,  w_k = (|cos t_k|^e + |sin t_k|^e)^(-2/e),
+            Q = sum_k w_k (1 + eps(t_k))^-2 / sum_k w_k
+        (the flux inside an isophote is proportional to the integral of [h(t) (1 + eps(t))]^-2 over the angle, with
+        h = rho_0 / r = w^(-1/2); for one mode at c = 0 the integral is (1 - a^2)^(-3/2))."""
+        e = float(boxiness) + 2.0
+        t = 2.0 * np.pi * (np.arange(points) + 0.5) / points
+        c, s = np.cos(t), np.sin(t)
+        w = (np.abs(c) ** e + np.abs(s) ** e) ** (-2.0 / e)
+        return np.sum(w * (1.0 + Sersic._fourier_eps(c, s, modes)) ** -2) / np.sum(w)
+
+    @staticmethod
+    def fourier_image(row, boxiness, modes, shape):
+        """The profile with azimuthal Fourier modes on the isophote radius on a `shape` image, from a derived row
+        (`derived_row`: the plain component's), c = `boxiness` (0.0 for a component without the keyword) and
+        `modes`, a list of (m, a_m, phi_m) with m distinct integers in 1 ... 6 and phi_m in radians.  This numpy
+        text is the DEFINITION the device kernels (csrc/psfmc_general.h) are held to.  With e = c + 2,
+
+            u = m00 dx + m01 dy,  v = m10 dx + m11 dy,  r = hypot(u, v),  cos t = u / r,  sin t = v / r
+            eps = sum_m a_m (cos(m t) cos(m phi_m) - sin(m t) sin(m phi_m))                 (`_fourier_eps`)
+            rho^2 = (|u|^e + |v|^e)^(2/e) (1 + eps)^2
+
+        (GALFIT's r = r0 (1 + sum_m a_m cos(m (theta + phi_m))) with theta the angle in the component's (u, v) frame),
+        and then `general_image` unchanged with sb = Sigma_e / (A(c) Q), Q = `fourier_area_ratio`, which keeps
+        `mag` the total magnitude.  Zero amplitudes give `general_image`; where the centre is a pixel centre the
+        value is NaN like that one's.  Support: finite values and sum_m |a_m| < 1 (1 + eps > 0 at every angle)."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        e = float(boxiness) + 2.0
+        yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+        dx, dy = xx - x0, yy - y0
+        u = m00 * dx + m01 * dy
+        v = m10 * dx + m11 * dy
+        with np.errstate(all='ignore'):
+            r = np.hypot(u, v)
+            eps = Sersic._fourier_eps(u / r, v / r, modes)
+            rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e) * (1.0 + eps) ** 2
+            q = rho2 / (dx ** 2 + dy ** 2)
+            L = np.log(rho2)
+            sb = sbeff / (Sersic.superellipse_area_ratio(boxiness) * Sersic.fourier_area_ratio(boxiness, modes))
             g = -2 * kappa * p * np.exp(L * (p - 0.5))
             return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
 

@@ -15,8 +15,18 @@
 //                     leave the neutral block; c <= -2 or not finite: the walker is skipped (log-posterior -inf)
 //   k_general_rows    a wave per image row over the field's own ly x lx pixels: the slope terms of the flagged skies
 //                     (the constant level stays in the record's head) plus every general component
+//   k_fourier_prep    (contexts with azimuthal Fourier modes only, between the two) a wave per (walker, component
+//                     with modes): a_m cos(m phi_m), a_m sin(m phi_m) per mode and the area ratio Q of the
+//                     perturbed isophote, Sigma_e / A(c) becomes Sigma_e / (A(c) Q); outside the support (a value
+//                     not finite, sum |a_m| >= 1) the walker is skipped
 // The work per walker is fixed, each pixel is one lane's own sum in component order, there are no atomics: a
 // walker's bits do not depend on its batch.
+//
+// AZIMUTHAL FOURIER MODES (`Sersic(..., fourier={m: (a_m, phi_m)})`, GALFIT's F1 ... F6; definition: Sersic.py
+// `Sersic.fourier_image`): rho^2 = (|u|^e + |v|^e)^(2/e) (1 + eps)^2, eps = sum_m a_m cos(m (t + phi_m)), t the angle
+// of (u, v).  psfmc_set_fourier_layout appends 2 kFouModes entries per Sersic -- per mode 1 ... 6 its amplitude and
+// its phase as declared (degrees where the layout's sersic_degrees flag is set) -- to the walkers' auxiliary vectors
+// BEHIND the aux_len entries; a per (field, Sersic) byte holds the mode mask (bit m - 1) and the degrees flag (bit 6).
 #pragma once
 #include "psfmc_device.h"
 #include "psfmc_integrated.h"
@@ -27,6 +37,13 @@ constexpr int kGenPar = 12;          // the nine of a Sersic block (Sigma_e / A(
 
 // aux[2 k], aux[2 k + 1]: Sky k's slope; aux[2 n_sky + k]: Sersic k's boxiness
 __host__ __device__ inline int aux_len(int n_sky, int n_sersic) { return 2 * n_sky + n_sersic; }
+
+constexpr int kFouModes = 6;         // modes 1 ... 6 (PSFMC_FOURIER_MODES)
+constexpr int kFouPar = 2 * kFouModes;   // per mode a_m cos(m phi_m), a_m sin(m phi_m); zeros for an absent mode
+constexpr int kFouPoints = 128;      // midpoint rule of Q (Sersic.FOURIER_POINTS): two points per lane
+constexpr int kFouModeBits = (1 << kFouModes) - 1, kFouDegrees = 1 << kFouModes;
+// the Fourier entries behind the aux_len ones: aux[base + kFouPar k + 2 (m - 1)] = a_m, ... + 1 = phi_m of Sersic k
+__host__ __device__ inline int fourier_len(int n_sersic) { return kFouPar * n_sersic; }
 
 // skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
 // component, and with it the walker's likelihood, NaN)
@@ -59,6 +76,103 @@ __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __
     if (bad && skip) skip[w] = 1;
 }
 
+// eps = sum_m a_m cos(m (t + phi_m)) = sum_m (cos(m t) A_m - sin(m t) B_m) from c1 = cos t, s1 = sin t: cos(m t),
+// sin(m t) by complex multiplication; modes above `top` (wave-uniform) are absent
+struct FouPar { double a[kFouModes], b[kFouModes]; int top; };
+__device__ __forceinline__ double fourier_eps(const FouPar& F, double c1, double s1) {
+    double cm = c1, sm = s1;
+    double eps = __builtin_fma(cm, F.a[0], -(sm * F.b[0]));
+#pragma unroll
+    for (int m = 1; m < kFouModes; ++m) {
+        if (m < F.top) {                                               // wave-uniform
+            const double cn = __builtin_fma(cm, c1, -(sm * s1));
+            sm = __builtin_fma(sm, c1, cm * s1);
+            cm = cn;
+            eps += __builtin_fma(cm, F.a[m], -(sm * F.b[m]));
+        }
+    }
+    return eps;
+}
+
+// 1 / sqrt(x): v_rsq_f64 and two Newton steps (as fast_rcp); x = 0 gives NaN (inf 0), which is what the centre
+// pixel is to be
+__device__ __forceinline__ double general_rsqrt(double x) {
+    double r = __builtin_amdgcn_rsq(x);
+    r = __builtin_fma(0.5 * r, __builtin_fma(-(x * r), r, 1.0), r);
+    return __builtin_fma(0.5 * r, __builtin_fma(-(x * r), r, 1.0), r);
+}
+
+// A wave per (walker, component): grid ceil(n n_sersic / 4), 4 waves per workgroup.  Lanes 0 ... 5 form their mode's
+// A_m = a_m cos(m phi_m), B_m = a_m sin(m phi_m) (zeros for an absent mode) and write them to fpar[w][k][kFouPar];
+// every lane then takes two of the kFouPoints points of
+//     Q = sum_k w_k (1 + eps(t_k))^-2 / sum_k w_k,   t_k = 2 pi (k + 1/2) / kFouPoints,  w_k = (|cos|^e + |sin|^e)^(-2/e)
+// and the two sums are reduced by a fixed xor butterfly (no atomics: the bits do not depend on the batch).  Lane 0
+// divides the component's Sigma_e / A(c) (gpar[8], written by k_general_split) by Q.  Outside the support -- an
+// amplitude or phase of the component's modes not finite, or sum |a_m| >= 1 in mode order -- gpar[8] becomes NaN and
+// the walker is skipped where the flags are writable (skip as for k_general_split).
+__global__ void __launch_bounds__(256)
+k_fourier_prep(const double* __restrict__ prep, int plen, uint8_t* __restrict__ skip, double* __restrict__ gpar,
+               double* __restrict__ fpar, const double* __restrict__ aux, int aux_stride, int aux_base,
+               const uint8_t* __restrict__ masks, int n_sersic, int n_psf, int n_psf_field, int n) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= n * n_sersic) return;                                     // wave-uniform
+    const int w = i / n_sersic, k = i - w * n_sersic;
+    int idx = (int)prep[(size_t)w * plen + kPrepPsfIdx];
+    idx = idx < 0 ? 0 : (idx >= n_psf ? n_psf - 1 : idx);
+    const int mask = masks[(idx / n_psf_field) * n_sersic + k];
+    if (!(mask & kFouModeBits)) return;                                // wave-uniform
+    const double* a = aux + (size_t)w * aux_stride + aux_base + kFouPar * k;
+    double amp = 0.0, ca = 0.0, sa = 0.0;
+    bool fin = true;
+    if (lane < kFouModes && ((mask >> lane) & 1)) {
+        amp = a[2 * lane];
+        double ph = a[2 * lane + 1];
+        fin = fabs(amp) < INFINITY && fabs(ph) < INFINITY;             // (false for a NaN)
+        if (mask & kFouDegrees) ph *= M_PI / 180.0;
+        double sn, cs;
+        sincos((double)(lane + 1) * ph, &sn, &cs);
+        ca = amp * cs;
+        sa = amp * sn;
+    }
+    FouPar F;
+    double sum_abs = 0.0;
+#pragma unroll
+    for (int m = 0; m < kFouModes; ++m) {
+        F.a[m] = __shfl(ca, m, 64);
+        F.b[m] = __shfl(sa, m, 64);
+        sum_abs += fabs(__shfl(amp, m, 64));
+    }
+    F.top = kFouModes;
+    const bool bad = __any(!fin) || !(sum_abs < 1.0);
+    double* g = gpar + (size_t)i * kGenPar;
+    const double e = g[9], me2 = -g[10];
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const double t = 6.283185307179586 * ((double)(lane + 64 * half) + 0.5) / (double)kFouPoints;
+        double sn, cs;
+        sincos(t, &sn, &cs);
+        const double wk = pow(pow(fabs(cs), e) + pow(fabs(sn), e), me2);
+        const double d = 1.0 + fourier_eps(F, cs, sn);
+        num += wk / (d * d);
+        den += wk;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        num += __shfl_xor(num, off, 64);
+        den += __shfl_xor(den, off, 64);
+    }
+    if (lane < kFouModes) {
+        double* o = fpar + (size_t)i * kFouPar;
+        o[2 * lane] = ca;
+        o[2 * lane + 1] = sa;
+    }
+    if (lane == 0) {
+        g[8] = bad ? __builtin_nan("") : g[8] * (den / num);
+        if (bad && skip) skip[w] = 1;
+    }
+}
+
 // one general component at one pixel: Sigma_e / A exp(-kappa (t - 1)) (1 + (2 kappa p t)^2 / (12 (dx^2 + dy^2))),
 // t = (|u|^e + |v|^e)^(2 p / e) -- the reference's formula with rho^2 = (|u|^e + |v|^e)^(2/e) (the elliptical radius of
 // its centroid term cancels as in raster_row), through the rasteriser's log2 / exp2
@@ -72,7 +186,11 @@ __device__ __forceinline__ GenPar load_general(const double* __restrict__ g) {
     G.gk = -2.0 * G.s.kappa * G.s.p * 0.28867513459481288225;      // sqrt(1/12)
     return G;
 }
-__device__ __forceinline__ double general_pixel(const GenPar& G, double x, double y) {
+// FOURIER: the component has azimuthal modes -- t = rho^(2p) gains the factor (1 + eps)^(2p), folded into the third
+// log2 / exp2 pair at the price of one more fast_log2; cos t, sin t from a reciprocal square root of u^2 + v^2.  The
+// FOURIER = false instantiation is the function as it was before the modes existed.
+template <bool FOURIER>
+__device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y) {
     const double dx = x - G.s.x0, dy = y - G.s.y0;
     const double u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
     const double v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
@@ -81,7 +199,17 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, double x, doubl
     const double pu = au > 0.0 ? fast_exp2(G.e * fast_log2(au)) : 0.0;
     const double pv = av > 0.0 ? fast_exp2(G.e * fast_log2(av)) : 0.0;
     const double s = pu + pv;
-    const double t = s > 0.0 ? fast_exp2(G.pe2 * fast_log2(s)) : 0.0;
+    double t;
+    if constexpr (FOURIER) {
+        const double rinv = general_rsqrt(__builtin_fma(u, u, v * v));
+        const double eps = fourier_eps(F, u * rinv, v * rinv);
+        // (1 + eps > 0 inside the support; a NaN of the centre pixel is swallowed by the clamps and comes back
+        // through the 0 * inf of the last term, as without modes)
+        const double l1 = (G.s.p + G.s.p) * fast_log2(1.0 + eps);
+        t = s > 0.0 ? fast_exp2(__builtin_fma(G.pe2, fast_log2(s), l1)) : 0.0;
+    } else {
+        t = s > 0.0 ? fast_exp2(G.pe2 * fast_log2(s)) : 0.0;
+    }
     const double sb = G.s.sbeff * fast_exp2_floor(__builtin_fma(G.nkl, t, -G.nkl));
     const double gt = G.gk * t;
     const double val = sb * __builtin_fma(gt * gt, fast_rcp(__builtin_fma(dx, dx, dy * dy)), 1.0);
@@ -93,12 +221,15 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, double x, doubl
 // written the walkers' extra images, this one adds to them; else it writes them.
 // Only the field's own ly x lx corner of a walker's [ny][nx] slot is written (as k_integ_rows does); the EXTRA
 // readers clip to the same ly, lx from wrap_tab and never read beyond it.
+// FOU: the context has Fourier modes (fpar, fmasks set); the FOU = false instantiation is the kernel as it was before
+// the modes existed -- its registers and occupancy are not paid for by contexts without modes.
+template <bool FOU>
 __global__ void __launch_bounds__(256)
 k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                const uint8_t* __restrict__ sky_flags, const uint8_t* __restrict__ flags, int n_sersic, int n_psf,
                int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
-               int add) {
+               int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -130,9 +261,26 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
     for (int k = 0; k < n_sersic; ++k) {
         if (!fl[k]) continue;                                          // wave-uniform
         const GenPar G = load_general(gpar + ((size_t)w * n_sersic + k) * kGenPar);
-        for (int x0 = 0; x0 < xn; x0 += 64) {
-            const int ix = x0 + lane;
-            if (ix < xn) out[ix] = (first ? base(ix) : out[ix]) + general_pixel(G, (double)ix, y);
+        FouPar F{};
+        // a component without modes runs the loop it always ran
+        const int modes = FOU ? fmasks[field * n_sersic + k] & kFouModeBits : 0;         // wave-uniform
+        if (FOU && modes) {
+            const double* f = fpar + ((size_t)w * n_sersic + k) * kFouPar;
+#pragma unroll
+            for (int m = 0; m < kFouModes; ++m) {
+                F.a[m] = f[2 * m];
+                F.b[m] = f[2 * m + 1];
+            }
+            F.top = 32 - __builtin_clz((unsigned)modes);                                 // the highest mode present
+            for (int x0 = 0; x0 < xn; x0 += 64) {
+                const int ix = x0 + lane;
+                if (ix < xn) out[ix] = (first ? base(ix) : out[ix]) + general_pixel<true>(G, F, (double)ix, y);
+            }
+        } else {
+            for (int x0 = 0; x0 < xn; x0 += 64) {
+                const int ix = x0 + lane;
+                if (ix < xn) out[ix] = (first ? base(ix) : out[ix]) + general_pixel<false>(G, F, (double)ix, y);
+            }
         }
         first = false;
     }

@@ -279,6 +279,14 @@ struct psfmc_ctx {
     double* d_aux = nullptr;             // [max_walkers][aux_stride]
     std::vector<void*> aux_blobs;        // [n_fields] the allocations behind the layouts' aux_col / aux_const
     int aux_rows_w = -1;                 // walkers whose aux rows psfmc_set_aux_rows left in d_aux for the next row-based call
+    // azimuthal Fourier modes (psfmc_set_fourier_layout, psfmc_general.h); nothing is allocated and no kernel changes
+    // until a field registers modes.  aux_base = 2 n_sky + n_sersic; aux_stride grows to aux_base + 12 n_sersic
+    // with the first registration
+    int aux_base = 0;
+    bool fou_any = false;
+    std::vector<uint8_t> fou_masks;      // [n_fields][n_sersic] mode mask (bit m - 1), bit 6: the phases are in degrees
+    uint8_t* d_fou_masks = nullptr;
+    double* d_fou_par = nullptr;         // [max_walkers][n_sersic][kFouPar]
 };
 
 // the extra image of the walker whose record `prep` points at (nullptr: none to add)
@@ -1391,7 +1399,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
-                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux};
+                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (void* p : c->aux_blobs)
@@ -1707,10 +1715,17 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
             hipLaunchKernelGGL(k_general_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
                                c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
+        if (c->fou_any && items > 0)
+            hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
+                               skip ? own_skip : nullptr, gpar, c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar,
+                               aux, c->aux_stride, c->aux_base, c->d_fou_masks, c->n_sersic, c->n_psf, c->n_psf_field,
+                               n);
         if (!c->integ_any) {
-            hipLaunchKernelGGL(k_general_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
-                               aux, c->aux_stride, c->aux_n_sky, sky_flags, c->d_gen_flags, c->n_sersic, c->n_psf,
-                               c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0);
+            hipLaunchKernelGGL(c->fou_any ? k_general_rows<true> : k_general_rows<false>, dim3((c->ny + 3) / 4, n),
+                               dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
+                               c->d_gen_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
+                               c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
+                               c->fou_any ? c->d_fou_masks : nullptr);
             return;
         }
     }
@@ -1722,11 +1737,14 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     if (c->gen_any)
-        hipLaunchKernelGGL(k_general_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip,
+        hipLaunchKernelGGL(c->fou_any ? k_general_rows<true> : k_general_rows<false>, dim3((c->ny + 3) / 4, n),
+                           dim3(256), 0, st, prep, c->plen, skip,
                            c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
                            c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
                            c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, c->d_gen_flags, c->n_sersic, c->n_psf,
-                           c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1);
+                           c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1,
+                           c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
+                           c->fou_any ? c->d_fou_masks : nullptr);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -1970,6 +1988,18 @@ extern "C" int psfmc_eval_images_field(psfmc_ctx* c, int field, int W, const dou
 // ---------------------------------------------------------------------------
 // raw-vector path
 // ---------------------------------------------------------------------------
+// a field's layout or aux layout is replaced: its Fourier modes (psfmc_set_fourier_layout) go with it
+static int drop_fourier_masks(psfmc_ctx* c, int field) {
+    if (c->fou_masks.empty()) return PSFMC_OK;
+    for (int k = 0; k < c->n_sersic; ++k) c->fou_masks[(size_t)field * c->n_sersic + k] = 0;
+    bool any = false;
+    for (uint8_t m : c->fou_masks) any = any || (m & kFouModeBits);
+    if (c->d_fou_masks)
+        HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), c->fou_masks.size(), hipMemcpyHostToDevice));
+    c->fou_any = any;
+    return PSFMC_OK;
+}
+
 static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, const int* slot_col,
                            const double* slot_const, const int* ps_method, const int* sersic_degrees,
                            double mag_zeropoint, const int* family, const double* p0,
@@ -2033,7 +2063,8 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
     // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again)
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr;
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0;
+    RC_TRY(drop_fourier_masks(c, field));
     if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
     if (!c->gen_flags.empty()) {
         const size_t n_ser = c->n_sersic, n_sk = c->aux_n_sky;
@@ -2155,9 +2186,9 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
         if (sersic_general_flags[k] && !c->integ_flags.empty() && c->integ_flags[(size_t)field * c->n_sersic + k])
             return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: boxiness and integrate exclude each other",
                         k, field);
-    if (c->d_aux && n_aux && (want != c->aux_stride || L.n_sky != c->aux_n_sky))
+    if (c->d_aux && n_aux && (want != c->aux_base || L.n_sky != c->aux_n_sky))
         return fail(PSFMC_EINVAL, "n_aux=%d: the context's auxiliary vectors were allocated with %d values per walker",
-                    n_aux, c->aux_stride);
+                    n_aux, c->aux_base);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and flags being replaced
     c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
@@ -2172,7 +2203,8 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     for (uint8_t f : c->gen_flags) any = any || f;
     if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
     if (c->aux_blobs[field]) { (void)hipFree(c->aux_blobs[field]); c->aux_blobs[field] = nullptr; }
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr;
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0;
+    RC_TRY(drop_fourier_masks(c, field));                // (the field's modes are registered after its aux layout)
     if (n_aux) {
         // aux_const first (8-byte units), then aux_col
         std::vector<unsigned char> blob((size_t)n_aux * (sizeof(double) + sizeof(int)));
@@ -2188,7 +2220,7 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     if (c->n_fields > 1 && c->d_field_layouts)
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
     if (n_aux && !c->d_aux) {                          // (every layout with n_aux > 0 writes aux vectors)
-        c->aux_stride = want;
+        c->aux_stride = c->aux_base = want;
         c->aux_n_sky = n_sky;
         HIP_TRY(hipMalloc(&c->d_gen_flags, n_flags));
         HIP_TRY(hipMalloc(&c->d_gen_par, ((size_t)c->max_walkers * n_ser * kGenPar + 1) * sizeof(double)));
@@ -2213,6 +2245,98 @@ extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
     HIP_TRY(hipStreamSynchronize(c->stream));          // (no batch in flight reads d_aux)
     if (W) HIP_TRY(hipMemcpy(c->d_aux, aux, (size_t)W * c->aux_stride * sizeof(double), hipMemcpyHostToDevice));
     c->aux_rows_w = W;
+    return PSFMC_OK;
+}
+
+static_assert(kFouModes == PSFMC_FOURIER_MODES, "mode count of include/psfmc_hip.h");
+extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, const int* mode_mask, const int* col,
+                                        const double* konst) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    if (n_sersic && (!mode_mask || !col || !konst)) return fail(PSFMC_EINVAL, "NULL fourier array");
+    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const int n_base = L.n_aux - L.n_fou, n_fou = fourier_len(n_sersic);
+    bool any_here = false;
+    for (int k = 0; k < n_sersic; ++k) {
+        if (mode_mask[k] & ~kFouModeBits)
+            return fail(PSFMC_EINVAL, "Sersic %d: mode mask 0x%x names a mode outside 1 ... %d", k, mode_mask[k], kFouModes);
+        any_here = any_here || mode_mask[k];
+    }
+    if (any_here && n_base <= 0)
+        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
+                    "modes flagged general) before psfmc_set_fourier_layout", field);
+    for (int k = 0; k < n_sersic; ++k) {
+        if (!mode_mask[k]) continue;
+        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: fourier and integrate exclude each other",
+                        k, field);
+        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d has modes but is not flagged general in the field's aux "
+                        "layout", k, field);
+    }
+    for (int j = 0; any_here && j < n_fou; ++j)
+        if (col[j] < -1 || col[j] >= L.n_params)
+            return fail(PSFMC_EINVAL, "fourier value %d refers to column %d of %d", j, col[j], L.n_params);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
+    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
+    if (!any_here && c->fou_masks.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
+    if (n_base > 0) {
+        // the field's table again: its aux entries as they are, then (with modes) the Fourier entries
+        std::vector<double> cst((size_t)n_base + (any_here ? n_fou : 0));
+        std::vector<int> cl(cst.size());
+        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_base * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_base * sizeof(int), hipMemcpyDeviceToHost));
+        for (int j = 0; any_here && j < n_fou; ++j) {
+            cst[(size_t)n_base + j] = konst[j];
+            cl[(size_t)n_base + j] = col[j];
+        }
+        const size_t n_all = cst.size();
+        std::vector<unsigned char> blob(n_all * (sizeof(double) + sizeof(int)));
+        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
+        memcpy(blob.data() + n_all * sizeof(double), cl.data(), n_all * sizeof(int));
+        void* fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, blob.size()));
+        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        (void)hipFree(c->aux_blobs[field]);
+        c->aux_blobs[field] = fresh;
+        L.n_aux = (int)n_all;
+        L.n_fou = any_here ? n_fou : 0;
+        L.aux_const = static_cast<const double*>(fresh);
+        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
+        if (c->n_fields > 1 && c->d_field_layouts)
+            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    }
+    if (c->fou_masks.empty()) c->fou_masks.assign((size_t)c->n_fields * n_sersic, 0);
+    std::vector<int> deg(n_sersic > 0 ? n_sersic : 1, 0);
+    if (any_here) HIP_TRY(hipMemcpy(deg.data(), L.sersic_deg, (size_t)n_sersic * sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n_sersic; ++k)
+        c->fou_masks[(size_t)field * n_sersic + k] =
+            (uint8_t)(mode_mask[k] ? (mode_mask[k] | (deg[k] ? kFouDegrees : 0)) : 0);
+    if (any_here && !c->d_fou_masks) {
+        // the first modes of the context: longer auxiliary vectors (the aux entries keep their places), the
+        // components' mode blocks and the masks
+        const int stride = c->aux_base + n_fou;
+        double* longer = nullptr;
+        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
+        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
+        (void)hipFree(c->d_aux);
+        c->d_aux = longer;
+        c->aux_stride = stride;
+        HIP_TRY(hipMalloc(&c->d_fou_masks, c->fou_masks.size()));
+        HIP_TRY(hipMalloc(&c->d_fou_par, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
+        HIP_TRY(hipMemset(c->d_fou_par, 0, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
+    }
+    bool any = false;
+    for (uint8_t m : c->fou_masks) any = any || (m & kFouModeBits);
+    if (c->d_fou_masks)
+        HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), c->fou_masks.size(), hipMemcpyHostToDevice));
+    c->fou_any = any;
+    c->aux_rows_w = -1;
+    c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
     return PSFMC_OK;
 }
 
@@ -3569,6 +3693,13 @@ extern "C" int psfmc_group_set_aux_layout(psfmc_group* g, int n_aux, const int* 
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx)
         RC_TRY(psfmc_set_aux_layout(c, 0, n_aux, aux_col, aux_const, sky_slope_flags, sersic_general_flags));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_fourier_layout(psfmc_group* g, int n_sersic, const int* mode_mask, const int* col,
+                                              const double* konst) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_fourier_layout(c, 0, n_sersic, mode_mask, col, konst));
     return PSFMC_OK;
 }
 

@@ -47,6 +47,9 @@ struct ThetaLayout {
     int n_aux;
     const int* aux_col;         // [n_aux] column of theta, or -1
     const double* aux_const;    // [n_aux]
+    // azimuthal Fourier modes (psfmc_set_fourier_layout): the LAST n_fou = 12 n_sersic of the n_aux entries, per
+    // Sersic and mode 1 ... 6 an amplitude and a phase; 0: none (every layout before the call)
+    int n_fou;
 };
 
 // where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
@@ -619,11 +622,28 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
                 // reff_b > reff is)
                 double* a = ax.aux + (size_t)w * ax.stride;
-                for (int j = 0; j < G.n_aux; ++j) {
+                const int n_base = G.n_aux - G.n_fou;
+                for (int j = 0; j < n_base; ++j) {
                     const int col = G.aux_col[j];
                     const double v = col >= 0 ? th[col] : G.aux_const[j];
                     a[j] = v;
                     if (j >= 2 * G.n_sky && (!(v > -2.0) || !(v < INFINITY))) lp = -INFINITY;
+                }
+                if (G.n_fou > 0) {                                          // wave-uniform
+                    // the Fourier entries, per Sersic 6 x (amplitude, phase); a value that is not finite or
+                    // sum |a_m| >= 1 (in mode order) is outside the support
+                    for (int j0 = n_base; j0 < G.n_aux; j0 += 12) {
+                        double sum_abs = 0.0;
+                        bool fin = true;
+                        for (int j = j0; j < j0 + 12; ++j) {
+                            const int col = G.aux_col[j];
+                            const double v = col >= 0 ? th[col] : G.aux_const[j];
+                            a[j] = v;
+                            fin = fin && fabs(v) < INFINITY;
+                            if (!((j - j0) & 1)) sum_abs += fabs(v);
+                        }
+                        if (!fin || !(sum_abs < 1.0)) lp = -INFINITY;
+                    }
                 }
             }
             ok = lp == lp && fabs(lp) != INFINITY;                          // finite

@@ -263,6 +263,10 @@ def load_library():
     lib.psfmc_set_aux_rows.argtypes = [vp, ci, _c_double_p]
     lib.psfmc_group_set_aux_layout.restype = ci
     lib.psfmc_group_set_aux_layout.argtypes = [vp, ci, ip, _c_double_p, ip, ip]
+    lib.psfmc_set_fourier_layout.restype = ci
+    lib.psfmc_set_fourier_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
+    lib.psfmc_group_set_fourier_layout.restype = ci
+    lib.psfmc_group_set_fourier_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -316,13 +320,31 @@ def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
     return (col, const, sky, ser), (len(col), ipt(col), _dp(const), ipt(sky), ipt(ser))
 
 
-def _send_aux_rows(lib, ctx, check, aux, n_w):
-    """psfmc_set_aux_rows for the next row-based call of n_w walkers (aux None: nothing to send)."""
+FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude and a phase entry each
+
+
+def _fourier_layout_args(mode_masks, col, const):
+    """The arrays of psfmc_set_fourier_layout (kept alive by the caller's tuple) and their ctypes pointers."""
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
+    mask, col, const = i32(mode_masks), i32(col), _f64(const).ravel()
+    if len(col) != len(const) or len(col) != 2 * FOURIER_MODES * len(mask):
+        raise ValueError('fourier layout: {} entries per Sersic, got {} for {}'.format(
+            2 * FOURIER_MODES, len(col), len(mask)))
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    return (mask, col, const), (len(mask), ipt(mask), ipt(col), _dp(const))
+
+
+def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
+    """psfmc_set_aux_rows for the next row-based call of n_w walkers (aux None: nothing to send).  width: the
+    context's values per walker where a field's rows may be shorter (a field without Fourier modes in a context
+    that has some): the rows are padded with zeros."""
     if aux is None:
         return
     aux = _f64(aux)
     if aux.ndim != 2 or aux.shape[0] != n_w:
         raise ValueError('aux rows must be [W, n_aux] with the rows\' W')
+    if width is not None and aux.shape[1] < width:
+        aux = np.ascontiguousarray(np.pad(aux, ((0, 0), (0, width - aux.shape[1]))))
     check(lib.psfmc_set_aux_rows(ctx, int(n_w), _dp(aux)))
 
 
@@ -525,6 +547,13 @@ class Context(object):
         that never gets the call is what it was without it."""
         keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
         self._check(self._lib.psfmc_set_aux_layout(self._ctx, 0, *args))
+
+    def set_fourier_layout(self, mode_masks, col, const):
+        """Azimuthal Fourier modes (psfmc_set_fourier_layout; after `set_aux_layout`): per Sersic a mask of its
+        modes (bit m - 1: mode m) and, per Sersic and mode 1 ... 6, an amplitude and a phase entry -- column of theta
+        or -1 and a constant.  A context that never gets the call is what it was without it."""
+        keep, args = _fourier_layout_args(mode_masks, col, const)
+        self._check(self._lib.psfmc_set_fourier_layout(self._ctx, 0, *args))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -858,6 +887,12 @@ class FieldSetContext(object):
             def set_aux_layout(self, aux_col, aux_const, sky_flags, sersic_flags):
                 keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
                 owner._check(owner._lib.psfmc_set_aux_layout(owner._ctx, int(field), *args))
+                owner._aux_base = len(keep[0])
+
+            def set_fourier_layout(self, mode_masks, col, const):
+                keep, args = _fourier_layout_args(mode_masks, col, const)
+                owner._check(owner._lib.psfmc_set_fourier_layout(owner._ctx, int(field), *args))
+                owner._aux_fourier = len(keep[1])
         return _Proxy()
 
     @staticmethod
@@ -1003,6 +1038,12 @@ class FieldSetContext(object):
         field's own vectors and places them there."""
         return FieldView(self, field, columns)
 
+    def _aux_width(self):
+        """Values per walker of the context's auxiliary vectors once a field registered Fourier modes (its fields'
+        rows without modes are padded to it), else None."""
+        fou = getattr(self, '_aux_fourier', 0)
+        return getattr(self, '_aux_base', 0) + fou if fou else None
+
     def loglike(self, field, rows, skip=None, aux=None):
         """[W] log-likelihoods of derived rows of one field (`Context.loglike` for a field of this context)."""
         rows = _f64(rows)
@@ -1015,7 +1056,7 @@ class FieldSetContext(object):
             skip = np.ascontiguousarray(np.asarray(skip).astype(bool), dtype=np.uint8)
             skip_p = skip.ctypes.data_as(_c_u8_p)
         if n_w:
-            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w, self._aux_width())
             self._check(self._lib.psfmc_eval_batch_field(self._ctx, int(field), n_w, _dp(rows), skip_p, _dp(out)))
         return out
 
@@ -1032,7 +1073,7 @@ class FieldSetContext(object):
             else:
                 args.append(None)
         if n_w:
-            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
+            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w, self._aux_width())
             self._check(self._lib.psfmc_eval_images_field(self._ctx, int(field), n_w, _dp(rows), *args))
         return bufs
 
@@ -1221,6 +1262,11 @@ class ContextGroup(object):
         """`Context.set_aux_layout` on every device of the group."""
         keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
         self._check(self._lib.psfmc_group_set_aux_layout(self._grp, *args))
+
+    def set_fourier_layout(self, mode_masks, col, const):
+        """`Context.set_fourier_layout` on every device of the group."""
+        keep, args = _fourier_layout_args(mode_masks, col, const)
+        self._check(self._lib.psfmc_group_set_fourier_layout(self._grp, *args))
 
     def loglike(self, rows, skip=None, aux=None):
         if aux is not None:

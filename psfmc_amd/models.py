@@ -241,12 +241,26 @@ class MultiComponentModel(object):
                 slot_col.append(-1); slot_const.append(0.0)
         aux_col, aux_const = slot_col[n_main:], slot_const[n_main:]
         slot_col, slot_const = slot_col[:n_main], slot_const[:n_main]
+        # azimuthal Fourier modes (Sersic `fourier`): per Sersic and mode 1 ... 6 an amplitude and a phase entry, a
+        # mode that is absent two neutral constants; registered after the aux layout, and only by a model with modes
+        n_before = len(slot_col)
+        for c in self._sersic:
+            for m in Sersic.FOURIER_MODES:
+                if m in c.fourier_modes:
+                    add(c, 'f%d_amp' % m); add(c, 'f%d_phase' % m)
+                else:
+                    slot_col += [-1, -1]; slot_const += [0.0, 0.0]
+        fou_col, fou_const = slot_col[n_before:], slot_const[n_before:]
+        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
         if columns is not None:
             aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
+            fou_col = [int(columns[c]) if c >= 0 else -1 for c in fou_col]
 
         def register_aux():
             if self.has_aux:
                 eng.set_aux_layout(aux_col, aux_const, self.sky_slope_flags, self.sersic_general_flags)
+            if any(self.sersic_fourier_masks):
+                eng.set_fourier_layout(self.sersic_fourier_masks, fou_col, fou_const)
         if columns is not None:
             slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
             zero = np.zeros(n_params)
@@ -276,18 +290,26 @@ class MultiComponentModel(object):
 
     @property
     def sersic_general_flags(self):
-        """[n_sersic] which Sersic components (model-file order) were given a `boxiness`."""
-        return [bool(getattr(c, 'has_boxiness', False)) for c in self._sersic]
+        """[n_sersic] which Sersic components (model-file order) run the general kernels: those given a `boxiness`
+        or `fourier` modes (a component with modes alone is a general one at c = 0)."""
+        return [bool(getattr(c, 'is_general', False)) for c in self._sersic]
+
+    @property
+    def sersic_fourier_masks(self):
+        """[n_sersic] bit m - 1 set where the Sersic component (model-file order) has Fourier mode m; 0: none."""
+        return [sum(1 << (m - 1) for m in getattr(c, 'fourier_modes', ())) for c in self._sersic]
 
     @property
     def has_aux(self):
-        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`)?"""
+        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness` or `fourier`)?"""
         return any(self.sky_slope_flags) or any(self.sersic_general_flags)
 
     def aux_rows(self, theta):
         """[W, P] emcee vectors -> [W, 2 n_sky + n_sersic] auxiliary vectors (include/psfmc_hip.h
         psfmc_set_aux_layout: per Sky its slope, per Sersic its boxiness; zeros for components without the
-        keyword), or None for a model without the keywords: the companion of `derived_rows`."""
+        keyword), or None for a model without the keywords: the companion of `derived_rows`.  A model with Fourier
+        modes appends psfmc_set_fourier_layout's 12 n_sersic entries: per Sersic and mode 1 ... 6 the amplitude and
+        the phase as declared (zeros for absent modes)."""
         if not self.has_aux:
             return None
         theta = self._theta(theta)
@@ -302,6 +324,13 @@ class MultiComponentModel(object):
             if isinstance(c, Sersic):
                 cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
+        if any(self.sersic_fourier_masks):
+            for c, s in zip(self.components, self._spans):
+                if isinstance(c, Sersic):
+                    vals = c.values_batch(theta[:, s]) if c.fourier_modes else {}
+                    for m in Sersic.FOURIER_MODES:
+                        for key in ('f%d_amp' % m, 'f%d_phase' % m):
+                            cols.append(np.reshape(vals[key], (n_w,)) if m in c.fourier_modes else np.zeros(n_w))
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
     @staticmethod
@@ -858,12 +887,15 @@ class JointModel(object):
 
     def header_flags(self):
         """`MultiComponentModel.header_flags` over the fields: a key's value is T where every field has the flag
-        (pixel-integrated, boxiness, sky slope), else one letter per field ('TF': field 0 only)."""
+        (pixel-integrated, boxiness, sky slope) -- or, for a valued key (the Fourier mode numbers), the value the
+        fields share -- else one letter per field ('TF': field 0 only)."""
         per = [m.header_flags() for m in self.field_models]
         out = {}
         for key in sorted(set().union(*per)):
             marks = ''.join('T' if key in p else 'F' for p in per)
-            out[key] = True if 'F' not in marks else marks
+            vals = [p[key] for p in per if key in p]
+            same = vals[0] if all(v == vals[0] for v in vals) else True
+            out[key] = same if 'F' not in marks else marks
         return out
 
     def field_columns(self, f):

@@ -2,7 +2,9 @@
 second of the same synthetic field (Sky + PS + 1 Sersic) with one general Sersic and a tilted sky and without the
 keywords, vectors resident on the device (psfmc_eval_theta_device, what bench.py times), at 256^2 with 4096 walkers
 (the headline shape) and at 128^2 with 22 walkers.  One JSON line per configuration, a table at the end.
-Usage: python tools/time_general.py [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+--fourier: the cost of the azimuthal modes instead -- Sky + PS + one Sersic with a free boxiness and two free modes
+(`fourier={1: ..., 3: ...}`) against the same model with the boxiness only.
+Usage: python tools/time_general.py [--fourier] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
 import argparse
 import json
 import os
@@ -37,6 +39,24 @@ def build(side, directory, max_walkers, general):
     return MultiComponentModel(path, max_walkers=max_walkers), fld
 
 
+FOURIER = (', fourier={1: (Uniform(loc=-0.4, scale=0.8), Uniform(loc=-180, scale=360)), '
+           '3: (Uniform(loc=-0.4, scale=0.8), Uniform(loc=-180, scale=360))}')
+
+
+def build_fourier(side, directory, max_walkers, modes):
+    """Sky + PS + one Sersic with a free boxiness, and with `modes` two free Fourier modes beside it."""
+    fld = synth_field.make_field(side, n_sersic=1, seed=0)
+    for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
+        fits_io.write_image(os.path.join(directory, name), fld[key])
+    text = synth_field.model_file_text(side, 1).replace('PointSource(', SKY[0] + '\nPointSource(', 1)
+    text = text.replace('angle_degrees=True)', 'angle_degrees=True, boxiness=Uniform(loc=-1, scale=2)%s)'
+                        % (FOURIER if modes else ''))
+    path = os.path.join(directory, 'model_f%d.py' % modes)
+    with open(path, 'w') as f:
+        f.write(text)
+    return MultiComponentModel(path, max_walkers=max_walkers), fld
+
+
 def evals_per_second(model, theta, seconds):
     import torch
     eng = model.engine
@@ -64,6 +84,7 @@ def main():
     ap.add_argument('--shapes', nargs='+', default=['256:4096', '128:22'], help='side:walkers')
     ap.add_argument('--seconds', type=float, default=1.0)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--fourier', action='store_true', help='boxiness + two free modes against boxiness only')
     args = ap.parse_args()
     rows = []
     for shape in args.shapes:
@@ -71,11 +92,17 @@ def main():
         with tempfile.TemporaryDirectory() as tmp:
             rates = {}
             for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
-                model, fld = build(side, tmp, n_w, general)
+                model, fld = (build_fourier if args.fourier else build)(side, tmp, n_w, general)
                 theta = synth_field.draw_walkers(side, 1, n_w, seed=2, near_truth=fld['truth'])
                 rng = np.random.RandomState(3)
                 theta = np.hstack([rng.normal(size=(n_w, 1)) * 1e-3, theta])            # the sky level
-                if general:                                                            # the slope, the boxiness
+                if args.fourier:                                   # the boxiness, then (a_1, phi_1, a_3, phi_3)
+                    theta = np.insert(theta, [5], rng.uniform(-0.5, 0.5, (n_w, 1)), axis=1)
+                    if general:
+                        theta = np.insert(theta, [6, 6, 6, 6], np.c_[rng.uniform(-0.3, 0.3, n_w), rng.uniform(-180, 180, n_w),
+                                                                     rng.uniform(-0.3, 0.3, n_w), rng.uniform(-180, 180, n_w)],
+                                          axis=1)
+                elif general:                                                          # the slope, the boxiness
                     theta = np.insert(theta, [1, 1, 5], np.c_[rng.normal(size=(n_w, 2)) * 1e-5,
                                                               rng.uniform(-0.5, 0.5, n_w)], axis=1)
                 rate, _ = evals_per_second(model, theta, args.seconds)
@@ -85,7 +112,8 @@ def main():
                        general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    lines = ['side     W   default evals/s     general evals/s  ratio']
+    lines = ['side     W   default evals/s     general evals/s  ratio' if not args.fourier else
+             'side     W  boxiness evals/s  box + modes evals/s  ratio']
     for r in rows:
         lines.append('%4d %5d %16.0f %19.0f %6.3f' % (r['side'], r['walkers'], r['default_evals_per_s'],
                                                      r['general_evals_per_s'], r['ratio']))
