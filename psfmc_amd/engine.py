@@ -1044,6 +1044,15 @@ class FieldSetContext(object):
         fou = getattr(self, '_aux_fourier', 0)
         return getattr(self, '_aux_base', 0) + fou if fou else None
 
+    def _field_aux(self, aux, n_w):
+        """The auxiliary rows of a row-based call of one field: the field's own, or -- for a field WITHOUT the keywords
+        in a context where another field has them, whose model has no auxiliary vectors (`aux_rows` is None) -- zero
+        rows of the context's width: the library wants rows for every row-based call of such a context, and nothing
+        reads them for a field whose flags are all clear."""
+        if aux is None and getattr(self, '_aux_base', 0):
+            return np.zeros((n_w, self._aux_base + getattr(self, '_aux_fourier', 0)))
+        return aux
+
     def loglike(self, field, rows, skip=None, aux=None):
         """[W] log-likelihoods of derived rows of one field (`Context.loglike` for a field of this context)."""
         rows = _f64(rows)
@@ -1056,7 +1065,8 @@ class FieldSetContext(object):
             skip = np.ascontiguousarray(np.asarray(skip).astype(bool), dtype=np.uint8)
             skip_p = skip.ctypes.data_as(_c_u8_p)
         if n_w:
-            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w, self._aux_width())
+            _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w), n_w,
+                           self._aux_width())
             self._check(self._lib.psfmc_eval_batch_field(self._ctx, int(field), n_w, _dp(rows), skip_p, _dp(out)))
         return out
 
@@ -1073,7 +1083,8 @@ class FieldSetContext(object):
             else:
                 args.append(None)
         if n_w:
-            _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w, self._aux_width())
+            _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w), n_w,
+                           self._aux_width())
             self._check(self._lib.psfmc_eval_images_field(self._ctx, int(field), n_w, _dp(rows), *args))
         return bufs
 
