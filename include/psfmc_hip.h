@@ -260,6 +260,35 @@ int psfmc_set_aux_rows(psfmc_ctx* ctx, int W, const double* aux);
 #define PSFMC_FOURIER_MODES 6
 int psfmc_set_fourier_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* mode_mask, const int* col,
                              const double* konst);
+/*
+ * Spiral arms on general Sersic components by coordinate rotation (Sersic(..., spiral={...}); GALFIT-style, not
+ * GALFIT's formula and not the reference's).  Definition: psfmc_amd/ModelComponents/Sersic.py Sersic.spiral_image;
+ * kernels: csrc/psfmc_general.h.  flags [n_sersic]: nonzero where Sersic component k (model-file order) has a spiral;
+ * col / konst [n_sersic][PSFMC_SPIRAL_PARAMS] have the meaning of psfmc_set_layout's slot_col / slot_const, per
+ * component in the order r_in, r_out, winding, alpha, inclination, sky_angle, as declared: the three angles are in
+ * degrees where the layout's sersic_degrees flag of the component is set.  An unflagged component's entries are never
+ * read; give it constants inside the support.  The call APPENDS these 6 n_sersic entries to the field's auxiliary
+ * table BEHIND everything it holds: the 2 n_sky + n_sersic entries of psfmc_set_aux_layout and the 12 n_sersic of
+ * psfmc_set_fourier_layout, whose indexing and argument checks do not change.  A context with spirals ALWAYS carries
+ * the Fourier block: a field without modes gets an empty one (constants 0, nothing more is launched for it), so that
+ * from the first such call on every walker's auxiliary vector of the context -- psfmc_set_aux_rows' rows included --
+ * has 2 n_sky + 19 n_sersic doubles, the spiral entries of Sersic k at 2 n_sky + 13 n_sersic + 6 k, the entries of a
+ * field without a spiral unused; the first call also allocates the per-walker constants spar[w][k][8].  A flagged
+ * component is rendered with its pixel offsets deprojected into the disk plane (sky angle, inclination), turned there
+ * by t = winding T(r) (r / r_out)^alpha, T = (1 + tanh(2 (2 r - r_in - r_out) / (r_out - r_in))) / 2, and then as a
+ * general component (boxiness and modes included) at Sigma_e / cos(inclination) (total magnitude kept).  A value that
+ * is not finite, r_in < 0, r_out <= r_in, alpha < 0 or |inclination| >= a right angle gives log-posterior -inf (NaN
+ * through a row-based call without writable skip flags).  Call after the field's psfmc_set_aux_layout, which must
+ * flag the components that have a spiral as general, after its psfmc_set_fourier_layout where that one is called (a
+ * new layout, aux layout or Fourier layout of the field drops its spirals) and, in joint fits, before
+ * psfmc_set_joint_priors; all-zero flags remove the field's spirals.  Refused (PSFMC_EINVAL): a flag on a
+ * pixel-integrated component or on one that is not flagged general, a field without an aux layout, a wrong n_sersic.
+ * The fields of one context keep their own flags, registered in any order.  A context that never receives a spiral
+ * allocates nothing, launches nothing more and computes what it did without this call.
+ */
+#define PSFMC_SPIRAL_PARAMS 6
+int psfmc_set_spiral_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* flags, const int* col,
+                            const double* konst);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -482,10 +511,13 @@ int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, 
  * psfmc_group_eval_batch has no aux rows and is refused on such a group) */
 int psfmc_group_set_aux_layout(psfmc_group* group, int n_aux, const int* aux_col, const double* aux_const,
                                const int* sky_slope_flags, const int* sersic_general_flags);
-/* psfmc_set_sersic_integrate (field 0) on every device of the group */
 /* psfmc_set_fourier_layout (field 0) on every device of the group */
 int psfmc_group_set_fourier_layout(psfmc_group* group, int n_sersic, const int* mode_mask, const int* col,
                                    const double* konst);
+/* psfmc_set_spiral_layout (field 0) on every device of the group */
+int psfmc_group_set_spiral_layout(psfmc_group* group, int n_sersic, const int* flags, const int* col,
+                                  const double* konst);
+/* psfmc_set_sersic_integrate (field 0) on every device of the group */
 int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,
                            double* loglike);

@@ -39,11 +39,28 @@ class Sersic(ComponentBase):
     (`Sersic.fourier_image`): m = 1 is lopsidedness, m = 3 and above pick up tails and arms; `mag` stays the total
     magnitude.  The parameters are the attributes `f<m>_amp` and `f<m>_phase` (the phase in radians, or in degrees with
     `angle_degrees`).  Amplitudes and phases must be finite and sum_m |a_m| < 1 (log-prior -inf otherwise).  A
-    component with `fourier` but without `boxiness` has c = 0; `fourier` with `integrate=True` raises ValueError."""
+    component with `fourier` but without `boxiness` has c = 0; `fourier` with `integrate=True` raises ValueError.
+
+    `spiral={'r_in': .., 'r_out': .., 'winding': .., 'alpha': .., 'inclination': .., 'sky_angle': ..}` (numbers or
+    priors; the first three keys are required, the others are fixed at 0.0 when absent; GALFIT-style coordinate
+    rotation, not GALFIT's formula and not the reference's) winds the component's coordinates in a disk plane that is
+    inclined to the sky, so that a bar turns into arms: the position angle grows by `winding` between `r_in` and
+    `r_out` along a tanh ramp times the power law (r / r_out)^alpha (`Sersic.spiral_image`); `mag` stays the total
+    magnitude.  The parameters are the attributes `spiral_r_in`, `spiral_r_out`, `spiral_wind`, `spiral_alpha`,
+    `spiral_incl`, `spiral_sky` (the three angles in radians, or in degrees with `angle_degrees`).  Support: all six
+    finite, r_in >= 0, r_out > r_in, alpha >= 0, |inclination| < pi/2 (log-prior -inf otherwise).  A component with
+    `spiral` alone is a general one with c = 0 and no modes; `spiral` with `integrate=True` raises ValueError."""
     device_kind = 'sersic'
     FOURIER_MODES = (1, 2, 3, 4, 5, 6)
     FOURIER_POINTS = 128      # midpoint rule of the area ratio Q (`fourier_area_ratio`); fixed, the same on the device
-    _fits_abbrs = ([('Sersic', 'SER'), ('reff_b', 'REB'), ('reff', 'RE'),
+    # the keys of `spiral` in the order of psfmc_set_spiral_layout's entries, their attributes and FITS abbreviations
+    SPIRAL_KEYS = ('r_in', 'r_out', 'winding', 'alpha', 'inclination', 'sky_angle')
+    SPIRAL_REQUIRED = ('r_in', 'r_out', 'winding')
+    SPIRAL_ATTRS = ('spiral_r_in', 'spiral_r_out', 'spiral_wind', 'spiral_alpha', 'spiral_incl', 'spiral_sky')
+    SPIRAL_ANGLES = ('spiral_wind', 'spiral_incl', 'spiral_sky')
+    _fits_abbrs = ([('Sersic', 'SER'), ('spiral_r_in', 'SRI'), ('spiral_r_out', 'SRO'), ('spiral_wind', 'SWD'),
+                    ('spiral_alpha', 'SAL'), ('spiral_incl', 'SIN'), ('spiral_sky', 'SPA'),
+                    ('reff_b', 'REB'), ('reff', 'RE'),
                     ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')] +
                    [('f%d_amp' % m, 'F%dA' % m) for m in FOURIER_MODES] +
                    [('f%d_phase' % m, 'F%dP' % m) for m in FOURIER_MODES])
@@ -67,9 +84,15 @@ class Sersic(ComponentBase):
     f5_phase = StochasticProperty()
     f6_amp = StochasticProperty()
     f6_phase = StochasticProperty()
+    spiral_r_in = StochasticProperty()
+    spiral_r_out = StochasticProperty()
+    spiral_wind = StochasticProperty()
+    spiral_alpha = StochasticProperty()
+    spiral_incl = StochasticProperty()
+    spiral_sky = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
-                 angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None):
+                 angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None, spiral=None):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -105,22 +128,58 @@ class Sersic(ComponentBase):
                 setattr(self, 'f%d_phase' % int(m), phase)
             self.fourier_modes = tuple(sorted(modes))
         self.has_fourier = bool(self.fourier_modes)
+        self.has_spiral = spiral is not None
+        if self.has_spiral:
+            if self.integrate:
+                raise ValueError('Sersic: spiral together with integrate=True is not supported (the '
+                                 'pixel-integrated profile is defined for elliptical isophotes)')
+            spiral = dict(spiral)
+            unknown = [k for k in spiral if k not in Sersic.SPIRAL_KEYS]
+            if unknown:
+                raise ValueError('Sersic: spiral has no key {!r} (keys: {})'.format(
+                    unknown[0], ', '.join(Sersic.SPIRAL_KEYS)))
+            missing = [k for k in Sersic.SPIRAL_REQUIRED if k not in spiral]
+            if missing:
+                raise ValueError('Sersic: spiral needs the key {!r}'.format(missing[0]))
+            for key, attr in zip(Sersic.SPIRAL_KEYS, Sersic.SPIRAL_ATTRS):
+                setattr(self, attr, spiral.get(key, 0.0))
 
     @property
     def is_general(self):
-        """Does the component run the general kernels (a `boxiness` or `fourier` keyword)?"""
-        return self.has_boxiness or self.has_fourier
+        """Does the component run the general kernels (a `boxiness`, `fourier` or `spiral` keyword)?"""
+        return self.has_boxiness or self.has_fourier or self.has_spiral
 
     def header_flags(self, count):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
         when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, `<count>SERFOU` = the
-        comma-separated mode numbers when it has Fourier modes, nothing otherwise."""
+        comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral, nothing
+        otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
             out['{:d}SERBOX'.format(count)] = True
         if self.has_fourier:
             out['{:d}SERFOU'.format(count)] = ','.join(str(m) for m in self.fourier_modes)
+        if self.has_spiral:
+            out['{:d}SERSPI'.format(count)] = True
         return out
+
+    @staticmethod
+    def _spiral_ok(spiral):
+        """The support of the spiral, spiral [..., 6] = (r_in, r_out, winding, alpha, inclination, sky_angle) with
+        the angles in radians: every value finite, r_in >= 0, r_out > r_in, alpha >= 0, |inclination| < pi/2."""
+        s = np.asarray(spiral, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            return (np.all(np.isfinite(s), axis=-1) & (s[..., 0] >= 0) & (s[..., 1] > s[..., 0]) & (s[..., 3] >= 0) &
+                    (np.abs(s[..., 4]) < 0.5 * np.pi))
+
+    def _spiral_values(self, vals, n_w=None):
+        """(r_in, r_out, winding, alpha, inclination, sky_angle), the angles in radians: [6] (n_w None: current
+        values) or [n_w, 6]."""
+        get = (lambda k: np.reshape(vals[k], (n_w,))) if n_w is not None else (lambda k: float(np.ravel(vals(k))[0]))
+        cols = [np.asarray(get(a), dtype=np.float64) for a in Sersic.SPIRAL_ATTRS]
+        if self.angle_degrees:
+            cols = [np.deg2rad(c) if a in Sersic.SPIRAL_ANGLES else c for a, c in zip(Sersic.SPIRAL_ATTRS, cols)]
+        return np.stack(cols, axis=-1)
 
     @staticmethod
     def _fourier_ok(amps, phases):
@@ -153,6 +212,8 @@ class Sersic(ComponentBase):
             return -np.inf
         if self.has_fourier and not Sersic._fourier_ok(*self._fourier_values(lambda k: getattr(self, k))):
             return -np.inf
+        if self.has_spiral and not Sersic._spiral_ok(self._spiral_values(lambda k: getattr(self, k))):
+            return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
     def log_priors_batch(self, block):
@@ -163,6 +224,8 @@ class Sersic(ComponentBase):
             logp = np.where(Sersic._boxiness_ok(np.reshape(vals['boxiness'], (len(logp),))), logp, -np.inf)
         if self.has_fourier:
             logp = np.where(Sersic._fourier_ok(*self._fourier_values(vals, len(logp))), logp, -np.inf)
+        if self.has_spiral:
+            logp = np.where(Sersic._spiral_ok(self._spiral_values(vals, len(logp))), logp, -np.inf)
         return logp
 
     @staticmethod
@@ -196,6 +259,12 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.has_spiral:
+            amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
+            arr += Sersic.spiral_image(row, float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
+                                       list(zip(self.fourier_modes, amps, phases)),
+                                       self._spiral_values(lambda k: getattr(self, k)), arr.shape)
+            return arr
         if self.has_fourier:
             amps, phases = self._fourier_values(lambda k: getattr(self, k))
             arr += Sersic.fourier_image(row, float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
@@ -300,6 +369,61 @@ class Sersic(ComponentBase):
             q = rho2 / (dx ** 2 + dy ** 2)
             L = np.log(rho2)
             sb = sbeff / (Sersic.superellipse_area_ratio(boxiness) * Sersic.fourier_area_ratio(boxiness, modes))
+            g = -2 * kappa * p * np.exp(L * (p - 0.5))
+            return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
+
+    @staticmethod
+    def spiral_image(row, boxiness, modes, spiral, shape):
+        """The profile with its coordinates wound into arms on a `shape` image, from a derived row (`derived_row`:
+        the plain component's), c = `boxiness` (0.0 without the keyword), `modes` as for `fourier_image` (may be
+        empty) and `spiral` = (r_in, r_out, winding, alpha, inclination, sky_angle), angles in radians.  This numpy
+        text is the DEFINITION the device kernels (csrc/psfmc_general.h) are held to.  GALFIT-style coordinate
+        rotation, not GALFIT's formula:
+
+            dx = x - x0,  dy = y - y0                                                         (pixel plane)
+            X = cos(sky) dx + sin(sky) dy,  Y = (-sin(sky) dx + cos(sky) dy) / cos(incl)      (disk plane)
+            r = hypot(X, Y)
+            T = (1 + tanh(2 (2 r - r_in - r_out) / (r_out - r_in))) / 2         (0.018 at r_in, 0.982 at r_out)
+            P = (r / r_out)^alpha for r > 0;  at r = 0: 1 if alpha == 0 else 0
+            t = winding T P
+            X' = cos(t) X + sin(t) Y,  Y' = -sin(t) X + cos(t) Y         (the pattern at radius r is turned by +t)
+            u = m00 X' + m01 Y',  v = m10 X' + m11 Y'
+
+        and from u, v on `fourier_image` unchanged -- eps from u, v, rho^2 = (|u|^e + |v|^e)^(2/e) (1 + eps)^2, the
+        reference's formula with q = rho^2 / (dx^2 + dy^2) taken in the PIXEL plane -- with sb = Sigma_e / (A(c) Q
+        cos(incl)).  The rotation (r, phi) -> (r, phi + t(r)) has unit Jacobian and the deprojection the constant
+        Jacobian 1 / cos(incl), so every isophote's pixel-plane area is cos(incl) times its disk-plane area and
+        `mag` stays the total magnitude in closed form.  winding = inclination = sky_angle = 0 gives `fourier_image`
+        (`general_image` without modes) bit for bit; where the centre is a pixel centre the value is NaN like
+        theirs.  Support: `_spiral_ok`."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        r_in, r_out, winding, alpha, incl, sky = [float(s) for s in spiral]
+        e = float(boxiness) + 2.0
+        yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+        dx, dy = xx - x0, yy - y0
+        cs, sn, ci = np.cos(sky), np.sin(sky), np.cos(incl)
+        with np.errstate(all='ignore'):
+            X = cs * dx + sn * dy
+            Y = (-sn * dx + cs * dy) / ci
+            r = np.hypot(X, Y)
+            T = 0.5 * (1.0 + np.tanh(2.0 * (2.0 * r - r_in - r_out) / (r_out - r_in)))
+            P = np.where(r > 0, (r / r_out) ** alpha, 1.0 if alpha == 0 else 0.0)
+            t = winding * T * P
+            ct, st = np.cos(t), np.sin(t)
+            Xr = ct * X + st * Y
+            Yr = -st * X + ct * Y
+            u = m00 * Xr + m01 * Yr
+            v = m10 * Xr + m11 * Yr
+            rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
+            area = Sersic.superellipse_area_ratio(boxiness)
+            if modes:
+                ruv = np.hypot(u, v)
+                rho2 = rho2 * (1.0 + Sersic._fourier_eps(u / ruv, v / ruv, modes)) ** 2
+                area = area * Sersic.fourier_area_ratio(boxiness, modes)
+            q = rho2 / (dx ** 2 + dy ** 2)
+            L = np.log(rho2)
+            sb = sbeff / area / ci
             g = -2 * kappa * p * np.exp(L * (p - 0.5))
             return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
 

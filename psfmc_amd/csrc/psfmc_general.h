@@ -27,6 +27,16 @@
 // of (u, v).  psfmc_set_fourier_layout appends 2 kFouModes entries per Sersic -- per mode 1 ... 6 its amplitude and
 // its phase as declared (degrees where the layout's sersic_degrees flag is set) -- to the walkers' auxiliary vectors
 // BEHIND the aux_len entries; a per (field, Sersic) byte holds the mode mask (bit m - 1) and the degrees flag (bit 6).
+//
+// SPIRAL ARMS (`Sersic(..., spiral={...})`, GALFIT-style coordinate rotation; definition: Sersic.py
+// `Sersic.spiral_image`): ahead of u, v the pixel offsets are deprojected into a disk plane (sky angle, inclination),
+// r is the radius there and the coordinates are turned by t = winding T(r) (r / r_out)^alpha, T the tanh ramp between
+// r_in and r_out; Sigma_e is divided by cos(inclination).  psfmc_set_spiral_layout appends kSpiIn entries per Sersic
+// -- r_in, r_out, winding, alpha, inclination, sky angle as declared (angles in degrees where the layout's
+// sersic_degrees flag is set) -- BEHIND the Fourier entries (a context with spirals always carries the Fourier block,
+// zeros where a field has no modes); a per (field, Sersic) byte holds the flag (bit 0) and the degrees flag (bit 1).
+// The per-walker constants spar[w][k][kSpiPar] are formed by the SPI instantiation of k_general_split, in the thread
+// that moves the component's block: no launch is added.
 #pragma once
 #include "psfmc_device.h"
 #include "psfmc_integrated.h"
@@ -45,12 +55,26 @@ constexpr int kFouModeBits = (1 << kFouModes) - 1, kFouDegrees = 1 << kFouModes;
 // the Fourier entries behind the aux_len ones: aux[base + kFouPar k + 2 (m - 1)] = a_m, ... + 1 = phi_m of Sersic k
 __host__ __device__ inline int fourier_len(int n_sersic) { return kFouPar * n_sersic; }
 
+constexpr int kSpiIn = 6;            // r_in, r_out, winding, alpha, inclination, sky angle (PSFMC_SPIRAL_PARAMS)
+constexpr int kSpiPar = 8;           // cos, sin of the sky angle, 1 / cos(incl), k1, k0, alpha, log2 r_out, winding
+constexpr int kSpiFlag = 1, kSpiDegrees = 2;
+// the spiral entries behind the Fourier ones: aux[base + fourier_len + kSpiIn k + j] of Sersic k
+__host__ __device__ inline int spiral_len(int n_sersic) { return kSpiIn * n_sersic; }
+
 // skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
 // component, and with it the walker's likelihood, NaN)
+// SPI: the context has spirals (spar, smasks set, aux_spi the offset of the spiral entries in a walker's vector); the
+// thread of a flagged component also forms the spiral's constants
+//     cos(sky), sin(sky), 1 / cos(incl), k1 = 4 / (r_out - r_in), k0 = -2 (r_in + r_out) / (r_out - r_in)  (the ramp's
+//     argument is k1 r + k0), alpha, log2 r_out, the winding in radians
+// and divides Sigma_e / A(c) by cos(incl); outside the support (a value not finite, r_in < 0, r_out <= r_in,
+// alpha < 0, |incl| >= a right angle in its declared unit) Sigma_e becomes NaN and the walker is skipped like a bad
+// boxiness.  The SPI = false instantiation is the kernel as it was.
+template <bool SPI>
 __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __restrict__ skip,
                                 double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                                 const uint8_t* __restrict__ flags, int n_ps, int n_sersic, int n_psf, int n_psf_field,
-                                int n) {
+                                int n, double* __restrict__ spar, const uint8_t* __restrict__ smasks, int aux_spi) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * n_sersic) return;
     const int w = i / n_sersic, k = i - w * n_sersic;
@@ -64,9 +88,39 @@ __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __
     double* o = gpar + (size_t)i * kGenPar;
     const double c = aux[(size_t)w * aux_stride + 2 * n_sky + k];
     const double e = c + 2.0;
-    const bool bad = !(c > -2.0) || !(c < INFINITY);
+    bool bad = !(c > -2.0) || !(c < INFINITY);
     // 1 / A(c): the ellipse's area over the superellipse's
-    const double inv_a = 0.78539816339744830962 * exp(lgamma(1.0 + 2.0 / e) - 2.0 * lgamma(1.0 + 1.0 / e));
+    double inv_a = 0.78539816339744830962 * exp(lgamma(1.0 + 2.0 / e) - 2.0 * lgamma(1.0 + 1.0 / e));
+    if constexpr (SPI) {
+        const int sm = smasks[(idx / n_psf_field) * n_sersic + k];
+        if (sm & kSpiFlag) {
+            const double* a = aux + (size_t)w * aux_stride + aux_spi + kSpiIn * k;
+            const double r_in = a[0], r_out = a[1], alpha = a[3];
+            double wind = a[2], incl = a[4], sky = a[5];
+            const double quarter = (sm & kSpiDegrees) ? 90.0 : 1.57079632679489661923;
+            bool fin = true;
+            for (int j = 0; j < kSpiIn; ++j) fin = fin && fabs(a[j]) < INFINITY;     // (false for a NaN)
+            bad = bad || !fin || !(r_in >= 0.0) || !(r_out > r_in) || !(alpha >= 0.0) || !(fabs(incl) < quarter);
+            if (sm & kSpiDegrees) {
+                wind *= M_PI / 180.0;
+                incl *= M_PI / 180.0;
+                sky *= M_PI / 180.0;
+            }
+            double sn, cs;
+            sincos(sky, &sn, &cs);
+            const double ci = cos(incl), span = r_out - r_in;
+            double* sp = spar + (size_t)i * kSpiPar;
+            sp[0] = cs;
+            sp[1] = sn;
+            sp[2] = 1.0 / ci;
+            sp[3] = 4.0 / span;
+            sp[4] = -2.0 * (r_in + r_out) / span;
+            sp[5] = alpha;
+            sp[6] = log2(r_out);
+            sp[7] = wind;
+            inv_a /= ci;                                               // (incl = 0: a division by 1, exact)
+        }
+    }
     for (int j = 0; j < kPrepSersic - 1; ++j) o[j] = b[j];
     o[8] = bad ? __builtin_nan("") : b[8] * inv_a;
     o[9] = e;
@@ -189,11 +243,76 @@ __device__ __forceinline__ GenPar load_general(const double* __restrict__ g) {
 // FOURIER: the component has azimuthal modes -- t = rho^(2p) gains the factor (1 + eps)^(2p), folded into the third
 // log2 / exp2 pair at the price of one more fast_log2; cos t, sin t from a reciprocal square root of u^2 + v^2.  The
 // FOURIER = false instantiation is the function as it was before the modes existed.
-template <bool FOURIER>
-__device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y) {
+// SPIRAL: the component's coordinates are wound ahead of u, v (file header; `Sersic.spiral_image`); dx, dy of the
+// centroid term stay the pixel plane's.  The SPIRAL = false forms are the functions as they were.
+struct SpiPar { double cs, sn, icos, ek1, ek0, alpha, l2ro, wind, chk; };
+__device__ __forceinline__ SpiPar load_spiral(const double* __restrict__ sp) {
+    SpiPar S;
+    S.cs = sp[0]; S.sn = sp[1]; S.icos = sp[2];
+    // T = (1 + tanh z) / 2 = 1 / (1 + 2^(-2 log2(e) z)), z = k1 r + k0
+    S.ek1 = -2.0 * kIntegLog2e * sp[3];
+    S.ek0 = -2.0 * kIntegLog2e * sp[4];
+    S.alpha = sp[5]; S.l2ro = sp[6]; S.wind = sp[7];
+    // (a NaN among the constants reaches the pixel through general_pixel's chk, whatever the clamps do)
+    S.chk = ((S.cs + S.sn) + (S.icos + S.ek1)) + ((S.ek0 + S.alpha) + (S.l2ro + S.wind));
+    return S;
+}
+
+// sin and cos of t for the winding angle, |t| up to tens (thousands) of radians: t = n pi/2 + r by a two-constant
+// Cody-Waite reduction -- with fused multiply-adds the first step's error is one rounding of r, so r is good to
+// ~1e-16 + |n| 1.5e-33 -- and the fdlibm kernel polynomials on |r| <= pi/4 (below 1 ulp each).  t not finite: NaN.
+__device__ __forceinline__ void spiral_sincos(double t, double* sn, double* cs) {
+    const double n = __builtin_rint(t * 0.63661977236758134308);
+    double r = __builtin_fma(-n, 1.57079632679489655800e+00, t);
+    r = __builtin_fma(-n, 6.12323399573676603587e-17, r);
+    const double z = r * r;
+    double ps = 1.58969099521155010221e-10;
+    ps = __builtin_fma(ps, z, -2.50507602534068634195e-08);
+    ps = __builtin_fma(ps, z, 2.75573137070700676789e-06);
+    ps = __builtin_fma(ps, z, -1.98412698298579493134e-04);
+    ps = __builtin_fma(ps, z, 8.33333333332248946124e-03);
+    ps = __builtin_fma(ps, z, -1.66666666666666324348e-01);
+    const double s = __builtin_fma(r * z, ps, r);
+    double pc = -1.13596475577881948265e-11;
+    pc = __builtin_fma(pc, z, 2.08757232129817482790e-09);
+    pc = __builtin_fma(pc, z, -2.75573143513906633035e-07);
+    pc = __builtin_fma(pc, z, 2.48015872894767294178e-05);
+    pc = __builtin_fma(pc, z, -1.38888888888741095749e-03);
+    pc = __builtin_fma(pc, z, 4.16666666666666019037e-02);
+    const double c = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
+    const int q = (int)(n - 4.0 * __builtin_floor(0.25 * n));          // n mod 4 in 0 ... 3
+    const double a = (q & 1) ? c : s, b = (q & 1) ? s : c;
+    *sn = (q & 2) ? -a : a;
+    *cs = ((q + 1) & 2) ? -b : b;
+}
+
+template <bool FOURIER, bool SPIRAL = false>
+__device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y,
+                                                const SpiPar* SP = nullptr) {
     const double dx = x - G.s.x0, dy = y - G.s.y0;
-    const double u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
-    const double v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
+    double u, v, spi_chk = 0.0;
+    if constexpr (SPIRAL) {
+        const SpiPar& S = *SP;
+        const double X = __builtin_fma(S.cs, dx, S.sn * dy);
+        const double Y = __builtin_fma(S.cs, dy, -(S.sn * dx)) * S.icos;
+        const double r2 = __builtin_fma(X, X, Y * Y);
+        const bool pos = r2 > 0.0;
+        const double r = pos ? r2 * general_rsqrt(r2) : 0.0;
+        const double T = fast_rcp(1.0 + fast_exp2(__builtin_fma(S.ek1, r, S.ek0)));
+        double wt = S.wind * T;
+        if (S.alpha != 0.0)                                            // wave-uniform; (r / r_out)^0 = 1 at r = 0 too
+            wt *= pos ? fast_exp2(S.alpha * __builtin_fma(0.5, fast_log2(r2), -S.l2ro)) : 0.0;
+        double st, ct;
+        spiral_sincos(wt, &st, &ct);
+        const double Xr = __builtin_fma(ct, X, st * Y);
+        const double Yr = __builtin_fma(ct, Y, -(st * X));
+        u = __builtin_fma(G.s.m00, Xr, G.s.m01 * Yr);
+        v = __builtin_fma(G.s.m10, Xr, G.s.m11 * Yr);
+        spi_chk = S.chk;
+    } else {
+        u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
+        v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
+    }
     const double au = fabs(u), av = fabs(v);
     // |u| = 0 gives the term exactly 0 (not log2(0) e)
     const double pu = au > 0.0 ? fast_exp2(G.e * fast_log2(au)) : 0.0;
@@ -213,7 +332,8 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
     const double sb = G.s.sbeff * fast_exp2_floor(__builtin_fma(G.nkl, t, -G.nkl));
     const double gt = G.gk * t;
     const double val = sb * __builtin_fma(gt * gt, fast_rcp(__builtin_fma(dx, dx, dy * dy)), 1.0);
-    const double chk = (u + v) + (G.nkl + G.pe2);      // (the comparisons and the exponentials' clamps swallow a NaN)
+    double chk = (u + v) + (G.nkl + G.pe2);            // (the comparisons and the exponentials' clamps swallow a NaN)
+    if constexpr (SPIRAL) chk += spi_chk;
     return chk == chk ? val : chk;
 }
 
@@ -223,13 +343,16 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
 // readers clip to the same ly, lx from wrap_tab and never read beyond it.
 // FOU: the context has Fourier modes (fpar, fmasks set); the FOU = false instantiation is the kernel as it was before
 // the modes existed -- its registers and occupancy are not paid for by contexts without modes.
-template <bool FOU>
+// SPI: the context has spirals (spar, smasks set); a component with the flag runs the SPIRAL pixel function, with or
+// without modes.  The SPI = false instantiations are the kernels as they were.
+template <bool FOU, bool SPI = false>
 __global__ void __launch_bounds__(256)
 k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                const uint8_t* __restrict__ sky_flags, const uint8_t* __restrict__ flags, int n_sersic, int n_psf,
                int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
-               int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks) {
+               int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
+               const double* __restrict__ spar = nullptr, const uint8_t* __restrict__ smasks = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -264,6 +387,7 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
         FouPar F{};
         // a component without modes runs the loop it always ran
         const int modes = FOU ? fmasks[field * n_sersic + k] & kFouModeBits : 0;         // wave-uniform
+        const bool wound = SPI ? (smasks[field * n_sersic + k] & kSpiFlag) != 0 : false; // wave-uniform
         if (FOU && modes) {
             const double* f = fpar + ((size_t)w * n_sersic + k) * kFouPar;
 #pragma unroll
@@ -272,6 +396,23 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
                 F.b[m] = f[2 * m + 1];
             }
             F.top = 32 - __builtin_clz((unsigned)modes);                                 // the highest mode present
+        }
+        if (SPI && wound) {
+            const SpiPar S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);
+            if (FOU && modes) {
+                for (int x0 = 0; x0 < xn; x0 += 64) {
+                    const int ix = x0 + lane;
+                    if (ix < xn)
+                        out[ix] = (first ? base(ix) : out[ix]) + general_pixel<true, true>(G, F, (double)ix, y, &S);
+                }
+            } else {
+                for (int x0 = 0; x0 < xn; x0 += 64) {
+                    const int ix = x0 + lane;
+                    if (ix < xn)
+                        out[ix] = (first ? base(ix) : out[ix]) + general_pixel<false, true>(G, F, (double)ix, y, &S);
+                }
+            }
+        } else if (FOU && modes) {
             for (int x0 = 0; x0 < xn; x0 += 64) {
                 const int ix = x0 + lane;
                 if (ix < xn) out[ix] = (first ? base(ix) : out[ix]) + general_pixel<true>(G, F, (double)ix, y);

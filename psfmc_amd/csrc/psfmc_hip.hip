@@ -287,6 +287,13 @@ struct psfmc_ctx {
     std::vector<uint8_t> fou_masks;      // [n_fields][n_sersic] mode mask (bit m - 1), bit 6: the phases are in degrees
     uint8_t* d_fou_masks = nullptr;
     double* d_fou_par = nullptr;         // [max_walkers][n_sersic][kFouPar]
+    // spiral arms (psfmc_set_spiral_layout, psfmc_general.h); nothing is allocated and no kernel changes until a field
+    // registers one.  With the first registration aux_stride grows to aux_base + 18 n_sersic: the spiral entries sit
+    // behind the Fourier block, which such a context always carries (zeros where no field has modes)
+    bool spi_any = false;
+    std::vector<uint8_t> spi_masks;      // [n_fields][n_sersic] bit 0: the component has a spiral, bit 1: angles in degrees
+    uint8_t* d_spi_masks = nullptr;
+    double* d_spi_par = nullptr;         // [max_walkers][n_sersic][kSpiPar]
 };
 
 // the extra image of the walker whose record `prep` points at (nullptr: none to add)
@@ -1399,7 +1406,8 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
-                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par};
+                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
+                    c->d_spi_par};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (void* p : c->aux_blobs)
@@ -1699,6 +1707,12 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 // and tilted skies (psfmc_general.h).  After every kernel that writes prep records, same stream, the images are
 // formed and the components' blocks made neutral for the rasterisers.  The integrated profile's kernels WRITE the
 // images, the general kernel then ADDS to them; alone it writes.
+// k_general_rows as the context needs it: a context without modes and without spirals runs the kernel it always ran
+static decltype(&k_general_rows<false, false>) general_rows_kernel(const psfmc_ctx* c) {
+    if (c->spi_any) return c->fou_any ? k_general_rows<true, true> : k_general_rows<false, true>;
+    return c->fou_any ? k_general_rows<true, false> : k_general_rows<false, false>;
+}
+
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
     if ((!c->integ_any && !c->gen_any) || n <= 0) return;
     double* prep = c->d_prep + (size_t)w_off * c->plen;
@@ -1711,21 +1725,26 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
         double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
         const double* aux = c->d_aux + (size_t)w_off * c->aux_stride;
         const uint8_t* sky_flags = c->d_gen_flags + (size_t)c->n_fields * c->n_sersic;
+        // (a context with spirals: the same launch also forms the spirals' per-walker constants)
+        double* spar = c->spi_any ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
+        const uint8_t* smasks = c->spi_any ? c->d_spi_masks : nullptr;
         if (items > 0)
-            hipLaunchKernelGGL(k_general_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen,
+            hipLaunchKernelGGL(c->spi_any ? k_general_split<true> : k_general_split<false>, dim3((items + 255) / 256),
+                               dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
-                               c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
+                               c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, spar, smasks,
+                               c->aux_base + fourier_len(c->n_sersic));
         if (c->fou_any && items > 0)
             hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar,
                                aux, c->aux_stride, c->aux_base, c->d_fou_masks, c->n_sersic, c->n_psf, c->n_psf_field,
                                n);
         if (!c->integ_any) {
-            hipLaunchKernelGGL(c->fou_any ? k_general_rows<true> : k_general_rows<false>, dim3((c->ny + 3) / 4, n),
+            hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                                dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
                                c->d_gen_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
                                c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                               c->fou_any ? c->d_fou_masks : nullptr);
+                               c->fou_any ? c->d_fou_masks : nullptr, spar, smasks);
             return;
         }
     }
@@ -1737,14 +1756,16 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     if (c->gen_any)
-        hipLaunchKernelGGL(c->fou_any ? k_general_rows<true> : k_general_rows<false>, dim3((c->ny + 3) / 4, n),
+        hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                            dim3(256), 0, st, prep, c->plen, skip,
                            c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
                            c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
                            c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, c->d_gen_flags, c->n_sersic, c->n_psf,
                            c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1,
                            c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                           c->fou_any ? c->d_fou_masks : nullptr);
+                           c->fou_any ? c->d_fou_masks : nullptr,
+                           c->spi_any ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr,
+                           c->spi_any ? c->d_spi_masks : nullptr);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -2000,6 +2021,18 @@ static int drop_fourier_masks(psfmc_ctx* c, int field) {
     return PSFMC_OK;
 }
 
+// ... and so do its spirals (psfmc_set_spiral_layout)
+static int drop_spiral_masks(psfmc_ctx* c, int field) {
+    if (c->spi_masks.empty()) return PSFMC_OK;
+    for (int k = 0; k < c->n_sersic; ++k) c->spi_masks[(size_t)field * c->n_sersic + k] = 0;
+    bool any = false;
+    for (uint8_t m : c->spi_masks) any = any || (m & kSpiFlag);
+    if (c->d_spi_masks)
+        HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), c->spi_masks.size(), hipMemcpyHostToDevice));
+    c->spi_any = any;
+    return PSFMC_OK;
+}
+
 static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, const int* slot_col,
                            const double* slot_const, const int* ps_method, const int* sersic_degrees,
                            double mag_zeropoint, const int* family, const double* p0,
@@ -2063,8 +2096,9 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
     // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again)
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0;
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
     RC_TRY(drop_fourier_masks(c, field));
+    RC_TRY(drop_spiral_masks(c, field));
     if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
     if (!c->gen_flags.empty()) {
         const size_t n_ser = c->n_sersic, n_sk = c->aux_n_sky;
@@ -2203,8 +2237,9 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     for (uint8_t f : c->gen_flags) any = any || f;
     if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
     if (c->aux_blobs[field]) { (void)hipFree(c->aux_blobs[field]); c->aux_blobs[field] = nullptr; }
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0;
+    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
     RC_TRY(drop_fourier_masks(c, field));                // (the field's modes are registered after its aux layout)
+    RC_TRY(drop_spiral_masks(c, field));                 // (and so is its spiral)
     if (n_aux) {
         // aux_const first (8-byte units), then aux_col
         std::vector<unsigned char> blob((size_t)n_aux * (sizeof(double) + sizeof(int)));
@@ -2258,7 +2293,8 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
     if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
     ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    const int n_base = L.n_aux - L.n_fou, n_fou = fourier_len(n_sersic);
+    // (a field's spiral is registered after its modes: a Fourier layout drops it with the entries it had)
+    const int n_base = L.n_aux - L.n_fou - L.n_spi, n_fou = fourier_len(n_sersic);
     bool any_here = false;
     for (int k = 0; k < n_sersic; ++k) {
         if (mode_mask[k] & ~kFouModeBits)
@@ -2283,7 +2319,9 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
     c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
-    if (!any_here && c->fou_masks.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
+    if (!any_here && c->fou_masks.empty() && !L.n_spi) return PSFMC_OK;    // (nothing registered, nothing to remove)
+    RC_TRY(drop_spiral_masks(c, field));
+    L.n_spi = 0;
     if (n_base > 0) {
         // the field's table again: its aux entries as they are, then (with modes) the Fourier entries
         std::vector<double> cst((size_t)n_base + (any_here ? n_fou : 0));
@@ -2319,7 +2357,7 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     if (any_here && !c->d_fou_masks) {
         // the first modes of the context: longer auxiliary vectors (the aux entries keep their places), the
         // components' mode blocks and the masks
-        const int stride = c->aux_base + n_fou;
+        const int stride = c->aux_stride > c->aux_base + n_fou ? c->aux_stride : c->aux_base + n_fou;
         double* longer = nullptr;
         HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
         HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
@@ -2335,6 +2373,96 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     if (c->d_fou_masks)
         HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), c->fou_masks.size(), hipMemcpyHostToDevice));
     c->fou_any = any;
+    c->aux_rows_w = -1;
+    c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
+    return PSFMC_OK;
+}
+
+static_assert(kSpiIn == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
+extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, const int* flags, const int* col,
+                                       const double* konst) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    if (n_sersic && (!flags || !col || !konst)) return fail(PSFMC_EINVAL, "NULL spiral array");
+    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const int n_keep = L.n_aux - L.n_spi, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
+    bool any_here = false;
+    for (int k = 0; k < n_sersic; ++k) any_here = any_here || flags[k];
+    if (any_here && n_keep <= 0)
+        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
+                    "a spiral flagged general) before psfmc_set_spiral_layout", field);
+    for (int k = 0; k < n_sersic; ++k) {
+        if (!flags[k]) continue;
+        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: spiral and integrate exclude each other",
+                        k, field);
+        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d has a spiral but is not flagged general in the field's aux "
+                        "layout", k, field);
+    }
+    for (int j = 0; any_here && j < n_spi; ++j)
+        if (col[j] < -1 || col[j] >= L.n_params)
+            return fail(PSFMC_EINVAL, "spiral value %d refers to column %d of %d", j, col[j], L.n_params);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
+    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
+    if (!any_here && c->spi_masks.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
+    if (n_keep > 0) {
+        // the field's table again: its aux and Fourier entries as they are -- a field without modes gets the empty
+        // Fourier block, so that a table index is the entry's place in the walker's vector -- then the spiral entries
+        const int n_pad = any_here && !L.n_fou ? n_fou : 0;
+        std::vector<double> cst((size_t)n_keep + n_pad + (any_here ? n_spi : 0), 0.0);
+        std::vector<int> cl(cst.size(), -1);
+        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_keep * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_keep * sizeof(int), hipMemcpyDeviceToHost));
+        for (int j = 0; any_here && j < n_spi; ++j) {
+            cst[(size_t)n_keep + n_pad + j] = konst[j];
+            cl[(size_t)n_keep + n_pad + j] = col[j];
+        }
+        const size_t n_all = cst.size();
+        std::vector<unsigned char> blob(n_all * (sizeof(double) + sizeof(int)));
+        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
+        memcpy(blob.data() + n_all * sizeof(double), cl.data(), n_all * sizeof(int));
+        void* fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, blob.size()));
+        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        (void)hipFree(c->aux_blobs[field]);
+        c->aux_blobs[field] = fresh;
+        L.n_aux = (int)n_all;
+        L.n_fou += n_pad;
+        L.n_spi = any_here ? n_spi : 0;
+        L.aux_const = static_cast<const double*>(fresh);
+        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
+        if (c->n_fields > 1 && c->d_field_layouts)
+            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    }
+    if (c->spi_masks.empty()) c->spi_masks.assign((size_t)c->n_fields * n_sersic, 0);
+    std::vector<int> deg(n_sersic > 0 ? n_sersic : 1, 0);
+    if (any_here) HIP_TRY(hipMemcpy(deg.data(), L.sersic_deg, (size_t)n_sersic * sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n_sersic; ++k)
+        c->spi_masks[(size_t)field * n_sersic + k] = (uint8_t)(flags[k] ? (kSpiFlag | (deg[k] ? kSpiDegrees : 0)) : 0);
+    if (any_here && !c->d_spi_masks) {
+        // the first spiral of the context: longer auxiliary vectors (the aux and Fourier entries keep their places),
+        // the components' constants and the masks
+        const int stride = c->aux_base + n_fou + n_spi;
+        double* longer = nullptr;
+        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
+        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
+        (void)hipFree(c->d_aux);
+        c->d_aux = longer;
+        c->aux_stride = stride;
+        HIP_TRY(hipMalloc(&c->d_spi_masks, c->spi_masks.size()));
+        HIP_TRY(hipMalloc(&c->d_spi_par, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
+        HIP_TRY(hipMemset(c->d_spi_par, 0, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
+    }
+    bool any = false;
+    for (uint8_t m : c->spi_masks) any = any || (m & kSpiFlag);
+    if (c->d_spi_masks)
+        HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), c->spi_masks.size(), hipMemcpyHostToDevice));
+    c->spi_any = any;
     c->aux_rows_w = -1;
     c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
     return PSFMC_OK;
@@ -3700,6 +3828,13 @@ extern "C" int psfmc_group_set_fourier_layout(psfmc_group* g, int n_sersic, cons
                                               const double* konst) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_fourier_layout(c, 0, n_sersic, mode_mask, col, konst));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_spiral_layout(psfmc_group* g, int n_sersic, const int* flags, const int* col,
+                                             const double* konst) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_spiral_layout(c, 0, n_sersic, flags, col, konst));
     return PSFMC_OK;
 }
 

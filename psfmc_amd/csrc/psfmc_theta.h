@@ -50,6 +50,10 @@ struct ThetaLayout {
     // azimuthal Fourier modes (psfmc_set_fourier_layout): the LAST n_fou = 12 n_sersic of the n_aux entries, per
     // Sersic and mode 1 ... 6 an amplitude and a phase; 0: none (every layout before the call)
     int n_fou;
+    // spiral arms (psfmc_set_spiral_layout): the LAST n_spi = 6 n_sersic of the n_aux entries, behind the Fourier
+    // ones (n_spi > 0 implies n_fou > 0: a field with a spiral carries the Fourier block, empty without modes); per
+    // Sersic r_in, r_out, winding, alpha, inclination, sky angle; 0: none (every layout before the call)
+    int n_spi;
 };
 
 // where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
@@ -622,7 +626,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
                 // reff_b > reff is)
                 double* a = ax.aux + (size_t)w * ax.stride;
-                const int n_base = G.n_aux - G.n_fou;
+                const int n_base = G.n_aux - G.n_fou - G.n_spi;
                 for (int j = 0; j < n_base; ++j) {
                     const int col = G.aux_col[j];
                     const double v = col >= 0 ? th[col] : G.aux_const[j];
@@ -632,7 +636,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 if (G.n_fou > 0) {                                          // wave-uniform
                     // the Fourier entries, per Sersic 6 x (amplitude, phase); a value that is not finite or
                     // sum |a_m| >= 1 (in mode order) is outside the support
-                    for (int j0 = n_base; j0 < G.n_aux; j0 += 12) {
+                    for (int j0 = n_base; j0 < n_base + G.n_fou; j0 += 12) {
                         double sum_abs = 0.0;
                         bool fin = true;
                         for (int j = j0; j < j0 + 12; ++j) {
@@ -643,6 +647,26 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                             if (!((j - j0) & 1)) sum_abs += fabs(v);
                         }
                         if (!fin || !(sum_abs < 1.0)) lp = -INFINITY;
+                    }
+                }
+                if (G.n_spi > 0) {                                          // wave-uniform
+                    // the spiral entries, per Sersic r_in, r_out, winding, alpha, inclination, sky angle; outside
+                    // the support: a value not finite, r_in < 0, r_out <= r_in, alpha < 0, |inclination| >= a
+                    // right angle in its declared unit
+                    int k = 0;
+                    for (int j0 = G.n_aux - G.n_spi; j0 < G.n_aux; j0 += 6, ++k) {
+                        double v6[6];
+                        bool fin = true;
+                        for (int j = 0; j < 6; ++j) {
+                            const int col = G.aux_col[j0 + j];
+                            const double v = col >= 0 ? th[col] : G.aux_const[j0 + j];
+                            a[j0 + j] = v;
+                            v6[j] = v;
+                            fin = fin && fabs(v) < INFINITY;
+                        }
+                        const double quarter = L.sersic_deg[k] ? 90.0 : 1.57079632679489661923;
+                        if (!fin || !(v6[0] >= 0.0) || !(v6[1] > v6[0]) || !(v6[3] >= 0.0) || !(fabs(v6[4]) < quarter))
+                            lp = -INFINITY;
                     }
                 }
             }

@@ -24,7 +24,8 @@ _COMMENTS = {'MCITER': 'number of retained samples',
              'PSFIMG': 'PSF image of maximum posterior model'}
 _INTEGRATE_COMMENT = 'pixel-integrated Sersic (not the reference profile)'
 _FLAG_COMMENTS = {'SERINT': _INTEGRATE_COMMENT, 'SERBOX': 'Sersic with boxy/disky isophotes (boxiness)',
-                  'SKYSLP': 'tilted sky (slope)', 'SERFOU': 'Sersic with azimuthal Fourier modes (fourier)'}
+                  'SKYSLP': 'tilted sky (slope)', 'SERFOU': 'Sersic with azimuthal Fourier modes (fourier)',
+                  'SERSPI': 'Sersic with spiral arms by coordinate rotation (spiral)'}
 
 
 class Table(object):

@@ -267,6 +267,10 @@ def load_library():
     lib.psfmc_set_fourier_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_fourier_layout.restype = ci
     lib.psfmc_group_set_fourier_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
+    lib.psfmc_set_spiral_layout.restype = ci
+    lib.psfmc_set_spiral_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
+    lib.psfmc_group_set_spiral_layout.restype = ci
+    lib.psfmc_group_set_spiral_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -332,6 +336,20 @@ def _fourier_layout_args(mode_masks, col, const):
             2 * FOURIER_MODES, len(col), len(mask)))
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     return (mask, col, const), (len(mask), ipt(mask), ipt(col), _dp(const))
+
+
+SPIRAL_PARAMS = 6          # PSFMC_SPIRAL_PARAMS: r_in, r_out, winding, alpha, inclination, sky angle
+
+
+def _spiral_layout_args(flags, col, const):
+    """The arrays of psfmc_set_spiral_layout (kept alive by the caller's tuple) and their ctypes pointers."""
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
+    flags, col, const = i32(np.asarray(flags, dtype=bool)), i32(col), _f64(const).ravel()
+    if len(col) != len(const) or len(col) != SPIRAL_PARAMS * len(flags):
+        raise ValueError('spiral layout: {} entries per Sersic, got {} for {}'.format(
+            SPIRAL_PARAMS, len(col), len(flags)))
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    return (flags, col, const), (len(flags), ipt(flags), ipt(col), _dp(const))
 
 
 def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
@@ -554,6 +572,13 @@ class Context(object):
         or -1 and a constant.  A context that never gets the call is what it was without it."""
         keep, args = _fourier_layout_args(mode_masks, col, const)
         self._check(self._lib.psfmc_set_fourier_layout(self._ctx, 0, *args))
+
+    def set_spiral_layout(self, flags, col, const):
+        """Spiral arms (psfmc_set_spiral_layout; after `set_aux_layout` and `set_fourier_layout`): per Sersic a flag
+        and six entries -- r_in, r_out, winding, alpha, inclination, sky angle; column of theta or -1 and a
+        constant.  A context that never gets the call is what it was without it."""
+        keep, args = _spiral_layout_args(flags, col, const)
+        self._check(self._lib.psfmc_set_spiral_layout(self._ctx, 0, *args))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -893,6 +918,13 @@ class FieldSetContext(object):
                 keep, args = _fourier_layout_args(mode_masks, col, const)
                 owner._check(owner._lib.psfmc_set_fourier_layout(owner._ctx, int(field), *args))
                 owner._aux_fourier = len(keep[1])
+
+            def set_spiral_layout(self, flags, col, const):
+                keep, args = _spiral_layout_args(flags, col, const)
+                owner._check(owner._lib.psfmc_set_spiral_layout(owner._ctx, int(field), *args))
+                # (a context with spirals carries the Fourier block, empty where no field has modes)
+                owner._aux_fourier = 2 * FOURIER_MODES * len(keep[0])
+                owner._aux_spiral = len(keep[1])
         return _Proxy()
 
     @staticmethod
@@ -1039,10 +1071,10 @@ class FieldSetContext(object):
         return FieldView(self, field, columns)
 
     def _aux_width(self):
-        """Values per walker of the context's auxiliary vectors once a field registered Fourier modes (its fields'
-        rows without modes are padded to it), else None."""
+        """Values per walker of the context's auxiliary vectors once a field registered Fourier modes or a spiral
+        (its fields' rows without them are padded to it), else None."""
         fou = getattr(self, '_aux_fourier', 0)
-        return getattr(self, '_aux_base', 0) + fou if fou else None
+        return getattr(self, '_aux_base', 0) + fou + getattr(self, '_aux_spiral', 0) if fou else None
 
     def _field_aux(self, aux, n_w):
         """The auxiliary rows of a row-based call of one field: the field's own, or -- for a field WITHOUT the keywords
@@ -1279,9 +1311,14 @@ class ContextGroup(object):
         keep, args = _fourier_layout_args(mode_masks, col, const)
         self._check(self._lib.psfmc_group_set_fourier_layout(self._grp, *args))
 
+    def set_spiral_layout(self, flags, col, const):
+        """`Context.set_spiral_layout` on every device of the group."""
+        keep, args = _spiral_layout_args(flags, col, const)
+        self._check(self._lib.psfmc_group_set_spiral_layout(self._grp, *args))
+
     def loglike(self, rows, skip=None, aux=None):
         if aux is not None:
-            raise NotImplementedError('derived rows of a model with a Sky `slope` or a Sersic `boxiness` are not '
+            raise NotImplementedError('derived rows of a model with a Sky `slope` or a Sersic `boxiness`, `fourier` or `spiral` are not '
                                       'split over a ContextGroup: use logpost_theta (raw vectors)')
         rows = _f64(rows)
         if rows.ndim != 2 or rows.shape[1] != self.row_len:

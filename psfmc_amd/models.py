@@ -31,6 +31,9 @@ _DEVICE_FAMILIES = {
     'cauchy': (10, 0), 'halfcauchy': (11, 0), 'logistic': (12, 0), 't': (13, 1), 'beta': (14, 2),
     'reciprocal': (15, 2), 'loguniform': (15, 2), 'weibull_max': (16, 1), 'invgamma': (17, 1),
 }
+# spiral entries (r_in, r_out, winding, alpha, inclination, sky angle) of a Sersic component without the keyword:
+# inside the support, never read
+_SPIRAL_ABSENT = (0.0, 1.0, 0.0, 0.0, 0.0, 0.0)
 _FIRST_NEW_FAMILY = 5           # psfmc_set_layout takes families 0-4; the rest go through psfmc_set_priors
 
 
@@ -252,15 +255,29 @@ class MultiComponentModel(object):
                     slot_col += [-1, -1]; slot_const += [0.0, 0.0]
         fou_col, fou_const = slot_col[n_before:], slot_const[n_before:]
         slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
+        # spiral arms (Sersic `spiral`): per Sersic r_in, r_out, winding, alpha, inclination, sky angle as declared; a
+        # component without the keyword gets constants inside the support that are never read; registered after the
+        # aux and Fourier layouts, and only by a model with the keyword
+        for c in self._sersic:
+            if c.has_spiral:
+                for attr in Sersic.SPIRAL_ATTRS:
+                    add(c, attr)
+            else:
+                slot_col += [-1] * 6; slot_const += list(_SPIRAL_ABSENT)
+        spi_col, spi_const = slot_col[n_before:], slot_const[n_before:]
+        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
         if columns is not None:
             aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
             fou_col = [int(columns[c]) if c >= 0 else -1 for c in fou_col]
+            spi_col = [int(columns[c]) if c >= 0 else -1 for c in spi_col]
 
         def register_aux():
             if self.has_aux:
                 eng.set_aux_layout(aux_col, aux_const, self.sky_slope_flags, self.sersic_general_flags)
             if any(self.sersic_fourier_masks):
                 eng.set_fourier_layout(self.sersic_fourier_masks, fou_col, fou_const)
+            if any(self.sersic_spiral_flags):
+                eng.set_spiral_layout(self.sersic_spiral_flags, spi_col, spi_const)
         if columns is not None:
             slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
             zero = np.zeros(n_params)
@@ -300,8 +317,13 @@ class MultiComponentModel(object):
         return [sum(1 << (m - 1) for m in getattr(c, 'fourier_modes', ())) for c in self._sersic]
 
     @property
+    def sersic_spiral_flags(self):
+        """[n_sersic] which Sersic components (model-file order) were given a `spiral`."""
+        return [bool(getattr(c, 'has_spiral', False)) for c in self._sersic]
+
+    @property
     def has_aux(self):
-        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness` or `fourier`)?"""
+        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier` or `spiral`)?"""
         return any(self.sky_slope_flags) or any(self.sersic_general_flags)
 
     def aux_rows(self, theta):
@@ -309,7 +331,9 @@ class MultiComponentModel(object):
         psfmc_set_aux_layout: per Sky its slope, per Sersic its boxiness; zeros for components without the
         keyword), or None for a model without the keywords: the companion of `derived_rows`.  A model with Fourier
         modes appends psfmc_set_fourier_layout's 12 n_sersic entries: per Sersic and mode 1 ... 6 the amplitude and
-        the phase as declared (zeros for absent modes)."""
+        the phase as declared (zeros for absent modes).  A model with a `spiral` carries those 12 n_sersic entries
+        (zeros without modes) and behind them psfmc_set_spiral_layout's 6 n_sersic: per Sersic r_in, r_out, winding,
+        alpha, inclination and sky angle as declared (constants inside the support for a component without it)."""
         if not self.has_aux:
             return None
         theta = self._theta(theta)
@@ -324,13 +348,19 @@ class MultiComponentModel(object):
             if isinstance(c, Sersic):
                 cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
-        if any(self.sersic_fourier_masks):
+        if any(self.sersic_fourier_masks) or any(self.sersic_spiral_flags):
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
                     vals = c.values_batch(theta[:, s]) if c.fourier_modes else {}
                     for m in Sersic.FOURIER_MODES:
                         for key in ('f%d_amp' % m, 'f%d_phase' % m):
                             cols.append(np.reshape(vals[key], (n_w,)) if m in c.fourier_modes else np.zeros(n_w))
+        if any(self.sersic_spiral_flags):
+            for c, s in zip(self.components, self._spans):
+                if isinstance(c, Sersic):
+                    vals = c.values_batch(theta[:, s]) if c.has_spiral else {}
+                    for attr, absent in zip(Sersic.SPIRAL_ATTRS, _SPIRAL_ABSENT):
+                        cols.append(np.reshape(vals[attr], (n_w,)) if c.has_spiral else np.full(n_w, absent))
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
     @staticmethod

@@ -4,7 +4,9 @@ keywords, vectors resident on the device (psfmc_eval_theta_device, what bench.py
 (the headline shape) and at 128^2 with 22 walkers.  One JSON line per configuration, a table at the end.
 --fourier: the cost of the azimuthal modes instead -- Sky + PS + one Sersic with a free boxiness and two free modes
 (`fourier={1: ..., 3: ...}`) against the same model with the boxiness only.
-Usage: python tools/time_general.py [--fourier] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+--spiral: the cost of the spiral arms -- the same model with a free boxiness and a free spiral (all six values)
+against the boxiness only.
+Usage: python tools/time_general.py [--fourier | --spiral] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
 import argparse
 import json
 import os
@@ -43,14 +45,20 @@ FOURIER = (', fourier={1: (Uniform(loc=-0.4, scale=0.8), Uniform(loc=-180, scale
            '3: (Uniform(loc=-0.4, scale=0.8), Uniform(loc=-180, scale=360))}')
 
 
-def build_fourier(side, directory, max_walkers, modes):
-    """Sky + PS + one Sersic with a free boxiness, and with `modes` two free Fourier modes beside it."""
+SPIRAL = (", spiral={'r_in': Uniform(loc=0, scale=4), 'r_out': Uniform(loc=5, scale=15), "
+          "'winding': Uniform(loc=-400, scale=800), 'alpha': Uniform(loc=0, scale=1), "
+          "'inclination': Uniform(loc=0, scale=70), 'sky_angle': Uniform(loc=-90, scale=180)}")
+
+
+def build_fourier(side, directory, max_walkers, modes, extra=FOURIER):
+    """Sky + PS + one Sersic with a free boxiness, and with `modes` the `extra` keyword (two free Fourier modes, or
+    the free spiral) beside it."""
     fld = synth_field.make_field(side, n_sersic=1, seed=0)
     for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
         fits_io.write_image(os.path.join(directory, name), fld[key])
     text = synth_field.model_file_text(side, 1).replace('PointSource(', SKY[0] + '\nPointSource(', 1)
     text = text.replace('angle_degrees=True)', 'angle_degrees=True, boxiness=Uniform(loc=-1, scale=2)%s)'
-                        % (FOURIER if modes else ''))
+                        % (extra if modes else ''))
     path = os.path.join(directory, 'model_f%d.py' % modes)
     with open(path, 'w') as f:
         f.write(text)
@@ -85,18 +93,31 @@ def main():
     ap.add_argument('--seconds', type=float, default=1.0)
     ap.add_argument('--out', default=None)
     ap.add_argument('--fourier', action='store_true', help='boxiness + two free modes against boxiness only')
+    ap.add_argument('--spiral', action='store_true', help='boxiness + a free spiral against boxiness only')
     args = ap.parse_args()
+    if args.fourier and args.spiral:
+        ap.error('--fourier and --spiral exclude each other')
     rows = []
     for shape in args.shapes:
         side, n_w = (int(v) for v in shape.split(':'))
         with tempfile.TemporaryDirectory() as tmp:
             rates = {}
             for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
-                model, fld = (build_fourier if args.fourier else build)(side, tmp, n_w, general)
+                if args.spiral:
+                    model, fld = build_fourier(side, tmp, n_w, general, SPIRAL)
+                else:
+                    model, fld = (build_fourier if args.fourier else build)(side, tmp, n_w, general)
                 theta = synth_field.draw_walkers(side, 1, n_w, seed=2, near_truth=fld['truth'])
                 rng = np.random.RandomState(3)
                 theta = np.hstack([rng.normal(size=(n_w, 1)) * 1e-3, theta])            # the sky level
-                if args.fourier:                                   # the boxiness, then (a_1, phi_1, a_3, phi_3)
+                if args.spiral:                # the boxiness; alpha, incl, r_in, r_out, sky, wind behind reff_b
+                    theta = np.insert(theta, [5], rng.uniform(-0.5, 0.5, (n_w, 1)), axis=1)
+                    if general:
+                        theta = np.insert(theta, [10] * 6, np.c_[rng.uniform(0.1, 0.9, n_w), rng.uniform(5, 60, n_w),
+                                                                 rng.uniform(0.5, 3.5, n_w), rng.uniform(6, 19, n_w),
+                                                                 rng.uniform(-80, 80, n_w), rng.uniform(-350, 350, n_w)],
+                                          axis=1)
+                elif args.fourier:                                 # the boxiness, then (a_1, phi_1, a_3, phi_3)
                     theta = np.insert(theta, [5], rng.uniform(-0.5, 0.5, (n_w, 1)), axis=1)
                     if general:
                         theta = np.insert(theta, [6, 6, 6, 6], np.c_[rng.uniform(-0.3, 0.3, n_w), rng.uniform(-180, 180, n_w),
@@ -112,7 +133,8 @@ def main():
                        general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    lines = ['side     W   default evals/s     general evals/s  ratio' if not args.fourier else
+    lines = ['side     W  boxiness evals/s box + spiral evals/s  ratio' if args.spiral else
+             'side     W   default evals/s     general evals/s  ratio' if not args.fourier else
              'side     W  boxiness evals/s  box + modes evals/s  ratio']
     for r in rows:
         lines.append('%4d %5d %16.0f %19.0f %6.3f' % (r['side'], r['walkers'], r['default_evals_per_s'],
