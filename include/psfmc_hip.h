@@ -289,6 +289,38 @@ int psfmc_set_fourier_layout(psfmc_ctx* ctx, int field, int n_sersic, const int*
 #define PSFMC_SPIRAL_PARAMS 6
 int psfmc_set_spiral_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* flags, const int* col,
                             const double* konst);
+/*
+ * Radial laws other than the Sersic law on general components (the Moffat and Ferrer component types of GALFIT; not
+ * the reference's).  Definition: psfmc_amd/ModelComponents/Sersic.py Sersic.radial_image; kernels:
+ * csrc/psfmc_general.h.  kinds [n_sersic]: per Sersic slot (model-file order) 0 the Sersic law, 1 Moffat, 2 Ferrer;
+ * col / konst [n_sersic][PSFMC_RADIAL_PARAMS] have the meaning of psfmc_set_layout's slot_col / slot_const, per slot
+ * (beta, unused) of a Moffat or (alpha, beta) of a Ferrer.  A slot of kind 0 has entries that are never read.  A slot
+ * with a law has index 1 in the field's layout and the law's two radii -- the full widths at half maximum of a
+ * Moffat, the truncation radii of a Ferrer -- in the places of reff and reff_b; mag stays the total magnitude.  It
+ * is rendered as a general component (boxiness, modes and spiral included) with
+ *     Moffat  Sigma_0 (1 + g rho^2)^-beta, g = 4 (2^(1/beta) - 1), Sigma_0 = F g (beta - 1) / (pi r_a r_b N)
+ *     Ferrer  Sigma_0 (1 - rho^(2 - beta))^alpha inside rho = 1 and 0 outside,
+ *             Sigma_0 = F / (pi r_a r_b N (2/k) B(2/k, alpha + 1)), k = 2 - beta
+ * (N = A(c) Q cos(inclination)) in place of the Sersic law and its centroid term: the value is the law at the pixel
+ * centre, Sigma_0 where the centre is a pixel centre.  The call APPENDS these 2 n_sersic entries to the field's
+ * auxiliary table BEHIND everything it holds.  A context with laws ALWAYS carries the Fourier block and the spiral
+ * block: a field without modes gets an empty Fourier block, a field without a spiral entries inside the spiral's
+ * support that are never read (nothing more is launched for either), so that from the first such call on every
+ * walker's auxiliary vector of the context -- psfmc_set_aux_rows' rows included -- has 2 n_sky + 21 n_sersic doubles,
+ * the laws' entries of Sersic k at 2 n_sky + 19 n_sersic + 2 k, the entries of a field without laws unused.  A
+ * Moffat's beta not finite or <= 1, a Ferrer's alpha or beta not finite, alpha < 0 or beta >= 2 gives log-posterior
+ * -inf (NaN through a row-based call without writable skip flags).  Call after the field's psfmc_set_aux_layout,
+ * which must flag the slots that have a law as general, after its psfmc_set_fourier_layout and
+ * psfmc_set_spiral_layout where those are called (a new layout, aux layout, Fourier layout or spiral layout of the
+ * field drops its laws) and, in joint fits, before psfmc_set_joint_priors; all-zero kinds remove the field's laws.
+ * Refused (PSFMC_EINVAL): a kind outside 0 ... 2, a law on a pixel-integrated slot or on one that is not flagged
+ * general, a field without an aux layout, a wrong n_sersic.  The fields of one context keep their own kinds,
+ * registered in any order.  A context that never receives a law allocates nothing, launches the kernels it launched
+ * and computes what it did without this call.
+ */
+#define PSFMC_RADIAL_PARAMS 2
+int psfmc_set_radial_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* kinds, const int* col,
+                            const double* konst);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -516,6 +548,9 @@ int psfmc_group_set_fourier_layout(psfmc_group* group, int n_sersic, const int* 
                                    const double* konst);
 /* psfmc_set_spiral_layout (field 0) on every device of the group */
 int psfmc_group_set_spiral_layout(psfmc_group* group, int n_sersic, const int* flags, const int* col,
+                                  const double* konst);
+/* psfmc_set_radial_layout (field 0) on every device of the group */
+int psfmc_group_set_radial_layout(psfmc_group* group, int n_sersic, const int* kinds, const int* col,
                                   const double* konst);
 /* psfmc_set_sersic_integrate (field 0) on every device of the group */
 int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);

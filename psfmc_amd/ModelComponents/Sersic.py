@@ -51,6 +51,12 @@ class Sersic(ComponentBase):
     finite, r_in >= 0, r_out > r_in, alpha >= 0, |inclination| < pi/2 (log-prior -inf otherwise).  A component with
     `spiral` alone is a general one with c = 0 and no modes; `spiral` with `integrate=True` raises ValueError."""
     device_kind = 'sersic'
+    # the radial law: None for the Sersic law, else a key of RADIAL_KINDS (the subclasses `Moffat` and `Ferrer`)
+    radial_law = None
+    RADIAL_KINDS = {None: 0, 'moffat': 1, 'ferrer': 2}      # psfmc_set_radial_layout's kind bytes
+    RADIAL_PARAMS = 2                                       # entries per Sersic slot: (beta, unused) or (alpha, beta)
+    # the attributes behind the slots angle, index, mag, reff, reff_b of psfmc_set_layout (a subclass renames the radii)
+    SLOT_ATTRS = ('angle', 'index', 'mag', 'reff', 'reff_b')
     FOURIER_MODES = (1, 2, 3, 4, 5, 6)
     FOURIER_POINTS = 128      # midpoint rule of the area ratio Q (`fourier_area_ratio`); fixed, the same on the device
     # the keys of `spiral` in the order of psfmc_set_spiral_layout's entries, their attributes and FITS abbreviations
@@ -102,6 +108,10 @@ class Sersic(ComponentBase):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = bool(integrate)
+        self._init_shape(boxiness, fourier, spiral)
+
+    def _init_shape(self, boxiness, fourier, spiral):
+        """The isophote-shape keywords `boxiness`, `fourier` and `spiral` (shared with the radial-law subclasses)."""
         self.has_boxiness = boxiness is not None
         if self.has_boxiness:
             if self.integrate:
@@ -152,7 +162,8 @@ class Sersic(ComponentBase):
     def header_flags(self, count):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
         when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, `<count>SERFOU` = the
-        comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral, nothing
+        comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral,
+        `<count>SERLAW = 'moffat' | 'ferrer'` when its radial law is not the Sersic law (`Moffat`, `Ferrer`), nothing
         otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
@@ -161,6 +172,8 @@ class Sersic(ComponentBase):
             out['{:d}SERFOU'.format(count)] = ','.join(str(m) for m in self.fourier_modes)
         if self.has_spiral:
             out['{:d}SERSPI'.format(count)] = True
+        if self.radial_law:
+            out['{:d}SERLAW'.format(count)] = self.radial_law
         return out
 
     @staticmethod
@@ -259,6 +272,14 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.radial_law:
+            amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
+            arr += Sersic.radial_image(self.radial_law, row, self._radial_values(lambda k: getattr(self, k)),
+                                       float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
+                                       list(zip(self.fourier_modes, amps, phases)),
+                                       self._spiral_values(lambda k: getattr(self, k)) if self.has_spiral else None,
+                                       arr.shape)
+            return arr
         if self.has_spiral:
             amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
             arr += Sersic.spiral_image(row, float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
@@ -426,6 +447,106 @@ class Sersic(ComponentBase):
             sb = sbeff / area / ci
             g = -2 * kappa * p * np.exp(L * (p - 0.5))
             return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
+
+    @staticmethod
+    def _radial_ok(law, pars):
+        """The support of a radial law's parameters, pars [..., 2]: 'moffat' (beta, unused) with beta finite and
+        > 1; 'ferrer' (alpha, beta) with both finite, alpha >= 0 and beta < 2."""
+        q = np.asarray(pars, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            if law == 'moffat':
+                return np.isfinite(q[..., 0]) & (q[..., 0] > 1)
+            if law == 'ferrer':
+                return np.isfinite(q[..., 0]) & np.isfinite(q[..., 1]) & (q[..., 0] >= 0) & (q[..., 1] < 2)
+        raise ValueError('radial law {!r}: one of moffat, ferrer'.format(law))
+
+    @staticmethod
+    def radial_central(law, row, pars, boxiness=0.0, modes=(), spiral=None):
+        """Sigma_0 of `radial_image`: the value at u = v = 0."""
+        kappa, sbeff = row[6], row[8]
+        # F / (pi r_a r_b) from the index-1 row: Sigma_e 2 n e^kappa kappa^(-2n) Gamma(2n) at n = 1
+        norm = sbeff * 2.0 * np.exp(kappa) / (kappa * kappa)
+        area = Sersic.superellipse_area_ratio(boxiness)
+        if len(modes):
+            area = area * Sersic.fourier_area_ratio(boxiness, modes)
+        if spiral is not None:
+            area = area * np.cos(float(spiral[4]))
+        if law == 'moffat':
+            beta = float(pars[0])
+            g = 4.0 * np.expm1(np.log(2.0) / beta)
+            return norm * g * (beta - 1.0) / area
+        if law == 'ferrer':
+            alpha, beta = float(pars[0]), float(pars[1])
+            k = 2.0 - beta
+            lnb = gammaln(2.0 / k) + gammaln(alpha + 1.0) - gammaln(2.0 / k + alpha + 1.0)
+            return norm / (area * (2.0 / k) * np.exp(lnb))
+        raise ValueError('radial law {!r}: one of moffat, ferrer'.format(law))
+
+    @staticmethod
+    def radial_image(law, row, pars, boxiness, modes, spiral, shape):
+        """A component whose RADIAL LAW is not the Sersic law (`Moffat`, `Ferrer`; GALFIT's component types, not the
+        reference's) on a `shape` image.  This numpy text is the DEFINITION the device kernels
+        (csrc/psfmc_general.h) are held to.  `row` is the derived row of the component's Sersic slot (index 1, the
+        radii in the places of reff / reff_b), `pars` = (beta, unused) for 'moffat' and (alpha, beta) for 'ferrer',
+        c = `boxiness` (0.0 without the keyword), `modes` as for `fourier_image` (may be empty), `spiral` as for
+        `spiral_image` or None.  The coordinates are `spiral_image`'s up to
+
+            rho^2 = (|u|^e + |v|^e)^(2/e) (1 + eps)^2,   e = c + 2
+
+        in units of the semi-major radius; an absent keyword leaves its step out, which gives the bits of its
+        neutral value.  With F the total flux, r_a, r_b the radii, N = A(c) Q cos(incl):
+
+            moffat:  g = 4 (2^(1/beta) - 1),  I = Sigma_0 (1 + g rho^2)^-beta,
+                     Sigma_0 = F g (beta - 1) / (pi r_a r_b N)        (half the peak at rho = 1/2: r_a is the FWHM)
+            ferrer:  k = 2 - beta,  x = rho^k,  I = Sigma_0 (1 - x)^alpha for x < 1, exactly 0 otherwise,
+                     Sigma_0 = F / (pi r_a r_b N (2/k) B(2/k, alpha + 1))
+
+        so that `mag` is the total magnitude.  The value is the law at the pixel centre: there is NO centroid term
+        (the reference's belongs to the Sersic law, and Ferrer's log-slope diverges at the edge).  Where u = v = 0
+        the value is Sigma_0, with or without modes and spiral: an on-pixel centre is finite, unlike the Sersic
+        law's NaN.  Support: `_radial_ok`."""
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        sigma0 = Sersic.radial_central(law, row, pars, boxiness, modes, spiral)
+        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape)
+        with np.errstate(all='ignore'):
+            if law == 'moffat':
+                beta = float(pars[0])
+                g = 4.0 * np.expm1(np.log(2.0) / beta)
+                img = sigma0 * (1.0 + g * rho2) ** -beta
+            else:
+                alpha, k = float(pars[0]), 2.0 - float(pars[1])
+                x = rho2 ** (0.5 * k)
+                img = np.where(x < 1.0, sigma0 * np.abs(1.0 - x) ** alpha, 0.0)
+            return np.where(centre, sigma0, img)
+
+    @staticmethod
+    def radial_rho2(row, boxiness, modes, spiral, shape):
+        """(rho^2, centre) of `radial_image` on a `shape` image: the squared generalised radius in units of the
+        semi-major radius (NaN or 0 where u = v = 0) and the mask of the pixels where u = v = 0."""
+        x0, y0, m00, m01, m10, m11 = row[:6]
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        e = float(boxiness) + 2.0
+        yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+        dx, dy = xx - x0, yy - y0
+        with np.errstate(all='ignore'):
+            if spiral is not None:
+                r_in, r_out, winding, alpha_s, incl, sky = [float(s) for s in spiral]
+                cs, sn, ci = np.cos(sky), np.sin(sky), np.cos(incl)
+                X = cs * dx + sn * dy
+                Y = (-sn * dx + cs * dy) / ci
+                r = np.hypot(X, Y)
+                T = 0.5 * (1.0 + np.tanh(2.0 * (2.0 * r - r_in - r_out) / (r_out - r_in)))
+                P = np.where(r > 0, (r / r_out) ** alpha_s, 1.0 if alpha_s == 0 else 0.0)
+                t = winding * T * P
+                ct, st = np.cos(t), np.sin(t)
+                dx, dy = ct * X + st * Y, -st * X + ct * Y
+            u = m00 * dx + m01 * dy
+            v = m10 * dx + m11 * dy
+            rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
+            if modes:
+                ruv = np.hypot(u, v)
+                rho2 = rho2 * (1.0 + Sersic._fourier_eps(u / ruv, v / ruv, modes)) ** 2
+            return rho2, (u == 0) & (v == 0)
 
     @staticmethod
     def _plain(row, x, y):

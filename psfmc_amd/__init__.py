@@ -3,6 +3,7 @@ psfmc_amd -- MI355X-native batched log-posterior for psfMC-style MCMC surface
 brightness modelling.  Public names mirror the reference package `psfMC`.
 """
 from .models import MultiComponentModel, FieldSet, JointModel
+from .ModelComponents import Moffat, Ferrer
 from .batch import BatchLogPosterior
 from .sampler import (EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler, TemperedEnsembleSampler,
                       DeviceTemperedSampler, default_betas)
@@ -14,4 +15,4 @@ __version__ = '0.1.0'
 __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior', 'EnsembleSampler',
            'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler', 'DeviceTemperedSampler',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
-           'model_joint_mcmc', 'model_galaxy_ptmcmc', 'load_database']
+           'model_joint_mcmc', 'model_galaxy_ptmcmc', 'load_database', 'Moffat', 'Ferrer']

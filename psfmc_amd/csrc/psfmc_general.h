@@ -37,9 +37,24 @@
 // zeros where a field has no modes); a per (field, Sersic) byte holds the flag (bit 0) and the degrees flag (bit 1).
 // The per-walker constants spar[w][k][kSpiPar] are formed by the SPI instantiation of k_general_split, in the thread
 // that moves the component's block: no launch is added.
+//
+// RADIAL LAWS (`Moffat`, `Ferrer`, GALFIT's component types; definition: Sersic.py `Sersic.radial_image`): a general
+// component whose value is a function of rho other than the Sersic law, without a centroid term:
+//     Moffat  Sigma_0 (1 + g rho^2)^-beta,  g = 4 (2^(1/beta) - 1),  Sigma_0 = F g (beta - 1) / (pi r_a r_b N)
+//     Ferrer  Sigma_0 (1 - rho^k)^alpha inside rho = 1, 0 outside,  k = 2 - beta,
+//             Sigma_0 = F / (pi r_a r_b N (2/k) B(2/k, alpha + 1))
+// N = A(c) Q cos(incl).  The component occupies a Sersic slot of index 1 with r_a, r_b in the places of the effective
+// radii, so F / (pi r_a r_b) = Sigma_e 2 e^kappa / kappa^2 comes from the block k_theta_prep made.
+// psfmc_set_radial_layout appends kRadIn entries per Sersic -- (beta, unused) or (alpha, beta) -- BEHIND the spiral
+// entries.  A context with laws ALWAYS carries the Fourier and the spiral block (zeros / constants inside the support
+// where a field has none): a walker's auxiliary vector then has 2 n_sky + 21 n_sersic doubles.  A per (field, Sersic)
+// byte holds the kind (0 Sersic, 1 Moffat, 2 Ferrer).  The per-walker constants rpar[w][k][kRadPar] are formed by the
+// LAW instantiation of k_general_split.  Such a context runs ONE further instantiation of each of the two kernels
+// (FOU, SPI and LAW all set; the kind is a wave-uniform branch); contexts without laws run the kernels they ran.
 #pragma once
 #include "psfmc_device.h"
 #include "psfmc_integrated.h"
+#include <type_traits>
 
 namespace psfmc {
 
@@ -61,6 +76,12 @@ constexpr int kSpiFlag = 1, kSpiDegrees = 2;
 // the spiral entries behind the Fourier ones: aux[base + fourier_len + kSpiIn k + j] of Sersic k
 __host__ __device__ inline int spiral_len(int n_sersic) { return kSpiIn * n_sersic; }
 
+constexpr int kRadIn = 2;            // (beta, unused) of a Moffat, (alpha, beta) of a Ferrer (PSFMC_RADIAL_PARAMS)
+constexpr int kRadPar = 4;           // Moffat: g, -beta, 0; Ferrer: k / e, k, alpha; then the kind
+constexpr int kRadMoffat = 1, kRadFerrer = 2;
+// the laws' entries behind the spiral ones: aux[base + fourier_len + spiral_len + kRadIn k + j] of Sersic k
+__host__ __device__ inline int radial_len(int n_sersic) { return kRadIn * n_sersic; }
+
 // skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
 // component, and with it the walker's likelihood, NaN)
 // SPI: the context has spirals (spar, smasks set, aux_spi the offset of the spiral entries in a walker's vector); the
@@ -70,11 +91,18 @@ __host__ __device__ inline int spiral_len(int n_sersic) { return kSpiIn * n_sers
 // and divides Sigma_e / A(c) by cos(incl); outside the support (a value not finite, r_in < 0, r_out <= r_in,
 // alpha < 0, |incl| >= a right angle in its declared unit) Sigma_e becomes NaN and the walker is skipped like a bad
 // boxiness.  The SPI = false instantiation is the kernel as it was.
-template <bool SPI>
+// LAW: the context has radial laws (rpar, rkinds set, aux_rad the offset of their entries); the thread of a slot of
+// kind != 0 turns Sigma_e / A(c) into Sigma_0 A(c) Q cos(incl) / (A(c) cos(incl)) -- k_fourier_prep's division by Q
+// follows as for every component -- and stores the law's constants: Moffat g, -beta; Ferrer k / e, k, alpha.  Outside
+// the support (Moffat: beta not finite or <= 1; Ferrer: alpha or beta not finite, alpha < 0, beta >= 2) the walker
+// is skipped like a bad boxiness.  lgamma, exp and expm1 run once per walker and component.
+template <bool SPI, bool LAW = false>
 __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __restrict__ skip,
                                 double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                                 const uint8_t* __restrict__ flags, int n_ps, int n_sersic, int n_psf, int n_psf_field,
-                                int n, double* __restrict__ spar, const uint8_t* __restrict__ smasks, int aux_spi) {
+                                int n, double* __restrict__ spar, const uint8_t* __restrict__ smasks, int aux_spi,
+                                double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr,
+                                int aux_rad = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * n_sersic) return;
     const int w = i / n_sersic, k = i - w * n_sersic;
@@ -119,6 +147,35 @@ __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __
             sp[6] = log2(r_out);
             sp[7] = wind;
             inv_a /= ci;                                               // (incl = 0: a division by 1, exact)
+        }
+    }
+    if constexpr (LAW) {
+        const int kind = rkinds[(idx / n_psf_field) * n_sersic + k];
+        if (kind) {
+            const double* a = aux + (size_t)w * aux_stride + aux_rad + kRadIn * k;
+            const double kap = b[6];
+            // F / (pi r_a r_b) over Sigma_e at index 1: 2 n e^kappa kappa^(-2n) Gamma(2n)
+            double f = 2.0 * exp(kap) / (kap * kap);
+            double* rp = rpar + (size_t)i * kRadPar;
+            if (kind == kRadMoffat) {
+                const double beta = a[0];
+                bad = bad || !(beta > 1.0) || !(beta < INFINITY);
+                const double g = 4.0 * expm1(0.69314718055994530942 / beta);
+                f *= g * (beta - 1.0);
+                rp[0] = g;
+                rp[1] = -beta;
+                rp[2] = 0.0;
+            } else {
+                const double alpha = a[0], beta = a[1];
+                bad = bad || !(alpha >= 0.0) || !(alpha < INFINITY) || !(beta < 2.0) || !(fabs(beta) < INFINITY);
+                const double kk = 2.0 - beta, tk = 2.0 / kk;
+                f /= tk * exp(lgamma(tk) + lgamma(alpha + 1.0) - lgamma(tk + alpha + 1.0));
+                rp[0] = kk / e;
+                rp[1] = kk;
+                rp[2] = alpha;
+            }
+            rp[3] = (double)kind;
+            inv_a *= f;
         }
     }
     for (int j = 0; j < kPrepSersic - 1; ++j) o[j] = b[j];
@@ -286,9 +343,24 @@ __device__ __forceinline__ void spiral_sincos(double t, double* sn, double* cs) 
     *cs = ((q + 1) & 2) ? -b : b;
 }
 
-template <bool FOURIER, bool SPIRAL = false>
+// LAW: the component's radial law is Moffat's or Ferrer's (file header; `Sersic.radial_image`): everything up to
+// s = |u|^e + |v|^e and eps is shared, then
+//     Moffat  Sigma_0 2^(-beta log2(1 + g rho^2)),  rho^2 = 2^((2/e) log2 s + 2 log2(1 + eps))
+//     Ferrer  x = 2^((k/e) log2 s + k log2(1 + eps));  x < 1 ? Sigma_0 2^(alpha log2(1 - x)) : 0
+// (alpha = 0: 2^0, exactly Sigma_0), no centroid term, and s = 0 gives Sigma_0 by a select.  The kind is
+// wave-uniform.  The LAW = false forms are the functions as they were.
+struct RadPar { double a, b, c, chk; int kind; };
+__device__ __forceinline__ RadPar load_radial(const double* __restrict__ rp) {
+    RadPar R;
+    R.a = rp[0]; R.b = rp[1]; R.c = rp[2];
+    R.kind = (int)rp[3];
+    R.chk = (R.a + R.b) + R.c;       // (a NaN among the constants reaches the pixel through general_pixel's chk)
+    return R;
+}
+
+template <bool FOURIER, bool SPIRAL = false, bool LAW = false>
 __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y,
-                                                const SpiPar* SP = nullptr) {
+                                                const SpiPar* SP = nullptr, const RadPar* RP = nullptr) {
     const double dx = x - G.s.x0, dy = y - G.s.y0;
     double u, v, spi_chk = 0.0;
     if constexpr (SPIRAL) {
@@ -318,6 +390,27 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
     const double pu = au > 0.0 ? fast_exp2(G.e * fast_log2(au)) : 0.0;
     const double pv = av > 0.0 ? fast_exp2(G.e * fast_log2(av)) : 0.0;
     const double s = pu + pv;
+    if constexpr (LAW) {
+        const RadPar& R = *RP;
+        double l1e = 0.0;                                              // log2(1 + eps)
+        if constexpr (FOURIER) {
+            const double rinv = general_rsqrt(__builtin_fma(u, u, v * v));
+            l1e = fast_log2(1.0 + fourier_eps(F, u * rinv, v * rinv));
+        }
+        const double ls = fast_log2(s);
+        double val;
+        if (R.kind == kRadMoffat) {                                    // wave-uniform
+            const double rho2 = fast_exp2(__builtin_fma(G.pe2 + G.pe2, ls, l1e + l1e));      // (p = 1/2: pe2 = 1/e)
+            val = G.s.sbeff * fast_exp2(R.b * fast_log2(__builtin_fma(R.a, rho2, 1.0)));
+        } else {
+            const double xk = fast_exp2(__builtin_fma(R.a, ls, R.b * l1e));
+            val = xk < 1.0 ? G.s.sbeff * fast_exp2(R.c * fast_log2(1.0 - xk)) : 0.0;
+        }
+        val = s > 0.0 ? val : G.s.sbeff;                               // the centre: Sigma_0, finite
+        double chk = (u + v) + (G.s.sbeff + R.chk);    // (the comparisons and the exponentials' clamps swallow a NaN)
+        if constexpr (SPIRAL) chk += spi_chk;
+        return chk == chk ? val : chk;
+    }
     double t;
     if constexpr (FOURIER) {
         const double rinv = general_rsqrt(__builtin_fma(u, u, v * v));
@@ -345,14 +438,17 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
 // the modes existed -- its registers and occupancy are not paid for by contexts without modes.
 // SPI: the context has spirals (spar, smasks set); a component with the flag runs the SPIRAL pixel function, with or
 // without modes.  The SPI = false instantiations are the kernels as they were.
-template <bool FOU, bool SPI = false>
+// LAW: the context has radial laws (rpar, rkinds set; instantiated with FOU and SPI set only, such a context carries
+// both blocks); a slot of kind != 0 runs the LAW pixel function, with or without modes and spiral.
+template <bool FOU, bool SPI = false, bool LAW = false>
 __global__ void __launch_bounds__(256)
 k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                const uint8_t* __restrict__ sky_flags, const uint8_t* __restrict__ flags, int n_sersic, int n_psf,
                int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
                int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
-               const double* __restrict__ spar = nullptr, const uint8_t* __restrict__ smasks = nullptr) {
+               const double* __restrict__ spar = nullptr, const uint8_t* __restrict__ smasks = nullptr,
+               const double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -397,7 +493,28 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
             }
             F.top = 32 - __builtin_clz((unsigned)modes);                                 // the highest mode present
         }
-        if (SPI && wound) {
+        const int kind = LAW ? rkinds[field * n_sersic + k] : 0;                         // wave-uniform
+        if (LAW && kind) {
+            const RadPar R = load_radial(rpar + ((size_t)w * n_sersic + k) * kRadPar);
+            SpiPar S{};
+            if (wound) S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);
+            auto pass = [&](auto fou, auto spi) {
+                for (int x0 = 0; x0 < xn; x0 += 64) {
+                    const int ix = x0 + lane;
+                    if (ix < xn)
+                        out[ix] = (first ? base(ix) : out[ix]) +
+                                  general_pixel<decltype(fou)::value, decltype(spi)::value, true>(G, F, (double)ix, y,
+                                                                                                  &S, &R);
+                }
+            };
+            if (wound) {
+                if (modes) pass(std::true_type{}, std::true_type{});
+                else pass(std::false_type{}, std::true_type{});
+            } else {
+                if (modes) pass(std::true_type{}, std::false_type{});
+                else pass(std::false_type{}, std::false_type{});
+            }
+        } else if (SPI && wound) {
             const SpiPar S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);
             if (FOU && modes) {
                 for (int x0 = 0; x0 < xn; x0 += 64) {

@@ -294,6 +294,14 @@ struct psfmc_ctx {
     std::vector<uint8_t> spi_masks;      // [n_fields][n_sersic] bit 0: the component has a spiral, bit 1: angles in degrees
     uint8_t* d_spi_masks = nullptr;
     double* d_spi_par = nullptr;         // [max_walkers][n_sersic][kSpiPar]
+    // radial laws (psfmc_set_radial_layout, psfmc_general.h); nothing is allocated and no kernel changes until a field
+    // registers one.  With the first registration aux_stride grows to aux_base + 20 n_sersic: the laws' entries sit
+    // behind the Fourier and the spiral block, which such a context always carries (and whose masks and constants it
+    // allocates, all clear where no field has modes or a spiral)
+    bool rad_any = false;
+    std::vector<uint8_t> rad_kinds;      // [n_fields][n_sersic] 0: the Sersic law, 1: Moffat, 2: Ferrer
+    uint8_t* d_rad_kinds = nullptr;
+    double* d_rad_par = nullptr;         // [max_walkers][n_sersic][kRadPar]
 };
 
 // the extra image of the walker whose record `prep` points at (nullptr: none to add)
@@ -1407,7 +1415,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
                     c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
-                    c->d_spi_par};
+                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (void* p : c->aux_blobs)
@@ -1709,8 +1717,15 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 // images, the general kernel then ADDS to them; alone it writes.
 // k_general_rows as the context needs it: a context without modes and without spirals runs the kernel it always ran
 static decltype(&k_general_rows<false, false>) general_rows_kernel(const psfmc_ctx* c) {
+    if (c->rad_any) return k_general_rows<true, true, true>;
     if (c->spi_any) return c->fou_any ? k_general_rows<true, true> : k_general_rows<false, true>;
     return c->fou_any ? k_general_rows<true, false> : k_general_rows<false, false>;
+}
+
+// ... and so does k_general_split
+static decltype(&k_general_split<false, false>) general_split_kernel(const psfmc_ctx* c) {
+    if (c->rad_any) return k_general_split<true, true>;
+    return c->spi_any ? k_general_split<true, false> : k_general_split<false, false>;
 }
 
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
@@ -1726,14 +1741,20 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
         const double* aux = c->d_aux + (size_t)w_off * c->aux_stride;
         const uint8_t* sky_flags = c->d_gen_flags + (size_t)c->n_fields * c->n_sersic;
         // (a context with spirals: the same launch also forms the spirals' per-walker constants)
-        double* spar = c->spi_any ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
-        const uint8_t* smasks = c->spi_any ? c->d_spi_masks : nullptr;
+        // (a context with laws carries the masks and constants of modes and spirals, and forms the laws' constants
+        // in the same launch too)
+        const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
+        double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
+        const uint8_t* smasks = spi ? c->d_spi_masks : nullptr;
+        double* rpar = c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
+        const uint8_t* rkinds = c->rad_any ? c->d_rad_kinds : nullptr;
         if (items > 0)
-            hipLaunchKernelGGL(c->spi_any ? k_general_split<true> : k_general_split<false>, dim3((items + 255) / 256),
+            hipLaunchKernelGGL(general_split_kernel(c), dim3((items + 255) / 256),
                                dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
                                c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, spar, smasks,
-                               c->aux_base + fourier_len(c->n_sersic));
+                               c->aux_base + fourier_len(c->n_sersic), rpar, rkinds,
+                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic));
         if (c->fou_any && items > 0)
             hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar,
@@ -1743,8 +1764,8 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
             hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                                dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
                                c->d_gen_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
-                               c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                               c->fou_any ? c->d_fou_masks : nullptr, spar, smasks);
+                               fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
+                               fou ? c->d_fou_masks : nullptr, spar, smasks, rpar, rkinds);
             return;
         }
     }
@@ -1755,6 +1776,7 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                        c->d_integ_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
+    const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
     if (c->gen_any)
         hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                            dim3(256), 0, st, prep, c->plen, skip,
@@ -1762,10 +1784,12 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                            c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
                            c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, c->d_gen_flags, c->n_sersic, c->n_psf,
                            c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1,
-                           c->fou_any ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                           c->fou_any ? c->d_fou_masks : nullptr,
-                           c->spi_any ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr,
-                           c->spi_any ? c->d_spi_masks : nullptr);
+                           fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
+                           fou ? c->d_fou_masks : nullptr,
+                           spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr,
+                           spi ? c->d_spi_masks : nullptr,
+                           c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr,
+                           c->rad_any ? c->d_rad_kinds : nullptr);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -2033,6 +2057,18 @@ static int drop_spiral_masks(psfmc_ctx* c, int field) {
     return PSFMC_OK;
 }
 
+// ... and so do its radial laws (psfmc_set_radial_layout)
+static int drop_radial_kinds(psfmc_ctx* c, int field) {
+    if (c->rad_kinds.empty()) return PSFMC_OK;
+    for (int k = 0; k < c->n_sersic; ++k) c->rad_kinds[(size_t)field * c->n_sersic + k] = 0;
+    bool any = false;
+    for (uint8_t m : c->rad_kinds) any = any || m;
+    if (c->d_rad_kinds)
+        HIP_TRY(hipMemcpy(c->d_rad_kinds, c->rad_kinds.data(), c->rad_kinds.size(), hipMemcpyHostToDevice));
+    c->rad_any = any;
+    return PSFMC_OK;
+}
+
 static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, const int* slot_col,
                            const double* slot_const, const int* ps_method, const int* sersic_degrees,
                            double mag_zeropoint, const int* family, const double* p0,
@@ -2097,8 +2133,10 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
     // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again)
     L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
+    L.n_rad = 0; L.rad_kind = nullptr;
     RC_TRY(drop_fourier_masks(c, field));
     RC_TRY(drop_spiral_masks(c, field));
+    RC_TRY(drop_radial_kinds(c, field));
     if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
     if (!c->gen_flags.empty()) {
         const size_t n_ser = c->n_sersic, n_sk = c->aux_n_sky;
@@ -2238,8 +2276,10 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
     if (c->aux_blobs[field]) { (void)hipFree(c->aux_blobs[field]); c->aux_blobs[field] = nullptr; }
     L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
+    L.n_rad = 0; L.rad_kind = nullptr;
     RC_TRY(drop_fourier_masks(c, field));                // (the field's modes are registered after its aux layout)
     RC_TRY(drop_spiral_masks(c, field));                 // (and so is its spiral)
+    RC_TRY(drop_radial_kinds(c, field));                 // (and so are its radial laws)
     if (n_aux) {
         // aux_const first (8-byte units), then aux_col
         std::vector<unsigned char> blob((size_t)n_aux * (sizeof(double) + sizeof(int)));
@@ -2294,7 +2334,7 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
     ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
     // (a field's spiral is registered after its modes: a Fourier layout drops it with the entries it had)
-    const int n_base = L.n_aux - L.n_fou - L.n_spi, n_fou = fourier_len(n_sersic);
+    const int n_base = L.n_aux - L.n_fou - L.n_spi - L.n_rad, n_fou = fourier_len(n_sersic);
     bool any_here = false;
     for (int k = 0; k < n_sersic; ++k) {
         if (mode_mask[k] & ~kFouModeBits)
@@ -2321,7 +2361,9 @@ extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, c
     c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
     if (!any_here && c->fou_masks.empty() && !L.n_spi) return PSFMC_OK;    // (nothing registered, nothing to remove)
     RC_TRY(drop_spiral_masks(c, field));
+    RC_TRY(drop_radial_kinds(c, field));               // (a field's laws are registered last of all)
     L.n_spi = 0;
+    L.n_rad = 0; L.rad_kind = nullptr;
     if (n_base > 0) {
         // the field's table again: its aux entries as they are, then (with modes) the Fourier entries
         std::vector<double> cst((size_t)n_base + (any_here ? n_fou : 0));
@@ -2388,7 +2430,8 @@ extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, co
     const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
     if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
     ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    const int n_keep = L.n_aux - L.n_spi, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
+    // (a field's radial laws are registered after its spiral: a spiral layout drops them with the entries they had)
+    const int n_keep = L.n_aux - L.n_spi - L.n_rad, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
     bool any_here = false;
     for (int k = 0; k < n_sersic; ++k) any_here = any_here || flags[k];
     if (any_here && n_keep <= 0)
@@ -2410,6 +2453,8 @@ extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, co
     HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
     c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
     if (!any_here && c->spi_masks.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
+    RC_TRY(drop_radial_kinds(c, field));
+    L.n_rad = 0; L.rad_kind = nullptr;
     if (n_keep > 0) {
         // the field's table again: its aux and Fourier entries as they are -- a field without modes gets the empty
         // Fourier block, so that a table index is the entry's place in the walker's vector -- then the spiral entries
@@ -2447,7 +2492,7 @@ extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, co
     if (any_here && !c->d_spi_masks) {
         // the first spiral of the context: longer auxiliary vectors (the aux and Fourier entries keep their places),
         // the components' constants and the masks
-        const int stride = c->aux_base + n_fou + n_spi;
+        const int stride = c->aux_stride > c->aux_base + n_fou + n_spi ? c->aux_stride : c->aux_base + n_fou + n_spi;
         double* longer = nullptr;
         HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
         HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
@@ -2465,6 +2510,119 @@ extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, co
     c->spi_any = any;
     c->aux_rows_w = -1;
     c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
+    return PSFMC_OK;
+}
+
+static_assert(kRadIn == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
+extern "C" int psfmc_set_radial_layout(psfmc_ctx* c, int field, int n_sersic, const int* kinds, const int* col,
+                                       const double* konst) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    if (n_sersic && (!kinds || !col || !konst)) return fail(PSFMC_EINVAL, "NULL radial array");
+    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const int n_keep = L.n_aux - L.n_rad, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
+    const int n_rad = radial_len(n_sersic);
+    bool any_here = false;
+    for (int k = 0; k < n_sersic; ++k) {
+        if (kinds[k] < 0 || kinds[k] > kRadFerrer)
+            return fail(PSFMC_EINVAL, "Sersic %d: radial kind %d outside 0 ... %d", k, kinds[k], kRadFerrer);
+        any_here = any_here || kinds[k];
+    }
+    if (any_here && n_keep <= 0)
+        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
+                    "a radial law flagged general) before psfmc_set_radial_layout", field);
+    for (int k = 0; k < n_sersic; ++k) {
+        if (!kinds[k]) continue;
+        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: a radial law and integrate exclude each "
+                        "other", k, field);
+        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d has a radial law but is not flagged general in the field's "
+                        "aux layout", k, field);
+    }
+    for (int j = 0; any_here && j < n_rad; ++j)
+        if (col[j] < -1 || col[j] >= L.n_params)
+            return fail(PSFMC_EINVAL, "radial value %d refers to column %d of %d", j, col[j], L.n_params);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and kinds being replaced
+    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
+    if (!any_here && c->rad_kinds.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
+    if (n_keep > 0) {
+        // the field's table again: its aux, Fourier and spiral entries as they are -- a field without modes gets the
+        // empty Fourier block, one without a spiral constants inside the spiral's support that are never read, so that
+        // a table index is the entry's place in the walker's vector -- then the laws' entries and, behind the columns,
+        // the kinds
+        const int pad_fou = any_here && !L.n_fou ? n_fou : 0, pad_spi = any_here && !L.n_spi ? n_spi : 0;
+        const size_t n_all = (size_t)n_keep + pad_fou + pad_spi + (any_here ? n_rad : 0);
+        std::vector<double> cst(n_all, 0.0);
+        std::vector<int> cl(n_all + (any_here ? n_sersic : 0), -1);
+        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_keep * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_keep * sizeof(int), hipMemcpyDeviceToHost));
+        for (int k = 0; k < (pad_spi ? n_sersic : 0); ++k) cst[(size_t)n_keep + pad_fou + kSpiIn * k + 1] = 1.0;   // r_out
+        for (int j = 0; any_here && j < n_rad; ++j) {
+            cst[(size_t)n_keep + pad_fou + pad_spi + j] = konst[j];
+            cl[(size_t)n_keep + pad_fou + pad_spi + j] = col[j];
+        }
+        for (int k = 0; any_here && k < n_sersic; ++k) cl[n_all + k] = kinds[k];
+        std::vector<unsigned char> blob(n_all * sizeof(double) + cl.size() * sizeof(int));
+        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
+        memcpy(blob.data() + n_all * sizeof(double), cl.data(), cl.size() * sizeof(int));
+        void* fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, blob.size()));
+        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        (void)hipFree(c->aux_blobs[field]);
+        c->aux_blobs[field] = fresh;
+        L.n_aux = (int)n_all;
+        L.n_fou += pad_fou;
+        L.n_spi += pad_spi;
+        L.n_rad = any_here ? n_rad : 0;
+        L.aux_const = static_cast<const double*>(fresh);
+        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
+        L.rad_kind = any_here ? L.aux_col + n_all : nullptr;
+        if (c->n_fields > 1 && c->d_field_layouts)
+            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    }
+    if (c->rad_kinds.empty()) c->rad_kinds.assign((size_t)c->n_fields * n_sersic, 0);
+    for (int k = 0; k < n_sersic; ++k) c->rad_kinds[(size_t)field * n_sersic + k] = (uint8_t)kinds[k];
+    if (any_here && !c->d_rad_kinds) {
+        // the first law of the context: longer auxiliary vectors (the entries they hold keep their places), the laws'
+        // constants and kinds, and what a context with modes and spirals has, all clear, where it is missing
+        const size_t n_masks = (size_t)c->n_fields * n_sersic;
+        const int stride = c->aux_base + n_fou + n_spi + n_rad;
+        double* longer = nullptr;
+        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
+        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
+        (void)hipFree(c->d_aux);
+        c->d_aux = longer;
+        c->aux_stride = stride;
+        if (c->fou_masks.empty()) c->fou_masks.assign(n_masks, 0);
+        if (!c->d_fou_masks) {
+            HIP_TRY(hipMalloc(&c->d_fou_masks, n_masks));
+            HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), n_masks, hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc(&c->d_fou_par, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
+            HIP_TRY(hipMemset(c->d_fou_par, 0, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
+        }
+        if (c->spi_masks.empty()) c->spi_masks.assign(n_masks, 0);
+        if (!c->d_spi_masks) {
+            HIP_TRY(hipMalloc(&c->d_spi_masks, n_masks));
+            HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), n_masks, hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc(&c->d_spi_par, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
+            HIP_TRY(hipMemset(c->d_spi_par, 0, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
+        }
+        HIP_TRY(hipMalloc(&c->d_rad_kinds, n_masks));
+        HIP_TRY(hipMalloc(&c->d_rad_par, ((size_t)c->max_walkers * n_sersic * kRadPar + 1) * sizeof(double)));
+        HIP_TRY(hipMemset(c->d_rad_par, 0, ((size_t)c->max_walkers * n_sersic * kRadPar + 1) * sizeof(double)));
+    }
+    bool any = false;
+    for (uint8_t m : c->rad_kinds) any = any || m;
+    if (c->d_rad_kinds)
+        HIP_TRY(hipMemcpy(c->d_rad_kinds, c->rad_kinds.data(), c->rad_kinds.size(), hipMemcpyHostToDevice));
+    c->rad_any = any;
+    c->aux_rows_w = -1;
+    c->prep_tabs_valid = false;                        // records written under the old kinds are not to be rasterised
     return PSFMC_OK;
 }
 
@@ -3835,6 +3993,13 @@ extern "C" int psfmc_group_set_spiral_layout(psfmc_group* g, int n_sersic, const
                                              const double* konst) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_spiral_layout(c, 0, n_sersic, flags, col, konst));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_radial_layout(psfmc_group* g, int n_sersic, const int* kinds, const int* col,
+                                             const double* konst) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_radial_layout(c, 0, n_sersic, kinds, col, konst));
     return PSFMC_OK;
 }
 

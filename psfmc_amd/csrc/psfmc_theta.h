@@ -54,6 +54,12 @@ struct ThetaLayout {
     // ones (n_spi > 0 implies n_fou > 0: a field with a spiral carries the Fourier block, empty without modes); per
     // Sersic r_in, r_out, winding, alpha, inclination, sky angle; 0: none (every layout before the call)
     int n_spi;
+    // radial laws (psfmc_set_radial_layout): the LAST n_rad = 2 n_sersic of the n_aux entries, behind the spiral ones
+    // (n_rad > 0 implies n_fou > 0 and n_spi > 0: a field with a law carries both blocks, empty without the
+    // keywords); per Sersic slot (beta, unused) of a Moffat or (alpha, beta) of a Ferrer; rad_kind [n_sersic] in
+    // global memory: 0 Sersic, 1 Moffat, 2 Ferrer; 0 / nullptr: none (every layout before the call)
+    int n_rad;
+    const int* rad_kind;
 };
 
 // where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
@@ -626,7 +632,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
                 // reff_b > reff is)
                 double* a = ax.aux + (size_t)w * ax.stride;
-                const int n_base = G.n_aux - G.n_fou - G.n_spi;
+                const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad;
                 for (int j = 0; j < n_base; ++j) {
                     const int col = G.aux_col[j];
                     const double v = col >= 0 ? th[col] : G.aux_const[j];
@@ -654,7 +660,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // the support: a value not finite, r_in < 0, r_out <= r_in, alpha < 0, |inclination| >= a
                     // right angle in its declared unit
                     int k = 0;
-                    for (int j0 = G.n_aux - G.n_spi; j0 < G.n_aux; j0 += 6, ++k) {
+                    for (int j0 = n_base + G.n_fou; j0 < n_base + G.n_fou + G.n_spi; j0 += 6, ++k) {
                         double v6[6];
                         bool fin = true;
                         for (int j = 0; j < 6; ++j) {
@@ -666,6 +672,22 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                         }
                         const double quarter = L.sersic_deg[k] ? 90.0 : 1.57079632679489661923;
                         if (!fin || !(v6[0] >= 0.0) || !(v6[1] > v6[0]) || !(v6[3] >= 0.0) || !(fabs(v6[4]) < quarter))
+                            lp = -INFINITY;
+                    }
+                }
+                if (G.n_rad > 0) {                                          // wave-uniform
+                    // the radial laws' entries, per Sersic slot two; outside the support: a Moffat's beta not
+                    // finite or <= 1; a Ferrer's alpha or beta not finite, alpha < 0 or beta >= 2
+                    int k = 0;
+                    for (int j0 = G.n_aux - G.n_rad; j0 < G.n_aux; j0 += 2, ++k) {
+                        const int c0 = G.aux_col[j0], c1 = G.aux_col[j0 + 1];
+                        const double v0 = c0 >= 0 ? th[c0] : G.aux_const[j0];
+                        const double v1 = c1 >= 0 ? th[c1] : G.aux_const[j0 + 1];
+                        a[j0] = v0;
+                        a[j0 + 1] = v1;
+                        const int kind = G.rad_kind[k];
+                        if (kind == 1 && (!(v0 > 1.0) || !(v0 < INFINITY))) lp = -INFINITY;
+                        if (kind == 2 && (!(v0 >= 0.0) || !(v0 < INFINITY) || !(v1 < 2.0) || !(fabs(v1) < INFINITY)))
                             lp = -INFINITY;
                     }
                 }

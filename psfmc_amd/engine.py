@@ -271,6 +271,10 @@ def load_library():
     lib.psfmc_set_spiral_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_spiral_layout.restype = ci
     lib.psfmc_group_set_spiral_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
+    lib.psfmc_set_radial_layout.restype = ci
+    lib.psfmc_set_radial_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
+    lib.psfmc_group_set_radial_layout.restype = ci
+    lib.psfmc_group_set_radial_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -350,6 +354,20 @@ def _spiral_layout_args(flags, col, const):
             SPIRAL_PARAMS, len(col), len(flags)))
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     return (flags, col, const), (len(flags), ipt(flags), ipt(col), _dp(const))
+
+
+RADIAL_PARAMS = 2          # PSFMC_RADIAL_PARAMS: (beta, unused) of a Moffat slot, (alpha, beta) of a Ferrer slot
+
+
+def _radial_layout_args(kinds, col, const):
+    """The arrays of psfmc_set_radial_layout (kept alive by the caller's tuple) and their ctypes pointers."""
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
+    kinds, col, const = i32(kinds), i32(col), _f64(const).ravel()
+    if len(col) != len(const) or len(col) != RADIAL_PARAMS * len(kinds):
+        raise ValueError('radial layout: {} entries per Sersic, got {} for {}'.format(
+            RADIAL_PARAMS, len(col), len(kinds)))
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    return (kinds, col, const), (len(kinds), ipt(kinds), ipt(col), _dp(const))
 
 
 def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
@@ -579,6 +597,13 @@ class Context(object):
         constant.  A context that never gets the call is what it was without it."""
         keep, args = _spiral_layout_args(flags, col, const)
         self._check(self._lib.psfmc_set_spiral_layout(self._ctx, 0, *args))
+
+    def set_radial_layout(self, kinds, col, const):
+        """Radial laws (psfmc_set_radial_layout; the last of the layout calls): per Sersic slot a kind -- 0 Sersic,
+        1 Moffat, 2 Ferrer -- and two entries, (beta, unused) or (alpha, beta); column of theta or -1 and a
+        constant.  A context that never gets the call is what it was without it."""
+        keep, args = _radial_layout_args(kinds, col, const)
+        self._check(self._lib.psfmc_set_radial_layout(self._ctx, 0, *args))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -925,6 +950,14 @@ class FieldSetContext(object):
                 # (a context with spirals carries the Fourier block, empty where no field has modes)
                 owner._aux_fourier = 2 * FOURIER_MODES * len(keep[0])
                 owner._aux_spiral = len(keep[1])
+
+            def set_radial_layout(self, kinds, col, const):
+                keep, args = _radial_layout_args(kinds, col, const)
+                owner._check(owner._lib.psfmc_set_radial_layout(owner._ctx, int(field), *args))
+                # (a context with laws carries the Fourier and the spiral block, empty where no field has them)
+                owner._aux_fourier = 2 * FOURIER_MODES * len(keep[0])
+                owner._aux_spiral = SPIRAL_PARAMS * len(keep[0])
+                owner._aux_radial = len(keep[1])
         return _Proxy()
 
     @staticmethod
@@ -1074,7 +1107,8 @@ class FieldSetContext(object):
         """Values per walker of the context's auxiliary vectors once a field registered Fourier modes or a spiral
         (its fields' rows without them are padded to it), else None."""
         fou = getattr(self, '_aux_fourier', 0)
-        return getattr(self, '_aux_base', 0) + fou + getattr(self, '_aux_spiral', 0) if fou else None
+        return (getattr(self, '_aux_base', 0) + fou + getattr(self, '_aux_spiral', 0) +
+                getattr(self, '_aux_radial', 0)) if fou else None
 
     def _field_aux(self, aux, n_w):
         """The auxiliary rows of a row-based call of one field: the field's own, or -- for a field WITHOUT the keywords
@@ -1315,6 +1349,11 @@ class ContextGroup(object):
         """`Context.set_spiral_layout` on every device of the group."""
         keep, args = _spiral_layout_args(flags, col, const)
         self._check(self._lib.psfmc_group_set_spiral_layout(self._grp, *args))
+
+    def set_radial_layout(self, kinds, col, const):
+        """`Context.set_radial_layout` on every device of the group."""
+        keep, args = _radial_layout_args(kinds, col, const)
+        self._check(self._lib.psfmc_group_set_radial_layout(self._grp, *args))
 
     def loglike(self, rows, skip=None, aux=None):
         if aux is not None:

@@ -128,7 +128,7 @@ class MultiComponentModel(object):
             if not isinstance(comp, PSFSelector) and comp.device_kind is None:
                 raise NotImplementedError(
                     'component {} has no GPU rasteriser; supported: Sky, '
-                    'PointSource, Sersic'.format(type(comp).__name__))
+                    'PointSource, Sersic, Moffat, Ferrer'.format(type(comp).__name__))
 
         self.config = config
         self.components = components
@@ -225,7 +225,7 @@ class MultiComponentModel(object):
         for c in self._ps:
             add(c, 'mag'); add(c, 'xy', 0); add(c, 'xy', 1)
         for c in self._sersic:
-            for name in ('angle', 'index', 'mag', 'reff', 'reff_b'):
+            for name in c.SLOT_ATTRS:                 # angle, index, mag and the class's names of the two radii
                 add(c, name)
             add(c, 'xy', 0); add(c, 'xy', 1)
         add(self.config.psf_selector, 'psf_index')
@@ -266,10 +266,24 @@ class MultiComponentModel(object):
                 slot_col += [-1] * 6; slot_const += list(_SPIRAL_ABSENT)
         spi_col, spi_const = slot_col[n_before:], slot_const[n_before:]
         slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
+        # radial laws (`Moffat`, `Ferrer`): per Sersic slot the law's two entries as declared -- (beta, unused) or
+        # (alpha, beta) -- a slot with the Sersic law two constants that are never read; registered last, and only by
+        # a model with such a component
+        for c in self._sersic:
+            if c.radial_law:
+                for attr in c.LAW_ATTRS:
+                    add(c, attr)
+                pad = Sersic.RADIAL_PARAMS - len(c.LAW_ATTRS)
+                slot_col += [-1] * pad; slot_const += [0.0] * pad
+            else:
+                slot_col += [-1] * Sersic.RADIAL_PARAMS; slot_const += [0.0] * Sersic.RADIAL_PARAMS
+        rad_col, rad_const = slot_col[n_before:], slot_const[n_before:]
+        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
         if columns is not None:
             aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
             fou_col = [int(columns[c]) if c >= 0 else -1 for c in fou_col]
             spi_col = [int(columns[c]) if c >= 0 else -1 for c in spi_col]
+            rad_col = [int(columns[c]) if c >= 0 else -1 for c in rad_col]
 
         def register_aux():
             if self.has_aux:
@@ -278,6 +292,8 @@ class MultiComponentModel(object):
                 eng.set_fourier_layout(self.sersic_fourier_masks, fou_col, fou_const)
             if any(self.sersic_spiral_flags):
                 eng.set_spiral_layout(self.sersic_spiral_flags, spi_col, spi_const)
+            if any(self.sersic_radial_kinds):
+                eng.set_radial_layout(self.sersic_radial_kinds, rad_col, rad_const)
         if columns is not None:
             slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
             zero = np.zeros(n_params)
@@ -322,6 +338,11 @@ class MultiComponentModel(object):
         return [bool(getattr(c, 'has_spiral', False)) for c in self._sersic]
 
     @property
+    def sersic_radial_kinds(self):
+        """[n_sersic] the radial law of each Sersic slot (model-file order): 0 Sersic, 1 Moffat, 2 Ferrer."""
+        return [Sersic.RADIAL_KINDS[getattr(c, 'radial_law', None)] for c in self._sersic]
+
+    @property
     def has_aux(self):
         """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier` or `spiral`)?"""
         return any(self.sky_slope_flags) or any(self.sersic_general_flags)
@@ -333,7 +354,9 @@ class MultiComponentModel(object):
         modes appends psfmc_set_fourier_layout's 12 n_sersic entries: per Sersic and mode 1 ... 6 the amplitude and
         the phase as declared (zeros for absent modes).  A model with a `spiral` carries those 12 n_sersic entries
         (zeros without modes) and behind them psfmc_set_spiral_layout's 6 n_sersic: per Sersic r_in, r_out, winding,
-        alpha, inclination and sky angle as declared (constants inside the support for a component without it)."""
+        alpha, inclination and sky angle as declared (constants inside the support for a component without it).  A
+        model with a `Moffat` or `Ferrer` carries both blocks and behind them psfmc_set_radial_layout's 2 n_sersic:
+        per Sersic slot (beta, 0) or (alpha, beta), zeros for a slot with the Sersic law."""
         if not self.has_aux:
             return None
         theta = self._theta(theta)
@@ -348,19 +371,26 @@ class MultiComponentModel(object):
             if isinstance(c, Sersic):
                 cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
-        if any(self.sersic_fourier_masks) or any(self.sersic_spiral_flags):
+        laws = any(self.sersic_radial_kinds)
+        if any(self.sersic_fourier_masks) or any(self.sersic_spiral_flags) or laws:
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
                     vals = c.values_batch(theta[:, s]) if c.fourier_modes else {}
                     for m in Sersic.FOURIER_MODES:
                         for key in ('f%d_amp' % m, 'f%d_phase' % m):
                             cols.append(np.reshape(vals[key], (n_w,)) if m in c.fourier_modes else np.zeros(n_w))
-        if any(self.sersic_spiral_flags):
+        if any(self.sersic_spiral_flags) or laws:
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
                     vals = c.values_batch(theta[:, s]) if c.has_spiral else {}
                     for attr, absent in zip(Sersic.SPIRAL_ATTRS, _SPIRAL_ABSENT):
                         cols.append(np.reshape(vals[attr], (n_w,)) if c.has_spiral else np.full(n_w, absent))
+        if laws:
+            for c, s in zip(self.components, self._spans):
+                if isinstance(c, Sersic):
+                    pars = (c._radial_values(c.values_batch(theta[:, s]), n_w) if c.radial_law
+                            else np.zeros((n_w, Sersic.RADIAL_PARAMS)))
+                    cols += [pars[:, j] for j in range(Sersic.RADIAL_PARAMS)]
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
     @staticmethod

@@ -6,7 +6,9 @@ keywords, vectors resident on the device (psfmc_eval_theta_device, what bench.py
 (`fourier={1: ..., 3: ...}`) against the same model with the boxiness only.
 --spiral: the cost of the spiral arms -- the same model with a free boxiness and a free spiral (all six values)
 against the boxiness only.
-Usage: python tools/time_general.py [--fourier | --spiral] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+--radial: the cost of the radial laws -- Sky + PS + one boxy `Ferrer` and one `Moffat` against the same model with two
+boxy `Sersic`s.
+Usage: python tools/time_general.py [--fourier | --spiral | --radial] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
 import argparse
 import json
 import os
@@ -65,6 +67,53 @@ def build_fourier(side, directory, max_walkers, modes, extra=FOURIER):
     return MultiComponentModel(path, max_walkers=max_walkers), fld
 
 
+RADIAL_COMMON = ('xy=Uniform(loc=c - ms, scale=2 * ms), mag=Uniform(loc=19.0, scale=5.0), '
+                 'angle=Uniform(loc=0, scale=180), angle_degrees=True')
+# the free values the timed vectors draw, by the parameter's attribute: (low, high) in units of the side where scaled
+RADIAL_RANGES = {'adu': (-1e-3, 1e-3), 'alpha': (0.5, 3.0), 'angle': (10.0, 170.0), 'beta': (1.2, 1.9),
+                 'boxiness': (-0.5, 0.5), 'index': (0.7, 3.0), 'mag': (19.5, 21.0)}
+
+
+def build_radial(side, directory, max_walkers, laws):
+    """Sky + PS + a boxy Ferrer and a Moffat (`laws`), or two boxy Sersics with the same radii; the model and a
+    function drawing n_w vectors inside every support."""
+    fld = synth_field.make_field(side, n_sersic=1, seed=0)
+    for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
+        fits_io.write_image(os.path.join(directory, name), fld[key])
+    text = synth_field.model_file_text(side, 0).replace('PointSource(', SKY[0] + '\nPointSource(', 1)
+    big, small = 'Uniform(loc=%r, scale=%r)' % (side / 16.0 + 2.0, side / 8.0), 'Uniform(loc=2.0, scale=%r)' % (side / 16.0)
+    box = 'boxiness=Uniform(loc=-1, scale=2)'
+    if laws:
+        text += 'Ferrer(%s, r_out=%s, r_out_b=%s, alpha=Uniform(loc=0, scale=4), beta=Uniform(loc=-2, scale=3.95), %s)\n' % (
+            RADIAL_COMMON, big, small, box)
+        text += 'Moffat(%s, fwhm=%s, fwhm_b=%s, beta=Uniform(loc=1.05, scale=8))\n' % (RADIAL_COMMON, big, small)
+    else:
+        for _ in range(2):
+            text += 'Sersic(%s, reff=%s, reff_b=%s, index=Uniform(loc=0.5, scale=6), %s)\n' % (RADIAL_COMMON, big, small, box)
+    path = os.path.join(directory, 'model_r%d.py' % laws)
+    with open(path, 'w') as f:
+        f.write(text)
+    model = MultiComponentModel(path, max_walkers=max_walkers)
+
+    def draw(n_w, seed=3):
+        rng = np.random.RandomState(seed)
+        cols = []
+        for name, width in zip(model.param_names, model.param_lens):
+            attr = name.split('_', 2)[2]
+            if attr == 'xy':
+                cols.append(side / 2.0 + 0.5 + rng.uniform(-4.0, 4.0, (n_w, 2)))
+            elif attr in ('r_out', 'fwhm', 'reff'):
+                cols.append(rng.uniform(side / 16.0 + 2.0, side / 8.0, (n_w, 1)))
+            elif attr in ('r_out_b', 'fwhm_b', 'reff_b'):
+                cols.append(rng.uniform(2.0, side / 16.0, (n_w, 1)))
+            elif name.endswith('PointSource_mag'):
+                cols.append(rng.uniform(18.5, 19.5, (n_w, 1)))
+            else:
+                cols.append(rng.uniform(*RADIAL_RANGES[attr], size=(n_w, width)))
+        return np.hstack(cols)
+    return model, draw
+
+
 def evals_per_second(model, theta, seconds):
     import torch
     eng = model.engine
@@ -94,15 +143,22 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--fourier', action='store_true', help='boxiness + two free modes against boxiness only')
     ap.add_argument('--spiral', action='store_true', help='boxiness + a free spiral against boxiness only')
+    ap.add_argument('--radial', action='store_true', help='a boxy Ferrer and a Moffat against two boxy Sersics')
     args = ap.parse_args()
-    if args.fourier and args.spiral:
-        ap.error('--fourier and --spiral exclude each other')
+    if args.fourier + args.spiral + args.radial > 1:
+        ap.error('--fourier, --spiral and --radial exclude each other')
     rows = []
     for shape in args.shapes:
         side, n_w = (int(v) for v in shape.split(':'))
         with tempfile.TemporaryDirectory() as tmp:
             rates = {}
             for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
+                if args.radial:
+                    model, draw = build_radial(side, tmp, n_w, general)
+                    rate, _ = evals_per_second(model, draw(n_w), args.seconds)
+                    rates[general] = max(rates.get(general, 0.0), rate)
+                    model.close()
+                    continue
                 if args.spiral:
                     model, fld = build_fourier(side, tmp, n_w, general, SPIRAL)
                 else:
@@ -133,7 +189,8 @@ def main():
                        general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    lines = ['side     W  boxiness evals/s box + spiral evals/s  ratio' if args.spiral else
+    lines = ['side     W 2 Sersics evals/s Ferrer + Moffat evals/s ratio' if args.radial else
+             'side     W  boxiness evals/s box + spiral evals/s  ratio' if args.spiral else
              'side     W   default evals/s     general evals/s  ratio' if not args.fourier else
              'side     W  boxiness evals/s  box + modes evals/s  ratio']
     for r in rows:
