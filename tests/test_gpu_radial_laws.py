@@ -10,17 +10,13 @@ import pytest
 import test_gpu_fourier_modes as tgf
 import test_gpu_general_components as tgg
 import test_gpu_spiral_arms as tgs
+from extra_contract import EDGE_MARGIN, ferrer_state, law_error
 from test_gpu_general_components import RAW_BOUND, contract_evaluate, make_field, oracle_field, raw_error
 from psfmc_amd import MultiComponentModel
 from psfmc_amd.ModelComponents import Configuration, Ferrer, Moffat, PointSource, Sersic, Sky
 from psfmc_amd.distributions import Normal, Uniform
 
 pytestmark = pytest.mark.gpu
-
-# |1 - x| of every compared pixel of a Ferrer component is at least this (asserted on the host from the definition
-# before the device is asked): 1 - x cancels at the edge, where a pixel's absolute error is alpha (1 - x)^(alpha - 1) dx;
-# with dx ~ 1e-15 this stays below 1e-12 of Sigma_0 for alpha >= 0.5, and at alpha = 0 no pixel changes sides
-EDGE_MARGIN = 1e-6
 
 
 def U(lo, hi):
@@ -136,42 +132,6 @@ def contract_sets(fld):
                         **named(4, 'Sersic', angle=45.0, index=4.0, mag=18.8, reff=3.0, reff_b=1.5, xy=(cx - 4.3, cy + 2.6))))]),
     ]
     return sets
-
-
-def ferrer_state(model):
-    """(smallest Sigma_0, smallest |1 - x| over the image's pixels) of the model's Ferrer components at the model's
-    current values, from the definition alone; (0, inf) without one."""
-    sigma0, margin = [], np.inf
-    shape = model.config.obs_data.shape
-    for comp in model.components:
-        if not isinstance(comp, Ferrer):
-            continue
-        get = lambda k: getattr(comp, k)
-        row = comp.derived_row(model.config.mag_zeropoint)
-        box = float(np.ravel(comp.boxiness)[0]) if comp.has_boxiness else 0.0
-        amps, phases = comp._fourier_values(get) if comp.has_fourier else ((), ())
-        modes = list(zip(comp.fourier_modes, amps, phases))
-        spiral = comp._spiral_values(get) if comp.has_spiral else None
-        pars = comp._radial_values(get)
-        sigma0.append(Sersic.radial_central('ferrer', row, pars, box, modes, spiral))
-        rho2, centre = Sersic.radial_rho2(row, box, modes, spiral, shape)
-        with np.errstate(all='ignore'):
-            x = np.where(centre, 0.0, rho2 ** (0.5 * (2.0 - pars[1])))
-        margin = min(margin, float(np.min(np.abs(1.0 - x))))
-    return (min(sigma0) if sigma0 else 0.0), margin
-
-
-def law_error(got, want, sigma0, tag):
-    """A Moffat, a Sersic, the sky and the point source relative to the pixel, a Ferrer relative to its Sigma_0: the
-    absolute error over max(|pixel|, Sigma_0), on every pixel where that is above 1e-12 of the peak (`raw_error`'s
-    pixels; with a Ferrer in the model no pixel is left out)."""
-    assert np.all(np.isfinite(got)) and np.all(np.isfinite(want)), tag
-    scale = np.maximum(np.abs(want), sigma0)
-    big = scale > 1e-12 * np.abs(want).max()
-    assert sigma0 == 0.0 or np.all(big), tag
-    err = float(np.max(np.abs(got - want)[big] / scale[big]))
-    print('%s: raw model max error %.2e (Sigma_0 of the Ferrer %.3e)' % (tag, err, sigma0))
-    return err
 
 
 @pytest.mark.parametrize('backend,shape', [('fused', s) for s in tgg.SHAPES] + [('hipfft', (64, 64)), ('hipfft', (70, 66))],
