@@ -608,6 +608,8 @@ int psfmc_get_spectra(psfmc_ctx* ctx, double* psf_spec, double* var_spec);
  * transforms of more than 256 pixels per row --, 0: log2 + exp2 per pixel; a property of the transform shape),
  * "pow_tabs_built" (1: the last batch's forward rows read the tables k_pow_tables built in memory, 0: its row waves
  * formed the entries themselves -- small batches, psfmc_hip.hip launch_pow_tables -- or the context has no tables),
+ * "raster_group" (the pixels per lane the forward row kernel's power-table rasteriser takes through the profile
+ * together: 1, 2 or 4 by row length and embedding; 0 where it is the log2 + exp2 form; NaN on the hipFFT back end),
  * "transform_ny" / "transform_nx" (the transform shape: the image's own, or the built sides an
  * image of unbuilt sides is embedded in), "speculated_runs", "graph_launches", "row_group",
  * "partials_per_walker", "cols3", "column_engine" (the column kernel this context launches now: 0 k_cols, 1 k_cols3, 2

@@ -92,9 +92,17 @@ template <int NX> constexpr int row_group() { return FftShape<NX>::TPW; }       
                                          512^2; whole step +0.7 % / +1.2 % (51.82 -> 52.17 k, 279.0 -> 282.2 k evals/s): small, consistent, taken
                                          (round 3 read the same numbers as noise) */
 #endif
+// GUARD: tests/helpers.py RASTER_FORMS lists one row length per rasteriser form (log2 + exp2, G = 1, 2, 4, one row per
+// wave; plain and WRAP) and tests/test_gpu_raster_extremes.py asserts the form through get_option("raster_group"):
+// a new side or a changed pick here updates that table.
 template <int NX> constexpr int raster_group() {
     if (FftShape<NX>::kPlain && NX >= 512) return PSFMC_RASTER_GROUP_PLAIN;
     return (pow_tabs_side(NX) && !FftShape<NX>::kPlain && FftShape<NX>::R > 16 && NX != 264 && NX != 286 && NX != 294) ? PSFMC_RASTER_GROUP : 1;
+}
+// the G of k_rows_fwd<NX, ..., WRAP>'s raster_row (what get_option("raster_group") reports; 0: the log2 + exp2 form,
+// which has no groups).  The WRAP variants keep the serial pixel order (see k_rows_fwd).
+template <int NX, bool WRAP> constexpr int fwd_raster_group() {
+    return !pow_tabs_side(NX) ? 0 : WRAP ? 1 : raster_group<NX>();
 }
 // rows that share a contiguous run of T per kx (the "RG" of the layout comment above): the rows
 // of one wave for the power-of-two shapes, 4 otherwise (ny is rounded up to a multiple of it in
@@ -352,8 +360,8 @@ k_rows_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip,
         } else {
             // (the WRAP variants keep the serial pixel order: with their P wrapped coordinates on top, the grouped
             // form spilled or lost a wave -- embedded 586^2 -17 %, 698^2 -21 % whole step)
-            raster_row<P, T, 0, WRAP, WRAP ? 1 : raster_group<NX>()>(wprep, n_ps, n_sersic, t, iy, ps_only != 0, log_tab, r,
-                                                                    wr, pow_mode);
+            raster_row<P, T, 0, WRAP, fwd_raster_group<NX, WRAP>()>(wprep, n_ps, n_sersic, t, iy, ps_only != 0, log_tab, r,
+                                                                   wr, pow_mode);
         }
         if constexpr (EXTRA) {
             if (!ps_only && row_on) {

@@ -574,6 +574,16 @@ template <int NY> static int col_engine_code(const psfmc_ctx* c) {
     return 0;
 }
 
+// the G of the raster_row this context's forward row kernel runs (launch_rows_fwd's choices); 0: log2 + exp2 per pixel
+template <int NX> static int raster_group_code(const psfmc_ctx* c) {
+    if constexpr (!two_stage_side(NX)) {
+        return rows3_raster_group(c->embed);
+    } else {
+        if (c->rows3_fwd) return rows3_raster_group(c->embed);
+        return c->embed ? fwd_raster_group<NX, true>() : fwd_raster_group<NX, false>();
+    }
+}
+
 template <int NX, typename TS, bool FAST, bool MULTI>
 static int launch_rows_inv_kernel(psfmc_ctx* c, int n, const TS* Tbuf, const double* prep, const uint8_t* skip,
                                   double* partial, double* conv_out, double* var_out, hipStream_t st) {
@@ -705,7 +715,7 @@ static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int group
 // ---------------------------------------------------------------------------
 // size-erased entry to the per-side launchers: what crosses the boundary between the parts
 // ---------------------------------------------------------------------------
-enum SizeOp { SZ_ROW_SHAPE, SZ_FIELD_LEN, SZ_PACK_FIELD, SZ_ROWS_FWD, SZ_COLS, SZ_ROWS_INV, SZ_RASTER_SUMS, SZ_COL_ENGINE };
+enum SizeOp { SZ_ROW_SHAPE, SZ_FIELD_LEN, SZ_PACK_FIELD, SZ_ROWS_FWD, SZ_COLS, SZ_ROWS_INV, SZ_RASTER_SUMS, SZ_COL_ENGINE, SZ_RASTER_GROUP };
 struct SizeCall {
     psfmc_ctx* c = nullptr;
     int n = 0;                              // walkers
@@ -772,6 +782,9 @@ static int size_call_here(int op, int side, SizeCall& a) {
             return PSFMC_OK;
         case SZ_COL_ENGINE:
             DISPATCH_LEN(side, *a.code = col_engine_code<N_>(c));
+            return PSFMC_OK;
+        case SZ_RASTER_GROUP:
+            DISPATCH_LEN(side, *a.code = raster_group_code<N_>(c));
             return PSFMC_OK;
     }
     return fail(PSFMC_EINVAL, "unknown size operation %d", op);
@@ -1554,6 +1567,13 @@ extern "C" double psfmc_get_option(const psfmc_ctx* cc, const char* key) {
         SizeCall a;
         a.c = c; a.code = &code;
         return size_call(SZ_COL_ENGINE, c->ny, a) == PSFMC_OK ? (double)code : NAN;
+    }
+    if (!strcmp(key, "raster_group")) {        // pixels per group of the forward row kernel's power-table rasteriser (0: log2 + exp2 form)
+        if (c->backend != PSFMC_BACKEND_FUSED) return NAN;
+        int code = 0;
+        SizeCall a;
+        a.c = c; a.code = &code;
+        return size_call(SZ_RASTER_GROUP, c->nx, a) == PSFMC_OK ? (double)code : NAN;
     }
     if (!strcmp(key, "speculate")) return c->speculate;
     if (!strcmp(key, "pow_tabs")) return c->use_pow_tabs ? 1.0 : 0.0;

@@ -92,6 +92,8 @@ constexpr int rows3_rg_log2(int n) { return n > 1024 ? PSFMC_ROWS3_BIG_RG_LOG2 :
 //             at 1024^2 / 6 walkers, measured by compiling the phases out), and the table traffic per pixel doubles.
 // So: the inverse kernel for the six sides above and 720, both kernels for the sides above 1024 (nothing else
 // reaches them).
+// GUARD: tests/helpers.py RASTER_FORMS names the row length that stands for the one-row-per-wave rasteriser (and the
+// other forms); a side added here, or a forward kernel taken below 1024, updates that table.
 constexpr Fft3gPick rows3_pick(int n) {
     switch (n) {
         // sides above 1024: the only row kernels there are (the two-stage shapes end at P = T = 32)
@@ -173,6 +175,8 @@ template <class S, bool INVERSE> constexpr int rows3_min_waves() {
 #define PSFMC_ROWS3_PREFETCH 0      /* the next component's parameters and tables in flight during this one's pixels
                                        (measured: 840 -6 %, 900 0, 1024 +3 % kernel time; 15 registers) */
 #endif
+// the G of k_rows3_fwd's raster_row (get_option("raster_group"))
+constexpr int rows3_raster_group(bool wrap) { return wrap ? 1 : PSFMC_ROWS3_RASTER_GROUP; }
 #ifndef PSFMC_DEBUG_ROWS3
 #define PSFMC_DEBUG_ROWS3 0          /* timing experiments: 1 = no store phase, 2 = no transform, 4 = no rasteriser */
 #endif
@@ -279,7 +283,7 @@ k_rows3_fwd(const double* __restrict__ prep, const uint8_t* __restrict__ skip, c
 #pragma unroll
             for (int k = 0; k < R1; ++k) r[k] = wprep[0] * (double)(t + k);
 #else
-            raster_row<R1, L, 0, WRAP, WRAP ? 1 : PSFMC_ROWS3_RASTER_GROUP, PSFMC_ROWS3_PREFETCH != 0>(
+            raster_row<R1, L, 0, WRAP, rows3_raster_group(WRAP), PSFMC_ROWS3_PREFETCH != 0>(
                 wprep, n_ps, n_sersic, tl, iy, ps_only != 0, wave_lds, r, wr, pow_mode);
 #endif
             if constexpr (EXTRA) {
