@@ -615,7 +615,10 @@ int psfmc_get_spectra(psfmc_ctx* ctx, double* psf_spec, double* var_spec);
  * "partials_per_walker", "cols3", "column_engine" (the column kernel this context launches now: 0 k_cols, 1 k_cols3, 2
  * k_cols3g, 3 k_cols3f), "rows3" (bit 0 / bit 1: the forward / inverse row kernel is the one-row-per-wave
  * three-stage one of csrc/psfmc_rows3_path.h -- both above 1024, the inverse one at seven general sides; the
- * environment variable PSFMC_ROWS3 = 1 / 0, read at context creation, forces every built one / none: A/B runs).
+ * environment variable PSFMC_ROWS3 = 1 / 0, read at context creation, forces every built one / none: A/B runs),
+ * "aux_stride" (doubles per walker of the context's auxiliary vectors, psfmc_set_aux_rows' rows included: 0 before
+ * the first aux layout, then 2 n_sky + n_sersic, + 12 / 18 / 20 n_sersic from the first modes / spiral / law of any
+ * field on; it never shrinks).
  */
 int psfmc_set_option(psfmc_ctx* ctx, const char* key, double value);
 double psfmc_get_option(const psfmc_ctx* ctx, const char* key);
@@ -628,6 +631,20 @@ double psfmc_get_option(const psfmc_ctx* ctx, const char* key);
  * check the hand-written elementary functions of the rasteriser against numpy.
  */
 int psfmc_debug_math(int device, int op, int n, const double* in, double* out);
+/*
+ * Diagnostic hook: the auxiliary table the library composes for ONE field from what the field registered, on the
+ * host alone (no context, no device).  base_col / base_const [2 n_sky + n_sersic]: psfmc_set_aux_layout's arrays
+ * (NULL: no aux layout); per block the tags [n_sersic] -- mode masks, spiral flags, radial kinds -- and col / konst
+ * of psfmc_set_fourier_layout, psfmc_set_spiral_layout and psfmc_set_radial_layout (NULL tags: never registered).
+ * out_const / out_col [2 n_sky + 21 n_sersic] receive the table's first counts[0] entries in the order the device
+ * reads them, out_kinds [n_sersic] the kinds behind the columns (written where counts[3] > 0); counts [4] =
+ * n_aux, n_fou, n_spi, n_rad of the field's layout.
+ */
+int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                          const int* mode_mask, const int* fou_col, const double* fou_const,
+                          const int* spi_flags, const int* spi_col, const double* spi_const,
+                          const int* rad_kinds, const int* rad_col, const double* rad_const,
+                          double* out_const, int* out_col, int* out_kinds, int* counts);
 
 /*
  * Diagnostic hook: time `reps` plain sweeps over a scratch buffer of nbytes (>= 1 MiB) -- mode 0

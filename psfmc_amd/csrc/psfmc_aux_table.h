@@ -1,0 +1,84 @@
+// A field's auxiliary table on the host: the record of what the field registered, and the one function that
+// composes the table the device reads from it.  No HIP call in this file.
+//
+// The table: the base entries (psfmc_set_aux_layout: 2 n_sky + n_sersic), then the blocks in the order of kAuxBlocks
+// -- Fourier modes, spiral arms, radial laws -- each with the entries of psfmc_set_*_layout.  A table index is the
+// entry's place in the walker's auxiliary vector, so a present block forces every block before it to be present:
+// where the field registered none, that block is PADDED with entries no kernel reads (column -1 and the block's
+// pad constants, inside the support of what would read them).
+#pragma once
+#include <vector>
+
+#include "psfmc_general.h"
+
+namespace psfmc {
+
+enum { kBlkFou = 0, kBlkSpi, kBlkRad, kAuxBlocks };
+
+// entries of block b for n_sersic components
+inline int aux_block_len(int b, int n_sersic) {
+    return b == kBlkFou ? fourier_len(n_sersic) : b == kBlkSpi ? spiral_len(n_sersic) : radial_len(n_sersic);
+}
+
+// what one registration call passed: the per-Sersic tags (mode masks, spiral flags, radial kinds) and the entries.
+// Empty: never registered, dropped, or registered with all-zero tags.
+struct AuxBlockRecord {
+    std::vector<int> tags, col;
+    std::vector<double> konst;
+    bool empty() const { return tags.empty(); }
+    void clear() { tags.clear(); col.clear(); konst.clear(); }
+    void store(int n_sersic, int len, const int* t, const int* cl, const double* k) {
+        clear();
+        bool any = false;
+        for (int i = 0; i < n_sersic; ++i) any = any || t[i];
+        if (!any) return;
+        tags.assign(t, t + n_sersic);
+        col.assign(cl, cl + len);
+        konst.assign(k, k + len);
+    }
+};
+
+struct FieldAuxRecord {
+    std::vector<int> sersic_degrees;     // psfmc_set_layout's, [n_sersic]
+    std::vector<int> base_col;           // psfmc_set_aux_layout's aux_col / aux_const
+    std::vector<double> base_const;
+    AuxBlockRecord block[kAuxBlocks];
+};
+
+// the table in upload order: konst | col | kinds.  kinds (the radial kinds, [n_sersic]) is empty without laws.
+struct AuxTable {
+    std::vector<double> konst;
+    std::vector<int> col, kinds;
+    int n_aux = 0, n_fou = 0, n_spi = 0, n_rad = 0;
+};
+
+inline AuxTable compose_aux_table(const FieldAuxRecord& r, int n_sky, int n_sersic) {
+    AuxTable t;
+    if ((int)r.base_col.size() != aux_len(n_sky, n_sersic) || r.base_col.empty()) return t;   // no aux layout, no table
+    t.col = r.base_col;
+    t.konst = r.base_const;
+    int last = -1;                       // the last block the field registered
+    for (int b = 0; b < kAuxBlocks; ++b)
+        if (!r.block[b].empty()) last = b;
+    int n[kAuxBlocks] = {0, 0, 0};
+    for (int b = 0; b <= last; ++b) {
+        const AuxBlockRecord& blk = r.block[b];
+        const size_t at = t.col.size();
+        n[b] = aux_block_len(b, n_sersic);
+        if (!blk.empty()) {
+            t.col.insert(t.col.end(), blk.col.begin(), blk.col.end());
+            t.konst.insert(t.konst.end(), blk.konst.begin(), blk.konst.end());
+            continue;
+        }
+        t.col.resize(at + n[b], -1);
+        t.konst.resize(at + n[b], 0.0);
+        if (b == kBlkSpi)
+            for (int k = 0; k < n_sersic; ++k) t.konst[at + kSpiIn * k + 1] = 1.0;   // r_out > r_in = 0
+    }
+    if (last == kBlkRad) t.kinds = r.block[kBlkRad].tags;
+    t.n_aux = (int)t.col.size();
+    t.n_fou = n[kBlkFou]; t.n_spi = n[kBlkSpi]; t.n_rad = n[kBlkRad];
+    return t;
+}
+
+}  // namespace psfmc

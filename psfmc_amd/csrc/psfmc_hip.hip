@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <hipfft/hipfft.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -35,6 +36,7 @@
 #if PSFMC_PART == 0
 #include "psfmc_integrated.h"
 #include "psfmc_general.h"
+#include "psfmc_aux_table.h"
 #endif
 
 using namespace psfmc;
@@ -122,6 +124,7 @@ static_assert(side_costs_match_sides(), "psfmc_side_costs.h: regenerate it (tool
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
+namespace psfmc { struct FieldAuxRecord; }   // psfmc_aux_table.h: complete in part 0, the only part that makes contexts
 struct psfmc_ctx {
     int device = 0;
     int ny = 0, nx = 0, nxh = 0, S = 0, F = 0;
@@ -272,12 +275,17 @@ struct psfmc_ctx {
     // auxiliary parameters, general Sersic components and tilted skies (psfmc_set_aux_layout, psfmc_general.h);
     // nothing is allocated and no kernel changes until a field registers an aux layout with a flag set
     bool gen_any = false;
-    int aux_stride = 0, aux_n_sky = 0;   // doubles per walker of d_aux (2 n_sky + n_sersic), the same for every field
+    // doubles per walker of d_aux, the same for every field: the longest table a field of the context ever had
+    // (apply_aux_record; 2 n_sky + n_sersic, + 12 / 18 / 20 n_sersic from the first modes / spiral / law on)
+    int aux_stride = 0, aux_n_sky = 0;
     std::vector<uint8_t> gen_flags;      // [n_fields][n_sersic] general components, then [n_fields][n_sky] tilted skies
     uint8_t* d_gen_flags = nullptr;
     double* d_gen_par = nullptr;         // [max_walkers][n_sersic][kGenPar] the general components' real blocks
     double* d_aux = nullptr;             // [max_walkers][aux_stride]
     std::vector<void*> aux_blobs;        // [n_fields] the allocations behind the layouts' aux_col / aux_const
+    // [n_fields] what each field registered (psfmc_set_layout's degrees, the arguments of psfmc_set_aux_layout and
+    // of the three block layouts): apply_aux_record composes the field's table and mask rows from it
+    std::vector<psfmc::FieldAuxRecord> aux_records;
     int aux_rows_w = -1;                 // walkers whose aux rows psfmc_set_aux_rows left in d_aux for the next row-based call
     // azimuthal Fourier modes (psfmc_set_fourier_layout, psfmc_general.h); nothing is allocated and no kernel changes
     // until a field registers modes.  aux_base = 2 n_sky + n_sersic; aux_stride grows to aux_base + 12 n_sersic
@@ -1301,6 +1309,7 @@ static int ctx_create_impl(psfmc_ctx** out, int device, int n_fields, const int*
     c->embed = embed; c->wraps = wraps;
     c->n_fields = n_fields; c->n_psf_field = n_psf;
     c->acc_more.assign(n_fields - 1, 0);
+    c->aux_records.resize(n_fields);
     c->n_psf = n_fields * n_psf; c->n_ps = n_ps; c->n_sersic = n_sersic;
     c->max_walkers = max_walkers; c->backend = backend;
     c->rlen = row_len(n_ps, n_sersic);
@@ -1593,6 +1602,7 @@ extern "C" double psfmc_get_option(const psfmc_ctx* cc, const char* key) {
     if (!strcmp(key, "exclusive")) return c->exclusive;
     if (!strcmp(key, "cols3")) return c->cols3;
     if (!strcmp(key, "linear_accumulation")) return c->linear_acc ? 1.0 : 0.0;
+    if (!strcmp(key, "aux_stride")) return c->aux_stride;  // doubles per walker of the auxiliary vectors (0: none yet)
     return NAN;
 }
 
@@ -2053,39 +2063,111 @@ extern "C" int psfmc_eval_images_field(psfmc_ctx* c, int field, int W, const dou
 // ---------------------------------------------------------------------------
 // raw-vector path
 // ---------------------------------------------------------------------------
-// a field's layout or aux layout is replaced: its Fourier modes (psfmc_set_fourier_layout) go with it
-static int drop_fourier_masks(psfmc_ctx* c, int field) {
-    if (c->fou_masks.empty()) return PSFMC_OK;
-    for (int k = 0; k < c->n_sersic; ++k) c->fou_masks[(size_t)field * c->n_sersic + k] = 0;
-    bool any = false;
-    for (uint8_t m : c->fou_masks) any = any || (m & kFouModeBits);
-    if (c->d_fou_masks)
-        HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), c->fou_masks.size(), hipMemcpyHostToDevice));
-    c->fou_any = any;
+// The blocks behind a field's base aux entries (psfmc_aux_table.h), in table order: what the context keeps for each,
+// how a registration's per-Sersic tag becomes the mask byte the kernels read, and its name in messages.
+struct AuxBlockFacts {
+    const char *name, *what, *excl;      // psfmc_set_<name>_layout; "components that have <what>"; "<excl> and integrate"
+    std::vector<uint8_t>& masks;         // [n_fields][n_sersic]; empty until the context meets the block
+    uint8_t*& d_masks;
+    double*& d_par;                      // [max_walkers][n_sersic][par] (+ 1)
+    bool& any;
+    int par;
+    int flag, deg_bit;                   // mask byte: flag (0: the tag itself) | deg_bit where the angles are in degrees
+    int any_bits;                        // the bits of a mask byte that say "registered"
+    int first;                           // a context with this block carries the buffers of blocks first ... this one
+};
+static AuxBlockFacts aux_block(psfmc_ctx* c, int b) {
+    if (b == kBlkFou)
+        return {"fourier", "modes", "fourier", c->fou_masks, c->d_fou_masks, c->d_fou_par, c->fou_any, kFouPar,
+                0, kFouDegrees, kFouModeBits, kBlkFou};
+    if (b == kBlkSpi)
+        return {"spiral", "a spiral", "spiral", c->spi_masks, c->d_spi_masks, c->d_spi_par, c->spi_any, kSpiPar,
+                kSpiFlag, kSpiDegrees, kSpiFlag, kBlkSpi};
+    return {"radial", "a radial law", "a radial law", c->rad_kinds, c->d_rad_kinds, c->d_rad_par, c->rad_any, kRadPar,
+            0, 0, 0xff, kBlkFou};
+}
+
+// no launch may read the tables, flags and masks a layout call replaces
+static int layout_sync(psfmc_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    c->joint.ready = false;                  // (the joint layouts are copies of the fields' layouts)
     return PSFMC_OK;
 }
 
-// ... and so do its spirals (psfmc_set_spiral_layout)
-static int drop_spiral_masks(psfmc_ctx* c, int field) {
-    if (c->spi_masks.empty()) return PSFMC_OK;
-    for (int k = 0; k < c->n_sersic; ++k) c->spi_masks[(size_t)field * c->n_sersic + k] = 0;
-    bool any = false;
-    for (uint8_t m : c->spi_masks) any = any || (m & kSpiFlag);
-    if (c->d_spi_masks)
-        HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), c->spi_masks.size(), hipMemcpyHostToDevice));
-    c->spi_any = any;
+// field `field`'s rows of the blocks' mask arrays from its record, the any-bits and the device copies where they
+// exist.  `touched`: the block this call registers; the context has its mask array from then on.
+static int write_block_masks(psfmc_ctx* c, int field, int touched = -1) {
+    const FieldAuxRecord& r = c->aux_records[field];
+    const size_t n_ser = c->n_sersic;
+    for (int b = 0; b < kAuxBlocks; ++b) {
+        AuxBlockFacts k = aux_block(c, b);
+        if (b == touched && k.masks.empty()) k.masks.assign((size_t)c->n_fields * n_ser, 0);
+        if (k.masks.empty()) continue;
+        const std::vector<int>& tags = r.block[b].tags;
+        for (size_t i = 0; i < n_ser; ++i) {
+            const int t = tags.empty() ? 0 : tags[i];
+            k.masks[(size_t)field * n_ser + i] =
+                (uint8_t)(t ? ((k.flag ? k.flag : t) | (r.sersic_degrees[i] ? k.deg_bit : 0)) : 0);
+        }
+        bool any = false;
+        for (uint8_t m : k.masks) any = any || (m & k.any_bits);
+        if (k.d_masks) HIP_TRY(hipMemcpy(k.d_masks, k.masks.data(), k.masks.size(), hipMemcpyHostToDevice));
+        k.any = any;
+    }
     return PSFMC_OK;
 }
 
-// ... and so do its radial laws (psfmc_set_radial_layout)
-static int drop_radial_kinds(psfmc_ctx* c, int field) {
-    if (c->rad_kinds.empty()) return PSFMC_OK;
-    for (int k = 0; k < c->n_sersic; ++k) c->rad_kinds[(size_t)field * c->n_sersic + k] = 0;
-    bool any = false;
-    for (uint8_t m : c->rad_kinds) any = any || m;
-    if (c->d_rad_kinds)
-        HIP_TRY(hipMemcpy(c->d_rad_kinds, c->rad_kinds.data(), c->rad_kinds.size(), hipMemcpyHostToDevice));
-    c->rad_any = any;
+// Make field `field`'s record live: its table composed afresh (psfmc_aux_table.h) in a new blob, the layout's counts
+// and pointers, the mask rows, and -- the first time the context needs them -- longer auxiliary vectors (the entries
+// they hold keep their places; aux_stride only grows) and the blocks' masks and parameter buffers, all clear.
+static int apply_aux_record(psfmc_ctx* c, int field, int touched = -1) {
+    RC_TRY(layout_sync(c));
+    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const FieldAuxRecord& r = c->aux_records[field];
+    const AuxTable t = compose_aux_table(r, L.n_sky, c->n_sersic);
+    void* fresh = nullptr;
+    if (t.n_aux) {
+        // konst first (8-byte units), then col and, behind the columns, the kinds
+        const size_t cb = t.konst.size() * sizeof(double), ib = t.col.size() * sizeof(int);
+        std::vector<unsigned char> blob(cb + ib + t.kinds.size() * sizeof(int));
+        memcpy(blob.data(), t.konst.data(), cb);
+        memcpy(blob.data() + cb, t.col.data(), ib);
+        if (!t.kinds.empty()) memcpy(blob.data() + cb + ib, t.kinds.data(), t.kinds.size() * sizeof(int));
+        HIP_TRY(hipMalloc(&fresh, blob.size()));
+        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    }
+    if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
+    if (c->aux_blobs[field]) (void)hipFree(c->aux_blobs[field]);
+    c->aux_blobs[field] = fresh;
+    L.n_aux = t.n_aux; L.n_fou = t.n_fou; L.n_spi = t.n_spi; L.n_rad = t.n_rad;
+    L.aux_const = static_cast<const double*>(fresh);
+    L.aux_col = fresh ? reinterpret_cast<const int*>(L.aux_const + t.n_aux) : nullptr;
+    L.rad_kind = t.kinds.empty() ? nullptr : L.aux_col + t.n_aux;
+    if (c->n_fields > 1 && c->d_field_layouts)
+        HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
+    if (t.n_aux > c->aux_stride) {           // (a table index is the entry's place in the walker's vector)
+        double* longer = nullptr;
+        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * t.n_aux * sizeof(double)));
+        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * t.n_aux * sizeof(double)));
+        if (c->d_aux) (void)hipFree(c->d_aux);
+        c->d_aux = longer;
+        c->aux_stride = t.n_aux;
+    }
+    const size_t n_masks = (size_t)c->n_fields * c->n_sersic;
+    for (int b = 0; b < kAuxBlocks; ++b)
+        for (int j = aux_block(c, b).first; !r.block[b].empty() && j <= b; ++j) {
+            AuxBlockFacts k = aux_block(c, j);
+            if (k.d_masks) continue;
+            const size_t par_bytes = ((size_t)c->max_walkers * c->n_sersic * k.par + 1) * sizeof(double);
+            if (k.masks.empty()) k.masks.assign(n_masks, 0);
+            HIP_TRY(hipMalloc(&k.d_masks, n_masks));
+            HIP_TRY(hipMalloc(&k.d_par, par_bytes));
+            HIP_TRY(hipMemset(k.d_par, 0, par_bytes));
+        }
+    RC_TRY(write_block_masks(c, field, touched));
+    c->aux_rows_w = -1;
+    c->prep_tabs_valid = false;              // records written under the old flags and masks are not to be rasterised
     return PSFMC_OK;
 }
 
@@ -2112,9 +2194,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     for (int i = 0; i < n_params; ++i)
         if (family[i] < 0 || family[i] > PRIOR_RANDINT)
             return fail(PSFMC_EINVAL, "unknown prior family %d for column %d", family[i], i);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
-    c->joint.ready = false;                  // (the joint layouts are copies of the fields' layouts)
+    RC_TRY(layout_sync(c));
     // pack everything into one device allocation (8-byte units)
     const size_t n_int = (size_t)ns + c->n_ps + c->n_sersic + n_params;
     const size_t n_dbl = (size_t)ns + 5 * (size_t)n_params;         // slot constants, pa, pb, pc, pd (0 here), pk
@@ -2145,18 +2225,18 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     const int* dip = reinterpret_cast<const int*>(*blob_slot);
     const double* ddp = reinterpret_cast<const double*>(static_cast<unsigned char*>(*blob_slot) + int_bytes);
     ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again, and no modes, spirals
+    // or laws: the record keeps only the degrees)
+    L = ThetaLayout{};
+    c->aux_records[field] = FieldAuxRecord{};
+    c->aux_records[field].sersic_degrees.assign(sersic_degrees, sersic_degrees + c->n_sersic);
     L.n_sky = n_sky; L.n_ps = c->n_ps; L.n_sersic = c->n_sersic; L.n_params = n_params; L.n_psf = c->n_psf_field;
     L.mag_zp = mag_zeropoint;
     L.slot_col = dip; L.ps_method = dip + ns; L.sersic_deg = dip + ns + c->n_ps;
     L.family = dip + ns + c->n_ps + c->n_sersic;
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
-    // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again)
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
-    L.n_rad = 0; L.rad_kind = nullptr;
-    RC_TRY(drop_fourier_masks(c, field));
-    RC_TRY(drop_spiral_masks(c, field));
-    RC_TRY(drop_radial_kinds(c, field));
+    RC_TRY(write_block_masks(c, field));
     if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
     if (!c->gen_flags.empty()) {
         const size_t n_ser = c->n_sersic, n_sk = c->aux_n_sky;
@@ -2281,9 +2361,13 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     if (c->d_aux && n_aux && (want != c->aux_base || L.n_sky != c->aux_n_sky))
         return fail(PSFMC_EINVAL, "n_aux=%d: the context's auxiliary vectors were allocated with %d values per walker",
                     n_aux, c->aux_base);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and flags being replaced
-    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
+    // (the field's modes, spirals and laws are registered after its aux layout: a new one drops them)
+    FieldAuxRecord& r = c->aux_records[field];
+    r.base_col.assign(aux_col, aux_col + n_aux);
+    r.base_const.assign(aux_const, aux_const + n_aux);
+    for (AuxBlockRecord& blk : r.block) blk.clear();
+    const bool first = n_aux && !c->d_aux;             // (every layout with n_aux > 0 writes aux vectors)
+    RC_TRY(apply_aux_record(c, field));
     const int n_sky = L.n_sky, n_ser = c->n_sersic;
     const size_t n_flags = (size_t)c->n_fields * (n_ser + n_sky);
     if (c->gen_flags.size() != n_flags) c->gen_flags.assign(n_flags, 0);
@@ -2293,41 +2377,16 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     for (int k = 0; k < n_sky; ++k) sky_fl[k] = n_aux && sky_slope_flags[k] ? 1 : 0;
     bool any = false;
     for (uint8_t f : c->gen_flags) any = any || f;
-    if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
-    if (c->aux_blobs[field]) { (void)hipFree(c->aux_blobs[field]); c->aux_blobs[field] = nullptr; }
-    L.n_aux = 0; L.aux_col = nullptr; L.aux_const = nullptr; L.n_fou = 0; L.n_spi = 0;
-    L.n_rad = 0; L.rad_kind = nullptr;
-    RC_TRY(drop_fourier_masks(c, field));                // (the field's modes are registered after its aux layout)
-    RC_TRY(drop_spiral_masks(c, field));                 // (and so is its spiral)
-    RC_TRY(drop_radial_kinds(c, field));                 // (and so are its radial laws)
-    if (n_aux) {
-        // aux_const first (8-byte units), then aux_col
-        std::vector<unsigned char> blob((size_t)n_aux * (sizeof(double) + sizeof(int)));
-        memcpy(blob.data(), aux_const, (size_t)n_aux * sizeof(double));
-        memcpy(blob.data() + (size_t)n_aux * sizeof(double), aux_col, (size_t)n_aux * sizeof(int));
-        HIP_TRY(hipMalloc(&c->aux_blobs[field], blob.size()));
-        HIP_TRY(hipMemcpy(c->aux_blobs[field], blob.data(), blob.size(), hipMemcpyHostToDevice));
-        L.n_aux = n_aux;
-        L.aux_const = static_cast<const double*>(c->aux_blobs[field]);
-        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(c->aux_blobs[field]) +
-                                                 (size_t)n_aux * sizeof(double));
-    }
-    if (c->n_fields > 1 && c->d_field_layouts)
-        HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
-    if (n_aux && !c->d_aux) {                          // (every layout with n_aux > 0 writes aux vectors)
-        c->aux_stride = c->aux_base = want;
+    if (first) {
+        c->aux_base = want;
         c->aux_n_sky = n_sky;
         HIP_TRY(hipMalloc(&c->d_gen_flags, n_flags));
         HIP_TRY(hipMalloc(&c->d_gen_par, ((size_t)c->max_walkers * n_ser * kGenPar + 1) * sizeof(double)));
-        HIP_TRY(hipMalloc(&c->d_aux, (size_t)c->max_walkers * want * sizeof(double)));
-        HIP_TRY(hipMemset(c->d_aux, 0, (size_t)c->max_walkers * want * sizeof(double)));
     }
     if (any) RC_TRY(ensure_extra_images(c, "general-component"));
     if (c->d_gen_flags)
         HIP_TRY(hipMemcpy(c->d_gen_flags, c->gen_flags.data(), n_flags, hipMemcpyHostToDevice));
     c->gen_any = any;
-    c->aux_rows_w = -1;
-    c->prep_tabs_valid = false;                        // records written under the old flags are not to be rasterised
     return PSFMC_OK;
 }
 
@@ -2344,305 +2403,91 @@ extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
 }
 
 static_assert(kFouModes == PSFMC_FOURIER_MODES, "mode count of include/psfmc_hip.h");
+static_assert(kSpiIn == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
+static_assert(kRadIn == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
+// psfmc_set_fourier_layout, _spiral_layout and _radial_layout: block b of field `field` with its per-Sersic tags.
+// Everything is checked before the record changes, so a refused call leaves the field as it was.
+static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const int* tags, const int* col,
+                            const double* konst) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    const AuxBlockFacts k = aux_block(c, b);
+    if (n_sersic && (!tags || !col || !konst)) return fail(PSFMC_EINVAL, "NULL %s array", k.name);
+    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
+    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    const ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    FieldAuxRecord& r = c->aux_records[field];
+    bool any_here = false;
+    for (int i = 0; i < n_sersic; ++i) {
+        if (b == kBlkFou && (tags[i] & ~kFouModeBits))
+            return fail(PSFMC_EINVAL, "Sersic %d: mode mask 0x%x names a mode outside 1 ... %d", i, tags[i], kFouModes);
+        if (b == kBlkRad && (tags[i] < 0 || tags[i] > kRadFerrer))
+            return fail(PSFMC_EINVAL, "Sersic %d: radial kind %d outside 0 ... %d", i, tags[i], kRadFerrer);
+        any_here = any_here || tags[i];
+    }
+    if (any_here && r.base_col.empty())
+        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
+                    "%s flagged general) before psfmc_set_%s_layout", field, k.what, k.name);
+    for (int i = 0; i < n_sersic; ++i) {
+        if (!tags[i]) continue;
+        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + i])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: %s and integrate exclude each other", i,
+                        field, k.excl);
+        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + i])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d has %s but is not flagged general in the field's aux layout",
+                        i, field, k.what);
+    }
+    const int len = aux_block_len(b, n_sersic);
+    for (int j = 0; any_here && j < len; ++j)
+        if (col[j] < -1 || col[j] >= L.n_params)
+            return fail(PSFMC_EINVAL, "%s value %d refers to column %d of %d", k.name, j, col[j], L.n_params);
+    // (a field's blocks are registered in table order: a call drops the blocks behind its own with their entries)
+    bool behind = false;
+    for (int j = b + 1; j < kAuxBlocks; ++j) behind = behind || !r.block[j].empty();
+    if (!any_here && k.masks.empty() && !behind) return layout_sync(c);    // (nothing registered, nothing to remove)
+    r.block[b].store(n_sersic, len, tags, col, konst);
+    for (int j = b + 1; j < kAuxBlocks; ++j) r.block[j].clear();
+    return apply_aux_record(c, field, b);
+}
+
 extern "C" int psfmc_set_fourier_layout(psfmc_ctx* c, int field, int n_sersic, const int* mode_mask, const int* col,
                                         const double* konst) {
-    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
-    if (n_sersic && (!mode_mask || !col || !konst)) return fail(PSFMC_EINVAL, "NULL fourier array");
-    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    // (a field's spiral is registered after its modes: a Fourier layout drops it with the entries it had)
-    const int n_base = L.n_aux - L.n_fou - L.n_spi - L.n_rad, n_fou = fourier_len(n_sersic);
-    bool any_here = false;
-    for (int k = 0; k < n_sersic; ++k) {
-        if (mode_mask[k] & ~kFouModeBits)
-            return fail(PSFMC_EINVAL, "Sersic %d: mode mask 0x%x names a mode outside 1 ... %d", k, mode_mask[k], kFouModes);
-        any_here = any_here || mode_mask[k];
-    }
-    if (any_here && n_base <= 0)
-        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
-                    "modes flagged general) before psfmc_set_fourier_layout", field);
-    for (int k = 0; k < n_sersic; ++k) {
-        if (!mode_mask[k]) continue;
-        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: fourier and integrate exclude each other",
-                        k, field);
-        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d has modes but is not flagged general in the field's aux "
-                        "layout", k, field);
-    }
-    for (int j = 0; any_here && j < n_fou; ++j)
-        if (col[j] < -1 || col[j] >= L.n_params)
-            return fail(PSFMC_EINVAL, "fourier value %d refers to column %d of %d", j, col[j], L.n_params);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
-    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
-    if (!any_here && c->fou_masks.empty() && !L.n_spi) return PSFMC_OK;    // (nothing registered, nothing to remove)
-    RC_TRY(drop_spiral_masks(c, field));
-    RC_TRY(drop_radial_kinds(c, field));               // (a field's laws are registered last of all)
-    L.n_spi = 0;
-    L.n_rad = 0; L.rad_kind = nullptr;
-    if (n_base > 0) {
-        // the field's table again: its aux entries as they are, then (with modes) the Fourier entries
-        std::vector<double> cst((size_t)n_base + (any_here ? n_fou : 0));
-        std::vector<int> cl(cst.size());
-        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_base * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_base * sizeof(int), hipMemcpyDeviceToHost));
-        for (int j = 0; any_here && j < n_fou; ++j) {
-            cst[(size_t)n_base + j] = konst[j];
-            cl[(size_t)n_base + j] = col[j];
-        }
-        const size_t n_all = cst.size();
-        std::vector<unsigned char> blob(n_all * (sizeof(double) + sizeof(int)));
-        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
-        memcpy(blob.data() + n_all * sizeof(double), cl.data(), n_all * sizeof(int));
-        void* fresh = nullptr;
-        HIP_TRY(hipMalloc(&fresh, blob.size()));
-        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        (void)hipFree(c->aux_blobs[field]);
-        c->aux_blobs[field] = fresh;
-        L.n_aux = (int)n_all;
-        L.n_fou = any_here ? n_fou : 0;
-        L.aux_const = static_cast<const double*>(fresh);
-        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
-        if (c->n_fields > 1 && c->d_field_layouts)
-            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
-    }
-    if (c->fou_masks.empty()) c->fou_masks.assign((size_t)c->n_fields * n_sersic, 0);
-    std::vector<int> deg(n_sersic > 0 ? n_sersic : 1, 0);
-    if (any_here) HIP_TRY(hipMemcpy(deg.data(), L.sersic_deg, (size_t)n_sersic * sizeof(int), hipMemcpyDeviceToHost));
-    for (int k = 0; k < n_sersic; ++k)
-        c->fou_masks[(size_t)field * n_sersic + k] =
-            (uint8_t)(mode_mask[k] ? (mode_mask[k] | (deg[k] ? kFouDegrees : 0)) : 0);
-    if (any_here && !c->d_fou_masks) {
-        // the first modes of the context: longer auxiliary vectors (the aux entries keep their places), the
-        // components' mode blocks and the masks
-        const int stride = c->aux_stride > c->aux_base + n_fou ? c->aux_stride : c->aux_base + n_fou;
-        double* longer = nullptr;
-        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
-        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
-        (void)hipFree(c->d_aux);
-        c->d_aux = longer;
-        c->aux_stride = stride;
-        HIP_TRY(hipMalloc(&c->d_fou_masks, c->fou_masks.size()));
-        HIP_TRY(hipMalloc(&c->d_fou_par, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
-        HIP_TRY(hipMemset(c->d_fou_par, 0, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
-    }
-    bool any = false;
-    for (uint8_t m : c->fou_masks) any = any || (m & kFouModeBits);
-    if (c->d_fou_masks)
-        HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), c->fou_masks.size(), hipMemcpyHostToDevice));
-    c->fou_any = any;
-    c->aux_rows_w = -1;
-    c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
-    return PSFMC_OK;
+    return set_block_layout(c, kBlkFou, field, n_sersic, mode_mask, col, konst);
 }
 
-static_assert(kSpiIn == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
 extern "C" int psfmc_set_spiral_layout(psfmc_ctx* c, int field, int n_sersic, const int* flags, const int* col,
                                        const double* konst) {
-    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
-    if (n_sersic && (!flags || !col || !konst)) return fail(PSFMC_EINVAL, "NULL spiral array");
-    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    // (a field's radial laws are registered after its spiral: a spiral layout drops them with the entries they had)
-    const int n_keep = L.n_aux - L.n_spi - L.n_rad, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
-    bool any_here = false;
-    for (int k = 0; k < n_sersic; ++k) any_here = any_here || flags[k];
-    if (any_here && n_keep <= 0)
-        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
-                    "a spiral flagged general) before psfmc_set_spiral_layout", field);
-    for (int k = 0; k < n_sersic; ++k) {
-        if (!flags[k]) continue;
-        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: spiral and integrate exclude each other",
-                        k, field);
-        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d has a spiral but is not flagged general in the field's aux "
-                        "layout", k, field);
-    }
-    for (int j = 0; any_here && j < n_spi; ++j)
-        if (col[j] < -1 || col[j] >= L.n_params)
-            return fail(PSFMC_EINVAL, "spiral value %d refers to column %d of %d", j, col[j], L.n_params);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and masks being replaced
-    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
-    if (!any_here && c->spi_masks.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
-    RC_TRY(drop_radial_kinds(c, field));
-    L.n_rad = 0; L.rad_kind = nullptr;
-    if (n_keep > 0) {
-        // the field's table again: its aux and Fourier entries as they are -- a field without modes gets the empty
-        // Fourier block, so that a table index is the entry's place in the walker's vector -- then the spiral entries
-        const int n_pad = any_here && !L.n_fou ? n_fou : 0;
-        std::vector<double> cst((size_t)n_keep + n_pad + (any_here ? n_spi : 0), 0.0);
-        std::vector<int> cl(cst.size(), -1);
-        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_keep * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_keep * sizeof(int), hipMemcpyDeviceToHost));
-        for (int j = 0; any_here && j < n_spi; ++j) {
-            cst[(size_t)n_keep + n_pad + j] = konst[j];
-            cl[(size_t)n_keep + n_pad + j] = col[j];
-        }
-        const size_t n_all = cst.size();
-        std::vector<unsigned char> blob(n_all * (sizeof(double) + sizeof(int)));
-        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
-        memcpy(blob.data() + n_all * sizeof(double), cl.data(), n_all * sizeof(int));
-        void* fresh = nullptr;
-        HIP_TRY(hipMalloc(&fresh, blob.size()));
-        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        (void)hipFree(c->aux_blobs[field]);
-        c->aux_blobs[field] = fresh;
-        L.n_aux = (int)n_all;
-        L.n_fou += n_pad;
-        L.n_spi = any_here ? n_spi : 0;
-        L.aux_const = static_cast<const double*>(fresh);
-        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
-        if (c->n_fields > 1 && c->d_field_layouts)
-            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
-    }
-    if (c->spi_masks.empty()) c->spi_masks.assign((size_t)c->n_fields * n_sersic, 0);
-    std::vector<int> deg(n_sersic > 0 ? n_sersic : 1, 0);
-    if (any_here) HIP_TRY(hipMemcpy(deg.data(), L.sersic_deg, (size_t)n_sersic * sizeof(int), hipMemcpyDeviceToHost));
-    for (int k = 0; k < n_sersic; ++k)
-        c->spi_masks[(size_t)field * n_sersic + k] = (uint8_t)(flags[k] ? (kSpiFlag | (deg[k] ? kSpiDegrees : 0)) : 0);
-    if (any_here && !c->d_spi_masks) {
-        // the first spiral of the context: longer auxiliary vectors (the aux and Fourier entries keep their places),
-        // the components' constants and the masks
-        const int stride = c->aux_stride > c->aux_base + n_fou + n_spi ? c->aux_stride : c->aux_base + n_fou + n_spi;
-        double* longer = nullptr;
-        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
-        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
-        (void)hipFree(c->d_aux);
-        c->d_aux = longer;
-        c->aux_stride = stride;
-        HIP_TRY(hipMalloc(&c->d_spi_masks, c->spi_masks.size()));
-        HIP_TRY(hipMalloc(&c->d_spi_par, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
-        HIP_TRY(hipMemset(c->d_spi_par, 0, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
-    }
-    bool any = false;
-    for (uint8_t m : c->spi_masks) any = any || (m & kSpiFlag);
-    if (c->d_spi_masks)
-        HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), c->spi_masks.size(), hipMemcpyHostToDevice));
-    c->spi_any = any;
-    c->aux_rows_w = -1;
-    c->prep_tabs_valid = false;                        // records written under the old masks are not to be rasterised
-    return PSFMC_OK;
+    return set_block_layout(c, kBlkSpi, field, n_sersic, flags, col, konst);
 }
 
-static_assert(kRadIn == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
 extern "C" int psfmc_set_radial_layout(psfmc_ctx* c, int field, int n_sersic, const int* kinds, const int* col,
                                        const double* konst) {
-    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
-    if (n_sersic && (!kinds || !col || !konst)) return fail(PSFMC_EINVAL, "NULL radial array");
-    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
-    const int n_keep = L.n_aux - L.n_rad, n_fou = fourier_len(n_sersic), n_spi = spiral_len(n_sersic);
-    const int n_rad = radial_len(n_sersic);
-    bool any_here = false;
-    for (int k = 0; k < n_sersic; ++k) {
-        if (kinds[k] < 0 || kinds[k] > kRadFerrer)
-            return fail(PSFMC_EINVAL, "Sersic %d: radial kind %d outside 0 ... %d", k, kinds[k], kRadFerrer);
-        any_here = any_here || kinds[k];
+    return set_block_layout(c, kBlkRad, field, n_sersic, kinds, col, konst);
+}
+
+extern "C" int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                                     const int* mode_mask, const int* fou_col, const double* fou_const,
+                                     const int* spi_flags, const int* spi_col, const double* spi_const,
+                                     const int* rad_kinds, const int* rad_col, const double* rad_const,
+                                     double* out_const, int* out_col, int* out_kinds, int* counts) {
+    if (n_sky < 0 || n_sersic < 0 || !out_const || !out_col || !out_kinds || !counts)
+        return fail(PSFMC_EINVAL, "bad counts or NULL output");
+    FieldAuxRecord r;
+    if (base_col && base_const) {
+        r.base_col.assign(base_col, base_col + aux_len(n_sky, n_sersic));
+        r.base_const.assign(base_const, base_const + aux_len(n_sky, n_sersic));
     }
-    if (any_here && n_keep <= 0)
-        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the components that have "
-                    "a radial law flagged general) before psfmc_set_radial_layout", field);
-    for (int k = 0; k < n_sersic; ++k) {
-        if (!kinds[k]) continue;
-        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: a radial law and integrate exclude each "
-                        "other", k, field);
-        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
-            return fail(PSFMC_EINVAL, "Sersic %d of field %d has a radial law but is not flagged general in the field's "
-                        "aux layout", k, field);
-    }
-    for (int j = 0; any_here && j < n_rad; ++j)
-        if (col[j] < -1 || col[j] >= L.n_params)
-            return fail(PSFMC_EINVAL, "radial value %d refers to column %d of %d", j, col[j], L.n_params);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());                   // no launch may read the tables and kinds being replaced
-    c->joint.ready = false;                            // (the joint layouts are copies of the fields' layouts)
-    if (!any_here && c->rad_kinds.empty()) return PSFMC_OK;            // (nothing registered, nothing to remove)
-    if (n_keep > 0) {
-        // the field's table again: its aux, Fourier and spiral entries as they are -- a field without modes gets the
-        // empty Fourier block, one without a spiral constants inside the spiral's support that are never read, so that
-        // a table index is the entry's place in the walker's vector -- then the laws' entries and, behind the columns,
-        // the kinds
-        const int pad_fou = any_here && !L.n_fou ? n_fou : 0, pad_spi = any_here && !L.n_spi ? n_spi : 0;
-        const size_t n_all = (size_t)n_keep + pad_fou + pad_spi + (any_here ? n_rad : 0);
-        std::vector<double> cst(n_all, 0.0);
-        std::vector<int> cl(n_all + (any_here ? n_sersic : 0), -1);
-        HIP_TRY(hipMemcpy(cst.data(), L.aux_const, (size_t)n_keep * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cl.data(), L.aux_col, (size_t)n_keep * sizeof(int), hipMemcpyDeviceToHost));
-        for (int k = 0; k < (pad_spi ? n_sersic : 0); ++k) cst[(size_t)n_keep + pad_fou + kSpiIn * k + 1] = 1.0;   // r_out
-        for (int j = 0; any_here && j < n_rad; ++j) {
-            cst[(size_t)n_keep + pad_fou + pad_spi + j] = konst[j];
-            cl[(size_t)n_keep + pad_fou + pad_spi + j] = col[j];
-        }
-        for (int k = 0; any_here && k < n_sersic; ++k) cl[n_all + k] = kinds[k];
-        std::vector<unsigned char> blob(n_all * sizeof(double) + cl.size() * sizeof(int));
-        memcpy(blob.data(), cst.data(), n_all * sizeof(double));
-        memcpy(blob.data() + n_all * sizeof(double), cl.data(), cl.size() * sizeof(int));
-        void* fresh = nullptr;
-        HIP_TRY(hipMalloc(&fresh, blob.size()));
-        HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        (void)hipFree(c->aux_blobs[field]);
-        c->aux_blobs[field] = fresh;
-        L.n_aux = (int)n_all;
-        L.n_fou += pad_fou;
-        L.n_spi += pad_spi;
-        L.n_rad = any_here ? n_rad : 0;
-        L.aux_const = static_cast<const double*>(fresh);
-        L.aux_col = reinterpret_cast<const int*>(static_cast<unsigned char*>(fresh) + n_all * sizeof(double));
-        L.rad_kind = any_here ? L.aux_col + n_all : nullptr;
-        if (c->n_fields > 1 && c->d_field_layouts)
-            HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
-    }
-    if (c->rad_kinds.empty()) c->rad_kinds.assign((size_t)c->n_fields * n_sersic, 0);
-    for (int k = 0; k < n_sersic; ++k) c->rad_kinds[(size_t)field * n_sersic + k] = (uint8_t)kinds[k];
-    if (any_here && !c->d_rad_kinds) {
-        // the first law of the context: longer auxiliary vectors (the entries they hold keep their places), the laws'
-        // constants and kinds, and what a context with modes and spirals has, all clear, where it is missing
-        const size_t n_masks = (size_t)c->n_fields * n_sersic;
-        const int stride = c->aux_base + n_fou + n_spi + n_rad;
-        double* longer = nullptr;
-        HIP_TRY(hipMalloc(&longer, (size_t)c->max_walkers * stride * sizeof(double)));
-        HIP_TRY(hipMemset(longer, 0, (size_t)c->max_walkers * stride * sizeof(double)));
-        (void)hipFree(c->d_aux);
-        c->d_aux = longer;
-        c->aux_stride = stride;
-        if (c->fou_masks.empty()) c->fou_masks.assign(n_masks, 0);
-        if (!c->d_fou_masks) {
-            HIP_TRY(hipMalloc(&c->d_fou_masks, n_masks));
-            HIP_TRY(hipMemcpy(c->d_fou_masks, c->fou_masks.data(), n_masks, hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc(&c->d_fou_par, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
-            HIP_TRY(hipMemset(c->d_fou_par, 0, ((size_t)c->max_walkers * n_sersic * kFouPar + 1) * sizeof(double)));
-        }
-        if (c->spi_masks.empty()) c->spi_masks.assign(n_masks, 0);
-        if (!c->d_spi_masks) {
-            HIP_TRY(hipMalloc(&c->d_spi_masks, n_masks));
-            HIP_TRY(hipMemcpy(c->d_spi_masks, c->spi_masks.data(), n_masks, hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc(&c->d_spi_par, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
-            HIP_TRY(hipMemset(c->d_spi_par, 0, ((size_t)c->max_walkers * n_sersic * kSpiPar + 1) * sizeof(double)));
-        }
-        HIP_TRY(hipMalloc(&c->d_rad_kinds, n_masks));
-        HIP_TRY(hipMalloc(&c->d_rad_par, ((size_t)c->max_walkers * n_sersic * kRadPar + 1) * sizeof(double)));
-        HIP_TRY(hipMemset(c->d_rad_par, 0, ((size_t)c->max_walkers * n_sersic * kRadPar + 1) * sizeof(double)));
-    }
-    bool any = false;
-    for (uint8_t m : c->rad_kinds) any = any || m;
-    if (c->d_rad_kinds)
-        HIP_TRY(hipMemcpy(c->d_rad_kinds, c->rad_kinds.data(), c->rad_kinds.size(), hipMemcpyHostToDevice));
-    c->rad_any = any;
-    c->aux_rows_w = -1;
-    c->prep_tabs_valid = false;                        // records written under the old kinds are not to be rasterised
+    const int* tags[kAuxBlocks] = {mode_mask, spi_flags, rad_kinds};
+    const int* col[kAuxBlocks] = {fou_col, spi_col, rad_col};
+    const double* konst[kAuxBlocks] = {fou_const, spi_const, rad_const};
+    for (int b = 0; b < kAuxBlocks; ++b)
+        if (tags[b] && col[b] && konst[b]) r.block[b].store(n_sersic, aux_block_len(b, n_sersic), tags[b], col[b], konst[b]);
+    const AuxTable t = compose_aux_table(r, n_sky, n_sersic);
+    std::copy(t.konst.begin(), t.konst.end(), out_const);
+    std::copy(t.col.begin(), t.col.end(), out_col);
+    std::copy(t.kinds.begin(), t.kinds.end(), out_kinds);
+    counts[0] = t.n_aux; counts[1] = t.n_fou; counts[2] = t.n_spi; counts[3] = t.n_rad;
     return PSFMC_OK;
 }
 

@@ -283,6 +283,8 @@ def load_library():
     lib.psfmc_group_eval_theta.argtypes = [vp, ci, _c_double_p, _c_double_p, _c_double_p]
     lib.psfmc_debug_math.restype = ci
     lib.psfmc_debug_math.argtypes = [ci, ci, ci, _c_double_p, _c_double_p]
+    lib.psfmc_debug_aux_table.restype = ci
+    lib.psfmc_debug_aux_table.argtypes = [ci, ci, ip, _c_double_p] + 3 * [ip, ip, _c_double_p] + [_c_double_p, ip, ip, ip]
     lib.psfmc_debug_sweep.restype = ci
     lib.psfmc_debug_sweep.argtypes = [ci, ci, ctypes.c_size_t, ci, _c_double_p]
     lib.psfmc_debug_valu_rate.restype = ci
@@ -329,45 +331,26 @@ def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
 
 
 FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude and a phase entry each
-
-
-def _fourier_layout_args(mode_masks, col, const):
-    """The arrays of psfmc_set_fourier_layout (kept alive by the caller's tuple) and their ctypes pointers."""
-    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
-    mask, col, const = i32(mode_masks), i32(col), _f64(const).ravel()
-    if len(col) != len(const) or len(col) != 2 * FOURIER_MODES * len(mask):
-        raise ValueError('fourier layout: {} entries per Sersic, got {} for {}'.format(
-            2 * FOURIER_MODES, len(col), len(mask)))
-    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    return (mask, col, const), (len(mask), ipt(mask), ipt(col), _dp(const))
-
-
 SPIRAL_PARAMS = 6          # PSFMC_SPIRAL_PARAMS: r_in, r_out, winding, alpha, inclination, sky angle
-
-
-def _spiral_layout_args(flags, col, const):
-    """The arrays of psfmc_set_spiral_layout (kept alive by the caller's tuple) and their ctypes pointers."""
-    i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
-    flags, col, const = i32(np.asarray(flags, dtype=bool)), i32(col), _f64(const).ravel()
-    if len(col) != len(const) or len(col) != SPIRAL_PARAMS * len(flags):
-        raise ValueError('spiral layout: {} entries per Sersic, got {} for {}'.format(
-            SPIRAL_PARAMS, len(col), len(flags)))
-    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    return (flags, col, const), (len(flags), ipt(flags), ipt(col), _dp(const))
-
-
 RADIAL_PARAMS = 2          # PSFMC_RADIAL_PARAMS: (beta, unused) of a Moffat slot, (alpha, beta) of a Ferrer slot
+# the blocks behind the aux entries: name -> (entries per Sersic, the per-Sersic tags are flags)
+_BLOCKS = {'fourier': (2 * FOURIER_MODES, False), 'spiral': (SPIRAL_PARAMS, True), 'radial': (RADIAL_PARAMS, False)}
 
 
-def _radial_layout_args(kinds, col, const):
-    """The arrays of psfmc_set_radial_layout (kept alive by the caller's tuple) and their ctypes pointers."""
+def _block_layout_args(name, per_sersic, tags, col, const, tags_are_flags):
+    """The arrays of psfmc_set_<name>_layout (kept alive by the caller's tuple) and their ctypes pointers: per
+    Sersic a tag -- mode mask, spiral flag, radial kind -- and `per_sersic` entries."""
     i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
-    kinds, col, const = i32(kinds), i32(col), _f64(const).ravel()
-    if len(col) != len(const) or len(col) != RADIAL_PARAMS * len(kinds):
-        raise ValueError('radial layout: {} entries per Sersic, got {} for {}'.format(
-            RADIAL_PARAMS, len(col), len(kinds)))
+    tags = i32(np.asarray(tags, dtype=bool) if tags_are_flags else tags)
+    col, const = i32(col), _f64(const).ravel()
+    if len(col) != len(const) or len(col) != per_sersic * len(tags):
+        raise ValueError('{} layout: {} entries per Sersic, got {} for {}'.format(name, per_sersic, len(col), len(tags)))
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    return (kinds, col, const), (len(kinds), ipt(kinds), ipt(col), _dp(const))
+    return (tags, col, const), (len(tags), ipt(tags), ipt(col), _dp(const))
+
+
+def _block_args(name, tags, col, const):
+    return _block_layout_args(name, _BLOCKS[name][0], tags, col, const, _BLOCKS[name][1])
 
 
 def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
@@ -408,6 +391,30 @@ def debug_pow_tab(values, p, device=0):
     if rc != 0:
         raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
     return out.reshape(np.shape(values))
+
+
+def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radial=None):
+    """The auxiliary table the library composes for one field (psfmc_debug_aux_table; host only, no device): base =
+    (col, const) of the aux layout, each block (tags, col, const) as its layout call takes them, None where the
+    field registered none -> (const, col, kinds, (n_aux, n_fou, n_spi, n_rad))."""
+    lib = load_library()
+    keep, args = [], [None, None]
+    if base is not None:
+        keep.append(_aux_layout_args(base[0], base[1], np.zeros(n_sky), np.zeros(n_sersic)))
+        args = list(keep[-1][1][1:3])
+    for name, block in (('fourier', fourier), ('spiral', spiral), ('radial', radial)):
+        if block is not None:
+            keep.append(_block_args(name, *block))
+        args += [None, None, None] if block is None else list(keep[-1][1][1:])
+    n_max = 2 * n_sky + (1 + sum(per for per, _ in _BLOCKS.values())) * n_sersic
+    const, col = np.full(n_max, np.nan), np.full(n_max, -2, dtype=np.int32)
+    kinds, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(4, dtype=np.int32)
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    rc = lib.psfmc_debug_aux_table(int(n_sky), int(n_sersic), *(args + [_dp(const), ipt(col), ipt(kinds), ipt(counts)]))
+    if rc != 0:
+        raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
+    n_aux = int(counts[0])
+    return const[:n_aux], col[:n_aux], kinds[:n_sersic if counts[3] else 0], tuple(int(n) for n in counts)
 
 
 def debug_sweep(mode, nbytes, reps=20, device=0):
@@ -588,21 +595,21 @@ class Context(object):
         """Azimuthal Fourier modes (psfmc_set_fourier_layout; after `set_aux_layout`): per Sersic a mask of its
         modes (bit m - 1: mode m) and, per Sersic and mode 1 ... 6, an amplitude and a phase entry -- column of theta
         or -1 and a constant.  A context that never gets the call is what it was without it."""
-        keep, args = _fourier_layout_args(mode_masks, col, const)
+        keep, args = _block_args('fourier', mode_masks, col, const)
         self._check(self._lib.psfmc_set_fourier_layout(self._ctx, 0, *args))
 
     def set_spiral_layout(self, flags, col, const):
         """Spiral arms (psfmc_set_spiral_layout; after `set_aux_layout` and `set_fourier_layout`): per Sersic a flag
         and six entries -- r_in, r_out, winding, alpha, inclination, sky angle; column of theta or -1 and a
         constant.  A context that never gets the call is what it was without it."""
-        keep, args = _spiral_layout_args(flags, col, const)
+        keep, args = _block_args('spiral', flags, col, const)
         self._check(self._lib.psfmc_set_spiral_layout(self._ctx, 0, *args))
 
     def set_radial_layout(self, kinds, col, const):
         """Radial laws (psfmc_set_radial_layout; the last of the layout calls): per Sersic slot a kind -- 0 Sersic,
         1 Moffat, 2 Ferrer -- and two entries, (beta, unused) or (alpha, beta); column of theta or -1 and a
         constant.  A context that never gets the call is what it was without it."""
-        keep, args = _radial_layout_args(kinds, col, const)
+        keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_set_radial_layout(self._ctx, 0, *args))
 
     def _theta(self, theta):
@@ -937,27 +944,18 @@ class FieldSetContext(object):
             def set_aux_layout(self, aux_col, aux_const, sky_flags, sersic_flags):
                 keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
                 owner._check(owner._lib.psfmc_set_aux_layout(owner._ctx, int(field), *args))
-                owner._aux_base = len(keep[0])
 
             def set_fourier_layout(self, mode_masks, col, const):
-                keep, args = _fourier_layout_args(mode_masks, col, const)
+                keep, args = _block_args('fourier', mode_masks, col, const)
                 owner._check(owner._lib.psfmc_set_fourier_layout(owner._ctx, int(field), *args))
-                owner._aux_fourier = len(keep[1])
 
             def set_spiral_layout(self, flags, col, const):
-                keep, args = _spiral_layout_args(flags, col, const)
+                keep, args = _block_args('spiral', flags, col, const)
                 owner._check(owner._lib.psfmc_set_spiral_layout(owner._ctx, int(field), *args))
-                # (a context with spirals carries the Fourier block, empty where no field has modes)
-                owner._aux_fourier = 2 * FOURIER_MODES * len(keep[0])
-                owner._aux_spiral = len(keep[1])
 
             def set_radial_layout(self, kinds, col, const):
-                keep, args = _radial_layout_args(kinds, col, const)
+                keep, args = _block_args('radial', kinds, col, const)
                 owner._check(owner._lib.psfmc_set_radial_layout(owner._ctx, int(field), *args))
-                # (a context with laws carries the Fourier and the spiral block, empty where no field has them)
-                owner._aux_fourier = 2 * FOURIER_MODES * len(keep[0])
-                owner._aux_spiral = SPIRAL_PARAMS * len(keep[0])
-                owner._aux_radial = len(keep[1])
         return _Proxy()
 
     @staticmethod
@@ -1104,19 +1102,17 @@ class FieldSetContext(object):
         return FieldView(self, field, columns)
 
     def _aux_width(self):
-        """Values per walker of the context's auxiliary vectors once a field registered Fourier modes or a spiral
-        (its fields' rows without them are padded to it), else None."""
-        fou = getattr(self, '_aux_fourier', 0)
-        return (getattr(self, '_aux_base', 0) + fou + getattr(self, '_aux_spiral', 0) +
-                getattr(self, '_aux_radial', 0)) if fou else None
+        """Values per walker of the context's auxiliary vectors, as the library keeps it (0: no field has an aux
+        layout yet): a field's shorter rows are padded to it."""
+        return int(self.get_option('aux_stride'))
 
     def _field_aux(self, aux, n_w):
         """The auxiliary rows of a row-based call of one field: the field's own, or -- for a field WITHOUT the keywords
         in a context where another field has them, whose model has no auxiliary vectors (`aux_rows` is None) -- zero
         rows of the context's width: the library wants rows for every row-based call of such a context, and nothing
         reads them for a field whose flags are all clear."""
-        if aux is None and getattr(self, '_aux_base', 0):
-            return np.zeros((n_w, self._aux_base + getattr(self, '_aux_fourier', 0)))
+        if aux is None and self._aux_width():
+            return np.zeros((n_w, self._aux_width()))
         return aux
 
     def loglike(self, field, rows, skip=None, aux=None):
@@ -1342,17 +1338,17 @@ class ContextGroup(object):
 
     def set_fourier_layout(self, mode_masks, col, const):
         """`Context.set_fourier_layout` on every device of the group."""
-        keep, args = _fourier_layout_args(mode_masks, col, const)
+        keep, args = _block_args('fourier', mode_masks, col, const)
         self._check(self._lib.psfmc_group_set_fourier_layout(self._grp, *args))
 
     def set_spiral_layout(self, flags, col, const):
         """`Context.set_spiral_layout` on every device of the group."""
-        keep, args = _spiral_layout_args(flags, col, const)
+        keep, args = _block_args('spiral', flags, col, const)
         self._check(self._lib.psfmc_group_set_spiral_layout(self._grp, *args))
 
     def set_radial_layout(self, kinds, col, const):
         """`Context.set_radial_layout` on every device of the group."""
-        keep, args = _radial_layout_args(kinds, col, const)
+        keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_group_set_radial_layout(self._grp, *args))
 
     def loglike(self, rows, skip=None, aux=None):

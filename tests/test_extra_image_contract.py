@@ -187,22 +187,28 @@ def test_a_field_without_keywords_gets_zero_aux_rows_in_a_shared_context(monkeyp
     from psfmc_amd import engine
 
     class Shared(object):
+        """The width is the library's (`get_option('aux_stride')`): the stand-in answers for it."""
         _field_aux = engine.FieldSetContext._field_aux
+        _aux_width = engine.FieldSetContext._aux_width
+        stride = 0.0
+
+        def get_option(self, key):
+            assert key == 'aux_stride'
+            return self.stride
     ctx = Shared()
-    assert ctx._field_aux(None, 3) is None
-    ctx._aux_base = 4
+    assert ctx._aux_width() == 0 and ctx._field_aux(None, 3) is None
+    ctx.stride = 4.0
     rows = ctx._field_aux(None, 3)
     assert rows.shape == (3, 4) and not rows.any()
-    ctx._aux_fourier = 24
+    ctx.stride = 28.0
     assert ctx._field_aux(None, 2).shape == (2, 28)
     own = np.ones((2, 4))
     assert ctx._field_aux(own, 2) is own
     # a context where fields registered spirals and laws as well: what reaches the library after `_send_aux_rows`'
     # padding has the context's full width, for a plain field's zero rows and for a modes-only field's own rows
-    Shared._aux_width = engine.FieldSetContext._aux_width
     assert ctx._aux_width() == 28
-    ctx._aux_spiral, ctx._aux_radial = 12, 4
-    assert ctx._aux_width() == 4 + 24 + 12 + 4
+    ctx.stride = 4.0 + 24 + 12 + 4
+    assert ctx._aux_width() == 44 and isinstance(ctx._aux_width(), int)
     sent = []
 
     class Library(object):
