@@ -24,7 +24,7 @@ MAG_ZP = 25.0
 PSF_SHAPE = (15, 13)
 FREE = object()
 ABSENT = object()
-KEYWORDS = ('integrate', 'boxiness', 'fourier', 'spiral', 'law')
+KEYWORDS = ('integrate', 'boxiness', 'fourier', 'spiral', 'law', 'fixed')
 THREE = {1: (FREE, FREE), 3: (FREE, 25.0), 4: (FREE, FREE)}          # one constant phase among free ones
 MODES_1_4 = {1: (FREE, FREE), 4: (FREE, FREE)}
 
@@ -116,7 +116,8 @@ def make_model(case, sersics, slope=ABSENT, backend='fused', max_walkers=8, lean
     one Sersic per entry of `sersics`, a dict with any of `integrate`, `boxiness` (FREE or a value), `fourier`
     ({m: (amplitude, phase)}, FREE or values), `spiral` ({key: FREE or a value}, `Sersic`'s keys) and `law`: 'moffat'
     or 'ferrer' -- a `Moffat` / `Ferrer` with its own argument names in the Sersic's place -- or (law, {argument: a
-    constant}) for constants among the law's own arguments.  FREE: the test's prior, a fresh object per model; those of
+    constant}) for constants among the law's own arguments; `fixed`: {argument: a constant} among a plain Sersic's
+    own (`xy`, `mag`, `reff`, `reff_b`, `index`).  FREE: the test's prior, a fresh object per model; those of
     the spiral's and the laws' arguments are tests/test_gpu_radial_laws.py build's, wider than the support.
     `PSF_Index` is free (and last) when the case has several PSFs.  lean: the point source's position, the Sersics'
     angle and every boxiness given as FREE are constants (a 24-walker ensemble is allowed with one Sersic).  extent:
@@ -151,6 +152,7 @@ def make_model(case, sersics, slope=ABSENT, backend='fused', max_walkers=8, lean
         kw.update(xy=wide(), mag=Uniform(loc=15.0, scale=10.0), angle=30.0 if lean else Uniform(loc=-360, scale=720),
                   angle_degrees=True)
         if 'law' in spec:
+            assert 'fixed' not in spec, spec                             # (a law's constants come with the law)
             law, consts = (spec['law'], {}) if isinstance(spec['law'], str) else spec['law']
             radius = lambda: Uniform(loc=0.5, scale=big - 0.5)
             if law == 'moffat':
@@ -162,8 +164,10 @@ def make_model(case, sersics, slope=ABSENT, backend='fused', max_walkers=8, lean
             kw.update(consts)
             comps.append(LAWS[law](**kw))
             continue
-        comps.append(Sersic(reff=Uniform(loc=0.5, scale=40.0), reff_b=Uniform(loc=0.5, scale=40.0),
-                            index=Uniform(loc=0.2, scale=8.0), **kw))
+        kw.update(reff=Uniform(loc=0.5, scale=40.0), reff_b=Uniform(loc=0.5, scale=40.0), index=Uniform(loc=0.2, scale=8.0))
+        assert set(spec.get('fixed', {})) <= {'xy', 'mag', 'reff', 'reff_b', 'index'}, spec
+        kw.update(spec.get('fixed', {}))
+        comps.append(Sersic(**kw))
     return MultiComponentModel(comps, backend=backend, max_walkers=max_walkers)
 
 

@@ -147,6 +147,135 @@ def test_ranks_reproduce_one_rank(tmp_path, world, N_WALK):
     assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max()
 
 
+FORMS_WORKER = r'''
+import os, sys
+import numpy as np
+import torch, torch.distributed as dist
+root, out = sys.argv[1], sys.argv[2]
+sys.path[:0] = [root, root + '/oracle', root + '/tools', root + '/tests']
+import extra_contract as xc
+from psfmc_amd.parallel import ShardedLogPosterior
+from psfmc_amd.sampler import DeviceEnsembleSampler
+dist.init_process_group('gloo')
+rank = dist.get_rank()
+torch.cuda.set_device(0)
+given = np.load(os.path.join(out, 'given.npz'))
+case = dict(sci=given['sci'], ivm=given['ivm'], mask=given['mask'], psfs=list(given['psfs']), pivms=list(given['pivms']),
+            zp=float(given['zp']), shape=given['sci'].shape)
+model = xc.make_model(case, max_walkers=__MAXW__, **xc.KINDS['X'])
+p0 = given['p0']
+# (a) the sharded evaluation of host vectors; (a') of resident ones, blocks larger than the context's max_walkers
+sharded = ShardedLogPosterior(model)
+np.save(os.path.join(out, 'lnp%d.npy' % rank), sharded(p0))
+big = torch.from_numpy(np.ascontiguousarray(np.tile(p0, (__TILES__, 1)))).to('cuda:0')
+assert -(-len(big) // dist.get_world_size()) > model.engine.max_walkers
+lnp_big = sharded.evaluate_device(big)
+torch.cuda.synchronize()
+np.save(os.path.join(out, 'lnpbig%d.npy' % rank), lnp_big.cpu().numpy())
+# (b) the device-resident sampler, half-steps sharded, images accumulated per rank
+samp = DeviceEnsembleSampler(len(p0), model, group=True, accumulate=True, live_dangerously=True)
+samp.random_state = np.random.RandomState(123).get_state()
+for res in samp.sample(p0, iterations=__NITER__):
+    pass
+np.save(os.path.join(out, 'chain%d.npy' % rank), samp.chain)
+np.save(os.path.join(out, 'lnchain%d.npy' % rank), samp.lnprobability)
+np.save(os.path.join(out, 'nacc%d.npy' % rank), samp.naccepted)
+own = model.accumulated_samples
+model.reduce_accumulated(samp.ranks)
+post = model.collect_posterior_images()
+np.savez(os.path.join(out, 'post%d.npz' % rank), count=model.accumulated_samples, own=own, **post)
+model.close()
+dist.destroy_process_group()
+'''
+
+# 14 walkers on three ranks: half-ensemble blocks 3, 2, 2, accumulation blocks 5, 5, 4
+FORMS_SHAPE, FORMS_WALKERS, FORMS_TILES, FORMS_MAX = (70, 96), 14, 6, 16
+
+
+def forms_model():
+    """(model, start [14, P]) of the product-path run: `extra_contract.KINDS['X']` -- a boxy Ferrer with a spiral and
+    modes, a pixel-integrated Sersic, a Moffat, a tilted sky, every keyword free -- on the embedded 70 x 96 field
+    with two PSFs; a ball about the scene, PSF_Index alternating over the walkers.  Also (case, oracle field)."""
+    import extra_contract as xc
+    case, field = xc.law_case('X', FORMS_SHAPE)
+    model = xc.make_model(case, max_walkers=FORMS_MAX, **xc.KINDS['X'])
+    assert model.param_names[-1] == 'PSF_Index'
+    base = xc.theta_of(model, *xc.scene(FORMS_SHAPE), psf=0.0)
+    p0 = base + np.random.RandomState(2).normal(size=(FORMS_WALKERS, len(base))) * 1e-2
+    p0[:, -1] = np.arange(FORMS_WALKERS) % 2
+    assert np.all(np.isfinite(model.log_priors_batch(p0)))
+    return model, p0, case, field
+
+
+def test_three_ranks_on_every_form_at_once(tmp_path):
+    """The product path -- `ShardedLogPosterior`, `DeviceEnsembleSampler(group=True)`, `reduce_accumulated` over gloo,
+    three ranks on device 0 -- on kind X (auxiliary vectors, general / Fourier / spiral / radial / integrated
+    constants and extra images per walker, behind every rank's block offset) on the embedded, rectangular 70 x 96
+    field with two PSFs: held to the single-process results exactly as test_ranks_reproduce_one_rank holds synth256,
+    and its log-posteriors to the contract (tests/extra_contract.py, 1e-9 |ll|).  The single process works while the
+    ranks start; the ranks have the time limit of the other tests here."""
+    import extra_contract as xc
+    from psfmc_amd.parallel import shard_bounds
+    from psfmc_amd.sampler import DeviceEnsembleSampler
+    from test_gpu_extra_image_fields import check_ll
+    world = 3
+    script = tmp_path / 'worker.py'
+    script.write_text(FORMS_WORKER.replace('__NITER__', str(N_ITER)).replace('__TILES__', str(FORMS_TILES))
+                      .replace('__MAXW__', str(FORMS_MAX)))
+    out = tmp_path / 'out'
+    out.mkdir()
+    model, p0, case, field = forms_model()
+    np.savez(out / 'given.npz', p0=p0, **{k: np.asarray(case[k]) for k in ('sci', 'ivm', 'mask', 'psfs', 'pivms', 'zp')})
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, OMP_NUM_THREADS='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
+    ranks = subprocess.Popen(
+        [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=%d' % world,
+         '--master-addr', '127.0.0.1', '--master-port', str(port), str(script), ROOT, str(out)], env=env)
+    try:
+        # while the ranks start: the single process's results, and the contract's log-posteriors of the start and
+        # the final positions
+        single = model.log_posterior_batch(p0)
+        samp = DeviceEnsembleSampler(FORMS_WALKERS, model, accumulate=True, live_dangerously=True)
+        samp.random_state = np.random.RandomState(123).get_state()
+        for _ in samp.sample(p0, iterations=N_ITER):
+            pass
+        assert samp.naccepted.sum() > 0
+        worst = 0.0
+        for theta, got in list(zip(p0, single)) + list(zip(samp.chain[:, -1], samp.lnprobability[:, -1])):
+            ll, _, _, margin = xc.contract_with_state(model, field, theta)
+            assert margin >= xc.EDGE_MARGIN, margin
+            worst = max(worst, check_ll(got, ll + model.log_priors_batch(theta[None])[0], ll, 'forms'))
+        print('three ranks, kind X 70x96: worst log-posterior relative error %.2e' % worst)
+        post = model.collect_posterior_images()
+        model.close()
+        assert ranks.wait(timeout=600) == 0
+    finally:
+        if ranks.poll() is None:
+            ranks.kill()
+            ranks.wait()
+
+    # (a) gathered log-posteriors: identical on every rank, the single process's bit for bit
+    for r in range(world):
+        assert np.array_equal(np.load(out / ('lnp%d.npy' % r)), single), r
+        assert np.array_equal(np.load(out / ('lnpbig%d.npy' % r)), np.tile(single, FORMS_TILES)), r
+    # (b) the three-rank chain is the one-rank chain
+    for r in range(world):
+        assert np.array_equal(np.load(out / ('chain%d.npy' % r)), samp.chain), r
+        assert np.array_equal(np.load(out / ('lnchain%d.npy' % r)), samp.lnprobability), r
+        assert np.array_equal(np.load(out / ('nacc%d.npy' % r)), samp.naccepted), r
+    for r in range(world):
+        got = np.load(out / ('post%d.npz' % r))
+        assert int(got['count']) == FORMS_WALKERS * N_ITER == model.accumulated_samples
+        lo, hi = shard_bounds(FORMS_WALKERS, world, r)
+        assert int(got['own']) == (hi - lo) * N_ITER
+        for kind, img in post.items():
+            fin = np.isfinite(img)
+            assert np.array_equal(np.isfinite(got[kind]), fin), (r, kind)
+            assert np.abs(got[kind][fin] - img[fin]).max() <= 1e-12 * np.abs(img[fin]).max(), (r, kind)
+
+
 RCCL_WORKER = r'''
 import json, os, sys, time
 import numpy as np
