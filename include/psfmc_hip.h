@@ -321,6 +321,27 @@ int psfmc_set_spiral_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* 
 #define PSFMC_RADIAL_PARAMS 2
 int psfmc_set_radial_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* kinds, const int* col,
                             const double* konst);
+/*
+ * General components rendered as the MEAN OF THEIR LAW OVER EACH PIXEL (Sersic(..., pixel_mean=True) with a boxiness,
+ * modes or a spiral, Moffat(..., pixel_mean=True), Ferrer(..., pixel_mean=True); not the reference's).  Definition:
+ * psfmc_amd/ModelComponents/Sersic.py Sersic.general_point and Sersic.general_mean_image; kernels:
+ * csrc/psfmc_general_mean.h.  flags [n_sersic]: nonzero where Sersic slot k (model-file order) of the field is
+ * rendered so.  A flagged slot's value at a pixel is no longer its law at the pixel centre (times the reference's
+ * centroid term for the Sersic law) but (2 g(centre) + the mean of g at the four corners) / 3 with g the law without
+ * a centroid term; the mean of g over an 8 x 8 midpoint grid in a pixel that a Ferrer's truncation edge crosses; and
+ * in the 7 x 7 pixels around the centre the midpoint grids and the dyadic refinement of the pixel-integrated profile
+ * (psfmc_set_sersic_integrate) with g in place of the plain profile: finite where the centre is a pixel centre, mag
+ * the total magnitude as before.  The call adds NO entries to the auxiliary table and no parameter: the walkers'
+ * auxiliary vectors, psfmc_set_aux_rows' rows and psfmc_debug_aux_table are what they were.  Call after the field's
+ * psfmc_set_aux_layout, which must flag the slots as general; psfmc_set_fourier_layout, psfmc_set_spiral_layout and
+ * psfmc_set_radial_layout keep the flags (call them before or after), psfmc_set_layout[_field] and
+ * psfmc_set_aux_layout drop the field's; all-zero flags remove them, and the slots are rendered as they were, bit for
+ * bit.  Refused (PSFMC_EINVAL) with nothing changed: a flag on a slot that is not flagged general or that is
+ * pixel-integrated, a field without an aux layout, a wrong n_sersic.  The fields of one context keep their own flags,
+ * registered in any order.  A context that never receives a nonzero flag allocates nothing, launches nothing more and
+ * passes every kernel the arguments it passed without this call.
+ */
+int psfmc_set_general_mean(psfmc_ctx* ctx, int field, int n_sersic, const int* flags);
 /* host buffers theta [W][n_params], extra_lnprior [W] or NULL, lnprob [W] */
 int psfmc_eval_theta(psfmc_ctx* ctx, int W, const double* theta, const double* extra_lnprior,
                      double* lnprob);
@@ -552,6 +573,8 @@ int psfmc_group_set_spiral_layout(psfmc_group* group, int n_sersic, const int* f
 /* psfmc_set_radial_layout (field 0) on every device of the group */
 int psfmc_group_set_radial_layout(psfmc_group* group, int n_sersic, const int* kinds, const int* col,
                                   const double* konst);
+/* psfmc_set_general_mean (field 0) on every device of the group */
+int psfmc_group_set_general_mean(psfmc_group* group, int n_sersic, const int* flags);
 /* psfmc_set_sersic_integrate (field 0) on every device of the group */
 int psfmc_group_set_sersic_integrate(psfmc_group* group, int n_sersic, const int* integrate);
 int psfmc_group_eval_batch(psfmc_group* group, int W, const double* rows, const uint8_t* skip,

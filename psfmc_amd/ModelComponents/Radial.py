@@ -19,7 +19,7 @@ class _RadialLaw(Sersic):
     reff = property(lambda self: getattr(self, self.RADII[0]))
     reff_b = property(lambda self: getattr(self, self.RADII[1]))
 
-    def _init_law(self, xy, mag, angle, angle_degrees, boxiness, fourier, spiral):
+    def _init_law(self, xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean=False):
         ComponentBase.__init__(self)
         self.xy = xy
         self.mag = mag
@@ -27,7 +27,7 @@ class _RadialLaw(Sersic):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = False
-        self._init_shape(boxiness, fourier, spiral)
+        self._init_shape(boxiness, fourier, spiral, pixel_mean)
 
     @property
     def is_general(self):
@@ -72,8 +72,9 @@ class Moffat(_RadialLaw):
     `beta` the wing exponent, `mag` the total magnitude: Sigma_0 = F g (beta - 1) / (pi fwhm fwhm_b A(c) Q cos(incl)).
     Support: beta finite and > 1, fwhm_b <= fwhm (log-prior -inf otherwise).  `angle`, `angle_degrees`, `boxiness`,
     `fourier` and `spiral` are `Sersic`'s.  The value is the law at the pixel centre -- no centroid term, the
-    reference's belongs to the Sersic law -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`.
-    Definition: `Sersic.radial_image`."""
+    reference's belongs to the Sersic law -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`;
+    `pixel_mean=True` renders the mean of the law over each pixel instead (`Sersic.general_mean_image`), which is what
+    a `fwhm` of a few pixels needs.  Definition: `Sersic.radial_image`."""
     radial_law = 'moffat'
     RADII = ('fwhm', 'fwhm_b')
     LAW_ATTRS = ('beta',)
@@ -86,8 +87,8 @@ class Moffat(_RadialLaw):
     beta = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, fwhm=None, fwhm_b=None, beta=None, angle=None, angle_degrees=False,
-                 boxiness=None, fourier=None, spiral=None):
-        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral)
+                 boxiness=None, fourier=None, spiral=None, pixel_mean=False):
+        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean)
         self.fwhm = fwhm
         self.fwhm_b = fwhm_b
         self.beta = beta
@@ -101,8 +102,9 @@ class Ferrer(_RadialLaw):
     k = 2 - beta.  Support: alpha, beta finite, alpha >= 0, beta < 2, r_out_b <= r_out (log-prior -inf otherwise).
     `angle`, `angle_degrees`, `boxiness`, `fourier` and `spiral` are `Sersic`'s.  The value is the law at the pixel
     centre -- no centroid term: the reference's belongs to the Sersic law, and this law's log-slope diverges at the
-    edge -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`.  Definition:
-    `Sersic.radial_image`."""
+    edge -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`; `pixel_mean=True` renders the mean
+    of the law over each pixel instead (`Sersic.general_mean_image`: the pixels the truncation edge crosses are
+    sampled on an 8 x 8 grid).  Definition: `Sersic.radial_image`."""
     radial_law = 'ferrer'
     RADII = ('r_out', 'r_out_b')
     LAW_ATTRS = ('alpha', 'beta')
@@ -116,8 +118,8 @@ class Ferrer(_RadialLaw):
     beta = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, r_out=None, r_out_b=None, alpha=None, beta=None, angle=None,
-                 angle_degrees=False, boxiness=None, fourier=None, spiral=None):
-        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral)
+                 angle_degrees=False, boxiness=None, fourier=None, spiral=None, pixel_mean=False):
+        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean)
         self.r_out = r_out
         self.r_out_b = r_out_b
         self.alpha = alpha

@@ -13,6 +13,9 @@ INTEG_GRID_FAR = 4        # ... and further out in the box
 INTEG_SPLIT = 4           # s0: a cell that holds the centre is split s0 x s0
 INTEG_LEVELS = 8          # L: the sub-cell(s) holding the centre are split again, L times
 INTEG_SUB = 4             # midpoint grid of every sub-cell that is not split (even: see integrated_image)
+# The pixel-averaged mode of the general components (`pixel_mean=True`, `Sersic.general_mean_image`) uses the
+# constants above unchanged and one of its own; the same on the device (csrc/psfmc_general_mean.h).
+MEAN_EDGE_GRID = 8        # midpoint grid of a Ferrer pixel that the truncation edge crosses
 
 
 class Sersic(ComponentBase):
@@ -49,7 +52,13 @@ class Sersic(ComponentBase):
     magnitude.  The parameters are the attributes `spiral_r_in`, `spiral_r_out`, `spiral_wind`, `spiral_alpha`,
     `spiral_incl`, `spiral_sky` (the three angles in radians, or in degrees with `angle_degrees`).  Support: all six
     finite, r_in >= 0, r_out > r_in, alpha >= 0, |inclination| < pi/2 (log-prior -inf otherwise).  A component with
-    `spiral` alone is a general one with c = 0 and no modes; `spiral` with `integrate=True` raises ValueError."""
+    `spiral` alone is a general one with c = 0 and no modes; `spiral` with `integrate=True` raises ValueError.
+
+    `pixel_mean=True` (only together with `boxiness`, `fourier` or `spiral`; not the reference's) renders the general
+    component as the MEAN OF ITS LAW OVER EACH PIXEL instead of the law at the pixel centre times the centroid term
+    (`Sersic.general_mean_image`): finite where the centre is a pixel centre, and several times to a hundred times
+    closer to the true pixel mean in the core.  It adds no parameter.  On a plain Sersic it raises ValueError (use
+    `integrate=True` there), and so does `pixel_mean=True` together with `integrate=True`."""
     device_kind = 'sersic'
     # the radial law: None for the Sersic law, else a key of RADIAL_KINDS (the subclasses `Moffat` and `Ferrer`)
     radial_law = None
@@ -98,7 +107,8 @@ class Sersic(ComponentBase):
     spiral_sky = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
-                 angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None, spiral=None):
+                 angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None, spiral=None,
+                 pixel_mean=False):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -108,21 +118,29 @@ class Sersic(ComponentBase):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = bool(integrate)
-        self._init_shape(boxiness, fourier, spiral)
+        self._init_shape(boxiness, fourier, spiral, pixel_mean)
 
-    def _init_shape(self, boxiness, fourier, spiral):
-        """The isophote-shape keywords `boxiness`, `fourier` and `spiral` (shared with the radial-law subclasses)."""
+    def _init_shape(self, boxiness, fourier, spiral, pixel_mean=False):
+        """The isophote-shape keywords `boxiness`, `fourier` and `spiral` and the rendering keyword `pixel_mean`
+        (shared with the radial-law subclasses)."""
+        self.pixel_mean = bool(pixel_mean)
+        if self.pixel_mean and self.integrate:
+            raise ValueError('Sersic: pixel_mean=True together with integrate=True is not supported (integrate=True '
+                             'is the plain profile\'s pixel integral, pixel_mean=True a general component\'s)')
+        if self.pixel_mean and self.radial_law is None and boxiness is None and fourier is None and spiral is None:
+            raise ValueError('Sersic: pixel_mean=True needs boxiness, fourier or spiral; the plain profile has '
+                             'integrate=True')
         self.has_boxiness = boxiness is not None
         if self.has_boxiness:
             if self.integrate:
                 raise ValueError('Sersic: boxiness together with integrate=True is not supported (the '
-                                 'pixel-integrated profile is defined for elliptical isophotes)')
+                                 'pixel-integrated profile is defined for elliptical isophotes; use pixel_mean=True)')
             self.boxiness = boxiness
         self.fourier_modes = ()
         if fourier is not None:
             if self.integrate:
                 raise ValueError('Sersic: fourier together with integrate=True is not supported (the '
-                                 'pixel-integrated profile is defined for elliptical isophotes)')
+                                 'pixel-integrated profile is defined for elliptical isophotes; use pixel_mean=True)')
             modes = []
             for m, entry in dict(fourier).items():
                 if isinstance(m, bool) or int(m) != m or int(m) not in Sersic.FOURIER_MODES:
@@ -142,7 +160,7 @@ class Sersic(ComponentBase):
         if self.has_spiral:
             if self.integrate:
                 raise ValueError('Sersic: spiral together with integrate=True is not supported (the '
-                                 'pixel-integrated profile is defined for elliptical isophotes)')
+                                 'pixel-integrated profile is defined for elliptical isophotes; use pixel_mean=True)')
             spiral = dict(spiral)
             unknown = [k for k in spiral if k not in Sersic.SPIRAL_KEYS]
             if unknown:
@@ -163,8 +181,8 @@ class Sersic(ComponentBase):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
         when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, `<count>SERFOU` = the
         comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral,
-        `<count>SERLAW = 'moffat' | 'ferrer'` when its radial law is not the Sersic law (`Moffat`, `Ferrer`), nothing
-        otherwise."""
+        `<count>SERLAW = 'moffat' | 'ferrer'` when its radial law is not the Sersic law (`Moffat`, `Ferrer`),
+        `<count>SERAVG = T` when it is rendered as the mean over each pixel (`pixel_mean=True`), nothing otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
             out['{:d}SERBOX'.format(count)] = True
@@ -174,6 +192,8 @@ class Sersic(ComponentBase):
             out['{:d}SERSPI'.format(count)] = True
         if self.radial_law:
             out['{:d}SERLAW'.format(count)] = self.radial_law
+        if self.pixel_mean:
+            out['{:d}SERAVG'.format(count)] = True
         return out
 
     @staticmethod
@@ -272,6 +292,14 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.pixel_mean:
+            amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
+            arr += Sersic.general_mean_image(
+                self.radial_law, row, self._radial_values(lambda k: getattr(self, k)) if self.radial_law else None,
+                float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
+                list(zip(self.fourier_modes, amps, phases)),
+                self._spiral_values(lambda k: getattr(self, k)) if self.has_spiral else None, arr.shape)
+            return arr
         if self.radial_law:
             amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
             arr += Sersic.radial_image(self.radial_law, row, self._radial_values(lambda k: getattr(self, k)),
@@ -636,4 +664,138 @@ class Sersic(ComponentBase):
                                 continue
                             sx, sy = np.meshgrid(ix * cw - 0.5 + o * cw, iy * cw - 0.5 + o * cw)
                             img[j, i] += cw * cw * Sersic._plain(row, sx, sy)[0].mean()
+        return img
+
+    # -- the pixel-averaged mode of the general components (`pixel_mean=True`) ------------------------------------
+    @staticmethod
+    def _general_point_x(law, row, pars, boxiness, modes, spiral, x, y):
+        """(`general_point`'s value, Ferrer's x = rho^(2 - beta) with 0 at u = v = 0 -- None for the other laws)."""
+        x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        if law not in Sersic.RADIAL_KINDS:
+            raise ValueError('radial law {!r}: one of None, moffat, ferrer'.format(law))
+        e = float(boxiness) + 2.0
+        dx, dy = np.asarray(x, dtype=np.float64) - x0, np.asarray(y, dtype=np.float64) - y0
+        ci = 1.0
+        with np.errstate(all='ignore'):
+            if spiral is not None:
+                r_in, r_out, winding, alpha_s, incl, sky = [float(s) for s in spiral]
+                cs, sn, ci = np.cos(sky), np.sin(sky), np.cos(incl)
+                X = cs * dx + sn * dy
+                Y = (-sn * dx + cs * dy) / ci
+                r = np.hypot(X, Y)
+                T = 0.5 * (1.0 + np.tanh(2.0 * (2.0 * r - r_in - r_out) / (r_out - r_in)))
+                P = np.where(r > 0, (r / r_out) ** alpha_s, 1.0 if alpha_s == 0 else 0.0)
+                t = winding * T * P
+                ct, st = np.cos(t), np.sin(t)
+                dx, dy = ct * X + st * Y, -st * X + ct * Y
+            u = m00 * dx + m01 * dy
+            v = m10 * dx + m11 * dy
+            rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
+            if modes:
+                ruv = np.hypot(u, v)
+                rho2 = rho2 * (1.0 + Sersic._fourier_eps(u / ruv, v / ruv, modes)) ** 2
+            centre = (u == 0) & (v == 0)
+            if law is None:
+                area = Sersic.superellipse_area_ratio(boxiness)
+                if modes:
+                    area = area * Sersic.fourier_area_ratio(boxiness, modes)
+                sb = sbeff / area / ci if spiral is not None else sbeff / area
+                return np.where(centre, sb * np.exp(kappa), sb * np.exp(-kappa * (rho2 ** p - 1.0))), None
+            sigma0 = Sersic.radial_central(law, row, pars, boxiness, modes, spiral)
+            if law == 'moffat':
+                beta = float(pars[0])
+                g = 4.0 * np.expm1(np.log(2.0) / beta)
+                return np.where(centre, sigma0, sigma0 * (1.0 + g * rho2) ** -beta), None
+            alpha, k = float(pars[0]), 2.0 - float(pars[1])
+            xk = np.where(centre, 0.0, rho2 ** (0.5 * k))
+            return np.where(xk < 1.0, sigma0 * np.abs(1.0 - xk) ** alpha, 0.0), xk
+
+    @staticmethod
+    def general_point(law, row, pars, boxiness, modes, spiral, x, y):
+        """The law of a general component at ARBITRARY POINTS (x, y) (arrays of one shape, pixel coordinates): what
+        `general_mean_image` averages.  `law` is None (the Sersic law), 'moffat' or 'ferrer'; `row`, `pars`
+        (ignored for None), `boxiness`, `modes` and `spiral` as for `radial_image`.  The coordinate chain is
+        `spiral_image`'s and `radial_rho2`'s -- an absent keyword leaves its step out -- up to
+        rho^2 = (|u|^e + |v|^e)^(2/e) (1 + eps)^2, and then
+
+            Sersic  sb exp(-kappa (rho^(2p) - 1)),  sb = Sigma_e / (A(c) Q cos(incl))
+            Moffat, Ferrer  exactly as `radial_image`
+
+        There is NO centroid term: the reference's is a correction for sampling the law at the pixel centre, and this
+        is the law itself.  Where u = v = 0 the value is the finite peak, sb e^kappa or Sigma_0."""
+        return Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y)[0]
+
+    @staticmethod
+    def general_mean_image(law, row, pars, boxiness, modes, spiral, shape):
+        """A general component rendered as the MEAN OF ITS LAW OVER EACH PIXEL on a `shape` image (`pixel_mean=True`;
+        not the reference's).  This numpy text is the DEFINITION the device kernels (csrc/psfmc_general_mean.h) are
+        held to.  With g = `general_point` and the constants INTEG_* of `integrated_image`:
+
+        1. Every pixel: (2 g(centre) + the mean of g at the pixel's four corners) / 3 -- the second-order term of the
+           mean over the pixel, which `integrated_image` part 1 takes from the closed Laplacian; the general forms
+           have none, and neighbouring pixels share the corner samples.
+        2. Ferrer only: a pixel of part 1 whose five samples do not all have x < 1, or all x >= 1 (the truncation
+           edge crosses it), is the mean of g over a MEAN_EDGE_GRID x MEAN_EDGE_GRID midpoint grid instead.
+        3. The (2H+1)^2 pixels around (px, py) = floor(centre + 1/2), clipped to the image: the mean of g over an
+           s x s midpoint grid, s = INTEG_GRID_NEAR at Chebyshev distance <= INTEG_NEAR_RING from (px, py), else
+           INTEG_GRID_FAR (`integrated_image` part 2 with g in place of the plain profile).
+        4. Every pixel whose closed square holds the centre: `integrated_image` part 3 with g -- the same dyadic
+           "holds" decisions, the same even sub-grids, so that no sample falls on the centre unless the centre
+           coincides with one, where g is its finite peak.
+
+        Parts 3 and 4 overwrite parts 1 and 2.  `mag` stays the total magnitude through the closed-form factors of
+        `general_image`, `fourier_image`, `spiral_image` and `radial_image`."""
+        ny, nx = shape
+        x0, y0 = row[0], row[1]
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        point = lambda x, y: Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y)
+        yy, xx = np.mgrid[0:ny, 0:nx].astype(np.float64)
+        cyy, cxx = np.mgrid[0:ny + 1, 0:nx + 1].astype(np.float64) - 0.5
+        mid, mid_x = point(xx, yy)
+        cor, cor_x = point(cxx, cyy)
+        img = (2.0 * mid + 0.25 * ((cor[:-1, :-1] + cor[:-1, 1:]) + (cor[1:, :-1] + cor[1:, 1:]))) / 3.0
+        if law == 'ferrer':
+            ins = [mid_x < 1.0, cor_x[:-1, :-1] < 1.0, cor_x[:-1, 1:] < 1.0, cor_x[1:, :-1] < 1.0, cor_x[1:, 1:] < 1.0]
+            n_in = np.sum(ins, axis=0)
+            o = (np.arange(MEAN_EDGE_GRID) + 0.5) / MEAN_EDGE_GRID - 0.5
+            for j, i in zip(*np.nonzero((n_in > 0) & (n_in < 5))):
+                sx, sy = np.meshgrid(i + o, j + o)
+                img[j, i] = point(sx, sy)[0].mean()
+        gx, gy = x0 + 0.5, y0 + 0.5
+        if not (np.isfinite(gx) and np.isfinite(gy)) or abs(gx) > 2.0 ** 30 or abs(gy) > 2.0 ** 30:
+            return img                                                  # (no pixel of any image is near)
+        px, py = int(np.floor(gx)), int(np.floor(gy))
+        grid = lambda d: INTEG_GRID_NEAR if d <= INTEG_NEAR_RING else INTEG_GRID_FAR
+        split, levels, sub = INTEG_SPLIT, INTEG_LEVELS, INTEG_SUB
+
+        def held(g, scale):               # indices of the pitch-1/scale cells holding the centre along one axis
+            a = np.floor(g * scale)
+            return ([int(a) - 1] if g * scale == a else []) + [int(a)]
+        for j in range(max(py - INTEG_HALF_BOX, 0), min(py + INTEG_HALF_BOX + 1, ny)):
+            for i in range(max(px - INTEG_HALF_BOX, 0), min(px + INTEG_HALF_BOX + 1, nx)):
+                if i in held(gx, 1.0) and j in held(gy, 1.0):
+                    img[j, i] = 0.0                                     # part 4 below
+                    continue
+                s = grid(max(abs(i - px), abs(j - py)))
+                o = (np.arange(s) + 0.5) / s - 0.5
+                sx, sy = np.meshgrid(i + o, j + o)
+                img[j, i] = point(sx, sy)[0].mean()
+        o = (np.arange(sub) + 0.5) / sub
+        for l in range(levels + 1):
+            scale = float(split) ** l
+            cw = 1.0 / (scale * split)                                  # sub-cell pitch of this level
+            nxt_x, nxt_y = held(gx, scale * split), held(gy, scale * split)
+            for cy in held(gy, scale):
+                for cx in held(gx, scale):
+                    i, j = int(np.floor(cx / scale)), int(np.floor(cy / scale))      # the pixel of this cell
+                    if not (0 <= i < nx and 0 <= j < ny):
+                        continue
+                    for b in range(split):
+                        for a in range(split):
+                            ix, iy = cx * split + a, cy * split + b
+                            if l < levels and ix in nxt_x and iy in nxt_y:
+                                continue
+                            sx, sy = np.meshgrid(ix * cw - 0.5 + o * cw, iy * cw - 0.5 + o * cw)
+                            img[j, i] += cw * cw * point(sx, sy)[0].mean()
         return img

@@ -36,6 +36,7 @@
 #if PSFMC_PART == 0
 #include "psfmc_integrated.h"
 #include "psfmc_general.h"
+#include "psfmc_general_mean.h"
 #include "psfmc_aux_table.h"
 #endif
 
@@ -310,6 +311,14 @@ struct psfmc_ctx {
     std::vector<uint8_t> rad_kinds;      // [n_fields][n_sersic] 0: the Sersic law, 1: Moffat, 2: Ferrer
     uint8_t* d_rad_kinds = nullptr;
     double* d_rad_par = nullptr;         // [max_walkers][n_sersic][kRadPar]
+    // general components rendered as the mean over each pixel (psfmc_set_general_mean, psfmc_general_mean.h): flags
+    // only, no per-walker entries; nothing is allocated, nothing more is launched and every kernel gets the arguments
+    // it got until a field registers a flag
+    bool mean_any = false;
+    std::vector<uint8_t> mean_flags;     // [n_fields][n_sersic]
+    // [n_fields][n_sersic] the flags, then [n_fields][n_sersic] the general flags with the mean components cleared
+    // (what k_general_rows reads in a context with mean components)
+    uint8_t* d_mean_flags = nullptr;
 };
 
 // the extra image of the walker whose record `prep` points at (nullptr: none to add)
@@ -1437,7 +1446,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
                     c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
-                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par};
+                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par, c->d_mean_flags};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (void* p : c->aux_blobs)
@@ -1758,8 +1767,30 @@ static decltype(&k_general_split<false, false>) general_split_kernel(const psfmc
     return c->spi_any ? k_general_split<true, false> : k_general_split<false, false>;
 }
 
+// the mean components of a context that has some (psfmc_general_mean.h): behind k_general_rows, which left them out
+static void launch_general_mean(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
+    const double* prep = c->d_prep + (size_t)w_off * c->plen;
+    double* img = c->d_extra_img + (size_t)w_off * c->S;
+    const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
+    const double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
+    const double* fpar = fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr;
+    const double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
+    const double* rpar = c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
+    hipLaunchKernelGGL(k_general_mean_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
+                       c->d_mean_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
+                       fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
+                       c->rad_any ? c->d_rad_kinds : nullptr);
+    hipLaunchKernelGGL(k_general_mean_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags,
+                       c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
+                       fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
+                       c->rad_any ? c->d_rad_kinds : nullptr);
+}
+
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
     if ((!c->integ_any && !c->gen_any) || n <= 0) return;
+    // what k_general_rows renders: every general component, less the mean ones where the context has some (the same
+    // pointer as ever where it has none)
+    const uint8_t* rows_flags = c->mean_any ? c->d_mean_flags + (size_t)c->n_fields * c->n_sersic : c->d_gen_flags;
     double* prep = c->d_prep + (size_t)w_off * c->plen;
     double* img = c->d_extra_img + (size_t)w_off * c->S;
     const int items = n * c->n_sersic;
@@ -1793,9 +1824,10 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
         if (!c->integ_any) {
             hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                                dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
-                               c->d_gen_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
+                               rows_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
                                fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
                                fou ? c->d_fou_masks : nullptr, spar, smasks, rpar, rkinds);
+            if (c->mean_any) launch_general_mean(c, n, w_off, skip, st);
             return;
         }
     }
@@ -1812,7 +1844,7 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                            dim3(256), 0, st, prep, c->plen, skip,
                            c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
                            c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
-                           c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, c->d_gen_flags, c->n_sersic, c->n_psf,
+                           c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, rows_flags, c->n_sersic, c->n_psf,
                            c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1,
                            fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
                            fou ? c->d_fou_masks : nullptr,
@@ -1820,6 +1852,7 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                            spi ? c->d_spi_masks : nullptr,
                            c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr,
                            c->rad_any ? c->d_rad_kinds : nullptr);
+    if (c->gen_any && c->mean_any) launch_general_mean(c, n, w_off, skip, st);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -2095,6 +2128,35 @@ static int layout_sync(psfmc_ctx* c) {
     return PSFMC_OK;
 }
 
+// the device copy of the mean flags (psfmc_set_general_mean) and of the general flags less the mean components, and
+// the any-bit; a context that never had a flag has neither
+static int sync_mean_flags(psfmc_ctx* c) {
+    bool any = false;
+    for (uint8_t f : c->mean_flags) any = any || f;
+    if (!any && !c->d_mean_flags) {
+        c->mean_any = false;
+        return PSFMC_OK;
+    }
+    RC_TRY(layout_sync(c));                            // (no batch in flight reads the flags)
+    const size_t n = (size_t)c->n_fields * c->n_sersic;
+    if (!c->d_mean_flags) HIP_TRY(hipMalloc(&c->d_mean_flags, 2 * n));
+    std::vector<uint8_t> both(2 * n, 0);
+    for (size_t i = 0; i < n && i < c->mean_flags.size(); ++i) {
+        both[i] = c->mean_flags[i];
+        both[n + i] = (i < c->gen_flags.size() && c->gen_flags[i] && !c->mean_flags[i]) ? 1 : 0;
+    }
+    HIP_TRY(hipMemcpy(c->d_mean_flags, both.data(), 2 * n, hipMemcpyHostToDevice));
+    c->mean_any = any;
+    c->prep_tabs_valid = false;                        // records written under the old flags are not to be rasterised
+    return PSFMC_OK;
+}
+// a new layout or aux layout of a field drops its mean flags
+static int drop_mean_flags(psfmc_ctx* c, int field) {
+    if (c->mean_flags.empty()) return PSFMC_OK;
+    for (int k = 0; k < c->n_sersic; ++k) c->mean_flags[(size_t)field * c->n_sersic + k] = 0;
+    return sync_mean_flags(c);
+}
+
 // field `field`'s rows of the blocks' mask arrays from its record, the any-bits and the device copies where they
 // exist.  `touched`: the block this call registers; the context has its mask array from then on.
 static int write_block_masks(psfmc_ctx* c, int field, int touched = -1) {
@@ -2248,6 +2310,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
             HIP_TRY(hipMemcpy(c->d_gen_flags, c->gen_flags.data(), c->gen_flags.size(), hipMemcpyHostToDevice));
         c->gen_any = any;
     }
+    RC_TRY(drop_mean_flags(c, field));
     if (c->n_fields > 1) {
         if (!c->d_field_layouts) HIP_TRY(hipMalloc(&c->d_field_layouts, (size_t)c->n_fields * sizeof(ThetaLayout)));
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
@@ -2387,7 +2450,31 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
     if (c->d_gen_flags)
         HIP_TRY(hipMemcpy(c->d_gen_flags, c->gen_flags.data(), n_flags, hipMemcpyHostToDevice));
     c->gen_any = any;
-    return PSFMC_OK;
+    return drop_mean_flags(c, field);
+}
+
+extern "C" int psfmc_set_general_mean(psfmc_ctx* c, int field, int n_sersic, const int* flags) {
+    if (!c || !flags) return fail(PSFMC_EINVAL, "NULL argument");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
+    bool any_here = false;
+    for (int k = 0; k < n_sersic; ++k) any_here = any_here || flags[k];
+    if (any_here && c->aux_records[field].base_col.empty())
+        return fail(PSFMC_EINVAL, "field %d has no aux layout: call psfmc_set_aux_layout (with the mean components "
+                    "flagged general) before psfmc_set_general_mean", field);
+    for (int k = 0; k < n_sersic; ++k) {
+        if (!flags[k]) continue;
+        if (!c->integ_flags.empty() && c->integ_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: pixel_mean and integrate exclude each "
+                        "other", k, field);
+        if (c->gen_flags.empty() || !c->gen_flags[(size_t)field * n_sersic + k])
+            return fail(PSFMC_EINVAL, "Sersic %d of field %d is not flagged general in the field's aux layout: the pixel "
+                        "mean is a general component's", k, field);
+    }
+    if (!any_here && c->mean_flags.empty()) return PSFMC_OK;           // (nothing registered, nothing to remove)
+    if (c->mean_flags.empty()) c->mean_flags.assign((size_t)c->n_fields * n_sersic, 0);
+    for (int k = 0; k < n_sersic; ++k) c->mean_flags[(size_t)field * n_sersic + k] = flags[k] ? 1 : 0;
+    return sync_mean_flags(c);
 }
 
 extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
@@ -3865,6 +3952,12 @@ extern "C" int psfmc_group_set_radial_layout(psfmc_group* g, int n_sersic, const
                                              const double* konst) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_radial_layout(c, 0, n_sersic, kinds, col, konst));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_general_mean(psfmc_group* g, int n_sersic, const int* flags) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_general_mean(c, 0, n_sersic, flags));
     return PSFMC_OK;
 }
 

@@ -275,6 +275,10 @@ def load_library():
     lib.psfmc_set_radial_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_radial_layout.restype = ci
     lib.psfmc_group_set_radial_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
+    lib.psfmc_set_general_mean.restype = ci
+    lib.psfmc_set_general_mean.argtypes = [vp, ci, ci, ip]
+    lib.psfmc_group_set_general_mean.restype = ci
+    lib.psfmc_group_set_general_mean.argtypes = [vp, ci, ip]
     lib.psfmc_group_set_priors.restype = ci
     lib.psfmc_group_set_priors.argtypes = [vp, ci, ip, _c_double_p]
     lib.psfmc_group_eval_batch.restype = ci
@@ -611,6 +615,14 @@ class Context(object):
         constant.  A context that never gets the call is what it was without it."""
         keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_set_radial_layout(self._ctx, 0, *args))
+
+    def set_general_mean(self, flags):
+        """Which general Sersic slots (model-file order) are rendered as the mean of their law over each pixel
+        (psfmc_set_general_mean; after the aux and block layouts, which keep the flags -- a new layout or aux layout
+        drops them).  A context that never gets a true flag is what it was without the call."""
+        flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+        self._check(self._lib.psfmc_set_general_mean(
+            self._ctx, 0, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
 
     def _theta(self, theta):
         theta = _f64(theta)
@@ -956,6 +968,11 @@ class FieldSetContext(object):
             def set_radial_layout(self, kinds, col, const):
                 keep, args = _block_args('radial', kinds, col, const)
                 owner._check(owner._lib.psfmc_set_radial_layout(owner._ctx, int(field), *args))
+
+            def set_general_mean(self, flags):
+                flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+                owner._check(owner._lib.psfmc_set_general_mean(
+                    owner._ctx, int(field), len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return _Proxy()
 
     @staticmethod
@@ -1350,6 +1367,12 @@ class ContextGroup(object):
         """`Context.set_radial_layout` on every device of the group."""
         keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_group_set_radial_layout(self._grp, *args))
+
+    def set_general_mean(self, flags):
+        """`Context.set_general_mean` on every device of the group."""
+        flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
+        self._check(self._lib.psfmc_group_set_general_mean(
+            self._grp, len(flags), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
 
     def loglike(self, rows, skip=None, aux=None):
         if aux is not None:

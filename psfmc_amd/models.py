@@ -294,6 +294,10 @@ class MultiComponentModel(object):
                 eng.set_spiral_layout(self.sersic_spiral_flags, spi_col, spi_const)
             if any(self.sersic_radial_kinds):
                 eng.set_radial_layout(self.sersic_radial_kinds, rad_col, rad_const)
+            # which general components are rendered as the mean over each pixel (`pixel_mean=True`): flags, no
+            # entries; the last call, and only by a model with the keyword
+            if any(self.sersic_general_mean):
+                eng.set_general_mean(self.sersic_general_mean)
         if columns is not None:
             slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
             zero = np.zeros(n_params)
@@ -341,6 +345,11 @@ class MultiComponentModel(object):
     def sersic_radial_kinds(self):
         """[n_sersic] the radial law of each Sersic slot (model-file order): 0 Sersic, 1 Moffat, 2 Ferrer."""
         return [Sersic.RADIAL_KINDS[getattr(c, 'radial_law', None)] for c in self._sersic]
+
+    @property
+    def sersic_general_mean(self):
+        """[n_sersic] which Sersic slots (model-file order) were given `pixel_mean=True`."""
+        return [bool(getattr(c, 'pixel_mean', False)) for c in self._sersic]
 
     @property
     def has_aux(self):

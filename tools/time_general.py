@@ -8,7 +8,9 @@ keywords, vectors resident on the device (psfmc_eval_theta_device, what bench.py
 against the boxiness only.
 --radial: the cost of the radial laws -- Sky + PS + one boxy `Ferrer` and one `Moffat` against the same model with two
 boxy `Sersic`s.
-Usage: python tools/time_general.py [--fourier | --spiral | --radial] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+--mean: the cost of the pixel-averaged mode -- the `--radial` model with `pixel_mean=True` on both components against
+the same model without it.
+Usage: python tools/time_general.py [--fourier | --spiral | --radial | --mean] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
 import argparse
 import json
 import os
@@ -74,23 +76,26 @@ RADIAL_RANGES = {'adu': (-1e-3, 1e-3), 'alpha': (0.5, 3.0), 'angle': (10.0, 170.
                  'boxiness': (-0.5, 0.5), 'index': (0.7, 3.0), 'mag': (19.5, 21.0)}
 
 
-def build_radial(side, directory, max_walkers, laws):
-    """Sky + PS + a boxy Ferrer and a Moffat (`laws`), or two boxy Sersics with the same radii; the model and a
-    function drawing n_w vectors inside every support."""
+def build_radial(side, directory, max_walkers, laws, mean=False):
+    """Sky + PS + a boxy Ferrer and a Moffat (`laws`; with `mean` both have `pixel_mean=True`), or two boxy Sersics
+    with the same radii; the model and a function drawing n_w vectors inside every support."""
     fld = synth_field.make_field(side, n_sersic=1, seed=0)
     for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
         fits_io.write_image(os.path.join(directory, name), fld[key])
     text = synth_field.model_file_text(side, 0).replace('PointSource(', SKY[0] + '\nPointSource(', 1)
     big, small = 'Uniform(loc=%r, scale=%r)' % (side / 16.0 + 2.0, side / 8.0), 'Uniform(loc=2.0, scale=%r)' % (side / 16.0)
     box = 'boxiness=Uniform(loc=-1, scale=2)'
+    if mean:
+        box += ', pixel_mean=True'
     if laws:
         text += 'Ferrer(%s, r_out=%s, r_out_b=%s, alpha=Uniform(loc=0, scale=4), beta=Uniform(loc=-2, scale=3.95), %s)\n' % (
             RADIAL_COMMON, big, small, box)
-        text += 'Moffat(%s, fwhm=%s, fwhm_b=%s, beta=Uniform(loc=1.05, scale=8))\n' % (RADIAL_COMMON, big, small)
+        text += 'Moffat(%s, fwhm=%s, fwhm_b=%s, beta=Uniform(loc=1.05, scale=8)%s)\n' % (
+            RADIAL_COMMON, big, small, ', pixel_mean=True' if mean else '')
     else:
         for _ in range(2):
             text += 'Sersic(%s, reff=%s, reff_b=%s, index=Uniform(loc=0.5, scale=6), %s)\n' % (RADIAL_COMMON, big, small, box)
-    path = os.path.join(directory, 'model_r%d.py' % laws)
+    path = os.path.join(directory, 'model_r%d%d.py' % (laws, mean))
     with open(path, 'w') as f:
         f.write(text)
     model = MultiComponentModel(path, max_walkers=max_walkers)
@@ -144,17 +149,19 @@ def main():
     ap.add_argument('--fourier', action='store_true', help='boxiness + two free modes against boxiness only')
     ap.add_argument('--spiral', action='store_true', help='boxiness + a free spiral against boxiness only')
     ap.add_argument('--radial', action='store_true', help='a boxy Ferrer and a Moffat against two boxy Sersics')
+    ap.add_argument('--mean', action='store_true', help='the --radial model with pixel_mean=True against the same without')
     args = ap.parse_args()
-    if args.fourier + args.spiral + args.radial > 1:
-        ap.error('--fourier, --spiral and --radial exclude each other')
+    if args.fourier + args.spiral + args.radial + args.mean > 1:
+        ap.error('--fourier, --spiral, --radial and --mean exclude each other')
     rows = []
     for shape in args.shapes:
         side, n_w = (int(v) for v in shape.split(':'))
         with tempfile.TemporaryDirectory() as tmp:
             rates = {}
             for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
-                if args.radial:
-                    model, draw = build_radial(side, tmp, n_w, general)
+                if args.radial or args.mean:
+                    model, draw = (build_radial(side, tmp, n_w, 1, mean=bool(general)) if args.mean else
+                                   build_radial(side, tmp, n_w, general))
                     rate, _ = evals_per_second(model, draw(n_w), args.seconds)
                     rates[general] = max(rates.get(general, 0.0), rate)
                     model.close()
@@ -189,7 +196,8 @@ def main():
                        general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    lines = ['side     W 2 Sersics evals/s Ferrer + Moffat evals/s ratio' if args.radial else
+    lines = ['side     W   centres evals/s  pixel means evals/s  ratio' if args.mean else
+             'side     W 2 Sersics evals/s Ferrer + Moffat evals/s ratio' if args.radial else
              'side     W  boxiness evals/s box + spiral evals/s  ratio' if args.spiral else
              'side     W   default evals/s     general evals/s  ratio' if not args.fourier else
              'side     W  boxiness evals/s  box + modes evals/s  ratio']
