@@ -470,6 +470,39 @@ int psfmc_stretch_run(psfmc_ctx* ctx, int W, int n_iter, double* pos, double* ln
                       long long* naccepted, int accumulate);
 
 /*
+ * Proposal moves (no reference counterpart; the contract is psfmc_amd/sampler.py's EnsembleSampler(moves=...),
+ * which these calls reproduce bit for bit).  psfmc_stretch_run's sampler with the move of every iteration named
+ * by the caller: kind[it] is the move of BOTH half-steps of iteration it,
+ *   PSFMC_MOVE_STRETCH  q_i = c[a_i] - z_i (c[a_i] - s_i)   scal = z, lz = (P-1) ln z, partner_b unread
+ *   PSFMC_MOVE_DE       q_i = s_i + g_i (c[a_i] - c[b_i])   scal = g, lz = 0 (no Hastings term), a_i != b_i
+ * (s the active half-ensemble, c the other one; differential evolution, ter Braak 2006, on the split ensemble
+ * as emcee 3's DEMove).  Acceptance is psfmc_stretch_run's, (lz + lnp_new) - lnp > ln u.
+ *   psfmc_move_run        psfmc_stretch_run's arguments (scal in the place of z; partner is a) plus
+ *                           kind [n_iter]             the move codes
+ *                           partner_b [n_iter][2][W/2]   the second partner of a DE proposal
+ *                         One-field contexts.  Every half-step is four stages: the proposal kernel, the
+ *                         record derivation from the proposals, the likelihood pipeline, the accept step; never
+ *                         whole-iteration launches ("speculate") or a captured graph.
+ *   psfmc_move_run_joint  the same for ONE ensemble of joint walkers (psfmc_stretch_run_joint's rules)
+ *   psfmc_stretch_set_moves   between psfmc_stretch_open and the first psfmc_stretch_half_eval: the open run
+ *                         proposes by kind (open's z is scal, its partner is a); without it nothing changes
+ * PSFMC_EINVAL, with a psfmc_last_error text and before anything is uploaded, for: a kind that is no move code;
+ * W < 4 with any DE kind; a partner index outside [0, W/2) (a always, b in DE iterations); a == b in a DE
+ * iteration; a PSFMC_PRIOR_HOST column; a context of several fields (psfmc_move_run, psfmc_stretch_set_moves).
+ */
+#define PSFMC_MOVE_STRETCH 0
+#define PSFMC_MOVE_DE 1
+int psfmc_move_run(psfmc_ctx* ctx, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                   const double* scal, const double* lz, const int* partner, const double* log_u,
+                   const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
+                   long long* naccepted, int accumulate);
+int psfmc_move_run_joint(psfmc_ctx* ctx, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                         const double* scal, const double* lz, const int* partner, const double* log_u,
+                         const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
+                         long long* naccepted, int accumulate);
+int psfmc_stretch_set_moves(psfmc_ctx* ctx, const int* kind, const int* partner_b);
+
+/*
  * Parallel tempering (no reference counterpart; the contract is psfmc_amd/sampler.py's
  * TemperedEnsembleSampler, which these calls reproduce bit for bit).  One-field contexts with every prior
  * on the device; multi-field and joint contexts and PSFMC_PRIOR_HOST columns return PSFMC_EINVAL.

@@ -260,6 +260,11 @@ struct psfmc_ctx {
         int W = 0, n_iter = 0;
         int F = 1;                // ensembles in the run (psfmc_stretch_run_fields: one per field)
         bool store = false, open = false;
+        // proposal moves (psfmc_move_run, psfmc_stretch_set_moves): the move of every iteration and the DE
+        // moves' second partner; `moves`: this run forms its proposals with k_move_propose
+        int *kind = nullptr, *partner_b = nullptr;
+        size_t cap_kind = 0, cap_pb = 0;
+        bool moves = false;
     } stretch;
     // parallel-tempering state (psfmc_pt_run): one grow-only allocation carved per call
     unsigned char* pt_blob = nullptr;
@@ -1444,7 +1449,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_layout_blob, c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
-                    c->stretch.nacc, c->stretch.accflag, c->pt_blob, c->d_integ_flags, c->d_integ_par,
+                    c->stretch.nacc, c->stretch.accflag, c->stretch.kind, c->stretch.partner_b, c->pt_blob, c->d_integ_flags, c->d_integ_par,
                     c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
                     c->d_spi_par, c->d_rad_kinds, c->d_rad_par, c->d_mean_flags};
     for (void* p : bufs)
@@ -3091,6 +3096,7 @@ static int stretch_upload(psfmc_ctx* c, int W, int n_iter, const double* pos, co
         RC_TRY(grow(&S.lnchain, &S.cap_lnchain, WF * n_iter));
     }
     S.W = W; S.n_iter = n_iter; S.F = F; S.store = store && n_iter; S.open = true;
+    S.moves = false;                                          // (moves_upload sets it for the runs that propose by kind)
     if (n_rand) {
         HIP_TRY(hipMemcpyAsync(S.rand, z, n_rand * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(S.rand + n_rand, lz, n_rand * sizeof(double), hipMemcpyHostToDevice, st));
@@ -3305,6 +3311,106 @@ extern "C" int psfmc_stretch_run_fields(psfmc_ctx* c, int W, int n_iter, double*
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     return stretch_run_impl(c, c->n_fields, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, chain,
                             lnprob_chain, naccepted, accumulate);
+}
+
+// ---------------------------------------------------------------------------
+// proposal moves (include/psfmc_hip.h psfmc_move_run): every iteration proposes with the move kind[it] names,
+// the stretch move or differential evolution.  A half-step is four stages: k_move_propose writes the
+// proposals to S.q, k_theta_prep derives their records from S.q (its "theta is given" mode), the likelihood
+// pipeline, and k_stretch_finish as it is (the caller's lz is 0 for a DE half-step: no Hastings term).  No
+// whole-iteration launches and no hipGraph here: a DE proposal of the second half depends on the outcomes of
+// two walkers of the first.
+// ---------------------------------------------------------------------------
+// the indices are checked on the host before anything is uploaded: they address the positions on the device
+static int moves_check(int W, int n_iter, const int* kind, const int* partner, const int* partner_b) {
+    if (n_iter && (!kind || !partner || !partner_b)) return fail(PSFMC_EINVAL, "NULL buffer");
+    const int half = W / 2;
+    for (int it = 0; it < n_iter; ++it) {
+        const int k = kind[it];
+        if (k != MOVE_STRETCH && k != MOVE_DE)
+            return fail(PSFMC_EINVAL, "kind[%d] = %d is not a move (0 stretch, 1 differential evolution)", it, k);
+        if (k == MOVE_DE && W < 4)
+            return fail(PSFMC_EINVAL, "a differential-evolution move needs W >= 4 (two distinct partners in each "
+                        "half-ensemble); W = %d", W);
+        for (int j = 0; j < 2 * half; ++j) {
+            const size_t i = (size_t)it * 2 * half + j;
+            const int a = partner[i];
+            if (a < 0 || a >= half)
+                return fail(PSFMC_EINVAL, "partner index %d out of range [0, %d) at iteration %d", a, half, it);
+            if (k != MOVE_DE) continue;                       // (partner_b is not read for a stretch move)
+            const int b = partner_b[i];
+            if (b < 0 || b >= half)
+                return fail(PSFMC_EINVAL, "partner index %d out of range [0, %d) at iteration %d", b, half, it);
+            if (a == b)
+                return fail(PSFMC_EINVAL, "the two partners of a differential-evolution proposal must differ "
+                            "(a == b == %d at iteration %d)", a, it);
+        }
+    }
+    return PSFMC_OK;
+}
+
+// after stretch_upload: the kinds and second partners of the run's iterations
+static int moves_upload(psfmc_ctx* c, const int* kind, const int* partner_b, hipStream_t st) {
+    psfmc_ctx::Stretch& S = c->stretch;
+    const size_t n_rand = (size_t)S.n_iter * S.W;
+    RC_TRY(grow(&S.kind, &S.cap_kind, (size_t)S.n_iter));
+    RC_TRY(grow(&S.partner_b, &S.cap_pb, n_rand));
+    if (S.n_iter) {
+        HIP_TRY(hipMemcpyAsync(S.kind, kind, (size_t)S.n_iter * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(S.partner_b, partner_b, n_rand * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    S.moves = true;
+    S.spec = false;
+    return PSFMC_OK;
+}
+
+// the proposals of half `h` at iteration `it` -> S.q
+static void move_propose(psfmc_ctx* c, int it, int h, hipStream_t st) {
+    psfmc_ctx::Stretch& S = c->stretch;
+    const int half = S.W / 2, P = c->layout.n_params;
+    hipLaunchKernelGGL(k_move_propose, dim3((half * P + kMoveThreads - 1) / kMoveThreads), dim3(kMoveThreads), 0, st,
+                       S.pos, S.q, S.kind, S.partner, S.partner_b, S.rand, it, half, h, P);
+}
+
+// ... and their priors and prep records (stretch_propose's results, by k_theta_prep's "theta is given" mode)
+static void move_propose_records(psfmc_ctx* c, int it, int h, hipStream_t st) {
+    move_propose(c, it, h, st);
+    launch_theta_prep(c, c->stretch.W / 2, c->stretch.q, nullptr, nullptr, st, StretchIn{});
+}
+
+extern "C" int psfmc_move_run(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                              const double* scal, const double* lz, const int* partner, const double* log_u,
+                              const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
+                              long long* naccepted, int accumulate) {
+    RC_TRY(stretch_check(c, W, 1));                  // one field, a layout, W even, every prior on the device
+    if (n_iter < 0 || !pos || !lnprob || !naccepted || (n_iter && (!scal || !lz || !partner || !log_u)))
+        return fail(PSFMC_EINVAL, "NULL buffer");
+    RC_TRY(moves_check(W, n_iter, kind, partner, partner_b));
+    const int half = W / 2;
+    hipStream_t st = c->stream;
+    psfmc_ctx::Stretch& S = c->stretch;
+    RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, naccepted,
+                          chain != nullptr, st));
+    int rc = moves_upload(c, kind, partner_b, st);
+    if (rc == PSFMC_OK && !lnprob_valid) rc = stretch_eval_positions(c, st);
+    if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
+    for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
+        for (int h = 0; h < 2 && rc == PSFMC_OK; ++h) {
+            move_propose_records(c, it, h, st);
+            rc = run_pipeline(c, half, c->d_skip, st);
+            if (rc == PSFMC_OK) stretch_accept(c, it, h, nullptr, false, st);
+        }
+        if (rc == PSFMC_OK && accumulate) {
+            launch_theta_prep(c, W, S.pos, nullptr, nullptr, st, StretchIn{});
+            rc = accumulate_from_prep(c, W, st, 0, 1, W);
+        }
+    }
+    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
+    (void)hipStreamSynchronize(st);
+    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
+    S.open = false;
+    S.moves = false;
+    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -3610,14 +3716,17 @@ extern "C" int psfmc_eval_theta_joint(psfmc_ctx* c, int W, const double* theta, 
 // each proposal's fields.  Plain half-steps only (no whole-iteration launches, no hipGraph): the chain is
 // the one of psfmc_stretch_run's rules either way.  accumulate: after every iteration, each field's
 // posterior-image sums get the current positions mapped to that field.
-extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
-                                       int lnprob_valid, const double* z, const double* lz, const int* partner,
-                                       const double* log_u, double* chain, double* lnprob_chain,
-                                       long long* naccepted, int accumulate) {
+// moves (psfmc_move_run_joint; kind and partner_b of psfmc_move_run): k_move_propose forms each half-step's
+// proposals and k_joint_prior takes them as given vectors (the mode of psfmc_eval_theta_joint)
+static int joint_run_impl(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
+                          int lnprob_valid, const double* z, const double* lz, const int* partner,
+                          const double* log_u, bool moves, const int* kind, const int* partner_b, double* chain,
+                          double* lnprob_chain, long long* naccepted, int accumulate) {
     RC_TRY(joint_check(c, W));
     if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
     if (n_iter < 0 || !pos || !lnprob || !naccepted || (n_iter && (!z || !lz || !partner || !log_u)))
         return fail(PSFMC_EINVAL, "NULL buffer");
+    if (moves) RC_TRY(moves_check(W, n_iter, kind, partner, partner_b));
     HIP_TRY(hipSetDevice(c->device));
     const int F = c->n_fields, half = W / 2, P = c->layout.n_params;
     hipStream_t st = c->stream;
@@ -3625,15 +3734,22 @@ extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* 
     RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
                           chain != nullptr, st));
     S.spec = false;
-    int rc = PSFMC_OK;
-    if (!lnprob_valid) rc = eval_theta_joint(c, W, S.pos, S.lnp, st);
+    int rc = moves ? moves_upload(c, kind, partner_b, st) : PSFMC_OK;
+    if (rc == PSFMC_OK && !lnprob_valid) rc = eval_theta_joint(c, W, S.pos, S.lnp, st);
     if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
     const size_t n_rand = (size_t)n_iter * W;                  // per random array (S.rand: z | lz | log u)
     for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
         for (int h = 0; h < 2 && rc == PSFMC_OK; ++h) {
-            hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
-                               c->joint.d_fields, F, nullptr, S.pos, S.q, S.rand, S.partner, it, half, h,
-                               c->joint.d_lp, half);
+            if (moves) {
+                move_propose(c, it, h, st);
+                hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
+                                   c->joint.d_fields, F, S.q, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
+                                   c->joint.d_lp, half);
+            } else {
+                hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
+                                   c->joint.d_fields, F, nullptr, S.pos, S.q, S.rand, S.partner, it, half, h,
+                                   c->joint.d_lp, half);
+            }
             launch_theta_prep_joint(c, half, S.q, c->joint.d_lp, st);
             rc = run_pipeline(c, half * F, c->d_skip, st);
             if (rc != PSFMC_OK) break;
@@ -3652,7 +3768,25 @@ extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* 
     (void)hipStreamSynchronize(st);
     if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
     S.open = false;
+    S.moves = false;
     return rc;
+}
+
+extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
+                                       int lnprob_valid, const double* z, const double* lz, const int* partner,
+                                       const double* log_u, double* chain, double* lnprob_chain,
+                                       long long* naccepted, int accumulate) {
+    return joint_run_impl(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, false, nullptr, nullptr,
+                          chain, lnprob_chain, naccepted, accumulate);
+}
+
+// psfmc_move_run for ONE ensemble of W joint walkers
+extern "C" int psfmc_move_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                                    const double* scal, const double* lz, const int* partner, const double* log_u,
+                                    const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
+                                    long long* naccepted, int accumulate) {
+    return joint_run_impl(c, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, true, kind, partner_b,
+                          chain, lnprob_chain, naccepted, accumulate);
 }
 
 // ---------------------------------------------------------------------------
@@ -3675,6 +3809,22 @@ extern "C" int psfmc_stretch_open(psfmc_ctx* c, int W, int n_iter, const double*
     return PSFMC_OK;
 }
 
+// Between psfmc_stretch_open and the first psfmc_stretch_half_eval: the open run proposes by kind[it] (the
+// arrays psfmc_move_run adds to psfmc_stretch_run's; open's z is the moves' scalar, its partner their first
+// partner).  psfmc_stretch_half_eval then forms the half's proposals with k_move_propose.
+extern "C" int psfmc_stretch_set_moves(psfmc_ctx* c, const int* kind, const int* partner_b) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    psfmc_ctx::Stretch& S = c->stretch;
+    if (!S.open) return fail(PSFMC_EINVAL, "psfmc_stretch_open has not been called");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> partner((size_t)S.n_iter * S.W);          // the first partners, as open uploaded them
+    HIP_TRY(hipMemcpy(partner.data(), S.partner, partner.size() * sizeof(int), hipMemcpyDeviceToHost));
+    RC_TRY(moves_check(S.W, S.n_iter, kind, partner.data(), partner_b));
+    RC_TRY(moves_upload(c, kind, partner_b, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PSFMC_OK;
+}
+
 static int stretch_step_check(psfmc_ctx* c, int it, int h) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (!c->stretch.open) return fail(PSFMC_EINVAL, "psfmc_stretch_open has not been called");
@@ -3691,7 +3841,8 @@ extern "C" int psfmc_stretch_half_eval(psfmc_ctx* c, int it, int h, int lo, int 
     if (n > 0 && !d_newlnp_block) return fail(PSFMC_EINVAL, "NULL output");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    stretch_propose(c, it, h, false, st);
+    if (c->stretch.moves) move_propose_records(c, it, h, st);     // (psfmc_stretch_set_moves)
+    else stretch_propose(c, it, h, false, st);
     if (n > 0) {
         RC_TRY(run_pipeline(c, n, c->d_skip, st, lo));
         hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st,

@@ -1040,4 +1040,43 @@ k_joint_prior(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_field
 __global__ void k_stretch_next(int* __restrict__ d_iter) { *d_iter += 1; }
 #endif
 
+// ---------------------------------------------------------------------------
+// proposal moves (psfmc_move_run, psfmc_stretch_set_moves, psfmc_move_run_joint; the contract is sampler.py's
+// EnsembleSampler(moves=...)).  kind[it] names the move of BOTH half-steps of iteration it:
+//   MOVE_STRETCH  q_i = c[a_i] - z_i (c[a_i] - s_i)          (stretch_point; scal = z, b unread)
+//   MOVE_DE       q_i = s_i + g_i (c[a_i] - c[b_i])          (differential evolution; scal = g, a_i != b_i)
+// s = half h of pos, c = the other half.  The DE proposal is three roundings -- the difference, the product,
+// the sum -- as the numpy expression of the host contract; no FMA contraction.
+// ---------------------------------------------------------------------------
+constexpr int MOVE_STRETCH = 0, MOVE_DE = 1;
+constexpr int kMoveThreads = 256;
+
+__device__ inline double de_point(double s, double ca, double cb, double g) {
+#pragma clang fp contract(off)
+    const double diff = ca - cb;
+    const double step = g * diff;
+    return s + step;
+}
+
+#if PSFMC_PART == 0          /* not a template: defined in the API part only */
+// The proposals q [half][P] of half h at iteration `it`: one thread per (walker, parameter) element, grid-stride
+// over half P elements (launch: ceil(half P / kMoveThreads) x kMoveThreads).  a, b, scal: [n_iter][2][half].
+__global__ void __launch_bounds__(kMoveThreads)
+k_move_propose(const double* __restrict__ pos, double* __restrict__ q, const int* __restrict__ kind,
+               const int* __restrict__ a, const int* __restrict__ b, const double* __restrict__ scal,
+               int it, int half, int h, int P) {
+    const int n = half * P;
+    const size_t off = ((size_t)it * 2 + h) * half;
+    const int move = kind[it];                                   // the same in every thread
+    const double* s = pos + (size_t)h * half * P;
+    const double* c = pos + (size_t)(1 - h) * half * P;
+    for (int i = blockIdx.x * kMoveThreads + threadIdx.x; i < n; i += gridDim.x * kMoveThreads) {
+        const int w = i / P, d = i - w * P;
+        const double ca = c[(size_t)a[off + w] * P + d];
+        const double g = scal[off + w];
+        q[i] = move == MOVE_DE ? de_point(s[i], ca, c[(size_t)b[off + w] * P + d], g) : stretch_point(s[i], ca, g);
+    }
+}
+#endif
+
 }  // namespace psfmc

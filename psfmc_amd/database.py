@@ -19,6 +19,7 @@ _COMMENTS = {'MCITER': 'number of retained samples',
              'MCCONVRG': 'Has MCMC sampler converged?',
              'MCFIELDS': 'number of fields fitted jointly',
              'MCACCEPT': 'Acceptance fraction (avg of all walkers)',
+             'MCMOVES': 'proposal moves and their weights',
              'MAPWLKR': 'Walker index of maximum posterior model',
              'MAPSAMP': 'Sample index of maximum posterior model',
              'PSFIMG': 'PSF image of maximum posterior model'}

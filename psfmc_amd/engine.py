@@ -225,6 +225,13 @@ def load_library():
     lib.psfmc_stretch_open.restype = ci
     lib.psfmc_stretch_open.argtypes = [vp, ci, ci, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ip,
                                        _c_double_p, llp, ci]
+    lib.psfmc_move_run.restype = ci
+    lib.psfmc_move_run.argtypes = [vp, ci, ci, _c_double_p, _c_double_p, ci, _c_double_p, _c_double_p,
+                                   ip, _c_double_p, ip, ip, _c_double_p, _c_double_p, llp, ci]
+    lib.psfmc_move_run_joint.restype = ci
+    lib.psfmc_move_run_joint.argtypes = lib.psfmc_move_run.argtypes
+    lib.psfmc_stretch_set_moves.restype = ci
+    lib.psfmc_stretch_set_moves.argtypes = [vp, ip, ip]
     lib.psfmc_stretch_half_eval.restype = ci
     lib.psfmc_stretch_half_eval.argtypes = [vp, ci, ci, ci, ci, vp, vp]
     lib.psfmc_stretch_half_accept.restype = ci
@@ -320,6 +327,33 @@ def _prior_table(family, params):
 
 def _f64(arr):
     return np.ascontiguousarray(arr, dtype=np.float64)
+
+
+MOVE_STRETCH, MOVE_DE = 0, 1          # include/psfmc_hip.h PSFMC_MOVE_*
+
+
+def _move_run(fn, ctx, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store, accumulate):
+    """The arrays of psfmc_move_run / psfmc_move_run_joint (`fn`) shaped and the call made: (rc, (pos, lnprob,
+    chain [W, n_iter, P] | None, lnprob_chain [W, n_iter] | None)); naccepted is updated."""
+    pos = np.array(pos, dtype=np.float64, order='C')
+    n_w, n_p = pos.shape
+    n_iter = int(np.shape(scal)[0])
+    have = lnprob is not None
+    lnp = np.array(lnprob, dtype=np.float64) if have else np.empty(n_w)
+    scal, lz, log_u = (_f64(a).reshape(n_iter, 2, n_w // 2) for a in (scal, lz, log_u))
+    partner, partner_b = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
+                          for a in (partner, partner_b))
+    kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(n_iter)
+    if naccepted.dtype != np.int64 or naccepted.shape != (n_w,) or not naccepted.flags.c_contiguous:
+        raise ValueError('naccepted must be a contiguous int64 [W]')
+    chain = np.empty((n_w, n_iter, n_p)) if store and n_iter else None
+    lnchain = np.empty((n_w, n_iter)) if store and n_iter else None
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    rc = fn(ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(scal), _dp(lz), ipt(partner), _dp(log_u),
+            ipt(kind), ipt(partner_b), _dp(chain) if chain is not None else None,
+            _dp(lnchain) if lnchain is not None else None,
+            naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate)))
+    return rc, (pos, lnp, chain, lnchain)
 
 
 def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
@@ -690,6 +724,17 @@ class Context(object):
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
         return pos, lnp, chain, lnchain
 
+    def move_run(self, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store=True,
+                 accumulate=False):
+        """`stretch_run` with the move of every iteration named (include/psfmc_hip.h psfmc_move_run): kind int32
+        [n_iter] (MOVE_STRETCH / MOVE_DE), partner_b [n_iter, 2, W/2] the DE moves' second partner; scal is z
+        for a stretch iteration and g for a DE one, lz its Hastings term (0 for DE).  Returns what `stretch_run`
+        returns."""
+        rc, out = _move_run(self._lib.psfmc_move_run, self._ctx, pos, lnprob, scal, lz, partner, log_u, kind,
+                            partner_b, naccepted, store, accumulate)
+        self._check(rc)
+        return out
+
     def loglike_prior_theta(self, theta, extra_lnprior=None):
         """[W, P] raw parameter vectors -> (lnlike [W], lnprior [W]) as the device computes them
         (psfmc_eval_theta_split): lnlike -inf outside the priors or where it is not finite."""
@@ -765,6 +810,15 @@ class Context(object):
             partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(log_u),
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(store))))
         self._stretch_shape = (n_w, n_iter, pos.shape[1], bool(store))
+
+    def stretch_set_moves(self, kind, partner_b):
+        """After `stretch_open`, before the first `stretch_half_eval`: the open run proposes by kind
+        (psfmc_stretch_set_moves; the arrays `move_run` adds to `stretch_run`'s)."""
+        n_w, n_iter = self._stretch_shape[:2]
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(n_iter)
+        partner_b = np.ascontiguousarray(partner_b, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
+        ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self._check(self._lib.psfmc_stretch_set_moves(self._ctx, ipt(kind), ipt(partner_b)))
 
     def stretch_half_eval(self, it, h, lo, n, d_out, stream=None):
         self._check(self._lib.psfmc_stretch_half_eval(
@@ -1084,6 +1138,14 @@ class FieldSetContext(object):
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
         return pos, lnp, chain, lnchain
 
+    def move_run_joint(self, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store=True,
+                       accumulate=False):
+        """`Context.move_run` for ONE ensemble of joint walkers (psfmc_move_run_joint)."""
+        rc, out = _move_run(self._lib.psfmc_move_run_joint, self._ctx, pos, lnprob, scal, lz, partner, log_u,
+                            kind, partner_b, naccepted, store, accumulate)
+        self._check(rc)
+        return out
+
     def joint_view(self):
         """The interface a `JointModel` and `DeviceEnsembleSampler` use: `JointView`."""
         return JointView(self)
@@ -1267,6 +1329,11 @@ class JointView(object):
     def stretch_run(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True, accumulate=False):
         return self.owner.stretch_run_joint(pos, lnprob, z, lz, partner, log_u, naccepted, store=store,
                                             accumulate=accumulate)
+
+    def move_run(self, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store=True,
+                 accumulate=False):
+        return self.owner.move_run_joint(pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted,
+                                         store=store, accumulate=accumulate)
 
     def accumulated(self, field):
         return self.owner.accumulated(field)

@@ -15,7 +15,7 @@ import numpy as np
 from .analysis import check_convergence_autocorr, save_posterior_images, default_filetypes
 from .database import Table, save_database, load_database
 from .models import JointModel, MultiComponentModel
-from .sampler import EnsembleSampler, DeviceEnsembleSampler
+from .sampler import EnsembleSampler, DeviceEnsembleSampler, moves_label
 from .utils import print_progress
 
 
@@ -41,6 +41,16 @@ def _rank_group(group, device):
             return None
         raise
     return None if ranks.single else ranks
+
+
+def _takes_moves(cls):
+    """Whether a sampler class's constructor has a `moves` keyword."""
+    import inspect
+    try:
+        params = inspect.signature(cls.__init__).parameters
+    except (TypeError, ValueError):
+        return False
+    return 'moves' in params
 
 
 def _burn_and_sample(sampler, model, param_vec, burn, iterations, max_iterations, convergence_check,
@@ -79,7 +89,7 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
                       burn=0, chains=None, max_iterations=1,
                       convergence_check=check_convergence_autocorr, sampler_class=None,
                       device=0, backend='auto', random_state=None, accumulate=True, quiet=False,
-                      group='auto'):
+                      group='auto', moves=None):
     """Model a galaxy's surface brightness with MCMC.
 
     model_file, output_name, write_fits, iterations, burn, chains, max_iterations,
@@ -90,7 +100,11 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
     torch.distributed process group ('auto': the default group if there is one; or a group
     object) the walkers of every half-step are sharded over the ranks, one process per GPU
     (`device` should then be the rank's LOCAL_RANK); rank 0 draws the start positions and the
-    sampler's random state and writes the outputs, every rank returns the same database."""
+    sampler's random state and writes the outputs, every rank returns the same database.
+    `moves`: the sampler's proposal moves (`sampler.StretchMove`, `sampler.DEMove`, or a list of (move, weight)
+    pairs; None: the stretch move, outputs byte for byte as without the keyword).  The database header then
+    records them as MCMOVES, e.g. 'stretch:0.5,de:0.5'.  A `sampler_class` that does not take a `moves` keyword
+    raises ValueError."""
     if output_name is None:
         output_name = 'out_' + model_file.replace('.py', '')
     output_name += '_{}'
@@ -113,8 +127,11 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
         mc_model.engine
         cls = EnsembleSampler if mc_model._host_priors else DeviceEnsembleSampler
     device_acc = False
+    extra = {} if moves is None else {'moves': moves}
+    if extra and not _takes_moves(cls):
+        raise ValueError('sampler_class {} does not take a `moves` keyword'.format(getattr(cls, '__name__', cls)))
     if cls is DeviceEnsembleSampler:
-        sampler = cls(chains, mc_model, group=ranks)
+        sampler = cls(chains, mc_model, group=ranks, **extra)
         device_acc = accumulate
     elif cls is EnsembleSampler:
         if ranks:
@@ -122,11 +139,11 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
             evaluate = ShardedLogPosterior(mc_model, group=ranks)
         else:
             evaluate = mc_model.log_posterior_batch
-        sampler = cls(chains, mc_model.num_params, batch_lnpostfn=evaluate)
+        sampler = cls(chains, mc_model.num_params, batch_lnpostfn=evaluate, **extra)
     else:                      # a real emcee: batch through its pool hook
         from .batch import BatchLogPosterior
         sampler = cls(chains, mc_model.num_params, mc_model.log_posterior,
-                      kwargs={'model': mc_model}, pool=BatchLogPosterior(mc_model).as_pool())
+                      kwargs={'model': mc_model}, pool=BatchLogPosterior(mc_model).as_pool(), **extra)
     if random_state is not None:
         if isinstance(random_state, (int, np.integer)):
             random_state = np.random.RandomState(int(random_state)).get_state()
@@ -151,6 +168,8 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
         meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
                             ('MCCHAINS', chains), ('MCCONVRG', bool(converged)),
                             ('MCACCEPT', float(sampler.acceptance_fraction.mean()))])
+        if moves is not None:
+            meta['MCMOVES'] = moves_label(moves)
         database = save_database(sampler, mc_model, db_name, meta_dict=meta) if writer else None
         if ranks is not None:
             ranks.broadcast_object(True)          # the file is complete
@@ -270,7 +289,7 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
 
 def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=default_filetypes, iterations=0,
                      burn=0, chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
-                     device=0, random_state=None, accumulate=True, quiet=False):
+                     device=0, random_state=None, accumulate=True, quiet=False, moves=None):
     """`model_galaxy_mcmc` for ONE model fitted jointly to several exposures of the same object
     (`models.JointModel`: each field its own data, PSFs, constants and zeropoint; the parameters not named
     in `per_field` shared).  The reference's flow -- burn-in, reset, sampling with posterior images
@@ -281,7 +300,8 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
     Outputs: ONE trace database `<output_name>_db.fits` with the joint columns (metadata MCFIELDS = number
     of fields), and each field's posterior images `<output_name>_f<k>_<type>.fits` at that field's shape
     (what `save_posterior_images` writes for the field's model and the database's rows mapped to the
-    field's own parameter names).  An existing database skips sampling.  Returns (JointModel, database)."""
+    field's own parameter names).  An existing database skips sampling.  `moves`: as `model_galaxy_mcmc`'s
+    (recorded as MCMOVES).  Returns (JointModel, database)."""
     if output_name is None:
         output_name = 'out_joint_' + str(model_files[0]).replace('.py', '')
     joint = model_files if isinstance(model_files, JointModel) else None
@@ -298,7 +318,7 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
                          'two halves'.format(chains))
     if chains * n_f > joint._max_walkers:
         raise ValueError('{} fields x {} chains exceed max_walkers={}'.format(n_f, chains, joint._max_walkers))
-    sampler = DeviceEnsembleSampler(chains, joint)
+    sampler = DeviceEnsembleSampler(chains, joint, moves=moves)
     if random_state is not None:
         if isinstance(random_state, (int, np.integer)):
             random_state = np.random.RandomState(int(random_state)).get_state()
@@ -312,6 +332,8 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
         meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
                             ('MCCONVRG', bool(converged)),
                             ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f)])
+        if moves is not None:
+            meta['MCMOVES'] = moves_label(moves)
         database = save_database(sampler, joint, db_name, meta_dict=meta)
     else:
         if not quiet:

@@ -25,7 +25,8 @@ import threading
 import numpy as np
 
 __all__ = ['EnsembleSampler', 'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler',
-           'DeviceTemperedSampler', 'default_betas', 'AutocorrError', 'integrated_time']
+           'DeviceTemperedSampler', 'default_betas', 'AutocorrError', 'integrated_time',
+           'StretchMove', 'DEMove', 'moves_label']
 
 
 class AutocorrError(Exception):
@@ -76,9 +77,123 @@ class _Wrapped(object):
         return self.f(x, *self.args, **self.kwargs)
 
 
+class StretchMove(object):
+    """The Goodman & Weare stretch move, the proposal of `EnsembleSampler(moves=None)`: per half-step
+    `z = ((a-1) rand(half) + 1)^2 / a`, `partner = randint(half, size=half)`, `ln u = log(rand(half))`;
+    `q_i = c[partner_i] - z_i (c[partner_i] - s_i)`, accepted where `(P-1) ln z + lnp_new - lnp > ln u`."""
+
+    kind, name = 0, 'stretch'               # (the library's PSFMC_MOVE_STRETCH)
+
+    def __init__(self, a=2.0):
+        self.a = float(a)
+
+    def check(self, nwalkers):
+        pass
+
+    def draw(self, rs, half, dim):
+        """One half-step's random numbers -> (scalar [half], Hastings term [half], a [half], b [half], ln u
+        [half]); b is not used."""
+        z = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
+        a = rs.randint(half, size=(half,))
+        log_u = np.log(rs.rand(half))
+        return z, (dim - 1.0) * np.log(z), a, np.zeros(half, dtype=a.dtype), log_u
+
+    @staticmethod
+    def propose(s, c, z, a, b):
+        return c[a] - z[:, np.newaxis] * (c[a] - s)
+
+
+class DEMove(object):
+    """Differential evolution (ter Braak 2006) on the split ensemble, as emcee 3's `DEMove`: walker i of the
+    active half s takes two DISTINCT walkers a_i != b_i of the complementary half c and proposes
+    `q_i = s_i + g_i (c[a_i] - c[b_i])`.  The proposal is symmetric: the Hastings term is 0 and it is accepted
+    where `lnp_new - lnp > ln u`.  `g_i = gamma0 (1 + sigma (2 u1_i - 1))`, `gamma0` by default
+    `2.38 / sqrt(2 P)`; with probability `jump` g_i is exactly 1.0 instead (ter Braak's mode-jumping step).
+
+    The jitter of g is UNIFORM, not emcee's normal, on purpose: the draws then use `rand` and `randint` only,
+    and `DeviceEnsembleSampler._state_snapshotter` relies on the generator's Gaussian cache never being touched.
+
+    Draw order per half-step, whatever the options: `rand(half)` -> u1, `rand(half)` -> the jump selector (g_i = 1
+    where it is < jump), `randint(half, size=half)` -> a, `randint(half - 1, size=half)` -> b then `b += (b >= a)`,
+    `rand(half)` -> u.  The proposal is three roundings, never fused: `diff = c[a] - c[b]`, `step = g * diff`,
+    `q = s + step`.  Needs two walkers to choose from in each half: nwalkers >= 4."""
+
+    kind, name = 1, 'de'                    # (the library's PSFMC_MOVE_DE)
+
+    def __init__(self, sigma=1e-5, gamma0=None, jump=0.0):
+        self.sigma = float(sigma)
+        self.gamma0 = None if gamma0 is None else float(gamma0)
+        self.jump = float(jump)
+        if not (np.isfinite(self.sigma) and 0.0 <= self.jump <= 1.0) or \
+                (self.gamma0 is not None and not np.isfinite(self.gamma0)):
+            raise ValueError('DEMove needs finite sigma and gamma0, and jump in [0, 1]')
+
+    def check(self, nwalkers):
+        if nwalkers < 4:
+            raise ValueError('DEMove needs at least 4 walkers (two distinct partners in each half-ensemble); '
+                             'got {}'.format(nwalkers))
+
+    def draw(self, rs, half, dim):
+        """One half-step's random numbers -> (g [half], Hastings term (0) [half], a [half], b [half], ln u [half])."""
+        u1 = rs.rand(half)
+        jump = rs.rand(half)
+        a = rs.randint(half, size=(half,))
+        b = rs.randint(half - 1, size=(half,))
+        b += (b >= a)
+        log_u = np.log(rs.rand(half))
+        gamma0 = self.gamma0 if self.gamma0 is not None else 2.38 / np.sqrt(2.0 * dim)
+        g = gamma0 * (1.0 + self.sigma * (2.0 * u1 - 1.0))
+        g[jump < self.jump] = 1.0
+        return g, np.zeros(half), a, b, log_u
+
+    @staticmethod
+    def propose(s, c, g, a, b):
+        diff = c[a] - c[b]
+        step = g[:, np.newaxis] * diff
+        return s + step
+
+
+def _parse_moves(moves, nwalkers):
+    """`moves=` -> (list of moves, cumulative normalised weights): a single move, or a list of (move, weight)."""
+    if hasattr(moves, 'draw'):
+        pairs = [(moves, 1.0)]
+    else:
+        try:
+            pairs = [(m, float(w)) for m, w in moves]
+        except (TypeError, ValueError):
+            raise ValueError('moves must be None, a move, or a list of (move, weight) pairs')
+    if not pairs or not all(hasattr(m, 'draw') and hasattr(m, 'propose') for m, _ in pairs):
+        raise ValueError('moves must be None, a move, or a list of (move, weight) pairs')
+    weights = np.array([w for _, w in pairs], dtype=np.float64)
+    if not np.all(np.isfinite(weights)) or np.any(weights < 0) or not weights.sum() > 0:
+        raise ValueError('move weights must be finite, non-negative and not all zero')
+    for m, _ in pairs:
+        m.check(nwalkers)
+    cum = np.cumsum(weights / weights.sum())
+    cum[-1] = 1.0
+    return [m for m, _ in pairs], cum
+
+
+def moves_label(moves):
+    """'stretch:0.5,de:0.5': the moves and their normalised weights, as the database header's MCMOVES records
+    them; None for moves=None."""
+    if moves is None:
+        return None
+    pairs = [(moves, 1.0)] if hasattr(moves, 'draw') else [(m, float(w)) for m, w in moves]
+    total = sum(w for _, w in pairs)
+    return ','.join('{}:{:g}'.format(getattr(m, 'name', type(m).__name__), w / total) for m, w in pairs)
+
+
 class EnsembleSampler(object):
+    """moves: None (the stretch move with this sampler's `a`: emcee 2.2.1's sampler, draw for draw), a single
+    move (`StretchMove`, `DEMove`), or a list of (move, weight) pairs.  With more than one move ONE extra `rand()`
+    is drawn at the start of every iteration and selects, by cumulative normalised weight, the move of BOTH
+    half-steps of that iteration; with exactly one move no selector is drawn.  Each half-step then draws in its
+    move's own order (see the move classes) and accepts where `(hastings + lnp_new) - lnp > ln u`."""
+
     def __init__(self, nwalkers, dim, lnpostfn=None, a=2.0, args=None, kwargs=None,
-                 threads=1, pool=None, live_dangerously=False, batch_lnpostfn=None):
+                 threads=1, pool=None, live_dangerously=False, batch_lnpostfn=None, moves=None):
+        self._moves, self._move_cum = (None, None) if moves is None else _parse_moves(moves, int(nwalkers))
         if nwalkers % 2:
             raise ValueError('The number of walkers must be even.')
         if nwalkers < 2 * dim and not live_dangerously:
@@ -186,6 +301,22 @@ class EnsembleSampler(object):
         accept = lnpdiff > np.log(self._random.rand(len(lnpdiff)))
         return q, newlnprob, accept, blob
 
+    def _select_move(self):
+        """The move of the coming iteration (`moves=`): one `rand()` when there is more than one to choose from."""
+        if len(self._moves) == 1:
+            return 0
+        r = self._random.rand()
+        return min(int(np.searchsorted(self._move_cum, r, side='right')), len(self._moves) - 1)
+
+    def _propose_move(self, move, p0, p1, lnprob0):
+        s, c = np.atleast_2d(p0), np.atleast_2d(p1)
+        scal, hastings, a, b, log_u = move.draw(self._random, len(s), self.dim)
+        q = move.propose(s, c, scal, a, b)
+        newlnprob, blob = self._get_lnprob(q)
+        with np.errstate(invalid='ignore'):
+            accept = hastings + newlnprob - lnprob0 > log_u
+        return q, newlnprob, accept, blob
+
     # -- sampling ----------------------------------------------------------------
     def sample(self, p0, lnprob0=None, rstate0=None, blobs0=None, iterations=1, thin=1,
                storechain=True):
@@ -211,8 +342,12 @@ class EnsembleSampler(object):
         first, second = slice(halfk), slice(halfk, self.k)
         for i in range(int(iterations)):
             self.iterations += 1
+            move = None if self._moves is None else self._moves[self._select_move()]
             for s0, s1 in ((first, second), (second, first)):
-                q, newlnp, acc, blob = self._propose_stretch(p[s0], p[s1], lnprob[s0])
+                if move is None:
+                    q, newlnp, acc, blob = self._propose_stretch(p[s0], p[s1], lnprob[s0])
+                else:
+                    q, newlnp, acc, blob = self._propose_move(move, p[s0], p[s1], lnprob[s0])
                 if np.any(acc):
                     lnprob[s0][acc] = newlnp[acc]
                     p[s0][acc] = q[acc]
@@ -287,10 +422,17 @@ class DeviceEnsembleSampler(EnsembleSampler):
     Needs a `MultiComponentModel` whose priors all belong to the families the library
     evaluates (uniform, normal, weibull_min, discrete uniform); otherwise use
     `EnsembleSampler(batch_lnpostfn=model.log_posterior_batch)`.
+
+    moves: as `EnsembleSampler`'s (None, a move, or (move, weight) pairs).  With moves given the run goes
+    through `psfmc_move_run` (`psfmc_move_run_joint` for a `JointModel`, `psfmc_stretch_set_moves` with
+    `group`): a proposal kernel per half-step, plain half-steps, never whole-iteration launches.  The chain,
+    `naccepted` and the yielded generator states equal those of `EnsembleSampler(...,
+    batch_lnpostfn=model.log_posterior_batch, moves=moves)` bit for bit.  moves=None launches exactly what it
+    always did.
     """
 
     def __init__(self, nwalkers, model, a=2.0, live_dangerously=False, block=64, accumulate=False,
-                 group=None):
+                 group=None, moves=None):
         from .parallel import RankGroup, ShardedLogPosterior
         ranks = group if isinstance(group, RankGroup) else None
         if ranks is None and group is not None:
@@ -300,13 +442,16 @@ class DeviceEnsembleSampler(EnsembleSampler):
                     else model.log_posterior_batch)
         super(DeviceEnsembleSampler, self).__init__(nwalkers, model.num_params, a=a,
                                                     batch_lnpostfn=evaluate,
-                                                    live_dangerously=live_dangerously)
+                                                    live_dangerously=live_dangerously, moves=moves)
         self.model = model
         self.block = int(block)
         self.accumulate = bool(accumulate)
         if nwalkers > model._max_walkers:
             raise ValueError('model was built for at most {} walkers'.format(model._max_walkers))
         eng = model.engine                # context + layout
+        if moves is not None and not hasattr(type(eng), 'move_run'):
+            raise NotImplementedError('moves= is not available on a {}: the proposal moves serve one-field models and '
+                                      'joint fits (DESIGN.md section 21)'.format(type(eng).__name__))
         if not hasattr(type(eng), 'stretch_run'):
             # (a model of a FieldSet: its context is shared by the set's fields)
             eng.stretch_run()             # raises NotImplementedError naming the FieldSet
@@ -314,9 +459,11 @@ class DeviceEnsembleSampler(EnsembleSampler):
             raise ValueError('priors {} are evaluated on the host: the device sampler cannot be '
                              'used'.format([p.name for p, _ in model._host_priors]))
 
-    def _run_block_sharded(self, pos, lnprob, z, lz, partner, log_u, nacc, store=True, accumulate=False):
+    def _run_block_sharded(self, pos, lnprob, z, lz, partner, log_u, *more, store=True, accumulate=False):
         """One block of iterations with every half-step's proposals sharded over the ranks
-        (include/psfmc_hip.h psfmc_stretch_open / _half_eval / _half_accept / _close)."""
+        (include/psfmc_hip.h psfmc_stretch_open / _half_eval / _half_accept / _close).  more: (nacc,), or with
+        `moves` (kind, partner_b, nacc): the open run then proposes by kind (psfmc_stretch_set_moves)."""
+        nacc = more[-1]
         rg, eng = self.ranks, self.model.engine
         torch = rg.torch
         n_iter, half = int(np.shape(z)[0]), self.k // 2
@@ -326,6 +473,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
             stream = rg.stream_ptr()
             send = torch.zeros(rg.slot(half), dtype=torch.float64, device=rg.device)
             eng.stretch_open(pos, lnprob, z, lz, partner, log_u, nacc, store=store)
+            if len(more) == 3:
+                eng.stretch_set_moves(more[0], more[1])
             for it in range(n_iter):
                 for h in range(2):
                     eng.stretch_half_eval(it, h, lo, hi - lo, send.data_ptr(), stream)
@@ -365,6 +514,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
     def _draw(self, n_iter):
         """Random numbers of n_iter iterations in emcee's order (per half-step:
         rand(Ns) -> z, randint(Nc, Ns) -> partner, rand(Ns) -> ln u)."""
+        if self._moves is not None:
+            return self._draw_moves(n_iter)
         half = self.k // 2
         z = np.empty((n_iter, 2, half))
         partner = np.empty((n_iter, 2, half), dtype=np.int32)
@@ -378,6 +529,28 @@ class DeviceEnsembleSampler(EnsembleSampler):
                 log_u[it, h] = np.log(self._random.rand(half))
             states.append(snap())
         return (z, (self.dim - 1.0) * np.log(z), partner, log_u), states
+
+    def _draw_moves(self, n_iter):
+        """Random numbers of n_iter iterations in the order of `EnsembleSampler(moves=...)`: per iteration the
+        selector `rand()` (more than one move only), then each half-step's draws in its move's order.  Returns
+        the arrays of `Context.move_run`: (scalar, Hastings term, a, ln u, kind [n_iter], b)."""
+        half = self.k // 2
+        scal = np.empty((n_iter, 2, half))
+        lz = np.empty((n_iter, 2, half))
+        partner = np.empty((n_iter, 2, half), dtype=np.int32)
+        partner_b = np.zeros((n_iter, 2, half), dtype=np.int32)
+        log_u = np.empty((n_iter, 2, half))
+        kind = np.empty(n_iter, dtype=np.int32)
+        states = []
+        snap = self._state_snapshotter()
+        for it in range(n_iter):
+            move = self._moves[self._select_move()]
+            kind[it] = move.kind
+            for h in range(2):
+                scal[it, h], lz[it, h], partner[it, h], partner_b[it, h], log_u[it, h] = \
+                    move.draw(self._random, half, self.dim)
+            states.append(snap())
+        return (scal, lz, partner, log_u, kind, partner_b), states
 
     def sample(self, p0, lnprob0=None, rstate0=None, blobs0=None, iterations=1, thin=1,
                storechain=True):
@@ -414,8 +587,9 @@ class DeviceEnsembleSampler(EnsembleSampler):
                                                  accumulate=self.accumulate)
                 draws, states = self._draw(n_next) if n_next > 0 else (None, None)
             else:
-                job = _run_async(self.model.engine.stretch_run, p, lnprob, *draws, nacc, store=True,
-                                 accumulate=self.accumulate)
+                # (`moves`: the draws carry kind and partner_b as well -- Context.move_run's arguments)
+                run = self.model.engine.stretch_run if self._moves is None else self.model.engine.move_run
+                job = _run_async(run, p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
                 try:
                     draws, states = self._draw(n_next) if n_next > 0 else (None, None)
                 finally:
@@ -469,7 +643,8 @@ class FieldSetSampler(object):
     large one (BASELINE config 5 as a fit).  `fields[f]` is field f's emcee-style sampler object (`.chain`,
     `.lnprobability`, `.acceptance_fraction`, `.random_state`, ...).  A field's chain equals the chain its
     own one-field `DeviceEnsembleSampler` produces from the same start and random state, bit for bit.
-    The reference fits one field per process (psfMC/fitting.py:13-113)."""
+    The reference fits one field per process (psfMC/fitting.py:13-113).
+    Stretch move only: there is no `moves` keyword here yet."""
 
     def __init__(self, nwalkers, fieldset, a=2.0, block=64, accumulate=False):
         if nwalkers % 2:
@@ -625,7 +800,7 @@ class TemperedEnsembleSampler(object):
     like_prior_fn(theta [N, P]) -> (lnL [N], lnpi [N]), e.g. `model.log_likelihood_and_prior_batch`.
     Stored: `chain` [W, n, P] and `lnprobability` [W, n] of the beta = 1 rung (what `save_database` and
     `check_convergence_autocorr` read), `lnlikelihood` [T, W, n] of every rung; counters `naccepted_t` [T, W],
-    `nswap` [T-1]."""
+    `nswap` [T-1].  Stretch move only: there is no `moves` keyword here yet."""
 
     def __init__(self, nwalkers, dim, betas, like_prior_fn, a=2.0):
         if nwalkers % 2 or nwalkers < 2:
@@ -815,7 +990,8 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
 
     The ladder is `betas`, or `default_betas(ntemps, tmax)`.  The defaults (ntemps=16, tmax=1e6) are argued in
     DESIGN.md section 13.  One-field `MultiComponentModel` only, every prior on the device; its `max_walkers`
-    must hold ntemps x nwalkers.  `accumulate`: posterior images of the beta = 1 rung after every iteration."""
+    must hold ntemps x nwalkers.  `accumulate`: posterior images of the beta = 1 rung after every iteration.
+    Stretch move only: there is no `moves` keyword here yet."""
 
     def __init__(self, nwalkers, model, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
         from .models import MultiComponentModel
