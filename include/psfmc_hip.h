@@ -505,7 +505,8 @@ int psfmc_stretch_set_moves(psfmc_ctx* ctx, const int* kind, const int* partner_
 /*
  * Parallel tempering (no reference counterpart; the contract is psfmc_amd/sampler.py's
  * TemperedEnsembleSampler, which these calls reproduce bit for bit).  One-field contexts with every prior
- * on the device; multi-field and joint contexts and PSFMC_PRIOR_HOST columns return PSFMC_EINVAL.
+ * on the device; multi-field and joint contexts and PSFMC_PRIOR_HOST columns return PSFMC_EINVAL (a joint fit
+ * goes through psfmc_eval_theta_joint_split / psfmc_pt_run_joint below).
  * psfmc_eval_theta_split: psfmc_eval_theta's evaluation with the two terms apart -- lnlike [W] (-inf when
  *   the walker is skipped or its log-likelihood is not finite) and lnprior [W] (the device log-prior plus
  *   extra_lnprior), the values psfmc_pt_run works with.
@@ -538,6 +539,30 @@ int psfmc_pt_run(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, 
                  const double* log_u, const int* swap_i, const int* swap_j, const double* swap_log_u,
                  double* chain, double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
                  long long* naccepted, long long* nswap, int accumulate);
+
+/*
+ * Parallel tempering of a JOINT fit: contexts of psfmc_ctx_create_fields after psfmc_set_joint_priors.  A
+ * walker is one joint vector (P = the joint column count) and F field records.
+ * psfmc_eval_theta_joint_split: psfmc_eval_theta_joint with the two terms apart.  lnlike [W] =
+ *   ((ll_0 + ll_1) + ...) + ll_{F-1} in psfmc_eval_theta_joint's order, -inf where any field's record is
+ *   skipped or the sum is not finite; lnprior [W] the joint log-prior (every joint column once, then every
+ *   field's axis-ratio rule).  Where both are finite, lnlike + lnprior is psfmc_eval_theta_joint's value bit
+ *   for bit.  F W <= max_walkers, as psfmc_eval_theta_joint.
+ * psfmc_pt_run_joint: psfmc_pt_run for T ensembles of W joint walkers -- the same arguments, array shapes,
+ *   ladder rules, index checks and swap rule.  Per half-step: one proposal-and-prior launch over T W/2 records,
+ *   one record launch over the F fields, one pipeline pass over T W/2 F records (record r of field f at
+ *   r + f T W/2), one accept launch that sums each proposal's fields; then psfmc_pt_run's swap launch.  The
+ *   start state is one batch of T W walkers.  accumulate: every field's posterior sums get the beta = 1 rung's
+ *   W positions after every iteration.
+ *   PSFMC_EINVAL, before anything is uploaded, for T W F > max_walkers, an odd W, a bad ladder, an index out
+ *   of range, swap indices that are no permutations, or a context without joint priors.
+ */
+int psfmc_eval_theta_joint_split(psfmc_ctx* ctx, int W, const double* theta, double* lnlike, double* lnprior);
+int psfmc_pt_run_joint(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos, double* lnlike,
+                       double* lnprior, int state_valid, const double* z, const double* lz, const int* partner,
+                       const double* log_u, const int* swap_i, const int* swap_j, const double* swap_log_u,
+                       double* chain, double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                       long long* naccepted, long long* nswap, int accumulate);
 
 /*
  * The same sampler one half-step at a time, for walkers sharded over several GPUs (one

@@ -8,11 +8,13 @@ from .batch import BatchLogPosterior
 from .sampler import (EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler, TemperedEnsembleSampler,
                       DeviceTemperedSampler, default_betas, StretchMove, DEMove)
 from .parallel import RankGroup, ShardedLogPosterior
-from .fitting import model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc
+from .fitting import (model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc,
+                      model_joint_ptmcmc)
 from .database import load_database
 
 __version__ = '0.1.0'
 __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior', 'EnsembleSampler',
            'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler', 'DeviceTemperedSampler',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
-           'model_joint_mcmc', 'model_galaxy_ptmcmc', 'load_database', 'Moffat', 'Ferrer', 'StretchMove', 'DEMove']
+           'model_joint_mcmc', 'model_galaxy_ptmcmc', 'model_joint_ptmcmc', 'load_database', 'Moffat', 'Ferrer',
+           'StretchMove', 'DEMove']

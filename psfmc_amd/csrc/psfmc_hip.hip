@@ -3439,15 +3439,32 @@ extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, 
     return PSFMC_OK;
 }
 
-extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
-                            double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
-                            const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
-                            const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
-                            double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
+static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
+                                    hipStream_t st);
+static int joint_check(psfmc_ctx* c, int W);
+
+// psfmc_pt_run, and (joint) psfmc_pt_run_joint: the same ladder rules, index checks, device state, swap kernel
+// and downloads; a joint walker is F field records, its proposals come from k_pt_joint_propose and its
+// likelihood is the sum over its fields (k_pt_finish_joint).  The one-field path launches what it always did.
+static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const double* betas, double* pos,
+                       double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                       const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
+                       const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
+                       double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (T < 1 || W < 0 || (long long)T * W > c->max_walkers)
-        return fail(PSFMC_EINVAL, "T=%d temperatures x W=%d walkers outside [1, max_walkers=%d]", T, W, c->max_walkers);
-    RC_TRY(stretch_check(c, W, 1));               // one field, a layout, W even, every prior on the device
+    const int F = joint ? c->n_fields : 1;
+    if (joint) {
+        if (T < 1 || W < 0 || (long long)T * W * F > c->max_walkers)
+            return fail(PSFMC_EINVAL, "T=%d temperatures x W=%d walkers x %d fields outside [1, max_walkers=%d]", T, W,
+                        F, c->max_walkers);
+        RC_TRY(joint_check(c, T * W));            // joint priors set (every prior on the device)
+        if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
+    } else {
+        if (T < 1 || W < 0 || (long long)T * W > c->max_walkers)
+            return fail(PSFMC_EINVAL, "T=%d temperatures x W=%d walkers outside [1, max_walkers=%d]", T, W,
+                        c->max_walkers);
+        RC_TRY(stretch_check(c, W, 1));           // one field, a layout, W even, every prior on the device
+    }
     const bool swaps = T > 1 && n_iter > 0;
     if (n_iter < 0 || !betas || !pos || !lnlike || !lnprior || !naccepted || (T > 1 && !nswap) ||
         (n_iter && (!z || !lz || !partner || !log_u)) || (swaps && (!swap_i || !swap_j || !swap_log_u)))
@@ -3527,6 +3544,15 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
     if (state_valid) {
         RC_TRY(up(d_lnL, lnlike, TW * sizeof(double)));
         RC_TRY(up(d_lnpi, lnprior, TW * sizeof(double)));
+    } else if (joint) {                           // every rung's start positions in one batch of T W F records
+        hipLaunchKernelGGL(k_joint_prior, dim3(((int)TW + 63) / 64), dim3(64), 0, st, c->joint.prior,
+                           c->joint.d_fields, F, d_pos, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp,
+                           (int)TW);
+        launch_theta_prep_joint(c, (int)TW, d_pos, c->joint.d_lp, st);
+        RC_TRY(run_pipeline(c, (int)TW * F, c->d_skip, st));
+        hipLaunchKernelGGL(k_split_finish_joint, dim3(finish_blocks((int)TW)), dim3(kFinishThreads), 0, st,
+                           c->d_partial, c->d_skip, c->nblk, d_lnL, (int)TW, F, (int)TW);
+        HIP_TRY(hipMemcpyAsync(d_lnpi, c->joint.d_lp, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
     } else {                                      // every rung's start positions in one batch
         launch_theta_prep(c, (int)TW, d_pos, nullptr, nullptr, st, StretchIn{});
         RC_TRY(run_pipeline(c, (int)TW, c->d_skip, st));
@@ -3538,9 +3564,21 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
                        (int)TW, W);
     if (accumulate) RC_TRY(stretch_prepare_accumulation(c));
     // one iteration is seven launches whatever T is: per half-step the T rungs' proposals (one k_theta_prep),
-    // one pipeline pass over T half records, one accept kernel; then one swap kernel
+    // one pipeline pass over T half records, one accept kernel; then one swap kernel.  A joint fit adds one
+    // proposal-and-prior kernel per half-step, whatever T and F are; its pass is over T half F records
     for (int it = 0; it < n_iter; ++it) {
         for (int h = 0; h < 2; ++h) {
+            if (joint) {
+                const int n = T * half;
+                hipLaunchKernelGGL(k_pt_joint_propose, dim3((n + 63) / 64), dim3(64), 0, st, c->joint.prior,
+                                   c->joint.d_fields, F, d_pos, d_q, d_z, d_partner, it, T, half, h, c->joint.d_lp);
+                launch_theta_prep_joint(c, n, d_q, c->joint.d_lp, st);
+                RC_TRY(run_pipeline(c, n * F, c->d_skip, st));
+                hipLaunchKernelGGL(k_pt_finish_joint, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st,
+                                   c->d_partial, c->d_skip, c->d_lnprior, c->nblk, d_beta, d_pos, d_lnL, d_lnpi,
+                                   d_lnp, d_q, d_lz, d_logu, d_nacc, it, T, half, h, P, F, n);
+                continue;
+            }
             StretchIn sp{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T};
             launch_theta_prep(c, T * half, nullptr, nullptr, nullptr, st, sp);
             RC_TRY(run_pipeline(c, T * half, c->d_skip, st));
@@ -3550,7 +3588,10 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
         }
         hipLaunchKernelGGL(k_pt_swap, dim3(1), dim3(kPtSwapThreads), 0, st, d_beta, d_pos, d_lnL, d_lnpi, d_lnp,
                            d_si, d_sj, d_slu, d_nswap, d_chain, d_lnpc, d_lnlc, d_lnqc, it, n_iter, T, W, P);
-        if (accumulate) {                         // the beta = 1 rung: the first W walkers
+        if (accumulate && joint) {                // the beta = 1 rung: the first W walkers, every field's sums
+            launch_theta_prep_joint(c, W, d_pos, nullptr, st);
+            RC_TRY(accumulate_from_prep(c, W * F, st, 0, F, W));
+        } else if (accumulate) {                  // the beta = 1 rung: the first W walkers
             launch_theta_prep(c, W, d_pos, nullptr, nullptr, st, StretchIn{});
             RC_TRY(accumulate_from_prep(c, W, st, 0, 1, W));
         }
@@ -3572,6 +3613,16 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
     HIP_TRY(hipStreamSynchronize(st));
     if (hipGetLastError() != hipSuccess) return fail(PSFMC_EHIP, "kernel launch failed");
     return PSFMC_OK;
+}
+
+extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                            double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                            const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
+                            const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
+                            double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
+    return pt_run_impl(c, false, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate);
 }
 
 // ---------------------------------------------------------------------------
@@ -3709,6 +3760,43 @@ extern "C" int psfmc_eval_theta_joint(psfmc_ctx* c, int W, const double* theta, 
     HIP_TRY(hipMemcpyAsync(lnprob, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PSFMC_OK;
+}
+
+// psfmc_eval_theta_joint with the two terms apart: lnlike the fields' sum (walker_lnprob's, without the prior),
+// lnprior the joint log-prior as k_joint_prior writes it
+extern "C" int psfmc_eval_theta_joint_split(psfmc_ctx* c, int W, const double* theta, double* lnlike,
+                                            double* lnprior) {
+    RC_TRY(joint_check(c, W));
+    if (W == 0) return PSFMC_OK;
+    if (!theta || !lnlike || !lnprior) return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int F = c->n_fields;
+    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_joint_prior, dim3((W + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields, F,
+                       c->d_theta, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp, W);
+    launch_theta_prep_joint(c, W, c->d_theta, c->joint.d_lp, st);
+    RC_TRY(run_pipeline(c, W * F, c->d_skip, st));
+    hipLaunchKernelGGL(k_split_finish_joint, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       c->d_skip, c->nblk, c->d_like, W, F, W);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lnlike, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lnprior, c->joint.d_lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PSFMC_OK;
+}
+
+// psfmc_pt_run for T ensembles of W joint walkers (pt_run_impl)
+extern "C" int psfmc_pt_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                                  double* lnlike, double* lnprior, int state_valid, const double* z,
+                                  const double* lz, const int* partner, const double* log_u, const int* swap_i,
+                                  const int* swap_j, const double* swap_log_u, double* chain, double* lnprob_chain,
+                                  double* lnlike_chain, double* lnprior_chain, long long* naccepted,
+                                  long long* nswap, int accumulate) {
+    return pt_run_impl(c, true, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate);
 }
 
 // The stretch-move sampler of psfmc_stretch_run for ONE ensemble of W joint walkers: every half-step's

@@ -864,11 +864,16 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
 // log-posterior lnp = beta lnL + lnpi -- exactly that product, then that sum.  A walker whose lnpi or lnL is
 // not finite has lnL = lnp = -inf at every beta (no 0 * inf = NaN on the beta = 0 rung).
 // ---------------------------------------------------------------------------
-// the log-likelihood of walker w: walker_lnprob's sum without the prior, -inf if skipped or not finite
+// the log-likelihood of walker w: walker_lnprob's sum without the prior, -inf if skipped or not finite.
+// Joint walkers (nf > 1 fields, records of field f at w + f fstride): walker_lnprob's sum over the fields, in
+// its order and with its skip rule
 __device__ inline double walker_loglike(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
-                                        int nblk, int w, int lane) {
-    if (skip[w]) return -INFINITY;
-    const double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+                                        int nblk, int w, int lane, int nf = 1, int fstride = 0) {
+    for (int f = 0; f < nf; ++f)
+        if (skip[w + (size_t)f * fstride]) return -INFINITY;
+    double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+    for (int f = 1; f < nf; ++f)
+        ll += -0.5 * wave_sum_partials(partial + (w + (size_t)f * fstride) * nblk, nblk, lane);
     return ll == ll && fabs(ll) != INFINITY ? ll : -INFINITY;
 }
 
@@ -1033,6 +1038,79 @@ k_joint_prior(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_field
     double lp = theta_log_prior(J, th, 0.0);
     for (int f = 0; f < n_fields; ++f) lp = theta_axis_ratio(fields[f], th, lp);
     lnprior[w] = lp;
+}
+#endif
+
+// ---------------------------------------------------------------------------
+// parallel tempering of a joint fit (psfmc_eval_theta_joint_split, psfmc_pt_run_joint): T ensembles of joint
+// walkers, each walker nf field records.  A half-step's T half proposals are ONE field-major batch -- record r
+// of field f at r + f (T half) -- so k_theta_prep and the pipeline run once whatever T and nf are.
+// ---------------------------------------------------------------------------
+#if PSFMC_PART == 0          /* not a template: defined in the API part only */
+// k_split_finish for walkers of nf field records (fstride apart): walker_lnprob's sum without the prior
+__global__ void k_split_finish_joint(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
+                                     int nblk, double* __restrict__ lnlike, int W, int nf, int fstride) {
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
+    if (w >= W) return;
+    const double ll = walker_loglike(partial, skip, nblk, w, lane, nf, fstride);
+    if (lane == 0) lnlike[w] = ll;
+}
+
+// the half-step proposals of T joint ensembles and their joint log-priors: record r = t half + w is walker
+// h half + w of rung t (rows [t 2 half, (t + 1) 2 half) of pos), its partner from the rung's other half; random
+// numbers [n_iter][2][T][half] (StretchIn::n_ens).  The proposal is stretch_point's, the prior k_joint_prior's:
+// every joint column once, then every field's axis-ratio rule.  One lane per record (launch: ceil(T half / 64)
+// x 64).
+__global__ void __launch_bounds__(64)
+k_pt_joint_propose(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields,
+                   const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
+                   const int* __restrict__ partner, int it, int T, int half, int h, double* __restrict__ lnprior) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= T * half) return;
+    const int P = J.n_params;
+    const int t = r / half, w = r - t * half;
+    const size_t off = ((size_t)it * 2 + h) * T * half + r;
+    const size_t first = (size_t)t * 2 * half;               // rung t's first walker
+    const double* s = pos + (first + (size_t)h * half + w) * P;
+    const double* c = pos + (first + (size_t)(1 - h) * half + partner[off]) * P;
+    const double zz = z[off];
+    double* qr = q + (size_t)r * P;
+    for (int d = 0; d < P; ++d) qr[d] = stretch_point(s[d], c[d], zz);
+    double lp = theta_log_prior(J, qr, 0.0);
+    for (int f = 0; f < n_fields; ++f) lp = theta_axis_ratio(fields[f], qr, lp);
+    lnprior[r] = lp;
+}
+
+// k_pt_finish for joint records: the proposal's log-likelihood is walker_lnprob's sum over its nf field records
+// (fstride = T half apart), lnprior[r] (field 0's record) the joint log-prior.  One wave per proposal (launch:
+// finish_blocks(T half) x kFinishThreads).
+__global__ void k_pt_finish_joint(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
+                                  const double* __restrict__ lnprior, int nblk, const double* __restrict__ betas,
+                                  double* __restrict__ pos, double* __restrict__ lnL, double* __restrict__ lnpi,
+                                  double* __restrict__ lnp, const double* __restrict__ q,
+                                  const double* __restrict__ lz, const double* __restrict__ log_u,
+                                  long long* __restrict__ nacc, int it, int T, int half, int h, int P, int nf,
+                                  int fstride) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
+    if (r >= T * half) return;                               // wave-uniform
+    const int t = r / half, w = r - t * half;
+    const size_t off = ((size_t)it * 2 + h) * T * half + r;
+    const double ll = walker_loglike(partial, skip, nblk, r, lane, nf, fstride);
+    const double lp = lnprior[r];
+    const double newlnp = tempered_lnp(betas[t], ll, lp);
+    const size_t g = (size_t)t * 2 * half + (size_t)h * half + w;
+    const double diff = (lz[off] + newlnp) - lnp[g];
+    if (!(diff > log_u[off])) return;                        // the same in every lane
+    for (int d = lane; d < P; d += 64) pos[g * P + d] = q[(size_t)r * P + d];
+    if (lane == 0) {
+        lnL[g] = newlnp == -INFINITY ? -INFINITY : ll;
+        lnpi[g] = lp;
+        lnp[g] = newlnp;
+        nacc[g] += 1;
+    }
 }
 #endif
 

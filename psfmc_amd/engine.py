@@ -214,6 +214,10 @@ def load_library():
     lib.psfmc_eval_theta_joint_device.argtypes = [vp, ci, vp, vp, vp]
     lib.psfmc_stretch_run_joint.restype = ci
     lib.psfmc_stretch_run_joint.argtypes = lib.psfmc_stretch_run.argtypes
+    lib.psfmc_eval_theta_joint_split.restype = ci
+    lib.psfmc_eval_theta_joint_split.argtypes = [vp, ci, _c_double_p, _c_double_p, _c_double_p]
+    lib.psfmc_pt_run_joint.restype = ci
+    lib.psfmc_pt_run_joint.argtypes = lib.psfmc_pt_run.argtypes
     lib.psfmc_accumulate_theta_field.restype = ci
     lib.psfmc_accumulate_theta_field.argtypes = [vp, ci, ci, _c_double_p]
     lib.psfmc_reset_accumulated_field.restype = ci
@@ -354,6 +358,39 @@ def _move_run(fn, ctx, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, n
             _dp(lnchain) if lnchain is not None else None,
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate)))
     return rc, (pos, lnp, chain, lnchain)
+
+
+def _pt_run(fn, ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u, naccepted,
+            nswap, store, accumulate):
+    """The arrays of psfmc_pt_run / psfmc_pt_run_joint (`fn`) shaped and the call made; betas [T] and pos
+    [T, W, P] are contiguous float64 already.  Returns (rc, (pos, lnlike, lnprior, chain, lnprob_chain,
+    lnlike_chain, lnprior_chain)); naccepted and nswap are updated."""
+    n_t, n_w, n_p = pos.shape
+    n_iter = int(np.shape(z)[0])
+    have = lnlike is not None and lnprior is not None
+    ll = np.array(lnlike, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
+    lp = np.array(lnprior, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
+    z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_t, n_w // 2) for a in (z, lz, log_u))
+    partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_t, n_w // 2)
+    n_sw = max(n_t - 1, 0)
+    swap_i, swap_j = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, n_sw, n_w) for a in (swap_i, swap_j))
+    swap_log_u = _f64(swap_log_u).reshape(n_iter, n_sw, n_w)
+    if naccepted.dtype != np.int64 or naccepted.shape != (n_t, n_w) or not naccepted.flags.c_contiguous:
+        raise ValueError('naccepted must be int64 [T, W]')
+    if nswap.dtype != np.int64 or nswap.shape != (n_sw,):
+        raise ValueError('nswap must be int64 [T-1]')
+    store = store and n_iter > 0
+    chain = np.empty((n_t, n_w, n_iter, n_p)) if store else None
+    lnchain = np.empty((n_w, n_iter)) if store else None
+    llchain = np.empty((n_t, n_w, n_iter)) if store else None
+    lpchain = np.empty((n_t, n_w, n_iter)) if store else None
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    lpt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+    opt = lambda a: _dp(a) if a is not None else None
+    rc = fn(ctx, n_t, n_w, n_iter, _dp(betas), _dp(pos), _dp(ll), _dp(lp), int(have), _dp(z), _dp(lz),
+            ipt(partner), _dp(log_u), ipt(swap_i), ipt(swap_j), _dp(swap_log_u), opt(chain), opt(lnchain),
+            opt(llchain), opt(lpchain), lpt(naccepted), lpt(nswap) if n_sw else None, int(bool(accumulate)))
+    return rc, (pos, ll, lp, chain, lnchain, llchain, lpchain)
 
 
 def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
@@ -769,32 +806,10 @@ class Context(object):
             raise ValueError('pos must have {} parameters'.format(self.n_params))
         if n_t * n_w > self.max_walkers:
             raise ValueError('T x W = {} exceeds max_walkers={}'.format(n_t * n_w, self.max_walkers))
-        n_iter = int(np.shape(z)[0])
-        have = lnlike is not None and lnprior is not None
-        ll = np.array(lnlike, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
-        lp = np.array(lnprior, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
-        z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_t, n_w // 2) for a in (z, lz, log_u))
-        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_t, n_w // 2)
-        n_sw = max(n_t - 1, 0)
-        swap_i, swap_j = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, n_sw, n_w) for a in (swap_i, swap_j))
-        swap_log_u = _f64(swap_log_u).reshape(n_iter, n_sw, n_w)
-        if naccepted.dtype != np.int64 or naccepted.shape != (n_t, n_w) or not naccepted.flags.c_contiguous:
-            raise ValueError('naccepted must be int64 [T, W]')
-        if nswap.dtype != np.int64 or nswap.shape != (n_sw,):
-            raise ValueError('nswap must be int64 [T-1]')
-        store = store and n_iter > 0
-        chain = np.empty((n_t, n_w, n_iter, n_p)) if store else None
-        lnchain = np.empty((n_w, n_iter)) if store else None
-        llchain = np.empty((n_t, n_w, n_iter)) if store else None
-        lpchain = np.empty((n_t, n_w, n_iter)) if store else None
-        ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        lpt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
-        opt = lambda a: _dp(a) if a is not None else None
-        self._check(self._lib.psfmc_pt_run(
-            self._ctx, n_t, n_w, n_iter, _dp(betas), _dp(pos), _dp(ll), _dp(lp), int(have), _dp(z), _dp(lz),
-            ipt(partner), _dp(log_u), ipt(swap_i), ipt(swap_j), _dp(swap_log_u), opt(chain), opt(lnchain),
-            opt(llchain), opt(lpchain), lpt(naccepted), lpt(nswap) if n_sw else None, int(bool(accumulate))))
-        return pos, ll, lp, chain, lnchain, llchain, lpchain
+        rc, out = _pt_run(self._lib.psfmc_pt_run, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u,
+                          swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        self._check(rc)
+        return out
 
     # -- the sampler one half-step at a time (walkers sharded over ranks) -----
     def stretch_open(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True):
@@ -1146,6 +1161,34 @@ class FieldSetContext(object):
         self._check(rc)
         return out
 
+    def eval_joint_split(self, theta):
+        """[W, n_params] joint vectors -> (lnlike [W], lnprior [W]), the two terms of `logpost_theta_joint`
+        apart (psfmc_eval_theta_joint_split): lnlike the fields' sum, -inf where a field's record is skipped
+        or the sum is not finite; lnprior the joint log-prior.  n_fields x W <= max_walkers."""
+        theta = _f64(theta)
+        if theta.ndim != 2 or theta.shape[1] != self.n_params:
+            raise ValueError('theta must be [W, {}]'.format(self.n_params))
+        ll, lp = np.empty(len(theta)), np.empty(len(theta))
+        if len(theta):
+            self._check(self._lib.psfmc_eval_theta_joint_split(self._ctx, len(theta), _dp(theta), _dp(ll), _dp(lp)))
+        return ll, lp
+
+    def pt_run_joint(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+                     naccepted, nswap, store=True, accumulate=False):
+        """`Context.pt_run` for T ensembles of joint walkers (psfmc_pt_run_joint): the same arrays and return
+        values, P the joint column count; T x W x n_fields <= max_walkers (the library checks it).
+        accumulate: every field's posterior sums get the beta = 1 rung's positions after every iteration."""
+        betas = _f64(betas)
+        pos = np.array(pos, dtype=np.float64, order='C')
+        if pos.ndim != 3 or betas.shape != (pos.shape[0],):
+            raise ValueError('pos must be [T, W, P] with betas [T]')
+        if pos.shape[2] != self.n_params:
+            raise ValueError('pos must have {} parameters'.format(self.n_params))
+        rc, out = _pt_run(self._lib.psfmc_pt_run_joint, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
+                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        self._check(rc)
+        return out
+
     def joint_view(self):
         """The interface a `JointModel` and `DeviceEnsembleSampler` use: `JointView`."""
         return JointView(self)
@@ -1304,7 +1347,8 @@ class FieldView(object):
 class JointView(object):
     """A `FieldSetContext` whose fields are fitted jointly (`models.JointModel`), behind the part of a
     one-field `Context`'s interface that `DeviceEnsembleSampler` uses: `stretch_run` is the joint run
-    (psfmc_stretch_run_joint), `logpost_theta` the joint log-posterior."""
+    (psfmc_stretch_run_joint), `logpost_theta` the joint log-posterior; and of the part that
+    `DeviceTemperedSampler` uses: `pt_run` (psfmc_pt_run_joint) and `loglike_prior_theta`."""
 
     IMAGE_KINDS = Context.IMAGE_KINDS
 
@@ -1334,6 +1378,16 @@ class JointView(object):
                  accumulate=False):
         return self.owner.move_run_joint(pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted,
                                          store=store, accumulate=accumulate)
+
+    def loglike_prior_theta(self, theta, extra_lnprior=None):
+        if extra_lnprior is not None:
+            raise ValueError('a joint fit evaluates priors on the GPU only')
+        return self.owner.eval_joint_split(theta)
+
+    def pt_run(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+               naccepted, nswap, store=True, accumulate=False):
+        return self.owner.pt_run_joint(betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j,
+                                       swap_log_u, naccepted, nswap, store=store, accumulate=accumulate)
 
     def accumulated(self, field):
         return self.owner.accumulated(field)

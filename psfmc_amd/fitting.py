@@ -340,6 +340,13 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
             print('Database already contains sampled chains, skipping sampling')
         database = load_database(db_name)
 
+    _save_joint_images(joint, database, output_name, write_fits)
+    return joint, database
+
+
+def _save_joint_images(joint, database, output_name, write_fits):
+    """Each field's posterior images `<output_name>_f<k>_<type>.fits` from a joint database: the rows mapped to
+    the field's own parameter names, then `save_posterior_images` for the field's model."""
     theta = database.param_matrix(joint.param_names)
     for f, m in enumerate(joint.field_models):
         own = joint.field_theta(theta, f)
@@ -351,7 +358,6 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
             cols[name] = database[name]
         save_posterior_images(m, Table(cols, database.meta), output_name='{}_f{}_{{}}'.format(output_name, f),
                               filetypes=write_fits)
-    return joint, database
 
 
 def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetypes, iterations=0, burn=0,
@@ -419,3 +425,77 @@ def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetyp
             evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
     save_posterior_images(mc_model, database, output_name=output_name, filetypes=write_fits)
     return mc_model, database, evidence
+
+
+def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=default_filetypes, iterations=0,
+                       burn=0, chains=None, ntemps=16, tmax=1e6, betas=None, device=0, random_state=None,
+                       accumulate=True, quiet=False):
+    """`model_galaxy_ptmcmc` for ONE model fitted jointly to several exposures (`models.JointModel`, as
+    `model_joint_mcmc` builds it): the Bayesian evidence of the joint fit, every exposure counted.  Burn-in,
+    reset and `iterations` sampling iterations on `sampler.DeviceTemperedSampler` with `chains` walkers per rung
+    (default 2 P_joint + 2) on the ladder `betas`, or `default_betas(ntemps, tmax)`; then `log_evidence()` of the
+    sampling iterations.  The model is sized so that `max_walkers` holds ntemps x chains x F field records.
+
+    Outputs: ONE database `<output_name>_db.fits` with the joint columns and the beta = 1 rung's chain, the
+    header keys MCFIELDS, MCNTEMPS, MCLNZ, MCLNZERR and MCTSWAP (mean swap acceptance), and each field's
+    posterior images `<output_name>_f<k>_<type>.fits` at that field's shape.  An existing database skips
+    sampling; the evidence is then read back from its header.  Returns (JointModel, database, (lnZ, err))."""
+    from .sampler import DeviceTemperedSampler, check_betas, default_betas
+    betas = default_betas(ntemps, tmax) if betas is None else check_betas(betas)
+    n_t = len(betas)
+    if chains is not None and (chains < 2 or chains % 2):
+        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
+                         'two halves'.format(chains))
+    if output_name is None:
+        output_name = 'out_joint_' + str(model_files[0]).replace('.py', '')
+    given = isinstance(model_files, JointModel)
+    joint = model_files if given else None
+    if joint is None:
+        # room for the image recomputation's batches (as model_joint_mcmc) and for every rung's walkers
+        n_f = len(model_files)
+        joint = JointModel(model_files, per_field=per_field, device=device,
+                           max_walkers=n_f * max(n_t * (chains or 0), 1024))
+    n_f = len(joint.field_models)
+    if chains is None:
+        chains = 2 * joint.num_params + 2
+    if n_t * chains * n_f > joint._max_walkers:
+        if given:
+            raise ValueError('{} temperatures x {} chains x {} fields exceed max_walkers={}'.format(
+                n_t, chains, n_f, joint._max_walkers))
+        joint = JointModel(model_files, per_field=per_field, device=device, max_walkers=n_t * chains * n_f)
+    sampler = DeviceTemperedSampler(chains, joint, betas=betas)
+    if random_state is not None:
+        if isinstance(random_state, (int, np.integer)):
+            random_state = np.random.RandomState(int(random_state)).get_state()
+        sampler.random_state = random_state
+
+    db_name = output_name + '_db.fits'
+    evidence = (float('nan'), float('nan'))
+    if not os.path.exists(db_name):
+        pos = np.stack([joint.init_params_from_priors(chains) for _ in range(n_t)])
+        lnlike = lnprior = None
+        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, iterations=burn)):
+            if not quiet:
+                print_progress(step, burn, 'Burning')
+        sampler.reset()
+        sampler.accumulate = bool(accumulate)
+        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, lnlike, lnprior,
+                                                                        iterations=iterations)):
+            if not quiet:
+                print_progress(step, iterations, 'Sampling')
+        sampler.accumulate = False
+        evidence = sampler.log_evidence(fburnin=0.0) if n_t > 1 and iterations > 0 else evidence
+        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
+                            ('MCCHAINS', chains), ('MCCONVRG', bool(check_convergence_autocorr(sampler))),
+                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f),
+                            ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
+                            ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+        database = save_database(sampler, joint, db_name, meta_dict=meta)
+    else:
+        if not quiet:
+            print('Database already contains sampled chains, skipping sampling')
+        database = load_database(db_name)
+        if 'MCLNZ' in database.meta:
+            evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
+    _save_joint_images(joint, database, output_name, write_fits)
+    return joint, database, evidence

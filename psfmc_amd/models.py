@@ -1020,6 +1020,18 @@ class JointModel(object):
         parts = [eng.logpost_theta(theta[lo:lo + cap]) for lo in range(0, theta.shape[0], cap)]
         return np.concatenate(parts) if parts else np.zeros(0)
 
+    def log_likelihood_and_prior_batch(self, theta):
+        """(lnL [W], lnprior [W]) of W joint vectors, the two terms of `log_posterior_batch` apart
+        (psfmc_eval_theta_joint_split), in the same slices: lnL is the fields' sum, -inf outside the priors and
+        where it is not finite; lnprior the joint log-prior.  The tempered samplers work with these values."""
+        theta = self._theta(theta)
+        eng = self.engine
+        cap = max(self._max_walkers // len(self.field_models), 1)
+        parts = [eng.loglike_prior_theta(theta[lo:lo + cap]) for lo in range(0, theta.shape[0], cap)]
+        if not parts:
+            return np.zeros(0), np.zeros(0)
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
     # -- posterior-image bookkeeping: the device sampler counts samples on the model, every field's sums
     # get each of them -------------------------------------------------------------------
     @property

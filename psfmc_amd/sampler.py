@@ -989,16 +989,19 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
     and the stored chain advance a block at a time.
 
     The ladder is `betas`, or `default_betas(ntemps, tmax)`.  The defaults (ntemps=16, tmax=1e6) are argued in
-    DESIGN.md section 13.  One-field `MultiComponentModel` only, every prior on the device; its `max_walkers`
-    must hold ntemps x nwalkers.  `accumulate`: posterior images of the beta = 1 rung after every iteration.
-    Stretch move only: there is no `moves` keyword here yet."""
+    DESIGN.md section 13.  A one-field `MultiComponentModel` with every prior on the device, whose `max_walkers`
+    must hold ntemps x nwalkers; or a `JointModel` of F fields (`psfmc_pt_run_joint`, DESIGN.md section 22: a
+    walker is F field records, the likelihood the fields' sum), whose `max_walkers` must hold ntemps x nwalkers
+    x F.  `accumulate`: posterior images of the beta = 1 rung after every iteration (every field's, for a joint
+    fit).  Stretch move only: there is no `moves` keyword here yet."""
 
     def __init__(self, nwalkers, model, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
-        from .models import MultiComponentModel
-        from .engine import Context
-        if not isinstance(model, MultiComponentModel):
-            raise ValueError('the tempered device sampler serves one-field MultiComponentModel fits; FieldSets and '
-                             'joint fits are not supported')
+        from .models import JointModel, MultiComponentModel
+        from .engine import Context, JointView
+        joint = isinstance(model, JointModel)
+        if not joint and not isinstance(model, MultiComponentModel):
+            raise ValueError('the tempered device sampler serves one-field MultiComponentModel fits and JointModel '
+                             'fits; FieldSets and device groups are not supported')
         if betas is None:
             betas = default_betas(ntemps, tmax)
         super(DeviceTemperedSampler, self).__init__(nwalkers, model.num_params, betas,
@@ -1006,12 +1009,16 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
         self.model = model
         self.block = int(block)
         self.accumulate = bool(accumulate)
+        n_f = len(model.field_models) if joint else 1
+        if joint and self.ntemps * self.k * n_f > model._max_walkers:
+            raise ValueError('model was built for at most {} field records; {} temperatures x {} walkers x F={} fields '
+                             'need more'.format(model._max_walkers, self.ntemps, self.k, n_f))
         if self.ntemps * self.k > model._max_walkers:
             raise ValueError('model was built for at most {} walkers; {} temperatures x {} walkers need more'
                              .format(model._max_walkers, self.ntemps, self.k))
         eng = model.engine
-        if type(eng) is not Context:
-            raise ValueError('the tempered device sampler serves one-field models only')
+        if type(eng) is not (JointView if joint else Context):
+            raise ValueError('the tempered device sampler serves one-field models and joint fits only')
         if model._host_priors:
             raise ValueError('priors {} are evaluated on the host: the tempered device sampler cannot be '
                              'used'.format([p.name for p, _ in model._host_priors]))
