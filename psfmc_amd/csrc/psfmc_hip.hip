@@ -3141,8 +3141,10 @@ static void stretch_propose(psfmc_ctx* c, int it, int h, bool graph_iter, hipStr
                       0, 0, S.F);
 }
 
-// last stage: sum (or take the gathered values), accept, move, chain entry
-static void stretch_accept(psfmc_ctx* c, int it, int h, const double* d_newlnp, bool graph_iter, hipStream_t st) {
+// last stage: sum (or take the gathered values), accept, move, chain entry.  nf > 1: joint walkers, each
+// proposal nf field records, half apart
+static void stretch_accept(psfmc_ctx* c, int it, int h, const double* d_newlnp, bool graph_iter, hipStream_t st,
+                           int nf = 1) {
     psfmc_ctx::Stretch& S = c->stretch;
     const int half = S.W / 2;
     const size_t per_field = (size_t)S.n_iter * S.W;
@@ -3154,7 +3156,21 @@ static void stretch_accept(psfmc_ctx* c, int it, int h, const double* d_newlnp, 
                        c->d_skip, c->d_lnprior, c->nblk, d_newlnp, S.pos, S.lnp, S.q, S.rand + n_rand,
                        S.rand + 2 * n_rand, S.nacc, S.store ? S.chain : nullptr, S.store ? S.lnchain : nullptr,
                        graph_iter ? S.iter : nullptr, it, S.n_iter, half, h, c->layout.n_params, per_field,
-                       acc_out, acc_in, S.partner, 1, 0);
+                       acc_out, acc_in, S.partner, nf, half);
+}
+
+// the end of every run that called stretch_upload, on every path: the results come down if all went well, the
+// stream is drained, and the run is closed
+static int stretch_end_run(psfmc_ctx* c, int rc, double* pos, double* lnprob, double* chain, double* lnprob_chain,
+                           long long* naccepted, hipStream_t st) {
+    psfmc_ctx::Stretch& S = c->stretch;
+    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
+    (void)hipStreamSynchronize(st);
+    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
+    S.open = false;
+    S.spec = false;
+    S.moves = false;
+    return rc;
 }
 
 // a whole iteration's proposals in one launch (StretchIn::spec): 3 half walkers
@@ -3198,10 +3214,11 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
     const int half = W / 2;
     hipStream_t st = c->stream;
     psfmc_ctx::Stretch& S = c->stretch;
-    RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
-                          chain != nullptr, st, F));
-    if (!lnprob_valid) RC_TRY(stretch_eval_positions(c, st));
-    if (accumulate) RC_TRY(stretch_prepare_accumulation(c));
+    int rc = stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
+                            chain != nullptr, st, F);
+    if (rc == PSFMC_OK && !lnprob_valid) rc = stretch_eval_positions(c, st);
+    if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
+    if (rc != PSFMC_OK) return stretch_end_run(c, rc, pos, lnprob, chain, lnprob_chain, naccepted, st);
     // one iteration: two half-ensemble proposals (chain entries included), optional image
     // sums.  A half-step is three stages: proposals + priors + prep records (one kernel), the
     // likelihood pipeline, and sum + accept + move + chain entry (one kernel).  The kernels take
@@ -3242,7 +3259,6 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
     };
     // Optionally capture one iteration into a hipGraph and replay it (set_option "graph";
     // measured: no gain, the iteration is kernel-time- not launch-bound).
-    int rc = PSFMC_OK;
     hipGraphExec_t exec = nullptr;
     if (use_d_iter) {
         hipGraph_t graph = nullptr;
@@ -3281,12 +3297,7 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
         (void)hipStreamSynchronize(st);
         (void)hipGraphExecDestroy(exec);
     }
-    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
-    (void)hipStreamSynchronize(st);
-    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
-    S.open = false;
-    S.spec = false;
-    return rc;
+    return stretch_end_run(c, rc, pos, lnprob, chain, lnprob_chain, naccepted, st);
 }
 
 extern "C" int psfmc_stretch_run(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
@@ -3378,44 +3389,71 @@ static void move_propose_records(psfmc_ctx* c, int it, int h, hipStream_t st) {
     launch_theta_prep(c, c->stretch.W / 2, c->stretch.q, nullptr, nullptr, st, StretchIn{});
 }
 
-extern "C" int psfmc_move_run(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
-                              const double* scal, const double* lz, const int* partner, const double* log_u,
-                              const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
-                              long long* naccepted, int accumulate) {
-    RC_TRY(stretch_check(c, W, 1));                  // one field, a layout, W even, every prior on the device
-    if (n_iter < 0 || !pos || !lnprob || !naccepted || (n_iter && (!scal || !lz || !partner || !log_u)))
-        return fail(PSFMC_EINVAL, "NULL buffer");
-    RC_TRY(moves_check(W, n_iter, kind, partner, partner_b));
-    const int half = W / 2;
-    hipStream_t st = c->stream;
-    psfmc_ctx::Stretch& S = c->stretch;
-    RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, naccepted,
-                          chain != nullptr, st));
-    int rc = moves_upload(c, kind, partner_b, st);
-    if (rc == PSFMC_OK && !lnprob_valid) rc = stretch_eval_positions(c, st);
-    if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
-    for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
-        for (int h = 0; h < 2 && rc == PSFMC_OK; ++h) {
-            move_propose_records(c, it, h, st);
-            rc = run_pipeline(c, half, c->d_skip, st);
-            if (rc == PSFMC_OK) stretch_accept(c, it, h, nullptr, false, st);
-        }
-        if (rc == PSFMC_OK && accumulate) {
-            launch_theta_prep(c, W, S.pos, nullptr, nullptr, st, StretchIn{});
-            rc = accumulate_from_prep(c, W, st, 0, 1, W);
-        }
-    }
-    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
-    (void)hipStreamSynchronize(st);
-    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
-    S.open = false;
-    S.moves = false;
-    return rc;
+// ---------------------------------------------------------------------------
+// joint walkers (the joint fits' section, psfmc_set_joint_priors, is further down): record derivation and
+// proposals, used by the tempered and the plain run loops alike
+// ---------------------------------------------------------------------------
+// W walkers' vectors d_theta [W][P] -> the prep records, skip flags and log-priors of their F field
+// records (field-major).  d_extra: the joint log-priors (joint.d_lp), or nullptr where only the records
+// are needed (posterior-image sums)
+static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
+                                    hipStream_t st) {
+    const int F = c->n_fields;
+    const FieldSegs segs = F > 1 ? FieldSegs{c->joint.d_fields, c->d_field_sides, c->n_psf_field, 1}
+                                 : FieldSegs{nullptr, nullptr, 0, 0};
+    c->prep_tabs_valid = false;
+    hipLaunchKernelGGL(k_theta_prep, dim3((W + kThetaThreads - 1) / kThetaThreads, F),
+                       dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
+                       c->joint.fields[0], d_theta, d_extra, nullptr, c->d_prep, c->d_lnprior, c->d_skip, W,
+                       c->wraps[0].ly, c->wraps[0].lx, c->d_rho, StretchIn{}, 0, segs, aux_out(c, 0));
+    launch_pow_tables(c, W * F, 0, c->d_skip, st);
+}
+
+// n given vectors d_theta [n][P] -> their joint log-priors (joint.d_lp) and the records of their fields
+static void launch_joint_records(psfmc_ctx* c, int n, const double* d_theta, hipStream_t st) {
+    hipLaunchKernelGGL(k_joint_prior, dim3((n + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields,
+                       c->n_fields, d_theta, c->joint.d_lp, n);
+    launch_theta_prep_joint(c, n, d_theta, c->joint.d_lp, st);
+}
+
+// the stretch proposals of half `h` at iteration `it` of T ensembles of 2 half joint walkers (k_joint_propose)
+// -> d_q [T half][P], joint.d_lp and the records of their fields
+static void launch_joint_propose(psfmc_ctx* c, const double* d_pos, double* d_q, const double* d_z,
+                                 const int* d_partner, int it, int T, int half, int h, hipStream_t st) {
+    const int n = T * half;
+    hipLaunchKernelGGL(k_joint_propose, dim3((n + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields,
+                       c->n_fields, d_pos, d_q, d_z, d_partner, it, T, half, h, c->joint.d_lp);
+    launch_theta_prep_joint(c, n, d_q, c->joint.d_lp, st);
+}
+
+static int joint_check(psfmc_ctx* c, int W) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (!c->joint.ready)
+        return fail(PSFMC_EINVAL, "psfmc_set_joint_priors has not been called since the last field layout");
+    if (W < 0 || (long long)W * c->n_fields > c->max_walkers)
+        return fail(PSFMC_EINVAL, "n_fields x W = %d x %d exceeds max_walkers=%d", c->n_fields, W, c->max_walkers);
+    return PSFMC_OK;
 }
 
 // ---------------------------------------------------------------------------
 // parallel tempering (include/psfmc_hip.h psfmc_eval_theta_split, psfmc_pt_run)
 // ---------------------------------------------------------------------------
+// n vectors d_theta [n][P] on the device -> their log-likelihoods d_lnL [n]; *d_lnpi: where their log-priors
+// are left.  One-field walkers (d_extra: optional extra log-priors), or joint walkers of F field records,
+// whose likelihood is the sum over their fields and whose prior is the joint one
+static int eval_theta_split_device(psfmc_ctx* c, bool joint, int n, const double* d_theta, const double* d_extra,
+                                   double* d_lnL, const double** d_lnpi, hipStream_t st) {
+    const int F = joint ? c->n_fields : 1;
+    if (joint) launch_joint_records(c, n, d_theta, st);
+    else launch_theta_prep(c, n, d_theta, d_extra, nullptr, st, StretchIn{});
+    RC_TRY(run_pipeline(c, n * F, c->d_skip, st));
+    hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st, c->d_partial, c->d_skip,
+                       c->nblk, d_lnL, n, F, n);
+    HIP_TRY(hipGetLastError());
+    *d_lnpi = joint ? c->joint.d_lp : c->d_lnprior;
+    return PSFMC_OK;
+}
+
 extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, const double* extra,
                                       double* lnlike, double* lnprior) {
     if (c && c->n_fields > 1) return fail(PSFMC_EINVAL, "this entry point serves contexts of one field");
@@ -3428,24 +3466,17 @@ extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, 
         HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_theta_prep(c, W, c->d_theta, extra ? c->d_extra : nullptr, nullptr, st, StretchIn{});
-    RC_TRY(run_pipeline(c, W, c->d_skip, st));
-    hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial, c->d_skip,
-                       c->nblk, c->d_like, W);
-    HIP_TRY(hipGetLastError());
+    const double* d_lnpi = nullptr;
+    RC_TRY(eval_theta_split_device(c, false, W, c->d_theta, extra ? c->d_extra : nullptr, c->d_like, &d_lnpi, st));
     HIP_TRY(hipMemcpyAsync(lnlike, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(lnprior, c->d_lnprior, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lnprior, d_lnpi, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PSFMC_OK;
 }
 
-static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
-                                    hipStream_t st);
-static int joint_check(psfmc_ctx* c, int W);
-
 // psfmc_pt_run, and (joint) psfmc_pt_run_joint: the same ladder rules, index checks, device state, swap kernel
-// and downloads; a joint walker is F field records, its proposals come from k_pt_joint_propose and its
-// likelihood is the sum over its fields (k_pt_finish_joint).  The one-field path launches what it always did.
+// and downloads.  A joint walker is F field records: its capacity check counts them, its proposals come from
+// k_joint_propose (k_theta_prep forms the one-field ones itself), and its image sums take every field's records.
 static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const double* betas, double* pos,
                        double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
                        const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
@@ -3544,21 +3575,10 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     if (state_valid) {
         RC_TRY(up(d_lnL, lnlike, TW * sizeof(double)));
         RC_TRY(up(d_lnpi, lnprior, TW * sizeof(double)));
-    } else if (joint) {                           // every rung's start positions in one batch of T W F records
-        hipLaunchKernelGGL(k_joint_prior, dim3(((int)TW + 63) / 64), dim3(64), 0, st, c->joint.prior,
-                           c->joint.d_fields, F, d_pos, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp,
-                           (int)TW);
-        launch_theta_prep_joint(c, (int)TW, d_pos, c->joint.d_lp, st);
-        RC_TRY(run_pipeline(c, (int)TW * F, c->d_skip, st));
-        hipLaunchKernelGGL(k_split_finish_joint, dim3(finish_blocks((int)TW)), dim3(kFinishThreads), 0, st,
-                           c->d_partial, c->d_skip, c->nblk, d_lnL, (int)TW, F, (int)TW);
-        HIP_TRY(hipMemcpyAsync(d_lnpi, c->joint.d_lp, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else {                                      // every rung's start positions in one batch
-        launch_theta_prep(c, (int)TW, d_pos, nullptr, nullptr, st, StretchIn{});
-        RC_TRY(run_pipeline(c, (int)TW, c->d_skip, st));
-        hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks((int)TW)), dim3(kFinishThreads), 0, st, c->d_partial,
-                           c->d_skip, c->nblk, d_lnL, (int)TW);
-        HIP_TRY(hipMemcpyAsync(d_lnpi, c->d_lnprior, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else {                                      // every rung's start positions in one batch of T W F records
+        const double* d_start_lnpi = nullptr;
+        RC_TRY(eval_theta_split_device(c, joint, (int)TW, d_pos, nullptr, d_lnL, &d_start_lnpi, st));
+        HIP_TRY(hipMemcpyAsync(d_lnpi, d_start_lnpi, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     hipLaunchKernelGGL(k_pt_tempered, dim3(((int)TW + 255) / 256), dim3(256), 0, st, d_beta, d_lnL, d_lnpi, d_lnp,
                        (int)TW, W);
@@ -3566,34 +3586,24 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     // one iteration is seven launches whatever T is: per half-step the T rungs' proposals (one k_theta_prep),
     // one pipeline pass over T half records, one accept kernel; then one swap kernel.  A joint fit adds one
     // proposal-and-prior kernel per half-step, whatever T and F are; its pass is over T half F records
+    const auto finish = joint ? k_pt_finish<true> : k_pt_finish<false>;     // (one-field: nf = 1 compiled in)
     for (int it = 0; it < n_iter; ++it) {
         for (int h = 0; h < 2; ++h) {
-            if (joint) {
-                const int n = T * half;
-                hipLaunchKernelGGL(k_pt_joint_propose, dim3((n + 63) / 64), dim3(64), 0, st, c->joint.prior,
-                                   c->joint.d_fields, F, d_pos, d_q, d_z, d_partner, it, T, half, h, c->joint.d_lp);
-                launch_theta_prep_joint(c, n, d_q, c->joint.d_lp, st);
-                RC_TRY(run_pipeline(c, n * F, c->d_skip, st));
-                hipLaunchKernelGGL(k_pt_finish_joint, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st,
-                                   c->d_partial, c->d_skip, c->d_lnprior, c->nblk, d_beta, d_pos, d_lnL, d_lnpi,
-                                   d_lnp, d_q, d_lz, d_logu, d_nacc, it, T, half, h, P, F, n);
-                continue;
-            }
-            StretchIn sp{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T};
-            launch_theta_prep(c, T * half, nullptr, nullptr, nullptr, st, sp);
-            RC_TRY(run_pipeline(c, T * half, c->d_skip, st));
-            hipLaunchKernelGGL(k_pt_finish, dim3(finish_blocks(T * half)), dim3(kFinishThreads), 0, st, c->d_partial,
+            const int n = T * half;
+            if (joint) launch_joint_propose(c, d_pos, d_q, d_z, d_partner, it, T, half, h, st);
+            else launch_theta_prep(c, n, nullptr, nullptr, nullptr, st,
+                                   StretchIn{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T});
+            RC_TRY(run_pipeline(c, n * F, c->d_skip, st));
+            hipLaunchKernelGGL(finish, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st, c->d_partial,
                                c->d_skip, c->d_lnprior, c->nblk, d_beta, d_pos, d_lnL, d_lnpi, d_lnp, d_q, d_lz,
-                               d_logu, d_nacc, it, T, half, h, P);
+                               d_logu, d_nacc, it, T, half, h, P, F, n);
         }
         hipLaunchKernelGGL(k_pt_swap, dim3(1), dim3(kPtSwapThreads), 0, st, d_beta, d_pos, d_lnL, d_lnpi, d_lnp,
                            d_si, d_sj, d_slu, d_nswap, d_chain, d_lnpc, d_lnlc, d_lnqc, it, n_iter, T, W, P);
-        if (accumulate && joint) {                // the beta = 1 rung: the first W walkers, every field's sums
-            launch_theta_prep_joint(c, W, d_pos, nullptr, st);
+        if (accumulate) {                         // the beta = 1 rung: the first W walkers, every field's sums
+            if (joint) launch_theta_prep_joint(c, W, d_pos, nullptr, st);
+            else launch_theta_prep(c, W, d_pos, nullptr, nullptr, st, StretchIn{});
             RC_TRY(accumulate_from_prep(c, W * F, st, 0, F, W));
-        } else if (accumulate) {                  // the beta = 1 rung: the first W walkers
-            launch_theta_prep(c, W, d_pos, nullptr, nullptr, st, StretchIn{});
-            RC_TRY(accumulate_from_prep(c, W, st, 0, 1, W));
         }
     }
     HIP_TRY(hipGetLastError());
@@ -3702,36 +3712,9 @@ extern "C" int psfmc_set_joint_priors(psfmc_ctx* c, int n_params, const int* fam
     return PSFMC_OK;
 }
 
-// W walkers' vectors d_theta [W][P] -> the prep records, skip flags and log-priors of their F field
-// records (field-major).  d_extra: the joint log-priors (k_joint_prior), or nullptr where only the records
-// are needed (posterior-image sums)
-static void launch_theta_prep_joint(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
-                                    hipStream_t st) {
-    const int F = c->n_fields;
-    const FieldSegs segs = F > 1 ? FieldSegs{c->joint.d_fields, c->d_field_sides, c->n_psf_field, 1}
-                                 : FieldSegs{nullptr, nullptr, 0, 0};
-    c->prep_tabs_valid = false;
-    hipLaunchKernelGGL(k_theta_prep, dim3((W + kThetaThreads - 1) / kThetaThreads, F),
-                       dim3(kThetaThreads, theta_task_waves(c->n_ps, c->n_sersic)), c->theta_lds, st,
-                       c->joint.fields[0], d_theta, d_extra, nullptr, c->d_prep, c->d_lnprior, c->d_skip, W,
-                       c->wraps[0].ly, c->wraps[0].lx, c->d_rho, StretchIn{}, 0, segs, aux_out(c, 0));
-    launch_pow_tables(c, W * F, 0, c->d_skip, st);
-}
-
-static int joint_check(psfmc_ctx* c, int W) {
-    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    if (!c->joint.ready)
-        return fail(PSFMC_EINVAL, "psfmc_set_joint_priors has not been called since the last field layout");
-    if (W < 0 || (long long)W * c->n_fields > c->max_walkers)
-        return fail(PSFMC_EINVAL, "n_fields x W = %d x %d exceeds max_walkers=%d", c->n_fields, W, c->max_walkers);
-    return PSFMC_OK;
-}
-
 static int eval_theta_joint(psfmc_ctx* c, int W, const double* d_theta, double* d_lnprob, hipStream_t st) {
     const int F = c->n_fields;
-    hipLaunchKernelGGL(k_joint_prior, dim3((W + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields, F,
-                       d_theta, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp, W);
-    launch_theta_prep_joint(c, W, d_theta, c->joint.d_lp, st);
+    launch_joint_records(c, W, d_theta, st);
     RC_TRY(run_pipeline(c, W * F, c->d_skip, st));
     hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
                        c->d_skip, c->d_lnprior, d_lnprob, W, c->nblk, F, W);
@@ -3771,18 +3754,12 @@ extern "C" int psfmc_eval_theta_joint_split(psfmc_ctx* c, int W, const double* t
     if (!theta || !lnlike || !lnprior) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const int F = c->n_fields;
     HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
                            hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_joint_prior, dim3((W + 63) / 64), dim3(64), 0, st, c->joint.prior, c->joint.d_fields, F,
-                       c->d_theta, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, c->joint.d_lp, W);
-    launch_theta_prep_joint(c, W, c->d_theta, c->joint.d_lp, st);
-    RC_TRY(run_pipeline(c, W * F, c->d_skip, st));
-    hipLaunchKernelGGL(k_split_finish_joint, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
-                       c->d_skip, c->nblk, c->d_like, W, F, W);
-    HIP_TRY(hipGetLastError());
+    const double* d_lnpi = nullptr;
+    RC_TRY(eval_theta_split_device(c, true, W, c->d_theta, nullptr, c->d_like, &d_lnpi, st));
     HIP_TRY(hipMemcpyAsync(lnlike, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(lnprior, c->joint.d_lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lnprior, d_lnpi, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PSFMC_OK;
 }
@@ -3799,73 +3776,70 @@ extern "C" int psfmc_pt_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const 
                        nswap, accumulate);
 }
 
-// The stretch-move sampler of psfmc_stretch_run for ONE ensemble of W joint walkers: every half-step's
-// proposals (formed by k_joint_prior) are F W / 2 field records in one pipeline pass; k_stretch_finish sums
-// each proposal's fields.  Plain half-steps only (no whole-iteration launches, no hipGraph): the chain is
-// the one of psfmc_stretch_run's rules either way.  accumulate: after every iteration, each field's
-// posterior-image sums get the current positions mapped to that field.
-// moves (psfmc_move_run_joint; kind and partner_b of psfmc_move_run): k_move_propose forms each half-step's
-// proposals and k_joint_prior takes them as given vectors (the mode of psfmc_eval_theta_joint)
-static int joint_run_impl(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
-                          int lnprob_valid, const double* z, const double* lz, const int* partner,
-                          const double* log_u, bool moves, const int* kind, const int* partner_b, double* chain,
-                          double* lnprob_chain, long long* naccepted, int accumulate) {
-    RC_TRY(joint_check(c, W));
-    if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
+// The plain half-step loop of psfmc_move_run (one-field walkers, proposals by kind), psfmc_stretch_run_joint and
+// psfmc_move_run_joint (ONE ensemble of W joint walkers).  No whole-iteration launches and no hipGraph: a DE
+// proposal of the second half depends on the outcomes of two walkers of the first, and the joint chain is the
+// one of psfmc_stretch_run's rules either way.  A half-step: the proposals to S.q (k_move_propose, or
+// k_joint_propose with their joint priors), their records (a joint walker's are F field records, F W / 2 in
+// one pipeline pass), the pipeline, and k_stretch_finish, which sums each proposal's fields.  accumulate:
+// after every iteration, each field's posterior-image sums get the current positions mapped to that field.
+// One-field walkers come here only with moves: psfmc_stretch_run has its own loop (stretch_run_impl).
+static int half_step_run(psfmc_ctx* c, bool joint, bool moves, int W, int n_iter, double* pos, double* lnprob,
+                         int lnprob_valid, const double* z, const double* lz, const int* partner,
+                         const double* log_u, const int* kind, const int* partner_b, double* chain,
+                         double* lnprob_chain, long long* naccepted, int accumulate) {
+    if (joint) {
+        RC_TRY(joint_check(c, W));
+        if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
+    } else {
+        RC_TRY(stretch_check(c, W, 1));              // one field, a layout, W even, every prior on the device
+    }
     if (n_iter < 0 || !pos || !lnprob || !naccepted || (n_iter && (!z || !lz || !partner || !log_u)))
         return fail(PSFMC_EINVAL, "NULL buffer");
     if (moves) RC_TRY(moves_check(W, n_iter, kind, partner, partner_b));
     HIP_TRY(hipSetDevice(c->device));
-    const int F = c->n_fields, half = W / 2, P = c->layout.n_params;
+    const int F = joint ? c->n_fields : 1, half = W / 2;
     hipStream_t st = c->stream;
     psfmc_ctx::Stretch& S = c->stretch;
-    RC_TRY(stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
-                          chain != nullptr, st));
+    int rc = stretch_upload(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, naccepted,
+                            chain != nullptr, st);
     S.spec = false;
-    int rc = moves ? moves_upload(c, kind, partner_b, st) : PSFMC_OK;
-    if (rc == PSFMC_OK && !lnprob_valid) rc = eval_theta_joint(c, W, S.pos, S.lnp, st);
+    if (rc == PSFMC_OK && moves) rc = moves_upload(c, kind, partner_b, st);
+    if (rc == PSFMC_OK && !lnprob_valid)
+        rc = joint ? eval_theta_joint(c, W, S.pos, S.lnp, st) : stretch_eval_positions(c, st);
     if (rc == PSFMC_OK && accumulate) rc = stretch_prepare_accumulation(c);
-    const size_t n_rand = (size_t)n_iter * W;                  // per random array (S.rand: z | lz | log u)
     for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
         for (int h = 0; h < 2 && rc == PSFMC_OK; ++h) {
-            if (moves) {
-                move_propose(c, it, h, st);
-                hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
-                                   c->joint.d_fields, F, S.q, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-                                   c->joint.d_lp, half);
-            } else {
-                hipLaunchKernelGGL(k_joint_prior, dim3((half + 63) / 64), dim3(64), 0, st, c->joint.prior,
-                                   c->joint.d_fields, F, nullptr, S.pos, S.q, S.rand, S.partner, it, half, h,
-                                   c->joint.d_lp, half);
-            }
-            launch_theta_prep_joint(c, half, S.q, c->joint.d_lp, st);
+            if (moves) move_propose(c, it, h, st);
+            if (!joint) launch_theta_prep(c, half, S.q, nullptr, nullptr, st, StretchIn{});
+            else if (moves) launch_joint_records(c, half, S.q, st);
+            else launch_joint_propose(c, S.pos, S.q, S.rand, S.partner, it, 1, half, h, st);
             rc = run_pipeline(c, half * F, c->d_skip, st);
-            if (rc != PSFMC_OK) break;
-            hipLaunchKernelGGL(k_stretch_finish, dim3(finish_blocks(half)), dim3(kFinishThreads), 0, st, c->d_partial,
-                               c->d_skip, c->d_lnprior, c->nblk, nullptr, S.pos, S.lnp, S.q, S.rand + n_rand,
-                               S.rand + 2 * n_rand, S.nacc, S.store ? S.chain : nullptr,
-                               S.store ? S.lnchain : nullptr, nullptr, it, n_iter, half, h, P, (size_t)0, nullptr,
-                               nullptr, S.partner, F, half);
+            if (rc == PSFMC_OK) stretch_accept(c, it, h, nullptr, false, st, F);
         }
         if (rc == PSFMC_OK && accumulate) {
-            launch_theta_prep_joint(c, W, S.pos, nullptr, st);
+            if (joint) launch_theta_prep_joint(c, W, S.pos, nullptr, st);
+            else launch_theta_prep(c, W, S.pos, nullptr, nullptr, st, StretchIn{});
             rc = accumulate_from_prep(c, W * F, st, 0, F, W);
         }
     }
-    if (rc == PSFMC_OK) rc = stretch_download(c, pos, lnprob, chain, lnprob_chain, naccepted, st);
-    (void)hipStreamSynchronize(st);
-    if (rc == PSFMC_OK && hipGetLastError() != hipSuccess) rc = fail(PSFMC_EHIP, "kernel launch failed");
-    S.open = false;
-    S.moves = false;
-    return rc;
+    return stretch_end_run(c, rc, pos, lnprob, chain, lnprob_chain, naccepted, st);
+}
+
+extern "C" int psfmc_move_run(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob, int lnprob_valid,
+                              const double* scal, const double* lz, const int* partner, const double* log_u,
+                              const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
+                              long long* naccepted, int accumulate) {
+    return half_step_run(c, false, true, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, kind,
+                         partner_b, chain, lnprob_chain, naccepted, accumulate);
 }
 
 extern "C" int psfmc_stretch_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos, double* lnprob,
                                        int lnprob_valid, const double* z, const double* lz, const int* partner,
                                        const double* log_u, double* chain, double* lnprob_chain,
                                        long long* naccepted, int accumulate) {
-    return joint_run_impl(c, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, false, nullptr, nullptr,
-                          chain, lnprob_chain, naccepted, accumulate);
+    return half_step_run(c, true, false, W, n_iter, pos, lnprob, lnprob_valid, z, lz, partner, log_u, nullptr,
+                         nullptr, chain, lnprob_chain, naccepted, accumulate);
 }
 
 // psfmc_move_run for ONE ensemble of W joint walkers
@@ -3873,8 +3847,8 @@ extern "C" int psfmc_move_run_joint(psfmc_ctx* c, int W, int n_iter, double* pos
                                     const double* scal, const double* lz, const int* partner, const double* log_u,
                                     const int* kind, const int* partner_b, double* chain, double* lnprob_chain,
                                     long long* naccepted, int accumulate) {
-    return joint_run_impl(c, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, true, kind, partner_b,
-                          chain, lnprob_chain, naccepted, accumulate);
+    return half_step_run(c, true, true, W, n_iter, pos, lnprob, lnprob_valid, scal, lz, partner, log_u, kind,
+                         partner_b, chain, lnprob_chain, naccepted, accumulate);
 }
 
 // ---------------------------------------------------------------------------

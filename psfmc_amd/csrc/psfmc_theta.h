@@ -749,19 +749,27 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
 }
 #endif
 
+// A walker is nf field records, field f's at w + f fstride of the per-record arrays (nf = 1, fstride = 0: an
+// ordinary walker).  Its log-likelihood is ((ll_0 + ll_1) + ...) + ll_{nf-1}, each ll_f the one-field sum.  The
+// sum is returned unguarded: walker_lnprob and walker_loglike each keep their own skip and finiteness tests, so
+// that the product, the sum and the `+ lnprior` compile to what they would standing alone.
+__device__ inline double walker_field_sum(const double* __restrict__ partial, int nblk, int w, int lane, int nf,
+                                          int fstride) {
+    double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
+    for (int f = 1; f < nf; ++f)
+        ll += -0.5 * wave_sum_partials(partial + (w + (size_t)f * fstride) * nblk, nblk, lane);
+    return ll;
+}
+
 // lnprob = loglike + lnprior, non-finite likelihood -> -inf (models.py:238-243); all
-// lanes of the walker's wave get the value.
-// Joint fits (nf > 1 fields, records of field f at w + f fstride): loglike = ((ll_0 + ll_1) + ...) +
-// ll_{nf-1}, each ll_f the one-field sum; -inf if any field's record is skipped.  lnprior[w] (field 0's
-// record) is the joint log-prior.
+// lanes of the walker's wave get the value.  A joint walker is -inf if any field's record is skipped; lnprior[w]
+// (field 0's record) is its joint log-prior.
 __device__ inline double walker_lnprob(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
                                        const double* __restrict__ lnprior, int nblk, int w, int lane,
                                        int nf = 1, int fstride = 0) {
     for (int f = 0; f < nf; ++f)
         if (skip[w + (size_t)f * fstride]) return -INFINITY;
-    double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
-    for (int f = 1; f < nf; ++f)
-        ll += -0.5 * wave_sum_partials(partial + (w + (size_t)f * fstride) * nblk, nblk, lane);
+    const double ll = walker_field_sum(partial, nblk, w, lane, nf, fstride);
     const bool fin = ll == ll && fabs(ll) != INFINITY;
     return fin ? ll + lnprior[w] : -INFINITY;
 }
@@ -864,16 +872,12 @@ __global__ void k_stretch_finish(const double* __restrict__ partial, const uint8
 // log-posterior lnp = beta lnL + lnpi -- exactly that product, then that sum.  A walker whose lnpi or lnL is
 // not finite has lnL = lnp = -inf at every beta (no 0 * inf = NaN on the beta = 0 rung).
 // ---------------------------------------------------------------------------
-// the log-likelihood of walker w: walker_lnprob's sum without the prior, -inf if skipped or not finite.
-// Joint walkers (nf > 1 fields, records of field f at w + f fstride): walker_lnprob's sum over the fields, in
-// its order and with its skip rule
+// the log-likelihood of walker w: walker_lnprob's sum without the prior, -inf if skipped or not finite
 __device__ inline double walker_loglike(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
-                                        int nblk, int w, int lane, int nf = 1, int fstride = 0) {
+                                        int nblk, int w, int lane, int nf, int fstride) {
     for (int f = 0; f < nf; ++f)
         if (skip[w + (size_t)f * fstride]) return -INFINITY;
-    double ll = -0.5 * wave_sum_partials(partial + (size_t)w * nblk, nblk, lane);
-    for (int f = 1; f < nf; ++f)
-        ll += -0.5 * wave_sum_partials(partial + (w + (size_t)f * fstride) * nblk, nblk, lane);
+    const double ll = walker_field_sum(partial, nblk, w, lane, nf, fstride);
     return ll == ll && fabs(ll) != INFINITY ? ll : -INFINITY;
 }
 
@@ -885,14 +889,15 @@ __device__ inline double tempered_lnp(double beta, double ll, double lp) {
 }
 
 #if PSFMC_PART == 0          /* not a template: defined in the API part only */
-// log-likelihoods of W walkers whose partial sums are in `partial` (their log-priors stay in d_lnprior).
-// One wave per walker (launch: finish_blocks(W) x kFinishThreads).
+// log-likelihoods of W walkers whose partial sums are in `partial` (their log-priors stay where the record
+// derivation wrote them); nf, fstride: see walker_field_sum.  One wave per walker (launch: finish_blocks(W) x
+// kFinishThreads).
 __global__ void k_split_finish(const double* __restrict__ partial, const uint8_t* __restrict__ skip, int nblk,
-                               double* __restrict__ lnlike, int W) {
+                               double* __restrict__ lnlike, int W, int nf, int fstride) {
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
     if (w >= W) return;
-    const double ll = walker_loglike(partial, skip, nblk, w, lane);
+    const double ll = walker_loglike(partial, skip, nblk, w, lane, nf, fstride);
     if (lane == 0) lnlike[w] = ll;
 }
 
@@ -908,23 +913,27 @@ __global__ void k_pt_tempered(const double* __restrict__ betas, double* __restri
 }
 
 // accept / move of one tempered half-step: record r = t half + w is walker h half + w of rung t's ensemble,
-// its proposal q[r] (formed by k_theta_prep with StretchIn::n_ens = T); random numbers [n_iter][2][T][half].
-// Acceptance as k_stretch_finish's, ((P - 1) ln z + lnp_new) - lnp > ln u, with the tempered lnp.  No chain
-// entry here: k_pt_swap writes the iteration's.  One wave per proposal (launch: finish_blocks(T half) x
-// kFinishThreads).
+// its proposal q[r] (formed by k_theta_prep with StretchIn::n_ens = T, or by k_joint_propose); random numbers
+// [n_iter][2][T][half].  Acceptance as k_stretch_finish's, ((P - 1) ln z + lnp_new) - lnp > ln u, with the
+// tempered lnp.  A joint proposal is nf field records (fstride = T half apart, see walker_field_sum), lnprior[r]
+// its joint log-prior.  No chain entry here: k_pt_swap writes the iteration's.  One wave per proposal (launch:
+// finish_blocks(T half) x kFinishThreads).
+// kJoint = false fixes nf = 1 when the kernel is compiled: the one-field tempered run launches this kernel twice
+// per iteration, and with nf read at run time it measured 0.5 to 2.4 % slower per iteration
+template <bool kJoint>
 __global__ void k_pt_finish(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
                             const double* __restrict__ lnprior, int nblk, const double* __restrict__ betas,
                             double* __restrict__ pos, double* __restrict__ lnL, double* __restrict__ lnpi,
                             double* __restrict__ lnp, const double* __restrict__ q, const double* __restrict__ lz,
                             const double* __restrict__ log_u, long long* __restrict__ nacc, int it, int T,
-                            int half, int h, int P) {
+                            int half, int h, int P, int nf, int fstride) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
     if (r >= T * half) return;                               // wave-uniform
     const int t = r / half, w = r - t * half;
     const size_t off = ((size_t)it * 2 + h) * T * half + r;
-    const double ll = walker_loglike(partial, skip, nblk, r, lane);
+    const double ll = walker_loglike(partial, skip, nblk, r, lane, kJoint ? nf : 1, kJoint ? fstride : 0);
     const double lp = lnprior[r];
     const double newlnp = tempered_lnp(betas[t], ll, lp);
     const size_t g = (size_t)t * 2 * half + (size_t)h * half + w;
@@ -1007,65 +1016,38 @@ k_pt_swap(const double* __restrict__ betas, double* __restrict__ pos, double* __
 #endif
 
 // ---------------------------------------------------------------------------
-// joint fits (psfmc_eval_theta_joint, psfmc_stretch_run_joint): the joint log-prior of W parameter vectors,
-// ONCE per walker -- every column's prior from the joint table J (J.n_sersic = 0: no slots), then the
-// Sersic axis-ratio rule of every field from that field's own slots (fields[f]).  k_theta_prep then
+// joint fits (psfmc_eval_theta_joint, psfmc_stretch_run_joint, psfmc_pt_run_joint): the joint log-prior of a
+// parameter vector, ONCE per walker -- every column's prior from the joint table J (J.n_sersic = 0: no slots),
+// then the Sersic axis-ratio rule of every field from that field's own slots (fields[f]).  k_theta_prep then
 // takes it as `extra`, with every field's own prior columns PRIOR_HOST, so that a walker outside the joint
-// support is skipped in every field.  With pos set, the vectors are the stretch proposals of half h at
-// iteration it, formed here (stretch_point: the roundings of k_theta_prep's proposals) and written to q.
-// One lane per walker (launch: ceil(W / 64) x 64).
+// support is skipped in every field.
 // ---------------------------------------------------------------------------
-#if PSFMC_PART == 0          /* not a template: defined in the API part only */
-__global__ void __launch_bounds__(64)
-k_joint_prior(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields, const double* __restrict__ theta,
-              const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
-              const int* __restrict__ partner, int it, int half, int h, double* __restrict__ lnprior, int W) {
-    const int w = blockIdx.x * 64 + threadIdx.x;
-    if (w >= W) return;
-    const int P = J.n_params;
-    const double* th;
-    if (!pos) {
-        th = theta + (size_t)w * P;
-    } else {
-        const size_t off = ((size_t)it * 2 + h) * half;
-        const double* s = pos + (size_t)(h * half + w) * P;
-        const double* c = pos + (size_t)((1 - h) * half + partner[off + w]) * P;
-        const double zz = z[off + w];
-        double* qw = q + (size_t)w * P;
-        for (int d = 0; d < P; ++d) qw[d] = stretch_point(s[d], c[d], zz);
-        th = qw;
-    }
+__device__ inline double joint_log_prior(const ThetaLayout& J, const ThetaLayout* fields, int n_fields,
+                                         const double* th) {
     double lp = theta_log_prior(J, th, 0.0);
     for (int f = 0; f < n_fields; ++f) lp = theta_axis_ratio(fields[f], th, lp);
-    lnprior[w] = lp;
+    return lp;
 }
-#endif
 
-// ---------------------------------------------------------------------------
-// parallel tempering of a joint fit (psfmc_eval_theta_joint_split, psfmc_pt_run_joint): T ensembles of joint
-// walkers, each walker nf field records.  A half-step's T half proposals are ONE field-major batch -- record r
-// of field f at r + f (T half) -- so k_theta_prep and the pipeline run once whatever T and nf are.
-// ---------------------------------------------------------------------------
 #if PSFMC_PART == 0          /* not a template: defined in the API part only */
-// k_split_finish for walkers of nf field records (fstride apart): walker_lnprob's sum without the prior
-__global__ void k_split_finish_joint(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
-                                     int nblk, double* __restrict__ lnlike, int W, int nf, int fstride) {
-    const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
+// the joint log-priors of W given vectors theta [W][P].  One lane per walker (launch: ceil(W / 64) x 64).
+__global__ void __launch_bounds__(64)
+k_joint_prior(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields, const double* __restrict__ theta,
+              double* __restrict__ lnprior, int W) {
+    const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= W) return;
-    const double ll = walker_loglike(partial, skip, nblk, w, lane, nf, fstride);
-    if (lane == 0) lnlike[w] = ll;
+    lnprior[w] = joint_log_prior(J, fields, n_fields, theta + (size_t)w * J.n_params);
 }
 
-// the half-step proposals of T joint ensembles and their joint log-priors: record r = t half + w is walker
-// h half + w of rung t (rows [t 2 half, (t + 1) 2 half) of pos), its partner from the rung's other half; random
-// numbers [n_iter][2][T][half] (StretchIn::n_ens).  The proposal is stretch_point's, the prior k_joint_prior's:
-// every joint column once, then every field's axis-ratio rule.  One lane per record (launch: ceil(T half / 64)
-// x 64).
+// the half-step stretch proposals of T ensembles of joint walkers (T = 1: psfmc_stretch_run_joint) and their
+// joint log-priors: record r = t half + w is walker h half + w of rung t (rows [t 2 half, (t + 1) 2 half) of
+// pos), its partner from the rung's other half; random numbers [n_iter][2][T][half] (StretchIn::n_ens).  The
+// proposal is stretch_point's: the roundings of k_theta_prep's proposals.  One lane per record (launch:
+// ceil(T half / 64) x 64).
 __global__ void __launch_bounds__(64)
-k_pt_joint_propose(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields,
-                   const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
-                   const int* __restrict__ partner, int it, int T, int half, int h, double* __restrict__ lnprior) {
+k_joint_propose(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_fields,
+                const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
+                const int* __restrict__ partner, int it, int T, int half, int h, double* __restrict__ lnprior) {
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r >= T * half) return;
     const int P = J.n_params;
@@ -1077,40 +1059,7 @@ k_pt_joint_propose(ThetaLayout J, const ThetaLayout* __restrict__ fields, int n_
     const double zz = z[off];
     double* qr = q + (size_t)r * P;
     for (int d = 0; d < P; ++d) qr[d] = stretch_point(s[d], c[d], zz);
-    double lp = theta_log_prior(J, qr, 0.0);
-    for (int f = 0; f < n_fields; ++f) lp = theta_axis_ratio(fields[f], qr, lp);
-    lnprior[r] = lp;
-}
-
-// k_pt_finish for joint records: the proposal's log-likelihood is walker_lnprob's sum over its nf field records
-// (fstride = T half apart), lnprior[r] (field 0's record) the joint log-prior.  One wave per proposal (launch:
-// finish_blocks(T half) x kFinishThreads).
-__global__ void k_pt_finish_joint(const double* __restrict__ partial, const uint8_t* __restrict__ skip,
-                                  const double* __restrict__ lnprior, int nblk, const double* __restrict__ betas,
-                                  double* __restrict__ pos, double* __restrict__ lnL, double* __restrict__ lnpi,
-                                  double* __restrict__ lnp, const double* __restrict__ q,
-                                  const double* __restrict__ lz, const double* __restrict__ log_u,
-                                  long long* __restrict__ nacc, int it, int T, int half, int h, int P, int nf,
-                                  int fstride) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * (kFinishThreads / 64) + (threadIdx.x >> 6);
-    if (r >= T * half) return;                               // wave-uniform
-    const int t = r / half, w = r - t * half;
-    const size_t off = ((size_t)it * 2 + h) * T * half + r;
-    const double ll = walker_loglike(partial, skip, nblk, r, lane, nf, fstride);
-    const double lp = lnprior[r];
-    const double newlnp = tempered_lnp(betas[t], ll, lp);
-    const size_t g = (size_t)t * 2 * half + (size_t)h * half + w;
-    const double diff = (lz[off] + newlnp) - lnp[g];
-    if (!(diff > log_u[off])) return;                        // the same in every lane
-    for (int d = lane; d < P; d += 64) pos[g * P + d] = q[(size_t)r * P + d];
-    if (lane == 0) {
-        lnL[g] = newlnp == -INFINITY ? -INFINITY : ll;
-        lnpi[g] = lp;
-        lnp[g] = newlnp;
-        nacc[g] += 1;
-    }
+    lnprior[r] = joint_log_prior(J, fields, n_fields, qr);
 }
 #endif
 

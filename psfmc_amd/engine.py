@@ -337,25 +337,34 @@ MOVE_STRETCH, MOVE_DE = 0, 1          # include/psfmc_hip.h PSFMC_MOVE_*
 
 
 def _move_run(fn, ctx, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store, accumulate):
-    """The arrays of psfmc_move_run / psfmc_move_run_joint (`fn`) shaped and the call made: (rc, (pos, lnprob,
-    chain [W, n_iter, P] | None, lnprob_chain [W, n_iter] | None)); naccepted is updated."""
+    """The arrays of a psfmc_stretch_run* or psfmc_move_run* call (`fn`) shaped and the call made.  The leading
+    dimensions of pos, `lead` = [W] or [F, W], lead every per-walker array; the random arrays are lead[:-1] +
+    [n_iter, 2, W/2].  kind int32 [n_iter] and partner_b: the arrays a move run adds, None for the stretch
+    entry points (scal is then z).  Returns (rc, (pos, lnprob, chain lead + [n_iter, P] | None, lnprob_chain
+    lead + [n_iter] | None)); naccepted, a contiguous int64 array of shape `lead`, is updated."""
     pos = np.array(pos, dtype=np.float64, order='C')
-    n_w, n_p = pos.shape
-    n_iter = int(np.shape(scal)[0])
+    lead, n_p = pos.shape[:-1], pos.shape[-1]
+    if len(lead) not in (1, 2):
+        raise ValueError('pos must be [W, P] or [F, W, P]')
+    n_w = lead[-1]
+    n_iter = int(np.shape(scal)[len(lead) - 1])
+    rand = lead[:-1] + (n_iter, 2, n_w // 2)
     have = lnprob is not None
-    lnp = np.array(lnprob, dtype=np.float64) if have else np.empty(n_w)
-    scal, lz, log_u = (_f64(a).reshape(n_iter, 2, n_w // 2) for a in (scal, lz, log_u))
-    partner, partner_b = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
-                          for a in (partner, partner_b))
-    kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(n_iter)
-    if naccepted.dtype != np.int64 or naccepted.shape != (n_w,) or not naccepted.flags.c_contiguous:
-        raise ValueError('naccepted must be a contiguous int64 [W]')
-    chain = np.empty((n_w, n_iter, n_p)) if store and n_iter else None
-    lnchain = np.empty((n_w, n_iter)) if store and n_iter else None
+    lnp = np.array(lnprob, dtype=np.float64).reshape(lead) if have else np.empty(lead)
+    scal, lz, log_u = (_f64(a).reshape(rand) for a in (scal, lz, log_u))
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    rc = fn(ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(scal), _dp(lz), ipt(partner), _dp(log_u),
-            ipt(kind), ipt(partner_b), _dp(chain) if chain is not None else None,
-            _dp(lnchain) if lnchain is not None else None,
+    partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(rand)
+    moves = ()
+    if kind is not None:
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(n_iter)
+        partner_b = np.ascontiguousarray(partner_b, dtype=np.int32).reshape(rand)
+        moves = (ipt(kind), ipt(partner_b))
+    if naccepted.dtype != np.int64 or naccepted.shape != lead or not naccepted.flags.c_contiguous:
+        raise ValueError('naccepted must be a contiguous int64 {}'.format(list(lead)))
+    chain = np.empty(lead + (n_iter, n_p)) if store and n_iter else None
+    lnchain = np.empty(lead + (n_iter,)) if store and n_iter else None
+    rc = fn(ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(scal), _dp(lz), ipt(partner), _dp(log_u), *moves,
+            _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
             naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate)))
     return rc, (pos, lnp, chain, lnchain)
 
@@ -743,23 +752,10 @@ class Context(object):
         psfmc_stretch_run).  pos [W,P], lnprob [W] or None, z/lz/log_u/partner
         [n_iter, 2, W/2], naccepted int64 [W].  Returns (pos, lnprob, chain
         [W,n_iter,P] | None, lnprob_chain [W,n_iter] | None); naccepted is updated."""
-        pos = np.array(pos, dtype=np.float64, order='C')
-        n_w, n_p = pos.shape
-        n_iter = int(np.shape(z)[0])
-        have = lnprob is not None
-        lnp = np.array(lnprob, dtype=np.float64) if have else np.empty(n_w)
-        z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_w // 2) for a in (z, lz, log_u))
-        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
-        if naccepted.dtype != np.int64 or naccepted.shape != (n_w,):
-            raise ValueError('naccepted must be int64 [W]')
-        chain = np.empty((n_w, n_iter, n_p)) if store and n_iter else None
-        lnchain = np.empty((n_w, n_iter)) if store and n_iter else None
-        self._check(self._lib.psfmc_stretch_run(
-            self._ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(z), _dp(lz),
-            partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(log_u),
-            _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
-            naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
-        return pos, lnp, chain, lnchain
+        rc, out = _move_run(self._lib.psfmc_stretch_run, self._ctx, pos, lnprob, z, lz, partner, log_u, None,
+                            None, naccepted, store, accumulate)
+        self._check(rc)
+        return out
 
     def move_run(self, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store=True,
                  accumulate=False):
@@ -1090,25 +1086,12 @@ class FieldSetContext(object):
         pos [F, W, P], lnprob [F, W] or None, z / lz / log_u / partner [F, n_iter, 2, W/2], naccepted
         int64 [F, W] (updated).  Returns (pos, lnprob, chain [F, W, n_iter, P] | None, lnprob_chain
         [F, W, n_iter] | None)."""
-        pos = np.array(pos, dtype=np.float64, order='C')
-        if pos.ndim != 3 or pos.shape[0] != self.n_fields:
+        if np.ndim(pos) != 3 or np.shape(pos)[0] != self.n_fields:
             raise ValueError('pos must be [n_fields, W, P]')
-        n_f, n_w, n_p = pos.shape
-        n_iter = int(np.shape(z)[1])
-        have = lnprob is not None
-        lnp = np.array(lnprob, dtype=np.float64).reshape(n_f, n_w) if have else np.empty((n_f, n_w))
-        z, lz, log_u = (_f64(a).reshape(n_f, n_iter, 2, n_w // 2) for a in (z, lz, log_u))
-        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_f, n_iter, 2, n_w // 2)
-        if naccepted.dtype != np.int64 or naccepted.shape != (n_f, n_w) or not naccepted.flags.c_contiguous:
-            raise ValueError('naccepted must be a contiguous int64 [n_fields, W]')
-        chain = np.empty((n_f, n_w, n_iter, n_p)) if store and n_iter else None
-        lnchain = np.empty((n_f, n_w, n_iter)) if store and n_iter else None
-        self._check(self._lib.psfmc_stretch_run_fields(
-            self._ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(z), _dp(lz),
-            partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(log_u),
-            _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
-            naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
-        return pos, lnp, chain, lnchain
+        rc, out = _move_run(self._lib.psfmc_stretch_run_fields, self._ctx, pos, lnprob, z, lz, partner, log_u, None,
+                            None, naccepted, store, accumulate)
+        self._check(rc)
+        return out
 
     # -- joint fits: one parameter vector per walker for every field (include/psfmc_hip.h psfmc_*_joint) --
     def set_joint_priors(self, family, params):
@@ -1135,23 +1118,10 @@ class FieldSetContext(object):
         """`Context.stretch_run` for ONE ensemble of joint walkers (psfmc_stretch_run_joint): pos [W, P],
         lnprob [W] or None, z / lz / log_u / partner [n_iter, 2, W/2], naccepted int64 [W] (updated).
         accumulate: every field's posterior sums get the positions after every iteration."""
-        pos = np.array(pos, dtype=np.float64, order='C')
-        n_w, n_p = pos.shape
-        n_iter = int(np.shape(z)[0])
-        have = lnprob is not None
-        lnp = np.array(lnprob, dtype=np.float64) if have else np.empty(n_w)
-        z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_w // 2) for a in (z, lz, log_u))
-        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_w // 2)
-        if naccepted.dtype != np.int64 or naccepted.shape != (n_w,) or not naccepted.flags.c_contiguous:
-            raise ValueError('naccepted must be a contiguous int64 [W]')
-        chain = np.empty((n_w, n_iter, n_p)) if store and n_iter else None
-        lnchain = np.empty((n_w, n_iter)) if store and n_iter else None
-        self._check(self._lib.psfmc_stretch_run_joint(
-            self._ctx, n_w, n_iter, _dp(pos), _dp(lnp), int(have), _dp(z), _dp(lz),
-            partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(log_u),
-            _dp(chain) if chain is not None else None, _dp(lnchain) if lnchain is not None else None,
-            naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), int(bool(accumulate))))
-        return pos, lnp, chain, lnchain
+        rc, out = _move_run(self._lib.psfmc_stretch_run_joint, self._ctx, pos, lnprob, z, lz, partner, log_u, None,
+                            None, naccepted, store, accumulate)
+        self._check(rc)
+        return out
 
     def move_run_joint(self, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, naccepted, store=True,
                        accumulate=False):

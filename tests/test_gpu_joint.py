@@ -169,6 +169,35 @@ def test_device_sampler_equals_the_host_sampler(joint3, n_w):
         m.reset_images()
 
 
+def test_device_sampler_proposes_in_a_second_workgroup():
+    """The joint proposal kernel has one lane per proposal in workgroups of 64: with 132 walkers a half-step is
+    66 proposals, two of them in a second workgroup.  Two fields, six iterations in blocks of four, no image
+    sums; the chain, the log-posteriors and the counters are the host sampler's, bit for bit."""
+    from psfmc_amd import DeviceEnsembleSampler, EnsembleSampler, JointModel
+    n_w, n_iter = 132, 6
+    flds = [make_field(ny, nx, pk, seed=30 + f) for f, (ny, nx, pk) in enumerate(SHAPES[:2])]
+    joint = JointModel([make_model(fld) for fld in flds], per_field=POS, max_walkers=2 * n_w)
+    try:
+        p0 = _joint_truth(joint, flds) + np.random.RandomState(n_w).normal(size=(n_w, joint.num_params)) * 1e-3
+        for f in range(2):
+            p0[:, _col(joint, 'PSF_Index_f%d' % f)] = np.arange(n_w) % 2
+        dev = DeviceEnsembleSampler(n_w, joint, live_dangerously=True, block=4)
+        dev.random_state = np.random.RandomState(700 + n_w).get_state()
+        for _ in dev.sample(p0, iterations=n_iter):
+            pass
+        host = EnsembleSampler(n_w, joint.num_params, batch_lnpostfn=joint.log_posterior_batch, live_dangerously=True)
+        host.random_state = np.random.RandomState(700 + n_w).get_state()
+        for _ in host.sample(p0, iterations=n_iter):
+            pass
+        assert np.array_equal(dev.chain, host.chain)
+        assert np.array_equal(dev.lnprobability, host.lnprobability)
+        assert np.array_equal(dev.naccepted, host.naccepted)
+        # the second workgroup's lanes
+        assert host.naccepted[n_w // 2 - 2:n_w // 2].sum() + host.naccepted[-2:].sum() > 0
+    finally:
+        joint.close()
+
+
 def test_model_joint_mcmc(tmp_path):
     from psfmc_amd import load_database, model_joint_mcmc
     from psfmc_amd import fits_io
