@@ -506,7 +506,8 @@ int psfmc_stretch_set_moves(psfmc_ctx* ctx, const int* kind, const int* partner_
  * Parallel tempering (no reference counterpart; the contract is psfmc_amd/sampler.py's
  * TemperedEnsembleSampler, which these calls reproduce bit for bit).  One-field contexts with every prior
  * on the device; multi-field and joint contexts and PSFMC_PRIOR_HOST columns return PSFMC_EINVAL (a joint fit
- * goes through psfmc_eval_theta_joint_split / psfmc_pt_run_joint below).
+ * goes through psfmc_eval_theta_joint_split / psfmc_pt_run_joint below, the independent fields of a set through
+ * psfmc_eval_theta_split_fields / psfmc_pt_run_fields further down).
  * psfmc_eval_theta_split: psfmc_eval_theta's evaluation with the two terms apart -- lnlike [W] (-inf when
  *   the walker is skipped or its log-likelihood is not finite) and lnprior [W] (the device log-prior plus
  *   extra_lnprior), the values psfmc_pt_run works with.
@@ -563,6 +564,41 @@ int psfmc_pt_run_joint(psfmc_ctx* ctx, int T, int W, int n_iter, const double* b
                        const double* log_u, const int* swap_i, const int* swap_j, const double* swap_log_u,
                        double* chain, double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
                        long long* naccepted, long long* nswap, int accumulate);
+
+/*
+ * Parallel tempering of EVERY field of a set together: contexts of psfmc_ctx_create_fields[_shaped] with
+ * per-field layouts and device priors (no joint priors).  Field f's ladder is its own psfmc_pt_run: given the
+ * same start, ladder and random numbers, every output equals the one of field f's own one-field context bit for
+ * bit (a walker's value does not depend on its batch).
+ * psfmc_eval_theta_split_fields: psfmc_eval_theta_fields (its segments, order and capacity) with the two terms
+ *   apart by psfmc_eval_theta_split's rules -- lnlike [W] -inf where the walker is skipped or its log-likelihood
+ *   is not finite, lnprior [W] the device log-prior plus extra_lnprior.  Where both are finite, lnlike + lnprior
+ *   is psfmc_eval_theta_fields' value bit for bit.
+ * psfmc_pt_run_fields: psfmc_pt_run for the F = n_fields independent ladders, one ladder betas [T] for all.
+ *   Ensemble e = f T + t is rung t of field f; every array of psfmc_pt_run carries the field in front of the
+ *   rung, the random numbers behind the iteration (and half-step):
+ *     pos [F][T][W][P]; lnlike, lnprior, naccepted [F][T][W]; nswap [F][T-1]
+ *     z, lz, log_u, partner [n_iter][2][F][T][W/2]
+ *     swap_i, swap_j, swap_log_u [n_iter][F][T-1][W]
+ *     chain [F][T][W][n_iter][P]; lnprob_chain [F][W][n_iter] (each field's beta = 1 rung);
+ *     lnlike_chain, lnprior_chain [F][T][W][n_iter]
+ *   Launches per iteration do not depend on F or T.  Per half-step: one proposal launch over the F T W/2
+ *   records, one record launch over the F fields, one pipeline pass over F T W/2 records, one accept launch;
+ *   then ONE swap launch, workgroup f doing field f's ladder.  The start state is one batch of F T W records.
+ *   accumulate: after every iteration field f's posterior sums get the W positions of its beta = 1 rung.
+ *   PSFMC_EINVAL, with a psfmc_last_error text and before anything is uploaded, for F T W > max_walkers (the
+ *   text names max_walkers and the field count), an odd W, a bad ladder, a partner outside [0, W/2), swap
+ *   indices out of range or no permutations (per iteration, field and rung pair), a field without a layout, a
+ *   PSFMC_PRIOR_HOST column, or a context with joint priors set.
+ */
+int psfmc_eval_theta_split_fields(psfmc_ctx* ctx, int n_seg, const int* seg_field, const int* seg_count,
+                                  const double* theta, const double* extra_lnprior, double* lnlike,
+                                  double* lnprior);
+int psfmc_pt_run_fields(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos, double* lnlike,
+                        double* lnprior, int state_valid, const double* z, const double* lz, const int* partner,
+                        const double* log_u, const int* swap_i, const int* swap_j, const double* swap_log_u,
+                        double* chain, double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                        long long* naccepted, long long* nswap, int accumulate);
 
 /*
  * The same sampler one half-step at a time, for walkers sharded over several GPUs (one

@@ -6,10 +6,10 @@ from .models import MultiComponentModel, FieldSet, JointModel
 from .ModelComponents import Moffat, Ferrer
 from .batch import BatchLogPosterior
 from .sampler import (EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler, TemperedEnsembleSampler,
-                      DeviceTemperedSampler, default_betas, StretchMove, DEMove)
+                      DeviceTemperedSampler, FieldSetTemperedSampler, default_betas, StretchMove, DEMove)
 from .parallel import RankGroup, ShardedLogPosterior
 from .fitting import (model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc,
-                      model_joint_ptmcmc)
+                      model_joint_ptmcmc, model_fields_ptmcmc)
 from .database import load_database
 
 __version__ = '0.1.0'
@@ -17,4 +17,4 @@ __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior',
            'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler', 'DeviceTemperedSampler',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
            'model_joint_mcmc', 'model_galaxy_ptmcmc', 'model_joint_ptmcmc', 'load_database', 'Moffat', 'Ferrer',
-           'StretchMove', 'DEMove']
+           'StretchMove', 'DEMove', 'FieldSetTemperedSampler', 'model_fields_ptmcmc']

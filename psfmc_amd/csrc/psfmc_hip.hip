@@ -2627,13 +2627,13 @@ extern "C" int psfmc_eval_theta_device(psfmc_ctx* c, int W, const double* d_thet
     return eval_theta_device(c, W, d_theta, d_extra, d_lnprob, stream ? (hipStream_t)stream : c->stream);
 }
 
-// Walkers of several fields in one batch: segment i = seg_count[i] consecutive walkers of field
-// seg_field[i] (host arrays); d_theta [W][P] / d_lnprob [W] in that order, W = sum of the counts.
-// One record derivation per segment (its field's layout), then ONE pass of the likelihood pipeline
-// over all W walkers.
-extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int* seg_field, const int* seg_count,
-                                              const double* d_theta, const double* d_extra, double* d_lnprob,
-                                              void* stream) {
+// psfmc_eval_theta_device_fields (below) up to the pipeline pass: the segments checked, their records derived,
+// their partial sums in c->d_partial.  d_out: the caller's result buffer (checked only).  *n_w: the walkers in
+// all (0: nothing was enqueued)
+static int fields_records_pass(psfmc_ctx* c, int n_seg, const int* seg_field, const int* seg_count,
+                               const double* d_theta, const double* d_extra, const void* d_out, hipStream_t st,
+                               int* n_w) {
+    *n_w = 0;
     if (!c || n_seg < 0 || (n_seg && (!seg_field || !seg_count))) return fail(PSFMC_EINVAL, "bad segment list");
     if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
     long long W = 0;
@@ -2646,9 +2646,8 @@ extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int
     }
     if (W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%lld outside [0, max_walkers=%d]", W, c->max_walkers);
     if (W == 0) return PSFMC_OK;
-    if (!d_lnprob || (c->layout.n_params > 0 && !d_theta)) return fail(PSFMC_EINVAL, "NULL buffer");
+    if (!d_out || (c->layout.n_params > 0 && !d_theta)) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const int P = c->layout.n_params;
     int off = 0;
     for (int i = 0; i < n_seg; ++i) {
@@ -2658,8 +2657,23 @@ extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int
         off += seg_count[i];
     }
     RC_TRY(run_pipeline(c, (int)W, c->d_skip, st));
-    hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks((int)W)), dim3(kFinishThreads), 0, st, c->d_partial,
-                       c->d_skip, c->d_lnprior, d_lnprob, (int)W, c->nblk, 1, 0);
+    *n_w = (int)W;
+    return PSFMC_OK;
+}
+
+// Walkers of several fields in one batch: segment i = seg_count[i] consecutive walkers of field
+// seg_field[i] (host arrays); d_theta [W][P] / d_lnprob [W] in that order, W = sum of the counts.
+// One record derivation per segment (its field's layout), then ONE pass of the likelihood pipeline
+// over all W walkers.
+extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int* seg_field, const int* seg_count,
+                                              const double* d_theta, const double* d_extra, double* d_lnprob,
+                                              void* stream) {
+    hipStream_t st = stream ? (hipStream_t)stream : (c ? c->stream : nullptr);
+    int W = 0;
+    RC_TRY(fields_records_pass(c, n_seg, seg_field, seg_count, d_theta, d_extra, d_lnprob, st, &W));
+    if (W == 0) return PSFMC_OK;
+    hipLaunchKernelGGL(k_finish_posterior, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       c->d_skip, c->d_lnprior, d_lnprob, W, c->nblk, 1, 0);
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;
 }
@@ -2683,6 +2697,36 @@ extern "C" int psfmc_eval_theta_fields(psfmc_ctx* c, int n_seg, const int* seg_f
     RC_TRY(psfmc_eval_theta_device_fields(c, n_seg, seg_field, seg_count, c->d_theta, extra ? c->d_extra : nullptr,
                                           c->d_like, st));
     HIP_TRY(hipMemcpyAsync(lnprob, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PSFMC_OK;
+}
+
+// psfmc_eval_theta_fields with the two terms apart (psfmc_eval_theta_split's rules): the same records and the same
+// pass, the log-likelihoods by k_split_finish, the log-priors as the record derivation left them
+extern "C" int psfmc_eval_theta_split_fields(psfmc_ctx* c, int n_seg, const int* seg_field, const int* seg_count,
+                                             const double* theta, const double* extra, double* lnlike,
+                                             double* lnprior) {
+    if (!c || n_seg < 0 || (n_seg && !seg_count)) return fail(PSFMC_EINVAL, "bad segment list");
+    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    long long W = 0;
+    for (int i = 0; i < n_seg; ++i) W += seg_count[i] > 0 ? seg_count[i] : 0;
+    if (W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%lld outside [0, max_walkers=%d]", W, c->max_walkers);
+    if (W == 0) return PSFMC_OK;
+    if (!lnlike || !lnprior || (c->layout.n_params > 0 && !theta)) return fail(PSFMC_EINVAL, "NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (c->layout.n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+                               hipMemcpyHostToDevice, st));
+    if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
+    int n = 0;
+    RC_TRY(fields_records_pass(c, n_seg, seg_field, seg_count, c->d_theta, extra ? c->d_extra : nullptr, c->d_like, st,
+                               &n));
+    hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st, c->d_partial, c->d_skip,
+                       c->nblk, c->d_like, n, 1, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lnlike, c->d_like, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lnprior, c->d_lnprior, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PSFMC_OK;
 }
@@ -3474,17 +3518,44 @@ extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, 
     return PSFMC_OK;
 }
 
-// psfmc_pt_run, and (joint) psfmc_pt_run_joint: the same ladder rules, index checks, device state, swap kernel
-// and downloads.  A joint walker is F field records: its capacity check counts them, its proposals come from
-// k_joint_propose (k_theta_prep forms the one-field ones itself), and its image sums take every field's records.
-static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const double* betas, double* pos,
+// n vectors d_theta [n_seg][per][P], segment f field f's -> their log-likelihoods d_lnL [n_seg per], their
+// log-priors in c->d_lnprior: one record launch over the fields, one pipeline pass
+static int eval_fields_split_device(psfmc_ctx* c, int n_seg, int per, const double* d_theta, double* d_lnL,
+                                    hipStream_t st) {
+    launch_theta_prep(c, per, d_theta, nullptr, nullptr, st, StretchIn{}, 0, 0, n_seg);
+    RC_TRY(run_pipeline(c, n_seg * per, c->d_skip, st));
+    hipLaunchKernelGGL(k_split_finish, dim3(finish_blocks(n_seg * per)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       c->d_skip, c->nblk, d_lnL, n_seg * per, 1, 0);
+    HIP_TRY(hipGetLastError());
+    return PSFMC_OK;
+}
+
+// psfmc_pt_run, (joint) psfmc_pt_run_joint and (fields) psfmc_pt_run_fields: the same ladder rules, index checks,
+// device state, swap kernel and downloads.  A joint walker is F field records: its capacity check counts them,
+// its proposals come from k_joint_propose (k_theta_prep forms the one-field ones itself), and its image sums take
+// every field's records.  Fields: every field of the context has its own ladder -- L = n_fields ladders, L T
+// ensembles; the host arrays carry the field as their leading dimension, the random numbers behind the
+// iteration (and half-step); proposals by k_pt_fields_propose, records by ONE k_theta_prep launch over the fields.
+enum PtMode { PT_ONE, PT_JOINT, PT_FIELDS };
+static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, const double* betas, double* pos,
                        double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
                        const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
                        const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
                        double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
-    const int F = joint ? c->n_fields : 1;
-    if (joint) {
+    const bool joint = mode == PT_JOINT, fields = mode == PT_FIELDS;
+    const int F = joint ? c->n_fields : 1;        // field records per walker
+    const int L = fields ? c->n_fields : 1;       // ladders
+    if (fields) {
+        if (T < 1 || W < 0 || (long long)L * T * W > c->max_walkers)
+            return fail(PSFMC_EINVAL, "%d fields x T=%d temperatures x W=%d walkers outside [1, max_walkers=%d]", L, T,
+                        W, c->max_walkers);
+        if (c->joint.ready)
+            return fail(PSFMC_EINVAL, "the context has joint priors (psfmc_set_joint_priors): its fields are one joint "
+                        "fit (psfmc_pt_run_joint), not independent ladders");
+        if (W < 2 || (W & 1)) return fail(PSFMC_EINVAL, "W must be even and >= 2");
+        RC_TRY(stretch_check(c, W, L));           // every field a layout, every prior on the device
+    } else if (joint) {
         if (T < 1 || W < 0 || (long long)T * W * F > c->max_walkers)
             return fail(PSFMC_EINVAL, "T=%d temperatures x W=%d walkers x %d fields outside [1, max_walkers=%d]", T, W,
                         F, c->max_walkers);
@@ -3506,14 +3577,22 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
             return fail(PSFMC_EINVAL, "bad temperature ladder at rung %d", t);
     if (T > 1 && betas[T - 1] != 0.0) return fail(PSFMC_EINVAL, "the last rung of the ladder must be beta = 0");
     const int half = W / 2, P = c->layout.n_params;
-    const size_t TW = (size_t)T * W, n_rand = (size_t)n_iter * TW, n_swap = swaps ? (size_t)n_iter * (T - 1) * W : 0;
+    const int E = L * T;                          // ensembles: ensemble e = l T + t is rung t of ladder l
+    const size_t TW = (size_t)E * W, n_rand = (size_t)n_iter * TW,
+                 n_swap = swaps ? (size_t)n_iter * L * (T - 1) * W : 0;
     // every index is checked here: the kernels address walkers by them
     for (size_t i = 0; i < n_rand; ++i)
-        if (partner[i] < 0 || partner[i] >= half) return fail(PSFMC_EINVAL, "partner index %d outside [0, %d)", partner[i], half);
+        if (partner[i] < 0 || partner[i] >= half) {
+            if (fields)
+                return fail(PSFMC_EINVAL, "partner index %d outside [0, %d) (field %d)", partner[i], half,
+                            (int)(i / half % E / T));
+            return fail(PSFMC_EINVAL, "partner index %d outside [0, %d)", partner[i], half);
+        }
     for (size_t i = 0; i < n_swap; ++i)
         if (swap_i[i] < 0 || swap_i[i] >= W || swap_j[i] < 0 || swap_j[i] >= W)
             return fail(PSFMC_EINVAL, "swap index outside [0, %d)", W);
-    // swap pairs must form a matching (the swap kernel gives each pair its own thread)
+    // swap pairs must form a matching (the swap kernel gives each pair its own thread); a row of W pairs per
+    // (iteration, ladder, rung pair)
     if (n_swap) {
         std::vector<int> seen((size_t)2 * W, -1);
         for (size_t r = 0; r < n_swap / W; ++r)
@@ -3526,12 +3605,14 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     // one allocation: doubles, then long longs, then ints, each piece 256-byte aligned
     size_t bytes = 0;
     auto take = [&](size_t n, size_t elem) { const size_t at = bytes; bytes += (n * elem + 255) / 256 * 256; return at; };
-    const size_t o_beta = take(T, 8), o_pos = take(TW * P, 8), o_lnL = take(TW, 8), o_lnpi = take(TW, 8),
-                 o_lnp = take(TW, 8), o_q = take((size_t)T * half * P, 8), o_rand = take(3 * n_rand, 8),
+    // (q: the half-step's proposals; with several ladders also their beta = 1 rungs gathered for the image sums)
+    const size_t n_q = fields && accumulate && T == 1 ? (size_t)L * W : (size_t)E * half;
+    const size_t o_beta = take(E, 8), o_pos = take(TW * P, 8), o_lnL = take(TW, 8), o_lnpi = take(TW, 8),
+                 o_lnp = take(TW, 8), o_q = take(n_q * P, 8), o_rand = take(3 * n_rand, 8),
                  o_slu = take(n_swap, 8), o_chain = take(chain ? TW * n_iter * P : 0, 8),
-                 o_lnpc = take(lnprob_chain ? (size_t)W * n_iter : 0, 8),
+                 o_lnpc = take(lnprob_chain ? (size_t)L * W * n_iter : 0, 8),
                  o_lnlc = take(lnlike_chain ? TW * n_iter : 0, 8), o_lnqc = take(lnprior_chain ? TW * n_iter : 0, 8),
-                 o_nacc = take(TW, 8), o_nswap = take(T, 8),
+                 o_nacc = take(TW, 8), o_nswap = take(E, 8),
                  o_partner = take(n_rand, 4), o_si = take(n_swap, 4), o_sj = take(n_swap, 4);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -3561,10 +3642,10 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
         if (n) HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st));
         return PSFMC_OK;
     };
-    RC_TRY(up(d_beta, betas, T * sizeof(double)));
+    for (int l = 0; l < L; ++l) RC_TRY(up(d_beta + (size_t)l * T, betas, T * sizeof(double)));   // the ladder, per ensemble
     RC_TRY(up(d_pos, pos, TW * P * sizeof(double)));
     RC_TRY(up(d_nacc, naccepted, TW * sizeof(long long)));
-    if (T > 1) RC_TRY(up(d_nswap, nswap, (T - 1) * sizeof(long long)));
+    if (T > 1) RC_TRY(up(d_nswap, nswap, (size_t)L * (T - 1) * sizeof(long long)));
     RC_TRY(up(d_z, z, n_rand * sizeof(double)));
     RC_TRY(up(d_lz, lz, n_rand * sizeof(double)));
     RC_TRY(up(d_logu, log_u, n_rand * sizeof(double)));
@@ -3575,9 +3656,10 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     if (state_valid) {
         RC_TRY(up(d_lnL, lnlike, TW * sizeof(double)));
         RC_TRY(up(d_lnpi, lnprior, TW * sizeof(double)));
-    } else {                                      // every rung's start positions in one batch of T W F records
-        const double* d_start_lnpi = nullptr;
-        RC_TRY(eval_theta_split_device(c, joint, (int)TW, d_pos, nullptr, d_lnL, &d_start_lnpi, st));
+    } else {                                      // every rung's start positions in one batch of L T W F records
+        const double* d_start_lnpi = c->d_lnprior;
+        if (fields) RC_TRY(eval_fields_split_device(c, L, T * W, d_pos, d_lnL, st));
+        else RC_TRY(eval_theta_split_device(c, joint, (int)TW, d_pos, nullptr, d_lnL, &d_start_lnpi, st));
         HIP_TRY(hipMemcpyAsync(d_lnpi, d_start_lnpi, TW * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     hipLaunchKernelGGL(k_pt_tempered, dim3(((int)TW + 255) / 256), dim3(256), 0, st, d_beta, d_lnL, d_lnpi, d_lnp,
@@ -3585,22 +3667,35 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     if (accumulate) RC_TRY(stretch_prepare_accumulation(c));
     // one iteration is seven launches whatever T is: per half-step the T rungs' proposals (one k_theta_prep),
     // one pipeline pass over T half records, one accept kernel; then one swap kernel.  A joint fit adds one
-    // proposal-and-prior kernel per half-step, whatever T and F are; its pass is over T half F records
+    // proposal-and-prior kernel per half-step, whatever T and F are; its pass is over T half F records.  Several
+    // ladders add one proposal kernel per half-step, whatever their number: the L T rungs' proposals
+    // (k_pt_fields_propose), their records (one k_theta_prep launch, blockIdx.y the field), one pass over
+    // L T half records, the accept kernel over L T ensembles; the swap kernel with one workgroup per ladder
     const auto finish = joint ? k_pt_finish<true> : k_pt_finish<false>;     // (one-field: nf = 1 compiled in)
+    const int move_blocks = (int)(((size_t)E * half * P + kMoveThreads - 1) / kMoveThreads);
     for (int it = 0; it < n_iter; ++it) {
         for (int h = 0; h < 2; ++h) {
-            const int n = T * half;
+            const int n = E * half;
             if (joint) launch_joint_propose(c, d_pos, d_q, d_z, d_partner, it, T, half, h, st);
-            else launch_theta_prep(c, n, nullptr, nullptr, nullptr, st,
-                                   StretchIn{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T});
+            else if (fields) {
+                hipLaunchKernelGGL(k_pt_fields_propose, dim3(move_blocks), dim3(kMoveThreads), 0, st, d_pos, d_q, d_z,
+                                   d_partner, it, E, half, h, P);
+                launch_theta_prep(c, T * half, d_q, nullptr, nullptr, st, StretchIn{}, 0, 0, L);
+            } else launch_theta_prep(c, n, nullptr, nullptr, nullptr, st,
+                                     StretchIn{d_pos, d_q, d_z, d_partner, nullptr, it, half, h, 0, 0, 0, 0, T});
             RC_TRY(run_pipeline(c, n * F, c->d_skip, st));
             hipLaunchKernelGGL(finish, dim3(finish_blocks(n)), dim3(kFinishThreads), 0, st, c->d_partial,
                                c->d_skip, c->d_lnprior, c->nblk, d_beta, d_pos, d_lnL, d_lnpi, d_lnp, d_q, d_lz,
-                               d_logu, d_nacc, it, T, half, h, P, F, n);
+                               d_logu, d_nacc, it, E, half, h, P, F, n);
         }
-        hipLaunchKernelGGL(k_pt_swap, dim3(1), dim3(kPtSwapThreads), 0, st, d_beta, d_pos, d_lnL, d_lnpi, d_lnp,
+        hipLaunchKernelGGL(k_pt_swap, dim3(L), dim3(kPtSwapThreads), 0, st, d_beta, d_pos, d_lnL, d_lnpi, d_lnp,
                            d_si, d_sj, d_slu, d_nswap, d_chain, d_lnpc, d_lnlc, d_lnqc, it, n_iter, T, W, P);
-        if (accumulate) {                         // the beta = 1 rung: the first W walkers, every field's sums
+        if (accumulate && fields) {               // every ladder's beta = 1 rung, gathered: field f's sums
+            hipLaunchKernelGGL(k_pt_gather_cold, dim3((int)(((size_t)L * W * P + kMoveThreads - 1) / kMoveThreads)),
+                               dim3(kMoveThreads), 0, st, d_pos, d_q, L, T, W, P);
+            launch_theta_prep(c, W, d_q, nullptr, nullptr, st, StretchIn{}, 0, 0, L);
+            RC_TRY(accumulate_from_prep(c, W * L, st, 0, L, W));
+        } else if (accumulate) {                  // the beta = 1 rung: the first W walkers, every field's sums
             if (joint) launch_theta_prep_joint(c, W, d_pos, nullptr, st);
             else launch_theta_prep(c, W, d_pos, nullptr, nullptr, st, StretchIn{});
             RC_TRY(accumulate_from_prep(c, W * F, st, 0, F, W));
@@ -3615,9 +3710,9 @@ static int pt_run_impl(psfmc_ctx* c, bool joint, int T, int W, int n_iter, const
     RC_TRY(down(lnlike, d_lnL, TW * sizeof(double)));
     RC_TRY(down(lnprior, d_lnpi, TW * sizeof(double)));
     RC_TRY(down(naccepted, d_nacc, TW * sizeof(long long)));
-    if (T > 1) RC_TRY(down(nswap, d_nswap, (T - 1) * sizeof(long long)));
+    if (T > 1) RC_TRY(down(nswap, d_nswap, (size_t)L * (T - 1) * sizeof(long long)));
     if (chain) RC_TRY(down(chain, d_chain, TW * n_iter * P * sizeof(double)));
-    if (lnprob_chain) RC_TRY(down(lnprob_chain, d_lnpc, (size_t)W * n_iter * sizeof(double)));
+    if (lnprob_chain) RC_TRY(down(lnprob_chain, d_lnpc, (size_t)L * W * n_iter * sizeof(double)));
     if (lnlike_chain) RC_TRY(down(lnlike_chain, d_lnlc, TW * n_iter * sizeof(double)));
     if (lnprior_chain) RC_TRY(down(lnprior_chain, d_lnqc, TW * n_iter * sizeof(double)));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3630,7 +3725,7 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
                             const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
                             const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
                             double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
-    return pt_run_impl(c, false, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+    return pt_run_impl(c, PT_ONE, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
                        swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
                        nswap, accumulate);
 }
@@ -3764,6 +3859,18 @@ extern "C" int psfmc_eval_theta_joint_split(psfmc_ctx* c, int W, const double* t
     return PSFMC_OK;
 }
 
+// psfmc_pt_run for every field of the context, each its own ladder of T ensembles of W walkers (pt_run_impl)
+extern "C" int psfmc_pt_run_fields(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                                   double* lnlike, double* lnprior, int state_valid, const double* z,
+                                   const double* lz, const int* partner, const double* log_u, const int* swap_i,
+                                   const int* swap_j, const double* swap_log_u, double* chain, double* lnprob_chain,
+                                   double* lnlike_chain, double* lnprior_chain, long long* naccepted,
+                                   long long* nswap, int accumulate) {
+    return pt_run_impl(c, PT_FIELDS, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate);
+}
+
 // psfmc_pt_run for T ensembles of W joint walkers (pt_run_impl)
 extern "C" int psfmc_pt_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
                                   double* lnlike, double* lnprior, int state_valid, const double* z,
@@ -3771,7 +3878,7 @@ extern "C" int psfmc_pt_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const 
                                   const int* swap_j, const double* swap_log_u, double* chain, double* lnprob_chain,
                                   double* lnlike_chain, double* lnprior_chain, long long* naccepted,
                                   long long* nswap, int accumulate) {
-    return pt_run_impl(c, true, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+    return pt_run_impl(c, PT_JOINT, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
                        swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
                        nswap, accumulate);
 }

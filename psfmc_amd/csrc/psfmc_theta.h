@@ -954,7 +954,9 @@ __global__ void k_pt_finish(const double* __restrict__ partial, const uint8_t* _
 // matching: no two threads touch one walker.  Rungs run one after another (a barrier between them); the rung
 // pair's accepted swaps are reduced in LDS and added to nswap[t-1] by one thread.  Then the iteration's chain
 // entries: every rung's positions, lnL and lnpi (the host yields a resumable state per iteration), lnp of the
-// beta = 1 rung.  ONE workgroup (launch: 1 x kPtSwapThreads).
+// beta = 1 rung.  ONE workgroup per ladder (launch: 1 x kPtSwapThreads; psfmc_pt_run_fields: F x kPtSwapThreads,
+// workgroup f field f's ladder from its offsets into the same arrays, [F] leading every shape but the random
+// numbers', which are [n_iter][F][T-1][W]).
 // swap_i / swap_j / swap_log_u: [n_iter][T-1][W], entry t-1 the pair (t-1, t).
 constexpr int kPtSwapThreads = 256;
 __global__ void __launch_bounds__(kPtSwapThreads)
@@ -966,8 +968,23 @@ k_pt_swap(const double* __restrict__ betas, double* __restrict__ pos, double* __
 #pragma clang fp contract(off)
     __shared__ int count[kPtSwapThreads];
     const int tid = threadIdx.x;
+    size_t row0 = (size_t)it * (T - 1);                      // the iteration's first row of the random numbers
+    if (gridDim.x > 1) {                                     // several ladders: blockIdx.x's (workgroup-uniform)
+        const size_t f = blockIdx.x;
+        row0 = ((size_t)it * gridDim.x + f) * (T - 1);
+        betas += f * T;
+        pos += f * T * W * P;
+        lnL += f * T * W;
+        lnpi += f * T * W;
+        lnp += f * T * W;
+        nswap += f * (T - 1);
+        if (chain) chain += f * T * W * n_iter * P;
+        if (lnprob_chain) lnprob_chain += f * W * n_iter;
+        if (lnlike_chain) lnlike_chain += f * T * W * n_iter;
+        if (lnprior_chain) lnprior_chain += f * T * W * n_iter;
+    }
     for (int t = T - 1; t >= 1; --t) {
-        const size_t roff = ((size_t)it * (T - 1) + (t - 1)) * W;
+        const size_t roff = (row0 + (t - 1)) * W;
         const double b_hot = betas[t], b_cold = betas[t - 1];
         const double dbeta = b_cold - b_hot;
         int mine = 0;
@@ -1102,6 +1119,44 @@ k_move_propose(const double* __restrict__ pos, double* __restrict__ q, const int
         const double ca = c[(size_t)a[off + w] * P + d];
         const double g = scal[off + w];
         q[i] = move == MOVE_DE ? de_point(s[i], ca, c[(size_t)b[off + w] * P + d], g) : stretch_point(s[i], ca, g);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------
+// every field of a set tempered together (psfmc_pt_run_fields): E = F T ensembles of 2 half walkers, ensemble
+// e = f T + t rung t of field f's ladder, rows [e 2 half, (e + 1) 2 half) of pos.
+// ---------------------------------------------------------------------------
+#if PSFMC_PART == 0          /* not a template: defined in the API part only */
+// The half-step stretch proposals q [E half][P] of half h at iteration `it`: record r = e half + w is walker
+// h half + w of ensemble e, its partner from the ensemble's other half; z and partner [n_iter][2][E][half].  One
+// thread per (record, parameter) element, grid-stride over E half P elements (launch: ceil(E half P /
+// kMoveThreads) x kMoveThreads).  Each element is stretch_point's: the roundings of k_theta_prep's proposals.
+__global__ void __launch_bounds__(kMoveThreads)
+k_pt_fields_propose(const double* __restrict__ pos, double* __restrict__ q, const double* __restrict__ z,
+                    const int* __restrict__ partner, int it, int E, int half, int h, int P) {
+    const size_t n = (size_t)E * half * P;
+    const size_t off = ((size_t)it * 2 + h) * E * half;
+    for (size_t i = (size_t)blockIdx.x * kMoveThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kMoveThreads) {
+        const size_t r = i / P;
+        const int d = (int)(i - r * P);
+        const size_t e = r / half;
+        const int w = (int)(r - e * half);
+        const size_t first = e * 2 * half;                       // the ensemble's first walker
+        const double s = pos[(first + (size_t)h * half + w) * P + d];
+        const double c = pos[(first + (size_t)(1 - h) * half + partner[off + r]) * P + d];
+        q[i] = stretch_point(s, c, z[off + r]);
+    }
+}
+
+// the beta = 1 rungs of F ladders, W walkers each, gathered for the posterior-image sums: out [F][W][P] from
+// pos [F][T][W][P].  One thread per element, grid-stride (launch: ceil(F W P / kMoveThreads) x kMoveThreads).
+__global__ void __launch_bounds__(kMoveThreads)
+k_pt_gather_cold(const double* __restrict__ pos, double* __restrict__ out, int F, int T, int W, int P) {
+    const size_t per = (size_t)W * P, n = (size_t)F * per;
+    for (size_t i = (size_t)blockIdx.x * kMoveThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kMoveThreads) {
+        const size_t f = i / per;
+        out[i] = pos[f * T * per + (i - f * per)];
     }
 }
 #endif

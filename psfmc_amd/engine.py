@@ -218,6 +218,10 @@ def load_library():
     lib.psfmc_eval_theta_joint_split.argtypes = [vp, ci, _c_double_p, _c_double_p, _c_double_p]
     lib.psfmc_pt_run_joint.restype = ci
     lib.psfmc_pt_run_joint.argtypes = lib.psfmc_pt_run.argtypes
+    lib.psfmc_eval_theta_split_fields.restype = ci
+    lib.psfmc_eval_theta_split_fields.argtypes = [vp, ci, ip, ip, _c_double_p, _c_double_p, _c_double_p, _c_double_p]
+    lib.psfmc_pt_run_fields.restype = ci
+    lib.psfmc_pt_run_fields.argtypes = lib.psfmc_pt_run.argtypes
     lib.psfmc_accumulate_theta_field.restype = ci
     lib.psfmc_accumulate_theta_field.argtypes = [vp, ci, ci, _c_double_p]
     lib.psfmc_reset_accumulated_field.restype = ci
@@ -371,28 +375,33 @@ def _move_run(fn, ctx, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, n
 
 def _pt_run(fn, ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u, naccepted,
             nswap, store, accumulate):
-    """The arrays of psfmc_pt_run / psfmc_pt_run_joint (`fn`) shaped and the call made; betas [T] and pos
-    [T, W, P] are contiguous float64 already.  Returns (rc, (pos, lnlike, lnprior, chain, lnprob_chain,
-    lnlike_chain, lnprior_chain)); naccepted and nswap are updated."""
-    n_t, n_w, n_p = pos.shape
+    """The arrays of psfmc_pt_run / psfmc_pt_run_joint / psfmc_pt_run_fields (`fn`) shaped and the call made;
+    betas [T] and pos [T, W, P] -- or, for the fields of a set, [F, T, W, P]: `lead` = () or (F,) then leads every
+    per-walker array and follows the iteration (and half-step) in the random ones -- are contiguous float64
+    already.  Returns (rc, (pos, lnlike, lnprior, chain, lnprob_chain, lnlike_chain, lnprior_chain)); naccepted
+    and nswap are updated."""
+    lead, (n_t, n_w, n_p) = pos.shape[:-3], pos.shape[-3:]
     n_iter = int(np.shape(z)[0])
     have = lnlike is not None and lnprior is not None
-    ll = np.array(lnlike, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
-    lp = np.array(lnprior, dtype=np.float64).reshape(n_t, n_w) if have else np.empty((n_t, n_w))
-    z, lz, log_u = (_f64(a).reshape(n_iter, 2, n_t, n_w // 2) for a in (z, lz, log_u))
-    partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(n_iter, 2, n_t, n_w // 2)
+    ll = np.array(lnlike, dtype=np.float64).reshape(lead + (n_t, n_w)) if have else np.empty(lead + (n_t, n_w))
+    lp = np.array(lnprior, dtype=np.float64).reshape(lead + (n_t, n_w)) if have else np.empty(lead + (n_t, n_w))
+    rand = (n_iter, 2) + lead + (n_t, n_w // 2)
+    z, lz, log_u = (_f64(a).reshape(rand) for a in (z, lz, log_u))
+    partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(rand)
     n_sw = max(n_t - 1, 0)
-    swap_i, swap_j = (np.ascontiguousarray(a, dtype=np.int32).reshape(n_iter, n_sw, n_w) for a in (swap_i, swap_j))
-    swap_log_u = _f64(swap_log_u).reshape(n_iter, n_sw, n_w)
-    if naccepted.dtype != np.int64 or naccepted.shape != (n_t, n_w) or not naccepted.flags.c_contiguous:
-        raise ValueError('naccepted must be int64 [T, W]')
-    if nswap.dtype != np.int64 or nswap.shape != (n_sw,):
-        raise ValueError('nswap must be int64 [T-1]')
+    srand = (n_iter,) + lead + (n_sw, n_w)
+    swap_i, swap_j = (np.ascontiguousarray(a, dtype=np.int32).reshape(srand) for a in (swap_i, swap_j))
+    swap_log_u = _f64(swap_log_u).reshape(srand)
+    names = ''.join('F, ' for _ in lead)
+    if naccepted.dtype != np.int64 or naccepted.shape != lead + (n_t, n_w) or not naccepted.flags.c_contiguous:
+        raise ValueError('naccepted must be int64 [{}T, W]'.format(names))
+    if nswap.dtype != np.int64 or nswap.shape != lead + (n_sw,) or not nswap.flags.c_contiguous:
+        raise ValueError('nswap must be int64 [{}T-1]'.format(names))
     store = store and n_iter > 0
-    chain = np.empty((n_t, n_w, n_iter, n_p)) if store else None
-    lnchain = np.empty((n_w, n_iter)) if store else None
-    llchain = np.empty((n_t, n_w, n_iter)) if store else None
-    lpchain = np.empty((n_t, n_w, n_iter)) if store else None
+    chain = np.empty(lead + (n_t, n_w, n_iter, n_p)) if store else None
+    lnchain = np.empty(lead + (n_w, n_iter)) if store else None
+    llchain = np.empty(lead + (n_t, n_w, n_iter)) if store else None
+    lpchain = np.empty(lead + (n_t, n_w, n_iter)) if store else None
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     lpt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
     opt = lambda a: _dp(a) if a is not None else None
@@ -1093,6 +1102,52 @@ class FieldSetContext(object):
         self._check(rc)
         return out
 
+    # -- every field tempered together (include/psfmc_hip.h psfmc_eval_theta_split_fields, psfmc_pt_run_fields) --
+    def eval_split(self, thetas):
+        """`logpost_theta` with the two terms apart (psfmc_eval_theta_split_fields): thetas one [W_f, P] array per
+        field (None or empty to leave a field out) -> list of (lnlike [W_f], lnprior [W_f]); lnlike -inf outside
+        the priors or where it is not finite."""
+        if len(thetas) != self.n_fields:
+            raise ValueError('one parameter array per field')
+        parts = [(f, _f64(t)) for f, t in enumerate(thetas) if t is not None and len(t)]
+        outs = [(np.empty(0), np.empty(0)) for _ in range(self.n_fields)]
+        if not parts:
+            return outs
+        for _, t in parts:
+            if t.ndim != 2 or t.shape[1] != self.n_params:
+                raise ValueError('theta must be [W, {}]'.format(self.n_params))
+        theta = _f64(np.concatenate([t for _, t in parts]))
+        if len(theta) > self.max_walkers:
+            raise ValueError('W={} exceeds max_walkers={}'.format(len(theta), self.max_walkers))
+        f, n, fp, np_ = self._segments([f for f, _ in parts], [len(t) for _, t in parts])
+        ll, lp = np.empty(len(theta)), np.empty(len(theta))
+        self._check(self._lib.psfmc_eval_theta_split_fields(self._ctx, len(f), fp, np_, _dp(theta), None, _dp(ll),
+                                                            _dp(lp)))
+        off = 0
+        for fld, t in parts:
+            outs[fld] = (ll[off:off + len(t)].copy(), lp[off:off + len(t)].copy())
+            off += len(t)
+        return outs
+
+    def pt_run_fields(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+                      naccepted, nswap, store=True, accumulate=False):
+        """`Context.pt_run` for every field's own ladder at once (psfmc_pt_run_fields): betas [T] for all, pos
+        [F,T,W,P], lnlike / lnprior [F,T,W] or None, z/lz/log_u/partner [n_iter,2,F,T,W/2], swap_i/swap_j/
+        swap_log_u [n_iter,F,T-1,W], naccepted int64 [F,T,W], nswap int64 [F,T-1].  Returns `Context.pt_run`'s
+        values with the field in front: (pos, lnlike, lnprior, chain [F,T,W,n_iter,P], lnprob_chain
+        [F,W,n_iter], lnlike_chain, lnprior_chain [F,T,W,n_iter]).  F x T x W <= max_walkers (the library checks
+        it).  accumulate: field f's posterior sums get its beta = 1 rung's positions after every iteration."""
+        betas = _f64(betas)
+        pos = np.array(pos, dtype=np.float64, order='C')
+        if pos.ndim != 4 or pos.shape[0] != self.n_fields or betas.shape != (pos.shape[1],):
+            raise ValueError('pos must be [n_fields, T, W, P] with betas [T]')
+        if pos.shape[3] != self.n_params:
+            raise ValueError('pos must have {} parameters'.format(self.n_params))
+        rc, out = _pt_run(self._lib.psfmc_pt_run_fields, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
+                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        self._check(rc)
+        return out
+
     # -- joint fits: one parameter vector per walker for every field (include/psfmc_hip.h psfmc_*_joint) --
     def set_joint_priors(self, family, params):
         """The joint prior table (every field's layout registered first, with n_params joint columns)."""
@@ -1283,6 +1338,16 @@ class FieldView(object):
         thetas = [None] * self.owner.n_fields
         thetas[self.field] = theta
         return self.owner.logpost_theta(thetas)[self.field]
+
+    def loglike_prior_theta(self, theta, extra_lnprior=None):
+        if self.columns is not None:
+            raise NotImplementedError('field {} is part of a joint fit: its likelihood and prior are the '
+                                      'JointModel\'s (log_likelihood_and_prior_batch)'.format(self.field))
+        if extra_lnprior is not None:
+            raise ValueError('a FieldSet evaluates priors on the GPU only')
+        thetas = [None] * self.owner.n_fields
+        thetas[self.field] = theta
+        return self.owner.eval_split(thetas)[self.field]
 
     def images(self, rows, kinds=None, aux=None):
         return self.owner.images(self.field, rows, kinds, aux=aux)

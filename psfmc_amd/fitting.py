@@ -499,3 +499,108 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
             evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
     _save_joint_images(joint, database, output_name, write_fits)
     return joint, database, evidence
+
+
+def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filetypes, iterations=0, burn=0,
+                        chains=None, ntemps=16, tmax=1e6, betas=None, device=0, random_states=None,
+                        start_positions=None, accumulate=True, quiet=False):
+    """`model_galaxy_ptmcmc` for SEVERAL fields of one model structure at once, in one GPU context
+    (`models.FieldSet`, `sampler.FieldSetTemperedSampler`): the Bayesian evidence of every field's model from
+    one run.  Every field is tempered exactly as its own `model_galaxy_ptmcmc` run would temper it -- its own
+    ladder of `chains` walkers per rung on `betas` (or `default_betas(ntemps, tmax)`; one ladder for all), its
+    own random stream, burn-in, reset, `iterations` sampling iterations with the beta = 1 rung's posterior
+    images accumulated -- but all fields advance together, every half-step's proposals of all fields and rungs
+    ONE batch.  For samples of many small cut-outs, where a ladder per field leaves the GPU idle (DESIGN.md
+    section 24).  The set is sized so that `max_walkers` holds F x ntemps x chains.
+
+    model_files      model files (or MultiComponentModel objects) with the same component lists
+    output_names     one per field (default 'out_<model file>')
+    random_states    one RandomState state tuple or seed per field (default: numpy's global generator
+                     seeds them in field order)
+    start_positions  optional [F][T, chains, P] start positions (default: every rung drawn from its field's priors)
+    Outputs per field: the beta = 1 database `<output_name>_db.fits` with the header keys MCNTEMPS, MCLNZ, MCLNZERR
+    and MCTSWAP, and the posterior images, as `model_galaxy_ptmcmc` writes them.  Existing databases skip
+    sampling; the evidences are then read back from their headers.
+    Returns a list of (model, database, (lnZ, err)), one per field."""
+    from .models import FieldSet
+    from .sampler import FieldSetTemperedSampler, check_betas, default_betas
+    n_f = len(model_files)
+    betas = default_betas(ntemps, tmax) if betas is None else check_betas(betas)
+    n_t = len(betas)
+    if chains is not None and (chains < 2 or chains % 2):
+        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
+                         'two halves'.format(chains))
+    if random_states is not None and len(random_states) != n_f:
+        raise ValueError('random_states: one per field ({} given for {} fields)'.format(len(random_states), n_f))
+    if start_positions is not None and len(start_positions) != n_f:
+        raise ValueError('start_positions: one [T, chains, P] array per field ({} given for {} fields)'.format(
+            len(start_positions), n_f))
+    if output_names is None:
+        output_names = ['out_' + str(f).replace('.py', '') for f in model_files]
+    if len(output_names) != n_f:
+        raise ValueError('one output name per field')
+    output_names = [o + '_{}' for o in output_names]
+    if chains is None:
+        first = model_files[0]
+        if not isinstance(first, MultiComponentModel):
+            first = MultiComponentModel(first, device=device, backend='fused', max_walkers=1)
+            model_files = [first] + list(model_files[1:])
+        chains = 2 * first.num_params + 2
+    fieldset = FieldSet(model_files, max_walkers=n_f * n_t * chains, device=device)
+    models = fieldset.models
+    if start_positions is not None:
+        for f, p in enumerate(start_positions):
+            if np.shape(p) != (n_t, chains, fieldset.num_params):
+                raise ValueError('start_positions[{}] must be [{}, {}, {}], got {}'.format(
+                    f, n_t, chains, fieldset.num_params, np.shape(p)))
+    sampler = FieldSetTemperedSampler(chains, fieldset, betas=betas, accumulate=False)
+    for f, sub in enumerate(sampler.fields):
+        state = None if random_states is None else random_states[f]
+        if state is None:
+            state = int(np.random.randint(0, 2 ** 31 - 1))
+        if isinstance(state, (int, np.integer)):
+            state = np.random.RandomState(int(state)).get_state()
+        sub.random_state = state
+
+    db_names = [o.format('db') + '.fits' for o in output_names]
+    have = [os.path.exists(d) for d in db_names]
+    if any(have) and not all(have):
+        raise ValueError('some of the fields already have a database and some do not: {}'.format(
+            [d for d, h in zip(db_names, have) if h]))
+    evidences = [(float('nan'), float('nan'))] * n_f
+    if not all(have):
+        if start_positions is None:
+            start_positions = [np.stack([m.init_params_from_priors(chains) for _ in range(n_t)]) for m in models]
+        pos = np.array([np.asarray(p, dtype=np.float64) for p in start_positions])
+        lnlike = lnprior = None
+        for step, result in enumerate(sampler.sample(pos, iterations=burn)):
+            pos, lnlike, lnprior = (np.array([r[j] for r in result]) for j in range(3))
+            if not quiet:
+                print_progress(step, burn, 'Burning')
+        sampler.reset()
+        sampler.accumulate = bool(accumulate)
+        for step, result in enumerate(sampler.sample(pos, lnlike, lnprior, iterations=iterations)):
+            pos, lnlike, lnprior = (np.array([r[j] for r in result]) for j in range(3))
+            if not quiet:
+                print_progress(step, iterations, 'Sampling')
+        sampler.accumulate = False
+        databases = []
+        for f, sub in enumerate(sampler.fields):
+            if n_t > 1 and iterations > 0:
+                evidences[f] = sub.log_evidence(fburnin=0.0)
+            meta = OrderedDict([('MCITER', sub.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
+                                ('MCCONVRG', bool(check_convergence_autocorr(sub))),
+                                ('MCACCEPT', float(sub.acceptance_fraction.mean())), ('MCNTEMPS', n_t),
+                                ('MCLNZ', float(evidences[f][0])), ('MCLNZERR', float(evidences[f][1])),
+                                ('MCTSWAP', float(sub.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+            databases.append(save_database(sub, models[f], db_names[f], meta_dict=meta))
+    else:
+        if not quiet:
+            print('Databases already contain sampled chains, skipping sampling')
+        databases = [load_database(d) for d in db_names]
+        for f, db in enumerate(databases):
+            if 'MCLNZ' in db.meta:
+                evidences[f] = (float(db.meta['MCLNZ']), float(db.meta['MCLNZERR']))
+    for m, db, out in zip(models, databases, output_names):
+        save_posterior_images(m, db, output_name=out, filetypes=write_fits)
+    return [(m, db, ev) for m, db, ev in zip(models, databases, evidences)]

@@ -767,6 +767,12 @@ class FieldSet(object):
         """thetas: one [W_f, num_params] array per field -> list of [W_f] log-posteriors."""
         return self.context.logpost_theta(thetas)
 
+    def log_likelihood_and_prior_batch(self, thetas):
+        """thetas: one [W_f, num_params] array per field -> list of (lnL [W_f], lnprior [W_f]), the two terms of
+        `log_posterior_batch` apart from ONE device evaluation (psfmc_eval_theta_split_fields): what the
+        tempered samplers work with.  A member model's own `log_likelihood_and_prior_batch` gives its field's."""
+        return self.context.eval_split(thetas)
+
     def close(self):
         self.context.close()
         for m in self.models:

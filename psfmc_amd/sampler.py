@@ -1093,3 +1093,109 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
                 yield (chain[:, :, j, :].copy(), llchain[:, :, j].copy(), lpchain[:, :, j].copy(),
                        block_states[j])
             done += n
+
+
+class _FieldLadder(TemperedEnsembleSampler):
+    """One field's share of a `FieldSetTemperedSampler`: the `TemperedEnsembleSampler` state of that field's
+    ladder (chain, lnprobability, lnlikelihood, counters, random state, `log_evidence`) -- what `save_database`
+    and `check_convergence_autocorr` read -- and its draws, `DeviceTemperedSampler`'s from its own generator."""
+
+    def __init__(self, nwalkers, model, betas, a=2.0):
+        super(_FieldLadder, self).__init__(nwalkers, model.num_params, betas,
+                                           model.log_likelihood_and_prior_batch, a=a)
+        self.model = model
+
+    _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
+    _draw = DeviceTemperedSampler._draw
+
+
+class FieldSetTemperedSampler(object):
+    """The parallel-tempered device sampler for every field of a `models.FieldSet` at once
+    (`psfmc_pt_run_fields`): each field is its own ladder of T ensembles of `nwalkers` walkers with its own
+    `RandomState` -- exactly the `DeviceTemperedSampler` of that field alone on its own context -- but the
+    half-step proposals of all F T rungs are ONE batch of F T W/2 records, and the launches per iteration do not
+    depend on F or T.  One ladder, `betas` or `default_betas(ntemps, tmax)`, serves every
+    field.  `fields[f]` is field f's `TemperedEnsembleSampler`-style object (`.chain`, `.lnprobability`,
+    `.lnlikelihood`, `.naccepted_t`, `.nswap`, `.random_state`, `.log_evidence()`, ...): its contents equal the
+    field's own run from the same start, random state, ladder and block size bit for bit, so each field gets its
+    own Bayesian evidence.  The set's `max_walkers` must hold F x ntemps x nwalkers.  `accumulate`: every
+    field's posterior images of its beta = 1 rung after every iteration.
+    Stretch move only: there is no `moves` keyword here yet."""
+
+    def __init__(self, nwalkers, fieldset, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
+        if nwalkers % 2 or nwalkers < 2:
+            raise ValueError('The number of walkers must be even.')
+        self.betas = check_betas(default_betas(ntemps, tmax) if betas is None else betas)
+        self.ntemps = len(self.betas)
+        n_f = len(fieldset.models)
+        if n_f * self.ntemps * nwalkers > fieldset.max_walkers:
+            raise ValueError('the FieldSet was built for at most {} walkers in all; {} fields x {} temperatures x {} '
+                             'walkers need more'.format(fieldset.max_walkers, n_f, self.ntemps, nwalkers))
+        self.fieldset = fieldset
+        self.k, self.dim = int(nwalkers), fieldset.num_params
+        self.block = int(block)
+        self.accumulate = bool(accumulate)
+        self.fields = [_FieldLadder(nwalkers, m, self.betas, a=a) for m in fieldset.models]
+
+    def reset(self):
+        for f in self.fields:
+            f.reset()
+
+    def clear_blobs(self):
+        pass
+
+    def sample(self, p0, lnlike0=None, lnprior0=None, iterations=1, thin=1, storechain=True):
+        """p0: [F, T, W, P] (or a list of [T, W, P]) start positions; lnlike0 / lnprior0 [F, T, W] or None
+        (evaluated).  Yields, once per iteration, the list over fields of (pos [T, W, P], lnL [T, W],
+        lnpi [T, W], rstate) -- field f's entry a state its ladder resumes from."""
+        ctx = self.fieldset.context
+        n_f = len(self.fields)
+        p = np.array([f._start(q) for f, q in zip(self.fields, p0)]) if len(p0) == n_f else None
+        if p is None:
+            raise ValueError('p0 must have shape ({}, {}, {}, {})'.format(n_f, self.ntemps, self.k, self.dim))
+        ll = lp = None
+        if lnlike0 is not None and lnprior0 is not None:
+            ll = np.array([np.asarray(q, dtype=np.float64) for q in lnlike0])
+            lp = np.array([np.asarray(q, dtype=np.float64) for q in lnprior0])
+        i0 = [f._grow_storage(iterations, thin, storechain) for f in self.fields]
+        nacc = np.ascontiguousarray([f.naccepted_t.astype(np.int64) for f in self.fields])
+        nsw = np.ascontiguousarray([f.nswap.astype(np.int64) for f in self.fields])
+        done = 0
+
+        def draw(n):
+            per = [f._draw(n) for f in self.fields]            # every field from its own generator
+            # (z, lz, partner, log_u: [n_iter, 2, F, T, W/2]; the swaps' three: [n_iter, F, T-1, W])
+            arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2 if j < 4 else 1))
+                      for j in range(7)]
+            return arrays, [d[1] for d in per]
+
+        # the next block's random numbers are drawn while the GPU runs the current one (DeviceEnsembleSampler)
+        draws, states = draw(min(self.block, iterations)) if iterations > 0 else (None, None)
+        while done < iterations:
+            n = min(self.block, iterations - done)
+            n_next = min(self.block, iterations - done - n)
+            block_states = states
+            job = _run_async(ctx.pt_run_fields, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw,
+                             store=True, accumulate=self.accumulate)
+            try:
+                draws, states = draw(n_next) if n_next > 0 else (None, None)
+            finally:
+                p, ll, lp, chain, lnchain, llchain, lpchain = job()
+            first = (-done) % thin
+            for i, f in enumerate(self.fields):
+                if self.accumulate:
+                    f.model._device_samples += n * self.k
+                    f.model.accumulated_samples += n * self.k
+                if storechain and first < n:
+                    count = (n - first + thin - 1) // thin
+                    dst = i0[i] + (done + first) // thin
+                    f._chain[:, dst:dst + count, :] = chain[i, 0, :, first::thin, :]
+                    f._lnprob[:, dst:dst + count] = lnchain[i][:, first::thin]
+                    f._lnlike[:, :, dst:dst + count] = llchain[i][:, :, first::thin]
+                f.naccepted_t = nacc[i].astype(np.float64)
+                f.nswap = nsw[i].astype(np.float64)
+                f.iterations += n
+            for j in range(n):
+                yield [(chain[i, :, :, j, :].copy(), llchain[i, :, :, j].copy(), lpchain[i, :, :, j].copy(),
+                        block_states[i][j]) for i in range(n_f)]
+            done += n
