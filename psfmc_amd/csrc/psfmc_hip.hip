@@ -194,7 +194,7 @@ struct psfmc_ctx {
     bool rows3_fwd = false, rows3_inv = false;
     long long speculated_runs = 0;   // psfmc_stretch_run calls that took the whole-iteration route
     int speculate = -1;       // device sampler: ensembles of up to 2 x this many walkers run ONE pipeline pass per iteration (0 = never, -1 = the default rule)
-    int cols3 = 1;            // column kernel (set_option "cols3", launch_cols): 0 the two-stage k_cols (sides <= 1024 only), 1 the defaults (k_cols3f at 512 / 1024 / 1536 / 2048, k_cols3g at the other sides of fft3g_pick), 2 k_cols3g at those four as well, 3 round 3's k_cols3 at 512 / 1024 (elsewhere as 2), 4 the same as 1
+    int cols3 = 1;            // column kernel (set_option "cols3"; decided by col_engine alone): 0 the two-stage k_cols (sides <= 1024 only), 1 the defaults (k_cols3f at 512 / 1024 / 1536 / 2048, k_cols3g at the other sides of fft3g_pick), 2 k_cols3g at those four as well, 3 round 3's k_cols3 at 512 / 1024 (elsewhere as 2), 4 the same as 1; f32 storage takes k_cols3 at 512 / 1024 unless 0
     bool use_graph = false;   // psfmc_stretch_run replays a captured iteration (set_option "graph"; measured: no gain,
                               // the iteration is kernel-time- not launch-bound)
     long long graph_launches = 0;
@@ -349,317 +349,341 @@ struct RowShape { int rg, fast_waves, fast_rg_log2, regs; bool plain; };
 // ---------------------------------------------------------------------------
 // fused path launchers
 // ---------------------------------------------------------------------------
-// TS = the T element type: cd (complex128) or cf (complex64 STORAGE, set_option "storage_f32";
-// built for the power-of-two shapes only)
+// Which kernel a launch takes is decided ONCE, by the three constexpr choice functions below (column engine,
+// forward rows, inverse rows): the launchers switch on their answers and psfmc_get_option reports them
+// ("column_engine", "raster_group").  A new kernel family goes into its choice function and its launcher's switch.
+// f32: the T element type is cf (complex64 STORAGE, set_option "storage_f32"; built for the power-of-two shapes
+// only) instead of cd (complex128)
 template <int N> constexpr bool plain_side() {
     if constexpr (two_stage_side(N)) return FftShape<N>::kPlain;
     else return false;
 }
-template <int N, typename TS> constexpr bool storage_built() { return sizeof(TS) == sizeof(cd) || plain_side<N>(); }
+template <int N> constexpr bool storage_built(bool f32) { return !f32 || plain_side<N>(); }
 
-// ---- the three-stage row kernels (psfmc_rows3_path.h) ----
-template <int NX, bool FROM_IMAGE, bool WRAP, bool EXTRA = false>
-static int launch_rows3_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, cd* Tbuf, int ps_only,
-                                   const double* img, const double* img_scale, double* raw_out, hipStream_t st) {
-    using S = typename Rows3<NX>::S;
-    constexpr size_t lds = rows3_lds_bytes<S>();
-    if constexpr (!FROM_IMAGE && !EXTRA) {
-        // pixel-integrated components: the same kernel with their image added (its own instantiation)
-        if (const double* extra = ps_only ? nullptr : extra_image_of(c, prep))
-            return launch_rows3_fwd_kernel<NX, false, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra, img_scale, raw_out,
-                                                                  st);
+// the launch-relevant facts of a context.  t_f32 is the storage of THIS launch: the context's for a batch of walkers,
+// complex128 for the kernel spectra at set-up and for the convolution of the posterior sums
+struct LaunchFacts {
+    int cols3, rg_log2;
+    bool t_f32, embed, rows3_fwd, rows3_inv, row_fast, multi;      // multi: n_fields > 1
+};
+static LaunchFacts launch_facts(const psfmc_ctx* c, bool t_f32) {
+    return LaunchFacts{c->cols3, c->rg_log2, t_f32, c->embed, c->rows3_fwd, c->rows3_inv, c->row_fast, c->n_fields > 1};
+}
+
+// what a choice answers instead of a kernel, and the launcher returns
+enum Refusal { REFUSE_NOT, REFUSE_F32_SIDE, REFUSE_F32_GUARDED, REFUSE_F32_EMBED, REFUSE_F32_FIELDS, REFUSE_NO_ROWS3,
+               REFUSE_COLS3_ONLY };
+static int refuse(Refusal why, int side) {
+    switch (why) {
+        case REFUSE_F32_SIDE: return fail(PSFMC_EINVAL, "single-precision storage is built for power-of-two sides only");
+        case REFUSE_F32_GUARDED: return fail(PSFMC_EINVAL, "single-precision storage needs the unguarded row kernels");
+        case REFUSE_F32_EMBED: return fail(PSFMC_EINVAL, "single-precision storage does not serve embedded images");
+        case REFUSE_F32_FIELDS: return fail(PSFMC_EINVAL, "single-precision storage serves contexts of one field");
+        case REFUSE_NO_ROWS3: return fail(PSFMC_EINVAL, "side %d has no three-stage row kernels", side);
+        case REFUSE_COLS3_ONLY:
+            return fail(PSFMC_EINVAL, "side %d has only the three-stage column kernel (option cols3 = 0 and row groups "
+                        "other than 4 do not apply)", side);
+        case REFUSE_NOT: break;
     }
-    if constexpr (lds > 64 * 1024) {
+    return fail(PSFMC_EINVAL, "internal: side %d was chosen a kernel it is not built with", side);
+}
+
+// ---- the column engine; the values are what get_option("column_engine") reports ----
+enum ColEngine { COL_REFUSED = -1, COL_COLS = 0, COL_COLS3 = 1, COL_COLS3G = 2, COL_COLS3F = 3 };
+// whether side NY has the engine for this storage: what the choice may answer, and what launch_cols instantiates
+template <int NY> constexpr bool col_engine_built(ColEngine e, bool f32) {
+    switch (e) {
+        case COL_COLS: return two_stage_side(NY);
+        case COL_COLS3: return NY == 512 || NY == 1024;                       // long power-of-two columns, wave-wide
+        case COL_COLS3G: return cols3g_side<NY>() && !f32;                    // the sides of psfmc_fft.h fft3g_pick
+        case COL_COLS3F: return cols3f_shape<Fft3gShape<NY>>() && !f32;       // ny = 8 m x 64: 512, 1024, 1536, 2048
+        default: return false;
+    }
+}
+template <int NY> constexpr ColEngine col_engine(const LaunchFacts& f) {
+    // k_cols3f: the general three-stage engine run forward both ways (round 4).
+    // In the flow (same box, whole step): 512^2 +1.6 %, 1536^2 +18 %, 2048^2 +2 % (+5.4 % more with its load
+    // pipeline, cols3f_prefetch); at 1024 its third wave per SIMD measured SLOWER than k_cols3 (57.5 vs 52.7 us
+    // per 6-walker pass, step -0.8 %: 6 MB of columns in flight per XCD against a 4-MiB L2 that also has to hold
+    // the kernel-spectrum columns), with the load pipeline at two waves per SIMD it is the faster one (51.4 vs
+    // 52.6 us in the flow, step +0.5 %).  cols3 = 3 asks for k_cols3 at 512 / 1024; f32 storage takes it whenever
+    // cols3 is not 0
+    if (col_engine_built<NY>(COL_COLS3F, f.t_f32) && (f.cols3 == 1 || f.cols3 == 4)) return COL_COLS3F;
+    if (col_engine_built<NY>(COL_COLS3, f.t_f32) && (f.cols3 == 3 || (f.cols3 && f.t_f32))) return COL_COLS3;
+    // (so cols3 = 3 acts as 2 away from 512 / 1024); a row group the engine's layout does not serve falls back
+    if (col_engine_built<NY>(COL_COLS3G, f.t_f32) && f.cols3 && cols3g_layout_ok<Fft3gShape<NY>>(f.rg_log2))
+        return COL_COLS3G;
+    return col_engine_built<NY>(COL_COLS, f.t_f32) ? COL_COLS : COL_REFUSED;
+}
+
+// ---- the row kernels ----
+// ROWS3: one row per wave, three stages (psfmc_rows3_path.h); ROWS2_*: the two-stage kernels of psfmc_fused_path.h,
+// FAST the unguarded power-of-two ones (ny a whole number of their workgroups), GUARDED the general code path of
+// the same shape
+enum RowFamily { ROWS_REFUSED, ROWS3, ROWS2_FAST, ROWS2_GUARDED };
+struct RowChoice {
+    RowFamily family;
+    bool flag;          // forward: WRAP, the rasteriser wraps its coordinates; inverse: MULTI, chi^2 summed per field
+    Refusal why;
+};
+constexpr RowChoice row_refused(Refusal why) { return RowChoice{ROWS_REFUSED, false, why}; }
+// whether side NX has the family's forward / inverse kernel for this storage, and the kernel with the flag set: what
+// the choices may answer, and what the launchers instantiate
+template <int NX> constexpr bool row_family_built(RowFamily fam, bool f32, bool forward) {
+    switch (fam) {
+        case ROWS3: return !f32 && (forward ? rows3_fwd_built(NX) : rows3_side<NX>());
+        case ROWS2_FAST: return plain_side<NX>();
+        case ROWS2_GUARDED: return two_stage_side(NX) && !f32;
+        default: return false;
+    }
+}
+// WRAP: records rasterised into complex128 storage (images from memory -- the PSF canvases at set-up, the posterior
+// sums -- are in transform coordinates already)
+constexpr bool wrap_built(bool from_image, bool f32) { return !from_image && !f32; }
+// MULTI: every three-stage side; on the two-stage kernels from 1024 with complex128 storage (below, one text tells
+// the fields apart at run time)
+template <int NX> constexpr bool multi_built(RowFamily fam, bool f32) { return fam == ROWS3 || (!f32 && NX >= 1024); }
+
+template <int NX> constexpr RowChoice rows_fwd_choice(const LaunchFacts& f, bool from_image) {
+    if (!storage_built<NX>(f.t_f32)) return row_refused(REFUSE_F32_SIDE);
+    const bool wrap = !from_image && f.embed;              // the rasteriser of an embedded image wraps its coordinates
+    if (!two_stage_side(NX) || (f.rows3_fwd && !f.t_f32))
+        return row_family_built<NX>(ROWS3, f.t_f32, true) ? RowChoice{ROWS3, wrap, REFUSE_NOT} : row_refused(REFUSE_NO_ROWS3);
+    const bool fast = plain_side<NX>() && f.row_fast;
+    if (f.t_f32 && !fast) return row_refused(REFUSE_F32_GUARDED);
+    if (wrap && !wrap_built(from_image, f.t_f32)) return row_refused(REFUSE_F32_EMBED);
+    return RowChoice{fast ? ROWS2_FAST : ROWS2_GUARDED, wrap, REFUSE_NOT};
+}
+template <int NX> constexpr RowChoice rows_inv_choice(const LaunchFacts& f) {
+    if (!storage_built<NX>(f.t_f32)) return row_refused(REFUSE_F32_SIDE);
+    if (!two_stage_side(NX) || (f.rows3_inv && !f.t_f32))
+        return row_family_built<NX>(ROWS3, f.t_f32, false) ? RowChoice{ROWS3, f.multi, REFUSE_NOT} : row_refused(REFUSE_NO_ROWS3);
+    const bool fast = plain_side<NX>() && f.row_fast;
+    if (f.t_f32 && !fast) return row_refused(REFUSE_F32_GUARDED);
+    if (f.t_f32 && f.multi) return row_refused(REFUSE_F32_FIELDS);
+    const RowFamily fam = fast ? ROWS2_FAST : ROWS2_GUARDED;
+    return RowChoice{fam, f.multi && multi_built<NX>(fam, f.t_f32), REFUSE_NOT};
+}
+// the G of the raster_row the chosen forward kernel runs (get_option("raster_group")); 0: log2 + exp2 per pixel
+template <int NX> constexpr int raster_group_of(const RowChoice& ch) {
+    if constexpr (two_stage_side(NX)) {
+        if (ch.family == ROWS2_FAST || ch.family == ROWS2_GUARDED)
+            return ch.flag ? fwd_raster_group<NX, true>() : fwd_raster_group<NX, false>();
+    }
+    return rows3_raster_group(ch.flag);
+}
+
+// The choices pinned to the literal values the device tests assert through get_option (tests/test_gpu_variants.py
+// COLUMN_CASES, the raster-form table of tests/helpers.py): rows of 64 pixels come in groups of 8, of 96 / 100 in
+// groups of 4 (of 1024 in groups of 2)
+constexpr LaunchFacts col_facts(int cols3, int row_group, bool f32 = false) {
+    return LaunchFacts{cols3, row_group == 8 ? 3 : row_group == 4 ? 2 : 1, f32, false, false, false, true, false};
+}
+#define PSFMC_PIN_COLS(NY, cols3, engine) \
+    static_assert(col_engine<NY>(col_facts(cols3, 4)) == engine && col_engine<NY>(col_facts(cols3, 8)) == engine, #NY " " #cols3)
+PSFMC_PIN_COLS(512, 0, COL_COLS);   PSFMC_PIN_COLS(512, 1, COL_COLS3F);  PSFMC_PIN_COLS(512, 2, COL_COLS3G);
+PSFMC_PIN_COLS(512, 3, COL_COLS3);  PSFMC_PIN_COLS(512, 4, COL_COLS3F);
+PSFMC_PIN_COLS(1024, 0, COL_COLS);  PSFMC_PIN_COLS(1024, 1, COL_COLS3F); PSFMC_PIN_COLS(1024, 2, COL_COLS3G);
+PSFMC_PIN_COLS(1024, 3, COL_COLS3); PSFMC_PIN_COLS(1024, 4, COL_COLS3F);
+PSFMC_PIN_COLS(1536, 1, COL_COLS3F); PSFMC_PIN_COLS(1536, 2, COL_COLS3G); PSFMC_PIN_COLS(1536, 3, COL_COLS3G);
+PSFMC_PIN_COLS(1536, 4, COL_COLS3F); PSFMC_PIN_COLS(2048, 2, COL_COLS3G);
+PSFMC_PIN_COLS(384, 0, COL_COLS);   PSFMC_PIN_COLS(500, 0, COL_COLS);    PSFMC_PIN_COLS(640, 0, COL_COLS);
+PSFMC_PIN_COLS(900, 0, COL_COLS);   PSFMC_PIN_COLS(384, 1, COL_COLS3G);
+#undef PSFMC_PIN_COLS
+// 520 = 10 x 52: k_cols3g's L = 52 lanes are a multiple of 4 but not of 8 (cols3g_layout_ok)
+static_assert(col_engine<520>(col_facts(1, 4)) == COL_COLS3G && col_engine<520>(col_facts(2, 4)) == COL_COLS3G);
+static_assert(col_engine<520>(col_facts(1, 8)) == COL_COLS && col_engine<520>(col_facts(2, 8)) == COL_COLS);
+// f32 storage: k_cols3 whenever cols3 is not 0
+static_assert(col_engine<512>(col_facts(1, 8, true)) == COL_COLS3 && col_engine<512>(col_facts(1, 4, true)) == COL_COLS3 &&
+              col_engine<1024>(col_facts(2, 8, true)) == COL_COLS3 && col_engine<512>(col_facts(0, 4, true)) == COL_COLS &&
+              col_engine<128>(col_facts(1, 2, true)) == COL_COLS);
+// the transform of an embedded 530-pixel image; no engine: cols3 = 0 above 1024 (set_option refuses it there)
+static_assert(col_engine<576>(col_facts(1, 4)) == COL_COLS3G && col_engine<576>(col_facts(0, 4)) == COL_COLS &&
+              col_engine<1152>(col_facts(1, 4)) == COL_COLS3G && col_engine<1536>(col_facts(0, 4)) == COL_REFUSED);
+// the raster group (embedded: WRAP): an image of 170 pixels is embedded in 192, one of 270 in 294, one of 1100 in 1152
+template <int NX> constexpr int raster_group_pin(bool embed) {
+    return raster_group_of<NX>(rows_fwd_choice<NX>(LaunchFacts{1, 2, false, embed, !two_stage_side(NX), !two_stage_side(NX),
+                                                               false, false}, false));
+}
+static_assert(raster_group_pin<64>(false) == 0 && raster_group_pin<256>(false) == 0 && raster_group_pin<264>(false) == 1 &&
+              raster_group_pin<288>(false) == 4 && raster_group_pin<512>(false) == 2 && raster_group_pin<1152>(false) == 1);
+static_assert(raster_group_pin<1152>(true) == 1 && raster_group_pin<294>(true) == 1 && raster_group_pin<192>(true) == 0);
+// MULTI and WRAP where they apply, and the refusal of several fields in f32 storage
+static_assert(rows_inv_choice<64>(LaunchFacts{1, 3, true, false, false, false, true, true}).why == REFUSE_F32_FIELDS &&
+              !rows_inv_choice<512>(LaunchFacts{1, 2, false, false, false, false, true, true}).flag &&
+              rows_inv_choice<1024>(LaunchFacts{1, 1, false, false, false, false, true, true}).flag &&
+              rows_inv_choice<676>(LaunchFacts{1, 2, false, false, false, true, false, true}).flag &&
+              rows_inv_choice<676>(LaunchFacts{1, 2, false, false, false, true, false, true}).family == ROWS3 &&
+              rows_fwd_choice<676>(LaunchFacts{1, 2, false, false, false, true, false, true}, false).family == ROWS2_GUARDED &&
+              !rows_fwd_choice<576>(LaunchFacts{1, 2, false, true, false, false, false, false}, true).flag);
+
+// per-side answers about the row kernels, and everything a size-erased call carries (below)
+struct RowFamilies { bool two_stage, rows3_inv, rows3_fwd, rows3_inv_default; };
+struct SizeCall {
+    psfmc_ctx* c = nullptr;
+    int n = 0;                              // walkers
+    const double* prep = nullptr;
+    const uint8_t* skip = nullptr;
+    void* T = nullptr;
+    int ps_only = 0;
+    const double *img = nullptr, *img_scale = nullptr;
+    double *raw_out = nullptr, *partial = nullptr, *conv_out = nullptr, *var_out = nullptr;
+    hipStream_t st = nullptr;
+    bool from_image = false, convolve = true, f32 = false, rows3 = false;
+    int field = 0, groups = 0, group_size = 0, ny = 0, per_field = 0;
+    RowShape* shape = nullptr;
+    RowFamilies* families = nullptr;
+    size_t* len = nullptr;
+    int* code = nullptr;
+};
+
+// ---- one launch body per direction ----
+// raise kernel K's dynamic-LDS limit once per device (and thread) where it asks for more than every launch's 64 KiB
+template <auto K, size_t LDS> static int raise_lds_limit(const psfmc_ctx* c) {
+    if constexpr (LDS > 64 * 1024) {
         static thread_local int attr_device = -1;
         if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows3_fwd<NX, FROM_IMAGE, WRAP, S, EXTRA>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)LDS));
             attr_device = c->device;
         }
     }
-    if (!FROM_IMAGE && !c->prep_tabs_valid)
-        return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
-    hipLaunchKernelGGL((k_rows3_fwd<NX, FROM_IMAGE, WRAP, S, EXTRA>), dim3((c->ny + rows3_waves(NX) - 1) / rows3_waves(NX), n),
-                       dim3(rows3_threads(NX)), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic, c->ny, ps_only, img,
-                       img_scale, raw_out, c->d_wrap, c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
     return PSFMC_OK;
 }
-template <int NX, bool FROM_IMAGE>
-static int launch_rows3_fwd(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, cd* Tbuf, int ps_only,
-                            const double* img, const double* img_scale, double* raw_out, hipStream_t st) {
-    if constexpr (!rows3_fwd_built(NX)) {
-        return fail(PSFMC_EINVAL, "side %d has no three-stage row kernels", NX);
-    } else {
-        if constexpr (!FROM_IMAGE) {
-            if (c->embed)
-                return launch_rows3_fwd_kernel<NX, false, true>(c, n, prep, skip, Tbuf, ps_only, img, img_scale, raw_out, st);
-        }
-        return launch_rows3_fwd_kernel<NX, FROM_IMAGE, false>(c, n, prep, skip, Tbuf, ps_only, img, img_scale, raw_out, st);
-    }
-}
-template <int NX, bool MULTI>
-static int launch_rows3_inv_kernel(psfmc_ctx* c, int n, const cd* Tbuf, const double* prep, const uint8_t* skip,
-                                   double* partial, double* conv_out, double* var_out, hipStream_t st) {
+// a row family's kernels for the template flags, its LDS bytes, block size and grid.x
+template <int NX> struct Rows3Family {
     using S = typename Rows3<NX>::S;
-    constexpr size_t lds = rows3_lds_bytes<S>();
-    if constexpr (lds > 64 * 1024) {
-        static thread_local int attr_device = -1;
-        if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows3_inv<NX, MULTI>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_device = c->device;
-        }
+    static constexpr RowFamily kFamily = ROWS3;
+    static constexpr size_t kLds = rows3_lds_bytes<S>();
+    static constexpr int kThreads = rows3_threads(NX);
+    template <bool FROM_IMAGE, bool WRAP, bool EXTRA, typename TS> static constexpr auto fwd() {
+        return &k_rows3_fwd<NX, FROM_IMAGE, WRAP, S, EXTRA>;
     }
-    hipLaunchKernelGGL((k_rows3_inv<NX, MULTI>), dim3((c->ny + rows3_waves(NX) - 1) / rows3_waves(NX), n), dim3(rows3_threads(NX)), lds,
-                       st, Tbuf, skip, c->d_twx, c->d_field, partial, c->ny, prep, c->plen, conv_out, var_out,
+    template <bool MULTI, typename TS> static constexpr auto inv() { return &k_rows3_inv<NX, MULTI>; }
+    static int grid_x(const psfmc_ctx* c) { return (c->ny + rows3_waves(NX) - 1) / rows3_waves(NX); }
+};
+template <int NX, bool FAST> struct Rows2Family {
+    static constexpr RowFamily kFamily = FAST ? ROWS2_FAST : ROWS2_GUARDED;
+    static constexpr size_t kLds = fused_row_lds_bytes<NX, FAST>();
+    static constexpr int kThreads = row_threads<NX, FAST>();
+    template <bool FROM_IMAGE, bool WRAP, bool EXTRA, typename TS> static constexpr auto fwd() {
+        return &k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP, EXTRA>;
+    }
+    template <bool MULTI, typename TS> static constexpr auto inv() { return &k_rows_inv<NX, TS, FAST, MULTI>; }
+    static int grid_x(const psfmc_ctx* c) { return (c->nblk + row_waves<NX, FAST>() - 1) / row_waves<NX, FAST>(); }
+};
+// `launch` on the chosen family's traits: the choice's run-time answer as a template argument.  A family the side is
+// not built with for this storage (forward or inverse kernel) is never named
+template <int NX, bool F32, bool FORWARD, class Launch> static int with_row_family(const RowChoice& ch, Launch launch) {
+    switch (ch.family) {
+        case ROWS3:
+            if constexpr (row_family_built<NX>(ROWS3, F32, FORWARD)) return launch(Rows3Family<NX>{});
+            break;
+        case ROWS2_FAST:
+            if constexpr (row_family_built<NX>(ROWS2_FAST, F32, FORWARD)) return launch(Rows2Family<NX, true>{});
+            break;
+        case ROWS2_GUARDED:
+            if constexpr (row_family_built<NX>(ROWS2_GUARDED, F32, FORWARD)) return launch(Rows2Family<NX, false>{});
+            break;
+        case ROWS_REFUSED: break;
+    }
+    return refuse(ch.why, NX);
+}
+
+template <class Fam, bool FROM_IMAGE, bool WRAP, typename TS, bool EXTRA = false>
+static int launch_fwd_kernel(const SizeCall& a, const double* img) {
+    psfmc_ctx* c = a.c;
+    if constexpr (!FROM_IMAGE && !EXTRA) {
+        // pixel-integrated components: the same kernel with their image added (its own instantiation)
+        if (const double* extra = a.ps_only ? nullptr : extra_image_of(c, a.prep))
+            return launch_fwd_kernel<Fam, false, WRAP, TS, true>(a, extra);
+    }
+    constexpr auto K = Fam::template fwd<FROM_IMAGE, WRAP, EXTRA, TS>();
+    RC_TRY((raise_lds_limit<K, Fam::kLds>(c)));
+    if (!FROM_IMAGE && !c->prep_tabs_valid)
+        return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
+    hipLaunchKernelGGL(K, dim3(Fam::grid_x(c), a.n), dim3(Fam::kThreads), Fam::kLds, a.st, a.prep, a.skip, c->d_twx,
+                       static_cast<TS*>(a.T), c->n_ps, c->n_sersic, c->ny, a.ps_only, img, a.img_scale, a.raw_out,
+                       c->d_wrap, c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
+    return PSFMC_OK;
+}
+template <int NX, bool FROM_IMAGE, typename TS = cd> static int launch_rows_fwd(const SizeCall& a) {
+    constexpr bool F32 = sizeof(TS) != sizeof(cd);
+    const RowChoice ch = rows_fwd_choice<NX>(launch_facts(a.c, F32), FROM_IMAGE);
+    return with_row_family<NX, F32, true>(ch, [&](auto fam) -> int {
+        using Fam = decltype(fam);
+        if constexpr (wrap_built(FROM_IMAGE, F32))
+            if (ch.flag) return launch_fwd_kernel<Fam, FROM_IMAGE, true, TS>(a, a.img);
+        return launch_fwd_kernel<Fam, FROM_IMAGE, false, TS>(a, a.img);
+    });
+}
+
+template <class Fam, bool MULTI, typename TS> static int launch_inv_kernel(const SizeCall& a) {
+    psfmc_ctx* c = a.c;
+    constexpr auto K = Fam::template inv<MULTI, TS>();
+    RC_TRY((raise_lds_limit<K, Fam::kLds>(c)));
+    hipLaunchKernelGGL(K, dim3(Fam::grid_x(c), a.n), dim3(Fam::kThreads), Fam::kLds, a.st, static_cast<const TS*>(a.T),
+                       a.skip, c->d_twx, c->d_field, a.partial, c->ny, a.prep, c->plen, a.conv_out, a.var_out,
                        c->n_fields > 1 ? c->n_psf_field : 0, (unsigned)c->field_len);
     return PSFMC_OK;
 }
-template <int NX>
-static int launch_rows3_inv(psfmc_ctx* c, int n, const cd* Tbuf, const double* prep, const uint8_t* skip,
-                            double* partial, double* conv_out, double* var_out, hipStream_t st) {
-    if constexpr (!rows3_side<NX>()) {
-        return fail(PSFMC_EINVAL, "side %d has no three-stage row kernels", NX);
-    } else {
-        if (c->n_fields > 1) return launch_rows3_inv_kernel<NX, true>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-        return launch_rows3_inv_kernel<NX, false>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-    }
+template <int NX, typename TS = cd> static int launch_rows_inv(const SizeCall& a) {
+    constexpr bool F32 = sizeof(TS) != sizeof(cd);
+    const RowChoice ch = rows_inv_choice<NX>(launch_facts(a.c, F32));
+    return with_row_family<NX, F32, false>(ch, [&](auto fam) -> int {
+        using Fam = decltype(fam);
+        if constexpr (multi_built<NX>(Fam::kFamily, F32))
+            if (ch.flag) return launch_inv_kernel<Fam, true, TS>(a);
+        return launch_inv_kernel<Fam, false, TS>(a);
+    });
 }
 
-template <int NX, bool FROM_IMAGE, typename TS, bool FAST, bool WRAP, bool EXTRA = false>
-static int launch_rows_fwd_kernel(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, TS* Tbuf,
-                                  int ps_only, const double* img, const double* img_scale, double* raw_out,
-                                  hipStream_t st) {
-    constexpr size_t lds = fused_row_lds_bytes<NX, FAST>();
-    if constexpr (!FROM_IMAGE && !EXTRA) {
-        // pixel-integrated components: the same kernel with their image added (its own instantiation)
-        if (const double* extra = ps_only ? nullptr : extra_image_of(c, prep))
-            return launch_rows_fwd_kernel<NX, false, TS, FAST, WRAP, true>(c, n, prep, skip, Tbuf, ps_only, extra,
-                                                                           img_scale, raw_out, st);
-    }
-    if constexpr (lds > 64 * 1024) {
-        static thread_local int attr_device = -1;
-        if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP, EXTRA>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_device = c->device;
-        }
-    }
-    constexpr int waves = row_waves<NX, FAST>();
-    if (!FROM_IMAGE && !c->prep_tabs_valid)
-        return fail(PSFMC_EINVAL, "internal: forward rows launched on prep records without a power-table decision");
-    hipLaunchKernelGGL((k_rows_fwd<NX, FROM_IMAGE, TS, FAST, WRAP, EXTRA>), dim3((c->nblk + waves - 1) / waves, n),
-                       dim3((row_threads<NX, FAST>())), lds, st, prep, skip, c->d_twx, Tbuf, c->n_ps, c->n_sersic,
-                       c->ny, ps_only, img, img_scale, raw_out, c->d_wrap,
-                       c->prep_tabs_built ? kPowTabsBuilt : kPowTabsInWave);
+// the grid of the wave-wide column kernels: a wave per column, per_block of them in a workgroup
+static int cols3_grid(const psfmc_ctx* c, int n_cols, int per_block) {
+    const int blocks = (n_cols + per_block - 1) / per_block;
+    return blocks < 4 * c->cols_grid ? blocks : 4 * c->cols_grid;
+}
+template <auto K, size_t LDS, typename TS> static int launch_col_kernel(const SizeCall& a, int grid, int threads) {
+    psfmc_ctx* c = a.c;
+    RC_TRY((raise_lds_limit<K, LDS>(c)));
+    hipLaunchKernelGGL(K, dim3(grid), dim3(threads), LDS, a.st, static_cast<TS*>(a.T), c->d_Kt, a.prep, a.skip, c->d_twy,
+                       c->plen, c->nxh, a.n, c->rg_log2);
     return PSFMC_OK;
 }
-
-template <int NX, bool FROM_IMAGE, typename TS, bool FAST>
-static int launch_rows_fwd_impl(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, TS* Tbuf,
-                                int ps_only, const double* img, const double* img_scale, double* raw_out,
-                                hipStream_t st) {
-    // the rasteriser of an embedded image wraps its coordinates (images from memory -- the PSF canvases at
-    // set-up, the posterior sums -- are in transform coordinates already)
-    if constexpr (!FROM_IMAGE && sizeof(TS) == sizeof(cd)) {
-        if (c->embed)
-            return launch_rows_fwd_kernel<NX, FROM_IMAGE, TS, FAST, true>(c, n, prep, skip, Tbuf, ps_only, img,
-                                                                          img_scale, raw_out, st);
-    }
-    if (!FROM_IMAGE && c->embed) return fail(PSFMC_EINVAL, "single-precision storage does not serve embedded images");
-    return launch_rows_fwd_kernel<NX, FROM_IMAGE, TS, FAST, false>(c, n, prep, skip, Tbuf, ps_only, img, img_scale,
-                                                                   raw_out, st);
-}
-
-// c->row_fast: the unguarded power-of-two row kernels (ny a whole number of their workgroups);
-// otherwise the guarded general code path of the same shape
-template <int NX, bool FROM_IMAGE, typename TS = cd>
-static int launch_rows_fwd(psfmc_ctx* c, int n, const double* prep, const uint8_t* skip, void* Tvoid,
-                           int ps_only, const double* img, const double* img_scale, double* raw_out,
-                           hipStream_t st) {
-    if constexpr (!storage_built<NX, TS>()) {
-        return fail(PSFMC_EINVAL, "single-precision storage is built for power-of-two sides only");
-    } else if constexpr (!two_stage_side(NX)) {
-        return launch_rows3_fwd<NX, FROM_IMAGE>(c, n, prep, skip, static_cast<cd*>(Tvoid), ps_only, img, img_scale, raw_out, st);
+template <int NY, bool CONVOLVE, typename TS = cd> static int launch_cols(const SizeCall& a) {
+    constexpr bool F32 = sizeof(TS) != sizeof(cd);
+    if constexpr (!storage_built<NY>(F32)) {
+        return refuse(REFUSE_F32_SIDE, NY);
     } else {
-        TS* Tbuf = static_cast<TS*>(Tvoid);
-        if constexpr (sizeof(TS) == sizeof(cd)) {
-            if (c->rows3_fwd)
-                return launch_rows3_fwd<NX, FROM_IMAGE>(c, n, prep, skip, static_cast<cd*>(Tvoid), ps_only, img, img_scale,
-                                                        raw_out, st);
+        psfmc_ctx* c = a.c;
+        using S3 = Fft3gShape<NY>;
+        const int n_cols = a.n * 2 * c->nxh;
+        switch (col_engine<NY>(launch_facts(c, F32))) {
+            case COL_COLS3F:
+                if constexpr (col_engine_built<NY>(COL_COLS3F, F32))
+                    return launch_col_kernel<&k_cols3f<NY, CONVOLVE>, fused_col3f_lds_bytes<S3>(), TS>(
+                        a, cols3_grid(c, n_cols, cols3f_waves<S3>()), cols3f_threads<S3>());
+                break;
+            case COL_COLS3:
+                if constexpr (col_engine_built<NY>(COL_COLS3, F32))
+                    return launch_col_kernel<&k_cols3<NY, CONVOLVE, TS>, fused_col3_lds_bytes<NY>(), TS>(
+                        a, cols3_grid(c, n_cols, kColThreads / 64), kColThreads);
+                break;
+            case COL_COLS3G:
+                if constexpr (col_engine_built<NY>(COL_COLS3G, F32))
+                    return launch_col_kernel<&k_cols3g<NY, CONVOLVE>, fused_col3g_lds_bytes<S3>(), TS>(
+                        a, cols3_grid(c, n_cols, cols3g_waves<S3>()), cols3g_threads<S3>());
+                break;
+            case COL_COLS:                  // persistent: a workgroup takes col_ffts_per_block columns at a time
+                if constexpr (col_engine_built<NY>(COL_COLS, F32)) {
+                    const int groups = (n_cols + col_ffts_per_block<NY>() - 1) / col_ffts_per_block<NY>();
+                    return launch_col_kernel<&k_cols<NY, CONVOLVE, TS>, fused_col_lds_bytes<NY>(), TS>(
+                        a, groups < c->cols_grid ? groups : c->cols_grid, kColThreads);
+                }
+                break;
+            case COL_REFUSED: break;
         }
-        if constexpr (FftShape<NX>::kPlain) {
-            if (c->row_fast)
-                return launch_rows_fwd_impl<NX, FROM_IMAGE, TS, true>(c, n, prep, skip, Tbuf, ps_only, img,
-                                                                      img_scale, raw_out, st);
-        }
-        if constexpr (sizeof(TS) == sizeof(cd)) {
-            return launch_rows_fwd_impl<NX, FROM_IMAGE, TS, false>(c, n, prep, skip, Tbuf, ps_only, img,
-                                                                   img_scale, raw_out, st);
-        } else {
-            return fail(PSFMC_EINVAL, "single-precision storage needs the unguarded row kernels");
-        }
-    }
-}
-
-template <int NY, bool CONVOLVE, typename TS = cd>
-static int launch_cols(psfmc_ctx* c, void* Tvoid, int n_w, const double* prep, const uint8_t* skip,
-                       hipStream_t st) {
-  if constexpr (!storage_built<NY, TS>()) {
-    return fail(PSFMC_EINVAL, "single-precision storage is built for power-of-two sides only");
-  } else {
-    TS* Tbuf = static_cast<TS*>(Tvoid);
-    const int n_cols = n_w * 2 * c->nxh;
-    if constexpr (cols3f_shape<Fft3gShape<NY>>() && sizeof(TS) == sizeof(cd)) {
-        // ny = 8 m x 64 (512, 1024, 1536, 2048): the general three-stage engine run forward both ways (round 4).
-        // In the flow (same box, whole step): 512^2 +1.6 %, 1536^2 +18 %, 2048^2 +2 % (+5.4 % more with its load
-        // pipeline, cols3f_prefetch); at 1024 its third wave per SIMD measured SLOWER than k_cols3 (57.5 vs 52.7 us
-        // per 6-walker pass, step -0.8 %: 6 MB of columns in flight per XCD against a 4-MiB L2 that also has to hold
-        // the kernel-spectrum columns), with the load pipeline at two waves per SIMD it is the faster one (51.4 vs
-        // 52.6 us in the flow, step +0.5 %).  cols3 = 3 asks for k_cols3 at 512 / 1024
-        if (c->cols3 == 1 || c->cols3 == 4) {
-            using S3 = Fft3gShape<NY>;
-            constexpr size_t lds3 = fused_col3f_lds_bytes<S3>();
-            static thread_local int attr3f_device = -1;
-            if (attr3f_device != c->device) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cols3f<NY, CONVOLVE>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-                attr3f_device = c->device;
-            }
-            const int per_block = cols3f_waves<S3>();
-            const int blocks = (n_cols + per_block - 1) / per_block;
-            const int grid3 = blocks < 4 * c->cols_grid ? blocks : 4 * c->cols_grid;
-            hipLaunchKernelGGL((k_cols3f<NY, CONVOLVE>), dim3(grid3), dim3(cols3f_threads<S3>()), lds3, st, Tbuf, c->d_Kt, prep, skip,
-                               c->d_twy, c->plen, c->nxh, n_w, c->rg_log2);
-            return PSFMC_OK;
-        }
-    }
-    if constexpr (NY == 512 || NY == 1024) {          // long power-of-two columns: wave-wide three-stage engine
-        if (c->cols3 == 3 || (c->cols3 && sizeof(TS) != sizeof(cd))) {
-            constexpr size_t lds3 = fused_col3_lds_bytes<NY>();
-            const int per_block = kColThreads / 64;
-            const int blocks = (n_cols + per_block - 1) / per_block;
-            const int grid3 = blocks < 4 * c->cols_grid ? blocks : 4 * c->cols_grid;
-            hipLaunchKernelGGL((k_cols3<NY, CONVOLVE, TS>), dim3(grid3), dim3(kColThreads), lds3, st, Tbuf,
-                               c->d_Kt, prep, skip, c->d_twy, c->plen, c->nxh, n_w, c->rg_log2);
-            return PSFMC_OK;
-        }
-    }
-    if constexpr (cols3g_side<NY>() && sizeof(TS) == sizeof(cd)) {   // the sides of psfmc_fft.h fft3g_pick: general three-stage engine
-        if (c->cols3 && cols3g_layout_ok<Fft3gShape<NY>>(c->rg_log2)) {
-            constexpr size_t lds3 = fused_col3g_lds_bytes<Fft3gShape<NY>>();
-            static thread_local int attr3_device = -1;
-            if (attr3_device != c->device) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cols3g<NY, CONVOLVE>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-                attr3_device = c->device;
-            }
-            const int per_block = cols3g_waves<Fft3gShape<NY>>();
-            const int blocks = (n_cols + per_block - 1) / per_block;
-            const int grid3 = blocks < 4 * c->cols_grid ? blocks : 4 * c->cols_grid;
-            hipLaunchKernelGGL((k_cols3g<NY, CONVOLVE>), dim3(grid3), dim3(cols3g_threads<Fft3gShape<NY>>()), lds3, st, Tbuf, c->d_Kt, prep,
-                               skip, c->d_twy, c->plen, c->nxh, n_w, c->rg_log2);
-            return PSFMC_OK;
-        }
-    }
-    if constexpr (!two_stage_side(NY)) {
-        return fail(PSFMC_EINVAL, "side %d has only the three-stage column kernel (option cols3 = 0 and row groups "
-                    "other than 4 do not apply)", NY);
-    } else {
-    constexpr size_t lds = fused_col_lds_bytes<NY>();
-    static thread_local int attr_device = -1;          // raise the dynamic-LDS limit once per device
-    if (attr_device != c->device) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cols<NY, CONVOLVE, TS>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_device = c->device;
-    }
-    const int groups = (n_cols + col_ffts_per_block<NY>() - 1) / col_ffts_per_block<NY>();
-    const int grid = groups < c->cols_grid ? groups : c->cols_grid;
-    hipLaunchKernelGGL((k_cols<NY, CONVOLVE, TS>), dim3(grid), dim3(kColThreads), lds, st, Tbuf, c->d_Kt,
-                       prep, skip, c->d_twy, c->plen, c->nxh, n_w, c->rg_log2);
-    return PSFMC_OK;
-    }
-  }
-}
-
-// which column kernel launch_cols takes for this context: 0 k_cols, 1 k_cols3, 2 k_cols3g, 3 k_cols3f (the same conditions)
-template <int NY> static int col_engine_code(const psfmc_ctx* c) {
-    if constexpr (cols3f_shape<Fft3gShape<NY>>()) {
-        if ((c->cols3 == 1 || c->cols3 == 4) && !c->t_f32) return 3;
-    }
-    if constexpr (NY == 512 || NY == 1024) {
-        if (c->cols3 == 3 || (c->cols3 && c->t_f32)) return 1;
-    }
-    if constexpr (cols3g_side<NY>()) {
-        if (!c->t_f32 && c->cols3 && cols3g_layout_ok<Fft3gShape<NY>>(c->rg_log2)) return 2;
-    }
-    return 0;
-}
-
-// the G of the raster_row this context's forward row kernel runs (launch_rows_fwd's choices); 0: log2 + exp2 per pixel
-template <int NX> static int raster_group_code(const psfmc_ctx* c) {
-    if constexpr (!two_stage_side(NX)) {
-        return rows3_raster_group(c->embed);
-    } else {
-        if (c->rows3_fwd) return rows3_raster_group(c->embed);
-        return c->embed ? fwd_raster_group<NX, true>() : fwd_raster_group<NX, false>();
-    }
-}
-
-template <int NX, typename TS, bool FAST, bool MULTI>
-static int launch_rows_inv_kernel(psfmc_ctx* c, int n, const TS* Tbuf, const double* prep, const uint8_t* skip,
-                                  double* partial, double* conv_out, double* var_out, hipStream_t st) {
-    constexpr size_t lds = fused_row_lds_bytes<NX, FAST>();
-    if constexpr (lds > 64 * 1024) {
-        static thread_local int attr_device = -1;
-        if (attr_device != c->device) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_inv<NX, TS, FAST, MULTI>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_device = c->device;
-        }
-    }
-    constexpr int waves = row_waves<NX, FAST>();
-    const int gx = (c->nblk + waves - 1) / waves;
-    hipLaunchKernelGGL((k_rows_inv<NX, TS, FAST, MULTI>), dim3(gx, n),
-                       dim3((row_threads<NX, FAST>())), lds, st, Tbuf, skip, c->d_twx, c->d_field, partial, c->ny,
-                       prep, c->plen, conv_out, var_out, c->n_fields > 1 ? c->n_psf_field : 0, (unsigned)c->field_len);
-    return PSFMC_OK;
-}
-
-template <int NX, typename TS, bool FAST>
-static int launch_rows_inv_impl(psfmc_ctx* c, int n, const TS* Tbuf, const double* prep, const uint8_t* skip,
-                                double* partial, double* conv_out, double* var_out, hipStream_t st) {
-    if constexpr (sizeof(TS) == sizeof(cd) && NX >= 1024) {
-        if (c->n_fields > 1)
-            return launch_rows_inv_kernel<NX, TS, FAST, true>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-    } else if constexpr (sizeof(TS) != sizeof(cd)) {
-        if (c->n_fields > 1) return fail(PSFMC_EINVAL, "single-precision storage serves contexts of one field");
-    }
-    return launch_rows_inv_kernel<NX, TS, FAST, false>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-}
-
-template <int NX, typename TS = cd>
-static int launch_rows_inv(psfmc_ctx* c, int n, const void* Tvoid, const double* prep, const uint8_t* skip,
-                           double* partial, double* conv_out, double* var_out, hipStream_t st) {
-    if constexpr (!storage_built<NX, TS>()) {
-        return fail(PSFMC_EINVAL, "single-precision storage is built for power-of-two sides only");
-    } else if constexpr (!two_stage_side(NX)) {
-        return launch_rows3_inv<NX>(c, n, static_cast<const cd*>(Tvoid), prep, skip, partial, conv_out, var_out, st);
-    } else {
-        const TS* Tbuf = static_cast<const TS*>(Tvoid);
-        if constexpr (sizeof(TS) == sizeof(cd)) {
-            if (c->rows3_inv)
-                return launch_rows3_inv<NX>(c, n, static_cast<const cd*>(Tvoid), prep, skip, partial, conv_out, var_out, st);
-        }
-        if constexpr (FftShape<NX>::kPlain) {
-            if (c->row_fast)
-                return launch_rows_inv_impl<NX, TS, true>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-        }
-        if constexpr (sizeof(TS) == sizeof(cd)) {
-            return launch_rows_inv_impl<NX, TS, false>(c, n, Tbuf, prep, skip, partial, conv_out, var_out, st);
-        } else {
-            return fail(PSFMC_EINVAL, "single-precision storage needs the unguarded row kernels");
-        }
+        return refuse(REFUSE_COLS3_ONLY, NY);
     }
 }
 
@@ -691,11 +715,10 @@ template <int NX> static RowShape row_shape_of(bool rows3) {
     else
         return RowShape{1, rows3_waves(NX), rows3_rg_log2(NX), 0, false};
 }
-// bit 0: a two-stage family exists; bit 1: the three-stage inverse kernel is built; bit 2: the forward one;
-// bit 3: the three-stage inverse kernel is the default
-template <int NX> constexpr int row_families() {
-    return (two_stage_side(NX) ? 1 : 0) | (rows3_side<NX>() ? 2 : 0) | (rows3_fwd_built(NX) ? 4 : 0) |
-           (rows3_side<NX>() && rows3_inv_default(NX) ? 8 : 0);
+// which row kernels the side is built with: a two-stage family, the three-stage inverse kernel, the forward one, and
+// whether the three-stage inverse kernel is the default
+template <int NX> constexpr RowFamilies row_families() {
+    return RowFamilies{two_stage_side(NX), rows3_side<NX>(), rows3_fwd_built(NX), rows3_side<NX>() && rows3_inv_default(NX)};
 }
 template <int NX> static size_t field_len_of(int ny, bool rows3) {
     if constexpr (rows3_side<NX>()) {
@@ -704,32 +727,21 @@ template <int NX> static size_t field_len_of(int ny, bool rows3) {
     if constexpr (two_stage_side(NX)) return fused_field_len<NX>(ny);
     else return 0;
 }
-template <int NX> constexpr bool has_rows3() { return rows3_side<NX>(); }
 
-template <int NX>
-static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int groups, int group_size, hipStream_t st,
-                              int per_field, int f0) {
+// one launch: the kernel is chosen by WRAP (an embedded image) and EXTRA (pixel-integrated components: their image
+// is added, one more argument)
+template <int NX> static int launch_raster_sums(const SizeCall& a) {
+    psfmc_ctx* c = a.c;
     constexpr int RG = RasterShape<NX>::TPW;
-    if (const double* extra = extra_image_of(c, prep)) {      // pixel-integrated components: their image is added
-        if (c->embed)
-            hipLaunchKernelGGL((k_raster_sums_extra<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
-                               c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
-                               f0, c->n_psf_field, c->d_wrap, extra);
-        else
-            hipLaunchKernelGGL((k_raster_sums_extra<NX, false>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
-                               c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
-                               f0, c->n_psf_field, c->d_wrap, extra);
-        return PSFMC_OK;
-    }
-    if (c->embed) {
-        hipLaunchKernelGGL((k_raster_sums<NX, true>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep,
-                           c->plen, n, group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field,
-                           f0, c->n_psf_field, c->d_wrap);
-        return PSFMC_OK;
-    }
-    hipLaunchKernelGGL((k_raster_sums<NX, false>), dim3((c->ny + RG - 1) / RG, groups), dim3(64), 0, st, prep, c->plen, n,
-                       group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, per_field, f0,
-                       c->n_psf_field, c->d_wrap);
+    auto launch = [&](auto kernel, auto... extra) {
+        hipLaunchKernelGGL(kernel, dim3((c->ny + RG - 1) / RG, a.groups), dim3(64), 0, a.st, a.prep, c->plen, a.n,
+                           a.group_size, c->n_ps, c->n_sersic, c->ny, c->n_psf, c->d_linpart, a.per_field, a.field,
+                           c->n_psf_field, c->d_wrap, extra...);
+    };
+    if (const double* extra = extra_image_of(c, a.prep))
+        launch(c->embed ? &k_raster_sums_extra<NX, true> : &k_raster_sums_extra<NX, false>, extra);
+    else
+        launch(c->embed ? &k_raster_sums<NX, true> : &k_raster_sums<NX, false>);
     return PSFMC_OK;
 }
 
@@ -738,29 +750,13 @@ static int launch_raster_sums(psfmc_ctx* c, int n, const double* prep, int group
 // size-erased entry to the per-side launchers: what crosses the boundary between the parts
 // ---------------------------------------------------------------------------
 enum SizeOp { SZ_ROW_SHAPE, SZ_FIELD_LEN, SZ_PACK_FIELD, SZ_ROWS_FWD, SZ_COLS, SZ_ROWS_INV, SZ_RASTER_SUMS, SZ_COL_ENGINE, SZ_RASTER_GROUP };
-struct SizeCall {
-    psfmc_ctx* c = nullptr;
-    int n = 0;                              // walkers
-    const double* prep = nullptr;
-    const uint8_t* skip = nullptr;
-    void* T = nullptr;
-    int ps_only = 0;
-    const double *img = nullptr, *img_scale = nullptr;
-    double *raw_out = nullptr, *partial = nullptr, *conv_out = nullptr, *var_out = nullptr;
-    hipStream_t st = nullptr;
-    bool from_image = false, convolve = true, f32 = false, rows3 = false;
-    int field = 0, groups = 0, group_size = 0, ny = 0, per_field = 0;
-    RowShape* shape = nullptr;
-    size_t* len = nullptr;
-    int* code = nullptr;
-};
 
 static int size_call_here(int op, int side, SizeCall& a) {
     psfmc_ctx* c = a.c;
     switch (op) {
         case SZ_ROW_SHAPE:
-            // (a.rows3: the caller asks for the three-stage row family where the side has both; a.code: whether it has it)
-            DISPATCH_LEN(side, (*a.shape = row_shape_of<N_>(a.rows3), *a.code = row_families<N_>()));
+            // (a.rows3: the caller asks for the three-stage row family where the side has both)
+            DISPATCH_LEN(side, (*a.shape = row_shape_of<N_>(a.rows3), *a.families = row_families<N_>()));
             return PSFMC_OK;
         case SZ_FIELD_LEN:
             DISPATCH_LEN(side, *a.len = field_len_of<N_>(a.ny, a.rows3));
@@ -770,43 +766,38 @@ static int size_call_here(int op, int side, SizeCall& a) {
             return PSFMC_OK;
         case SZ_ROWS_FWD:
             if (a.from_image) {
-                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, true>(c, a.n, a.prep, a.skip, a.T, a.ps_only, a.img,
-                                                                     a.img_scale, a.raw_out, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, true>(a))));
             } else if (a.f32) {
-                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, false, cf>(c, a.n, a.prep, a.skip, a.T, a.ps_only, a.img,
-                                                                          a.img_scale, a.raw_out, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, false, cf>(a))));
             } else {
-                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, false>(c, a.n, a.prep, a.skip, a.T, a.ps_only, a.img,
-                                                                      a.img_scale, a.raw_out, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_rows_fwd<N_, false>(a))));
             }
             return PSFMC_OK;
         case SZ_COLS:
             if (!a.convolve) {
-                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, false>(c, a.T, a.n, a.prep, a.skip, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, false>(a))));
             } else if (a.f32) {
-                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, true, cf>(c, a.T, a.n, a.prep, a.skip, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, true, cf>(a))));
             } else {
-                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, true>(c, a.T, a.n, a.prep, a.skip, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_cols<N_, true>(a))));
             }
             return PSFMC_OK;
         case SZ_ROWS_INV:
             if (a.f32) {
-                DISPATCH_LEN(side, RC_TRY((launch_rows_inv<N_, cf>(c, a.n, a.T, a.prep, a.skip, a.partial, a.conv_out,
-                                                                   a.var_out, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_rows_inv<N_, cf>(a))));
             } else {
-                DISPATCH_LEN(side, RC_TRY((launch_rows_inv<N_>(c, a.n, a.T, a.prep, a.skip, a.partial, a.conv_out,
-                                                               a.var_out, a.st))));
+                DISPATCH_LEN(side, RC_TRY((launch_rows_inv<N_>(a))));
             }
             return PSFMC_OK;
         case SZ_RASTER_SUMS:
-            DISPATCH_LEN(side, RC_TRY((launch_raster_sums<N_>(c, a.n, a.prep, a.groups, a.group_size, a.st,
-                                                              a.per_field, a.field))));
+            DISPATCH_LEN(side, RC_TRY(launch_raster_sums<N_>(a)));
             return PSFMC_OK;
+        // what get_option reports: the choices' answers for the context's own storage (no column engine: 0, as ever)
         case SZ_COL_ENGINE:
-            DISPATCH_LEN(side, *a.code = col_engine_code<N_>(c));
+            DISPATCH_LEN(side, *a.code = std::max<int>(COL_COLS, col_engine<N_>(launch_facts(c, c->t_f32))));
             return PSFMC_OK;
         case SZ_RASTER_GROUP:
-            DISPATCH_LEN(side, *a.code = raster_group_code<N_>(c));
+            DISPATCH_LEN(side, *a.code = raster_group_of<N_>(rows_fwd_choice<N_>(launch_facts(c, c->t_f32), false)));
             return PSFMC_OK;
     }
     return fail(PSFMC_EINVAL, "unknown size operation %d", op);
@@ -837,16 +828,14 @@ static int size_call(int op, int side, SizeCall& a) {
 #endif
 }
 
-// rows3_wanted: the shape of the three-stage row family where the side has both; *family: row_families' bits
-static int row_shape_for(int nx, RowShape* out, bool rows3_wanted = false, int* family = nullptr) {
+// rows3_wanted: the shape of the three-stage row family where the side has both; *families: which it is built with
+static int row_shape_for(int nx, RowShape* out, bool rows3_wanted = false, RowFamilies* families = nullptr) {
     SizeCall a;
-    int code = 0;
+    RowFamilies fam{};
     a.shape = out;
     a.rows3 = rows3_wanted;
-    a.code = &code;
-    const int rc = size_call(SZ_ROW_SHAPE, nx, a);
-    if (family) *family = code;
-    return rc;
+    a.families = families ? families : &fam;
+    return size_call(SZ_ROW_SHAPE, nx, a);
 }
 
 static int flush_linear_sums(psfmc_ctx* c);   // posterior-image sums: see psfmc_reset_accumulated
@@ -1297,11 +1286,11 @@ static int ctx_create_impl(psfmc_ctx** out, int device, int n_fields, const int*
         }
         const char* env3 = getenv("PSFMC_ROWS3");
         const int force = env3 ? (atoi(env3) != 0 ? 1 : 0) : -1;          // -1: the defaults
-        int fam = 0;
+        RowFamilies fam{};
         RC_TRY(row_shape_for(nx, &rs, false, &fam));                       // (the two-stage shape where there is one)
-        const bool two = fam & 1;
-        rows3_inv = !two || ((fam & 2) && (force == 1 || (force < 0 && (fam & 8))));
-        rows3_fwd = !two || ((fam & 4) && force == 1);
+        const bool two = fam.two_stage;
+        rows3_inv = !two || (fam.rows3_inv && (force == 1 || (force < 0 && fam.rows3_inv_default)));
+        rows3_fwd = !two || (fam.rows3_fwd && force == 1);
         // a power-of-two side takes both kernels of a family (their layouts differ: row groups of 2 against 4)
         if (two && rs.plain && rows3_inv != rows3_fwd) rows3_inv = rows3_fwd = false;
         row_tiles = rows3_inv ? ny : (ny + rs.rg - 1) / rs.rg;             // chi^2 partial sums per walker
@@ -1532,7 +1521,7 @@ extern "C" int psfmc_set_option(psfmc_ctx* c, const char* key, double value) {
         return PSFMC_OK;
     }
     if (!strcmp(key, "cols3")) {
-        // refused here, not at the next evaluation: only the engines launch_cols knows, and k_cols only where the
+        // refused here, not at the next evaluation: only the engines col_engine knows, and k_cols only where the
         // transform's column side has a two-stage kernel
         if (!(value >= 0 && value <= 4) || value != (double)(int)value)
             return fail(PSFMC_EINVAL, "cols3 must be one of 0, 1, 2, 3, 4 (got %g)", value);
@@ -1584,19 +1573,16 @@ extern "C" double psfmc_get_option(const psfmc_ctx* cc, const char* key) {
     }
     if (!strcmp(key, "row_group")) return 1 << c->rg_log2;
     if (!strcmp(key, "rows3")) return (c->rows3_fwd ? 1.0 : 0.0) + (c->rows3_inv ? 2.0 : 0.0);   // bit 0 forward, bit 1 inverse
-    if (!strcmp(key, "column_engine")) {       // the column kernel this context launches NOW: 0 k_cols, 1 k_cols3, 2 k_cols3g, 3 k_cols3f
+    // what the choice functions answer for this context NOW.  column_engine: 0 k_cols, 1 k_cols3, 2 k_cols3g, 3 k_cols3f;
+    // raster_group: pixels per group of the forward row kernel's power-table rasteriser (0: log2 + exp2 form)
+    const bool col_engine_key = !strcmp(key, "column_engine");
+    if (col_engine_key || !strcmp(key, "raster_group")) {
         if (c->backend != PSFMC_BACKEND_FUSED) return NAN;
         int code = 0;
         SizeCall a;
         a.c = c; a.code = &code;
-        return size_call(SZ_COL_ENGINE, c->ny, a) == PSFMC_OK ? (double)code : NAN;
-    }
-    if (!strcmp(key, "raster_group")) {        // pixels per group of the forward row kernel's power-table rasteriser (0: log2 + exp2 form)
-        if (c->backend != PSFMC_BACKEND_FUSED) return NAN;
-        int code = 0;
-        SizeCall a;
-        a.c = c; a.code = &code;
-        return size_call(SZ_RASTER_GROUP, c->nx, a) == PSFMC_OK ? (double)code : NAN;
+        const int rc = col_engine_key ? size_call(SZ_COL_ENGINE, c->ny, a) : size_call(SZ_RASTER_GROUP, c->nx, a);
+        return rc == PSFMC_OK ? (double)code : NAN;
     }
     if (!strcmp(key, "speculate")) return c->speculate;
     if (!strcmp(key, "pow_tabs")) return c->use_pow_tabs ? 1.0 : 0.0;

@@ -51,15 +51,15 @@ for _sides, _shape in (((264, 308, 352, 484), (4, 11)), ((528, 576), (4, 12)),
 
 
 def column_engine(ny):
-    """Which column kernel the fused back end launches for transform side `ny` (psfmc_hip.hip
-    launch_cols): 'k_cols3f' (512, 1024, 1536, 2048: the general three-stage engine run forward both ways; round 3's
-    power-of-two kernel 'k_cols3' remains behind option cols3 = 3 and for storage='f32'), 'k_cols3g' (the
-    sides psfmc_fft.h fft3g_pick lists: ny = R1 * R2 * R3 on R2 * R3 <= 64 lanes) or 'k_cols' (the
-    two-stage engine).  Returns (kernel name, (R1, R2, R3) or None).  This is the default (option cols3 = 1) at row
+    """Which column kernel the fused back end launches for transform side `ny` (decided in one place,
+    psfmc_hip.hip col_engine, which launch_cols switches on): 'k_cols3f' (512, 1024, 1536, 2048: the general
+    three-stage engine run forward both ways; round 3's power-of-two kernel 'k_cols3' remains behind option
+    cols3 = 3 and for storage='f32'), 'k_cols3g' (the sides psfmc_fft.h fft3g_pick lists: ny = R1 * R2 * R3 on
+    R2 * R3 <= 64 lanes) or 'k_cols' (the two-stage engine).  Returns (kernel name, (R1, R2, R3) or None).  This is the default (option cols3 = 1) at row
     groups of 4; a context with rows in groups of 8 whose k_cols3g column length L = R2 * R3 is a multiple of 4 but
     not of 8 (psfmc_fused_path.h cols3g_layout_ok) runs 'k_cols' instead, and option cols3 or storage='f32' select
-    others.  `Context.get_option('column_engine')` reports what a context runs: 0 k_cols, 1 k_cols3, 2 k_cols3g,
-    3 k_cols3f."""
+    others.  `Context.get_option('column_engine')` reports what a context runs -- the answer of that same col_engine:
+    0 k_cols, 1 k_cols3, 2 k_cols3g, 3 k_cols3f."""
     if ny in (512, 1024, 1536, 2048):
         return 'k_cols3f', (ny // 64, 8, 8)
     if ny in _COLS3G_SHAPES:

@@ -343,6 +343,34 @@ def test_f32_storage_accepts_exactly_the_power_of_two_shapes_up_to_1024():
         model.close()
 
 
+def test_f32_storage_refuses_a_set_of_fields_at_the_launch():
+    """A set of two 64 x 64 fields: set_option('storage_f32', 1) is accepted (both sides are power-of-two shapes), and
+    the next evaluation is refused at its inverse-row launch -- complex64 storage has no kernel that sums chi^2 per
+    field.  With the option off again the set returns the bits it returned first."""
+    from psfmc_amd import FieldSet
+    from psfmc_amd.engine import NativeError
+    from test_gpu_random import edge_case, edge_components
+    cases = [edge_case(16000 + f, (64, 64), (9, 9), edge_components(64, 64), n_walkers=3) for f in range(2)]
+    fs = FieldSet([build(c, 'fused', max_walkers=1) for c in cases], max_walkers=8)
+    ctx = fs.context
+    assert ctx.n_fields == 2
+    assert_report(ctx, 'set', storage_f32=0, rows3=0, transform=(64, 64))
+    thetas = [c['theta'] for c in cases]
+    assert all(len(t) == 3 for t in thetas)
+    first = fs.log_posterior_batch(thetas)
+    assert all(np.isfinite(f).any() for f in first)
+    ctx.set_option('storage_f32', 1)
+    assert_report(ctx, 'set', storage_f32=1)
+    with pytest.raises(NativeError, match='single-precision storage serves contexts of one field') as err:
+        fs.log_posterior_batch(thetas)
+    assert err.value.code == -1                                   # PSFMC_EINVAL
+    ctx.set_option('storage_f32', 0)
+    assert_report(ctx, 'set', storage_f32=0)
+    again = fs.log_posterior_batch(thetas)
+    assert all(np.array_equal(a, f) for a, f in zip(again, first))
+    fs.close()
+
+
 def f32_invariance(model, theta, got32, tag):
     """Bitwise: the batch permuted, and in passes of at most two."""
     perm = np.random.RandomState(len(theta)).permutation(len(theta))
