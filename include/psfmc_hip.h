@@ -322,6 +322,39 @@ int psfmc_set_spiral_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* 
 int psfmc_set_radial_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* kinds, const int* col,
                             const double* konst);
 /*
+ * Inner and outer TRUNCATION of general components (GALFIT's truncation function in spirit, not its parametrisation;
+ * not the reference's).  Definition: psfmc_amd/ModelComponents/Sersic.py Sersic.truncation_weight and
+ * Sersic.truncated_image; kernels: csrc/psfmc_general.h.  flags [n_sersic]: per Sersic slot (model-file order) bit 0
+ * an inner, bit 1 an outer truncation; col / konst [n_sersic][PSFMC_TRUNC_PARAMS] have the meaning of
+ * psfmc_set_layout's slot_col / slot_const, per slot in_lo, in_hi, out_lo, out_hi in pixels along the slot's major
+ * axis; the entries of a side that is absent are never read.  With rho the slot's generalised radius in units of its
+ * semi-major radius r_major = 1 / hypot(m00, m01) (boxiness, modes and winding included) and s = r_major rho, the
+ * slot's value -- the Sersic law times its centroid term, a Moffat's or Ferrer's law, or with psfmc_set_general_mean
+ * every sample of the pixel mean -- is multiplied by
+ *     inner = (1 + tanh a(in_lo, in_hi)) / 2,  outer = (1 - tanh a(out_lo, out_hi)) / 2,
+ *     a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo)
+ * (0.018 / 0.982 at the two radii of a side; an absent side's factor is left out): the truncation follows the
+ * component's own isophotes.  mag stays the total magnitude of the UNTRUNCATED component.  The call APPENDS these
+ * 4 n_sersic entries to the field's auxiliary table BEHIND everything it holds.  A context with truncations ALWAYS
+ * carries the Fourier, the spiral and the radial block: a field without them gets entries inside their supports that
+ * are never read (nothing more is launched for them), so that from the first such call on every walker's auxiliary
+ * vector of the context -- psfmc_set_aux_rows' rows included -- has 2 n_sky + 25 n_sersic doubles, the truncation
+ * entries of Sersic k at 2 n_sky + 21 n_sersic + 4 k, the entries of a field without truncations unused.  A value of
+ * a side present that is not finite, lo < 0 or hi <= lo gives log-posterior -inf (NaN through a row-based call
+ * without writable skip flags); there is no condition between the two sides.  Call after the field's
+ * psfmc_set_aux_layout, which must flag the truncated slots as general, after its psfmc_set_fourier_layout,
+ * psfmc_set_spiral_layout and psfmc_set_radial_layout where those are called (each of them, like a new layout or aux
+ * layout, drops the field's truncations) and, in joint fits, before psfmc_set_joint_priors; psfmc_set_general_mean
+ * keeps them; all-zero flags remove them, and the slots are rendered as they were, bit for bit.  Refused
+ * (PSFMC_EINVAL) with nothing changed: a flag outside 0 ... 3, a truncation on a pixel-integrated slot or on one
+ * that is not flagged general, a field without an aux layout, a wrong n_sersic.  The fields of one context keep their
+ * own flags, registered in any order.  A context that never receives a nonzero flag allocates nothing, launches the
+ * kernels it launched and computes what it did without this call.
+ */
+#define PSFMC_TRUNC_PARAMS 4
+int psfmc_set_truncation_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* flags, const int* col,
+                                const double* konst);
+/*
  * General components rendered as the MEAN OF THEIR LAW OVER EACH PIXEL (Sersic(..., pixel_mean=True) with a boxiness,
  * modes or a spiral, Moffat(..., pixel_mean=True), Ferrer(..., pixel_mean=True); not the reference's).  Definition:
  * psfmc_amd/ModelComponents/Sersic.py Sersic.general_point and Sersic.general_mean_image; kernels:
@@ -664,6 +697,9 @@ int psfmc_group_set_fourier_layout(psfmc_group* group, int n_sersic, const int* 
 /* psfmc_set_spiral_layout (field 0) on every device of the group */
 int psfmc_group_set_spiral_layout(psfmc_group* group, int n_sersic, const int* flags, const int* col,
                                   const double* konst);
+/* psfmc_set_truncation_layout (field 0) on every device of the group */
+int psfmc_group_set_truncation_layout(psfmc_group* group, int n_sersic, const int* flags, const int* col,
+                                      const double* konst);
 /* psfmc_set_radial_layout (field 0) on every device of the group */
 int psfmc_group_set_radial_layout(psfmc_group* group, int n_sersic, const int* kinds, const int* col,
                                   const double* konst);
@@ -762,6 +798,18 @@ int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_col, const do
                           const int* spi_flags, const int* spi_col, const double* spi_const,
                           const int* rad_kinds, const int* rad_col, const double* rad_const,
                           double* out_const, int* out_col, int* out_kinds, int* counts);
+/*
+ * ... and with the truncation block (psfmc_set_truncation_layout's flags, col and konst; NULL flags: never
+ * registered, and the call is psfmc_debug_aux_table).  out_const / out_col [2 n_sky + 25 n_sersic]; where tru_flags
+ * is given, out_sides [n_sersic] receives the sides behind the kinds (written where counts[4] > 0; the kinds are
+ * then zeros for a field without laws) and counts has five entries: n_aux, n_fou, n_spi, n_rad, n_tru.
+ */
+int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                                 const int* mode_mask, const int* fou_col, const double* fou_const,
+                                 const int* spi_flags, const int* spi_col, const double* spi_const,
+                                 const int* rad_kinds, const int* rad_col, const double* rad_const,
+                                 const int* tru_flags, const int* tru_col, const double* tru_const,
+                                 double* out_const, int* out_col, int* out_kinds, int* out_sides, int* counts);
 
 /*
  * Diagnostic hook: time `reps` plain sweeps over a scratch buffer of nbytes (>= 1 MiB) -- mode 0

@@ -58,7 +58,21 @@ class Sersic(ComponentBase):
     component as the MEAN OF ITS LAW OVER EACH PIXEL instead of the law at the pixel centre times the centroid term
     (`Sersic.general_mean_image`): finite where the centre is a pixel centre, and several times to a hundred times
     closer to the true pixel mean in the core.  It adds no parameter.  On a plain Sersic it raises ValueError (use
-    `integrate=True` there), and so does `pixel_mean=True` together with `integrate=True`."""
+    `integrate=True` there), and so does `pixel_mean=True` together with `integrate=True`.
+
+    `truncation={'inner': (lo, hi), 'outer': (lo, hi)}` (either key or both; numbers or priors; GALFIT's truncation
+    function in spirit, not its parametrisation and not the reference's) multiplies the component by a tanh ramp that
+    rises from 0.018 at `lo` to 0.982 at `hi` (inner) and by one that falls from 0.982 at `lo` to 0.018 at `hi` (outer),
+    radii in pixels ALONG THE COMPONENT'S MAJOR AXIS (`Sersic.truncation_weight`, `Sersic.truncated_image`): a ring, a
+    lens, a disc or a pair of arms that starts outside the bar, a disc that stops.  The truncation follows the
+    component's own isophotes -- boxy, bent by the modes and wound with them; it has no centre or axis ratio of its
+    own.  The parameters are the attributes `trunc_in_lo`, `trunc_in_hi`, `trunc_out_lo`, `trunc_out_hi`.  Support:
+    the values of a side finite with 0 <= lo < hi (log-prior -inf otherwise); the two sides may overlap.  `mag` is the
+    total magnitude of the UNTRUNCATED component (GALFIT's flux parameter of a truncated component is not its total
+    either); `Sersic.truncation_flux_fraction` gives the fraction of it that survives.  The ramps are soft by
+    construction, so `pixel_mean=True` averages the product with its scheme unchanged and adds no refinement at the
+    radii.  A component with `truncation` alone is a general one with c = 0 and no modes; `truncation` with
+    `integrate=True` raises ValueError (use `pixel_mean=True`)."""
     device_kind = 'sersic'
     # the radial law: None for the Sersic law, else a key of RADIAL_KINDS (the subclasses `Moffat` and `Ferrer`)
     radial_law = None
@@ -73,7 +87,14 @@ class Sersic(ComponentBase):
     SPIRAL_REQUIRED = ('r_in', 'r_out', 'winding')
     SPIRAL_ATTRS = ('spiral_r_in', 'spiral_r_out', 'spiral_wind', 'spiral_alpha', 'spiral_incl', 'spiral_sky')
     SPIRAL_ANGLES = ('spiral_wind', 'spiral_incl', 'spiral_sky')
-    _fits_abbrs = ([('Sersic', 'SER'), ('spiral_r_in', 'SRI'), ('spiral_r_out', 'SRO'), ('spiral_wind', 'SWD'),
+    # the sides of `truncation` (psfmc_set_truncation_layout's flag bits 0 and 1) and the attributes in the order of
+    # its entries; TRUNC_ABSENT: what an absent side's entries hold (inside the support, never read)
+    TRUNC_KEYS = ('inner', 'outer')
+    TRUNC_ATTRS = ('trunc_in_lo', 'trunc_in_hi', 'trunc_out_lo', 'trunc_out_hi')
+    TRUNC_PARAMS = 4
+    TRUNC_ABSENT = (0.0, 1.0, 0.0, 1.0)
+    _fits_abbrs = ([('trunc_in_lo', 'TIL'), ('trunc_in_hi', 'TIH'), ('trunc_out_lo', 'TOL'), ('trunc_out_hi', 'TOH'),
+                    ('Sersic', 'SER'), ('spiral_r_in', 'SRI'), ('spiral_r_out', 'SRO'), ('spiral_wind', 'SWD'),
                     ('spiral_alpha', 'SAL'), ('spiral_incl', 'SIN'), ('spiral_sky', 'SPA'),
                     ('reff_b', 'REB'), ('reff', 'RE'),
                     ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')] +
@@ -105,10 +126,14 @@ class Sersic(ComponentBase):
     spiral_alpha = StochasticProperty()
     spiral_incl = StochasticProperty()
     spiral_sky = StochasticProperty()
+    trunc_in_lo = StochasticProperty()
+    trunc_in_hi = StochasticProperty()
+    trunc_out_lo = StochasticProperty()
+    trunc_out_hi = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
                  angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None, spiral=None,
-                 pixel_mean=False):
+                 pixel_mean=False, truncation=None):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -118,18 +143,45 @@ class Sersic(ComponentBase):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = bool(integrate)
-        self._init_shape(boxiness, fourier, spiral, pixel_mean)
+        self._init_shape(boxiness, fourier, spiral, pixel_mean, truncation)
 
-    def _init_shape(self, boxiness, fourier, spiral, pixel_mean=False):
-        """The isophote-shape keywords `boxiness`, `fourier` and `spiral` and the rendering keyword `pixel_mean`
-        (shared with the radial-law subclasses)."""
+    def _init_shape(self, boxiness, fourier, spiral, pixel_mean=False, truncation=None):
+        """The isophote-shape keywords `boxiness`, `fourier` and `spiral`, the rendering keyword `pixel_mean` and
+        `truncation` (shared with the radial-law subclasses)."""
         self.pixel_mean = bool(pixel_mean)
         if self.pixel_mean and self.integrate:
             raise ValueError('Sersic: pixel_mean=True together with integrate=True is not supported (integrate=True '
                              'is the plain profile\'s pixel integral, pixel_mean=True a general component\'s)')
-        if self.pixel_mean and self.radial_law is None and boxiness is None and fourier is None and spiral is None:
+        if (self.pixel_mean and self.radial_law is None and boxiness is None and fourier is None and spiral is None
+                and truncation is None):
             raise ValueError('Sersic: pixel_mean=True needs boxiness, fourier or spiral; the plain profile has '
                              'integrate=True')
+        self.truncation_sides = ()
+        if truncation is not None:
+            if self.integrate:
+                raise ValueError('Sersic: truncation together with integrate=True is not supported (the '
+                                 'pixel-integrated profile is the plain component\'s; use pixel_mean=True)')
+            truncation = dict(truncation)
+            unknown = [k for k in truncation if k not in Sersic.TRUNC_KEYS]
+            if unknown:
+                raise ValueError('Sersic: truncation has no key {!r} (keys: {})'.format(
+                    unknown[0], ', '.join(Sersic.TRUNC_KEYS)))
+            if not truncation:
+                raise ValueError('Sersic: truncation needs the key \'inner\' or \'outer\'')
+            for side, key in enumerate(Sersic.TRUNC_KEYS):
+                if key not in truncation:
+                    continue
+                entry = truncation[key]
+                try:
+                    if isinstance(entry, (str, bytes, dict)) or hasattr(entry, 'value'):
+                        raise TypeError
+                    lo, hi = entry
+                except (TypeError, ValueError):
+                    raise ValueError('Sersic: truncation {!r} needs a pair (lo, hi)'.format(key))
+                setattr(self, Sersic.TRUNC_ATTRS[2 * side], lo)
+                setattr(self, Sersic.TRUNC_ATTRS[2 * side + 1], hi)
+            self.truncation_sides = tuple(k for k in Sersic.TRUNC_KEYS if k in truncation)
+        self.has_truncation = bool(self.truncation_sides)
         self.has_boxiness = boxiness is not None
         if self.has_boxiness:
             if self.integrate:
@@ -174,15 +226,21 @@ class Sersic(ComponentBase):
 
     @property
     def is_general(self):
-        """Does the component run the general kernels (a `boxiness`, `fourier` or `spiral` keyword)?"""
-        return self.has_boxiness or self.has_fourier or self.has_spiral
+        """Does the component run the general kernels (a `boxiness`, `fourier`, `spiral` or `truncation` keyword)?"""
+        return self.has_boxiness or self.has_fourier or self.has_spiral or self.has_truncation
+
+    @property
+    def truncation_flags(self):
+        """psfmc_set_truncation_layout's flag of the slot: bit 0 an inner, bit 1 an outer truncation; 0: none."""
+        return sum(1 << Sersic.TRUNC_KEYS.index(k) for k in self.truncation_sides)
 
     def header_flags(self, count):
         """FITS header keys this component adds to a database beside its parameters' own: `<count>SERINT = T`
         when it is the pixel-integrated profile, `<count>SERBOX = T` when it has a boxiness, `<count>SERFOU` = the
         comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral,
         `<count>SERLAW = 'moffat' | 'ferrer'` when its radial law is not the Sersic law (`Moffat`, `Ferrer`),
-        `<count>SERAVG = T` when it is rendered as the mean over each pixel (`pixel_mean=True`), nothing otherwise."""
+        `<count>SERAVG = T` when it is rendered as the mean over each pixel (`pixel_mean=True`), `<count>SERTRU =
+        'inner' | 'outer' | 'inner,outer'` when it is truncated, nothing otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
             out['{:d}SERBOX'.format(count)] = True
@@ -194,7 +252,40 @@ class Sersic(ComponentBase):
             out['{:d}SERLAW'.format(count)] = self.radial_law
         if self.pixel_mean:
             out['{:d}SERAVG'.format(count)] = True
+        if self.has_truncation:
+            out['{:d}SERTRU'.format(count)] = ','.join(self.truncation_sides)
         return out
+
+    @staticmethod
+    def _truncation_ok(trunc, flags):
+        """The support of the truncation, trunc [..., 4] = (in_lo, in_hi, out_lo, out_hi) and `flags` the sides present
+        (bit 0 inner, bit 1 outer): the two values of a side present finite with 0 <= lo < hi; an absent side's
+        entries are not looked at, and there is no condition between the sides."""
+        t = np.asarray(trunc, dtype=np.float64)
+        ok = np.ones(t.shape[:-1], dtype=bool)
+        with np.errstate(invalid='ignore'):
+            for side in range(2):
+                if (flags >> side) & 1:
+                    lo, hi = t[..., 2 * side], t[..., 2 * side + 1]
+                    ok = ok & np.isfinite(lo) & np.isfinite(hi) & (lo >= 0) & (hi > lo)
+        return ok
+
+    def _truncation_values(self, vals, n_w=None):
+        """psfmc_set_truncation_layout's entries (in_lo, in_hi, out_lo, out_hi), TRUNC_ABSENT for an absent side: [4]
+        (n_w None: current values) or [n_w, 4]."""
+        get = (lambda k: np.reshape(vals[k], (n_w,))) if n_w is not None else (lambda k: float(np.ravel(vals(k))[0]))
+        fill = (lambda v: np.full(n_w, v)) if n_w is not None else float
+        cols = [np.asarray(get(a), dtype=np.float64) if (self.truncation_flags >> (j // 2)) & 1 else fill(absent)
+                for j, (a, absent) in enumerate(zip(Sersic.TRUNC_ATTRS, Sersic.TRUNC_ABSENT))]
+        return np.stack(cols, axis=-1)
+
+    def truncation_tuple(self):
+        """The current values as the definition functions take them: (in_lo, in_hi, out_lo, out_hi) with None for
+        an absent side, or None for a component without the keyword."""
+        if not self.has_truncation:
+            return None
+        t = self._truncation_values(lambda k: getattr(self, k))
+        return tuple(float(t[j]) if (self.truncation_flags >> (j // 2)) & 1 else None for j in range(4))
 
     @staticmethod
     def _spiral_ok(spiral):
@@ -247,6 +338,9 @@ class Sersic(ComponentBase):
             return -np.inf
         if self.has_spiral and not Sersic._spiral_ok(self._spiral_values(lambda k: getattr(self, k))):
             return -np.inf
+        if self.has_truncation and not Sersic._truncation_ok(self._truncation_values(lambda k: getattr(self, k)),
+                                                              self.truncation_flags):
+            return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
     def log_priors_batch(self, block):
@@ -259,6 +353,9 @@ class Sersic(ComponentBase):
             logp = np.where(Sersic._fourier_ok(*self._fourier_values(vals, len(logp))), logp, -np.inf)
         if self.has_spiral:
             logp = np.where(Sersic._spiral_ok(self._spiral_values(vals, len(logp))), logp, -np.inf)
+        if self.has_truncation:
+            logp = np.where(Sersic._truncation_ok(self._truncation_values(vals, len(logp)), self.truncation_flags),
+                            logp, -np.inf)
         return logp
 
     @staticmethod
@@ -292,6 +389,17 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
+        if self.has_truncation:
+            amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
+            args = (self.radial_law, row, self._radial_values(lambda k: getattr(self, k)) if self.radial_law else None,
+                    float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
+                    list(zip(self.fourier_modes, amps, phases)),
+                    self._spiral_values(lambda k: getattr(self, k)) if self.has_spiral else None)
+            if self.pixel_mean:
+                arr += Sersic.general_mean_image(*args, shape=arr.shape, truncation=self.truncation_tuple())
+            else:
+                arr += Sersic.truncated_image(*args, truncation=self.truncation_tuple(), shape=arr.shape)
+            return arr
         if self.pixel_mean:
             amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
             arr += Sersic.general_mean_image(
@@ -576,6 +684,114 @@ class Sersic(ComponentBase):
                 rho2 = rho2 * (1.0 + Sersic._fourier_eps(u / ruv, v / ruv, modes)) ** 2
             return rho2, (u == 0) & (v == 0)
 
+    # -- truncation (`truncation=...`) ----------------------------------------------------------------------------
+    @staticmethod
+    def truncation_weight(row, rho2, centre, truncation):
+        """The factors of a truncated component, (inner, outer), None for an absent side.  This numpy text is the
+        DEFINITION the device kernels (csrc/psfmc_general.h, psfmc_general_mean.h) are held to.  `rho2`, `centre`: the
+        squared generalised radius in units of the semi-major radius and the mask of u = v = 0, exactly as
+        `radial_rho2` / `general_point` form them (boxiness, (1 + eps)^2 and winding included); `truncation` =
+        (in_lo, in_hi, out_lo, out_hi) in pixels along the major axis, None for the values of an absent side.
+
+            r_major = 1 / hypot(m00, m01)            the row's semi-major radius in pixels (reff, fwhm, r_out)
+            s     = r_major sqrt(rho2)               the generalised radius in pixels; 0 where u = v = 0
+            a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo)          (the spiral ramp's argument)
+            inner = (1 + tanh(a(in_lo,  in_hi )))  / 2         0.018 at in_lo,  0.982 at in_hi
+            outer = (1 - tanh(a(out_lo, out_hi))) / 2          0.982 at out_lo, 0.018 at out_hi
+
+        (outer is not 1 - ramp: no cancellation where it is small).  The truncation follows the component's own
+        isophotes; it has no centre or axis ratio of its own.  Support: `_truncation_ok`."""
+        in_lo, in_hi, out_lo, out_hi = truncation
+        if (in_lo is None) != (in_hi is None) or (out_lo is None) != (out_hi is None):
+            raise ValueError('truncation: a side is (lo, hi) or (None, None)')
+        r_major = 1.0 / np.hypot(row[2], row[3])
+        with np.errstate(all='ignore'):
+            s = r_major * np.sqrt(np.where(centre, 0.0, rho2))
+            ramp = lambda lo, hi: np.tanh(2.0 * (2.0 * s - float(lo) - float(hi)) / (float(hi) - float(lo)))
+            inner = None if in_lo is None else 0.5 * (1.0 + ramp(in_lo, in_hi))
+            outer = None if out_lo is None else 0.5 * (1.0 - ramp(out_lo, out_hi))
+        return inner, outer
+
+    @staticmethod
+    def _truncate(value, row, rho2, centre, truncation):
+        """value * inner * outer; an absent side's factor is left out (not multiplied by 1.0), and `truncation`
+        None returns `value` itself."""
+        if truncation is None:
+            return value
+        for factor in Sersic.truncation_weight(row, rho2, centre, truncation):
+            if factor is not None:
+                value = value * factor
+        return value
+
+    @staticmethod
+    def truncated_image(law, row, pars, boxiness, modes, spiral, truncation, shape):
+        """A general component with an inner and / or outer truncation on a `shape` image: its PARENT VALUE -- what
+        the component renders without the keyword: `general_image`, `fourier_image` or `spiral_image` for the Sersic
+        law (`law` None; the law times the reference's centroid term, NaN where the centre is a pixel centre),
+        `radial_image` for 'moffat' / 'ferrer' (Sigma_0 at u = v = 0) -- times `truncation_weight`'s factors at the
+        pixel centre, with rho^2 from `radial_rho2` (the parent's own, modes and winding included).  `truncation`
+        None gives the parent's bits.  `mag` stays the total magnitude of the UNTRUNCATED parent
+        (`truncation_flux_fraction`).  No refinement is added at the truncation radii: the ramps are soft by
+        construction (`pixel_mean=True`, `general_mean_image`, averages the product over each pixel)."""
+        modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        if law is not None:
+            parent = Sersic.radial_image(law, row, pars, boxiness, modes, spiral, shape)
+        elif spiral is not None:
+            parent = Sersic.spiral_image(row, boxiness, modes, spiral, shape)
+        elif modes:
+            parent = Sersic.fourier_image(row, boxiness, modes, shape)
+        else:
+            parent = Sersic.general_image(row, boxiness, shape)
+        if truncation is None:
+            return parent
+        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape)
+        with np.errstate(all='ignore'):
+            return Sersic._truncate(parent, row, rho2, centre, truncation)
+
+    @staticmethod
+    def truncation_flux_fraction(law, index_or_pars, r_major, truncation):
+        """The fraction of the untruncated component's flux that survives the truncation:
+
+            int law(rho) W(r_major rho) rho drho / int law(rho) rho drho
+
+        over the law's own range (scipy.integrate.quad, split at the ramps' radii), W = inner * outer of
+        `truncation_weight` at s = r_major rho.  `law` None: the Sersic law exp(-kappa rho^(1/n)) with n =
+        `index_or_pars`; 'moffat': `index_or_pars` = (beta,); 'ferrer': (alpha, beta).  Valid with any boxiness, modes,
+        spiral and inclination, because every isophote's area is proportional to rho^2.  For reporting (the
+        truncated component's total magnitude is mag - 2.5 log10 of it); no kernel uses it."""
+        from scipy.integrate import quad
+        in_lo, in_hi, out_lo, out_hi = truncation
+        r_major = float(r_major)
+        if law is None:
+            n = float(index_or_pars)
+            kap = Sersic.kappa(n)
+            f, top = (lambda r: np.exp(-kap * (r ** (1.0 / n) - 1.0))), np.inf
+        elif law == 'moffat':
+            beta = float(np.ravel(index_or_pars)[0])
+            g = 4.0 * np.expm1(np.log(2.0) / beta)
+            f, top = (lambda r: (1.0 + g * r * r) ** -beta), np.inf
+        elif law == 'ferrer':
+            alpha, k = float(index_or_pars[0]), 2.0 - float(index_or_pars[1])
+            f, top = (lambda r: max(1.0 - r ** k, 0.0) ** alpha), 1.0
+        else:
+            raise ValueError('radial law {!r}: one of None, moffat, ferrer'.format(law))
+
+        def weight(r):
+            w, s = 1.0, r_major * r
+            if in_lo is not None:
+                w *= 0.5 * (1.0 + np.tanh(2.0 * (2.0 * s - in_lo - in_hi) / (in_hi - in_lo)))
+            if out_lo is not None:
+                w *= 0.5 * (1.0 - np.tanh(2.0 * (2.0 * s - out_lo - out_hi) / (out_hi - out_lo)))
+            return w
+        cuts = sorted(set(v / r_major for v in truncation if v is not None and 0.0 < v / r_major < top))
+        edges = [0.0] + cuts + [top]
+        whole = lambda fn: sum(quad(fn, a, b, epsabs=0.0, epsrel=1e-12, limit=200)[0]
+                               for a, b in zip(edges[:-1], edges[1:]))
+        import warnings
+        with warnings.catch_warnings():        # (1e-12 is at the rounding level of some pieces: quad says so, and is right)
+            warnings.simplefilter('ignore')
+            return whole(lambda r: f(r) * weight(r) * r) / whole(lambda r: f(r) * r)
+
     @staticmethod
     def _plain(row, x, y):
         """Sigma_e exp(-kappa (rho^(1/n) - 1)) at the points (x, y); at rho = 0 its finite peak Sigma_e e^kappa.
@@ -668,8 +884,9 @@ class Sersic(ComponentBase):
 
     # -- the pixel-averaged mode of the general components (`pixel_mean=True`) ------------------------------------
     @staticmethod
-    def _general_point_x(law, row, pars, boxiness, modes, spiral, x, y):
+    def _general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation=None):
         """(`general_point`'s value, Ferrer's x = rho^(2 - beta) with 0 at u = v = 0 -- None for the other laws)."""
+        trunc = lambda val: Sersic._truncate(val, row, rho2, centre, truncation)
         x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
         if law not in Sersic.RADIAL_KINDS:
@@ -701,18 +918,18 @@ class Sersic(ComponentBase):
                 if modes:
                     area = area * Sersic.fourier_area_ratio(boxiness, modes)
                 sb = sbeff / area / ci if spiral is not None else sbeff / area
-                return np.where(centre, sb * np.exp(kappa), sb * np.exp(-kappa * (rho2 ** p - 1.0))), None
+                return trunc(np.where(centre, sb * np.exp(kappa), sb * np.exp(-kappa * (rho2 ** p - 1.0)))), None
             sigma0 = Sersic.radial_central(law, row, pars, boxiness, modes, spiral)
             if law == 'moffat':
                 beta = float(pars[0])
                 g = 4.0 * np.expm1(np.log(2.0) / beta)
-                return np.where(centre, sigma0, sigma0 * (1.0 + g * rho2) ** -beta), None
+                return trunc(np.where(centre, sigma0, sigma0 * (1.0 + g * rho2) ** -beta)), None
             alpha, k = float(pars[0]), 2.0 - float(pars[1])
             xk = np.where(centre, 0.0, rho2 ** (0.5 * k))
-            return np.where(xk < 1.0, sigma0 * np.abs(1.0 - xk) ** alpha, 0.0), xk
+            return trunc(np.where(xk < 1.0, sigma0 * np.abs(1.0 - xk) ** alpha, 0.0)), xk
 
     @staticmethod
-    def general_point(law, row, pars, boxiness, modes, spiral, x, y):
+    def general_point(law, row, pars, boxiness, modes, spiral, x, y, truncation=None):
         """The law of a general component at ARBITRARY POINTS (x, y) (arrays of one shape, pixel coordinates): what
         `general_mean_image` averages.  `law` is None (the Sersic law), 'moffat' or 'ferrer'; `row`, `pars`
         (ignored for None), `boxiness`, `modes` and `spiral` as for `radial_image`.  The coordinate chain is
@@ -723,11 +940,13 @@ class Sersic(ComponentBase):
             Moffat, Ferrer  exactly as `radial_image`
 
         There is NO centroid term: the reference's is a correction for sampling the law at the pixel centre, and this
-        is the law itself.  Where u = v = 0 the value is the finite peak, sb e^kappa or Sigma_0."""
-        return Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y)[0]
+        is the law itself.  Where u = v = 0 the value is the finite peak, sb e^kappa or Sigma_0.  `truncation` (as for
+        `truncation_weight`; None: absent, the bits of the function without the argument) multiplies the value by the
+        inner and outer factors at the point, the peak by the factors at s = 0."""
+        return Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation)[0]
 
     @staticmethod
-    def general_mean_image(law, row, pars, boxiness, modes, spiral, shape):
+    def general_mean_image(law, row, pars, boxiness, modes, spiral, shape, truncation=None):
         """A general component rendered as the MEAN OF ITS LAW OVER EACH PIXEL on a `shape` image (`pixel_mean=True`;
         not the reference's).  This numpy text is the DEFINITION the device kernels (csrc/psfmc_general_mean.h) are
         held to.  With g = `general_point` and the constants INTEG_* of `integrated_image`:
@@ -745,11 +964,13 @@ class Sersic(ComponentBase):
            coincides with one, where g is its finite peak.
 
         Parts 3 and 4 overwrite parts 1 and 2.  `mag` stays the total magnitude through the closed-form factors of
-        `general_image`, `fourier_image`, `spiral_image` and `radial_image`."""
+        `general_image`, `fourier_image`, `spiral_image` and `radial_image`.  With `truncation` every sample is
+        `general_point(..., truncation)`, the product of the law and the truncation's factors: the scheme is applied
+        to the product unchanged, and no refinement is added at the truncation radii (the ramps are soft)."""
         ny, nx = shape
         x0, y0 = row[0], row[1]
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
-        point = lambda x, y: Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y)
+        point = lambda x, y: Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation)
         yy, xx = np.mgrid[0:ny, 0:nx].astype(np.float64)
         cyy, cxx = np.mgrid[0:ny + 1, 0:nx + 1].astype(np.float64) - 0.5
         mid, mid_x = point(xx, yy)

@@ -2,7 +2,7 @@
 // composes the table the device reads from it.  No HIP call in this file.
 //
 // The table: the base entries (psfmc_set_aux_layout: 2 n_sky + n_sersic), then the blocks in the order of kAuxBlocks
-// -- Fourier modes, spiral arms, radial laws -- each with the entries of psfmc_set_*_layout.  A table index is the
+// -- Fourier modes, spiral arms, radial laws, truncations -- each with the entries of psfmc_set_*_layout.  A table index is the
 // entry's place in the walker's auxiliary vector, so a present block forces every block before it to be present:
 // where the field registered none, that block is PADDED with entries no kernel reads (column -1 and the block's
 // pad constants, inside the support of what would read them).
@@ -13,14 +13,16 @@
 
 namespace psfmc {
 
-enum { kBlkFou = 0, kBlkSpi, kBlkRad, kAuxBlocks };
+enum { kBlkFou = 0, kBlkSpi, kBlkRad, kBlkTru, kAuxBlocks };
 
 // entries of block b for n_sersic components
 inline int aux_block_len(int b, int n_sersic) {
-    return b == kBlkFou ? fourier_len(n_sersic) : b == kBlkSpi ? spiral_len(n_sersic) : radial_len(n_sersic);
+    return b == kBlkFou ? fourier_len(n_sersic) : b == kBlkSpi ? spiral_len(n_sersic)
+         : b == kBlkRad ? radial_len(n_sersic) : trunc_len(n_sersic);
 }
 
-// what one registration call passed: the per-Sersic tags (mode masks, spiral flags, radial kinds) and the entries.
+// what one registration call passed: the per-Sersic tags (mode masks, spiral flags, radial kinds, truncation sides)
+// and the entries.
 // Empty: never registered, dropped, or registered with all-zero tags.
 struct AuxBlockRecord {
     std::vector<int> tags, col;
@@ -45,11 +47,12 @@ struct FieldAuxRecord {
     AuxBlockRecord block[kAuxBlocks];
 };
 
-// the table in upload order: konst | col | kinds.  kinds (the radial kinds, [n_sersic]) is empty without laws.
+// the table in upload order: konst | col | kinds | sides.  kinds (the radial kinds, [n_sersic]) is empty without a radial
+// block (zeros where the block is only padding in front of the truncations).
 struct AuxTable {
     std::vector<double> konst;
-    std::vector<int> col, kinds;
-    int n_aux = 0, n_fou = 0, n_spi = 0, n_rad = 0;
+    std::vector<int> col, kinds, sides;      // sides: the truncation sides, [n_sersic], empty without truncations
+    int n_aux = 0, n_fou = 0, n_spi = 0, n_rad = 0, n_tru = 0;
 };
 
 inline AuxTable compose_aux_table(const FieldAuxRecord& r, int n_sky, int n_sersic) {
@@ -60,7 +63,7 @@ inline AuxTable compose_aux_table(const FieldAuxRecord& r, int n_sky, int n_sers
     int last = -1;                       // the last block the field registered
     for (int b = 0; b < kAuxBlocks; ++b)
         if (!r.block[b].empty()) last = b;
-    int n[kAuxBlocks] = {0, 0, 0};
+    int n[kAuxBlocks] = {0, 0, 0, 0};
     for (int b = 0; b <= last; ++b) {
         const AuxBlockRecord& blk = r.block[b];
         const size_t at = t.col.size();
@@ -75,9 +78,13 @@ inline AuxTable compose_aux_table(const FieldAuxRecord& r, int n_sky, int n_sers
         if (b == kBlkSpi)
             for (int k = 0; k < n_sersic; ++k) t.konst[at + kSpiIn * k + 1] = 1.0;   // r_out > r_in = 0
     }
-    if (last == kBlkRad) t.kinds = r.block[kBlkRad].tags;
+    if (last >= kBlkRad) {
+        t.kinds = r.block[kBlkRad].tags;
+        if (t.kinds.empty()) t.kinds.assign(n_sersic, 0);
+    }
+    if (last == kBlkTru) t.sides = r.block[kBlkTru].tags;
     t.n_aux = (int)t.col.size();
-    t.n_fou = n[kBlkFou]; t.n_spi = n[kBlkSpi]; t.n_rad = n[kBlkRad];
+    t.n_fou = n[kBlkFou]; t.n_spi = n[kBlkSpi]; t.n_rad = n[kBlkRad]; t.n_tru = n[kBlkTru];
     return t;
 }
 

@@ -51,6 +51,19 @@
 // byte holds the kind (0 Sersic, 1 Moffat, 2 Ferrer).  The per-walker constants rpar[w][k][kRadPar] are formed by the
 // LAW instantiation of k_general_split.  Such a context runs ONE further instantiation of each of the two kernels
 // (FOU, SPI and LAW all set; the kind is a wave-uniform branch); contexts without laws run the kernels they ran.
+//
+// TRUNCATION (`Sersic / Moffat / Ferrer(..., truncation={'inner': (lo, hi), 'outer': (lo, hi)})`, GALFIT's truncation
+// function in spirit; definition: Sersic.py `Sersic.truncation_weight`): the component's value is multiplied by
+//     inner = (1 + tanh a(in_lo, in_hi)) / 2,  outer = (1 - tanh a(out_lo, out_hi)) / 2,
+//     a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo),  s = r_major rho
+// with rho the component's own generalised radius (boxiness, modes and winding included) and r_major its semi-major
+// radius in pixels: the truncation follows the component's isophotes.  psfmc_set_truncation_layout appends kTruIn
+// entries per Sersic -- in_lo, in_hi, out_lo, out_hi -- BEHIND the laws' entries.  A context with truncations ALWAYS
+// carries the Fourier, spiral and radial blocks: a walker's auxiliary vector then has 2 n_sky + 25 n_sersic doubles.
+// A per (field, Sersic) byte holds the sides (bit 0 inner, bit 1 outer).  The per-walker constants
+// tpar[w][k][kTruPar] are formed by the TRU instantiation of k_general_split.  Such a context runs ONE further
+// instantiation of each of the two kernels (every flag set; the byte is a wave-uniform branch); contexts without
+// truncations run the kernels they ran.  `mag` stays the magnitude of the UNTRUNCATED component.
 #pragma once
 #include "psfmc_device.h"
 #include "psfmc_integrated.h"
@@ -82,6 +95,12 @@ constexpr int kRadMoffat = 1, kRadFerrer = 2;
 // the laws' entries behind the spiral ones: aux[base + fourier_len + spiral_len + kRadIn k + j] of Sersic k
 __host__ __device__ inline int radial_len(int n_sersic) { return kRadIn * n_sersic; }
 
+constexpr int kTruIn = 4;            // in_lo, in_hi, out_lo, out_hi (PSFMC_TRUNC_PARAMS)
+constexpr int kTruPar = 6;           // inner k1, k0, outer k1, k0 (the ramp's argument is k1 rho + k0), 1 / e, spare
+constexpr int kTruInner = 1, kTruOuter = 2;
+// the truncations' entries behind the laws': aux[base + fourier_len + spiral_len + radial_len + kTruIn k + j]
+__host__ __device__ inline int trunc_len(int n_sersic) { return kTruIn * n_sersic; }
+
 // skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
 // component, and with it the walker's likelihood, NaN)
 // SPI: the context has spirals (spar, smasks set, aux_spi the offset of the spiral entries in a walker's vector); the
@@ -96,13 +115,19 @@ __host__ __device__ inline int radial_len(int n_sersic) { return kRadIn * n_sers
 // follows as for every component -- and stores the law's constants: Moffat g, -beta; Ferrer k / e, k, alpha.  Outside
 // the support (Moffat: beta not finite or <= 1; Ferrer: alpha or beta not finite, alpha < 0, beta >= 2) the walker
 // is skipped like a bad boxiness.  lgamma, exp and expm1 run once per walker and component.
-template <bool SPI, bool LAW = false>
+// TRU: the context has truncations (tpar, tmasks set, aux_tru the offset of their entries); the thread of a slot with
+// a side forms, per side present, k1 = 4 r_major / (hi - lo) and k0 = -2 (lo + hi) / (hi - lo) with r_major =
+// 1 / hypot(m00, m01) the slot's semi-major radius in pixels (zeros for an absent side), and 1 / e.  Outside the
+// support of a side present (a value not finite, lo < 0, hi <= lo) Sigma becomes NaN and the walker is skipped like a
+// bad boxiness.  The TRU = false instantiations are the kernels as they were.
+template <bool SPI, bool LAW = false, bool TRU = false>
 __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __restrict__ skip,
                                 double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                                 const uint8_t* __restrict__ flags, int n_ps, int n_sersic, int n_psf, int n_psf_field,
                                 int n, double* __restrict__ spar, const uint8_t* __restrict__ smasks, int aux_spi,
                                 double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr,
-                                int aux_rad = 0) {
+                                int aux_rad = 0, double* __restrict__ tpar = nullptr,
+                                const uint8_t* __restrict__ tmasks = nullptr, int aux_tru = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * n_sersic) return;
     const int w = i / n_sersic, k = i - w * n_sersic;
@@ -176,6 +201,23 @@ __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __
             }
             rp[3] = (double)kind;
             inv_a *= f;
+        }
+    }
+    if constexpr (TRU) {
+        const int tm = tmasks[(idx / n_psf_field) * n_sersic + k];
+        if (tm) {
+            const double* a = aux + (size_t)w * aux_stride + aux_tru + kTruIn * k;
+            const double r_major = 1.0 / hypot(b[2], b[3]);
+            double* tp = tpar + (size_t)i * kTruPar;
+            for (int side = 0; side < 2; ++side) {
+                const double lo = a[2 * side], hi = a[2 * side + 1], span = hi - lo;
+                const bool on = (tm >> side) & 1;
+                if (on) bad = bad || !(lo >= 0.0) || !(hi > lo) || !(hi < INFINITY);
+                tp[2 * side] = on ? 4.0 * r_major / span : 0.0;
+                tp[2 * side + 1] = on ? -2.0 * (lo + hi) / span : 0.0;
+            }
+            tp[4] = 1.0 / e;
+            tp[5] = 0.0;
         }
     }
     for (int j = 0; j < kPrepSersic - 1; ++j) o[j] = b[j];
@@ -358,9 +400,37 @@ __device__ __forceinline__ RadPar load_radial(const double* __restrict__ rp) {
     return R;
 }
 
-template <bool FOURIER, bool SPIRAL = false, bool LAW = false>
+// TRU: the component is truncated (file header; `Sersic.truncation_weight`): rho = 2^(log2(s) / e + log2(1 + eps)) from
+// the log2 terms the branch holds (0 at s = 0), then per side present one exp2 and one reciprocal,
+//     inner = 1 / (1 + 2^(-2 log2(e) (k1 rho + k0))),  outer = 1 / (1 + 2^(+2 log2(e) (k1 rho + k0)))
+// (the exponent is capped at 1000, so that the sum stays finite and a factor far outside its ramp is ~1e-301, not the
+// NaN of a reciprocal of inf).  The sides are wave-uniform.  The TRU = false forms are the functions as they were.
+struct TruPar { double ik1, ik0, ok1, ok0, ie, chk; int sides; };
+__device__ __forceinline__ TruPar load_trunc(const double* __restrict__ tp, int sides) {
+    TruPar T;
+    T.ik1 = -2.0 * kIntegLog2e * tp[0];
+    T.ik0 = -2.0 * kIntegLog2e * tp[1];
+    T.ok1 = 2.0 * kIntegLog2e * tp[2];
+    T.ok0 = 2.0 * kIntegLog2e * tp[3];
+    T.ie = tp[4];
+    T.sides = sides;
+    // (a NaN among the constants reaches the pixel through general_pixel's chk, whatever the clamps do)
+    T.chk = ((T.ik1 + T.ik0) + (T.ok1 + T.ok0)) + T.ie;
+    return T;
+}
+// value * inner * outer at generalised radius rho (in units of the semi-major radius)
+__device__ __forceinline__ double trunc_apply(const TruPar& T, double val, double rho) {
+    if (T.sides & kTruInner)                                           // wave-uniform
+        val *= fast_rcp(1.0 + fast_exp2(__builtin_fmin(__builtin_fma(T.ik1, rho, T.ik0), 1000.0)));
+    if (T.sides & kTruOuter)                                           // wave-uniform
+        val *= fast_rcp(1.0 + fast_exp2(__builtin_fmin(__builtin_fma(T.ok1, rho, T.ok0), 1000.0)));
+    return val;
+}
+
+template <bool FOURIER, bool SPIRAL = false, bool LAW = false, bool TRU = false>
 __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y,
-                                                const SpiPar* SP = nullptr, const RadPar* RP = nullptr) {
+                                                const SpiPar* SP = nullptr, const RadPar* RP = nullptr,
+                                                const TruPar* TP = nullptr) {
     const double dx = x - G.s.x0, dy = y - G.s.y0;
     double u, v, spi_chk = 0.0;
     if constexpr (SPIRAL) {
@@ -409,24 +479,37 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
         val = s > 0.0 ? val : G.s.sbeff;                               // the centre: Sigma_0, finite
         double chk = (u + v) + (G.s.sbeff + R.chk);    // (the comparisons and the exponentials' clamps swallow a NaN)
         if constexpr (SPIRAL) chk += spi_chk;
+        if constexpr (TRU) {
+            // (the centre: the factors at rho = 0; a NaN of l1e there is never read)
+            val = trunc_apply(*TP, val, s > 0.0 ? fast_exp2(__builtin_fma(TP->ie, ls, l1e)) : 0.0);
+            chk += TP->chk;
+        }
         return chk == chk ? val : chk;
     }
-    double t;
+    double t, rho = 0.0;
     if constexpr (FOURIER) {
         const double rinv = general_rsqrt(__builtin_fma(u, u, v * v));
         const double eps = fourier_eps(F, u * rinv, v * rinv);
         // (1 + eps > 0 inside the support; a NaN of the centre pixel is swallowed by the clamps and comes back
         // through the 0 * inf of the last term, as without modes)
-        const double l1 = (G.s.p + G.s.p) * fast_log2(1.0 + eps);
-        t = s > 0.0 ? fast_exp2(__builtin_fma(G.pe2, fast_log2(s), l1)) : 0.0;
+        const double l1e = fast_log2(1.0 + eps), ls = fast_log2(s);
+        const double l1 = (G.s.p + G.s.p) * l1e;
+        t = s > 0.0 ? fast_exp2(__builtin_fma(G.pe2, ls, l1)) : 0.0;
+        if constexpr (TRU) rho = s > 0.0 ? fast_exp2(__builtin_fma(TP->ie, ls, l1e)) : 0.0;
     } else {
-        t = s > 0.0 ? fast_exp2(G.pe2 * fast_log2(s)) : 0.0;
+        const double ls = fast_log2(s);
+        t = s > 0.0 ? fast_exp2(G.pe2 * ls) : 0.0;
+        if constexpr (TRU) rho = s > 0.0 ? fast_exp2(TP->ie * ls) : 0.0;
     }
     const double sb = G.s.sbeff * fast_exp2_floor(__builtin_fma(G.nkl, t, -G.nkl));
     const double gt = G.gk * t;
-    const double val = sb * __builtin_fma(gt * gt, fast_rcp(__builtin_fma(dx, dx, dy * dy)), 1.0);
+    double val = sb * __builtin_fma(gt * gt, fast_rcp(__builtin_fma(dx, dx, dy * dy)), 1.0);
     double chk = (u + v) + (G.nkl + G.pe2);            // (the comparisons and the exponentials' clamps swallow a NaN)
     if constexpr (SPIRAL) chk += spi_chk;
+    if constexpr (TRU) {
+        val = trunc_apply(*TP, val, rho);
+        chk += TP->chk;
+    }
     return chk == chk ? val : chk;
 }
 
@@ -440,7 +523,9 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
 // without modes.  The SPI = false instantiations are the kernels as they were.
 // LAW: the context has radial laws (rpar, rkinds set; instantiated with FOU and SPI set only, such a context carries
 // both blocks); a slot of kind != 0 runs the LAW pixel function, with or without modes and spiral.
-template <bool FOU, bool SPI = false, bool LAW = false>
+// TRU: the context has truncations (tpar, tmasks set; instantiated with every other flag set only, such a context
+// carries every block); a slot with a side runs the TRU pixel function of its law, with or without modes and spiral.
+template <bool FOU, bool SPI = false, bool LAW = false, bool TRU = false>
 __global__ void __launch_bounds__(256)
 k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
@@ -448,7 +533,8 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
                int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
                int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                const double* __restrict__ spar = nullptr, const uint8_t* __restrict__ smasks = nullptr,
-               const double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr) {
+               const double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr,
+               const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -494,7 +580,34 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
             F.top = 32 - __builtin_clz((unsigned)modes);                                 // the highest mode present
         }
         const int kind = LAW ? rkinds[field * n_sersic + k] : 0;                         // wave-uniform
-        if (LAW && kind) {
+        const int sides = TRU ? tmasks[field * n_sersic + k] : 0;                        // wave-uniform
+        if (TRU && sides) {
+            const TruPar T = load_trunc(tpar + ((size_t)w * n_sersic + k) * kTruPar, sides);
+            RadPar R{};
+            SpiPar S{};
+            if (kind) R = load_radial(rpar + ((size_t)w * n_sersic + k) * kRadPar);
+            if (wound) S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);
+            auto pass = [&](auto fou, auto spi, auto law) {
+                for (int x0 = 0; x0 < xn; x0 += 64) {
+                    const int ix = x0 + lane;
+                    if (ix < xn)
+                        out[ix] = (first ? base(ix) : out[ix]) +
+                                  general_pixel<decltype(fou)::value, decltype(spi)::value, decltype(law)::value,
+                                                true>(G, F, (double)ix, y, &S, &R, &T);
+                }
+            };
+            auto by_law = [&](auto fou, auto spi) {
+                if (kind) pass(fou, spi, std::true_type{});
+                else pass(fou, spi, std::false_type{});
+            };
+            if (wound) {
+                if (modes) by_law(std::true_type{}, std::true_type{});
+                else by_law(std::false_type{}, std::true_type{});
+            } else {
+                if (modes) by_law(std::true_type{}, std::false_type{});
+                else by_law(std::false_type{}, std::false_type{});
+            }
+        } else if (LAW && kind) {
             const RadPar R = load_radial(rpar + ((size_t)w * n_sersic + k) * kRadPar);
             SpiPar S{};
             if (wound) S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);

@@ -21,7 +21,10 @@
 //                         unless the centre is on a pixel edge), the 64 lanes = 16 sub-cells x 4 sample rows
 // g is `general_point`: the law without a centroid term, its finite peak at u = v = 0.  It repeats general_pixel's
 // coordinate code and its fast_log2 / fast_exp2 forms, with modes, spiral and kind as WAVE-UNIFORM RUNTIME BRANCHES:
-// one instantiation serves every context, and the instantiations of psfmc_general.h are the text they were.
+// one instantiation serves every context without truncations, and the instantiations of psfmc_general.h are the text
+// they were.  TRU: a context with truncations runs the second instantiation of the two kernels, whose g is
+// `general_point * inner * outer` (the sides a wave-uniform runtime branch): every scheme below averages the product.
+// The TRU = false instantiations are the kernels as they were, with their registers and occupancy.
 // The work per walker and component is fixed but for the Ferrer edge pixels, which depend on that walker's parameters
 // alone; every pixel is written by one lane in one fixed summation order (the xor butterfly of integ_wave_sum), there
 // are no atomics and no exchange through LDS: a walker's bits do not depend on its batch.
@@ -34,12 +37,15 @@ constexpr int kMeanEdgeGrid = 8;     // Sersic.py MEAN_EDGE_GRID
 constexpr int kMeanChunk = 63;       // pixels of a row per pass of k_general_mean_rows: the 64th lane holds their last corners
 static_assert(kMeanEdgeGrid * kMeanEdgeGrid == 64, "the 64 lanes of a wave are the samples of a Ferrer edge pixel");
 
-// a component's constants as the kernels of psfmc_general.h left them; F.top == 0: no modes; kind 0: the Sersic law
-struct MeanPar { GenPar G; FouPar F; SpiPar S; RadPar R; bool wound; int kind; };
+// a component's constants as the kernels of psfmc_general.h left them; F.top == 0: no modes; kind 0: the Sersic law;
+// T.sides == 0: not truncated
+struct MeanPar { GenPar G; FouPar F; SpiPar S; RadPar R; TruPar T; bool wound; int kind; };
 __device__ __forceinline__ MeanPar load_mean(const double* __restrict__ gpar, const double* __restrict__ fpar,
                                              const uint8_t* __restrict__ fmasks, const double* __restrict__ spar,
                                              const uint8_t* __restrict__ smasks, const double* __restrict__ rpar,
-                                             const uint8_t* __restrict__ rkinds, int w, int k, int field, int n_sersic) {
+                                             const uint8_t* __restrict__ rkinds, const double* __restrict__ tpar,
+                                             const uint8_t* __restrict__ tmasks, int w, int k, int field,
+                                             int n_sersic) {
     MeanPar M{};
     const size_t i = (size_t)w * n_sersic + k;
     M.G = load_general(gpar + i * kGenPar);
@@ -57,10 +63,13 @@ __device__ __forceinline__ MeanPar load_mean(const double* __restrict__ gpar, co
     if (M.wound) M.S = load_spiral(spar + i * kSpiPar);
     M.kind = rkinds ? rkinds[field * n_sersic + k] : 0;                                     // wave-uniform
     if (M.kind) M.R = load_radial(rpar + i * kRadPar);
+    const int sides = tmasks ? tmasks[field * n_sersic + k] : 0;                            // wave-uniform (TRU only)
+    if (sides) M.T = load_trunc(tpar + i * kTruPar, sides);
     return M;
 }
 
 // g at the point (x, y); *inside: Ferrer's x < 1 (true at u = v = 0), true for the other laws
+template <bool TRU = false>
 __device__ __forceinline__ double general_point(const MeanPar& M, double x, double y, bool* inside) {
     const GenPar& G = M.G;
     const double dx = x - G.s.x0, dy = y - G.s.y0;
@@ -118,6 +127,12 @@ __device__ __forceinline__ double general_point(const MeanPar& M, double x, doub
         chk = (u + v) + (G.s.sbeff + R.chk);
     }
     if (M.wound) chk += M.S.chk;
+    if constexpr (TRU) {
+        if (M.T.sides) {                                               // wave-uniform: g times the truncation's factors
+            val = trunc_apply(M.T, val, s > 0.0 ? fast_exp2(__builtin_fma(M.T.ie, ls, l1e)) : 0.0);
+            chk += M.T.chk;
+        }
+    }
     *inside = in;
     return chk == chk ? val : chk;
 }
@@ -135,14 +150,16 @@ __device__ __forceinline__ MeanBox mean_box(const SersicPar& s) {
 
 // parts 1 and 2; grid (ceil(ny / 4), n), 4 waves = 4 rows per workgroup.  Behind k_general_rows, which wrote or added
 // to every pixel of the row: this kernel ADDS.  mflags [n_fields][n_sersic]; fpar / fmasks, spar / smasks, rpar / rkinds
-// are nullptr in a context without modes, spirals or laws.
+// are nullptr in a context without modes, spirals or laws, tpar / tmasks in one without truncations.
+template <bool TRU = false>
 __global__ void __launch_bounds__(256)
 k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                     const double* __restrict__ gpar, const uint8_t* __restrict__ mflags, int n_sersic, int n_psf,
                     int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
                     const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                     const double* __restrict__ spar, const uint8_t* __restrict__ smasks,
-                    const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds) {
+                    const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds,
+                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -157,7 +174,8 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
     const int xn = lx < nx ? lx : nx;
     for (int k = 0; k < n_sersic; ++k) {
         if (!fl[k]) continue;                                          // wave-uniform
-        const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, w, k, field, n_sersic);
+        const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, tpar, tmasks, w, k, field,
+                                      n_sersic);
         const MeanBox box = mean_box(M.G.s);
         const bool row_boxed = box.any && abs(iy - box.py) <= kIntegHalfBox;
         // (every lane runs every chunk to its end, lane 63 and the ones beyond the row's last pixel included: they
@@ -166,9 +184,9 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
             const int ix = x0 + lane;
             const double x = (double)ix;
             bool ic, itl, ibl, itr, ibr;
-            const double c = general_point(M, x, y, &ic);
-            const double tl = general_point(M, x - 0.5, y - 0.5, &itl);
-            const double bl = general_point(M, x - 0.5, y + 0.5, &ibl);
+            const double c = general_point<TRU>(M, x, y, &ic);
+            const double tl = general_point<TRU>(M, x - 0.5, y - 0.5, &itl);
+            const double bl = general_point<TRU>(M, x - 0.5, y + 0.5, &ibl);
             const double tr = __shfl_down(tl, 1, 64), br = __shfl_down(bl, 1, 64);
             itr = __shfl_down((int)itl, 1, 64) != 0;
             ibr = __shfl_down((int)ibl, 1, 64) != 0;
@@ -185,7 +203,7 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
                     const int bit = __ffsll((long long)edge) - 1;
                     edge &= edge - 1;
                     bool unused;
-                    const double v = general_point(M, (double)(x0 + bit) + ox, y + oy, &unused);
+                    const double v = general_point<TRU>(M, (double)(x0 + bit) + ox, y + oy, &unused);
                     const double mean = integ_wave_sum(v) / (double)(kMeanEdgeGrid * kMeanEdgeGrid);
                     if (lane == bit) val = mean;
                 }
@@ -196,13 +214,15 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
 }
 
 // parts 3 and 4; grid (n), one wave per walker, its mean components one after the other (k_integ_core with g)
+template <bool TRU = false>
 __global__ void __launch_bounds__(64)
 k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                     const double* __restrict__ gpar, const uint8_t* __restrict__ mflags, int n_sersic, int n_psf,
                     int n_psf_field, const WrapDesc* __restrict__ wrap_tab, int ny, int nx, double* __restrict__ img,
                     const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                     const double* __restrict__ spar, const uint8_t* __restrict__ smasks,
-                    const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds) {
+                    const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds,
+                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
     const int w = blockIdx.x;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x;
@@ -216,7 +236,8 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
     bool unused;
     for (int k = 0; k < n_sersic; ++k) {
         if (!fl[k]) continue;                                          // wave-uniform
-        const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, w, k, field, n_sersic);
+        const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, tpar, tmasks, w, k, field,
+                                      n_sersic);
         const double gx = M.G.s.x0 + 0.5, gy = M.G.s.y0 + 0.5;
         if (!(fabs(gx) <= kIntegMaxCentre && fabs(gy) <= kIntegMaxCentre)) continue;   // (NaN too)
         const double fx = floor(gx), fy = floor(gy);
@@ -235,7 +256,7 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
                 const int a = lane % g, b = lane / g;
                 const double sx = (double)X + (((double)a + 0.5) / (double)g - 0.5);
                 const double sy = (double)Y + (((double)b + 0.5) / (double)g - 0.5);
-                const double pv = general_point(M, sx, sy, &unused);
+                const double pv = general_point<TRU>(M, sx, sy, &unused);
                 const double v = lane < g * g ? pv : 0.0;
                 const double mean = integ_wave_sum(v) / (double)(g * g);
                 if (lane == 0) out[(size_t)Y * nx + X] += mean;
@@ -267,7 +288,7 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
                 double sum = 0.0;
 #pragma unroll 1
                 for (int sx = 0; sx < kIntegSub; ++sx)
-                    sum += general_point(M, bx + (((double)sx + 0.5) / (double)kIntegSub) * cw, sy, &unused);
+                    sum += general_point<TRU>(M, bx + (((double)sx + 0.5) / (double)kIntegSub) * cw, sy, &unused);
                 const double part = deferred ? 0.0 : sum * (cw * cw * (1.0 / (kIntegSub * kIntegSub)));
                 const int dx = (int)(floor(cx / scale) - fx) + 1, dy = (int)(floor(cy / scale) - fy) + 1;   // its pixel
                 const int pix = (dy & 1) * 2 + (dx & 1);

@@ -282,7 +282,8 @@ struct psfmc_ctx {
     // nothing is allocated and no kernel changes until a field registers an aux layout with a flag set
     bool gen_any = false;
     // doubles per walker of d_aux, the same for every field: the longest table a field of the context ever had
-    // (apply_aux_record; 2 n_sky + n_sersic, + 12 / 18 / 20 n_sersic from the first modes / spiral / law on)
+    // (apply_aux_record; 2 n_sky + n_sersic, + 12 / 18 / 20 / 24 n_sersic from the first modes / spiral / law /
+    // truncation on)
     int aux_stride = 0, aux_n_sky = 0;
     std::vector<uint8_t> gen_flags;      // [n_fields][n_sersic] general components, then [n_fields][n_sky] tilted skies
     uint8_t* d_gen_flags = nullptr;
@@ -316,6 +317,14 @@ struct psfmc_ctx {
     std::vector<uint8_t> rad_kinds;      // [n_fields][n_sersic] 0: the Sersic law, 1: Moffat, 2: Ferrer
     uint8_t* d_rad_kinds = nullptr;
     double* d_rad_par = nullptr;         // [max_walkers][n_sersic][kRadPar]
+    // truncations (psfmc_set_truncation_layout, psfmc_general.h); nothing is allocated and no kernel changes until a
+    // field registers one.  With the first registration aux_stride grows to aux_base + 24 n_sersic: the truncations'
+    // entries sit behind the Fourier, spiral and radial blocks, which such a context always carries (and whose masks
+    // and constants it allocates, all clear where no field has the keywords)
+    bool tru_any = false;
+    std::vector<uint8_t> tru_masks;      // [n_fields][n_sersic] bit 0: inner, bit 1: outer
+    uint8_t* d_tru_masks = nullptr;
+    double* d_tru_par = nullptr;         // [max_walkers][n_sersic][kTruPar]
     // general components rendered as the mean over each pixel (psfmc_set_general_mean, psfmc_general_mean.h): flags
     // only, no per-walker entries; nothing is allocated, nothing more is launched and every kernel gets the arguments
     // it got until a field registers a flag
@@ -1440,7 +1449,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->stretch.kind, c->stretch.partner_b, c->pt_blob, c->d_integ_flags, c->d_integ_par,
                     c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
-                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par, c->d_mean_flags};
+                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par, c->d_mean_flags, c->d_tru_masks, c->d_tru_par};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (void* p : c->aux_blobs)
@@ -1747,6 +1756,7 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 // images, the general kernel then ADDS to them; alone it writes.
 // k_general_rows as the context needs it: a context without modes and without spirals runs the kernel it always ran
 static decltype(&k_general_rows<false, false>) general_rows_kernel(const psfmc_ctx* c) {
+    if (c->tru_any) return k_general_rows<true, true, true, true>;
     if (c->rad_any) return k_general_rows<true, true, true>;
     if (c->spi_any) return c->fou_any ? k_general_rows<true, true> : k_general_rows<false, true>;
     return c->fou_any ? k_general_rows<true, false> : k_general_rows<false, false>;
@@ -1754,6 +1764,7 @@ static decltype(&k_general_rows<false, false>) general_rows_kernel(const psfmc_c
 
 // ... and so does k_general_split
 static decltype(&k_general_split<false, false>) general_split_kernel(const psfmc_ctx* c) {
+    if (c->tru_any) return k_general_split<true, true, true>;
     if (c->rad_any) return k_general_split<true, true>;
     return c->spi_any ? k_general_split<true, false> : k_general_split<false, false>;
 }
@@ -1762,19 +1773,21 @@ static decltype(&k_general_split<false, false>) general_split_kernel(const psfmc
 static void launch_general_mean(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
     const double* prep = c->d_prep + (size_t)w_off * c->plen;
     double* img = c->d_extra_img + (size_t)w_off * c->S;
-    const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
+    // (a context with truncations carries the masks and constants of modes, spirals and laws)
+    const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
     const double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
     const double* fpar = fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr;
     const double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
-    const double* rpar = c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
-    hipLaunchKernelGGL(k_general_mean_rows, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
+    const double* rpar = rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
+    const double* tpar = c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr;
+    hipLaunchKernelGGL(c->tru_any ? k_general_mean_rows<true> : k_general_mean_rows<false>, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
                        c->d_mean_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
                        fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
-                       c->rad_any ? c->d_rad_kinds : nullptr);
-    hipLaunchKernelGGL(k_general_mean_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags,
+                       rad ? c->d_rad_kinds : nullptr, tpar, c->tru_any ? c->d_tru_masks : nullptr);
+    hipLaunchKernelGGL(c->tru_any ? k_general_mean_core<true> : k_general_mean_core<false>, dim3(n), dim3(64), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
                        fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
-                       c->rad_any ? c->d_rad_kinds : nullptr);
+                       rad ? c->d_rad_kinds : nullptr, tpar, c->tru_any ? c->d_tru_masks : nullptr);
 }
 
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
@@ -1795,18 +1808,24 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
         // (a context with spirals: the same launch also forms the spirals' per-walker constants)
         // (a context with laws carries the masks and constants of modes and spirals, and forms the laws' constants
         // in the same launch too)
-        const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
+        // (and a context with truncations those of modes, spirals and laws; the truncations' constants too are
+        // formed in that launch)
+        const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
         double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
         const uint8_t* smasks = spi ? c->d_spi_masks : nullptr;
-        double* rpar = c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
-        const uint8_t* rkinds = c->rad_any ? c->d_rad_kinds : nullptr;
+        double* rpar = rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
+        const uint8_t* rkinds = rad ? c->d_rad_kinds : nullptr;
+        double* tpar = c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr;
+        const uint8_t* tmasks = c->tru_any ? c->d_tru_masks : nullptr;
         if (items > 0)
             hipLaunchKernelGGL(general_split_kernel(c), dim3((items + 255) / 256),
                                dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
                                c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, spar, smasks,
                                c->aux_base + fourier_len(c->n_sersic), rpar, rkinds,
-                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic));
+                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic), tpar, tmasks,
+                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic) +
+                                   radial_len(c->n_sersic));
         if (c->fou_any && items > 0)
             hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar,
@@ -1817,7 +1836,7 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                                dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
                                rows_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
                                fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                               fou ? c->d_fou_masks : nullptr, spar, smasks, rpar, rkinds);
+                               fou ? c->d_fou_masks : nullptr, spar, smasks, rpar, rkinds, tpar, tmasks);
             if (c->mean_any) launch_general_mean(c, n, w_off, skip, st);
             return;
         }
@@ -1829,7 +1848,7 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                        c->d_integ_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
-    const bool spi = c->spi_any || c->rad_any, fou = c->fou_any || c->rad_any;
+    const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
     if (c->gen_any)
         hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
                            dim3(256), 0, st, prep, c->plen, skip,
@@ -1841,8 +1860,10 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                            fou ? c->d_fou_masks : nullptr,
                            spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr,
                            spi ? c->d_spi_masks : nullptr,
-                           c->rad_any ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr,
-                           c->rad_any ? c->d_rad_kinds : nullptr);
+                           rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr,
+                           rad ? c->d_rad_kinds : nullptr,
+                           c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr,
+                           c->tru_any ? c->d_tru_masks : nullptr);
     if (c->gen_any && c->mean_any) launch_general_mean(c, n, w_off, skip, st);
 }
 
@@ -2107,8 +2128,11 @@ static AuxBlockFacts aux_block(psfmc_ctx* c, int b) {
     if (b == kBlkSpi)
         return {"spiral", "a spiral", "spiral", c->spi_masks, c->d_spi_masks, c->d_spi_par, c->spi_any, kSpiPar,
                 kSpiFlag, kSpiDegrees, kSpiFlag, kBlkSpi};
-    return {"radial", "a radial law", "a radial law", c->rad_kinds, c->d_rad_kinds, c->d_rad_par, c->rad_any, kRadPar,
-            0, 0, 0xff, kBlkFou};
+    if (b == kBlkRad)
+        return {"radial", "a radial law", "a radial law", c->rad_kinds, c->d_rad_kinds, c->d_rad_par, c->rad_any,
+                kRadPar, 0, 0, 0xff, kBlkFou};
+    return {"truncation", "a truncation", "truncation", c->tru_masks, c->d_tru_masks, c->d_tru_par, c->tru_any, kTruPar,
+            0, 0, kTruInner | kTruOuter, kBlkFou};
 }
 
 // no launch may read the tables, flags and masks a layout call replaces
@@ -2181,22 +2205,25 @@ static int apply_aux_record(psfmc_ctx* c, int field, int touched = -1) {
     const AuxTable t = compose_aux_table(r, L.n_sky, c->n_sersic);
     void* fresh = nullptr;
     if (t.n_aux) {
-        // konst first (8-byte units), then col and, behind the columns, the kinds
+        // konst first (8-byte units), then col and, behind the columns, the kinds and the truncation sides
         const size_t cb = t.konst.size() * sizeof(double), ib = t.col.size() * sizeof(int);
-        std::vector<unsigned char> blob(cb + ib + t.kinds.size() * sizeof(int));
+        const size_t kb = t.kinds.size() * sizeof(int);
+        std::vector<unsigned char> blob(cb + ib + kb + t.sides.size() * sizeof(int));
         memcpy(blob.data(), t.konst.data(), cb);
         memcpy(blob.data() + cb, t.col.data(), ib);
-        if (!t.kinds.empty()) memcpy(blob.data() + cb + ib, t.kinds.data(), t.kinds.size() * sizeof(int));
+        if (!t.kinds.empty()) memcpy(blob.data() + cb + ib, t.kinds.data(), kb);
+        if (!t.sides.empty()) memcpy(blob.data() + cb + ib + kb, t.sides.data(), t.sides.size() * sizeof(int));
         HIP_TRY(hipMalloc(&fresh, blob.size()));
         HIP_TRY(hipMemcpy(fresh, blob.data(), blob.size(), hipMemcpyHostToDevice));
     }
     if (c->aux_blobs.size() != (size_t)c->n_fields) c->aux_blobs.assign(c->n_fields, nullptr);
     if (c->aux_blobs[field]) (void)hipFree(c->aux_blobs[field]);
     c->aux_blobs[field] = fresh;
-    L.n_aux = t.n_aux; L.n_fou = t.n_fou; L.n_spi = t.n_spi; L.n_rad = t.n_rad;
+    L.n_aux = t.n_aux; L.n_fou = t.n_fou; L.n_spi = t.n_spi; L.n_rad = t.n_rad; L.n_tru = t.n_tru;
     L.aux_const = static_cast<const double*>(fresh);
     L.aux_col = fresh ? reinterpret_cast<const int*>(L.aux_const + t.n_aux) : nullptr;
     L.rad_kind = t.kinds.empty() ? nullptr : L.aux_col + t.n_aux;
+    L.tru_side = t.sides.empty() ? nullptr : L.aux_col + t.n_aux + t.kinds.size();
     if (c->n_fields > 1 && c->d_field_layouts)
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
     if (t.n_aux > c->aux_stride) {           // (a table index is the entry's place in the walker's vector)
@@ -2483,7 +2510,8 @@ extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
 static_assert(kFouModes == PSFMC_FOURIER_MODES, "mode count of include/psfmc_hip.h");
 static_assert(kSpiIn == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
 static_assert(kRadIn == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
-// psfmc_set_fourier_layout, _spiral_layout and _radial_layout: block b of field `field` with its per-Sersic tags.
+static_assert(kTruIn == PSFMC_TRUNC_PARAMS, "truncation parameter count of include/psfmc_hip.h");
+// psfmc_set_fourier_layout, _spiral_layout, _radial_layout and _truncation_layout: block b of field `field` with its per-Sersic tags.
 // Everything is checked before the record changes, so a refused call leaves the field as it was.
 static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const int* tags, const int* col,
                             const double* konst) {
@@ -2502,6 +2530,9 @@ static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const 
             return fail(PSFMC_EINVAL, "Sersic %d: mode mask 0x%x names a mode outside 1 ... %d", i, tags[i], kFouModes);
         if (b == kBlkRad && (tags[i] < 0 || tags[i] > kRadFerrer))
             return fail(PSFMC_EINVAL, "Sersic %d: radial kind %d outside 0 ... %d", i, tags[i], kRadFerrer);
+        if (b == kBlkTru && (tags[i] & ~(kTruInner | kTruOuter)))
+            return fail(PSFMC_EINVAL, "Sersic %d: truncation flags %d outside 0 ... %d (bit 0 inner, bit 1 outer)", i,
+                        tags[i], kTruInner | kTruOuter);
         any_here = any_here || tags[i];
     }
     if (any_here && r.base_col.empty())
@@ -2544,21 +2575,39 @@ extern "C" int psfmc_set_radial_layout(psfmc_ctx* c, int field, int n_sersic, co
     return set_block_layout(c, kBlkRad, field, n_sersic, kinds, col, konst);
 }
 
+extern "C" int psfmc_set_truncation_layout(psfmc_ctx* c, int field, int n_sersic, const int* flags, const int* col,
+                                           const double* konst) {
+    return set_block_layout(c, kBlkTru, field, n_sersic, flags, col, konst);
+}
+
 extern "C" int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_col, const double* base_const,
                                      const int* mode_mask, const int* fou_col, const double* fou_const,
                                      const int* spi_flags, const int* spi_col, const double* spi_const,
                                      const int* rad_kinds, const int* rad_col, const double* rad_const,
                                      double* out_const, int* out_col, int* out_kinds, int* counts) {
-    if (n_sky < 0 || n_sersic < 0 || !out_const || !out_col || !out_kinds || !counts)
+    return psfmc_debug_aux_table_blocks(n_sky, n_sersic, base_col, base_const, mode_mask, fou_col, fou_const,
+                                        spi_flags, spi_col, spi_const, rad_kinds, rad_col, rad_const, nullptr, nullptr,
+                                        nullptr, out_const, out_col, out_kinds, nullptr, counts);
+}
+
+// ... with the truncation block: out_sides and counts[4] are written where tru_flags is given
+extern "C" int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                                            const int* mode_mask, const int* fou_col, const double* fou_const,
+                                            const int* spi_flags, const int* spi_col, const double* spi_const,
+                                            const int* rad_kinds, const int* rad_col, const double* rad_const,
+                                            const int* tru_flags, const int* tru_col, const double* tru_const,
+                                            double* out_const, int* out_col, int* out_kinds, int* out_sides,
+                                            int* counts) {
+    if (n_sky < 0 || n_sersic < 0 || !out_const || !out_col || !out_kinds || !counts || (tru_flags && !out_sides))
         return fail(PSFMC_EINVAL, "bad counts or NULL output");
     FieldAuxRecord r;
     if (base_col && base_const) {
         r.base_col.assign(base_col, base_col + aux_len(n_sky, n_sersic));
         r.base_const.assign(base_const, base_const + aux_len(n_sky, n_sersic));
     }
-    const int* tags[kAuxBlocks] = {mode_mask, spi_flags, rad_kinds};
-    const int* col[kAuxBlocks] = {fou_col, spi_col, rad_col};
-    const double* konst[kAuxBlocks] = {fou_const, spi_const, rad_const};
+    const int* tags[kAuxBlocks] = {mode_mask, spi_flags, rad_kinds, tru_flags};
+    const int* col[kAuxBlocks] = {fou_col, spi_col, rad_col, tru_col};
+    const double* konst[kAuxBlocks] = {fou_const, spi_const, rad_const, tru_const};
     for (int b = 0; b < kAuxBlocks; ++b)
         if (tags[b] && col[b] && konst[b]) r.block[b].store(n_sersic, aux_block_len(b, n_sersic), tags[b], col[b], konst[b]);
     const AuxTable t = compose_aux_table(r, n_sky, n_sersic);
@@ -2566,6 +2615,10 @@ extern "C" int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_co
     std::copy(t.col.begin(), t.col.end(), out_col);
     std::copy(t.kinds.begin(), t.kinds.end(), out_kinds);
     counts[0] = t.n_aux; counts[1] = t.n_fou; counts[2] = t.n_spi; counts[3] = t.n_rad;
+    if (tru_flags) {
+        std::copy(t.sides.begin(), t.sides.end(), out_sides);
+        counts[4] = t.n_tru;
+    }
     return PSFMC_OK;
 }
 
@@ -4258,6 +4311,13 @@ extern "C" int psfmc_group_set_radial_layout(psfmc_group* g, int n_sersic, const
                                              const double* konst) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_radial_layout(c, 0, n_sersic, kinds, col, konst));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_truncation_layout(psfmc_group* g, int n_sersic, const int* flags, const int* col,
+                                                 const double* konst) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_truncation_layout(c, 0, n_sersic, flags, col, konst));
     return PSFMC_OK;
 }
 

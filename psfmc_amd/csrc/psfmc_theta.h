@@ -60,6 +60,12 @@ struct ThetaLayout {
     // global memory: 0 Sersic, 1 Moffat, 2 Ferrer; 0 / nullptr: none (every layout before the call)
     int n_rad;
     const int* rad_kind;
+    // truncations (psfmc_set_truncation_layout): the LAST n_tru = 4 n_sersic of the n_aux entries, behind the laws'
+    // (n_tru > 0 implies the three blocks before it, empty without the keywords); per Sersic slot in_lo, in_hi, out_lo,
+    // out_hi; tru_side [n_sersic] in global memory: bit 0 inner, bit 1 outer; 0 / nullptr: none (every layout before
+    // the call)
+    int n_tru;
+    const int* tru_side;
 };
 
 // where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
@@ -632,7 +638,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
                 // reff_b > reff is)
                 double* a = ax.aux + (size_t)w * ax.stride;
-                const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad;
+                const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad - G.n_tru;
                 for (int j = 0; j < n_base; ++j) {
                     const int col = G.aux_col[j];
                     const double v = col >= 0 ? th[col] : G.aux_const[j];
@@ -679,7 +685,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // the radial laws' entries, per Sersic slot two; outside the support: a Moffat's beta not
                     // finite or <= 1; a Ferrer's alpha or beta not finite, alpha < 0 or beta >= 2
                     int k = 0;
-                    for (int j0 = G.n_aux - G.n_rad; j0 < G.n_aux; j0 += 2, ++k) {
+                    for (int j0 = G.n_aux - G.n_tru - G.n_rad; j0 < G.n_aux - G.n_tru; j0 += 2, ++k) {
                         const int c0 = G.aux_col[j0], c1 = G.aux_col[j0 + 1];
                         const double v0 = c0 >= 0 ? th[c0] : G.aux_const[j0];
                         const double v1 = c1 >= 0 ? th[c1] : G.aux_const[j0 + 1];
@@ -689,6 +695,23 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                         if (kind == 1 && (!(v0 > 1.0) || !(v0 < INFINITY))) lp = -INFINITY;
                         if (kind == 2 && (!(v0 >= 0.0) || !(v0 < INFINITY) || !(v1 < 2.0) || !(fabs(v1) < INFINITY)))
                             lp = -INFINITY;
+                    }
+                }
+                if (G.n_tru > 0) {                                          // wave-uniform
+                    // the truncations' entries, per Sersic slot two pairs (lo, hi); outside the support of a side
+                    // present: a value not finite, lo < 0 or hi <= lo
+                    int k = 0;
+                    for (int j0 = G.n_aux - G.n_tru; j0 < G.n_aux; j0 += 4, ++k) {
+                        const int sides = G.tru_side[k];
+                        for (int j = 0; j < 4; j += 2) {
+                            const int c0 = G.aux_col[j0 + j], c1 = G.aux_col[j0 + j + 1];
+                            const double lo = c0 >= 0 ? th[c0] : G.aux_const[j0 + j];
+                            const double hi = c1 >= 0 ? th[c1] : G.aux_const[j0 + j + 1];
+                            a[j0 + j] = lo;
+                            a[j0 + j + 1] = hi;
+                            if (((sides >> (j >> 1)) & 1) && (!(lo >= 0.0) || !(hi > lo) || !(hi < INFINITY)))
+                                lp = -INFINITY;
+                        }
                     }
                 }
             }

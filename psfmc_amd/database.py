@@ -27,7 +27,8 @@ _INTEGRATE_COMMENT = 'pixel-integrated Sersic (not the reference profile)'
 _FLAG_COMMENTS = {'SERINT': _INTEGRATE_COMMENT, 'SERBOX': 'Sersic with boxy/disky isophotes (boxiness)',
                   'SKYSLP': 'tilted sky (slope)', 'SERFOU': 'Sersic with azimuthal Fourier modes (fourier)',
                   'SERSPI': 'Sersic with spiral arms by coordinate rotation (spiral)',
-                  'SERLAW': 'radial law of the component (Moffat, Ferrer)'}
+                  'SERLAW': 'radial law of the component (Moffat, Ferrer)',
+                  'SERTRU': 'truncated sides of the component (truncation)'}
 
 
 class Table(object):

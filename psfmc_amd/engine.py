@@ -290,6 +290,10 @@ def load_library():
     lib.psfmc_set_radial_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_radial_layout.restype = ci
     lib.psfmc_group_set_radial_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
+    lib.psfmc_set_truncation_layout.restype = ci
+    lib.psfmc_set_truncation_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
+    lib.psfmc_group_set_truncation_layout.restype = ci
+    lib.psfmc_group_set_truncation_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
     lib.psfmc_set_general_mean.restype = ci
     lib.psfmc_set_general_mean.argtypes = [vp, ci, ci, ip]
     lib.psfmc_group_set_general_mean.restype = ci
@@ -304,6 +308,9 @@ def load_library():
     lib.psfmc_debug_math.argtypes = [ci, ci, ci, _c_double_p, _c_double_p]
     lib.psfmc_debug_aux_table.restype = ci
     lib.psfmc_debug_aux_table.argtypes = [ci, ci, ip, _c_double_p] + 3 * [ip, ip, _c_double_p] + [_c_double_p, ip, ip, ip]
+    lib.psfmc_debug_aux_table_blocks.restype = ci
+    lib.psfmc_debug_aux_table_blocks.argtypes = ([ci, ci, ip, _c_double_p] + 4 * [ip, ip, _c_double_p] +
+                                                 [_c_double_p, ip, ip, ip, ip])
     lib.psfmc_debug_sweep.restype = ci
     lib.psfmc_debug_sweep.argtypes = [ci, ci, ctypes.c_size_t, ci, _c_double_p]
     lib.psfmc_debug_valu_rate.restype = ci
@@ -426,13 +433,15 @@ def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
 FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude and a phase entry each
 SPIRAL_PARAMS = 6          # PSFMC_SPIRAL_PARAMS: r_in, r_out, winding, alpha, inclination, sky angle
 RADIAL_PARAMS = 2          # PSFMC_RADIAL_PARAMS: (beta, unused) of a Moffat slot, (alpha, beta) of a Ferrer slot
+TRUNC_PARAMS = 4           # PSFMC_TRUNC_PARAMS: in_lo, in_hi, out_lo, out_hi of a slot (flag bit 0 inner, bit 1 outer)
 # the blocks behind the aux entries: name -> (entries per Sersic, the per-Sersic tags are flags)
-_BLOCKS = {'fourier': (2 * FOURIER_MODES, False), 'spiral': (SPIRAL_PARAMS, True), 'radial': (RADIAL_PARAMS, False)}
+_BLOCKS = {'fourier': (2 * FOURIER_MODES, False), 'spiral': (SPIRAL_PARAMS, True), 'radial': (RADIAL_PARAMS, False),
+           'truncation': (TRUNC_PARAMS, False)}
 
 
 def _block_layout_args(name, per_sersic, tags, col, const, tags_are_flags):
     """The arrays of psfmc_set_<name>_layout (kept alive by the caller's tuple) and their ctypes pointers: per
-    Sersic a tag -- mode mask, spiral flag, radial kind -- and `per_sersic` entries."""
+    Sersic a tag -- mode mask, spiral flag, radial kind, truncation sides -- and `per_sersic` entries."""
     i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
     tags = i32(np.asarray(tags, dtype=bool) if tags_are_flags else tags)
     col, const = i32(col), _f64(const).ravel()
@@ -486,10 +495,11 @@ def debug_pow_tab(values, p, device=0):
     return out.reshape(np.shape(values))
 
 
-def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radial=None):
+def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radial=None, truncation=None):
     """The auxiliary table the library composes for one field (psfmc_debug_aux_table; host only, no device): base =
     (col, const) of the aux layout, each block (tags, col, const) as its layout call takes them, None where the
-    field registered none -> (const, col, kinds, (n_aux, n_fou, n_spi, n_rad))."""
+    field registered none -> (const, col, kinds, (n_aux, n_fou, n_spi, n_rad)).  With `truncation`
+    (psfmc_debug_aux_table_blocks) -> (const, col, kinds, sides, (n_aux, n_fou, n_spi, n_rad, n_tru))."""
     lib = load_library()
     keep, args = [], [None, None]
     if base is not None:
@@ -503,11 +513,20 @@ def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radia
     const, col = np.full(n_max, np.nan), np.full(n_max, -2, dtype=np.int32)
     kinds, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(4, dtype=np.int32)
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    rc = lib.psfmc_debug_aux_table(int(n_sky), int(n_sersic), *(args + [_dp(const), ipt(col), ipt(kinds), ipt(counts)]))
+    if truncation is not None:
+        keep.append(_block_args('truncation', *truncation))
+        sides, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(5, dtype=np.int32)
+        rc = lib.psfmc_debug_aux_table_blocks(int(n_sky), int(n_sersic), *(
+            args + list(keep[-1][1][1:]) + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(counts)]))
+    else:
+        rc = lib.psfmc_debug_aux_table(int(n_sky), int(n_sersic), *(args + [_dp(const), ipt(col), ipt(kinds), ipt(counts)]))
     if rc != 0:
         raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
     n_aux = int(counts[0])
-    return const[:n_aux], col[:n_aux], kinds[:n_sersic if counts[3] else 0], tuple(int(n) for n in counts)
+    out = (const[:n_aux], col[:n_aux], kinds[:n_sersic if counts[3] else 0])
+    if truncation is not None:
+        out += (sides[:n_sersic if counts[4] else 0],)
+    return out + (tuple(int(n) for n in counts),)
 
 
 def debug_sweep(mode, nbytes, reps=20, device=0):
@@ -704,6 +723,13 @@ class Context(object):
         constant.  A context that never gets the call is what it was without it."""
         keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_set_radial_layout(self._ctx, 0, *args))
+
+    def set_truncation_layout(self, flags, col, const):
+        """Truncations (psfmc_set_truncation_layout; behind the radial layout): per Sersic slot the sides -- bit 0
+        inner, bit 1 outer -- and four entries, in_lo, in_hi, out_lo, out_hi; column of theta or -1 and a constant.
+        A context that never gets the call is what it was without it."""
+        keep, args = _block_args('truncation', flags, col, const)
+        self._check(self._lib.psfmc_set_truncation_layout(self._ctx, 0, *args))
 
     def set_general_mean(self, flags):
         """Which general Sersic slots (model-file order) are rendered as the mean of their law over each pixel
@@ -1042,6 +1068,10 @@ class FieldSetContext(object):
             def set_radial_layout(self, kinds, col, const):
                 keep, args = _block_args('radial', kinds, col, const)
                 owner._check(owner._lib.psfmc_set_radial_layout(owner._ctx, int(field), *args))
+
+            def set_truncation_layout(self, flags, col, const):
+                keep, args = _block_args('truncation', flags, col, const)
+                owner._check(owner._lib.psfmc_set_truncation_layout(owner._ctx, int(field), *args))
 
             def set_general_mean(self, flags):
                 flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
@@ -1523,6 +1553,11 @@ class ContextGroup(object):
         """`Context.set_radial_layout` on every device of the group."""
         keep, args = _block_args('radial', kinds, col, const)
         self._check(self._lib.psfmc_group_set_radial_layout(self._grp, *args))
+
+    def set_truncation_layout(self, flags, col, const):
+        """`Context.set_truncation_layout` on every device of the group."""
+        keep, args = _block_args('truncation', flags, col, const)
+        self._check(self._lib.psfmc_group_set_truncation_layout(self._grp, *args))
 
     def set_general_mean(self, flags):
         """`Context.set_general_mean` on every device of the group."""

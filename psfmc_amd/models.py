@@ -279,11 +279,24 @@ class MultiComponentModel(object):
                 slot_col += [-1] * Sersic.RADIAL_PARAMS; slot_const += [0.0] * Sersic.RADIAL_PARAMS
         rad_col, rad_const = slot_col[n_before:], slot_const[n_before:]
         slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
+        # truncations (`truncation`): per Sersic slot in_lo, in_hi, out_lo, out_hi as declared, an absent side (and a
+        # slot without the keyword) constants inside the support that are never read; registered behind the laws, and
+        # only by a model with the keyword
+        for c in self._sersic:
+            flags = getattr(c, 'truncation_flags', 0)
+            for j, (attr, absent) in enumerate(zip(Sersic.TRUNC_ATTRS, Sersic.TRUNC_ABSENT)):
+                if (flags >> (j // 2)) & 1:
+                    add(c, attr)
+                else:
+                    slot_col.append(-1); slot_const.append(absent)
+        tru_col, tru_const = slot_col[n_before:], slot_const[n_before:]
+        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
         if columns is not None:
             aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
             fou_col = [int(columns[c]) if c >= 0 else -1 for c in fou_col]
             spi_col = [int(columns[c]) if c >= 0 else -1 for c in spi_col]
             rad_col = [int(columns[c]) if c >= 0 else -1 for c in rad_col]
+            tru_col = [int(columns[c]) if c >= 0 else -1 for c in tru_col]
 
         def register_aux():
             if self.has_aux:
@@ -294,6 +307,8 @@ class MultiComponentModel(object):
                 eng.set_spiral_layout(self.sersic_spiral_flags, spi_col, spi_const)
             if any(self.sersic_radial_kinds):
                 eng.set_radial_layout(self.sersic_radial_kinds, rad_col, rad_const)
+            if any(self.sersic_truncation_flags):
+                eng.set_truncation_layout(self.sersic_truncation_flags, tru_col, tru_const)
             # which general components are rendered as the mean over each pixel (`pixel_mean=True`): flags, no
             # entries; the last call, and only by a model with the keyword
             if any(self.sersic_general_mean):
@@ -328,7 +343,8 @@ class MultiComponentModel(object):
     @property
     def sersic_general_flags(self):
         """[n_sersic] which Sersic components (model-file order) run the general kernels: those given a `boxiness`
-        or `fourier` modes (a component with modes alone is a general one at c = 0)."""
+        or `fourier` modes (a component with modes alone is a general one at c = 0), a `spiral` or a `truncation`, and
+        every `Moffat` and `Ferrer`."""
         return [bool(getattr(c, 'is_general', False)) for c in self._sersic]
 
     @property
@@ -347,13 +363,19 @@ class MultiComponentModel(object):
         return [Sersic.RADIAL_KINDS[getattr(c, 'radial_law', None)] for c in self._sersic]
 
     @property
+    def sersic_truncation_flags(self):
+        """[n_sersic] the truncation of each Sersic slot (model-file order): bit 0 inner, bit 1 outer; 0: none."""
+        return [int(getattr(c, 'truncation_flags', 0)) for c in self._sersic]
+
+    @property
     def sersic_general_mean(self):
         """[n_sersic] which Sersic slots (model-file order) were given `pixel_mean=True`."""
         return [bool(getattr(c, 'pixel_mean', False)) for c in self._sersic]
 
     @property
     def has_aux(self):
-        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier` or `spiral`)?"""
+        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier`, `spiral` or
+        `truncation`, a `Moffat` or `Ferrer`)?"""
         return any(self.sky_slope_flags) or any(self.sersic_general_flags)
 
     def aux_rows(self, theta):
@@ -365,7 +387,9 @@ class MultiComponentModel(object):
         (zeros without modes) and behind them psfmc_set_spiral_layout's 6 n_sersic: per Sersic r_in, r_out, winding,
         alpha, inclination and sky angle as declared (constants inside the support for a component without it).  A
         model with a `Moffat` or `Ferrer` carries both blocks and behind them psfmc_set_radial_layout's 2 n_sersic:
-        per Sersic slot (beta, 0) or (alpha, beta), zeros for a slot with the Sersic law."""
+        per Sersic slot (beta, 0) or (alpha, beta), zeros for a slot with the Sersic law.  A model with a `truncation`
+        carries the three blocks and behind them psfmc_set_truncation_layout's 4 n_sersic: per Sersic slot in_lo,
+        in_hi, out_lo, out_hi (constants inside the support for an absent side): 2 n_sky + 25 n_sersic in all."""
         if not self.has_aux:
             return None
         theta = self._theta(theta)
@@ -380,7 +404,8 @@ class MultiComponentModel(object):
             if isinstance(c, Sersic):
                 cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
-        laws = any(self.sersic_radial_kinds)
+        trunc = any(self.sersic_truncation_flags)
+        laws = any(self.sersic_radial_kinds) or trunc
         if any(self.sersic_fourier_masks) or any(self.sersic_spiral_flags) or laws:
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
@@ -400,6 +425,12 @@ class MultiComponentModel(object):
                     pars = (c._radial_values(c.values_batch(theta[:, s]), n_w) if c.radial_law
                             else np.zeros((n_w, Sersic.RADIAL_PARAMS)))
                     cols += [pars[:, j] for j in range(Sersic.RADIAL_PARAMS)]
+        if trunc:
+            for c, s in zip(self.components, self._spans):
+                if isinstance(c, Sersic):
+                    pars = (c._truncation_values(c.values_batch(theta[:, s]), n_w) if c.has_truncation
+                            else np.tile(Sersic.TRUNC_ABSENT, (n_w, 1)))
+                    cols += [pars[:, j] for j in range(Sersic.TRUNC_PARAMS)]
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
     @staticmethod
