@@ -9,17 +9,39 @@
 #pragma once
 #include <vector>
 
+#include "../../include/psfmc_hip.h"
 #include "psfmc_general.h"
 
 namespace psfmc {
 
 enum { kBlkFou = 0, kBlkSpi, kBlkRad, kBlkTru, kAuxBlocks };
 
+// A block's facts, in table order: its name in messages, its sizes, how a registration's per-Sersic tag becomes the
+// mask byte the kernels read, and which blocks' buffers a context that has it carries.
+struct AuxBlockFacts {
+    const char *name, *what, *excl;      // psfmc_set_<name>_layout; "components that have <what>"; "<excl> and integrate"
+    int in;                              // table entries per Sersic
+    int par;                             // per-walker device constants per Sersic
+    int flag, deg_bit;                   // mask byte: flag (0: the tag itself) | deg_bit where the angles are in degrees
+    int any_bits;                        // the bits of a mask byte that say "registered"
+    int first;                           // a context with this block carries the buffers of blocks first ... this one
+};
+// mask bytes: mode mask (bit m - 1), bit 6: the phases are in degrees | bit 0: the component has a spiral, bit 1:
+// angles in degrees | the kind, 0: the Sersic law, 1: Moffat, 2: Ferrer | bit 0: inner, bit 1: outer
+constexpr AuxBlockFacts kAuxBlock[kAuxBlocks] = {
+    {"fourier", "modes", "fourier", kFouPar, kFouPar, 0, kFouDegrees, kFouModeBits, kBlkFou},
+    {"spiral", "a spiral", "spiral", kSpiIn, kSpiPar, kSpiFlag, kSpiDegrees, kSpiFlag, kBlkSpi},
+    {"radial", "a radial law", "a radial law", kRadIn, kRadPar, 0, 0, 0xff, kBlkFou},
+    {"truncation", "a truncation", "truncation", kTruIn, kTruPar, 0, 0, kTruInner | kTruOuter, kBlkFou},
+};
+static_assert(kFouModes == PSFMC_FOURIER_MODES && kAuxBlock[kBlkFou].in == 2 * PSFMC_FOURIER_MODES,
+              "mode count of include/psfmc_hip.h");
+static_assert(kAuxBlock[kBlkSpi].in == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
+static_assert(kAuxBlock[kBlkRad].in == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
+static_assert(kAuxBlock[kBlkTru].in == PSFMC_TRUNC_PARAMS, "truncation parameter count of include/psfmc_hip.h");
+
 // entries of block b for n_sersic components
-inline int aux_block_len(int b, int n_sersic) {
-    return b == kBlkFou ? fourier_len(n_sersic) : b == kBlkSpi ? spiral_len(n_sersic)
-         : b == kBlkRad ? radial_len(n_sersic) : trunc_len(n_sersic);
-}
+inline int aux_block_len(int b, int n_sersic) { return kAuxBlock[b].in * n_sersic; }
 
 // what one registration call passed: the per-Sersic tags (mode masks, spiral flags, radial kinds, truncation sides)
 // and the entries.

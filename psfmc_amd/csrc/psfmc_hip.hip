@@ -213,17 +213,14 @@ struct psfmc_ctx {
     int rg_log2 = 0;          // log2(rows per wave of the row kernels)
     double *d_img0 = nullptr, *d_img1 = nullptr;      // [chunk][S] staging for eval_images
     int img_cap = 0;
-    // raw-vector path (psfmc_set_layout)
-    bool has_layout = false;
-    ThetaLayout layout{};
-    // fields 1.. of a multi-field context: their own layouts (same structure, own priors / constants)
-    std::vector<ThetaLayout> more_layouts;
-    std::vector<void*> more_blobs;
-    std::vector<char> more_has;
+    // raw-vector path (psfmc_set_layout[_field]), [n_fields] each: a field's layout (the same structure for every
+    // field, own priors / constants), whether it has been set, and the one allocation behind its pointers
+    std::vector<ThetaLayout> layouts;
+    std::vector<char> has_layout;
+    std::vector<void*> layout_blobs;
     size_t theta_lds = 0;
     ThetaLayout* d_field_layouts = nullptr;  // [n_fields] device copies of the layouts (launches that span several fields)
     int* d_field_sides = nullptr;            // [n_fields][2] each field's image sides (ly, lx), for the same launches
-    void* d_layout_blob = nullptr;           // one allocation behind the layout's pointers
     // joint fits (psfmc_set_joint_priors): one parameter vector per walker for every field
     struct Joint {
         bool ready = false;                  // set by psfmc_set_joint_priors, cleared by a new field layout
@@ -243,8 +240,7 @@ struct psfmc_ctx {
     long long lin_pending = 0;    // samples in d_lin not yet convolved into d_acc
     bool linear_acc = true;       // set_option "linear_accumulation" 0: every sample through the full pipeline (round 1's way)
     double* d_rawstage = nullptr;   // [img_cap][S] raw-model staging for the sums
-    long long acc_count = 0;        // samples in the sums of field 0 (the only field of an ordinary context)
-    std::vector<long long> acc_more;   // ... of fields 1.. (psfmc_ctx_create_fields)
+    std::vector<long long> acc_count;   // [n_fields] samples in each field's sums
     int cols_grid = 0;
     // device-resident sampler state (psfmc_stretch_*): grow-only buffers
     struct Stretch {
@@ -294,37 +290,21 @@ struct psfmc_ctx {
     // of the three block layouts): apply_aux_record composes the field's table and mask rows from it
     std::vector<psfmc::FieldAuxRecord> aux_records;
     int aux_rows_w = -1;                 // walkers whose aux rows psfmc_set_aux_rows left in d_aux for the next row-based call
-    // azimuthal Fourier modes (psfmc_set_fourier_layout, psfmc_general.h); nothing is allocated and no kernel changes
-    // until a field registers modes.  aux_base = 2 n_sky + n_sersic; aux_stride grows to aux_base + 12 n_sersic
-    // with the first registration
-    int aux_base = 0;
-    bool fou_any = false;
-    std::vector<uint8_t> fou_masks;      // [n_fields][n_sersic] mode mask (bit m - 1), bit 6: the phases are in degrees
-    uint8_t* d_fou_masks = nullptr;
-    double* d_fou_par = nullptr;         // [max_walkers][n_sersic][kFouPar]
-    // spiral arms (psfmc_set_spiral_layout, psfmc_general.h); nothing is allocated and no kernel changes until a field
-    // registers one.  With the first registration aux_stride grows to aux_base + 18 n_sersic: the spiral entries sit
-    // behind the Fourier block, which such a context always carries (zeros where no field has modes)
-    bool spi_any = false;
-    std::vector<uint8_t> spi_masks;      // [n_fields][n_sersic] bit 0: the component has a spiral, bit 1: angles in degrees
-    uint8_t* d_spi_masks = nullptr;
-    double* d_spi_par = nullptr;         // [max_walkers][n_sersic][kSpiPar]
-    // radial laws (psfmc_set_radial_layout, psfmc_general.h); nothing is allocated and no kernel changes until a field
-    // registers one.  With the first registration aux_stride grows to aux_base + 20 n_sersic: the laws' entries sit
-    // behind the Fourier and the spiral block, which such a context always carries (and whose masks and constants it
-    // allocates, all clear where no field has modes or a spiral)
-    bool rad_any = false;
-    std::vector<uint8_t> rad_kinds;      // [n_fields][n_sersic] 0: the Sersic law, 1: Moffat, 2: Ferrer
-    uint8_t* d_rad_kinds = nullptr;
-    double* d_rad_par = nullptr;         // [max_walkers][n_sersic][kRadPar]
-    // truncations (psfmc_set_truncation_layout, psfmc_general.h); nothing is allocated and no kernel changes until a
-    // field registers one.  With the first registration aux_stride grows to aux_base + 24 n_sersic: the truncations'
-    // entries sit behind the Fourier, spiral and radial blocks, which such a context always carries (and whose masks
-    // and constants it allocates, all clear where no field has the keywords)
-    bool tru_any = false;
-    std::vector<uint8_t> tru_masks;      // [n_fields][n_sersic] bit 0: inner, bit 1: outer
-    uint8_t* d_tru_masks = nullptr;
-    double* d_tru_par = nullptr;         // [max_walkers][n_sersic][kTruPar]
+    int aux_base = 0;                    // 2 n_sky + n_sersic: the entries of psfmc_set_aux_layout, in front of the blocks
+    // [kAuxBlocks] the blocks behind them, in table order (psfmc_aux_table.h kAuxBlock: Fourier modes, spiral arms,
+    // radial laws, truncations; psfmc_set_<name>_layout, psfmc_general.h).  Nothing is allocated and no kernel changes
+    // until a field registers a block.  The first registration of block b allocates the masks and per-walker
+    // constants, all clear, of blocks kAuxBlock[b].first ... b -- a law or a truncation those of every block before
+    // it, a spiral only its own -- and aux_stride grows to the end of block b in a walker's vector (aux_base + 12 /
+    // 18 / 20 / 24 n_sersic): a block's entries sit behind those of every block before it, zeros or padding where no
+    // field has them.  `any` follows the fields' registrations; general_launch reads what a launch carries from it.
+    struct AuxBlockState {
+        bool any = false;                // some field has the block registered now
+        std::vector<uint8_t> masks;      // [n_fields][n_sersic] mask bytes; empty until the context meets the block
+        uint8_t* d_masks = nullptr;
+        double* d_par = nullptr;         // [max_walkers][n_sersic][kAuxBlock[b].par] (+ 1)
+    };
+    std::vector<AuxBlockState> blk;      // (sized at creation, like aux_records: kAuxBlocks is part 0's to know)
     // general components rendered as the mean over each pixel (psfmc_set_general_mean, psfmc_general_mean.h): flags
     // only, no per-walker entries; nothing is allocated, nothing more is launched and every kernel gets the arguments
     // it got until a field registers a flag
@@ -348,9 +328,6 @@ static ImgWindow img_window(const psfmc_ctx* c, int field) {
 }
 // pixels of a field's own image (the shape of its arrays at the C ABI)
 static size_t img_pixels(const psfmc_ctx* c, int field) { return (size_t)c->wraps[field].ly * c->wraps[field].lx; }
-
-// samples in the posterior-image sums of one field
-static long long& acc_n(psfmc_ctx* c, int field) { return field == 0 ? c->acc_count : c->acc_more[field - 1]; }
 
 // per-side constants of the row kernels
 struct RowShape { int rg, fast_waves, fast_rg_log2, regs; bool plain; };
@@ -1320,8 +1297,12 @@ static int ctx_create_impl(psfmc_ctx** out, int device, int n_fields, const int*
     c->ny = ny; c->nx = nx; c->nxh = nx / 2 + 1; c->S = ny * nx; c->F = ny * c->nxh;
     c->embed = embed; c->wraps = wraps;
     c->n_fields = n_fields; c->n_psf_field = n_psf;
-    c->acc_more.assign(n_fields - 1, 0);
+    c->layouts.resize(n_fields);
+    c->has_layout.assign(n_fields, 0);
+    c->layout_blobs.assign(n_fields, nullptr);
+    c->acc_count.assign(n_fields, 0);
     c->aux_records.resize(n_fields);
+    c->blk.resize(kAuxBlocks);
     c->n_psf = n_fields * n_psf; c->n_ps = n_ps; c->n_sersic = n_sersic;
     c->max_walkers = max_walkers; c->backend = backend;
     c->rlen = row_len(n_ps, n_sersic);
@@ -1444,14 +1425,17 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
     void* bufs[] = {c->d_sci,  c->d_var,  c->d_bad,     c->d_pspec, c->d_vspec, c->d_rows, c->d_prep,
                     c->d_like, c->d_skip, c->d_partial, c->d_real,  c->d_spec,  c->d_Ts[0], c->d_Kraw,
                     c->d_Kt,   c->d_twx,  c->d_twy,     c->d_img0,  c->d_img1, c->d_rho,   c->d_field, c->d_Ts[1], c->d_acc, c->d_lin, c->d_linpart,
-                    c->d_layout_blob, c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
+                    c->d_theta, c->d_extra, c->d_lnprior, c->d_rawstage, c->d_field_layouts,
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->stretch.kind, c->stretch.partner_b, c->pt_blob, c->d_integ_flags, c->d_integ_par,
-                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_fou_masks, c->d_fou_par, c->d_spi_masks,
-                    c->d_spi_par, c->d_rad_kinds, c->d_rad_par, c->d_mean_flags, c->d_tru_masks, c->d_tru_par};
+                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_mean_flags};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
+    for (const psfmc_ctx::AuxBlockState& k : c->blk) {
+        if (k.d_masks) (void)hipFree(k.d_masks);
+        if (k.d_par) (void)hipFree(k.d_par);
+    }
     for (void* p : c->aux_blobs)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1462,7 +1446,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
         }
         if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
     }
-    for (void* b : c->more_blobs)
+    for (void* b : c->layout_blobs)
         if (b) (void)hipFree(b);
     free_joint(c);
     if (c->joint.d_lp) (void)hipFree(c->joint.d_lp);
@@ -1754,93 +1738,115 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 // and tilted skies (psfmc_general.h).  After every kernel that writes prep records, same stream, the images are
 // formed and the components' blocks made neutral for the rasterisers.  The integrated profile's kernels WRITE the
 // images, the general kernel then ADDS to them; alone it writes.
-// k_general_rows as the context needs it: a context without modes and without spirals runs the kernel it always ran
-static decltype(&k_general_rows<false, false>) general_rows_kernel(const psfmc_ctx* c) {
-    if (c->tru_any) return k_general_rows<true, true, true, true>;
-    if (c->rad_any) return k_general_rows<true, true, true>;
-    if (c->spi_any) return c->fou_any ? k_general_rows<true, true> : k_general_rows<false, true>;
-    return c->fou_any ? k_general_rows<true, false> : k_general_rows<false, false>;
+// What a launch of the general kernels carries is decided ONCE, here, from the blocks' any-bits and the facts table:
+// block j is carried when some block b with `any` set has kAuxBlock[b].first <= j <= b.  So laws and truncations
+// bring the masks and constants of every block before them, a context with only spirals does not carry the Fourier
+// buffers, and a context without modes and without spirals runs the kernels it always ran.
+enum GenLevel { GEN_PLAIN = 0, GEN_FOU = 1, GEN_SPI = 2, GEN_FOU_SPI = 3, GEN_RAD, GEN_TRU };
+struct GenLaunch {
+    double* par[kAuxBlocks];             // the block's per-walker constants from walker w_off on; nullptr: not carried
+    const uint8_t* masks[kAuxBlocks];    // its mask bytes, or nullptr
+    int off[kAuxBlocks];                 // its first entry in a walker's auxiliary vector
+    GenLevel level;                      // which instantiation of the general kernels the context needs
+};
+static GenLaunch general_launch(const psfmc_ctx* c, int w_off) {
+    GenLaunch g{};
+    int off = c->aux_base, last = -1;
+    for (int b = 0; b < kAuxBlocks; ++b) {
+        g.off[b] = off;
+        off += aux_block_len(b, c->n_sersic);
+        if (!c->blk[b].any) continue;
+        last = b;
+        for (int j = kAuxBlock[b].first; j <= b; ++j) {
+            g.par[j] = c->blk[j].d_par + (size_t)w_off * c->n_sersic * kAuxBlock[j].par;
+            g.masks[j] = c->blk[j].d_masks;
+        }
+    }
+    g.level = last == kBlkTru ? GEN_TRU : last == kBlkRad ? GEN_RAD
+            : GenLevel((c->blk[kBlkFou].any ? GEN_FOU : 0) | (c->blk[kBlkSpi].any ? GEN_SPI : 0));
+    return g;
+}
+static decltype(&k_general_rows<false, false>) general_rows_kernel(GenLevel level) {
+    switch (level) {
+        case GEN_TRU: return k_general_rows<true, true, true, true>;
+        case GEN_RAD: return k_general_rows<true, true, true>;
+        case GEN_FOU_SPI: return k_general_rows<true, true>;
+        case GEN_SPI: return k_general_rows<false, true>;
+        case GEN_FOU: return k_general_rows<true, false>;
+        default: return k_general_rows<false, false>;
+    }
+}
+static decltype(&k_general_split<false, false>) general_split_kernel(GenLevel level) {
+    switch (level) {
+        case GEN_TRU: return k_general_split<true, true, true>;
+        case GEN_RAD: return k_general_split<true, true>;
+        case GEN_FOU_SPI: case GEN_SPI: return k_general_split<true, false>;
+        default: return k_general_split<false, false>;
+    }
 }
 
-// ... and so does k_general_split
-static decltype(&k_general_split<false, false>) general_split_kernel(const psfmc_ctx* c) {
-    if (c->tru_any) return k_general_split<true, true, true>;
-    if (c->rad_any) return k_general_split<true, true>;
-    return c->spi_any ? k_general_split<true, false> : k_general_split<false, false>;
+// k_general_rows over walkers w_off ... w_off + n: every general component, less the mean ones where the context has
+// some (the same flags pointer as ever where it has none), and the tilted skies; add: onto the integrated images
+static void launch_general_rows(psfmc_ctx* c, const GenLaunch& g, int n, int w_off, const uint8_t* skip,
+                                hipStream_t st, int add) {
+    const uint8_t* rows_flags = c->mean_any ? c->d_mean_flags + (size_t)c->n_fields * c->n_sersic : c->d_gen_flags;
+    hipLaunchKernelGGL(general_rows_kernel(g.level), dim3((c->ny + 3) / 4, n), dim3(256), 0, st,
+                       c->d_prep + (size_t)w_off * c->plen, c->plen, skip,
+                       c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
+                       c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
+                       c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, rows_flags, c->n_sersic, c->n_psf,
+                       c->n_psf_field, c->d_wrap, c->ny, c->nx, c->d_extra_img + (size_t)w_off * c->S, add,
+                       g.par[kBlkFou], g.masks[kBlkFou], g.par[kBlkSpi], g.masks[kBlkSpi], g.par[kBlkRad],
+                       g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru]);
 }
 
 // the mean components of a context that has some (psfmc_general_mean.h): behind k_general_rows, which left them out
-static void launch_general_mean(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
+static void launch_general_mean(psfmc_ctx* c, const GenLaunch& g, int n, int w_off, const uint8_t* skip,
+                                hipStream_t st) {
     const double* prep = c->d_prep + (size_t)w_off * c->plen;
     double* img = c->d_extra_img + (size_t)w_off * c->S;
-    // (a context with truncations carries the masks and constants of modes, spirals and laws)
-    const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
     const double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
-    const double* fpar = fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr;
-    const double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
-    const double* rpar = rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
-    const double* tpar = c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr;
-    hipLaunchKernelGGL(c->tru_any ? k_general_mean_rows<true> : k_general_mean_rows<false>, dim3((c->ny + 3) / 4, n), dim3(256), 0, st, prep, c->plen, skip, gpar,
-                       c->d_mean_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
-                       fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
-                       rad ? c->d_rad_kinds : nullptr, tpar, c->tru_any ? c->d_tru_masks : nullptr);
-    hipLaunchKernelGGL(c->tru_any ? k_general_mean_core<true> : k_general_mean_core<false>, dim3(n), dim3(64), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags,
-                       c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, fpar,
-                       fou ? c->d_fou_masks : nullptr, spar, spi ? c->d_spi_masks : nullptr, rpar,
-                       rad ? c->d_rad_kinds : nullptr, tpar, c->tru_any ? c->d_tru_masks : nullptr);
+    const bool tru = g.level == GEN_TRU;
+    hipLaunchKernelGGL(tru ? k_general_mean_rows<true> : k_general_mean_rows<false>, dim3((c->ny + 3) / 4, n),
+                       dim3(256), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags, c->n_sersic, c->n_psf,
+                       c->n_psf_field, c->d_wrap, c->ny, c->nx, img, g.par[kBlkFou], g.masks[kBlkFou],
+                       g.par[kBlkSpi], g.masks[kBlkSpi], g.par[kBlkRad], g.masks[kBlkRad], g.par[kBlkTru],
+                       g.masks[kBlkTru]);
+    hipLaunchKernelGGL(tru ? k_general_mean_core<true> : k_general_mean_core<false>, dim3(n), dim3(64), 0, st, prep,
+                       c->plen, skip, gpar, c->d_mean_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny,
+                       c->nx, img, g.par[kBlkFou], g.masks[kBlkFou], g.par[kBlkSpi], g.masks[kBlkSpi],
+                       g.par[kBlkRad], g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru]);
 }
 
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
     if ((!c->integ_any && !c->gen_any) || n <= 0) return;
-    // what k_general_rows renders: every general component, less the mean ones where the context has some (the same
-    // pointer as ever where it has none)
-    const uint8_t* rows_flags = c->mean_any ? c->d_mean_flags + (size_t)c->n_fields * c->n_sersic : c->d_gen_flags;
     double* prep = c->d_prep + (size_t)w_off * c->plen;
-    double* img = c->d_extra_img + (size_t)w_off * c->S;
     const int items = n * c->n_sersic;
+    const GenLaunch g = c->gen_any ? general_launch(c, w_off) : GenLaunch{};
     if (c->gen_any) {
         // (the flags the context owns are writable: a boxiness outside its support skips the walker)
         uint8_t* own_skip = (skip && skip >= c->d_skip && skip < c->d_skip + c->max_walkers) ? const_cast<uint8_t*>(skip)
                                                                                            : nullptr;
         double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
         const double* aux = c->d_aux + (size_t)w_off * c->aux_stride;
-        const uint8_t* sky_flags = c->d_gen_flags + (size_t)c->n_fields * c->n_sersic;
-        // (a context with spirals: the same launch also forms the spirals' per-walker constants)
-        // (a context with laws carries the masks and constants of modes and spirals, and forms the laws' constants
-        // in the same launch too)
-        // (and a context with truncations those of modes, spirals and laws; the truncations' constants too are
-        // formed in that launch)
-        const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
-        double* spar = spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr;
-        const uint8_t* smasks = spi ? c->d_spi_masks : nullptr;
-        double* rpar = rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr;
-        const uint8_t* rkinds = rad ? c->d_rad_kinds : nullptr;
-        double* tpar = c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr;
-        const uint8_t* tmasks = c->tru_any ? c->d_tru_masks : nullptr;
+        // (the same launch also forms the per-walker constants of the spirals, laws and truncations the context carries)
         if (items > 0)
-            hipLaunchKernelGGL(general_split_kernel(c), dim3((items + 255) / 256),
-                               dim3(256), 0, st, prep, c->plen,
-                               skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky, c->d_gen_flags,
-                               c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, spar, smasks,
-                               c->aux_base + fourier_len(c->n_sersic), rpar, rkinds,
-                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic), tpar, tmasks,
-                               c->aux_base + fourier_len(c->n_sersic) + spiral_len(c->n_sersic) +
-                                   radial_len(c->n_sersic));
-        if (c->fou_any && items > 0)
+            hipLaunchKernelGGL(general_split_kernel(g.level), dim3((items + 255) / 256), dim3(256), 0, st, prep,
+                               c->plen, skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky,
+                               c->d_gen_flags, c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, g.par[kBlkSpi],
+                               g.masks[kBlkSpi], g.off[kBlkSpi], g.par[kBlkRad], g.masks[kBlkRad], g.off[kBlkRad],
+                               g.par[kBlkTru], g.masks[kBlkTru], g.off[kBlkTru]);
+        if (c->blk[kBlkFou].any && items > 0)
             hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
-                               skip ? own_skip : nullptr, gpar, c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar,
-                               aux, c->aux_stride, c->aux_base, c->d_fou_masks, c->n_sersic, c->n_psf, c->n_psf_field,
-                               n);
+                               skip ? own_skip : nullptr, gpar, g.par[kBlkFou], aux, c->aux_stride, g.off[kBlkFou],
+                               g.masks[kBlkFou], c->n_sersic, c->n_psf, c->n_psf_field, n);
         if (!c->integ_any) {
-            hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
-                               dim3(256), 0, st, prep, c->plen, skip, gpar, aux, c->aux_stride, c->aux_n_sky, sky_flags,
-                               rows_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 0,
-                               fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                               fou ? c->d_fou_masks : nullptr, spar, smasks, rpar, rkinds, tpar, tmasks);
-            if (c->mean_any) launch_general_mean(c, n, w_off, skip, st);
+            launch_general_rows(c, g, n, w_off, skip, st, 0);
+            if (c->mean_any) launch_general_mean(c, g, n, w_off, skip, st);
             return;
         }
     }
+    double* img = c->d_extra_img + (size_t)w_off * c->S;
     double* ipar = c->d_integ_par + (size_t)w_off * c->n_sersic * kPrepSersic;
     hipLaunchKernelGGL(k_integ_split, dim3((items + 255) / 256), dim3(256), 0, st, prep, c->plen, skip, ipar,
                        c->d_integ_flags, c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n);
@@ -1848,23 +1854,8 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                        c->d_integ_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
     hipLaunchKernelGGL(k_integ_core, dim3(n), dim3(64), 0, st, prep, c->plen, skip, ipar, c->d_integ_flags,
                        c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny, c->nx, img);
-    const bool rad = c->rad_any || c->tru_any, spi = c->spi_any || rad, fou = c->fou_any || rad;
-    if (c->gen_any)
-        hipLaunchKernelGGL(general_rows_kernel(c), dim3((c->ny + 3) / 4, n),
-                           dim3(256), 0, st, prep, c->plen, skip,
-                           c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar,
-                           c->d_aux + (size_t)w_off * c->aux_stride, c->aux_stride, c->aux_n_sky,
-                           c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, rows_flags, c->n_sersic, c->n_psf,
-                           c->n_psf_field, c->d_wrap, c->ny, c->nx, img, 1,
-                           fou ? c->d_fou_par + (size_t)w_off * c->n_sersic * kFouPar : nullptr,
-                           fou ? c->d_fou_masks : nullptr,
-                           spi ? c->d_spi_par + (size_t)w_off * c->n_sersic * kSpiPar : nullptr,
-                           spi ? c->d_spi_masks : nullptr,
-                           rad ? c->d_rad_par + (size_t)w_off * c->n_sersic * kRadPar : nullptr,
-                           rad ? c->d_rad_kinds : nullptr,
-                           c->tru_any ? c->d_tru_par + (size_t)w_off * c->n_sersic * kTruPar : nullptr,
-                           c->tru_any ? c->d_tru_masks : nullptr);
-    if (c->gen_any && c->mean_any) launch_general_mean(c, n, w_off, skip, st);
+    if (c->gen_any) launch_general_rows(c, g, n, w_off, skip, st, 1);
+    if (c->gen_any && c->mean_any) launch_general_mean(c, g, n, w_off, skip, st);
 }
 
 // Small batches run WITHOUT the launch: their forward row waves form the table entries they read themselves (same
@@ -1934,7 +1925,7 @@ static int take_aux_rows(psfmc_ctx* c, int W) {
 static void launch_theta_prep(psfmc_ctx* c, int W, const double* d_theta, const double* d_extra,
                               double* d_rows, hipStream_t st, const StretchIn& sp, int field = 0, int w_off = 0,
                               int n_seg = 1) {
-    const ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    const ThetaLayout& L = c->layouts[field];
     FieldSegs segs{nullptr, nullptr, 0};
     if (n_seg > 1) segs = FieldSegs{c->d_field_layouts + field, c->d_field_sides + 2 * field, c->n_psf_field};
     if (w_off == 0) c->prep_tabs_valid = false;       // d_prep is being rewritten (w_off > 0: a further piece of one batch)
@@ -2108,33 +2099,6 @@ extern "C" int psfmc_eval_images_field(psfmc_ctx* c, int field, int W, const dou
 // ---------------------------------------------------------------------------
 // raw-vector path
 // ---------------------------------------------------------------------------
-// The blocks behind a field's base aux entries (psfmc_aux_table.h), in table order: what the context keeps for each,
-// how a registration's per-Sersic tag becomes the mask byte the kernels read, and its name in messages.
-struct AuxBlockFacts {
-    const char *name, *what, *excl;      // psfmc_set_<name>_layout; "components that have <what>"; "<excl> and integrate"
-    std::vector<uint8_t>& masks;         // [n_fields][n_sersic]; empty until the context meets the block
-    uint8_t*& d_masks;
-    double*& d_par;                      // [max_walkers][n_sersic][par] (+ 1)
-    bool& any;
-    int par;
-    int flag, deg_bit;                   // mask byte: flag (0: the tag itself) | deg_bit where the angles are in degrees
-    int any_bits;                        // the bits of a mask byte that say "registered"
-    int first;                           // a context with this block carries the buffers of blocks first ... this one
-};
-static AuxBlockFacts aux_block(psfmc_ctx* c, int b) {
-    if (b == kBlkFou)
-        return {"fourier", "modes", "fourier", c->fou_masks, c->d_fou_masks, c->d_fou_par, c->fou_any, kFouPar,
-                0, kFouDegrees, kFouModeBits, kBlkFou};
-    if (b == kBlkSpi)
-        return {"spiral", "a spiral", "spiral", c->spi_masks, c->d_spi_masks, c->d_spi_par, c->spi_any, kSpiPar,
-                kSpiFlag, kSpiDegrees, kSpiFlag, kBlkSpi};
-    if (b == kBlkRad)
-        return {"radial", "a radial law", "a radial law", c->rad_kinds, c->d_rad_kinds, c->d_rad_par, c->rad_any,
-                kRadPar, 0, 0, 0xff, kBlkFou};
-    return {"truncation", "a truncation", "truncation", c->tru_masks, c->d_tru_masks, c->d_tru_par, c->tru_any, kTruPar,
-            0, 0, kTruInner | kTruOuter, kBlkFou};
-}
-
 // no launch may read the tables, flags and masks a layout call replaces
 static int layout_sync(psfmc_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
@@ -2178,19 +2142,20 @@ static int write_block_masks(psfmc_ctx* c, int field, int touched = -1) {
     const FieldAuxRecord& r = c->aux_records[field];
     const size_t n_ser = c->n_sersic;
     for (int b = 0; b < kAuxBlocks; ++b) {
-        AuxBlockFacts k = aux_block(c, b);
-        if (b == touched && k.masks.empty()) k.masks.assign((size_t)c->n_fields * n_ser, 0);
-        if (k.masks.empty()) continue;
+        const AuxBlockFacts& k = kAuxBlock[b];
+        psfmc_ctx::AuxBlockState& s = c->blk[b];
+        if (b == touched && s.masks.empty()) s.masks.assign((size_t)c->n_fields * n_ser, 0);
+        if (s.masks.empty()) continue;
         const std::vector<int>& tags = r.block[b].tags;
         for (size_t i = 0; i < n_ser; ++i) {
             const int t = tags.empty() ? 0 : tags[i];
-            k.masks[(size_t)field * n_ser + i] =
+            s.masks[(size_t)field * n_ser + i] =
                 (uint8_t)(t ? ((k.flag ? k.flag : t) | (r.sersic_degrees[i] ? k.deg_bit : 0)) : 0);
         }
         bool any = false;
-        for (uint8_t m : k.masks) any = any || (m & k.any_bits);
-        if (k.d_masks) HIP_TRY(hipMemcpy(k.d_masks, k.masks.data(), k.masks.size(), hipMemcpyHostToDevice));
-        k.any = any;
+        for (uint8_t m : s.masks) any = any || (m & k.any_bits);
+        if (s.d_masks) HIP_TRY(hipMemcpy(s.d_masks, s.masks.data(), s.masks.size(), hipMemcpyHostToDevice));
+        s.any = any;
     }
     return PSFMC_OK;
 }
@@ -2200,7 +2165,7 @@ static int write_block_masks(psfmc_ctx* c, int field, int touched = -1) {
 // they hold keep their places; aux_stride only grows) and the blocks' masks and parameter buffers, all clear.
 static int apply_aux_record(psfmc_ctx* c, int field, int touched = -1) {
     RC_TRY(layout_sync(c));
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    ThetaLayout& L = c->layouts[field];
     const FieldAuxRecord& r = c->aux_records[field];
     const AuxTable t = compose_aux_table(r, L.n_sky, c->n_sersic);
     void* fresh = nullptr;
@@ -2236,14 +2201,14 @@ static int apply_aux_record(psfmc_ctx* c, int field, int touched = -1) {
     }
     const size_t n_masks = (size_t)c->n_fields * c->n_sersic;
     for (int b = 0; b < kAuxBlocks; ++b)
-        for (int j = aux_block(c, b).first; !r.block[b].empty() && j <= b; ++j) {
-            AuxBlockFacts k = aux_block(c, j);
-            if (k.d_masks) continue;
-            const size_t par_bytes = ((size_t)c->max_walkers * c->n_sersic * k.par + 1) * sizeof(double);
-            if (k.masks.empty()) k.masks.assign(n_masks, 0);
-            HIP_TRY(hipMalloc(&k.d_masks, n_masks));
-            HIP_TRY(hipMalloc(&k.d_par, par_bytes));
-            HIP_TRY(hipMemset(k.d_par, 0, par_bytes));
+        for (int j = kAuxBlock[b].first; !r.block[b].empty() && j <= b; ++j) {
+            psfmc_ctx::AuxBlockState& s = c->blk[j];
+            if (s.d_masks) continue;
+            const size_t par_bytes = ((size_t)c->max_walkers * c->n_sersic * kAuxBlock[j].par + 1) * sizeof(double);
+            if (s.masks.empty()) s.masks.assign(n_masks, 0);
+            HIP_TRY(hipMalloc(&s.d_masks, n_masks));
+            HIP_TRY(hipMalloc(&s.d_par, par_bytes));
+            HIP_TRY(hipMemset(s.d_par, 0, par_bytes));
         }
     RC_TRY(write_block_masks(c, field, touched));
     c->aux_rows_w = -1;
@@ -2257,7 +2222,7 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
                            const double* p1, const double* p2) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    if (field > 0 && (!c->has_layout || n_sky != c->layout.n_sky || n_params != c->layout.n_params))
+    if (field > 0 && (!c->has_layout[0] || n_sky != c->layouts[0].n_sky || n_params != c->layouts[0].n_params))
         return fail(PSFMC_EINVAL, "set field 0's layout first; every field has the same slots and columns");
     if (n_sky < 0 || n_sky > 16 || n_params < 0 || n_params > 4096) return fail(PSFMC_EINVAL, "bad counts");
     if (c->d_aux && n_sky != c->aux_n_sky)
@@ -2293,18 +2258,13 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
         memcpy(dp + ns + 2 * n_params, p2, n_params * sizeof(double));
         for (int i = 0; i < n_params; ++i) dp[ns + 4 * n_params + i] = prior_log_norm(family[i], p0[i], p1[i], p2[i]);
     }
-    if (field > 0 && c->more_layouts.size() < (size_t)c->n_fields - 1) {
-        c->more_layouts.resize(c->n_fields - 1);
-        c->more_blobs.resize(c->n_fields - 1, nullptr);
-        c->more_has.resize(c->n_fields - 1, 0);
-    }
-    void** blob_slot = field == 0 ? &c->d_layout_blob : &c->more_blobs[field - 1];
+    void** blob_slot = &c->layout_blobs[field];
     if (*blob_slot) { (void)hipFree(*blob_slot); *blob_slot = nullptr; }
     HIP_TRY(hipMalloc(blob_slot, blob.size()));
     HIP_TRY(hipMemcpy(*blob_slot, blob.data(), blob.size(), hipMemcpyHostToDevice));
     const int* dip = reinterpret_cast<const int*>(*blob_slot);
     const double* ddp = reinterpret_cast<const double*>(static_cast<unsigned char*>(*blob_slot) + int_bytes);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    ThetaLayout& L = c->layouts[field];
     // (a new layout has no auxiliary parameters until psfmc_set_aux_layout names them again, and no modes, spirals
     // or laws: the record keeps only the degrees)
     L = ThetaLayout{};
@@ -2333,21 +2293,19 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
         if (!c->d_field_layouts) HIP_TRY(hipMalloc(&c->d_field_layouts, (size_t)c->n_fields * sizeof(ThetaLayout)));
         HIP_TRY(hipMemcpy(c->d_field_layouts + field, &L, sizeof(ThetaLayout), hipMemcpyHostToDevice));
     }
-    if (field > 0) {
-        c->more_has[field - 1] = 1;
-        return PSFMC_OK;
+    if (field == 0) {                        // (the walkers' staging, sized by the columns every field shares)
+        for (double** p : {&c->d_theta, &c->d_extra, &c->d_lnprior})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        HIP_TRY(hipMalloc(&c->d_theta, (size_t)c->max_walkers * (n_params > 0 ? n_params : 1) * sizeof(double)));
+        HIP_TRY(hipMalloc(&c->d_extra, (size_t)c->max_walkers * sizeof(double)));
+        HIP_TRY(hipMalloc(&c->d_lnprior, (size_t)c->max_walkers * sizeof(double)));
+        c->theta_lds = theta_prep_lds_bytes(n_sky, c->n_ps, c->n_sersic, n_params);
+        if (c->theta_lds > 64 * 1024) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_theta_prep),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->theta_lds));
+        }
     }
-    for (double** p : {&c->d_theta, &c->d_extra, &c->d_lnprior})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    HIP_TRY(hipMalloc(&c->d_theta, (size_t)c->max_walkers * (n_params > 0 ? n_params : 1) * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_extra, (size_t)c->max_walkers * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_lnprior, (size_t)c->max_walkers * sizeof(double)));
-    c->theta_lds = theta_prep_lds_bytes(n_sky, c->n_ps, c->n_sersic, n_params);
-    if (c->theta_lds > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_theta_prep),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->theta_lds));
-    }
-    c->has_layout = true;
+    c->has_layout[field] = 1;
     return PSFMC_OK;
 }
 
@@ -2423,9 +2381,8 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
                                     const int* sky_slope_flags, const int* sersic_general_flags) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    if (!c->has_layout[field]) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = c->layouts[field];
     const int want = aux_len(L.n_sky, c->n_sersic);
     if (n_aux != 0 && n_aux != want)
         return fail(PSFMC_EINVAL, "n_aux=%d: a layout of %d skies and %d Sersics has 2 x %d + %d", n_aux, L.n_sky,
@@ -2507,10 +2464,6 @@ extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
     return PSFMC_OK;
 }
 
-static_assert(kFouModes == PSFMC_FOURIER_MODES, "mode count of include/psfmc_hip.h");
-static_assert(kSpiIn == PSFMC_SPIRAL_PARAMS, "spiral parameter count of include/psfmc_hip.h");
-static_assert(kRadIn == PSFMC_RADIAL_PARAMS, "radial parameter count of include/psfmc_hip.h");
-static_assert(kTruIn == PSFMC_TRUNC_PARAMS, "truncation parameter count of include/psfmc_hip.h");
 // psfmc_set_fourier_layout, _spiral_layout, _radial_layout and _truncation_layout: block b of field `field` with its per-Sersic tags.
 // Everything is checked before the record changes, so a refused call leaves the field as it was.
 static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const int* tags, const int* col,
@@ -2518,11 +2471,10 @@ static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const 
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
     if (n_sersic != c->n_sersic) return fail(PSFMC_EINVAL, "n_sersic=%d, the context has %d", n_sersic, c->n_sersic);
-    const AuxBlockFacts k = aux_block(c, b);
+    const AuxBlockFacts& k = kAuxBlock[b];
     if (n_sersic && (!tags || !col || !konst)) return fail(PSFMC_EINVAL, "NULL %s array", k.name);
-    const bool has = field == 0 ? c->has_layout : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    const ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    if (!c->has_layout[field]) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    const ThetaLayout& L = c->layouts[field];
     FieldAuxRecord& r = c->aux_records[field];
     bool any_here = false;
     for (int i = 0; i < n_sersic; ++i) {
@@ -2554,7 +2506,7 @@ static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const 
     // (a field's blocks are registered in table order: a call drops the blocks behind its own with their entries)
     bool behind = false;
     for (int j = b + 1; j < kAuxBlocks; ++j) behind = behind || !r.block[j].empty();
-    if (!any_here && k.masks.empty() && !behind) return layout_sync(c);    // (nothing registered, nothing to remove)
+    if (!any_here && c->blk[b].masks.empty() && !behind) return layout_sync(c);    // (nothing registered, nothing to remove)
     r.block[b].store(n_sersic, len, tags, col, konst);
     for (int j = b + 1; j < kAuxBlocks; ++j) r.block[j].clear();
     return apply_aux_record(c, field, b);
@@ -2625,10 +2577,8 @@ extern "C" int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* 
 extern "C" int psfmc_set_priors(psfmc_ctx* c, int field, int n_params, const int* family, const double* params) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    const bool has = field == 0 ? c->has_layout
-                                : (size_t)field <= c->more_has.size() && c->more_has[field - 1];
-    if (!has) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
-    ThetaLayout& L = field == 0 ? c->layout : c->more_layouts[field - 1];
+    if (!c->has_layout[field]) return fail(PSFMC_EINVAL, "field %d has no layout yet (psfmc_set_layout[_field])", field);
+    ThetaLayout& L = c->layouts[field];
     if (n_params != L.n_params)
         return fail(PSFMC_EINVAL, "%d prior columns for a layout of %d", n_params, L.n_params);
     if (n_params == 0) return PSFMC_OK;
@@ -2653,8 +2603,8 @@ extern "C" int psfmc_set_layout_field(psfmc_ctx* c, int field, int n_sky, int n_
 
 static int check_theta_call(psfmc_ctx* c, int W, const void* theta, const void* out) {
     RC_TRY(check_call(c, W, theta ? theta : out, out));
-    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
-    if (W > 0 && c->layout.n_params > 0 && !theta) return fail(PSFMC_EINVAL, "NULL theta");
+    if (!c->has_layout[0]) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    if (W > 0 && c->layouts[0].n_params > 0 && !theta) return fail(PSFMC_EINVAL, "NULL theta");
     return PSFMC_OK;
 }
 
@@ -2674,20 +2624,20 @@ static int fields_records_pass(psfmc_ctx* c, int n_seg, const int* seg_field, co
                                int* n_w) {
     *n_w = 0;
     if (!c || n_seg < 0 || (n_seg && (!seg_field || !seg_count))) return fail(PSFMC_EINVAL, "bad segment list");
-    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    if (!c->has_layout[0]) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
     long long W = 0;
     for (int i = 0; i < n_seg; ++i) {
         if (seg_count[i] < 0 || seg_field[i] < 0 || seg_field[i] >= c->n_fields)
             return fail(PSFMC_EINVAL, "segment %d: field %d, count %d", i, seg_field[i], seg_count[i]);
-        if (seg_field[i] > 0 && ((size_t)seg_field[i] > c->more_has.size() || !c->more_has[seg_field[i] - 1]))
+        if (!c->has_layout[seg_field[i]])
             return fail(PSFMC_EINVAL, "field %d has no layout (psfmc_set_layout_field)", seg_field[i]);
         W += seg_count[i];
     }
     if (W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%lld outside [0, max_walkers=%d]", W, c->max_walkers);
     if (W == 0) return PSFMC_OK;
-    if (!d_out || (c->layout.n_params > 0 && !d_theta)) return fail(PSFMC_EINVAL, "NULL buffer");
+    if (!d_out || (c->layouts[0].n_params > 0 && !d_theta)) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
-    const int P = c->layout.n_params;
+    const int P = c->layouts[0].n_params;
     int off = 0;
     for (int i = 0; i < n_seg; ++i) {
         if (!seg_count[i]) continue;
@@ -2721,16 +2671,16 @@ extern "C" int psfmc_eval_theta_device_fields(psfmc_ctx* c, int n_seg, const int
 extern "C" int psfmc_eval_theta_fields(psfmc_ctx* c, int n_seg, const int* seg_field, const int* seg_count,
                                        const double* theta, const double* extra, double* lnprob) {
     if (!c || n_seg < 0 || (n_seg && !seg_count)) return fail(PSFMC_EINVAL, "bad segment list");
-    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    if (!c->has_layout[0]) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
     long long W = 0;
     for (int i = 0; i < n_seg; ++i) W += seg_count[i] > 0 ? seg_count[i] : 0;
     if (W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%lld outside [0, max_walkers=%d]", W, c->max_walkers);
     if (W == 0) return PSFMC_OK;
-    if (!lnprob || (c->layout.n_params > 0 && !theta)) return fail(PSFMC_EINVAL, "NULL buffer");
+    if (!lnprob || (c->layouts[0].n_params > 0 && !theta)) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
     RC_TRY(psfmc_eval_theta_device_fields(c, n_seg, seg_field, seg_count, c->d_theta, extra ? c->d_extra : nullptr,
@@ -2746,16 +2696,16 @@ extern "C" int psfmc_eval_theta_split_fields(psfmc_ctx* c, int n_seg, const int*
                                              const double* theta, const double* extra, double* lnlike,
                                              double* lnprior) {
     if (!c || n_seg < 0 || (n_seg && !seg_count)) return fail(PSFMC_EINVAL, "bad segment list");
-    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    if (!c->has_layout[0]) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
     long long W = 0;
     for (int i = 0; i < n_seg; ++i) W += seg_count[i] > 0 ? seg_count[i] : 0;
     if (W > c->max_walkers) return fail(PSFMC_EINVAL, "W=%lld outside [0, max_walkers=%d]", W, c->max_walkers);
     if (W == 0) return PSFMC_OK;
-    if (!lnlike || !lnprior || (c->layout.n_params > 0 && !theta)) return fail(PSFMC_EINVAL, "NULL buffer");
+    if (!lnlike || !lnprior || (c->layouts[0].n_params > 0 && !theta)) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
     int n = 0;
@@ -2776,8 +2726,8 @@ extern "C" int psfmc_eval_theta(psfmc_ctx* c, int W, const double* theta, const 
     if (rc != PSFMC_OK || W == 0) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
     RC_TRY(eval_theta_device(c, W, c->d_theta, extra ? c->d_extra : nullptr, c->d_like, st));
@@ -2792,8 +2742,8 @@ extern "C" int psfmc_debug_theta_rows(psfmc_ctx* c, int W, const double* theta, 
     if (rc != PSFMC_OK || W == 0) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->d_rows, 0, (size_t)W * c->rlen * sizeof(double), st));
     launch_theta_prep(c, W, c->d_theta, nullptr, c->d_rows, st, StretchIn{});
@@ -2815,7 +2765,7 @@ extern "C" int psfmc_reset_accumulated(psfmc_ctx* c) {
     HIP_TRY(hipMemsetAsync(c->d_acc, 0, acc_bytes, c->stream));
     if (c->d_lin) HIP_TRY(hipMemsetAsync(c->d_lin, 0, (size_t)c->n_psf * 3 * c->S * sizeof(double), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int f = 0; f < c->n_fields; ++f) acc_n(c, f) = 0;
+    for (int f = 0; f < c->n_fields; ++f) c->acc_count[f] = 0;
     c->lin_pending = 0;
     return PSFMC_OK;
 }
@@ -2833,7 +2783,7 @@ extern "C" int psfmc_reset_accumulated_field(psfmc_ctx* c, int field) {
         HIP_TRY(hipMemsetAsync(c->d_lin + (size_t)field * c->n_psf_field * 3 * S, 0,
                                (size_t)c->n_psf_field * 3 * S * sizeof(double), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    acc_n(c, field) = 0;
+    c->acc_count[field] = 0;
     return PSFMC_OK;
 }
 
@@ -2903,7 +2853,7 @@ static int accumulate_linear(psfmc_ctx* c, int W, hipStream_t st, int f0 = 0, in
                                c->d_lin + (size_t)f0 * n_el, n_el);
         }
         c->lin_pending += W;
-        for (int i = 0; i < nf; ++i) acc_n(c, f0 + i) += per;
+        for (int i = 0; i < nf; ++i) c->acc_count[f0 + i] += per;
         return PSFMC_OK;
     }
     const size_t n_el = (size_t)c->n_psf * 3 * c->S;
@@ -2917,7 +2867,7 @@ static int accumulate_linear(psfmc_ctx* c, int W, hipStream_t st, int f0 = 0, in
     }
     hipLaunchKernelGGL(k_sum_partials, dim3(512), dim3(256), 0, st, c->d_linpart, groups, c->d_lin, n_el);
     c->lin_pending += W;
-    acc_n(c, f0) += W;
+    c->acc_count[f0] += W;
     return PSFMC_OK;
 }
 
@@ -3059,7 +3009,7 @@ static int accumulate_from_prep(psfmc_ctx* c, int W, hipStream_t st, int f0 = 0,
         }
         acc(conv_src, stride, 0, 3, n);
     }
-    c->acc_count += W;
+    c->acc_count[0] += W;
     return PSFMC_OK;
 }
 
@@ -3090,14 +3040,14 @@ static int accumulate_theta_impl(psfmc_ctx* c, int field, int W, const double* t
     int rc = check_theta_call(c, W, theta, theta ? (const void*)theta : (const void*)c);
     if (rc != PSFMC_OK || W == 0) return rc;
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    if (field > 0 && ((size_t)field > c->more_has.size() || !c->more_has[field - 1]))
+    if (!c->has_layout[field])
         return fail(PSFMC_EINVAL, "field %d has no layout (psfmc_set_layout_field)", field);
     HIP_TRY(hipSetDevice(c->device));
     if (!c->d_acc) RC_TRY(psfmc_reset_accumulated(c));
     RC_TRY(ensure_linear_sums(c));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     launch_theta_prep(c, W, c->d_theta, nullptr, nullptr, st, StretchIn{}, field, 0);
     rc = accumulate_from_prep(c, W, st, field, 1, W);
@@ -3136,18 +3086,18 @@ static int stretch_check(psfmc_ctx* c, int W, int F = 1) {
     if (F != c->n_fields)
         return fail(PSFMC_EINVAL, F == 1 ? "this entry point serves contexts of one field"
                                          : "psfmc_stretch_run_fields samples every field of the context");
-    if (!c->has_layout) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
+    if (!c->has_layout[0]) return fail(PSFMC_EINVAL, "psfmc_set_layout has not been called");
     if (W < 2 || (W & 1) || (long long)W * F > c->max_walkers)
         return fail(PSFMC_EINVAL, "W must be even and fields x W within max_walkers");
-    const int P = c->layout.n_params;
+    const int P = c->layouts[0].n_params;
     if (P < 1) return fail(PSFMC_EINVAL, "model has no free parameter");
     // every prior must be evaluated on the device
     std::vector<int> fam(P);
     HIP_TRY(hipSetDevice(c->device));
     for (int f = 0; f < F; ++f) {
-        if (f > 0 && ((size_t)f > c->more_has.size() || !c->more_has[f - 1]))
+        if (!c->has_layout[f])
             return fail(PSFMC_EINVAL, "field %d has no layout (psfmc_set_layout_field)", f);
-        const ThetaLayout& L = f == 0 ? c->layout : c->more_layouts[f - 1];
+        const ThetaLayout& L = c->layouts[f];
         HIP_TRY(hipMemcpy(fam.data(), L.family, P * sizeof(int), hipMemcpyDeviceToHost));
         for (int v : fam)
             if (v == PRIOR_HOST) return fail(PSFMC_EINVAL, "a prior is evaluated on the host; use the host sampler");
@@ -3162,7 +3112,7 @@ static int stretch_upload(psfmc_ctx* c, int W, int n_iter, const double* pos, co
                           int lnprob_valid, const double* z, const double* lz, const int* partner,
                           const double* log_u, const long long* naccepted, bool store, hipStream_t st, int F = 1) {
     psfmc_ctx::Stretch& S = c->stretch;
-    const int P = c->layout.n_params, half = W / 2;
+    const int P = c->layouts[0].n_params, half = W / 2;
     const size_t n_rand = (size_t)n_iter * W * F;             // per random array, all ensembles
     const size_t WF = (size_t)W * F;
     RC_TRY(grow(&S.pos, &S.cap_pos, WF * P));
@@ -3197,7 +3147,7 @@ static int stretch_upload(psfmc_ctx* c, int W, int n_iter, const double* pos, co
 static int stretch_download(psfmc_ctx* c, double* pos, double* lnprob, double* chain, double* lnprob_chain,
                             long long* naccepted, hipStream_t st) {
     psfmc_ctx::Stretch& S = c->stretch;
-    const int P = c->layout.n_params;
+    const int P = c->layouts[0].n_params;
     const size_t W = (size_t)S.W * S.F;
     HIP_TRY(hipMemcpyAsync(pos, S.pos, W * P * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(lnprob, S.lnp, W * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -3216,7 +3166,7 @@ static int stretch_download(psfmc_ctx* c, double* pos, double* lnprob, double* c
 // priors and prep records (every walker of the half: the accept step needs every proposal)
 static void stretch_propose(psfmc_ctx* c, int it, int h, bool graph_iter, hipStream_t st) {
     psfmc_ctx::Stretch& S = c->stretch;
-    const int half = S.W / 2, P = c->layout.n_params;
+    const int half = S.W / 2, P = c->layouts[0].n_params;
     const size_t per_field = (size_t)S.n_iter * S.W;          // random numbers of one ensemble
     launch_theta_prep(c, half, nullptr, nullptr, nullptr, st,
                       StretchIn{S.pos, S.q, S.rand, S.partner, graph_iter ? S.iter : nullptr, it, half, h,
@@ -3238,7 +3188,7 @@ static void stretch_accept(psfmc_ctx* c, int it, int h, const double* d_newlnp, 
     hipLaunchKernelGGL(k_stretch_finish, dim3(finish_blocks(half), S.F), dim3(kFinishThreads), 0, st, c->d_partial,
                        c->d_skip, c->d_lnprior, c->nblk, d_newlnp, S.pos, S.lnp, S.q, S.rand + n_rand,
                        S.rand + 2 * n_rand, S.nacc, S.store ? S.chain : nullptr, S.store ? S.lnchain : nullptr,
-                       graph_iter ? S.iter : nullptr, it, S.n_iter, half, h, c->layout.n_params, per_field,
+                       graph_iter ? S.iter : nullptr, it, S.n_iter, half, h, c->layouts[0].n_params, per_field,
                        acc_out, acc_in, S.partner, nf, half);
 }
 
@@ -3259,7 +3209,7 @@ static int stretch_end_run(psfmc_ctx* c, int rc, double* pos, double* lnprob, do
 // a whole iteration's proposals in one launch (StretchIn::spec): 3 half walkers
 static void stretch_propose_iteration(psfmc_ctx* c, int it, bool graph_iter, hipStream_t st) {
     psfmc_ctx::Stretch& S = c->stretch;
-    const int half = S.W / 2, P = c->layout.n_params;
+    const int half = S.W / 2, P = c->layouts[0].n_params;
     StretchIn sp{S.pos, S.q, S.rand, S.partner, graph_iter ? S.iter : nullptr, it, half, 0,
                  (size_t)S.W * P, (size_t)half * P, (size_t)S.n_iter * S.W, 1};
     launch_theta_prep(c, 3 * half, nullptr, nullptr, nullptr, st, sp);
@@ -3348,7 +3298,7 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
         // un-captured warm-up of the pipeline: one-time attribute calls must not fall
         // inside the capture
         rc = eval_theta_device(c, half, S.pos, nullptr, S.newlnp, st);      // (F == 1 here)
-        const long long count_before = c->acc_count, pending_before = c->lin_pending;
+        const long long count_before = c->acc_count[0], pending_before = c->lin_pending;
         if (rc == PSFMC_OK && hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             const int crc = iteration();
             const hipError_t e = hipStreamEndCapture(st, &graph);
@@ -3359,7 +3309,7 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
             it_host = 0;
         }
         (void)hipGetLastError();
-        c->acc_count = count_before;            // the captured pass did not run
+        c->acc_count[0] = count_before;            // the captured pass did not run
         c->lin_pending = pending_before;
     }
     for (int it = 0; it < n_iter && rc == PSFMC_OK; ++it) {
@@ -3368,7 +3318,7 @@ static int stretch_run_impl(psfmc_ctx* c, int F, int W, int n_iter, double* pos,
             else {
                 ++c->graph_launches;
                 if (accumulate) {
-                    c->acc_count += W;
+                    c->acc_count[0] += W;
                     if (c->backend == PSFMC_BACKEND_FUSED && c->linear_acc) c->lin_pending += W;
                 }
             }
@@ -3461,7 +3411,7 @@ static int moves_upload(psfmc_ctx* c, const int* kind, const int* partner_b, hip
 // the proposals of half `h` at iteration `it` -> S.q
 static void move_propose(psfmc_ctx* c, int it, int h, hipStream_t st) {
     psfmc_ctx::Stretch& S = c->stretch;
-    const int half = S.W / 2, P = c->layout.n_params;
+    const int half = S.W / 2, P = c->layouts[0].n_params;
     hipLaunchKernelGGL(k_move_propose, dim3((half * P + kMoveThreads - 1) / kMoveThreads), dim3(kMoveThreads), 0, st,
                        S.pos, S.q, S.kind, S.partner, S.partner_b, S.rand, it, half, h, P);
 }
@@ -3545,8 +3495,8 @@ extern "C" int psfmc_eval_theta_split(psfmc_ctx* c, int W, const double* theta, 
     if (!lnprior) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->layout.n_params)
-        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    if (c->layouts[0].n_params)
+        HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                                hipMemcpyHostToDevice, st));
     if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
     const double* d_lnpi = nullptr;
@@ -3615,7 +3565,7 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
         if (!std::isfinite(betas[t]) || (t == 0 && betas[t] != 1.0) || (t > 0 && !(betas[t] < betas[t - 1])))
             return fail(PSFMC_EINVAL, "bad temperature ladder at rung %d", t);
     if (T > 1 && betas[T - 1] != 0.0) return fail(PSFMC_EINVAL, "the last rung of the ladder must be beta = 0");
-    const int half = W / 2, P = c->layout.n_params;
+    const int half = W / 2, P = c->layouts[0].n_params;
     const int E = L * T;                          // ensembles: ensemble e = l T + t is rung t of ladder l
     const size_t TW = (size_t)E * W, n_rand = (size_t)n_iter * TW,
                  n_swap = swaps ? (size_t)n_iter * L * (T - 1) * W : 0;
@@ -3782,9 +3732,7 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
 extern "C" int psfmc_set_joint_priors(psfmc_ctx* c, int n_params, const int* family, const double* params) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     for (int f = 0; f < c->n_fields; ++f) {
-        const bool has = f == 0 ? c->has_layout : (size_t)f <= c->more_has.size() && c->more_has[f - 1];
-        const ThetaLayout& L = f == 0 ? c->layout : c->more_layouts[f - 1];
-        if (!has || L.n_params != n_params)
+        if (!c->has_layout[f] || c->layouts[f].n_params != n_params)
             return fail(PSFMC_EINVAL, "field %d has no layout of %d columns (psfmc_set_layout[_field] first)", f,
                         n_params);
     }
@@ -3813,11 +3761,11 @@ extern "C" int psfmc_set_joint_priors(psfmc_ctx* c, int n_params, const int* fam
     J.prior.pa = dp; J.prior.pb = dp + P; J.prior.pc = dp + 2 * P; J.prior.pd = dp + 3 * P; J.prior.pk = dp + 4 * P;
     // each field's layout blob (set_layout_impl: int tables from slot_col on, then the double tables) copied,
     // its prior families set to PRIOR_HOST
-    const int ns = n_slots(c->layout.n_sky, c->n_ps, c->n_sersic);
+    const int ns = n_slots(c->layouts[0].n_sky, c->n_ps, c->n_sersic);
     const size_t int_bytes = (((size_t)ns + c->n_ps + c->n_sersic + P) * sizeof(int) + 7) / 8 * 8;
     const size_t bytes = int_bytes + ((size_t)ns + 5 * (size_t)P) * sizeof(double);
     for (int f = 0; f < c->n_fields; ++f) {
-        const ThetaLayout& L = f == 0 ? c->layout : c->more_layouts[f - 1];
+        const ThetaLayout& L = c->layouts[f];
         const unsigned char* old_base = reinterpret_cast<const unsigned char*>(L.slot_col);
         void* copy = nullptr;
         HIP_TRY(hipMalloc(&copy, bytes));
@@ -3871,7 +3819,7 @@ extern "C" int psfmc_eval_theta_joint(psfmc_ctx* c, int W, const double* theta, 
     if (!theta || !lnprob) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                            hipMemcpyHostToDevice, st));
     RC_TRY(eval_theta_joint(c, W, c->d_theta, c->d_like, st));
     HIP_TRY(hipMemcpyAsync(lnprob, c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -3888,7 +3836,7 @@ extern "C" int psfmc_eval_theta_joint_split(psfmc_ctx* c, int W, const double* t
     if (!theta || !lnlike || !lnprior) return fail(PSFMC_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layout.n_params * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(c->d_theta, theta, (size_t)W * c->layouts[0].n_params * sizeof(double),
                            hipMemcpyHostToDevice, st));
     const double* d_lnpi = nullptr;
     RC_TRY(eval_theta_split_device(c, true, W, c->d_theta, nullptr, c->d_like, &d_lnpi, st));
@@ -4079,7 +4027,7 @@ extern "C" int psfmc_stretch_accumulate(psfmc_ctx* c, int lo, int n, void* strea
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     RC_TRY(stretch_prepare_accumulation(c));
-    launch_theta_prep(c, n, S.pos + (size_t)lo * c->layout.n_params, nullptr, nullptr, st, StretchIn{});
+    launch_theta_prep(c, n, S.pos + (size_t)lo * c->layouts[0].n_params, nullptr, nullptr, st, StretchIn{});
     RC_TRY(accumulate_from_prep(c, n, st));
     HIP_TRY(hipGetLastError());
     return PSFMC_OK;
@@ -4104,7 +4052,7 @@ extern "C" int psfmc_get_accumulated_sums(psfmc_ctx* c, double* sums, long long*
     if (c->n_fields > 1) return fail(PSFMC_EINVAL, "this entry point serves contexts of one field");
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(flush_linear_sums(c));
-    *count = c->acc_count;
+    *count = c->acc_count[0];
     const WrapDesc& wr = c->wraps[0];
     const size_t S_img = img_pixels(c, 0);
     if (!c->d_acc) { memset(sums, 0, 4 * S_img * sizeof(double)); return PSFMC_OK; }
@@ -4141,7 +4089,7 @@ extern "C" int psfmc_set_accumulated_sums(psfmc_ctx* c, const double* sums, long
                        sums + k * S_img + (size_t)y * wr.lx, (size_t)wr.lx * sizeof(double));
         HIP_TRY(hipMemcpy(c->d_acc, full.data(), full.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    c->acc_count = count;
+    c->acc_count[0] = count;
     return PSFMC_OK;
 }
 
@@ -4149,7 +4097,7 @@ static int get_accumulated_impl(psfmc_ctx* c, int field, double* raw, double* co
                                 double* ps_sub, long long* count) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
-    const long long n = acc_n(c, field);
+    const long long n = c->acc_count[field];
     if (count) *count = n;
     if (n == 0 || !c->d_acc) return PSFMC_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -4293,32 +4241,32 @@ extern "C" int psfmc_group_set_aux_layout(psfmc_group* g, int n_aux, const int* 
     return PSFMC_OK;
 }
 
+// block b of the one field of every context of the group
+static int group_set_block_layout(psfmc_group* g, int b, int n_sersic, const int* tags, const int* col,
+                                  const double* konst) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx) RC_TRY(set_block_layout(c, b, 0, n_sersic, tags, col, konst));
+    return PSFMC_OK;
+}
+
 extern "C" int psfmc_group_set_fourier_layout(psfmc_group* g, int n_sersic, const int* mode_mask, const int* col,
                                               const double* konst) {
-    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
-    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_fourier_layout(c, 0, n_sersic, mode_mask, col, konst));
-    return PSFMC_OK;
+    return group_set_block_layout(g, kBlkFou, n_sersic, mode_mask, col, konst);
 }
 
 extern "C" int psfmc_group_set_spiral_layout(psfmc_group* g, int n_sersic, const int* flags, const int* col,
                                              const double* konst) {
-    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
-    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_spiral_layout(c, 0, n_sersic, flags, col, konst));
-    return PSFMC_OK;
+    return group_set_block_layout(g, kBlkSpi, n_sersic, flags, col, konst);
 }
 
 extern "C" int psfmc_group_set_radial_layout(psfmc_group* g, int n_sersic, const int* kinds, const int* col,
                                              const double* konst) {
-    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
-    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_radial_layout(c, 0, n_sersic, kinds, col, konst));
-    return PSFMC_OK;
+    return group_set_block_layout(g, kBlkRad, n_sersic, kinds, col, konst);
 }
 
 extern "C" int psfmc_group_set_truncation_layout(psfmc_group* g, int n_sersic, const int* flags, const int* col,
                                                  const double* konst) {
-    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
-    for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_truncation_layout(c, 0, n_sersic, flags, col, konst));
-    return PSFMC_OK;
+    return group_set_block_layout(g, kBlkTru, n_sersic, flags, col, konst);
 }
 
 extern "C" int psfmc_group_set_general_mean(psfmc_group* g, int n_sersic, const int* flags) {
@@ -4359,7 +4307,7 @@ static int group_eval(psfmc_group* g, int W, const double* rows, const uint8_t* 
             RC_TRY(eval_device(c, w, c->d_rows, skip ? c->d_skip : nullptr, c->d_like, st));
         } else {
             RC_TRY(check_theta_call(c, w, theta, out));
-            const int P = c->layout.n_params;
+            const int P = c->layouts[0].n_params;
             if (P) HIP_TRY(hipMemcpyAsync(c->d_theta, theta + (size_t)lo * P, (size_t)w * P * sizeof(double),
                                           hipMemcpyHostToDevice, st));
             if (extra) HIP_TRY(hipMemcpyAsync(c->d_extra, extra + lo, (size_t)w * sizeof(double),

@@ -434,14 +434,15 @@ FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude an
 SPIRAL_PARAMS = 6          # PSFMC_SPIRAL_PARAMS: r_in, r_out, winding, alpha, inclination, sky angle
 RADIAL_PARAMS = 2          # PSFMC_RADIAL_PARAMS: (beta, unused) of a Moffat slot, (alpha, beta) of a Ferrer slot
 TRUNC_PARAMS = 4           # PSFMC_TRUNC_PARAMS: in_lo, in_hi, out_lo, out_hi of a slot (flag bit 0 inner, bit 1 outer)
-# the blocks behind the aux entries: name -> (entries per Sersic, the per-Sersic tags are flags)
+# the blocks behind the aux entries, in table order: name -> (entries per Sersic, the per-Sersic tags are flags)
 _BLOCKS = {'fourier': (2 * FOURIER_MODES, False), 'spiral': (SPIRAL_PARAMS, True), 'radial': (RADIAL_PARAMS, False),
            'truncation': (TRUNC_PARAMS, False)}
 
 
-def _block_layout_args(name, per_sersic, tags, col, const, tags_are_flags):
+def _block_args(name, tags, col, const):
     """The arrays of psfmc_set_<name>_layout (kept alive by the caller's tuple) and their ctypes pointers: per
-    Sersic a tag -- mode mask, spiral flag, radial kind, truncation sides -- and `per_sersic` entries."""
+    Sersic a tag -- mode mask, spiral flag, radial kind, truncation sides -- and the block's entries."""
+    per_sersic, tags_are_flags = _BLOCKS[name]
     i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
     tags = i32(np.asarray(tags, dtype=bool) if tags_are_flags else tags)
     col, const = i32(col), _f64(const).ravel()
@@ -451,8 +452,33 @@ def _block_layout_args(name, per_sersic, tags, col, const, tags_are_flags):
     return (tags, col, const), (len(tags), ipt(tags), ipt(col), _dp(const))
 
 
-def _block_args(name, tags, col, const):
-    return _block_layout_args(name, _BLOCKS[name][0], tags, col, const, _BLOCKS[name][1])
+class _BlockLayouts(object):
+    """The four block layout calls of a context, a field of a set and a group: each class has
+    `_set_block(name, tags, col, const)`, psfmc_[group_]set_<name>_layout on what it stands for."""
+
+    def set_fourier_layout(self, mode_masks, col, const):
+        """Azimuthal Fourier modes (psfmc_set_fourier_layout; after `set_aux_layout`): per Sersic a mask of its
+        modes (bit m - 1: mode m) and, per Sersic and mode 1 ... 6, an amplitude and a phase entry -- column of theta
+        or -1 and a constant.  A context that never gets the call is what it was without it."""
+        self._set_block('fourier', mode_masks, col, const)
+
+    def set_spiral_layout(self, flags, col, const):
+        """Spiral arms (psfmc_set_spiral_layout; after `set_aux_layout` and `set_fourier_layout`): per Sersic a flag
+        and six entries -- r_in, r_out, winding, alpha, inclination, sky angle; column of theta or -1 and a
+        constant.  A context that never gets the call is what it was without it."""
+        self._set_block('spiral', flags, col, const)
+
+    def set_radial_layout(self, kinds, col, const):
+        """Radial laws (psfmc_set_radial_layout; behind the spiral layout): per Sersic slot a kind -- 0 Sersic,
+        1 Moffat, 2 Ferrer -- and two entries, (beta, unused) or (alpha, beta); column of theta or -1 and a
+        constant.  A context that never gets the call is what it was without it."""
+        self._set_block('radial', kinds, col, const)
+
+    def set_truncation_layout(self, flags, col, const):
+        """Truncations (psfmc_set_truncation_layout; behind the radial layout): per Sersic slot the sides -- bit 0
+        inner, bit 1 outer -- and four entries, in_lo, in_hi, out_lo, out_hi; column of theta or -1 and a constant.
+        A context that never gets the call is what it was without it."""
+        self._set_block('truncation', flags, col, const)
 
 
 def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
@@ -505,28 +531,24 @@ def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radia
     if base is not None:
         keep.append(_aux_layout_args(base[0], base[1], np.zeros(n_sky), np.zeros(n_sersic)))
         args = list(keep[-1][1][1:3])
-    for name, block in (('fourier', fourier), ('spiral', spiral), ('radial', radial)):
+    for name, block in zip(_BLOCKS, (fourier, spiral, radial, truncation)):
         if block is not None:
             keep.append(_block_args(name, *block))
         args += [None, None, None] if block is None else list(keep[-1][1][1:])
     n_max = 2 * n_sky + (1 + sum(per for per, _ in _BLOCKS.values())) * n_sersic
     const, col = np.full(n_max, np.nan), np.full(n_max, -2, dtype=np.int32)
-    kinds, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(4, dtype=np.int32)
+    kinds, sides = np.full(n_sersic, -2, dtype=np.int32), np.full(n_sersic, -2, dtype=np.int32)
+    counts = np.zeros(5, dtype=np.int32)
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    if truncation is not None:
-        keep.append(_block_args('truncation', *truncation))
-        sides, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(5, dtype=np.int32)
-        rc = lib.psfmc_debug_aux_table_blocks(int(n_sky), int(n_sersic), *(
-            args + list(keep[-1][1][1:]) + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(counts)]))
-    else:
-        rc = lib.psfmc_debug_aux_table(int(n_sky), int(n_sersic), *(args + [_dp(const), ipt(col), ipt(kinds), ipt(counts)]))
+    rc = lib.psfmc_debug_aux_table_blocks(int(n_sky), int(n_sersic), *(
+        args + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(counts)]))
     if rc != 0:
         raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
     n_aux = int(counts[0])
     out = (const[:n_aux], col[:n_aux], kinds[:n_sersic if counts[3] else 0])
-    if truncation is not None:
-        out += (sides[:n_sersic if counts[4] else 0],)
-    return out + (tuple(int(n) for n in counts),)
+    if truncation is None:
+        return out + (tuple(int(n) for n in counts[:4]),)
+    return out + (sides[:n_sersic if counts[4] else 0], tuple(int(n) for n in counts))
 
 
 def debug_sweep(mode, nbytes, reps=20, device=0):
@@ -552,7 +574,7 @@ def debug_valu_rate(waves_per_simd=2, iters=20000, device=0):
     return float(out.value)
 
 
-class Context(object):
+class Context(_BlockLayouts):
     """One observed field resident on one GPU (wraps `psfmc_ctx`)."""
 
     IMAGE_KINDS = ('raw_model', 'convolved_model', 'residual', 'composite_ivm',
@@ -703,33 +725,9 @@ class Context(object):
         keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
         self._check(self._lib.psfmc_set_aux_layout(self._ctx, 0, *args))
 
-    def set_fourier_layout(self, mode_masks, col, const):
-        """Azimuthal Fourier modes (psfmc_set_fourier_layout; after `set_aux_layout`): per Sersic a mask of its
-        modes (bit m - 1: mode m) and, per Sersic and mode 1 ... 6, an amplitude and a phase entry -- column of theta
-        or -1 and a constant.  A context that never gets the call is what it was without it."""
-        keep, args = _block_args('fourier', mode_masks, col, const)
-        self._check(self._lib.psfmc_set_fourier_layout(self._ctx, 0, *args))
-
-    def set_spiral_layout(self, flags, col, const):
-        """Spiral arms (psfmc_set_spiral_layout; after `set_aux_layout` and `set_fourier_layout`): per Sersic a flag
-        and six entries -- r_in, r_out, winding, alpha, inclination, sky angle; column of theta or -1 and a
-        constant.  A context that never gets the call is what it was without it."""
-        keep, args = _block_args('spiral', flags, col, const)
-        self._check(self._lib.psfmc_set_spiral_layout(self._ctx, 0, *args))
-
-    def set_radial_layout(self, kinds, col, const):
-        """Radial laws (psfmc_set_radial_layout; the last of the layout calls): per Sersic slot a kind -- 0 Sersic,
-        1 Moffat, 2 Ferrer -- and two entries, (beta, unused) or (alpha, beta); column of theta or -1 and a
-        constant.  A context that never gets the call is what it was without it."""
-        keep, args = _block_args('radial', kinds, col, const)
-        self._check(self._lib.psfmc_set_radial_layout(self._ctx, 0, *args))
-
-    def set_truncation_layout(self, flags, col, const):
-        """Truncations (psfmc_set_truncation_layout; behind the radial layout): per Sersic slot the sides -- bit 0
-        inner, bit 1 outer -- and four entries, in_lo, in_hi, out_lo, out_hi; column of theta or -1 and a constant.
-        A context that never gets the call is what it was without it."""
-        keep, args = _block_args('truncation', flags, col, const)
-        self._check(self._lib.psfmc_set_truncation_layout(self._ctx, 0, *args))
+    def _set_block(self, name, tags, col, const):
+        keep, args = _block_args(name, tags, col, const)
+        self._check(getattr(self._lib, 'psfmc_set_%s_layout' % name)(self._ctx, 0, *args))
 
     def set_general_mean(self, flags):
         """Which general Sersic slots (model-file order) are rendered as the mean of their law over each pixel
@@ -1030,7 +1028,7 @@ class FieldSetContext(object):
         """An object with the `set_layout` of a Context that registers field `field`'s layout."""
         owner = self
 
-        class _Proxy(object):
+        class _Proxy(_BlockLayouts):
             def set_layout(self, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees,
                            mag_zeropoint, family, p0, p1, p2):
                 i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
@@ -1057,21 +1055,9 @@ class FieldSetContext(object):
                 keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
                 owner._check(owner._lib.psfmc_set_aux_layout(owner._ctx, int(field), *args))
 
-            def set_fourier_layout(self, mode_masks, col, const):
-                keep, args = _block_args('fourier', mode_masks, col, const)
-                owner._check(owner._lib.psfmc_set_fourier_layout(owner._ctx, int(field), *args))
-
-            def set_spiral_layout(self, flags, col, const):
-                keep, args = _block_args('spiral', flags, col, const)
-                owner._check(owner._lib.psfmc_set_spiral_layout(owner._ctx, int(field), *args))
-
-            def set_radial_layout(self, kinds, col, const):
-                keep, args = _block_args('radial', kinds, col, const)
-                owner._check(owner._lib.psfmc_set_radial_layout(owner._ctx, int(field), *args))
-
-            def set_truncation_layout(self, flags, col, const):
-                keep, args = _block_args('truncation', flags, col, const)
-                owner._check(owner._lib.psfmc_set_truncation_layout(owner._ctx, int(field), *args))
+            def _set_block(self, name, tags, col, const):
+                keep, args = _block_args(name, tags, col, const)
+                owner._check(getattr(owner._lib, 'psfmc_set_%s_layout' % name)(owner._ctx, int(field), *args))
 
             def set_general_mean(self, flags):
                 flags = np.ascontiguousarray(np.asarray(flags, dtype=bool), dtype=np.int32)
@@ -1471,7 +1457,7 @@ class JointView(object):
         raise AttributeError(name)
 
 
-class ContextGroup(object):
+class ContextGroup(_BlockLayouts):
     """One observed field replicated on several GPUs driven by THIS process (wraps
     `psfmc_group`): walkers are split into contiguous blocks, one per listed device.
     The one-process-per-GPU form (torch.distributed / RCCL) is `psfmc_amd.parallel`."""
@@ -1539,25 +1525,10 @@ class ContextGroup(object):
         keep, args = _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags)
         self._check(self._lib.psfmc_group_set_aux_layout(self._grp, *args))
 
-    def set_fourier_layout(self, mode_masks, col, const):
-        """`Context.set_fourier_layout` on every device of the group."""
-        keep, args = _block_args('fourier', mode_masks, col, const)
-        self._check(self._lib.psfmc_group_set_fourier_layout(self._grp, *args))
-
-    def set_spiral_layout(self, flags, col, const):
-        """`Context.set_spiral_layout` on every device of the group."""
-        keep, args = _block_args('spiral', flags, col, const)
-        self._check(self._lib.psfmc_group_set_spiral_layout(self._grp, *args))
-
-    def set_radial_layout(self, kinds, col, const):
-        """`Context.set_radial_layout` on every device of the group."""
-        keep, args = _block_args('radial', kinds, col, const)
-        self._check(self._lib.psfmc_group_set_radial_layout(self._grp, *args))
-
-    def set_truncation_layout(self, flags, col, const):
-        """`Context.set_truncation_layout` on every device of the group."""
-        keep, args = _block_args('truncation', flags, col, const)
-        self._check(self._lib.psfmc_group_set_truncation_layout(self._grp, *args))
+    def _set_block(self, name, tags, col, const):
+        """The block's layout call (`_BlockLayouts`) on every device of the group."""
+        keep, args = _block_args(name, tags, col, const)
+        self._check(getattr(self._lib, 'psfmc_group_set_%s_layout' % name)(self._grp, *args))
 
     def set_general_mean(self, flags):
         """`Context.set_general_mean` on every device of the group."""

@@ -34,6 +34,25 @@ _DEVICE_FAMILIES = {
 # spiral entries (r_in, r_out, winding, alpha, inclination, sky angle) of a Sersic component without the keyword:
 # inside the support, never read
 _SPIRAL_ABSENT = (0.0, 1.0, 0.0, 0.0, 0.0, 0.0)
+# The four blocks behind the aux entries, in table order (engine._BLOCKS; include/psfmc_hip.h psfmc_set_<name>_layout):
+# the model property with the per-Sersic tags, and a Sersic slot's entries -- each the name of a parameter as declared,
+# or the constant an absent one holds (neutral, or inside the support of what never reads it).  A block is registered,
+# after the aux layout and in this order, only by a model with a tag set; a block in a walker's auxiliary row forces
+# those before it.
+_AUX_BLOCKS = (
+    # per mode 1 ... 6 an amplitude and a phase
+    ('fourier', 'sersic_fourier_masks', lambda c: [
+        name if m in c.fourier_modes else 0.0 for m in Sersic.FOURIER_MODES for name in ('f%d_amp' % m, 'f%d_phase' % m)]),
+    # r_in, r_out, winding, alpha, inclination, sky angle
+    ('spiral', 'sersic_spiral_flags', lambda c: list(Sersic.SPIRAL_ATTRS if c.has_spiral else _SPIRAL_ABSENT)),
+    # (beta, unused) of a `Moffat`, (alpha, beta) of a `Ferrer`
+    ('radial', 'sersic_radial_kinds', lambda c: (
+        list(c.LAW_ATTRS if c.radial_law else ()) + [0.0] * Sersic.RADIAL_PARAMS)[:Sersic.RADIAL_PARAMS]),
+    # in_lo, in_hi, out_lo, out_hi; flag bit 0 the inner side, bit 1 the outer
+    ('truncation', 'sersic_truncation_flags', lambda c: [
+        attr if (getattr(c, 'truncation_flags', 0) >> (j // 2)) & 1 else absent
+        for j, (attr, absent) in enumerate(zip(Sersic.TRUNC_ATTRS, Sersic.TRUNC_ABSENT))]),
+)
 _FIRST_NEW_FAMILY = 5           # psfmc_set_layout takes families 0-4; the rest go through psfmc_set_priors
 
 
@@ -244,71 +263,29 @@ class MultiComponentModel(object):
                 slot_col.append(-1); slot_const.append(0.0)
         aux_col, aux_const = slot_col[n_main:], slot_const[n_main:]
         slot_col, slot_const = slot_col[:n_main], slot_const[:n_main]
-        # azimuthal Fourier modes (Sersic `fourier`): per Sersic and mode 1 ... 6 an amplitude and a phase entry, a
-        # mode that is absent two neutral constants; registered after the aux layout, and only by a model with modes
-        n_before = len(slot_col)
-        for c in self._sersic:
-            for m in Sersic.FOURIER_MODES:
-                if m in c.fourier_modes:
-                    add(c, 'f%d_amp' % m); add(c, 'f%d_phase' % m)
-                else:
-                    slot_col += [-1, -1]; slot_const += [0.0, 0.0]
-        fou_col, fou_const = slot_col[n_before:], slot_const[n_before:]
-        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
-        # spiral arms (Sersic `spiral`): per Sersic r_in, r_out, winding, alpha, inclination, sky angle as declared; a
-        # component without the keyword gets constants inside the support that are never read; registered after the
-        # aux and Fourier layouts, and only by a model with the keyword
-        for c in self._sersic:
-            if c.has_spiral:
-                for attr in Sersic.SPIRAL_ATTRS:
-                    add(c, attr)
-            else:
-                slot_col += [-1] * 6; slot_const += list(_SPIRAL_ABSENT)
-        spi_col, spi_const = slot_col[n_before:], slot_const[n_before:]
-        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
-        # radial laws (`Moffat`, `Ferrer`): per Sersic slot the law's two entries as declared -- (beta, unused) or
-        # (alpha, beta) -- a slot with the Sersic law two constants that are never read; registered last, and only by
-        # a model with such a component
-        for c in self._sersic:
-            if c.radial_law:
-                for attr in c.LAW_ATTRS:
-                    add(c, attr)
-                pad = Sersic.RADIAL_PARAMS - len(c.LAW_ATTRS)
-                slot_col += [-1] * pad; slot_const += [0.0] * pad
-            else:
-                slot_col += [-1] * Sersic.RADIAL_PARAMS; slot_const += [0.0] * Sersic.RADIAL_PARAMS
-        rad_col, rad_const = slot_col[n_before:], slot_const[n_before:]
-        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
-        # truncations (`truncation`): per Sersic slot in_lo, in_hi, out_lo, out_hi as declared, an absent side (and a
-        # slot without the keyword) constants inside the support that are never read; registered behind the laws, and
-        # only by a model with the keyword
-        for c in self._sersic:
-            flags = getattr(c, 'truncation_flags', 0)
-            for j, (attr, absent) in enumerate(zip(Sersic.TRUNC_ATTRS, Sersic.TRUNC_ABSENT)):
-                if (flags >> (j // 2)) & 1:
-                    add(c, attr)
-                else:
-                    slot_col.append(-1); slot_const.append(absent)
-        tru_col, tru_const = slot_col[n_before:], slot_const[n_before:]
-        slot_col, slot_const = slot_col[:n_before], slot_const[:n_before]
+        # the blocks behind them (_AUX_BLOCKS): a declared entry its column or constant, an absent one its constant
+        blocks = []                                   # (name, tags, col, const)
+        for name, tags, entries in _AUX_BLOCKS:
+            n_before = len(slot_col)
+            for c in self._sersic:
+                for entry in entries(c):
+                    if isinstance(entry, str):
+                        add(c, entry)
+                    else:
+                        slot_col.append(-1); slot_const.append(entry)
+            blocks.append((name, getattr(self, tags), slot_col[n_before:], slot_const[n_before:]))
+            del slot_col[n_before:], slot_const[n_before:]
         if columns is not None:
             aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
-            fou_col = [int(columns[c]) if c >= 0 else -1 for c in fou_col]
-            spi_col = [int(columns[c]) if c >= 0 else -1 for c in spi_col]
-            rad_col = [int(columns[c]) if c >= 0 else -1 for c in rad_col]
-            tru_col = [int(columns[c]) if c >= 0 else -1 for c in tru_col]
+            blocks = [(name, tags, [int(columns[c]) if c >= 0 else -1 for c in col], const)
+                      for name, tags, col, const in blocks]
 
         def register_aux():
             if self.has_aux:
                 eng.set_aux_layout(aux_col, aux_const, self.sky_slope_flags, self.sersic_general_flags)
-            if any(self.sersic_fourier_masks):
-                eng.set_fourier_layout(self.sersic_fourier_masks, fou_col, fou_const)
-            if any(self.sersic_spiral_flags):
-                eng.set_spiral_layout(self.sersic_spiral_flags, spi_col, spi_const)
-            if any(self.sersic_radial_kinds):
-                eng.set_radial_layout(self.sersic_radial_kinds, rad_col, rad_const)
-            if any(self.sersic_truncation_flags):
-                eng.set_truncation_layout(self.sersic_truncation_flags, tru_col, tru_const)
+            for name, tags, col, const in blocks:
+                if any(tags):
+                    getattr(eng, 'set_%s_layout' % name)(tags, col, const)
             # which general components are rendered as the mean over each pixel (`pixel_mean=True`): flags, no
             # entries; the last call, and only by a model with the keyword
             if any(self.sersic_general_mean):
@@ -404,33 +381,13 @@ class MultiComponentModel(object):
             if isinstance(c, Sersic):
                 cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
-        trunc = any(self.sersic_truncation_flags)
-        laws = any(self.sersic_radial_kinds) or trunc
-        if any(self.sersic_fourier_masks) or any(self.sersic_spiral_flags) or laws:
+        present = [any(getattr(self, tags)) for _, tags, _ in _AUX_BLOCKS]
+        for _, _, entries in _AUX_BLOCKS[:max([0] + [b + 1 for b, p in enumerate(present) if p])]:
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
-                    vals = c.values_batch(theta[:, s]) if c.fourier_modes else {}
-                    for m in Sersic.FOURIER_MODES:
-                        for key in ('f%d_amp' % m, 'f%d_phase' % m):
-                            cols.append(np.reshape(vals[key], (n_w,)) if m in c.fourier_modes else np.zeros(n_w))
-        if any(self.sersic_spiral_flags) or laws:
-            for c, s in zip(self.components, self._spans):
-                if isinstance(c, Sersic):
-                    vals = c.values_batch(theta[:, s]) if c.has_spiral else {}
-                    for attr, absent in zip(Sersic.SPIRAL_ATTRS, _SPIRAL_ABSENT):
-                        cols.append(np.reshape(vals[attr], (n_w,)) if c.has_spiral else np.full(n_w, absent))
-        if laws:
-            for c, s in zip(self.components, self._spans):
-                if isinstance(c, Sersic):
-                    pars = (c._radial_values(c.values_batch(theta[:, s]), n_w) if c.radial_law
-                            else np.zeros((n_w, Sersic.RADIAL_PARAMS)))
-                    cols += [pars[:, j] for j in range(Sersic.RADIAL_PARAMS)]
-        if trunc:
-            for c, s in zip(self.components, self._spans):
-                if isinstance(c, Sersic):
-                    pars = (c._truncation_values(c.values_batch(theta[:, s]), n_w) if c.has_truncation
-                            else np.tile(Sersic.TRUNC_ABSENT, (n_w, 1)))
-                    cols += [pars[:, j] for j in range(Sersic.TRUNC_PARAMS)]
+                    ents = entries(c)
+                    vals = c.values_batch(theta[:, s]) if any(isinstance(e, str) for e in ents) else {}
+                    cols += [np.reshape(vals[e], (n_w,)) if isinstance(e, str) else np.full(n_w, e) for e in ents]
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
     @staticmethod
