@@ -634,6 +634,44 @@ int psfmc_pt_run_fields(psfmc_ctx* ctx, int T, int W, int n_iter, const double* 
                         long long* naccepted, long long* nswap, int accumulate);
 
 /*
+ * Proposal moves on tempered ladders (the contract is TemperedEnsembleSampler.set_moves): psfmc_pt_run,
+ * psfmc_pt_run_joint and psfmc_pt_run_fields with the move of every iteration named, as psfmc_move_run names
+ * it for one ensemble.  The arguments are the twin's plus, behind log_u,
+ *     kind        [n_iter] (psfmc_pt_move_run_fields: [n_iter][F], each field's ladder its own move)
+ *                 PSFMC_MOVE_STRETCH or PSFMC_MOVE_DE: the move of BOTH half-steps of EVERY rung of the ladder
+ *     partner_b   shaped as partner: the DE moves' second partner, from the same rung's other half; not read
+ *                 in a stretch iteration
+ * and z carries the move's scalar (z, or the DE g), lz its Hastings term ((P - 1) ln z, or 0), partner the
+ * first partner.  Per half-step: ONE proposal launch by kind over all rungs' (and ladders') records
+ * (k_pt_move_propose; a DE element is three roundings: the difference, the product, the sum), the records of
+ * the given vectors (a joint fit: the joint prior launch and the F fields' record launch), the pipeline pass and
+ * the twin's accept launch; swaps, chains, counters and accumulate are the twin's.  One launch more per
+ * half-step than psfmc_pt_run and psfmc_pt_run_joint, none more than psfmc_pt_run_fields.  With T = 1 and betas
+ * = {1}, psfmc_pt_move_run_fields is the moves run of a field set's plain ensembles.
+ * PSFMC_EINVAL, with a psfmc_last_error text and before anything is uploaded, for everything the twin refuses
+ * and for: a NULL kind or partner_b, a kind that is no move code, W < 4 in a DE iteration, and in a DE
+ * iteration a partner_b outside [0, W/2) or equal to partner.
+ */
+int psfmc_pt_move_run(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos, double* lnlike,
+                      double* lnprior, int state_valid, const double* z, const double* lz, const int* partner,
+                      const double* log_u, const int* kind, const int* partner_b, const int* swap_i,
+                      const int* swap_j, const double* swap_log_u, double* chain, double* lnprob_chain,
+                      double* lnlike_chain, double* lnprior_chain, long long* naccepted, long long* nswap,
+                      int accumulate);
+int psfmc_pt_move_run_joint(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos,
+                            double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                            const int* partner, const double* log_u, const int* kind, const int* partner_b,
+                            const int* swap_i, const int* swap_j, const double* swap_log_u, double* chain,
+                            double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                            long long* naccepted, long long* nswap, int accumulate);
+int psfmc_pt_move_run_fields(psfmc_ctx* ctx, int T, int W, int n_iter, const double* betas, double* pos,
+                             double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                             const int* partner, const double* log_u, const int* kind, const int* partner_b,
+                             const int* swap_i, const int* swap_j, const double* swap_log_u, double* chain,
+                             double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                             long long* naccepted, long long* nswap, int accumulate);
+
+/*
  * The same sampler one half-step at a time, for walkers sharded over several GPUs (one
  * process per GPU).  Every rank opens the SAME ensemble with the SAME
  * random numbers; per half-step each rank calls psfmc_stretch_half_eval for its contiguous

@@ -3525,14 +3525,17 @@ static int eval_fields_split_device(psfmc_ctx* c, int n_seg, int per, const doub
 // every field's records.  Fields: every field of the context has its own ladder -- L = n_fields ladders, L T
 // ensembles; the host arrays carry the field as their leading dimension, the random numbers behind the
 // iteration (and half-step); proposals by k_pt_fields_propose, records by ONE k_theta_prep launch over the fields.
+// kind, partner_b (psfmc_pt_move_run*; both null: none of this): every mode proposes by kind with k_pt_move_propose.
 enum PtMode { PT_ONE, PT_JOINT, PT_FIELDS };
 static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, const double* betas, double* pos,
                        double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
                        const int* partner, const double* log_u, const int* swap_i, const int* swap_j,
                        const double* swap_log_u, double* chain, double* lnprob_chain, double* lnlike_chain,
-                       double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate) {
+                       double* lnprior_chain, long long* naccepted, long long* nswap, int accumulate,
+                       const int* kind = nullptr, const int* partner_b = nullptr) {
     if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
     const bool joint = mode == PT_JOINT, fields = mode == PT_FIELDS;
+    const bool moves = kind || partner_b;         // (psfmc_pt_move_run*: proposals by kind)
     const int F = joint ? c->n_fields : 1;        // field records per walker
     const int L = fields ? c->n_fields : 1;       // ladders
     if (fields) {
@@ -3558,7 +3561,8 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
     }
     const bool swaps = T > 1 && n_iter > 0;
     if (n_iter < 0 || !betas || !pos || !lnlike || !lnprior || !naccepted || (T > 1 && !nswap) ||
-        (n_iter && (!z || !lz || !partner || !log_u)) || (swaps && (!swap_i || !swap_j || !swap_log_u)))
+        (n_iter && (!z || !lz || !partner || !log_u)) || (swaps && (!swap_i || !swap_j || !swap_log_u)) ||
+        (moves && n_iter && (!kind || !partner_b)))
         return fail(PSFMC_EINVAL, "NULL buffer");
     // the ladder: finite, beta_0 = 1, strictly decreasing, the last rung 0 (the evidence needs the prior rung)
     for (int t = 0; t < T; ++t)
@@ -3577,6 +3581,28 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
                             (int)(i / half % E / T));
             return fail(PSFMC_EINVAL, "partner index %d outside [0, %d)", partner[i], half);
         }
+    // the moves: kind [n_iter][L] a move code; a DE iteration of a ladder needs W >= 4 and, in both half-steps of
+    // every rung, a second partner in range and distinct from the first (partner_b is not read otherwise)
+    for (size_t k = 0; moves && k < (size_t)n_iter * L; ++k) {
+        const int it = (int)(k / L), l = (int)(k % L);
+        if (kind[k] != MOVE_STRETCH && kind[k] != MOVE_DE)
+            return fail(PSFMC_EINVAL, "kind[%d] = %d is not a move (0 stretch, 1 differential evolution)", (int)k,
+                        kind[k]);
+        if (kind[k] != MOVE_DE) continue;
+        if (W < 4)
+            return fail(PSFMC_EINVAL, "a differential-evolution move needs W >= 4 (two distinct partners in each "
+                        "half-ensemble); W = %d", W);
+        for (int h = 0; h < 2; ++h)
+            for (int j = 0; j < T * half; ++j) {
+                const size_t i = (((size_t)it * 2 + h) * E + (size_t)l * T) * half + j;
+                const int a = partner[i], b = partner_b[i];
+                if (b < 0 || b >= half)
+                    return fail(PSFMC_EINVAL, "partner index %d out of range [0, %d) at iteration %d", b, half, it);
+                if (a == b)
+                    return fail(PSFMC_EINVAL, "the two partners of a differential-evolution proposal must differ "
+                                "(a == b == %d at iteration %d)", a, it);
+            }
+    }
     for (size_t i = 0; i < n_swap; ++i)
         if (swap_i[i] < 0 || swap_i[i] >= W || swap_j[i] < 0 || swap_j[i] >= W)
             return fail(PSFMC_EINVAL, "swap index outside [0, %d)", W);
@@ -3602,7 +3628,8 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
                  o_lnpc = take(lnprob_chain ? (size_t)L * W * n_iter : 0, 8),
                  o_lnlc = take(lnlike_chain ? TW * n_iter : 0, 8), o_lnqc = take(lnprior_chain ? TW * n_iter : 0, 8),
                  o_nacc = take(TW, 8), o_nswap = take(E, 8),
-                 o_partner = take(n_rand, 4), o_si = take(n_swap, 4), o_sj = take(n_swap, 4);
+                 o_partner = take(n_rand, 4), o_si = take(n_swap, 4), o_sj = take(n_swap, 4),
+                 o_kind = take(moves ? (size_t)n_iter * L : 0, 4), o_pb = take(moves ? n_rand : 0, 4);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(st));            // a previous call may still use the blob
@@ -3627,6 +3654,8 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
     int* d_partner = reinterpret_cast<int*>(base + o_partner);
     int* d_si = reinterpret_cast<int*>(base + o_si);
     int* d_sj = reinterpret_cast<int*>(base + o_sj);
+    int* d_kind = reinterpret_cast<int*>(base + o_kind);
+    int* d_pb = reinterpret_cast<int*>(base + o_pb);
     auto up = [&](void* dst, const void* src, size_t n) -> int {
         if (n) HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st));
         return PSFMC_OK;
@@ -3642,6 +3671,10 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
     RC_TRY(up(d_si, swap_i, n_swap * sizeof(int)));
     RC_TRY(up(d_sj, swap_j, n_swap * sizeof(int)));
     RC_TRY(up(d_slu, swap_log_u, n_swap * sizeof(double)));
+    if (moves) {
+        RC_TRY(up(d_kind, kind, (size_t)n_iter * L * sizeof(int)));
+        RC_TRY(up(d_pb, partner_b, n_rand * sizeof(int)));
+    }
     if (state_valid) {
         RC_TRY(up(d_lnL, lnlike, TW * sizeof(double)));
         RC_TRY(up(d_lnpi, lnprior, TW * sizeof(double)));
@@ -3659,13 +3692,20 @@ static int pt_run_impl(psfmc_ctx* c, PtMode mode, int T, int W, int n_iter, cons
     // proposal-and-prior kernel per half-step, whatever T and F are; its pass is over T half F records.  Several
     // ladders add one proposal kernel per half-step, whatever their number: the L T rungs' proposals
     // (k_pt_fields_propose), their records (one k_theta_prep launch, blockIdx.y the field), one pass over
-    // L T half records, the accept kernel over L T ensembles; the swap kernel with one workgroup per ladder
+    // L T half records, the accept kernel over L T ensembles; the swap kernel with one workgroup per ladder.
+    // With moves every mode proposes with k_pt_move_propose and derives the records from d_q as given vectors:
+    // one launch more per half-step for one-field and joint ladders, none more for several ladders
     const auto finish = joint ? k_pt_finish<true> : k_pt_finish<false>;     // (one-field: nf = 1 compiled in)
     const int move_blocks = (int)(((size_t)E * half * P + kMoveThreads - 1) / kMoveThreads);
     for (int it = 0; it < n_iter; ++it) {
         for (int h = 0; h < 2; ++h) {
             const int n = E * half;
-            if (joint) launch_joint_propose(c, d_pos, d_q, d_z, d_partner, it, T, half, h, st);
+            if (moves) {                          // by kind to d_q, then the records of the given vectors
+                hipLaunchKernelGGL(k_pt_move_propose, dim3(move_blocks), dim3(kMoveThreads), 0, st, d_pos, d_q, d_kind,
+                                   d_partner, d_pb, d_z, it, E, T, half, h, P);
+                if (joint) launch_joint_records(c, n, d_q, st);
+                else launch_theta_prep(c, T * half, d_q, nullptr, nullptr, st, StretchIn{}, 0, 0, L);
+            } else if (joint) launch_joint_propose(c, d_pos, d_q, d_z, d_partner, it, T, half, h, st);
             else if (fields) {
                 hipLaunchKernelGGL(k_pt_fields_propose, dim3(move_blocks), dim3(kMoveThreads), 0, st, d_pos, d_q, d_z,
                                    d_partner, it, E, half, h, P);
@@ -3717,6 +3757,19 @@ extern "C" int psfmc_pt_run(psfmc_ctx* c, int T, int W, int n_iter, const double
     return pt_run_impl(c, PT_ONE, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
                        swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
                        nswap, accumulate);
+}
+
+// psfmc_pt_run with the move of every iteration named (pt_run_impl): z the move's scalar, lz its Hastings term
+extern "C" int psfmc_pt_move_run(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                                 double* lnlike, double* lnprior, int state_valid, const double* z, const double* lz,
+                                 const int* partner, const double* log_u, const int* kind, const int* partner_b,
+                                 const int* swap_i, const int* swap_j, const double* swap_log_u, double* chain,
+                                 double* lnprob_chain, double* lnlike_chain, double* lnprior_chain,
+                                 long long* naccepted, long long* nswap, int accumulate) {
+    if (!kind || !partner_b) return fail(PSFMC_EINVAL, "NULL buffer");
+    return pt_run_impl(c, PT_ONE, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate, kind, partner_b);
 }
 
 // ---------------------------------------------------------------------------
@@ -3868,6 +3921,34 @@ extern "C" int psfmc_pt_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const 
     return pt_run_impl(c, PT_JOINT, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
                        swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
                        nswap, accumulate);
+}
+
+// psfmc_pt_move_run for every field of the context: kind [n_iter][n_fields], each ladder its own move
+extern "C" int psfmc_pt_move_run_fields(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                                        double* lnlike, double* lnprior, int state_valid, const double* z,
+                                        const double* lz, const int* partner, const double* log_u, const int* kind,
+                                        const int* partner_b, const int* swap_i, const int* swap_j,
+                                        const double* swap_log_u, double* chain, double* lnprob_chain,
+                                        double* lnlike_chain, double* lnprior_chain, long long* naccepted,
+                                        long long* nswap, int accumulate) {
+    if (!kind || !partner_b) return fail(PSFMC_EINVAL, "NULL buffer");
+    return pt_run_impl(c, PT_FIELDS, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate, kind, partner_b);
+}
+
+// psfmc_pt_move_run for T ensembles of W joint walkers
+extern "C" int psfmc_pt_move_run_joint(psfmc_ctx* c, int T, int W, int n_iter, const double* betas, double* pos,
+                                       double* lnlike, double* lnprior, int state_valid, const double* z,
+                                       const double* lz, const int* partner, const double* log_u, const int* kind,
+                                       const int* partner_b, const int* swap_i, const int* swap_j,
+                                       const double* swap_log_u, double* chain, double* lnprob_chain,
+                                       double* lnlike_chain, double* lnprior_chain, long long* naccepted,
+                                       long long* nswap, int accumulate) {
+    if (!kind || !partner_b) return fail(PSFMC_EINVAL, "NULL buffer");
+    return pt_run_impl(c, PT_JOINT, T, W, n_iter, betas, pos, lnlike, lnprior, state_valid, z, lz, partner, log_u,
+                       swap_i, swap_j, swap_log_u, chain, lnprob_chain, lnlike_chain, lnprior_chain, naccepted,
+                       nswap, accumulate, kind, partner_b);
 }
 
 // The plain half-step loop of psfmc_move_run (one-field walkers, proposals by kind), psfmc_stretch_run_joint and

@@ -936,8 +936,8 @@ __global__ void k_pt_tempered(const double* __restrict__ betas, double* __restri
 }
 
 // accept / move of one tempered half-step: record r = t half + w is walker h half + w of rung t's ensemble,
-// its proposal q[r] (formed by k_theta_prep with StretchIn::n_ens = T, or by k_joint_propose); random numbers
-// [n_iter][2][T][half].  Acceptance as k_stretch_finish's, ((P - 1) ln z + lnp_new) - lnp > ln u, with the
+// its proposal q[r] (formed by k_theta_prep with StretchIn::n_ens = T, by k_joint_propose, or by
+// k_pt_move_propose); random numbers [n_iter][2][T][half].  Acceptance as k_stretch_finish's, ((P - 1) ln z + lnp_new) - lnp > ln u, with the
 // tempered lnp.  A joint proposal is nf field records (fstride = T half apart, see walker_field_sum), lnprior[r]
 // its joint log-prior.  No chain entry here: k_pt_swap writes the iteration's.  One wave per proposal (launch:
 // finish_blocks(T half) x kFinishThreads).
@@ -1169,6 +1169,34 @@ k_pt_fields_propose(const double* __restrict__ pos, double* __restrict__ q, cons
         const double s = pos[(first + (size_t)h * half + w) * P + d];
         const double c = pos[(first + (size_t)(1 - h) * half + partner[off + r]) * P + d];
         q[i] = stretch_point(s, c, z[off + r]);
+    }
+}
+
+// k_pt_fields_propose by kind (psfmc_pt_move_run, psfmc_pt_move_run_joint, psfmc_pt_move_run_fields; the contract
+// is sampler.py's TemperedEnsembleSampler.set_moves): ensemble e = l T + t is rung t of ladder l, and kind
+// [n_iter][L] names the move of BOTH half-steps of every rung of ladder l at iteration it.  scal, a and b
+// [n_iter][2][E][half]: z or g, the first partner, the DE moves' second partner (unread for a stretch element).
+// The kind is uniform within a ladder, not within a workgroup: a per-element select.  A stretch element is
+// stretch_point's, a DE element de_point's three roundings.  One thread per (record, parameter) element,
+// grid-stride over E half P elements (launch: ceil(E half P / kMoveThreads) x kMoveThreads).
+__global__ void __launch_bounds__(kMoveThreads)
+k_pt_move_propose(const double* __restrict__ pos, double* __restrict__ q, const int* __restrict__ kind,
+                  const int* __restrict__ a, const int* __restrict__ b, const double* __restrict__ scal,
+                  int it, int E, int T, int half, int h, int P) {
+    const size_t n = (size_t)E * half * P;
+    const size_t off = ((size_t)it * 2 + h) * E * half;
+    const int* kind_it = kind + (size_t)it * (E / T);
+    for (size_t i = (size_t)blockIdx.x * kMoveThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kMoveThreads) {
+        const size_t r = i / P;
+        const int d = (int)(i - r * P);
+        const size_t e = r / half;
+        const int w = (int)(r - e * half);
+        const size_t first = e * 2 * half;                       // the ensemble's first walker
+        const double* c = pos + (first + (size_t)(1 - h) * half) * P + d;    // the other half, column d
+        const double s = pos[(first + (size_t)h * half + w) * P + d];
+        const double ca = c[(size_t)a[off + r] * P];
+        const double g = scal[off + r];
+        q[i] = kind_it[e / T] == MOVE_DE ? de_point(s, ca, c[(size_t)b[off + r] * P], g) : stretch_point(s, ca, g);
     }
 }
 

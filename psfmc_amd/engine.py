@@ -222,6 +222,9 @@ def load_library():
     lib.psfmc_eval_theta_split_fields.argtypes = [vp, ci, ip, ip, _c_double_p, _c_double_p, _c_double_p, _c_double_p]
     lib.psfmc_pt_run_fields.restype = ci
     lib.psfmc_pt_run_fields.argtypes = lib.psfmc_pt_run.argtypes
+    for fn in (lib.psfmc_pt_move_run, lib.psfmc_pt_move_run_joint, lib.psfmc_pt_move_run_fields):
+        fn.restype = ci                         # (the twin's arguments with kind and partner_b behind log_u)
+        fn.argtypes = lib.psfmc_pt_run.argtypes[:13] + [ip, ip] + lib.psfmc_pt_run.argtypes[13:]
     lib.psfmc_accumulate_theta_field.restype = ci
     lib.psfmc_accumulate_theta_field.argtypes = [vp, ci, ci, _c_double_p]
     lib.psfmc_reset_accumulated_field.restype = ci
@@ -381,8 +384,9 @@ def _move_run(fn, ctx, pos, lnprob, scal, lz, partner, log_u, kind, partner_b, n
 
 
 def _pt_run(fn, ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u, naccepted,
-            nswap, store, accumulate):
-    """The arrays of psfmc_pt_run / psfmc_pt_run_joint / psfmc_pt_run_fields (`fn`) shaped and the call made;
+            nswap, store, accumulate, kind=None, partner_b=None):
+    """The arrays of psfmc_pt_run / psfmc_pt_run_joint / psfmc_pt_run_fields or, with kind int32 [n_iter] + lead
+    and partner_b shaped as partner, of their psfmc_pt_move_run* twins (`fn`) shaped and the call made;
     betas [T] and pos [T, W, P] -- or, for the fields of a set, [F, T, W, P]: `lead` = () or (F,) then leads every
     per-walker array and follows the iteration (and half-step) in the random ones -- are contiguous float64
     already.  Returns (rc, (pos, lnlike, lnprior, chain, lnprob_chain, lnlike_chain, lnprior_chain)); naccepted
@@ -412,8 +416,13 @@ def _pt_run(fn, ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i,
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     lpt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
     opt = lambda a: _dp(a) if a is not None else None
+    moves = ()
+    if kind is not None:
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape((n_iter,) + lead)
+        partner_b = np.ascontiguousarray(partner_b, dtype=np.int32).reshape(rand)
+        moves = (ipt(kind), ipt(partner_b))
     rc = fn(ctx, n_t, n_w, n_iter, _dp(betas), _dp(pos), _dp(ll), _dp(lp), int(have), _dp(z), _dp(lz),
-            ipt(partner), _dp(log_u), ipt(swap_i), ipt(swap_j), _dp(swap_log_u), opt(chain), opt(lnchain),
+            ipt(partner), _dp(log_u), *moves, ipt(swap_i), ipt(swap_j), _dp(swap_log_u), opt(chain), opt(lnchain),
             opt(llchain), opt(lpchain), lpt(naccepted), lpt(nswap) if n_sw else None, int(bool(accumulate)))
     return rc, (pos, ll, lp, chain, lnchain, llchain, lpchain)
 
@@ -819,7 +828,7 @@ class Context(_BlockLayouts):
         return ll, lp
 
     def pt_run(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
-               naccepted, nswap, store=True, accumulate=False):
+               naccepted, nswap, store=True, accumulate=False, kind=None, partner_b=None):
         """Run z.shape[0] parallel-tempered iterations on the device (include/psfmc_hip.h psfmc_pt_run).
         betas [T], pos [T,W,P], lnlike / lnprior [T,W] or None (then evaluated first), z/lz/log_u/partner
         [n_iter,2,T,W/2], swap_i/swap_j/swap_log_u [n_iter,T-1,W], naccepted int64 [T,W], nswap int64 [T-1].
@@ -835,10 +844,20 @@ class Context(_BlockLayouts):
             raise ValueError('pos must have {} parameters'.format(self.n_params))
         if n_t * n_w > self.max_walkers:
             raise ValueError('T x W = {} exceeds max_walkers={}'.format(n_t * n_w, self.max_walkers))
-        rc, out = _pt_run(self._lib.psfmc_pt_run, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u,
-                          swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        fn = self._lib.psfmc_pt_run if kind is None else self._lib.psfmc_pt_move_run
+        rc, out = _pt_run(fn, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner, log_u,
+                          swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate, kind, partner_b)
         self._check(rc)
         return out
+
+    def pt_move_run(self, betas, pos, lnlike, lnprior, scal, lz, partner, log_u, kind, partner_b, swap_i, swap_j,
+                    swap_log_u, naccepted, nswap, store=True, accumulate=False):
+        """`pt_run` with the move of every iteration named (include/psfmc_hip.h psfmc_pt_move_run): kind int32
+        [n_iter] (MOVE_STRETCH / MOVE_DE, the move of both half-steps of every rung), partner_b
+        [n_iter,2,T,W/2] the DE moves' second partner; scal is z for a stretch iteration and g for a DE one, lz
+        its Hastings term (0 for DE).  Returns what `pt_run` returns."""
+        return self.pt_run(betas, pos, lnlike, lnprior, scal, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+                           naccepted, nswap, store=store, accumulate=accumulate, kind=kind, partner_b=partner_b)
 
     # -- the sampler one half-step at a time (walkers sharded over ranks) -----
     def stretch_open(self, pos, lnprob, z, lz, partner, log_u, naccepted, store=True):
@@ -1146,7 +1165,7 @@ class FieldSetContext(object):
         return outs
 
     def pt_run_fields(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
-                      naccepted, nswap, store=True, accumulate=False):
+                      naccepted, nswap, store=True, accumulate=False, kind=None, partner_b=None):
         """`Context.pt_run` for every field's own ladder at once (psfmc_pt_run_fields): betas [T] for all, pos
         [F,T,W,P], lnlike / lnprior [F,T,W] or None, z/lz/log_u/partner [n_iter,2,F,T,W/2], swap_i/swap_j/
         swap_log_u [n_iter,F,T-1,W], naccepted int64 [F,T,W], nswap int64 [F,T-1].  Returns `Context.pt_run`'s
@@ -1159,10 +1178,20 @@ class FieldSetContext(object):
             raise ValueError('pos must be [n_fields, T, W, P] with betas [T]')
         if pos.shape[3] != self.n_params:
             raise ValueError('pos must have {} parameters'.format(self.n_params))
-        rc, out = _pt_run(self._lib.psfmc_pt_run_fields, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
-                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        fn = self._lib.psfmc_pt_run_fields if kind is None else self._lib.psfmc_pt_move_run_fields
+        rc, out = _pt_run(fn, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
+                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate, kind, partner_b)
         self._check(rc)
         return out
+
+    def pt_move_run_fields(self, betas, pos, lnlike, lnprior, scal, lz, partner, log_u, kind, partner_b, swap_i,
+                           swap_j, swap_log_u, naccepted, nswap, store=True, accumulate=False):
+        """`pt_run_fields` with every ladder's move named (psfmc_pt_move_run_fields): kind int32 [n_iter, F],
+        partner_b [n_iter,2,F,T,W/2]; scal and lz as `Context.pt_move_run`.  With T = 1 and betas (1,) it is the
+        moves run of the set's plain ensembles."""
+        return self.pt_run_fields(betas, pos, lnlike, lnprior, scal, lz, partner, log_u, swap_i, swap_j, swap_log_u,
+                                  naccepted, nswap, store=store, accumulate=accumulate, kind=kind,
+                                  partner_b=partner_b)
 
     # -- joint fits: one parameter vector per walker for every field (include/psfmc_hip.h psfmc_*_joint) --
     def set_joint_priors(self, family, params):
@@ -1215,7 +1244,7 @@ class FieldSetContext(object):
         return ll, lp
 
     def pt_run_joint(self, betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j, swap_log_u,
-                     naccepted, nswap, store=True, accumulate=False):
+                     naccepted, nswap, store=True, accumulate=False, kind=None, partner_b=None):
         """`Context.pt_run` for T ensembles of joint walkers (psfmc_pt_run_joint): the same arrays and return
         values, P the joint column count; T x W x n_fields <= max_walkers (the library checks it).
         accumulate: every field's posterior sums get the beta = 1 rung's positions after every iteration."""
@@ -1225,8 +1254,10 @@ class FieldSetContext(object):
             raise ValueError('pos must be [T, W, P] with betas [T]')
         if pos.shape[2] != self.n_params:
             raise ValueError('pos must have {} parameters'.format(self.n_params))
-        rc, out = _pt_run(self._lib.psfmc_pt_run_joint, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
-                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate)
+        # (kind, partner_b: psfmc_pt_move_run_joint, `JointView.pt_move_run`)
+        fn = self._lib.psfmc_pt_run_joint if kind is None else self._lib.psfmc_pt_move_run_joint
+        rc, out = _pt_run(fn, self._ctx, betas, pos, lnlike, lnprior, z, lz, partner,
+                          log_u, swap_i, swap_j, swap_log_u, naccepted, nswap, store, accumulate, kind, partner_b)
         self._check(rc)
         return out
 
@@ -1439,6 +1470,12 @@ class JointView(object):
                naccepted, nswap, store=True, accumulate=False):
         return self.owner.pt_run_joint(betas, pos, lnlike, lnprior, z, lz, partner, log_u, swap_i, swap_j,
                                        swap_log_u, naccepted, nswap, store=store, accumulate=accumulate)
+
+    def pt_move_run(self, betas, pos, lnlike, lnprior, scal, lz, partner, log_u, kind, partner_b, swap_i, swap_j,
+                    swap_log_u, naccepted, nswap, store=True, accumulate=False):
+        return self.owner.pt_run_joint(betas, pos, lnlike, lnprior, scal, lz, partner, log_u, swap_i, swap_j,
+                                       swap_log_u, naccepted, nswap, store=store, accumulate=accumulate, kind=kind,
+                                       partner_b=partner_b)
 
     def accumulated(self, field):
         return self.owner.accumulated(field)

@@ -188,7 +188,7 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
 
 def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetypes, iterations=0, burn=0,
                       chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
-                      device=0, random_states=None, start_positions=None, accumulate=True, quiet=False):
+                      device=0, random_states=None, start_positions=None, accumulate=True, quiet=False, moves=None):
     """`model_galaxy_mcmc` for SEVERAL fields of one model structure at once (their image and PSF sizes may
     differ: each field's database and posterior images have its own shape), in
     one GPU context (`models.FieldSet`): every field is fitted exactly as its own `model_galaxy_mcmc`
@@ -204,6 +204,7 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
     random_states    one RandomState state tuple or seed per field (default: numpy's global generator
                      seeds them in field order)
     start_positions  optional [F][chains, P] start positions (default: drawn from each field's priors)
+    moves            as `model_galaxy_mcmc`'s (`FieldSetSampler.set_moves`; recorded as MCMOVES)
     Returns a list of (model, database), one per field."""
     from .models import FieldSet
     from .sampler import FieldSetSampler
@@ -235,6 +236,7 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
                 raise ValueError('start_positions[{}] must be [{}, {}], got {}'.format(
                     f, chains, fieldset.num_params, np.shape(p)))
     sampler = FieldSetSampler(chains, fieldset, accumulate=False)
+    sampler.set_moves(moves)
     for f, sub in enumerate(sampler.fields):
         state = None if random_states is None else random_states[f]
         if state is None:
@@ -277,6 +279,8 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
             meta = OrderedDict([('MCITER', sub.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
                                 ('MCCONVRG', converged[f]),
                                 ('MCACCEPT', float(sub.acceptance_fraction.mean()))])
+            if moves is not None:
+                meta['MCMOVES'] = moves_label(moves)
             databases.append(save_database(sub, models[f], db_names[f], meta_dict=meta))
     else:
         if not quiet:
@@ -362,13 +366,14 @@ def _save_joint_images(joint, database, output_name, write_fits):
 
 def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetypes, iterations=0, burn=0,
                         chains=None, ntemps=16, tmax=1e6, betas=None, device=0, backend='auto', random_state=None,
-                        accumulate=True, quiet=False):
+                        accumulate=True, quiet=False, moves=None):
     """`model_galaxy_mcmc` on the parallel-tempered device sampler (`sampler.DeviceTemperedSampler`), for the
     Bayesian evidence of the model: burn-in, reset and `iterations` sampling iterations as the reference runs
     them, then the beta = 1 rung's database and posterior images exactly as `model_galaxy_mcmc` writes them, with
     the header keys MCNTEMPS (rungs), MCLNZ / MCLNZERR (`log_evidence()` of the sampling iterations) and MCTSWAP
     (mean swap acceptance).  The ladder is `betas`, or `default_betas(ntemps, tmax)` (defaults: DESIGN.md
-    section 13).  One-field models with every prior on the device.  Returns (model, database, (lnZ, err))."""
+    section 13).  One-field models with every prior on the device.  `moves`: as `model_galaxy_mcmc`'s, the moves
+    of every rung (`DeviceTemperedSampler.set_moves`; recorded as MCMOVES).  Returns (model, database, (lnZ, err))."""
     from .sampler import DeviceTemperedSampler, default_betas
     if output_name is None:
         output_name = 'out_' + model_file.replace('.py', '')
@@ -391,6 +396,7 @@ def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetyp
         mc_model = MultiComponentModel(model_file, device=device, backend=backend, max_walkers=n_t * chains)
     mc_model.engine
     sampler = DeviceTemperedSampler(chains, mc_model, betas=betas)
+    sampler.set_moves(moves)
     if random_state is not None:
         if isinstance(random_state, (int, np.integer)):
             random_state = np.random.RandomState(int(random_state)).get_state()
@@ -417,6 +423,8 @@ def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetyp
                             ('MCACCEPT', float(sampler.acceptance_fraction.mean())),
                             ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
                             ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+        if moves is not None:
+            meta['MCMOVES'] = moves_label(moves)
         database = save_database(sampler, mc_model, db_name, meta_dict=meta)
     else:
         print('Database already contains sampled chains, skipping sampling')
@@ -429,7 +437,7 @@ def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetyp
 
 def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=default_filetypes, iterations=0,
                        burn=0, chains=None, ntemps=16, tmax=1e6, betas=None, device=0, random_state=None,
-                       accumulate=True, quiet=False):
+                       accumulate=True, quiet=False, moves=None):
     """`model_galaxy_ptmcmc` for ONE model fitted jointly to several exposures (`models.JointModel`, as
     `model_joint_mcmc` builds it): the Bayesian evidence of the joint fit, every exposure counted.  Burn-in,
     reset and `iterations` sampling iterations on `sampler.DeviceTemperedSampler` with `chains` walkers per rung
@@ -439,7 +447,8 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
     Outputs: ONE database `<output_name>_db.fits` with the joint columns and the beta = 1 rung's chain, the
     header keys MCFIELDS, MCNTEMPS, MCLNZ, MCLNZERR and MCTSWAP (mean swap acceptance), and each field's
     posterior images `<output_name>_f<k>_<type>.fits` at that field's shape.  An existing database skips
-    sampling; the evidence is then read back from its header.  Returns (JointModel, database, (lnZ, err))."""
+    sampling; the evidence is then read back from its header.  `moves`: as `model_galaxy_ptmcmc`'s (recorded as
+    MCMOVES).  Returns (JointModel, database, (lnZ, err))."""
     from .sampler import DeviceTemperedSampler, check_betas, default_betas
     betas = default_betas(ntemps, tmax) if betas is None else check_betas(betas)
     n_t = len(betas)
@@ -464,6 +473,7 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
                 n_t, chains, n_f, joint._max_walkers))
         joint = JointModel(model_files, per_field=per_field, device=device, max_walkers=n_t * chains * n_f)
     sampler = DeviceTemperedSampler(chains, joint, betas=betas)
+    sampler.set_moves(moves)
     if random_state is not None:
         if isinstance(random_state, (int, np.integer)):
             random_state = np.random.RandomState(int(random_state)).get_state()
@@ -490,6 +500,8 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
                             ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f),
                             ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
                             ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+        if moves is not None:
+            meta['MCMOVES'] = moves_label(moves)
         database = save_database(sampler, joint, db_name, meta_dict=meta)
     else:
         if not quiet:
@@ -503,7 +515,7 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
 
 def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filetypes, iterations=0, burn=0,
                         chains=None, ntemps=16, tmax=1e6, betas=None, device=0, random_states=None,
-                        start_positions=None, accumulate=True, quiet=False):
+                        start_positions=None, accumulate=True, quiet=False, moves=None):
     """`model_galaxy_ptmcmc` for SEVERAL fields of one model structure at once, in one GPU context
     (`models.FieldSet`, `sampler.FieldSetTemperedSampler`): the Bayesian evidence of every field's model from
     one run.  Every field is tempered exactly as its own `model_galaxy_ptmcmc` run would temper it -- its own
@@ -518,6 +530,7 @@ def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filet
     random_states    one RandomState state tuple or seed per field (default: numpy's global generator
                      seeds them in field order)
     start_positions  optional [F][T, chains, P] start positions (default: every rung drawn from its field's priors)
+    moves            as `model_galaxy_ptmcmc`'s (`FieldSetTemperedSampler.set_moves`; recorded as MCMOVES)
     Outputs per field: the beta = 1 database `<output_name>_db.fits` with the header keys MCNTEMPS, MCLNZ, MCLNZERR
     and MCTSWAP, and the posterior images, as `model_galaxy_ptmcmc` writes them.  Existing databases skip
     sampling; the evidences are then read back from their headers.
@@ -554,6 +567,7 @@ def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filet
                 raise ValueError('start_positions[{}] must be [{}, {}, {}], got {}'.format(
                     f, n_t, chains, fieldset.num_params, np.shape(p)))
     sampler = FieldSetTemperedSampler(chains, fieldset, betas=betas, accumulate=False)
+    sampler.set_moves(moves)
     for f, sub in enumerate(sampler.fields):
         state = None if random_states is None else random_states[f]
         if state is None:
@@ -593,6 +607,8 @@ def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filet
                                 ('MCACCEPT', float(sub.acceptance_fraction.mean())), ('MCNTEMPS', n_t),
                                 ('MCLNZ', float(evidences[f][0])), ('MCLNZERR', float(evidences[f][1])),
                                 ('MCTSWAP', float(sub.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+            if moves is not None:
+                meta['MCMOVES'] = moves_label(moves)
             databases.append(save_database(sub, models[f], db_names[f], meta_dict=meta))
     else:
         if not quiet:

@@ -189,11 +189,13 @@ class EnsembleSampler(object):
     move (`StretchMove`, `DEMove`), or a list of (move, weight) pairs.  With more than one move ONE extra `rand()`
     is drawn at the start of every iteration and selects, by cumulative normalised weight, the move of BOTH
     half-steps of that iteration; with exactly one move no selector is drawn.  Each half-step then draws in its
-    move's own order (see the move classes) and accepts where `(hastings + lnp_new) - lnp > ln u`."""
+    move's own order (see the move classes) and accepts where `(hastings + lnp_new) - lnp > ln u`.
+    `set_moves(moves)` is the keyword after construction: before the first `sample()` or between two."""
 
     def __init__(self, nwalkers, dim, lnpostfn=None, a=2.0, args=None, kwargs=None,
                  threads=1, pool=None, live_dangerously=False, batch_lnpostfn=None, moves=None):
-        self._moves, self._move_cum = (None, None) if moves is None else _parse_moves(moves, int(nwalkers))
+        self.k = int(nwalkers)
+        self.set_moves(moves)
         if nwalkers % 2:
             raise ValueError('The number of walkers must be even.')
         if nwalkers < 2 * dim and not live_dangerously:
@@ -209,6 +211,13 @@ class EnsembleSampler(object):
         self._random = np.random.mtrand.RandomState()
         self._last_run_mcmc_result = None
         self.reset()
+
+    def set_moves(self, moves):
+        """The proposal moves of the coming iterations (named after the library's psfmc_stretch_set_moves): None
+        (the stretch move with this sampler's `a`, the path of a sampler that never had moves), one move, or
+        (move, weight) pairs, parsed by `_parse_moves` against this sampler's walkers per ensemble.  Every sampler
+        of this module has it; call it before the first `sample()` or between two `sample()` calls."""
+        self._moves, self._move_cum = (None, None) if moves is None else _parse_moves(moves, self.k)
 
     # -- state ----------------------------------------------------------------
     def reset(self):
@@ -449,15 +458,20 @@ class DeviceEnsembleSampler(EnsembleSampler):
         if nwalkers > model._max_walkers:
             raise ValueError('model was built for at most {} walkers'.format(model._max_walkers))
         eng = model.engine                # context + layout
-        if moves is not None and not hasattr(type(eng), 'move_run'):
-            raise NotImplementedError('moves= is not available on a {}: the proposal moves serve one-field models and '
-                                      'joint fits (DESIGN.md section 21)'.format(type(eng).__name__))
+        self.set_moves(moves)             # (again, now that the engine is known)
         if not hasattr(type(eng), 'stretch_run'):
             # (a model of a FieldSet: its context is shared by the set's fields)
             eng.stretch_run()             # raises NotImplementedError naming the FieldSet
         if model._host_priors:
             raise ValueError('priors {} are evaluated on the host: the device sampler cannot be '
                              'used'.format([p.name for p, _ in model._host_priors]))
+
+    def set_moves(self, moves):
+        eng = getattr(getattr(self, 'model', None), 'engine', None)
+        if moves is not None and eng is not None and not hasattr(type(eng), 'move_run'):
+            raise NotImplementedError('moves= is not available on a {}: the proposal moves serve one-field models and '
+                                      'joint fits (DESIGN.md section 21)'.format(type(eng).__name__))
+        super(DeviceEnsembleSampler, self).set_moves(moves)
 
     def _run_block_sharded(self, pos, lnprob, z, lz, partner, log_u, *more, store=True, accumulate=False):
         """One block of iterations with every half-step's proposals sharded over the ranks
@@ -633,6 +647,7 @@ class _FieldChain(EnsembleSampler):
 
     _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
     _draw = DeviceEnsembleSampler._draw
+    _draw_moves = DeviceEnsembleSampler._draw_moves
 
 
 class FieldSetSampler(object):
@@ -644,7 +659,10 @@ class FieldSetSampler(object):
     `.lnprobability`, `.acceptance_fraction`, `.random_state`, ...).  A field's chain equals the chain its
     own one-field `DeviceEnsembleSampler` produces from the same start and random state, bit for bit.
     The reference fits one field per process (psfMC/fitting.py:13-113).
-    Stretch move only: there is no `moves` keyword here yet."""
+    Proposal moves are given with `set_moves(moves)`, not by keyword: every field then
+    draws its own selector from its own generator -- in one iteration different fields may run different moves --
+    and its chain equals its own `DeviceEnsembleSampler(moves=moves)` run.  The run goes through
+    `psfmc_pt_move_run_fields` with one rung, beta = 1."""
 
     def __init__(self, nwalkers, fieldset, a=2.0, block=64, accumulate=False):
         if nwalkers % 2:
@@ -656,6 +674,13 @@ class FieldSetSampler(object):
         self.block = int(block)
         self.accumulate = bool(accumulate)
         self.fields = [_FieldChain(nwalkers, m, a=a) for m in fieldset.models]
+        self._moves = None
+
+    def set_moves(self, moves):
+        """`EnsembleSampler.set_moves` for every field's ensemble."""
+        self._moves = None if moves is None else _parse_moves(moves, self.k)[0]
+        for f in self.fields:
+            f.set_moves(moves)
 
     def reset(self):
         for f in self.fields:
@@ -688,17 +713,42 @@ class FieldSetSampler(object):
         nacc = np.ascontiguousarray([f.naccepted.astype(np.int64) for f in self.fields])
         done = 0
 
+        moves = self._moves is not None
+
         def draw(n):
             per = [f._draw(n) for f in self.fields]            # every field from its own generator
+            if moves:
+                # (scalar, Hastings term, a, ln u, b: [n_iter, 2, F, 1, W/2]; kind: [n_iter, F] -- the shapes of
+                # `pt_move_run_fields` with one rung)
+                arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2)[:, :, :, np.newaxis, :])
+                          for j in (0, 1, 2, 3, 5)]
+                arrays.insert(4, np.ascontiguousarray(np.stack([d[0][4] for d in per], axis=1)))
+                return arrays, [d[1] for d in per]
             arrays = [np.ascontiguousarray([d[0][j] for d in per]) for j in range(4)]
             return arrays, [d[1] for d in per]
+
+        def run_moves(pos, lnp, draws, counters):
+            """A block with moves: every field one rung at beta = 1, where lnp = 1 lnL + lnpi is the walker's
+            log-posterior bit for bit; a walker enters as (lnL, lnpi) = (lnp, 0), the same sum."""
+            n_it = len(draws[4])
+            none = np.empty((n_it, n_f, 0, self.k))
+            t_acc = np.ascontiguousarray(counters[:, np.newaxis, :])
+            out = ctx.pt_move_run_fields(np.ones(1), pos[:, np.newaxis], lnp[:, np.newaxis],
+                                         np.zeros((n_f, 1, self.k)), *draws, none, none, none, naccepted=t_acc,
+                                         nswap=np.zeros((n_f, 0), dtype=np.int64), store=True,
+                                         accumulate=self.accumulate)
+            counters[...] = t_acc[:, 0]
+            return out[0][:, 0], out[4][:, :, -1].copy(), out[3][:, 0], out[4]
 
         draws, states = draw(min(self.block, iterations)) if iterations > 0 else (None, None)
         while done < iterations:
             n = min(self.block, iterations - done)
             n_next = min(self.block, iterations - done - n)
             block_states = states
-            job = _run_async(ctx.stretch_run, p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
+            if moves:
+                job = _run_async(run_moves, p, lnprob, draws, nacc)
+            else:
+                job = _run_async(ctx.stretch_run, p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
             try:
                 draws, states = draw(n_next) if n_next > 0 else (None, None)
             finally:
@@ -790,6 +840,11 @@ class TemperedEnsembleSampler(object):
         t = 0 ... T-1 in turn: z = ((a-1) rand(half) + 1)^2 / a, partner = randint(half, size=half) (the same
         rung's other half), log_u = log(rand(half)); then ONE `like_prior_fn` call evaluates the T half proposals;
         accept where ((P-1) ln z + lnp_new) - lnp > log_u, lnp = beta_t lnL + lnpi;
+        with `set_moves`: at the start of the iteration, when there is more than one move, ONE `rand()` selects
+        (`EnsembleSampler._select_move`) the move of both half-steps of EVERY rung; in each half-step rung t then
+        calls `move.draw(rs, half, P)` -> (scalar, Hastings term, a, b, ln u) in its move's own draw order and
+        proposes `move.propose(s, c, scalar, a, b)`, partners from the same rung's other half; accept where
+        (Hastings + lnp_new) - lnp > ln u.  No moves is `StretchMove(a)`, draw for draw;
       * swaps: for t = T-1 down to 1: i = permutation(W), j = permutation(W), log_u = log(rand(W)); pair k swaps
         walker i[k] of rung t with walker j[k] of rung t-1 when log_u[k] < (beta_{t-1} - beta_t) (lnL[t, i[k]] -
         lnL[t-1, j[k]]): positions, lnL and lnpi are exchanged, lnp recomputed at the new beta;
@@ -800,7 +855,8 @@ class TemperedEnsembleSampler(object):
     like_prior_fn(theta [N, P]) -> (lnL [N], lnpi [N]), e.g. `model.log_likelihood_and_prior_batch`.
     Stored: `chain` [W, n, P] and `lnprobability` [W, n] of the beta = 1 rung (what `save_database` and
     `check_convergence_autocorr` read), `lnlikelihood` [T, W, n] of every rung; counters `naccepted_t` [T, W],
-    `nswap` [T-1].  Stretch move only: there is no `moves` keyword here yet."""
+    `nswap` [T-1].  Proposal moves are given with `set_moves(moves)` (DESIGN.md section 28), not by keyword;
+    with T = 1 the chain is then `EnsembleSampler(moves=moves)`'s, bit for bit."""
 
     def __init__(self, nwalkers, dim, betas, like_prior_fn, a=2.0):
         if nwalkers % 2 or nwalkers < 2:
@@ -810,7 +866,11 @@ class TemperedEnsembleSampler(object):
         self.ntemps = len(self.betas)
         self.like_prior_fn = like_prior_fn
         self._random = np.random.mtrand.RandomState()
+        self._moves = self._move_cum = None
         self.reset()
+
+    set_moves = EnsembleSampler.set_moves           # (DE needs 4 walkers per rung)
+    _select_move = EnsembleSampler._select_move
 
     def reset(self):
         self.iterations = 0
@@ -929,23 +989,22 @@ class TemperedEnsembleSampler(object):
         i0 = self._grow_storage(iterations, thin, storechain)
         half = n_w // 2
         rs = self._random
+        stretch = StretchMove(self.a)                   # no moves: the stretch move, draw for draw
         for i in range(int(iterations)):
             self.iterations += 1
+            move = stretch if self._moves is None else self._moves[self._select_move()]
             for s0, s1 in ((slice(0, half), slice(half, n_w)), (slice(half, n_w), slice(0, half))):
-                z = np.empty((n_t, half))
+                hastings = np.empty((n_t, half))
                 lu = np.empty((n_t, half))
                 q = np.empty((n_t, half, n_p))
                 for t in range(n_t):
-                    z[t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
-                    rint = rs.randint(half, size=(half,))
-                    lu[t] = np.log(rs.rand(half))
-                    c = p[t, s1][rint]
-                    q[t] = c - z[t][:, np.newaxis] * (c - p[t, s0])
+                    scal, hastings[t], a, b, lu[t] = move.draw(rs, half, n_p)
+                    q[t] = move.propose(p[t, s0], p[t, s1], scal, a, b)
                 nl, npri = self._like_prior(q.reshape(n_t * half, n_p))
                 nl, npri = nl.reshape(n_t, half), npri.reshape(n_t, half)
                 newlnp = _tempered(beta, nl, npri)
                 with np.errstate(invalid='ignore'):
-                    acc = (self.dim - 1.0) * np.log(z) + newlnp - lnp[:, s0] > lu
+                    acc = hastings + newlnp - lnp[:, s0] > lu
                 if np.any(acc):
                     p[:, s0][acc] = q[acc]
                     ll[:, s0][acc] = nl[acc]
@@ -993,7 +1052,9 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
     must hold ntemps x nwalkers; or a `JointModel` of F fields (`psfmc_pt_run_joint`, DESIGN.md section 22: a
     walker is F field records, the likelihood the fields' sum), whose `max_walkers` must hold ntemps x nwalkers
     x F.  `accumulate`: posterior images of the beta = 1 rung after every iteration (every field's, for a joint
-    fit).  Stretch move only: there is no `moves` keyword here yet."""
+    fit).  Proposal moves are given with `set_moves(moves)`, not by keyword: the run then
+    goes through `psfmc_pt_move_run` (`psfmc_pt_move_run_joint`), a proposal kernel by kind per half-step, and
+    equals `TemperedEnsembleSampler` + `set_moves` bit for bit; `set_moves(None)` launches what it always did."""
 
     def __init__(self, nwalkers, model, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
         from .models import JointModel, MultiComponentModel
@@ -1026,7 +1087,9 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
     _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
 
     def _draw(self, n_iter):
-        """Random numbers of n_iter iterations in the host sampler's order."""
+        """Random numbers of n_iter iterations in the host sampler's order: the arrays of `Context.pt_run` or,
+        with moves set, of `Context.pt_move_run` -- the selector `rand()` of every iteration drawn here too (more
+        than one move only), z the moves' scalar, lz their Hastings term, kind [n_iter] and partner_b added."""
         n_t, n_w, half = self.ntemps, self.k, self.k // 2
         n_s = max(n_t - 1, 0)
         z = np.empty((n_iter, 2, n_t, half))
@@ -1035,12 +1098,24 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
         si = np.empty((n_iter, n_s, n_w), dtype=np.int32)
         sj = np.empty((n_iter, n_s, n_w), dtype=np.int32)
         slu = np.empty((n_iter, n_s, n_w))
+        moves = self._moves is not None
+        if moves:
+            lz = np.empty((n_iter, 2, n_t, half))
+            partner_b = np.zeros((n_iter, 2, n_t, half), dtype=np.int32)
+            kind = np.empty(n_iter, dtype=np.int32)
         rs = self._random
         states = []
         snap = self._state_snapshotter()
         for it in range(n_iter):
+            if moves:
+                move = self._moves[self._select_move()]
+                kind[it] = move.kind
             for h in range(2):
                 for t in range(n_t):
+                    if moves:
+                        z[it, h, t], lz[it, h, t], partner[it, h, t], partner_b[it, h, t], log_u[it, h, t] = \
+                            move.draw(rs, half, self.dim)
+                        continue
                     z[it, h, t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
                     partner[it, h, t] = rs.randint(half, size=(half,))
                     log_u[it, h, t] = np.log(rs.rand(half))
@@ -1049,6 +1124,8 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
                 sj[it, t - 1] = rs.permutation(n_w)
                 slu[it, t - 1] = np.log(rs.rand(n_w))
             states.append(snap())
+        if moves:
+            return (z, lz, partner, log_u, kind, partner_b, si, sj, slu), states
         return (z, (self.dim - 1.0) * np.log(z), partner, log_u, si, sj, slu), states
 
     def sample(self, p0, lnlike0=None, lnprior0=None, rstate0=None, iterations=1, thin=1, storechain=True):
@@ -1069,7 +1146,9 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
             n = min(self.block, iterations - done)
             n_next = min(self.block, iterations - done - n)
             block_states = states
-            job = _run_async(eng.pt_run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
+            # (moves: the draws carry kind and partner_b as well -- Context.pt_move_run's arguments)
+            run = eng.pt_run if len(draws) == 7 else eng.pt_move_run
+            job = _run_async(run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
                              accumulate=self.accumulate)
             try:
                 draws, states = self._draw(n_next) if n_next > 0 else (None, None)
@@ -1120,7 +1199,9 @@ class FieldSetTemperedSampler(object):
     field's own run from the same start, random state, ladder and block size bit for bit, so each field gets its
     own Bayesian evidence.  The set's `max_walkers` must hold F x ntemps x nwalkers.  `accumulate`: every
     field's posterior images of its beta = 1 rung after every iteration.
-    Stretch move only: there is no `moves` keyword here yet."""
+    Proposal moves are given with `set_moves(moves)`, not by keyword: every field then
+    draws its own selector from its own generator, the run goes through `psfmc_pt_move_run_fields`, and a field's
+    contents equal its own `DeviceTemperedSampler` + `set_moves` run."""
 
     def __init__(self, nwalkers, fieldset, ntemps=16, tmax=1e6, betas=None, a=2.0, block=64, accumulate=False):
         if nwalkers % 2 or nwalkers < 2:
@@ -1136,6 +1217,11 @@ class FieldSetTemperedSampler(object):
         self.block = int(block)
         self.accumulate = bool(accumulate)
         self.fields = [_FieldLadder(nwalkers, m, self.betas, a=a) for m in fieldset.models]
+
+    def set_moves(self, moves):
+        """`TemperedEnsembleSampler.set_moves` for every field's ladder."""
+        for f in self.fields:
+            f.set_moves(moves)
 
     def reset(self):
         for f in self.fields:
@@ -1164,9 +1250,10 @@ class FieldSetTemperedSampler(object):
 
         def draw(n):
             per = [f._draw(n) for f in self.fields]            # every field from its own generator
-            # (z, lz, partner, log_u: [n_iter, 2, F, T, W/2]; the swaps' three: [n_iter, F, T-1, W])
-            arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2 if j < 4 else 1))
-                      for j in range(7)]
+            # (z, lz, partner, log_u and, with moves, partner_b: [n_iter, 2, F, T, W/2]; the swaps' three:
+            # [n_iter, F, T-1, W]; with moves, kind: [n_iter, F])
+            arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2 if per[0][0][j].ndim == 4 else 1))
+                      for j in range(len(per[0][0]))]
             return arrays, [d[1] for d in per]
 
         # the next block's random numbers are drawn while the GPU runs the current one (DeviceEnsembleSampler)
@@ -1175,7 +1262,8 @@ class FieldSetTemperedSampler(object):
             n = min(self.block, iterations - done)
             n_next = min(self.block, iterations - done - n)
             block_states = states
-            job = _run_async(ctx.pt_run_fields, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw,
+            run = ctx.pt_run_fields if len(draws) == 7 else ctx.pt_move_run_fields
+            job = _run_async(run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw,
                              store=True, accumulate=self.accumulate)
             try:
                 draws, states = draw(n_next) if n_next > 0 else (None, None)
