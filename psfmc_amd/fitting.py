@@ -85,6 +85,126 @@ def _burn_and_sample(sampler, model, param_vec, burn, iterations, max_iterations
     return False
 
 
+_NO_EVIDENCE = (float('nan'), float('nan'))
+
+
+def _burn_and_sample_tempered(sampler, pos, burn, iterations, accumulate, quiet):
+    """The tempered fits' flow: burn-in from `pos`, reset, `iterations` sampling iterations with the beta = 1
+    rung's posterior images accumulated inside the sampler, then `log_evidence()` of the sampling iterations
+    ((nan, nan) without a second rung or without iterations).  One text for a ladder and for a set of ladders
+    (a sampler with `fields`): the set's yields and the returned evidences are lists over fields."""
+    fields = getattr(sampler, 'fields', None)
+
+    def run(n, label, *state):
+        for step, result in enumerate(sampler.sample(*state, iterations=n)):
+            state = (result[:3] if fields is None else
+                     tuple(np.array([r[j] for r in result]) for j in range(3)))       # pos, lnL, lnpi
+            if not quiet:
+                print_progress(step, n, label)
+        return state
+
+    state = run(burn, 'Burning', pos, None, None)
+    sampler.reset()
+    sampler.accumulate = bool(accumulate)
+    run(iterations, 'Sampling', *state)
+    sampler.accumulate = False
+    evidences = [m.log_evidence(fburnin=0.0) if m.ntemps > 1 and iterations > 0 else _NO_EVIDENCE
+                 for m in ([sampler] if fields is None else fields)]
+    return evidences[0] if fields is None else evidences
+
+
+def _seed(sampler, state, default=None):
+    """`random_state=` of an entry point into a sampler, or one of `random_states=` into a set's member: a
+    RandomState state tuple, an int seed, or None -- then `default()`, or with no default the sampler keeps the
+    fresh generator it was built with."""
+    if state is None and default is not None:
+        state = default()
+    if state is None:
+        return
+    if isinstance(state, (int, np.integer)):
+        state = np.random.RandomState(int(state)).get_state()
+    sampler.random_state = state
+
+
+def _seed_fields(sampler, random_states):
+    """Every member of a set seeded from `random_states`; where there is none numpy's global generator seeds
+    them, in field order."""
+    for f, sub in enumerate(sampler.fields):
+        _seed(sub, None if random_states is None else random_states[f],
+              default=lambda: int(np.random.randint(0, 2 ** 31 - 1)))
+
+
+def _check_chains(chains):
+    if chains < 2 or chains % 2:
+        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
+                         'two halves'.format(chains))
+
+
+def _chain_meta(sampler, burn, chains, converged, moves, **extra):
+    """The database header of a sampler's (or member's) chain: the common keys, then `extra` in the caller's
+    order, then MCMOVES when moves were given.  The order is the order in the written file."""
+    meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
+                        ('MCCONVRG', bool(converged)), ('MCACCEPT', float(sampler.acceptance_fraction.mean()))])
+    meta.update(extra)
+    if moves is not None:
+        meta['MCMOVES'] = moves_label(moves)
+    return meta
+
+
+def _tempered_meta(sampler, n_t, evidence):
+    """The header keys of a tempered chain, `extra` of `_chain_meta`."""
+    return OrderedDict([('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
+                        ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
+
+
+def _load_existing(db_names, quiet, fields=False):
+    """The databases of an earlier run, which skip sampling, and the evidences in their headers."""
+    if not quiet:
+        print('Databases already contain sampled chains, skipping sampling' if fields else
+              'Database already contains sampled chains, skipping sampling')
+    databases = [load_database(d) for d in db_names]
+    return databases, [(float(db.meta['MCLNZ']), float(db.meta['MCLNZERR'])) if 'MCLNZ' in db.meta
+                       else _NO_EVIDENCE for db in databases]
+
+
+def _fields_arguments(model_files, output_names, random_states, start_positions, chains, device, n_t=None):
+    """The arguments of the two fields entry points, checked: -> (fieldset, output names with their '_{}',
+    chains, database names, whether the databases exist).  `chains` defaults to 2 P + 2 of the first model;
+    the set holds F x chains walkers, or F x n_t x chains for ladders of n_t rungs, whose start positions are
+    [T, chains, P]."""
+    from .models import FieldSet
+    n_f = len(model_files)
+    if output_names is None:
+        output_names = ['out_' + str(f).replace('.py', '') for f in model_files]
+    if len(output_names) != n_f:
+        raise ValueError('one output name per field')
+    output_names = [o + '_{}' for o in output_names]
+    if chains is None:
+        first = model_files[0]
+        if not isinstance(first, MultiComponentModel):
+            first = MultiComponentModel(first, device=device, backend='fused', max_walkers=1)
+            model_files = [first] + list(model_files[1:])
+        chains = 2 * first.num_params + 2
+    _check_chains(chains)
+    if random_states is not None and len(random_states) != n_f:
+        raise ValueError('random_states: one per field ({} given for {} fields)'.format(len(random_states), n_f))
+    if start_positions is not None and len(start_positions) != n_f:
+        raise ValueError('start_positions: one [{}chains, P] array per field ({} given for {} fields)'.format(
+            '' if n_t is None else 'T, ', len(start_positions), n_f))
+    fieldset = FieldSet(model_files, max_walkers=n_f * (n_t or 1) * chains, device=device)
+    shape = (() if n_t is None else (n_t,)) + (chains, fieldset.num_params)
+    for f, p in enumerate(() if start_positions is None else start_positions):
+        if np.shape(p) != shape:
+            raise ValueError('start_positions[{}] must be [{}], got {}'.format(
+                f, ', '.join(str(s) for s in shape), np.shape(p)))
+    db_names = [o.format('db') + '.fits' for o in output_names]
+    have = [os.path.exists(d) for d in db_names]
+    if any(have) and not all(have):
+        raise ValueError('some of the fields already have a database and some do not: {}'.format(
+            [d for d, h in zip(db_names, have) if h]))
+    return fieldset, output_names, chains, db_names, all(have)
+
+
 def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes, iterations=0,
                       burn=0, chains=None, max_iterations=1,
                       convergence_check=check_convergence_autocorr, sampler_class=None,
@@ -144,10 +264,7 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
         from .batch import BatchLogPosterior
         sampler = cls(chains, mc_model.num_params, mc_model.log_posterior,
                       kwargs={'model': mc_model}, pool=BatchLogPosterior(mc_model).as_pool(), **extra)
-    if random_state is not None:
-        if isinstance(random_state, (int, np.integer)):
-            random_state = np.random.RandomState(int(random_state)).get_state()
-        sampler.random_state = random_state
+    _seed(sampler, random_state)
     writer = ranks is None or ranks.rank == 0
     if ranks is not None:                      # one random stream for all ranks
         sampler.random_state = ranks.broadcast_object(sampler.random_state)
@@ -165,19 +282,13 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
                                      convergence_check, accumulate and writer, device_acc, quiet)
         if device_acc:
             mc_model.reduce_accumulated(ranks)
-        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
-                            ('MCCHAINS', chains), ('MCCONVRG', bool(converged)),
-                            ('MCACCEPT', float(sampler.acceptance_fraction.mean()))])
-        if moves is not None:
-            meta['MCMOVES'] = moves_label(moves)
+        meta = _chain_meta(sampler, burn, chains, converged, moves)
         database = save_database(sampler, mc_model, db_name, meta_dict=meta) if writer else None
         if ranks is not None:
             ranks.broadcast_object(True)          # the file is complete
             database = database if writer else load_database(db_name)
-    else:
-        if writer:
-            print('Database already contains sampled chains, skipping sampling')
-        database = load_database(db_name)
+    else:                                         # (the writer says so, whatever `quiet`)
+        (database,), _ = _load_existing([db_name], quiet=not writer)
 
     if writer:
         save_posterior_images(mc_model, database, output_name=output_name, filetypes=write_fits)
@@ -206,51 +317,15 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
     start_positions  optional [F][chains, P] start positions (default: drawn from each field's priors)
     moves            as `model_galaxy_mcmc`'s (`FieldSetSampler.set_moves`; recorded as MCMOVES)
     Returns a list of (model, database), one per field."""
-    from .models import FieldSet
     from .sampler import FieldSetSampler
-    n_f = len(model_files)
-    if output_names is None:
-        output_names = ['out_' + str(f).replace('.py', '') for f in model_files]
-    if len(output_names) != n_f:
-        raise ValueError('one output name per field')
-    output_names = [o + '_{}' for o in output_names]
-    first = model_files[0] if isinstance(model_files[0], MultiComponentModel) else None
-    if chains is None:
-        if first is None:
-            first = MultiComponentModel(model_files[0], device=device, backend='fused', max_walkers=1)
-            model_files = [first] + list(model_files[1:])
-        chains = 2 * first.num_params + 2
-    if chains < 2 or chains % 2:
-        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
-                         'two halves'.format(chains))
-    if random_states is not None and len(random_states) != n_f:
-        raise ValueError('random_states: one per field ({} given for {} fields)'.format(len(random_states), n_f))
-    if start_positions is not None and len(start_positions) != n_f:
-        raise ValueError('start_positions: one [chains, P] array per field ({} given for {} fields)'.format(
-            len(start_positions), n_f))
-    fieldset = FieldSet(model_files, max_walkers=chains * n_f, device=device)
+    fieldset, output_names, chains, db_names, have_db = _fields_arguments(
+        model_files, output_names, random_states, start_positions, chains, device)
     models = fieldset.models
-    if start_positions is not None:
-        for f, p in enumerate(start_positions):
-            if np.shape(p) != (chains, fieldset.num_params):
-                raise ValueError('start_positions[{}] must be [{}, {}], got {}'.format(
-                    f, chains, fieldset.num_params, np.shape(p)))
     sampler = FieldSetSampler(chains, fieldset, accumulate=False)
     sampler.set_moves(moves)
-    for f, sub in enumerate(sampler.fields):
-        state = None if random_states is None else random_states[f]
-        if state is None:
-            state = int(np.random.randint(0, 2 ** 31 - 1))
-        if isinstance(state, (int, np.integer)):
-            state = np.random.RandomState(int(state)).get_state()
-        sub.random_state = state
+    _seed_fields(sampler, random_states)
 
-    db_names = [o.format('db') + '.fits' for o in output_names]
-    have = [os.path.exists(d) for d in db_names]
-    if any(have) and not all(have):
-        raise ValueError('some of the fields already have a database and some do not: {}'.format(
-            [d for d, h in zip(db_names, have) if h]))
-    if not all(have):
+    if not have_db:
         if start_positions is None:
             start_positions = [m.init_params_from_priors(chains) for m in models]
         pos = np.array([np.asarray(p, dtype=np.float64) for p in start_positions])
@@ -262,7 +337,7 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
                 print_progress(step, burn, 'Burning')
         sampler.reset()
         sampler.accumulate = bool(accumulate)
-        converged = [False] * n_f
+        converged = [False] * len(models)
         for sampling_iter in range(max_iterations):
             for step, result in enumerate(sampler.sample(pos, lnprob0=lnprob, iterations=iterations)):
                 pos = np.array([r[0] for r in result])
@@ -274,18 +349,10 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
                 break
             warn('Not yet converged after {:d} iterations: fields {}'.format(
                 (sampling_iter + 1) * iterations, [f for f, ok in enumerate(converged) if not ok]))
-        databases = []
-        for f, sub in enumerate(sampler.fields):
-            meta = OrderedDict([('MCITER', sub.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
-                                ('MCCONVRG', converged[f]),
-                                ('MCACCEPT', float(sub.acceptance_fraction.mean()))])
-            if moves is not None:
-                meta['MCMOVES'] = moves_label(moves)
-            databases.append(save_database(sub, models[f], db_names[f], meta_dict=meta))
+        databases = [save_database(sub, m, name, meta_dict=_chain_meta(sub, burn, chains, ok, moves))
+                     for sub, m, name, ok in zip(sampler.fields, models, db_names, converged)]
     else:
-        if not quiet:
-            print('Databases already contain sampled chains, skipping sampling')
-        databases = [load_database(d) for d in db_names]
+        databases, _ = _load_existing(db_names, quiet, fields=True)
     for m, db, out in zip(models, databases, output_names):
         save_posterior_images(m, db, output_name=out, filetypes=write_fits)
     return list(zip(models, databases))
@@ -317,32 +384,21 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
     n_f = len(joint.field_models)
     if chains is None:
         chains = 2 * joint.num_params + 2
-    if chains < 2 or chains % 2:
-        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
-                         'two halves'.format(chains))
+    _check_chains(chains)
     if chains * n_f > joint._max_walkers:
         raise ValueError('{} fields x {} chains exceed max_walkers={}'.format(n_f, chains, joint._max_walkers))
     sampler = DeviceEnsembleSampler(chains, joint, moves=moves)
-    if random_state is not None:
-        if isinstance(random_state, (int, np.integer)):
-            random_state = np.random.RandomState(int(random_state)).get_state()
-        sampler.random_state = random_state
+    _seed(sampler, random_state)
 
     db_name = output_name + '_db.fits'
     if not os.path.exists(db_name):
         param_vec = joint.init_params_from_priors(chains)
         converged = _burn_and_sample(sampler, joint, param_vec, burn, iterations, max_iterations,
                                      convergence_check, False, accumulate, quiet)
-        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
-                            ('MCCONVRG', bool(converged)),
-                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f)])
-        if moves is not None:
-            meta['MCMOVES'] = moves_label(moves)
+        meta = _chain_meta(sampler, burn, chains, converged, moves, MCFIELDS=n_f)
         database = save_database(sampler, joint, db_name, meta_dict=meta)
     else:
-        if not quiet:
-            print('Database already contains sampled chains, skipping sampling')
-        database = load_database(db_name)
+        (database,), _ = _load_existing([db_name], quiet)
 
     _save_joint_images(joint, database, output_name, write_fits)
     return joint, database
@@ -397,40 +453,17 @@ def model_galaxy_ptmcmc(model_file, output_name=None, write_fits=default_filetyp
     mc_model.engine
     sampler = DeviceTemperedSampler(chains, mc_model, betas=betas)
     sampler.set_moves(moves)
-    if random_state is not None:
-        if isinstance(random_state, (int, np.integer)):
-            random_state = np.random.RandomState(int(random_state)).get_state()
-        sampler.random_state = random_state
+    _seed(sampler, random_state)
 
     db_name = output_name.format('db') + '.fits'
-    evidence = (float('nan'), float('nan'))
     if not os.path.exists(db_name):
         pos = np.stack([mc_model.init_params_from_priors(chains) for _ in range(n_t)])
-        lnlike = lnprior = None
-        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, iterations=burn)):
-            if not quiet:
-                print_progress(step, burn, 'Burning')
-        sampler.reset()
-        sampler.accumulate = bool(accumulate)
-        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, lnlike, lnprior,
-                                                                        iterations=iterations)):
-            if not quiet:
-                print_progress(step, iterations, 'Sampling')
-        sampler.accumulate = False
-        evidence = sampler.log_evidence(fburnin=0.0) if n_t > 1 and iterations > 0 else evidence
-        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
-                            ('MCCHAINS', chains), ('MCCONVRG', bool(check_convergence_autocorr(sampler))),
-                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())),
-                            ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
-                            ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
-        if moves is not None:
-            meta['MCMOVES'] = moves_label(moves)
+        evidence = _burn_and_sample_tempered(sampler, pos, burn, iterations, accumulate, quiet)
+        meta = _chain_meta(sampler, burn, chains, check_convergence_autocorr(sampler), moves,
+                           **_tempered_meta(sampler, n_t, evidence))
         database = save_database(sampler, mc_model, db_name, meta_dict=meta)
     else:
-        print('Database already contains sampled chains, skipping sampling')
-        database = load_database(db_name)
-        if 'MCLNZ' in database.meta:
-            evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
+        (database,), (evidence,) = _load_existing([db_name], quiet)
     save_posterior_images(mc_model, database, output_name=output_name, filetypes=write_fits)
     return mc_model, database, evidence
 
@@ -452,9 +485,8 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
     from .sampler import DeviceTemperedSampler, check_betas, default_betas
     betas = default_betas(ntemps, tmax) if betas is None else check_betas(betas)
     n_t = len(betas)
-    if chains is not None and (chains < 2 or chains % 2):
-        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
-                         'two halves'.format(chains))
+    if chains is not None:
+        _check_chains(chains)
     if output_name is None:
         output_name = 'out_joint_' + str(model_files[0]).replace('.py', '')
     given = isinstance(model_files, JointModel)
@@ -474,41 +506,17 @@ def model_joint_ptmcmc(model_files, per_field=(), output_name=None, write_fits=d
         joint = JointModel(model_files, per_field=per_field, device=device, max_walkers=n_t * chains * n_f)
     sampler = DeviceTemperedSampler(chains, joint, betas=betas)
     sampler.set_moves(moves)
-    if random_state is not None:
-        if isinstance(random_state, (int, np.integer)):
-            random_state = np.random.RandomState(int(random_state)).get_state()
-        sampler.random_state = random_state
+    _seed(sampler, random_state)
 
     db_name = output_name + '_db.fits'
-    evidence = (float('nan'), float('nan'))
     if not os.path.exists(db_name):
         pos = np.stack([joint.init_params_from_priors(chains) for _ in range(n_t)])
-        lnlike = lnprior = None
-        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, iterations=burn)):
-            if not quiet:
-                print_progress(step, burn, 'Burning')
-        sampler.reset()
-        sampler.accumulate = bool(accumulate)
-        for step, (pos, lnlike, lnprior, _) in enumerate(sampler.sample(pos, lnlike, lnprior,
-                                                                        iterations=iterations)):
-            if not quiet:
-                print_progress(step, iterations, 'Sampling')
-        sampler.accumulate = False
-        evidence = sampler.log_evidence(fburnin=0.0) if n_t > 1 and iterations > 0 else evidence
-        meta = OrderedDict([('MCITER', sampler.chain.shape[1]), ('MCBURN', burn),
-                            ('MCCHAINS', chains), ('MCCONVRG', bool(check_convergence_autocorr(sampler))),
-                            ('MCACCEPT', float(sampler.acceptance_fraction.mean())), ('MCFIELDS', n_f),
-                            ('MCNTEMPS', n_t), ('MCLNZ', float(evidence[0])), ('MCLNZERR', float(evidence[1])),
-                            ('MCTSWAP', float(sampler.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
-        if moves is not None:
-            meta['MCMOVES'] = moves_label(moves)
+        evidence = _burn_and_sample_tempered(sampler, pos, burn, iterations, accumulate, quiet)
+        meta = _chain_meta(sampler, burn, chains, check_convergence_autocorr(sampler), moves, MCFIELDS=n_f,
+                           **_tempered_meta(sampler, n_t, evidence))
         database = save_database(sampler, joint, db_name, meta_dict=meta)
     else:
-        if not quiet:
-            print('Database already contains sampled chains, skipping sampling')
-        database = load_database(db_name)
-        if 'MCLNZ' in database.meta:
-            evidence = (float(database.meta['MCLNZ']), float(database.meta['MCLNZERR']))
+        (database,), (evidence,) = _load_existing([db_name], quiet)
     _save_joint_images(joint, database, output_name, write_fits)
     return joint, database, evidence
 
@@ -535,88 +543,29 @@ def model_fields_ptmcmc(model_files, output_names=None, write_fits=default_filet
     and MCTSWAP, and the posterior images, as `model_galaxy_ptmcmc` writes them.  Existing databases skip
     sampling; the evidences are then read back from their headers.
     Returns a list of (model, database, (lnZ, err)), one per field."""
-    from .models import FieldSet
     from .sampler import FieldSetTemperedSampler, check_betas, default_betas
-    n_f = len(model_files)
     betas = default_betas(ntemps, tmax) if betas is None else check_betas(betas)
     n_t = len(betas)
-    if chains is not None and (chains < 2 or chains % 2):
-        raise ValueError('chains must be an even number >= 2 (got {}): the stretch move updates the ensemble in '
-                         'two halves'.format(chains))
-    if random_states is not None and len(random_states) != n_f:
-        raise ValueError('random_states: one per field ({} given for {} fields)'.format(len(random_states), n_f))
-    if start_positions is not None and len(start_positions) != n_f:
-        raise ValueError('start_positions: one [T, chains, P] array per field ({} given for {} fields)'.format(
-            len(start_positions), n_f))
-    if output_names is None:
-        output_names = ['out_' + str(f).replace('.py', '') for f in model_files]
-    if len(output_names) != n_f:
-        raise ValueError('one output name per field')
-    output_names = [o + '_{}' for o in output_names]
-    if chains is None:
-        first = model_files[0]
-        if not isinstance(first, MultiComponentModel):
-            first = MultiComponentModel(first, device=device, backend='fused', max_walkers=1)
-            model_files = [first] + list(model_files[1:])
-        chains = 2 * first.num_params + 2
-    fieldset = FieldSet(model_files, max_walkers=n_f * n_t * chains, device=device)
+    fieldset, output_names, chains, db_names, have_db = _fields_arguments(
+        model_files, output_names, random_states, start_positions, chains, device, n_t=n_t)
     models = fieldset.models
-    if start_positions is not None:
-        for f, p in enumerate(start_positions):
-            if np.shape(p) != (n_t, chains, fieldset.num_params):
-                raise ValueError('start_positions[{}] must be [{}, {}, {}], got {}'.format(
-                    f, n_t, chains, fieldset.num_params, np.shape(p)))
     sampler = FieldSetTemperedSampler(chains, fieldset, betas=betas, accumulate=False)
     sampler.set_moves(moves)
-    for f, sub in enumerate(sampler.fields):
-        state = None if random_states is None else random_states[f]
-        if state is None:
-            state = int(np.random.randint(0, 2 ** 31 - 1))
-        if isinstance(state, (int, np.integer)):
-            state = np.random.RandomState(int(state)).get_state()
-        sub.random_state = state
+    _seed_fields(sampler, random_states)
 
-    db_names = [o.format('db') + '.fits' for o in output_names]
-    have = [os.path.exists(d) for d in db_names]
-    if any(have) and not all(have):
-        raise ValueError('some of the fields already have a database and some do not: {}'.format(
-            [d for d, h in zip(db_names, have) if h]))
-    evidences = [(float('nan'), float('nan'))] * n_f
-    if not all(have):
+    if not have_db:
         if start_positions is None:
             start_positions = [np.stack([m.init_params_from_priors(chains) for _ in range(n_t)]) for m in models]
         pos = np.array([np.asarray(p, dtype=np.float64) for p in start_positions])
-        lnlike = lnprior = None
-        for step, result in enumerate(sampler.sample(pos, iterations=burn)):
-            pos, lnlike, lnprior = (np.array([r[j] for r in result]) for j in range(3))
-            if not quiet:
-                print_progress(step, burn, 'Burning')
-        sampler.reset()
-        sampler.accumulate = bool(accumulate)
-        for step, result in enumerate(sampler.sample(pos, lnlike, lnprior, iterations=iterations)):
-            pos, lnlike, lnprior = (np.array([r[j] for r in result]) for j in range(3))
-            if not quiet:
-                print_progress(step, iterations, 'Sampling')
-        sampler.accumulate = False
+        evidences = _burn_and_sample_tempered(sampler, pos, burn, iterations, accumulate, quiet)
         databases = []
-        for f, sub in enumerate(sampler.fields):
-            if n_t > 1 and iterations > 0:
-                evidences[f] = sub.log_evidence(fburnin=0.0)
-            meta = OrderedDict([('MCITER', sub.chain.shape[1]), ('MCBURN', burn), ('MCCHAINS', chains),
-                                ('MCCONVRG', bool(check_convergence_autocorr(sub))),
-                                ('MCACCEPT', float(sub.acceptance_fraction.mean())), ('MCNTEMPS', n_t),
-                                ('MCLNZ', float(evidences[f][0])), ('MCLNZERR', float(evidences[f][1])),
-                                ('MCTSWAP', float(sub.tswap_acceptance_fraction.mean()) if n_t > 1 else 0.0)])
-            if moves is not None:
-                meta['MCMOVES'] = moves_label(moves)
-            databases.append(save_database(sub, models[f], db_names[f], meta_dict=meta))
+        for sub, m, name, ev in zip(sampler.fields, models, db_names, evidences):
+            meta = _chain_meta(sub, burn, chains, check_convergence_autocorr(sub), moves,
+                               **_tempered_meta(sub, n_t, ev))
+            databases.append(save_database(sub, m, name, meta_dict=meta))
     else:
-        if not quiet:
-            print('Databases already contain sampled chains, skipping sampling')
-        databases = [load_database(d) for d in db_names]
-        for f, db in enumerate(databases):
-            if 'MCLNZ' in db.meta:
-                evidences[f] = (float(db.meta['MCLNZ']), float(db.meta['MCLNZERR']))
+        databases, evidences = _load_existing(db_names, quiet, fields=True)
     for m, db, out in zip(models, databases, output_names):
         save_posterior_images(m, db, output_name=out, filetypes=write_fits)
     return [(m, db, ev) for m, db, ev in zip(models, databases, evidences)]
+

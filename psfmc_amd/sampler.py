@@ -184,33 +184,19 @@ def moves_label(moves):
     return ','.join('{}:{:g}'.format(getattr(m, 'name', type(m).__name__), w / total) for m, w in pairs)
 
 
-class EnsembleSampler(object):
-    """moves: None (the stretch move with this sampler's `a`: emcee 2.2.1's sampler, draw for draw), a single
-    move (`StretchMove`, `DEMove`), or a list of (move, weight) pairs.  With more than one move ONE extra `rand()`
-    is drawn at the start of every iteration and selects, by cumulative normalised weight, the move of BOTH
-    half-steps of that iteration; with exactly one move no selector is drawn.  Each half-step then draws in its
-    move's own order (see the move classes) and accepts where `(hastings + lnp_new) - lnp > ln u`.
-    `set_moves(moves)` is the keyword after construction: before the first `sample()` or between two."""
+def _kept(done, n, thin):
+    """The kept iterations of a block of n that starts at iteration `done`: iteration done + i is kept iff
+    (done + i) % thin == 0, at index (done + i) // thin -- an arithmetic progression.  -> (first, count, offset):
+    the block's positions first::thin, `count` of them, stored from index i0 + offset on."""
+    first = (-done) % thin
+    count = (n - first + thin - 1) // thin if first < n else 0
+    return first, count, (done + first) // thin
 
-    def __init__(self, nwalkers, dim, lnpostfn=None, a=2.0, args=None, kwargs=None,
-                 threads=1, pool=None, live_dangerously=False, batch_lnpostfn=None, moves=None):
-        self.k = int(nwalkers)
-        self.set_moves(moves)
-        if nwalkers % 2:
-            raise ValueError('The number of walkers must be even.')
-        if nwalkers < 2 * dim and not live_dangerously:
-            raise ValueError('The number of walkers needs to be more than twice the '
-                             'dimension of your parameter space.')
-        if lnpostfn is None and batch_lnpostfn is None:
-            raise ValueError('need lnpostfn or batch_lnpostfn')
-        self.k, self.dim, self.a = int(nwalkers), int(dim), float(a)
-        self.lnprobfn = _Wrapped(lnpostfn, args, kwargs) if lnpostfn is not None else None
-        self.batch_lnpostfn = batch_lnpostfn
-        self.pool = pool
-        self.threads = threads
-        self._random = np.random.mtrand.RandomState()
-        self._last_run_mcmc_result = None
-        self.reset()
+
+class _SamplerState(object):
+    """What `EnsembleSampler` and `TemperedEnsembleSampler` have in common: the moves, the generator and the
+    beta = 1 chain's storage and readers.  Reads `k` (walkers per ensemble), `dim`, `_random`, `_chain` [W, n, P], `_lnprob` [W, n]
+    and, once `set_moves` has run, `_moves` / `_move_cum`."""
 
     def set_moves(self, moves):
         """The proposal moves of the coming iterations (named after the library's psfmc_stretch_set_moves): None
@@ -219,19 +205,24 @@ class EnsembleSampler(object):
         of this module has it; call it before the first `sample()` or between two `sample()` calls."""
         self._moves, self._move_cum = (None, None) if moves is None else _parse_moves(moves, self.k)
 
-    # -- state ----------------------------------------------------------------
-    def reset(self):
-        self.iterations = 0
-        self.naccepted = np.zeros(self.k)
-        self._chain = np.empty((self.k, 0, self.dim))
-        self._lnprob = np.empty((self.k, 0))
-        self._blobs = []
-        self._last_run_mcmc_result = None
-
-    clear_chain = reset
+    def _select_move(self):
+        """The move of the coming iteration (`moves=`): one `rand()` when there is more than one to choose from."""
+        if len(self._moves) == 1:
+            return 0
+        r = self._random.rand()
+        return min(int(np.searchsorted(self._move_cum, r, side='right')), len(self._moves) - 1)
 
     def clear_blobs(self):
-        self._blobs = []
+        pass
+
+    def _grow_storage(self, iterations, thin, storechain):
+        """Room for the kept iterations of a `sample()` call; -> the index of its first one."""
+        i0 = self._chain.shape[1]
+        if storechain:
+            n_keep = int(iterations // thin)
+            self._chain = np.concatenate((self._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
+            self._lnprob = np.concatenate((self._lnprob, np.zeros((self.k, n_keep))), axis=1)
+        return i0
 
     @property
     def random_state(self):
@@ -262,20 +253,63 @@ class EnsembleSampler(object):
         return self._lnprob.flatten()
 
     @property
-    def blobs(self):
-        return self._blobs
-
-    @property
-    def acceptance_fraction(self):
-        return self.naccepted / max(self.iterations, 1)
-
-    @property
     def acor(self):
         return self.get_autocorr_time()
 
     def get_autocorr_time(self, low=10, high=None, step=1, c=10):
         return integrated_time(np.mean(self._chain, axis=0), axis=0, low=low, high=high,
                                step=step, c=c)
+
+
+class EnsembleSampler(_SamplerState):
+    """moves: None (the stretch move with this sampler's `a`: emcee 2.2.1's sampler, draw for draw), a single
+    move (`StretchMove`, `DEMove`), or a list of (move, weight) pairs.  With more than one move ONE extra `rand()`
+    is drawn at the start of every iteration and selects, by cumulative normalised weight, the move of BOTH
+    half-steps of that iteration; with exactly one move no selector is drawn.  Each half-step then draws in its
+    move's own order (see the move classes) and accepts where `(hastings + lnp_new) - lnp > ln u`.
+    `set_moves(moves)` is the keyword after construction: before the first `sample()` or between two."""
+
+    def __init__(self, nwalkers, dim, lnpostfn=None, a=2.0, args=None, kwargs=None,
+                 threads=1, pool=None, live_dangerously=False, batch_lnpostfn=None, moves=None):
+        self.k = int(nwalkers)
+        self.set_moves(moves)
+        if nwalkers % 2:
+            raise ValueError('The number of walkers must be even.')
+        if nwalkers < 2 * dim and not live_dangerously:
+            raise ValueError('The number of walkers needs to be more than twice the '
+                             'dimension of your parameter space.')
+        if lnpostfn is None and batch_lnpostfn is None:
+            raise ValueError('need lnpostfn or batch_lnpostfn')
+        self.k, self.dim, self.a = int(nwalkers), int(dim), float(a)
+        self.lnprobfn = _Wrapped(lnpostfn, args, kwargs) if lnpostfn is not None else None
+        self.batch_lnpostfn = batch_lnpostfn
+        self.pool = pool
+        self.threads = threads
+        self._random = np.random.mtrand.RandomState()
+        self._last_run_mcmc_result = None
+        self.reset()
+
+    # -- state ----------------------------------------------------------------
+    def reset(self):
+        self.iterations = 0
+        self.naccepted = np.zeros(self.k)
+        self._chain = np.empty((self.k, 0, self.dim))
+        self._lnprob = np.empty((self.k, 0))
+        self._blobs = []
+        self._last_run_mcmc_result = None
+
+    clear_chain = reset
+
+    def clear_blobs(self):
+        self._blobs = []
+
+    @property
+    def blobs(self):
+        return self._blobs
+
+    @property
+    def acceptance_fraction(self):
+        return self.naccepted / max(self.iterations, 1)
 
     # -- evaluation -------------------------------------------------------------
     def _get_lnprob(self, pos):
@@ -310,13 +344,6 @@ class EnsembleSampler(object):
         accept = lnpdiff > np.log(self._random.rand(len(lnpdiff)))
         return q, newlnprob, accept, blob
 
-    def _select_move(self):
-        """The move of the coming iteration (`moves=`): one `rand()` when there is more than one to choose from."""
-        if len(self._moves) == 1:
-            return 0
-        r = self._random.rand()
-        return min(int(np.searchsorted(self._move_cum, r, side='right')), len(self._moves) - 1)
-
     def _propose_move(self, move, p0, p1, lnprob0):
         s, c = np.atleast_2d(p0), np.atleast_2d(p1)
         scal, hastings, a, b, log_u = move.draw(self._random, len(s), self.dim)
@@ -343,11 +370,7 @@ class EnsembleSampler(object):
         lnprob = np.array(lnprob, dtype=np.float64)
         if np.any(np.isnan(lnprob)):
             raise ValueError('The initial lnprob was NaN.')
-        i0 = self._chain.shape[1]
-        if storechain:
-            n_keep = int(iterations // thin)
-            self._chain = np.concatenate((self._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
-            self._lnprob = np.concatenate((self._lnprob, np.zeros((self.k, n_keep))), axis=1)
+        i0 = self._grow_storage(iterations, thin, storechain)
         first, second = slice(halfk), slice(halfk, self.k)
         for i in range(int(iterations)):
             self.iterations += 1
@@ -410,7 +433,251 @@ def _run_async(fn, *args, **kwargs):
     return join
 
 
-class DeviceEnsembleSampler(EnsembleSampler):
+def _run_blocks(iterations, block, draw, launch, overlap=True):
+    """The block loop of every device sampler: `iterations` in blocks of at most `block`; yields, per block,
+    (done, n, result, states): the iterations before it, its size, what `launch(draws)` returned and the states of
+    `draw(n) -> (draws, states)`.  `draw` is never called with 0.
+    overlap: the next block's random numbers are drawn while the GPU works on the current one (`launch` runs on a
+    thread; the library call releases the GIL) -- the draws stay in the host sampler's order because the stream
+    is sequential: block k+1 is drawn right after block k, only earlier in time.  Without it `launch` runs on the
+    calling thread and the next draw follows it (the sharded route: collectives are issued from the caller's
+    thread, in the same order on every rank).  A launch that fails raises once the draw beside it has ended, and
+    a draw that fails still joins the launch."""
+    done = 0
+    draws, states = draw(min(block, iterations)) if iterations > 0 else (None, None)
+    while done < iterations:
+        n = min(block, iterations - done)
+        n_next = min(block, iterations - done - n)
+        block_states = states
+        if overlap:
+            job = _run_async(launch, draws)
+            try:
+                draws, states = draw(n_next) if n_next > 0 else (None, None)
+            finally:
+                result = job()
+        else:
+            result = launch(draws)
+            draws, states = draw(n_next) if n_next > 0 else (None, None)
+        yield done, n, result, block_states
+        done += n
+
+
+_HALF_STEP = ('z', 'lz', 'partner', 'log_u', 'partner_b')
+
+
+class _Draws(object):
+    """The random numbers of a block of iterations, by name.  Per half-step, [n_iter, 2, (T,) W/2]: `z` (the move's
+    scalar), `lz` (its Hastings term), `partner`, `log_u` and, with moves, `partner_b`; with moves `kind`
+    [n_iter]; for a ladder the swaps' `swap_i`, `swap_j`, `swap_log_u` [n_iter, T-1, W].  What a draw does not have
+    is None: `kind is None` is the run without moves.  Iterating gives the arrays that are there, in the order
+    below -- the argument order of every entry point (`stretch_run`, `move_run`, `pt_run`, `pt_move_run` and their
+    `_fields` forms), so a launch is `run(pos, lnp, *draws, ...)`."""
+
+    __slots__ = ('z', 'lz', 'partner', 'log_u', 'kind', 'partner_b', 'swap_i', 'swap_j', 'swap_log_u')
+
+    def __init__(self, **arrays):
+        for name in self.__slots__:
+            setattr(self, name, arrays.pop(name, None))
+        if arrays:
+            raise TypeError('not a draw: {}'.format(sorted(arrays)))
+
+    def __iter__(self):
+        return (a for a in (getattr(self, name) for name in self.__slots__) if a is not None)
+
+
+def _stack_fields(per, one_rung=False):
+    """The fields' draws as one, by name, in the shapes of the `_fields` entry points: the half-step arrays
+    [n_iter, 2, F, T, W/2], the swaps' [n_iter, F, T-1, W], kind [n_iter, F].  one_rung: the fields' draws are an
+    ensemble's, without a rung axis, and get T = 1."""
+    out = {}
+    for name in _Draws.__slots__:
+        parts = [getattr(d, name) for d in per]
+        if parts[0] is None:
+            continue
+        if one_rung and name in _HALF_STEP:
+            parts = [a[:, :, np.newaxis, :] for a in parts]
+        out[name] = np.ascontiguousarray(np.stack(parts, axis=2 if name in _HALF_STEP else 1))
+    return _Draws(**out)
+
+
+def _check_start(p, lnprob, shape, evaluate):
+    """The start-state checks of the device samplers: p a float64 array of `shape`, finite; lnprob (from
+    `evaluate(p)` when None) without NaN.  -> lnprob."""
+    if p.shape != shape:
+        raise ValueError('p0 must have shape ({})'.format(', '.join(str(s) for s in shape)))
+    if np.any(~np.isfinite(p)):
+        raise ValueError('At least one parameter value was infinite or NaN.')
+    if lnprob is None:
+        lnprob = evaluate(p)
+    if np.any(np.isnan(lnprob)):
+        raise ValueError('The initial lnprob was NaN.')
+    return lnprob
+
+
+class _DeviceMember(object):
+    """The host side of one device-resident ensemble or ladder: the cheap state snapshot, the accumulate counters,
+    and (subclasses) the draws in the host sampler's order and the store of a block's kept iterations.  Mixed into
+    a host sampler, of which it reads `_random`, `k`, `dim`, `a`, `_moves`, `_select_move()`, `_chain`, `_lnprob`
+    and, for ladders, `ntemps` and `_lnlike`; `model` is the member's model."""
+
+    def _state_snapshotter(self):
+        """A cheap `get_state()` for the per-iteration snapshots: `RandomState.get_state` costs
+        ~50 us (it would double the host time per iteration); the MT19937 key and position are
+        copied straight from the bit generator's state block (1 us), the Gaussian cache -- which
+        `rand` / `randint` never touch -- is taken from one full call.  Falls back to `get_state`
+        if the bit generator does not expose its state the expected way."""
+        rs = self._random
+        full = rs.get_state()
+        try:
+            import ctypes
+            bg = rs._bit_generator
+            if type(bg).__name__ != 'MT19937':
+                return rs.get_state
+            block = (ctypes.c_uint32 * 625).from_address(bg.ctypes.state_address)
+            view = np.frombuffer(block, dtype=np.uint32)
+            if not (np.array_equal(view[:624], full[1]) and int(view[624]) == full[2]):
+                return rs.get_state
+        except Exception:
+            return rs.get_state
+        tail = tuple(full[3:])
+
+        def snap():
+            a = view.copy()
+            return ('MT19937', a[:624], int(a[624])) + tail
+        return snap
+
+    def _count_accumulated(self, samples):
+        self.model._device_samples += samples
+        self.model.accumulated_samples += samples
+
+
+class _EnsembleMember(_DeviceMember):
+    """A device-resident ensemble: `DeviceEnsembleSampler`, and a field's share of a `FieldSetSampler`."""
+
+    def _draw(self, n_iter):
+        """Random numbers of n_iter iterations in emcee's order (per half-step: rand(Ns) -> z, randint(Nc, Ns) ->
+        partner, rand(Ns) -> ln u) or, with moves, in the order of `EnsembleSampler(moves=...)`: per iteration
+        the selector `rand()` (more than one move only), then each half-step's draws in its move's order.
+        -> (`_Draws`, the generator state after each iteration's draws)."""
+        half = self.k // 2
+        z = np.empty((n_iter, 2, half))
+        partner = np.empty((n_iter, 2, half), dtype=np.int32)
+        log_u = np.empty((n_iter, 2, half))
+        moves = self._moves is not None
+        if moves:
+            lz = np.empty((n_iter, 2, half))
+            partner_b = np.zeros((n_iter, 2, half), dtype=np.int32)
+            kind = np.empty(n_iter, dtype=np.int32)
+        rs = self._random
+        states = []
+        snap = self._state_snapshotter()
+        for it in range(n_iter):
+            if moves:
+                move = self._moves[self._select_move()]
+                kind[it] = move.kind
+            for h in range(2):
+                if moves:
+                    z[it, h], lz[it, h], partner[it, h], partner_b[it, h], log_u[it, h] = \
+                        move.draw(rs, half, self.dim)
+                    continue
+                z[it, h] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
+                partner[it, h] = rs.randint(half, size=(half,))
+                log_u[it, h] = np.log(rs.rand(half))
+            states.append(snap())
+        if moves:
+            return _Draws(z=z, lz=lz, partner=partner, log_u=log_u, kind=kind, partner_b=partner_b), states
+        return _Draws(z=z, lz=(self.dim - 1.0) * np.log(z), partner=partner, log_u=log_u), states
+
+    def _store_block(self, i0, done, n, thin, chain, lnchain):
+        """The kept iterations of a block (chain [W, n, P], lnchain [W, n]) into the storage grown from i0 on:
+        an arithmetic progression, copied with slices (index arrays made this 1.6 ms per block)."""
+        first, count, offset = _kept(done, n, thin)
+        if count:
+            dst = i0 + offset
+            self._chain[:, dst:dst + count, :] = chain[:, first::thin, :]
+            self._lnprob[:, dst:dst + count] = lnchain[:, first::thin]
+
+
+class _LadderMember(_DeviceMember):
+    """A device-resident ladder: `DeviceTemperedSampler`, and a field's share of a `FieldSetTemperedSampler`."""
+
+    def _draw(self, n_iter):
+        """Random numbers of n_iter iterations in the host sampler's order: the arrays of `Context.pt_run` or,
+        with moves set, of `Context.pt_move_run` -- the selector `rand()` of every iteration drawn here too (more
+        than one move only), z the moves' scalar, lz their Hastings term, kind [n_iter] and partner_b added.
+        -> (`_Draws`, the generator state after each iteration's draws)."""
+        n_t, n_w, half = self.ntemps, self.k, self.k // 2
+        n_s = max(n_t - 1, 0)
+        z = np.empty((n_iter, 2, n_t, half))
+        partner = np.empty((n_iter, 2, n_t, half), dtype=np.int32)
+        log_u = np.empty((n_iter, 2, n_t, half))
+        si = np.empty((n_iter, n_s, n_w), dtype=np.int32)
+        sj = np.empty((n_iter, n_s, n_w), dtype=np.int32)
+        slu = np.empty((n_iter, n_s, n_w))
+        moves = self._moves is not None
+        if moves:
+            lz = np.empty((n_iter, 2, n_t, half))
+            partner_b = np.zeros((n_iter, 2, n_t, half), dtype=np.int32)
+            kind = np.empty(n_iter, dtype=np.int32)
+        rs = self._random
+        states = []
+        snap = self._state_snapshotter()
+        for it in range(n_iter):
+            if moves:
+                move = self._moves[self._select_move()]
+                kind[it] = move.kind
+            for h in range(2):
+                for t in range(n_t):
+                    if moves:
+                        z[it, h, t], lz[it, h, t], partner[it, h, t], partner_b[it, h, t], log_u[it, h, t] = \
+                            move.draw(rs, half, self.dim)
+                        continue
+                    z[it, h, t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
+                    partner[it, h, t] = rs.randint(half, size=(half,))
+                    log_u[it, h, t] = np.log(rs.rand(half))
+            for t in range(n_t - 1, 0, -1):
+                si[it, t - 1] = rs.permutation(n_w)
+                sj[it, t - 1] = rs.permutation(n_w)
+                slu[it, t - 1] = np.log(rs.rand(n_w))
+            states.append(snap())
+        swaps = dict(swap_i=si, swap_j=sj, swap_log_u=slu)
+        if moves:
+            return _Draws(z=z, lz=lz, partner=partner, log_u=log_u, kind=kind, partner_b=partner_b, **swaps), states
+        return _Draws(z=z, lz=(self.dim - 1.0) * np.log(z), partner=partner, log_u=log_u, **swaps), states
+
+    def _store_block(self, i0, done, n, thin, chain, lnchain, llchain):
+        """The kept iterations of a block into the storage grown from i0 on: the beta = 1 rung of chain
+        [T, W, n, P], its lnchain [W, n], and every rung's llchain [T, W, n]."""
+        first, count, offset = _kept(done, n, thin)
+        if count:
+            dst = i0 + offset
+            self._chain[:, dst:dst + count, :] = chain[0, :, first::thin, :]
+            self._lnprob[:, dst:dst + count] = lnchain[:, first::thin]
+            self._lnlike[:, :, dst:dst + count] = llchain[:, :, first::thin]
+
+
+class _FieldMembers(object):
+    """What the two field-set samplers do to every member of `fields`."""
+
+    def set_moves(self, moves):
+        """`set_moves` for every field's ensemble or ladder."""
+        for f in self.fields:
+            f.set_moves(moves)
+
+    def reset(self):
+        for f in self.fields:
+            f.reset()
+
+    def clear_blobs(self):
+        pass
+
+    def _draw(self, n_iter, one_rung=False):
+        """Every field's draws from its own generator, stacked by name (`_stack_fields`), and its states."""
+        per = [f._draw(n_iter) for f in self.fields]
+        return _stack_fields([d for d, _ in per], one_rung=one_rung), [s for _, s in per]
+
+
+class DeviceEnsembleSampler(_EnsembleMember, EnsembleSampler):
     """The same sampler with the walkers resident on the GPU: proposal, log-posterior
     (priors included), acceptance and chain storage all run on the device
     (`psfmc_stretch_run`); the host only draws the random numbers, from the same
@@ -473,22 +740,21 @@ class DeviceEnsembleSampler(EnsembleSampler):
                                       'joint fits (DESIGN.md section 21)'.format(type(eng).__name__))
         super(DeviceEnsembleSampler, self).set_moves(moves)
 
-    def _run_block_sharded(self, pos, lnprob, z, lz, partner, log_u, *more, store=True, accumulate=False):
+    def _run_block_sharded(self, pos, lnprob, draws, nacc, store=True, accumulate=False):
         """One block of iterations with every half-step's proposals sharded over the ranks
-        (include/psfmc_hip.h psfmc_stretch_open / _half_eval / _half_accept / _close).  more: (nacc,), or with
-        `moves` (kind, partner_b, nacc): the open run then proposes by kind (psfmc_stretch_set_moves)."""
-        nacc = more[-1]
+        (include/psfmc_hip.h psfmc_stretch_open / _half_eval / _half_accept / _close).  With `moves` the draws
+        carry kind and partner_b: the open run then proposes by kind (psfmc_stretch_set_moves)."""
         rg, eng = self.ranks, self.model.engine
         torch = rg.torch
-        n_iter, half = int(np.shape(z)[0]), self.k // 2
+        n_iter, half = int(np.shape(draws.z)[0]), self.k // 2
         lo, hi = rg.block(half)
         a_lo, a_hi = rg.block(self.k)
         with torch.cuda.device(rg.device), rg.on_stream():
             stream = rg.stream_ptr()
             send = torch.zeros(rg.slot(half), dtype=torch.float64, device=rg.device)
-            eng.stretch_open(pos, lnprob, z, lz, partner, log_u, nacc, store=store)
-            if len(more) == 3:
-                eng.stretch_set_moves(more[0], more[1])
+            eng.stretch_open(pos, lnprob, draws.z, draws.lz, draws.partner, draws.log_u, nacc, store=store)
+            if draws.kind is not None:
+                eng.stretch_set_moves(draws.kind, draws.partner_b)
             for it in range(n_iter):
                 for h in range(2):
                     eng.stretch_half_eval(it, h, lo, hi - lo, send.data_ptr(), stream)
@@ -499,131 +765,34 @@ class DeviceEnsembleSampler(EnsembleSampler):
             torch.cuda.current_stream(rg.device).synchronize()
             return eng.stretch_close(nacc, stream)
 
-    def _state_snapshotter(self):
-        """A cheap `get_state()` for the per-iteration snapshots: `RandomState.get_state` costs
-        ~50 us (it would double the host time per iteration); the MT19937 key and position are
-        copied straight from the bit generator's state block (1 us), the Gaussian cache -- which
-        `rand` / `randint` never touch -- is taken from one full call.  Falls back to `get_state`
-        if the bit generator does not expose its state the expected way."""
-        rs = self._random
-        full = rs.get_state()
-        try:
-            import ctypes
-            bg = rs._bit_generator
-            if type(bg).__name__ != 'MT19937':
-                return rs.get_state
-            block = (ctypes.c_uint32 * 625).from_address(bg.ctypes.state_address)
-            view = np.frombuffer(block, dtype=np.uint32)
-            if not (np.array_equal(view[:624], full[1]) and int(view[624]) == full[2]):
-                return rs.get_state
-        except Exception:
-            return rs.get_state
-        tail = tuple(full[3:])
-
-        def snap():
-            a = view.copy()
-            return ('MT19937', a[:624], int(a[624])) + tail
-        return snap
-
-    def _draw(self, n_iter):
-        """Random numbers of n_iter iterations in emcee's order (per half-step:
-        rand(Ns) -> z, randint(Nc, Ns) -> partner, rand(Ns) -> ln u)."""
-        if self._moves is not None:
-            return self._draw_moves(n_iter)
-        half = self.k // 2
-        z = np.empty((n_iter, 2, half))
-        partner = np.empty((n_iter, 2, half), dtype=np.int32)
-        log_u = np.empty((n_iter, 2, half))
-        states = []                     # generator state after each iteration's draws
-        snap = self._state_snapshotter()
-        for it in range(n_iter):
-            for h in range(2):
-                z[it, h] = ((self.a - 1.0) * self._random.rand(half) + 1) ** 2.0 / self.a
-                partner[it, h] = self._random.randint(half, size=(half,))
-                log_u[it, h] = np.log(self._random.rand(half))
-            states.append(snap())
-        return (z, (self.dim - 1.0) * np.log(z), partner, log_u), states
-
-    def _draw_moves(self, n_iter):
-        """Random numbers of n_iter iterations in the order of `EnsembleSampler(moves=...)`: per iteration the
-        selector `rand()` (more than one move only), then each half-step's draws in its move's order.  Returns
-        the arrays of `Context.move_run`: (scalar, Hastings term, a, ln u, kind [n_iter], b)."""
-        half = self.k // 2
-        scal = np.empty((n_iter, 2, half))
-        lz = np.empty((n_iter, 2, half))
-        partner = np.empty((n_iter, 2, half), dtype=np.int32)
-        partner_b = np.zeros((n_iter, 2, half), dtype=np.int32)
-        log_u = np.empty((n_iter, 2, half))
-        kind = np.empty(n_iter, dtype=np.int32)
-        states = []
-        snap = self._state_snapshotter()
-        for it in range(n_iter):
-            move = self._moves[self._select_move()]
-            kind[it] = move.kind
-            for h in range(2):
-                scal[it, h], lz[it, h], partner[it, h], partner_b[it, h], log_u[it, h] = \
-                    move.draw(self._random, half, self.dim)
-            states.append(snap())
-        return (scal, lz, partner, log_u, kind, partner_b), states
-
     def sample(self, p0, lnprob0=None, rstate0=None, blobs0=None, iterations=1, thin=1,
                storechain=True):
         if rstate0 is not None:
             self.random_state = rstate0
         p = np.array(p0, dtype=np.float64)
-        if p.shape != (self.k, self.dim):
-            raise ValueError('p0 must have shape ({}, {})'.format(self.k, self.dim))
-        if np.any(~np.isfinite(p)):
-            raise ValueError('At least one parameter value was infinite or NaN.')
-        lnprob = None if lnprob0 is None else np.array(lnprob0, dtype=np.float64)
-        if lnprob is None:
-            lnprob, _ = self._get_lnprob(p)
-        if np.any(np.isnan(lnprob)):
-            raise ValueError('The initial lnprob was NaN.')
-        i0 = self._chain.shape[1]
-        if storechain:
-            n_keep = int(iterations // thin)
-            self._chain = np.concatenate((self._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
-            self._lnprob = np.concatenate((self._lnprob, np.zeros((self.k, n_keep))), axis=1)
+        lnprob = _check_start(p, None if lnprob0 is None else np.array(lnprob0, dtype=np.float64),
+                              (self.k, self.dim), lambda q: self._get_lnprob(q)[0])
+        i0 = self._grow_storage(iterations, thin, storechain)
         nacc = self.naccepted.astype(np.int64)
-        done = 0
-        # The next block's random numbers are drawn while the GPU works on the current one
-        # (the library call releases the GIL).  The draws stay in emcee's order because the
-        # stream is sequential: block k+1 is drawn right after block k, only earlier in time.
-        draws, states = self._draw(min(self.block, iterations)) if iterations > 0 else (None, None)
-        while done < iterations:
-            n = min(self.block, iterations - done)
-            n_next = min(self.block, iterations - done - n)
-            block_states = states
+        eng = self.model.engine
+
+        def launch(draws):
             if self.ranks is not None:
-                # collectives are issued from this thread, in the same order on every rank
-                result = self._run_block_sharded(p, lnprob, *draws, nacc, store=True,
-                                                 accumulate=self.accumulate)
-                draws, states = self._draw(n_next) if n_next > 0 else (None, None)
-            else:
-                # (`moves`: the draws carry kind and partner_b as well -- Context.move_run's arguments)
-                run = self.model.engine.stretch_run if self._moves is None else self.model.engine.move_run
-                job = _run_async(run, p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
-                try:
-                    draws, states = self._draw(n_next) if n_next > 0 else (None, None)
-                finally:
-                    result = job()
+                return self._run_block_sharded(p, lnprob, draws, nacc, store=True, accumulate=self.accumulate)
+            run = eng.stretch_run if draws.kind is None else eng.move_run
+            return run(p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
+
+        # sharded: collectives are issued from this thread, and this rank sums its block of the walkers
+        lo, hi = (0, self.k) if self.ranks is None else self.ranks.block(self.k)
+        for done, n, result, states in _run_blocks(iterations, self.block, self._draw, launch,
+                                                   overlap=self.ranks is None):
             p, lnprob, chain, lnchain = result
-            if self.accumulate:                 # sharded: this rank summed its block of the walkers
-                share = n * self.k if self.ranks is None else n * (lambda b: b[1] - b[0])(self.ranks.block(self.k))
-                self.model._device_samples += share
-                self.model.accumulated_samples += share
+            if self.accumulate:
+                self._count_accumulated(n * (hi - lo))
             # per-block bookkeeping in whole-array operations: at a few hundred microseconds
             # per iteration on the GPU, per-iteration numpy calls here were 10 % of the run
             if storechain:
-                # kept iterations of this block: (done + i) % thin == 0 -- an arithmetic
-                # progression, copied with slices (index arrays made this 1.6 ms per block)
-                first = (-done) % thin
-                if first < n:
-                    count = (n - first + thin - 1) // thin
-                    dst = i0 + (done + first) // thin
-                    self._chain[:, dst:dst + count, :] = chain[:, first::thin, :]
-                    self._lnprob[:, dst:dst + count] = lnchain[:, first::thin]
+                self._store_block(i0, done, n, thin, chain, lnchain)
             # counters advance with the block (the device reports acceptances per block), so
             # `acceptance_fraction` is consistent whenever the consumer looks; the yielded
             # generator state is the one right after iteration j's draws, so that
@@ -631,11 +800,10 @@ class DeviceEnsembleSampler(EnsembleSampler):
             self.naccepted = nacc.astype(np.float64)
             self.iterations += n
             for j in range(n):
-                yield chain[:, j, :].copy(), lnchain[:, j].copy(), block_states[j]
-            done += n
+                yield chain[:, j, :].copy(), lnchain[:, j].copy(), states[j]
 
 
-class _FieldChain(EnsembleSampler):
+class _FieldChain(_EnsembleMember, EnsembleSampler):
     """One field's share of a `FieldSetSampler`: the emcee-style state (chain, lnprobability,
     acceptance counters, random state) of that field's ensemble -- what `save_database`,
     `check_convergence_autocorr` and the reference's own post-processing read."""
@@ -645,12 +813,8 @@ class _FieldChain(EnsembleSampler):
                                           batch_lnpostfn=model.log_posterior_batch)
         self.model = model
 
-    _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
-    _draw = DeviceEnsembleSampler._draw
-    _draw_moves = DeviceEnsembleSampler._draw_moves
 
-
-class FieldSetSampler(object):
+class FieldSetSampler(_FieldMembers):
     """The device-resident stretch-move sampler for every field of a `models.FieldSet` at once
     (`psfmc_stretch_run_fields`): each field is its own ensemble of `nwalkers` walkers with its own
     `RandomState` -- exactly the `DeviceEnsembleSampler` of that field alone -- but the half-step
@@ -674,101 +838,55 @@ class FieldSetSampler(object):
         self.block = int(block)
         self.accumulate = bool(accumulate)
         self.fields = [_FieldChain(nwalkers, m, a=a) for m in fieldset.models]
-        self._moves = None
 
-    def set_moves(self, moves):
-        """`EnsembleSampler.set_moves` for every field's ensemble."""
-        self._moves = None if moves is None else _parse_moves(moves, self.k)[0]
-        for f in self.fields:
-            f.set_moves(moves)
+    def _draw(self, n_iter):
+        """Every field's draws from its own generator, stacked by name: z, lz, partner, log_u [F, n_iter, 2, W/2]
+        for `stretch_run`; with moves the shapes of `pt_move_run_fields` with one rung."""
+        if self.fields[0]._moves is not None:
+            return super(FieldSetSampler, self)._draw(n_iter, one_rung=True)
+        per = [f._draw(n_iter) for f in self.fields]
+        return (_Draws(**{name: np.ascontiguousarray([getattr(d, name) for d, _ in per])
+                          for name in ('z', 'lz', 'partner', 'log_u')}), [s for _, s in per])
 
-    def reset(self):
-        for f in self.fields:
-            f.reset()
-
-    def clear_blobs(self):
-        pass
+    def _run_one_rung(self, pos, lnp, draws, counters):
+        """A block with moves: every field one rung at beta = 1, where lnp = 1 lnL + lnpi is the walker's
+        log-posterior bit for bit; a walker enters as (lnL, lnpi) = (lnp, 0), the same sum."""
+        n_f = len(self.fields)
+        none = np.empty((len(draws.kind), n_f, 0, self.k))
+        t_acc = np.ascontiguousarray(counters[:, np.newaxis, :])
+        out = self.fieldset.context.pt_move_run_fields(
+            np.ones(1), pos[:, np.newaxis], lnp[:, np.newaxis], np.zeros((n_f, 1, self.k)), *draws, none, none, none,
+            naccepted=t_acc, nswap=np.zeros((n_f, 0), dtype=np.int64), store=True, accumulate=self.accumulate)
+        counters[...] = t_acc[:, 0]
+        return out[0][:, 0], out[4][:, :, -1].copy(), out[3][:, 0], out[4]
 
     def sample(self, p0, lnprob0=None, iterations=1, thin=1, storechain=True):
         """p0: [F, W, P] (or a list of [W, P]) start positions; lnprob0 likewise or None.  Yields, once per
         iteration, the list over fields of (pos, lnprob, rstate)."""
-        ctx = self.fieldset.context
         n_f = len(self.fields)
         p = np.array([np.asarray(q, dtype=np.float64) for q in p0])
-        if p.shape != (n_f, self.k, self.dim):
-            raise ValueError('p0 must have shape ({}, {}, {})'.format(n_f, self.k, self.dim))
-        if np.any(~np.isfinite(p)):
-            raise ValueError('At least one parameter value was infinite or NaN.')
         lnprob = None if lnprob0 is None else np.array([np.asarray(q, dtype=np.float64) for q in lnprob0])
-        if lnprob is None:
-            lnprob = np.array(self.fieldset.log_posterior_batch(list(p)))
-        if np.any(np.isnan(lnprob)):
-            raise ValueError('The initial lnprob was NaN.')
-        i0 = [f._chain.shape[1] for f in self.fields]
-        if storechain:
-            n_keep = int(iterations // thin)
-            for f in self.fields:
-                f._chain = np.concatenate((f._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
-                f._lnprob = np.concatenate((f._lnprob, np.zeros((self.k, n_keep))), axis=1)
+        lnprob = _check_start(p, lnprob, (n_f, self.k, self.dim),
+                              lambda q: np.array(self.fieldset.log_posterior_batch(list(q))))
+        i0 = [f._grow_storage(iterations, thin, storechain) for f in self.fields]
         nacc = np.ascontiguousarray([f.naccepted.astype(np.int64) for f in self.fields])
-        done = 0
 
-        moves = self._moves is not None
+        def launch(draws):
+            if draws.kind is not None:
+                return self._run_one_rung(p, lnprob, draws, nacc)
+            return self.fieldset.context.stretch_run(p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
 
-        def draw(n):
-            per = [f._draw(n) for f in self.fields]            # every field from its own generator
-            if moves:
-                # (scalar, Hastings term, a, ln u, b: [n_iter, 2, F, 1, W/2]; kind: [n_iter, F] -- the shapes of
-                # `pt_move_run_fields` with one rung)
-                arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2)[:, :, :, np.newaxis, :])
-                          for j in (0, 1, 2, 3, 5)]
-                arrays.insert(4, np.ascontiguousarray(np.stack([d[0][4] for d in per], axis=1)))
-                return arrays, [d[1] for d in per]
-            arrays = [np.ascontiguousarray([d[0][j] for d in per]) for j in range(4)]
-            return arrays, [d[1] for d in per]
-
-        def run_moves(pos, lnp, draws, counters):
-            """A block with moves: every field one rung at beta = 1, where lnp = 1 lnL + lnpi is the walker's
-            log-posterior bit for bit; a walker enters as (lnL, lnpi) = (lnp, 0), the same sum."""
-            n_it = len(draws[4])
-            none = np.empty((n_it, n_f, 0, self.k))
-            t_acc = np.ascontiguousarray(counters[:, np.newaxis, :])
-            out = ctx.pt_move_run_fields(np.ones(1), pos[:, np.newaxis], lnp[:, np.newaxis],
-                                         np.zeros((n_f, 1, self.k)), *draws, none, none, none, naccepted=t_acc,
-                                         nswap=np.zeros((n_f, 0), dtype=np.int64), store=True,
-                                         accumulate=self.accumulate)
-            counters[...] = t_acc[:, 0]
-            return out[0][:, 0], out[4][:, :, -1].copy(), out[3][:, 0], out[4]
-
-        draws, states = draw(min(self.block, iterations)) if iterations > 0 else (None, None)
-        while done < iterations:
-            n = min(self.block, iterations - done)
-            n_next = min(self.block, iterations - done - n)
-            block_states = states
-            if moves:
-                job = _run_async(run_moves, p, lnprob, draws, nacc)
-            else:
-                job = _run_async(ctx.stretch_run, p, lnprob, *draws, nacc, store=True, accumulate=self.accumulate)
-            try:
-                draws, states = draw(n_next) if n_next > 0 else (None, None)
-            finally:
-                p, lnprob, chain, lnchain = job()
-            first = (-done) % thin
+        for done, n, result, states in _run_blocks(iterations, self.block, self._draw, launch):
+            p, lnprob, chain, lnchain = result
             for i, f in enumerate(self.fields):
                 if self.accumulate:
-                    f.model._device_samples += n * self.k
-                    f.model.accumulated_samples += n * self.k
-                if storechain and first < n:
-                    count = (n - first + thin - 1) // thin
-                    dst = i0[i] + (done + first) // thin
-                    f._chain[:, dst:dst + count, :] = chain[i][:, first::thin, :]
-                    f._lnprob[:, dst:dst + count] = lnchain[i][:, first::thin]
+                    f._count_accumulated(n * self.k)
+                if storechain:
+                    f._store_block(i0[i], done, n, thin, chain[i], lnchain[i])
                 f.naccepted = nacc[i].astype(np.float64)
                 f.iterations += n
             for j in range(n):
-                yield [(chain[i][:, j, :].copy(), lnchain[i][:, j].copy(), block_states[i][j])
-                       for i in range(n_f)]
-            done += n
+                yield [(chain[i][:, j, :].copy(), lnchain[i][:, j].copy(), states[i][j]) for i in range(n_f)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -828,7 +946,7 @@ def _stepping_stone(betas, lnlike):
     return total
 
 
-class TemperedEnsembleSampler(object):
+class TemperedEnsembleSampler(_SamplerState):
     """Parallel-tempered stretch-move sampler: T copies of an ensemble of `nwalkers` walkers sample the tempered
     posteriors beta_t lnL + lnpi on the ladder `betas` (1 = beta_0 > ... > beta_{T-1} = 0), and neighbouring
     rungs swap walkers.  The stored lnL samples of every rung give the Bayesian evidence (`log_evidence`).
@@ -869,9 +987,6 @@ class TemperedEnsembleSampler(object):
         self._moves = self._move_cum = None
         self.reset()
 
-    set_moves = EnsembleSampler.set_moves           # (DE needs 4 walkers per rung)
-    _select_move = EnsembleSampler._select_move
-
     def reset(self):
         self.iterations = 0
         self.naccepted_t = np.zeros((self.ntemps, self.k))
@@ -882,31 +997,9 @@ class TemperedEnsembleSampler(object):
 
     clear_chain = reset
 
-    def clear_blobs(self):
-        pass
-
-    random_state = EnsembleSampler.random_state
-
     @property
     def naccepted(self):
         return self.naccepted_t[0]
-
-    @property
-    def chain(self):
-        return self._chain
-
-    @property
-    def flatchain(self):
-        s = self._chain.shape
-        return self._chain.reshape(s[0] * s[1], s[2])
-
-    @property
-    def lnprobability(self):
-        return self._lnprob
-
-    @property
-    def flatlnprobability(self):
-        return self._lnprob.flatten()
 
     @property
     def lnlikelihood(self):
@@ -923,9 +1016,6 @@ class TemperedEnsembleSampler(object):
     @property
     def tswap_acceptance_fraction(self):
         return self.nswap / (max(self.iterations, 1) * self.k)
-
-    get_autocorr_time = EnsembleSampler.get_autocorr_time
-    acor = EnsembleSampler.acor
 
     def log_evidence(self, fburnin=0.1):
         """(ln Z, err): the stepping-stone estimate from the stored lnL samples of every rung after the first
@@ -962,11 +1052,9 @@ class TemperedEnsembleSampler(object):
         return ll, lp
 
     def _grow_storage(self, iterations, thin, storechain):
-        i0 = self._chain.shape[1]
+        i0 = super(TemperedEnsembleSampler, self)._grow_storage(iterations, thin, storechain)
         if storechain:
             n_keep = int(iterations // thin)
-            self._chain = np.concatenate((self._chain, np.zeros((self.k, n_keep, self.dim))), axis=1)
-            self._lnprob = np.concatenate((self._lnprob, np.zeros((self.k, n_keep))), axis=1)
             self._lnlike = np.concatenate((self._lnlike, np.zeros((self.ntemps, self.k, n_keep))), axis=2)
         return i0
 
@@ -1038,7 +1126,7 @@ class TemperedEnsembleSampler(object):
         return results
 
 
-class DeviceTemperedSampler(TemperedEnsembleSampler):
+class DeviceTemperedSampler(_LadderMember, TemperedEnsembleSampler):
     """`TemperedEnsembleSampler` with every rung resident on the GPU (`psfmc_pt_run`): proposals of all T rungs
     in one launch per half-step, one pipeline pass over T W/2 records, the tempered accept, the swaps and the
     chain entries on the device.  The host draws the random numbers from the same `RandomState` in the same
@@ -1084,50 +1172,6 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
             raise ValueError('priors {} are evaluated on the host: the tempered device sampler cannot be '
                              'used'.format([p.name for p, _ in model._host_priors]))
 
-    _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
-
-    def _draw(self, n_iter):
-        """Random numbers of n_iter iterations in the host sampler's order: the arrays of `Context.pt_run` or,
-        with moves set, of `Context.pt_move_run` -- the selector `rand()` of every iteration drawn here too (more
-        than one move only), z the moves' scalar, lz their Hastings term, kind [n_iter] and partner_b added."""
-        n_t, n_w, half = self.ntemps, self.k, self.k // 2
-        n_s = max(n_t - 1, 0)
-        z = np.empty((n_iter, 2, n_t, half))
-        partner = np.empty((n_iter, 2, n_t, half), dtype=np.int32)
-        log_u = np.empty((n_iter, 2, n_t, half))
-        si = np.empty((n_iter, n_s, n_w), dtype=np.int32)
-        sj = np.empty((n_iter, n_s, n_w), dtype=np.int32)
-        slu = np.empty((n_iter, n_s, n_w))
-        moves = self._moves is not None
-        if moves:
-            lz = np.empty((n_iter, 2, n_t, half))
-            partner_b = np.zeros((n_iter, 2, n_t, half), dtype=np.int32)
-            kind = np.empty(n_iter, dtype=np.int32)
-        rs = self._random
-        states = []
-        snap = self._state_snapshotter()
-        for it in range(n_iter):
-            if moves:
-                move = self._moves[self._select_move()]
-                kind[it] = move.kind
-            for h in range(2):
-                for t in range(n_t):
-                    if moves:
-                        z[it, h, t], lz[it, h, t], partner[it, h, t], partner_b[it, h, t], log_u[it, h, t] = \
-                            move.draw(rs, half, self.dim)
-                        continue
-                    z[it, h, t] = ((self.a - 1.0) * rs.rand(half) + 1) ** 2.0 / self.a
-                    partner[it, h, t] = rs.randint(half, size=(half,))
-                    log_u[it, h, t] = np.log(rs.rand(half))
-            for t in range(n_t - 1, 0, -1):
-                si[it, t - 1] = rs.permutation(n_w)
-                sj[it, t - 1] = rs.permutation(n_w)
-                slu[it, t - 1] = np.log(rs.rand(n_w))
-            states.append(snap())
-        if moves:
-            return (z, lz, partner, log_u, kind, partner_b, si, sj, slu), states
-        return (z, (self.dim - 1.0) * np.log(z), partner, log_u, si, sj, slu), states
-
     def sample(self, p0, lnlike0=None, lnprior0=None, rstate0=None, iterations=1, thin=1, storechain=True):
         if rstate0 is not None:
             self.random_state = rstate0
@@ -1139,42 +1183,26 @@ class DeviceTemperedSampler(TemperedEnsembleSampler):
         nacc = self.naccepted_t.astype(np.int64)
         nsw = self.nswap.astype(np.int64)
         eng = self.model.engine
-        done = 0
-        # the next block's random numbers are drawn while the GPU runs the current one (DeviceEnsembleSampler)
-        draws, states = self._draw(min(self.block, iterations)) if iterations > 0 else (None, None)
-        while done < iterations:
-            n = min(self.block, iterations - done)
-            n_next = min(self.block, iterations - done - n)
-            block_states = states
-            # (moves: the draws carry kind and partner_b as well -- Context.pt_move_run's arguments)
-            run = eng.pt_run if len(draws) == 7 else eng.pt_move_run
-            job = _run_async(run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
-                             accumulate=self.accumulate)
-            try:
-                draws, states = self._draw(n_next) if n_next > 0 else (None, None)
-            finally:
-                p, ll, lp, chain, lnchain, llchain, lpchain = job()
+
+        def launch(draws):
+            run = eng.pt_run if draws.kind is None else eng.pt_move_run
+            return run(self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
+                       accumulate=self.accumulate)
+
+        for done, n, result, states in _run_blocks(iterations, self.block, self._draw, launch):
+            p, ll, lp, chain, lnchain, llchain, lpchain = result
             if self.accumulate:
-                self.model._device_samples += n * self.k
-                self.model.accumulated_samples += n * self.k
+                self._count_accumulated(n * self.k)
             if storechain:
-                first = (-done) % thin
-                if first < n:
-                    count = (n - first + thin - 1) // thin
-                    dst = i0 + (done + first) // thin
-                    self._chain[:, dst:dst + count, :] = chain[0, :, first::thin, :]
-                    self._lnprob[:, dst:dst + count] = lnchain[:, first::thin]
-                    self._lnlike[:, :, dst:dst + count] = llchain[:, :, first::thin]
+                self._store_block(i0, done, n, thin, chain, lnchain, llchain)
             self.naccepted_t = nacc.astype(np.float64)
             self.nswap = nsw.astype(np.float64)
             self.iterations += n
             for j in range(n):
-                yield (chain[:, :, j, :].copy(), llchain[:, :, j].copy(), lpchain[:, :, j].copy(),
-                       block_states[j])
-            done += n
+                yield chain[:, :, j, :].copy(), llchain[:, :, j].copy(), lpchain[:, :, j].copy(), states[j]
 
 
-class _FieldLadder(TemperedEnsembleSampler):
+class _FieldLadder(_LadderMember, TemperedEnsembleSampler):
     """One field's share of a `FieldSetTemperedSampler`: the `TemperedEnsembleSampler` state of that field's
     ladder (chain, lnprobability, lnlikelihood, counters, random state, `log_evidence`) -- what `save_database`
     and `check_convergence_autocorr` read -- and its draws, `DeviceTemperedSampler`'s from its own generator."""
@@ -1184,11 +1212,8 @@ class _FieldLadder(TemperedEnsembleSampler):
                                            model.log_likelihood_and_prior_batch, a=a)
         self.model = model
 
-    _state_snapshotter = DeviceEnsembleSampler._state_snapshotter
-    _draw = DeviceTemperedSampler._draw
 
-
-class FieldSetTemperedSampler(object):
+class FieldSetTemperedSampler(_FieldMembers):
     """The parallel-tempered device sampler for every field of a `models.FieldSet` at once
     (`psfmc_pt_run_fields`): each field is its own ladder of T ensembles of `nwalkers` walkers with its own
     `RandomState` -- exactly the `DeviceTemperedSampler` of that field alone on its own context -- but the
@@ -1218,18 +1243,6 @@ class FieldSetTemperedSampler(object):
         self.accumulate = bool(accumulate)
         self.fields = [_FieldLadder(nwalkers, m, self.betas, a=a) for m in fieldset.models]
 
-    def set_moves(self, moves):
-        """`TemperedEnsembleSampler.set_moves` for every field's ladder."""
-        for f in self.fields:
-            f.set_moves(moves)
-
-    def reset(self):
-        for f in self.fields:
-            f.reset()
-
-    def clear_blobs(self):
-        pass
-
     def sample(self, p0, lnlike0=None, lnprior0=None, iterations=1, thin=1, storechain=True):
         """p0: [F, T, W, P] (or a list of [T, W, P]) start positions; lnlike0 / lnprior0 [F, T, W] or None
         (evaluated).  Yields, once per iteration, the list over fields of (pos [T, W, P], lnL [T, W],
@@ -1246,44 +1259,23 @@ class FieldSetTemperedSampler(object):
         i0 = [f._grow_storage(iterations, thin, storechain) for f in self.fields]
         nacc = np.ascontiguousarray([f.naccepted_t.astype(np.int64) for f in self.fields])
         nsw = np.ascontiguousarray([f.nswap.astype(np.int64) for f in self.fields])
-        done = 0
 
-        def draw(n):
-            per = [f._draw(n) for f in self.fields]            # every field from its own generator
-            # (z, lz, partner, log_u and, with moves, partner_b: [n_iter, 2, F, T, W/2]; the swaps' three:
-            # [n_iter, F, T-1, W]; with moves, kind: [n_iter, F])
-            arrays = [np.ascontiguousarray(np.stack([d[0][j] for d in per], axis=2 if per[0][0][j].ndim == 4 else 1))
-                      for j in range(len(per[0][0]))]
-            return arrays, [d[1] for d in per]
+        def launch(draws):
+            run = ctx.pt_run_fields if draws.kind is None else ctx.pt_move_run_fields
+            return run(self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw, store=True,
+                       accumulate=self.accumulate)
 
-        # the next block's random numbers are drawn while the GPU runs the current one (DeviceEnsembleSampler)
-        draws, states = draw(min(self.block, iterations)) if iterations > 0 else (None, None)
-        while done < iterations:
-            n = min(self.block, iterations - done)
-            n_next = min(self.block, iterations - done - n)
-            block_states = states
-            run = ctx.pt_run_fields if len(draws) == 7 else ctx.pt_move_run_fields
-            job = _run_async(run, self.betas, p, ll, lp, *draws, naccepted=nacc, nswap=nsw,
-                             store=True, accumulate=self.accumulate)
-            try:
-                draws, states = draw(n_next) if n_next > 0 else (None, None)
-            finally:
-                p, ll, lp, chain, lnchain, llchain, lpchain = job()
-            first = (-done) % thin
+        for done, n, result, states in _run_blocks(iterations, self.block, self._draw, launch):
+            p, ll, lp, chain, lnchain, llchain, lpchain = result
             for i, f in enumerate(self.fields):
                 if self.accumulate:
-                    f.model._device_samples += n * self.k
-                    f.model.accumulated_samples += n * self.k
-                if storechain and first < n:
-                    count = (n - first + thin - 1) // thin
-                    dst = i0[i] + (done + first) // thin
-                    f._chain[:, dst:dst + count, :] = chain[i, 0, :, first::thin, :]
-                    f._lnprob[:, dst:dst + count] = lnchain[i][:, first::thin]
-                    f._lnlike[:, :, dst:dst + count] = llchain[i][:, :, first::thin]
+                    f._count_accumulated(n * self.k)
+                if storechain:
+                    f._store_block(i0[i], done, n, thin, chain[i], lnchain[i], llchain[i])
                 f.naccepted_t = nacc[i].astype(np.float64)
                 f.nswap = nsw[i].astype(np.float64)
                 f.iterations += n
             for j in range(n):
                 yield [(chain[i, :, :, j, :].copy(), llchain[i, :, :, j].copy(), lpchain[i, :, :, j].copy(),
-                        block_states[i][j]) for i in range(n_f)]
-            done += n
+                        states[i][j]) for i in range(n_f)]
+
