@@ -850,6 +850,35 @@ int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* base_col, c
                                  double* out_const, int* out_col, int* out_kinds, int* out_sides, int* counts);
 
 /*
+ * Fisher matrix and gradient of the Gaussian log-likelihood
+ *   lnL = -1/2 sum_good [ r^2 w - ln(w / 2 pi) ],  r = sci - conv,  w = 1 / (model_var + obs_var)
+ * at n_base points, from central-difference stencils of images (the definition: psfmc_amd/mode.py
+ * fisher_from_stencil).  A stencil of K differentiated columns is 2K + 1 walkers: the base
+ * vector, then theta + h_k e_k and theta - h_k e_k for k = 0 ... K-1.
+ *   rows    [n_base][2K+1][row_len]  derived rows exactly as psfmc_eval_images[_field] takes them (a context with an
+ *                                    aux layout: psfmc_set_aux_rows for the n_base (2K+1) walkers first)
+ *   inv2h   [n_base][K]              1 / (2 h_k)
+ *   F       [n_base][K][K]           out: sum_good w dmu_k dmu_l + 1/2 sum_good w^2 dv_k dv_l  (exactly symmetric)
+ *   g       [n_base][K]              out: d lnL / d theta_k = sum_good r w dmu_k + 1/2 sum_good (r^2 w^2 - w) dv_k
+ *   lnlike  [n_base]                 out: the base's log-likelihood, the bits psfmc_eval_batch gives for its row
+ * 1 <= K <= 63 and n_base (2K+1) <= max_walkers.  The walkers run in passes of psfmc_get_option "chunk_walkers" like
+ * psfmc_eval_images'; a stencil may straddle passes, and its F, g and lnlike do not depend on where in the batch it
+ * stands or on what stands beside it.  "good": not in bad_px and a finite base weight; an image that is not finite
+ * on a good pixel (or a negative weight) gives NaN results for that stencil, not an error.  Both back ends.
+ * PSFMC_EINVAL with "storage_f32" on: images good to 1e-7 divided by a 1e-4 step are noise.  A context that never
+ * calls this allocates and launches nothing for it.
+ */
+int psfmc_fisher_rows(psfmc_ctx* ctx, int field, int n_base, int K, const double* rows, const double* inv2h,
+                      double* F, double* g, double* lnlike);
+/*
+ * Diagnostic hook: the Gram and finish kernels of psfmc_fisher_rows alone, on caller-supplied per-pixel vectors
+ * a, b [K][n_pix] and c, d [n_pix]:  F = sum_pix (a a^T + b b^T) [K][K],  g_k = sum_pix (a_k c + b_k d) [K].
+ * Small-integer data make every product and sum exact in fp64, so a wrong lane map shows as a wrong integer.
+ */
+int psfmc_debug_fisher_gram(int device, int K, int n_pix, const double* a, const double* b, const double* c,
+                            const double* d, double* F, double* g);
+
+/*
  * Diagnostic hook: time `reps` plain sweeps over a scratch buffer of nbytes (>= 1 MiB) -- mode 0
  * every byte written once, 1 read and written back in place, 2 read once: the memory traffic of
  * the three kernels of a pass without their arithmetic.  *us_per_sweep = average microseconds.

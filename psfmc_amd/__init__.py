@@ -11,10 +11,12 @@ from .parallel import RankGroup, ShardedLogPosterior
 from .fitting import (model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc,
                       model_joint_ptmcmc, model_fields_ptmcmc)
 from .database import load_database
+from .mode import find_mode
 
 __version__ = '0.1.0'
 __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior', 'EnsembleSampler',
            'DeviceEnsembleSampler', 'FieldSetSampler', 'TemperedEnsembleSampler', 'DeviceTemperedSampler',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
            'model_joint_mcmc', 'model_galaxy_ptmcmc', 'model_joint_ptmcmc', 'load_database', 'Moffat', 'Ferrer',
-           'StretchMove', 'DEMove', 'FieldSetTemperedSampler', 'model_fields_ptmcmc']
+           'StretchMove', 'DEMove', 'FieldSetTemperedSampler', 'model_fields_ptmcmc',
+           'find_mode']

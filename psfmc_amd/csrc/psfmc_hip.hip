@@ -38,6 +38,7 @@
 #include "psfmc_general.h"
 #include "psfmc_general_mean.h"
 #include "psfmc_aux_table.h"
+#include "psfmc_fisher.h"
 #endif
 
 using namespace psfmc;
@@ -313,6 +314,12 @@ struct psfmc_ctx {
     // [n_fields][n_sersic] the flags, then [n_fields][n_sersic] the general flags with the mean components cleared
     // (what k_general_rows reads in a context with mean components)
     uint8_t* d_mean_flags = nullptr;
+    // psfmc_fisher_rows (psfmc_fisher.h): the stencil walkers' stashed images, the Gram kernel's partial tiles and the
+    // step reciprocals / results; grow-only, nothing is allocated until the first call
+    struct Fisher {
+        double *stash = nullptr, *partial = nullptr, *io = nullptr;
+        size_t cap_stash = 0, cap_partial = 0, cap_io = 0;
+    } fisher;
 };
 
 // the extra image of the walker whose record `prep` points at (nullptr: none to add)
@@ -1429,7 +1436,8 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->d_wrap, c->d_field_sides, c->d_Ts[2], c->d_Ts[3], c->stretch.pos, c->stretch.lnp, c->stretch.q, c->stretch.newlnp,
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->stretch.kind, c->stretch.partner_b, c->pt_blob, c->d_integ_flags, c->d_integ_par,
-                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_mean_flags};
+                    c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_mean_flags, c->fisher.stash, c->fisher.partial,
+                    c->fisher.io};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (const psfmc_ctx::AuxBlockState& k : c->blk) {
@@ -2008,6 +2016,29 @@ static int ensure_image_staging(psfmc_ctx* c) {
     return PSFMC_OK;
 }
 
+// The image flow, shared by psfmc_eval_images[_field] and psfmc_fisher_rows: host rows (and the aux rows the caller
+// left) of W walkers of `field` -> prep records in c->d_prep, then passes of up to c->chunk walkers each.
+static int images_begin(psfmc_ctx* c, int field, int W, const double* rows, hipStream_t st) {
+    RC_TRY(take_aux_rows(c, W));
+    HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
+    c->prep_tabs_valid = false;                       // d_prep is being rewritten
+    hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
+                       c->n_sersic, c->wraps[field].ly, c->wraps[field].lx, c->d_rho, c->n_psf_field, field * c->n_psf_field);
+    launch_pow_tables(c, W, 0, nullptr, st);
+    return ensure_image_staging(c);
+}
+// One pass: the convolved model and model variance of the n walkers whose records start at `prep`, in c->d_img0 /
+// c->d_img1 (fused) or interleaved in c->d_real (hipFFT: image_source).  `partial`: where the fused pass leaves the
+// walkers' chi^2 partial sums.
+static int image_pass(psfmc_ctx* c, int n, const double* prep, int ps_only, double* raw_dev, double* partial,
+                      hipStream_t st) {
+    if (c->backend == PSFMC_BACKEND_FUSED) {
+        RC_TRY(fused_forward(c, n, c->d_T, prep, nullptr, ps_only, raw_dev, st));
+        return fused_inverse(c, n, c->d_T, prep, nullptr, partial, c->d_img0, c->d_img1, st);
+    }
+    return hipfft_convolve(c, n, prep, nullptr, st, ps_only);
+}
+
 static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, double* raw, double* conv,
                             double* resid, double* ivm, double* ps_sub) {
     int rc = check_call(c, W, rows, rows);
@@ -2020,13 +2051,7 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
     const bool fused = c->backend == PSFMC_BACKEND_FUSED;
     const size_t S_img = img_pixels(c, field);                  // pixels of a host image (the field's own shape)
     const size_t img = S_img * sizeof(double);
-    RC_TRY(take_aux_rows(c, W));
-    HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
-    c->prep_tabs_valid = false;                       // d_prep is being rewritten
-    hipLaunchKernelGGL(k_prep, dim3((W + 127) / 128), dim3(128), 0, st, c->d_rows, c->d_prep, W, c->n_ps,
-                       c->n_sersic, c->wraps[field].ly, c->wraps[field].lx, c->d_rho, c->n_psf_field, field * c->n_psf_field);
-    launch_pow_tables(c, W, 0, nullptr, st);
-    RC_TRY(ensure_image_staging(c));
+    RC_TRY(images_begin(c, field, W, rows, st));
     double *d_out = nullptr, *d_rawdev = nullptr;     // [chunk] staging for derived images / the raw models (transform shape)
     HIP_TRY(hipMalloc(&d_out, (size_t)c->chunk * img));
     if (raw && fused && hipMalloc(&d_rawdev, (size_t)c->chunk * c->S * sizeof(double)) != hipSuccess) {
@@ -2050,11 +2075,7 @@ static int eval_images_impl(psfmc_ctx* c, int field, int W, const double* rows, 
             return PSFMC_OK;
         };
         auto pass = [&](int ps_only, double* raw_dev) -> int {
-            if (fused) {
-                RC_TRY(fused_forward(c, n, c->d_T, prep, nullptr, ps_only, raw_dev, st));
-                return fused_inverse(c, n, c->d_T, prep, nullptr, c->d_partial, c->d_img0, c->d_img1, st);
-            }
-            return hipfft_convolve(c, n, prep, nullptr, st, ps_only);
+            return image_pass(c, n, prep, ps_only, raw_dev, c->d_partial, st);
         };
         if (raw && !fused) {   // raw model before the inverse transform overwrites it
             hipLaunchKernelGGL(k_raster, dim3((c->S + 1023) / 1024, n), dim3(256),
@@ -4423,6 +4444,96 @@ extern "C" int psfmc_group_eval_theta(psfmc_group* g, int W, const double* theta
                                       double* lnprob) {
     if (W > 0 && !theta) return fail(PSFMC_EINVAL, "NULL theta");
     return group_eval(g, W, nullptr, nullptr, theta, extra_lnprior, lnprob);
+}
+
+// ---------------------------------------------------------------------------
+// Fisher matrix and gradient of stencils of walkers (psfmc_fisher.h): the image flow of psfmc_eval_images, each pass's
+// images stashed, then one Gram launch over every stencil
+// ---------------------------------------------------------------------------
+extern "C" int psfmc_fisher_rows(psfmc_ctx* c, int field, int n_base, int K, const double* rows, const double* inv2h,
+                                 double* F, double* g, double* lnlike) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (!rows || !inv2h || !F || !g || !lnlike) return fail(PSFMC_EINVAL, "NULL buffer");
+    if (c->t_f32)
+        return fail(PSFMC_EINVAL, "psfmc_fisher_rows needs fp64 storage: differences of complex64-stored images over a "
+                    "1e-4 step are rounding noise");
+    const int n_pix = (int)img_pixels(c, field);
+    FisherPlan plan;
+    if (const char* why = fisher_plan(n_base, K, c->max_walkers, (size_t)n_pix, &plan))
+        return fail(PSFMC_EINVAL, "psfmc_fisher_rows: %s (n_base=%d, K=%d, max_walkers=%d)", why, n_base, K,
+                    c->max_walkers);
+    const int W = plan.W;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const bool fused = c->backend == PSFMC_BACKEND_FUSED;
+    const size_t px = (size_t)field * c->S;                          // this field's pixels
+    RC_TRY(images_begin(c, field, W, rows, st));
+    psfmc_ctx::Fisher& fi = c->fisher;
+    RC_TRY(grow(&fi.stash, &fi.cap_stash, plan.stash_doubles));
+    RC_TRY(grow(&fi.partial, &fi.cap_partial, plan.partial_doubles));
+    RC_TRY(grow(&fi.io, &fi.cap_io, plan.io_doubles));
+    double* d_inv2h = fi.io;
+    double* d_F = d_inv2h + (size_t)n_base * K;
+    double* d_g = d_F + (size_t)n_base * K * K;
+    HIP_TRY(hipMemcpyAsync(d_inv2h, inv2h, (size_t)n_base * K * sizeof(double), hipMemcpyHostToDevice, st));
+    // where the convolved model / model variance of walker w live after a pass (as eval_images_impl)
+    const double* conv_src = fused ? c->d_img0 : c->d_real;
+    const double* var_src = fused ? c->d_img1 : c->d_real;
+    const int stride = fused ? 1 : 2, var_c = fused ? 0 : 1;
+    for (int w0 = 0; w0 < W; w0 += c->chunk) {
+        const int n = W - w0 < c->chunk ? W - w0 : c->chunk;
+        const double* prep = c->d_prep + (size_t)w0 * c->plen;
+        double* partial = c->d_partial + (size_t)w0 * c->nblk;
+        RC_TRY(image_pass(c, n, prep, 0, nullptr, partial, st));
+        if (!fused)
+            hipLaunchKernelGGL(k_chi2, dim3(c->nblk, n), dim3(256), 0, st, c->d_real, c->d_sci + px, c->d_var + px,
+                               c->d_bad + px, (const uint8_t*)nullptr, partial, c->S);
+        hipLaunchKernelGGL(k_fisher_stash, dim3(16, n), dim3(256), 0, st, conv_src, var_src,
+                           fi.stash + (size_t)w0 * 2 * n_pix, c->S, stride, var_c, img_window(c, field));
+    }
+    hipLaunchKernelGGL(k_finish, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       (const uint8_t*)nullptr, c->d_like, W, c->nblk);
+    const FisherStencil src{fi.stash, d_inv2h, c->d_sci + px, c->d_var + px, c->d_bad + px, img_window(c, field)};
+    launch_fisher_gram(src, n_base, K, n_pix, plan, fi.partial, d_F, d_g, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> like(W);
+    HIP_TRY(hipMemcpyAsync(F, d_F, (size_t)n_base * K * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(g, d_g, (size_t)n_base * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(like.data(), c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < n_base; ++b) lnlike[b] = like[(size_t)b * (2 * K + 1)];
+    return PSFMC_OK;
+}
+
+// the Gram and finish kernels alone on caller-supplied vectors: a, b [K][n_pix], c, d [n_pix] -> F [K][K], g [K]
+extern "C" int psfmc_debug_fisher_gram(int device, int K, int n_pix, const double* a, const double* b, const double* c,
+                                       const double* d, double* F, double* g) {
+    if (!a || !b || !c || !d || !F || !g) return fail(PSFMC_EINVAL, "NULL buffer");
+    FisherPlan plan;
+    if (const char* why = fisher_plan(1, K, 2 * kFisherMaxK + 1, n_pix < 0 ? 0 : (size_t)n_pix, &plan))
+        return fail(PSFMC_EINVAL, "psfmc_debug_fisher_gram: %s (K=%d, n_pix=%d)", why, K, n_pix);
+    HIP_TRY(hipSetDevice(device));
+    const size_t vec = (size_t)K * n_pix;
+    const size_t total = 2 * vec + 2 * (size_t)n_pix + plan.partial_doubles + plan.io_doubles;
+    double* buf = nullptr;
+    HIP_TRY(hipMalloc(&buf, total * sizeof(double)));
+    double *d_a = buf, *d_b = d_a + vec, *d_c = d_b + vec, *d_d = d_c + n_pix, *d_part = d_d + n_pix;
+    double *d_F = d_part + plan.partial_doubles + K, *d_g = d_F + (size_t)K * K;
+    int rc = PSFMC_OK;
+    auto step = [&](hipError_t e) { if (e != hipSuccess && rc == PSFMC_OK) rc = fail(PSFMC_EHIP, "psfmc_debug_fisher_gram: %s", hipGetErrorString(e)); };
+    step(hipMemcpy(d_a, a, vec * sizeof(double), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_b, b, vec * sizeof(double), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_c, c, (size_t)n_pix * sizeof(double), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_d, d, (size_t)n_pix * sizeof(double), hipMemcpyHostToDevice));
+    if (rc == PSFMC_OK) {
+        launch_fisher_gram(FisherVectors{d_a, d_b, d_c, d_d}, 1, K, n_pix, plan, d_part, d_F, d_g, nullptr);
+        step(hipGetLastError());
+        step(hipMemcpy(F, d_F, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost));
+        step(hipMemcpy(g, d_g, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    (void)hipFree(buf);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------

@@ -314,6 +314,10 @@ def load_library():
     lib.psfmc_debug_aux_table_blocks.restype = ci
     lib.psfmc_debug_aux_table_blocks.argtypes = ([ci, ci, ip, _c_double_p] + 4 * [ip, ip, _c_double_p] +
                                                  [_c_double_p, ip, ip, ip, ip])
+    lib.psfmc_fisher_rows.restype = ci
+    lib.psfmc_fisher_rows.argtypes = [vp, ci, ci, ci] + [_c_double_p] * 5
+    lib.psfmc_debug_fisher_gram.restype = ci
+    lib.psfmc_debug_fisher_gram.argtypes = [ci, ci, ci] + [_c_double_p] * 6
     lib.psfmc_debug_sweep.restype = ci
     lib.psfmc_debug_sweep.argtypes = [ci, ci, ctypes.c_size_t, ci, _c_double_p]
     lib.psfmc_debug_valu_rate.restype = ci
@@ -502,6 +506,45 @@ def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
     if width is not None and aux.shape[1] < width:
         aux = np.ascontiguousarray(np.pad(aux, ((0, 0), (0, width - aux.shape[1]))))
     check(lib.psfmc_set_aux_rows(ctx, int(n_w), _dp(aux)))
+
+
+FISHER_MAX_COLUMNS = 63         # psfmc_fisher_rows: K + 1 vectors in four 16-row tiles of the matrix unit
+
+
+def _fisher_rows(lib, ctx, check, field, rows, inv2h, row_len, max_walkers, send_aux):
+    """psfmc_fisher_rows for one context: rows [n_base, 2K+1, row_len], inv2h [n_base, K] ->
+    (F [n_base, K, K], g [n_base, K], lnlike [n_base])."""
+    rows, inv2h = _f64(rows), _f64(inv2h)
+    if rows.ndim != 3 or rows.shape[2] != row_len:
+        raise ValueError('rows must be [n_base, 2K+1, {}], got {}'.format(row_len, rows.shape))
+    n_base, n_st = rows.shape[:2]
+    k = (n_st - 1) // 2
+    if n_base < 1 or k < 1 or n_st != 2 * k + 1 or inv2h.shape != (n_base, k):
+        raise ValueError('rows [n_base, 2K+1, row_len] need inv2h [n_base, K] with K >= 1; got {} and {}'.format(
+            rows.shape, inv2h.shape))
+    if k > FISHER_MAX_COLUMNS:
+        raise ValueError('K={} differentiated columns exceed {}'.format(k, FISHER_MAX_COLUMNS))
+    if n_base * n_st > max_walkers:
+        raise ValueError('n_base (2K+1) = {} exceeds max_walkers={}'.format(n_base * n_st, max_walkers))
+    f_out, g_out, ll = np.empty((n_base, k, k)), np.empty((n_base, k)), np.empty(n_base)
+    send_aux(n_base * n_st)
+    check(lib.psfmc_fisher_rows(ctx, int(field), n_base, k, _dp(rows), _dp(inv2h), _dp(f_out), _dp(g_out), _dp(ll)))
+    return f_out, g_out, ll
+
+
+def debug_fisher_gram(a, b, c, d, device=0):
+    """The Gram and finish kernels of psfmc_fisher_rows alone (psfmc_debug_fisher_gram): a, b [K, n_pix], c, d [n_pix]
+    -> (F [K, K] = sum_pix (a a^T + b b^T), g [K] = sum_pix (a c + b d)).  Test hook for the matrix unit's lane map."""
+    lib = load_library()
+    a, b, c, d = (_f64(v) for v in (a, b, c, d))
+    if a.ndim != 2 or b.shape != a.shape or c.shape != a.shape[1:] or d.shape != c.shape:
+        raise ValueError('a, b must be [K, n_pix] and c, d [n_pix]')
+    k, n_pix = a.shape
+    f_out, g_out = np.empty((k, k)), np.empty(k)
+    rc = lib.psfmc_debug_fisher_gram(int(device), k, n_pix, _dp(a), _dp(b), _dp(c), _dp(d), _dp(f_out), _dp(g_out))
+    if rc != 0:
+        raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
+    return f_out, g_out
 
 
 def debug_math(op, values, device=0):
@@ -700,6 +743,14 @@ class Context(_BlockLayouts):
             _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w)
             self._check(self._lib.psfmc_eval_images(self._ctx, n_w, _dp(rows), *args))
         return bufs
+
+    def fisher_rows(self, rows, inv2h, aux=None):
+        """Fisher matrix, gradient and base log-likelihood of n_base central-difference stencils
+        (psfmc_fisher_rows): rows [n_base, 2K+1, row_len] -- the base, then +h_k, -h_k per differentiated column --
+        inv2h [n_base, K] = 1 / (2 h_k), aux [n_base (2K+1), n_aux] as for `loglike` ->
+        (F [n_base, K, K], g [n_base, K], lnlike [n_base])."""
+        return _fisher_rows(self._lib, self._ctx, self._check, 0, rows, inv2h, self.row_len, self.max_walkers,
+                            lambda n_w: _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w))
 
     # -- raw emcee vectors (device-side priors and derivation) ---------------
     def set_layout(self, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees,
@@ -1344,6 +1395,13 @@ class FieldSetContext(object):
             self._check(self._lib.psfmc_eval_images_field(self._ctx, int(field), n_w, _dp(rows), *args))
         return bufs
 
+    def fisher_rows(self, field, rows, inv2h, aux=None):
+        """`Context.fisher_rows` for stencils of one field of this context."""
+        return _fisher_rows(self._lib, self._ctx, self._check, field, rows, inv2h,
+                            self._lib.psfmc_row_len(self._ctx), self.max_walkers,
+                            lambda n_w: _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w),
+                                                       n_w, self._aux_width()))
+
 
 class FieldView(object):
     """One field of a `FieldSetContext` behind the interface of a one-field `Context`, so that a
@@ -1401,6 +1459,9 @@ class FieldView(object):
 
     def loglike(self, rows, skip=None, aux=None):
         return self.owner.loglike(self.field, rows, skip, aux=aux)
+
+    def fisher_rows(self, rows, inv2h, aux=None):
+        return self.owner.fisher_rows(self.field, rows, inv2h, aux=aux)
 
     def __getattr__(self, name):
         # the rest of Context's interface (device-resident sampler, raw-sum exchange, device pointers, ...) has

@@ -126,6 +126,28 @@ def _seed(sampler, state, default=None):
     sampler.random_state = state
 
 
+def _start_from_mode(sampler, model, chains):
+    """`start='mode'` of `model_galaxy_mcmc`: -> (start positions [chains, P], header keys).  The search's prior
+    draws and the walkers' normal deviates come from the sampler's random stream, which moves on past them."""
+    from .mode import find_mode, draw_about_mode, default_columns, _prior_draws
+    random = np.random.RandomState()
+    random.set_state(sampler.random_state)
+    found = find_mode(model, rng=random)
+    if found.ok:
+        others = None
+        if len(default_columns(model)) < model.num_params:       # discrete columns take prior draws
+            others = _prior_draws(model, chains, random)
+        param_vec = draw_about_mode(found.theta, found.cov, found.columns, chains, random,
+                                    log_prior=model.log_priors_batch, others=others)
+        meta = OrderedDict([('MCSTART', 'mode'), ('MCMODELP', found.lnpost)])
+    else:
+        warn('the curvature at the mode found (log-posterior {:.6g}) is not positive definite: the walkers start '
+             'from prior draws'.format(found.lnpost))
+        param_vec, meta = _prior_draws(model, chains, random), OrderedDict()
+    sampler.random_state = random.get_state()
+    return param_vec, meta
+
+
 def _seed_fields(sampler, random_states):
     """Every member of a set seeded from `random_states`; where there is none numpy's global generator seeds
     them, in field order."""
@@ -209,7 +231,7 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
                       burn=0, chains=None, max_iterations=1,
                       convergence_check=check_convergence_autocorr, sampler_class=None,
                       device=0, backend='auto', random_state=None, accumulate=True, quiet=False,
-                      group='auto', moves=None):
+                      group='auto', moves=None, start='prior'):
     """Model a galaxy's surface brightness with MCMC.
 
     model_file, output_name, write_fits, iterations, burn, chains, max_iterations,
@@ -224,7 +246,15 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
     `moves`: the sampler's proposal moves (`sampler.StretchMove`, `sampler.DEMove`, or a list of (move, weight)
     pairs; None: the stretch move, outputs byte for byte as without the keyword).  The database header then
     records them as MCMOVES, e.g. 'stretch:0.5,de:0.5'.  A `sampler_class` that does not take a `moves` keyword
-    raises ValueError."""
+    raises ValueError.
+    `start`: where the walkers begin.  'prior' (default): draws from the priors, the reference's flow; outputs byte
+    for byte as without the keyword.  'mode': `mode.find_mode` searches the posterior mode first and the walkers are
+    drawn as mode + L z, L L^T = the mode's covariance, z from the sampler's RandomState (`mode.draw_about_mode`;
+    discrete columns take prior draws); the database header then records MCSTART = 'mode' and MCMODELP, the mode's
+    log-posterior.  Where the curvature at the mode is not positive definite the walkers are prior draws, with a
+    warning."""
+    if start not in ('prior', 'mode'):
+        raise ValueError("start must be 'prior' or 'mode' (got {!r})".format(start))
     if output_name is None:
         output_name = 'out_' + model_file.replace('.py', '')
     output_name += '_{}'
@@ -275,14 +305,22 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
     if ranks is not None:
         have_db = ranks.broadcast_object(have_db)
     if not have_db:
-        param_vec = mc_model.init_params_from_priors(chains)
-        if ranks is not None:
-            param_vec = ranks.broadcast_object(param_vec)
+        start_meta = OrderedDict()
+        if start == 'mode':
+            # rank 0 searches and draws; the others take its walkers (and, below, its random state)
+            param_vec, start_meta = _start_from_mode(sampler, mc_model, chains) if writer else (None, None)
+            if ranks is not None:
+                param_vec, start_meta = ranks.broadcast_object((param_vec, start_meta))
+                sampler.random_state = ranks.broadcast_object(sampler.random_state)
+        else:
+            param_vec = mc_model.init_params_from_priors(chains)
+            if ranks is not None:
+                param_vec = ranks.broadcast_object(param_vec)
         converged = _burn_and_sample(sampler, mc_model, param_vec, burn, iterations, max_iterations,
                                      convergence_check, accumulate and writer, device_acc, quiet)
         if device_acc:
             mc_model.reduce_accumulated(ranks)
-        meta = _chain_meta(sampler, burn, chains, converged, moves)
+        meta = _chain_meta(sampler, burn, chains, converged, moves, **start_meta)
         database = save_database(sampler, mc_model, db_name, meta_dict=meta) if writer else None
         if ranks is not None:
             ranks.broadcast_object(True)          # the file is complete

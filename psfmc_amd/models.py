@@ -615,6 +615,51 @@ class MultiComponentModel(object):
                  for lo in range(0, max(len(rows), 1), cap)]
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
+    # -- Fisher matrix and gradient -----------------------------------------------
+    def fisher(self, theta, step=None, columns=None):
+        """Fisher matrix and gradient of the log-likelihood at theta ([P] or [n, P]) from central-difference stencils
+        of device images (psfmc_fisher_rows; the definition: `mode.fisher_from_stencil`).
+
+        columns  the differentiated columns (default: every free column whose prior is not discrete -- the PSF index
+                 and its like stay at the base value)
+        step     [K] or [n, K] steps h_k (default: 1e-4 x the prior's standard deviation where that is finite and
+                 positive, else 1e-4 x max(|theta_k|, 1))
+        Returns dict(F [n, K, K], grad [n, K] (of lnL), loglike [n], columns [K], step [n, K]); without the leading
+        axis for a [P] theta.  The images do not care about prior supports, so there is no edge handling; a base
+        with a stencil image that is not finite on a good pixel gets NaN F and grad, which is not an error."""
+        from . import mode
+        if self._storage == 'f32':
+            raise ValueError("fisher() needs storage='f64': differences of float32-stored images over a 1e-4 step "
+                             "are rounding noise")
+        single = np.ndim(theta) == 1
+        theta = self._theta(theta)
+        columns = mode.default_columns(self) if columns is None else np.asarray(columns, dtype=np.int64)
+        if columns.ndim != 1 or len(columns) < 1 or columns.min() < 0 or columns.max() >= self.num_params:
+            raise ValueError('columns must be a non-empty list of columns of the parameter vector')
+        n, k = theta.shape[0], len(columns)
+        if step is None:
+            step = mode.default_steps(self, theta, columns)
+        step = np.array(np.broadcast_to(np.asarray(step, dtype=np.float64), (n, k)))
+        if not np.all(np.isfinite(step) & (step > 0)):
+            raise ValueError('steps must be finite and positive')
+        eng = self.engine
+        per_call = eng.max_walkers // (2 * k + 1)
+        if per_call < 1:
+            raise ValueError('a stencil of {} columns is {} walkers; the model was built for max_walkers={}'.format(
+                k, 2 * k + 1, eng.max_walkers))
+        fisher, grad, ll = np.empty((n, k, k)), np.empty((n, k)), np.empty(n)
+        for lo in range(0, n, per_call):
+            hi = min(lo + per_call, n)
+            vecs = mode.stencil(theta[lo:hi], step[lo:hi], columns).reshape(-1, self.num_params)
+            rows, aux = self.derived_rows(vecs), self.aux_rows(vecs)
+            fisher[lo:hi], grad[lo:hi], ll[lo:hi] = eng.fisher_rows(
+                rows.reshape(hi - lo, 2 * k + 1, -1), 0.5 / step[lo:hi], **self._aux_kw(aux, 0, len(vecs)))
+        bad = ~(np.isfinite(fisher).all(axis=(1, 2)) & np.isfinite(grad).all(axis=1))
+        fisher[bad], grad[bad] = np.nan, np.nan
+        ll = np.where(np.isfinite(ll), ll, -np.inf)
+        out = dict(F=fisher, grad=grad, loglike=ll, columns=columns, step=step)
+        return {key: (val[0] if single and key != 'columns' else val) for key, val in out.items()}
+
     def _one_image(self, kind):
         return self.sample_images(self._param_vector, (kind,))[kind][0]
 

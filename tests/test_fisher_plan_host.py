@@ -1,0 +1,18 @@
+"""The host arithmetic of psfmc_fisher_rows (psfmc_amd/csrc/psfmc_fisher_plan.h: argument checks, tile indices and
+buffer sizes) as a stand-alone program under the host compiler's address and undefined-behaviour sanitizers
+(tests/host/fisher_plan_check.cpp; no GPU, nothing loaded into python)."""
+import os
+import shutil
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def test_fisher_plan_under_host_sanitizers(tmp_path):
+    compiler = shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
+    assert compiler, 'no host C++ compiler'
+    exe = str(tmp_path / 'fisher_plan_check')
+    subprocess.check_call([compiler, '-std=c++17', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                           os.path.join(HERE, 'host', 'fisher_plan_check.cpp'), '-o', exe])
+    done = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+    assert done.returncode == 0 and 'fisher plan ok' in done.stdout, done.stdout
