@@ -6,7 +6,13 @@ The bound of the entry against the definition is derived, not picked (`mode_help
 per-pixel tolerance tests/test_gpu_parity.py test_images_match_fp64_oracle holds the device's images to -- 1e-12 of
 an image's largest value -- propagated to first order through a_k, b_k, w and r on the oracle's images, times the
 project's factor 4 (helpers.RASTER_ORACLE_FACTOR).  The figures it gives for the cases below are in DESIGN.md
-section 30."""
+section 30.
+
+That bound is as large as the variance half of the Gram matrix on every case but `noisy-psf`, so the entry is also
+held, on the device's OWN sample images, to the definition in long double within the roundings that separate the two
+(`mode_helpers.fisher_reference_longdouble`, `mode_helpers.fisher_rounding_bound`; tests/test_fisher_reference.py
+shows on the CPU what that bound catches).  tests/test_gpu_fisher_paths.py and tests/test_gpu_fisher_fields.py do the
+same on every tile count of the Gram kernel and for the fields of a set."""
 import numpy as np
 import pytest
 
@@ -24,16 +30,20 @@ BACKENDS = ['fused', 'hipfft']
 # ---------------------------------------------------------------------------
 # 1. the Gram kernel alone
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize('n_pix', [1, 3, 4, 255, 4099])
-@pytest.mark.parametrize('k', [1, 3, 16, 17, 33])
+@pytest.mark.parametrize('n_pix', [1, 3, 4, 64, 65, 255, 257, 4099])
+@pytest.mark.parametrize('k', [1, 3, 15, 16, 17, 31, 32, 33, 47, 48, 63])
 def test_gram_kernel_is_exact_on_small_integers(k, n_pix):
     """Small-integer vectors: every product and every sum is exact in fp64 (|sum| <= 4099 * 2 * 81 < 2^53), so F and g
     equal numpy's integer result exactly, whatever the order of the sums; every row and column of a tile holds a
     different vector, so a result written to the wrong row of the f64 fragment map is a wrong integer.  K = 1, 3 sit
     below one tile (K + 1 <= 16 with the gradient's column), 16 and 17 put that column or a row in a second tile, 33
-    needs three tile rows and their off-diagonal tiles; n_pix = 1, 3 are less than one MFMA, 4 exactly one, 255 one
-    short of four waves' slabs (one workgroup), 4099 sixty-five slabs with a tail of 3 in the last and a second
-    round of the finish kernel's four-way split.  A fifth of the pixels are zeroed (bad pixels)."""
+    needs three tile rows and their off-diagonal tiles; 15 fills one tile with the gradient in its last column, and
+    15 | 16, 31 | 32, 47 | 48 sit either side of each tile-row step, 63 is the largest K (four tile rows, ten tiles:
+    k_fisher_gram<4, FisherVectors> and the finish kernel's triangle walk at T = 4); n_pix = 1, 3 are less than one
+    MFMA, 4 exactly one, 64 exactly one wave, 65 a second wave that holds one pixel, 255 one short of four waves'
+    slabs (one workgroup), 257 a second workgroup that holds one pixel, 4099 sixty-five slabs with a tail of 3 in the
+    last and a second round of the finish kernel's four-way split.  A fifth of the pixels are zeroed (bad
+    pixels)."""
     rng = np.random.RandomState(1000 * k + n_pix)
     a = rng.randint(-9, 10, size=(k, n_pix)).astype(np.float64)
     b = rng.randint(-9, 10, size=(k, n_pix)).astype(np.float64)
@@ -62,16 +72,34 @@ def test_gram_hook_refuses_bad_arguments():
 # ---------------------------------------------------------------------------
 # 2. the entry against the definition on the oracle's images
 # ---------------------------------------------------------------------------
-def _synth_case():
-    import test_gpu_fullsize as tfs
-    fld, field = mh.synth_field_64()
-    return dict(build=lambda backend: tfs.make_model(64, 1, backend, max_walkers=64)[0], field=field,
+def _synth_model(fld, backend, max_walkers=64):
+    """test_gpu_fullsize.make_model's point source + Sersic model on a given synth field."""
+    from psfmc_amd import MultiComponentModel
+    from psfmc_amd.ModelComponents import Configuration, PointSource, Sersic
+    from psfmc_amd.distributions import Uniform, WeibullMinimum
+    side = fld['sci'].shape[0]
+    c = np.array((side / 2 + 0.5,) * 2)
+    comps = [Configuration(fld['sci'], fld['ivm'], fld['psf'], fld['psf_ivm'], mag_zeropoint=fld['mag_zp']),
+             PointSource(xy=Uniform(loc=c - 8, scale=16 * np.ones(2)), mag=Uniform(loc=18.0, scale=2.0)),
+             Sersic(xy=Uniform(loc=c - 8, scale=16 * np.ones(2)), mag=Uniform(loc=19.0, scale=5.0),
+                    reff=Uniform(loc=2.0, scale=side / 16.0), reff_b=Uniform(loc=2.0, scale=side / 16.0),
+                    index=WeibullMinimum(c=1.5, scale=4), angle=Uniform(loc=0, scale=180), angle_degrees=True)]
+    return MultiComponentModel(comps, backend=backend, max_walkers=max_walkers)
+
+
+NOISY_PSF_WEIGHT = 1e-3          # the `noisy-psf` case: the synth field's PSF weight map times this
+MIN_VARIANCE_SHARE = 0.5         # ... so that 1/2 sum w^2 dv_k^2 is at least this share of F_kk for some column
+
+
+def _synth_case(psf_weight=1.0):
+    fld, field = mh.synth_field_64(psf_weight)
+    return dict(build=lambda backend: _synth_model(fld, backend), field=field,
                 layout=mh.SYNTH_LAYOUT, has_psf_index=False, theta=fld['truth'], n_columns=10)
 
 
-def _edge_case(shape, comps, n_psf=1, spoil=False, seed=4100):
+def _edge_case(shape, comps, n_psf=1, spoil=False, seed=4100, psf_side=21, max_walkers=64):
     import test_gpu_random as tgr
-    case = tgr.edge_case(seed + shape[0] * 7 + shape[1], shape, (21, 21), comps, n_walkers=3, n_psf=n_psf)
+    case = tgr.edge_case(seed + shape[0] * 7 + shape[1], shape, (psf_side, psf_side), comps, n_walkers=3, n_psf=n_psf)
     if spoil:                    # a mask, weights <= 0 and NaN pixels, whatever the random field drew
         case['mask'] = np.zeros(shape, dtype=np.uint8)
         case['mask'][10:17, 40:52] = 1
@@ -80,8 +108,8 @@ def _edge_case(shape, comps, n_psf=1, spoil=False, seed=4100):
         case['sci'] = case['sci'].copy()
         case['sci'][12, 45], case['sci'][40, 21] = np.nan, np.nan      # one under the mask, one on its own
     field = orc.make_field(case['sci'], case['ivm'], case['psfs'], case['pivms'], mask=case['mask'], mag_zp=case['zp'])
-    return dict(build=lambda backend: tgr.build(case, backend, max_walkers=64), field=field, layout=case['layout'],
-                has_psf_index=case['has_psf_index'], theta=case['theta'][0],
+    return dict(build=lambda backend, max_walkers=max_walkers: tgr.build(case, backend, max_walkers=max_walkers),
+                field=field, layout=case['layout'], has_psf_index=case['has_psf_index'], theta=case['theta'][0],
                 n_columns=len(case['theta'][0]) - int(case['has_psf_index']))
 
 
@@ -113,6 +141,7 @@ def _general_case():
 
 CASES = {
     'synth64': _synth_case,
+    'noisy-psf': lambda: _synth_case(NOISY_PSF_WEIGHT),
     'embedded70x64': lambda: _edge_case((70, 64), [_ps(64, 70), _sersic(64, 70)]),
     'edge-mask-nan': lambda: _edge_case((64, 64), [dict(type='sky', adu=0.004), _ps(64, 64), _sersic(64, 64)],
                                         spoil=True),
@@ -123,12 +152,13 @@ CASES = {
 _REFS = {}
 
 
-def reference(name):
-    """The case, the steps and columns `model.fisher` takes by default, and the definition on the oracle's images of
-    the same 2K+1 vectors with its derived bounds: computed once per case, shared by the back ends."""
+def reference(name, make=None):
+    """The case (CASES[name], or make()), the steps and columns `model.fisher` takes by default, and the definition on
+    the oracle's images of the same 2K+1 vectors with its derived bounds: computed once per case, shared by the back
+    ends."""
     if name in _REFS:
         return _REFS[name]
-    case = CASES[name]()
+    case = (make or CASES[name])()
     model = case['build']('hipfft')              # host side only: columns and steps come from the priors
     columns = mode.default_columns(model)
     assert len(columns) == case['n_columns']
@@ -142,7 +172,12 @@ def reference(name):
     bound_f, bound_g = mh.fisher_error_bound(imgs, case['field'], 0.5 / step[0], eps_conv, eps_ivm)
     print('%s: K = %d, derived bounds F %.3g, g %.3g' % (name, len(columns), bound_f, bound_g))
     assert np.all(np.isfinite(want_f)) and np.linalg.eigvalsh(want_f).min() > 0
-    _REFS[name] = dict(case=case, columns=columns, step=step, F=want_f, g=want_g, imgs=imgs, bounds=(bound_f, bound_g))
+    share = mh.variance_share(imgs['conv'], imgs['ivm'], ~case['field'].bad_px, 0.5 / step[0])
+    print('%s: largest share of the variance half in F_kk %.3g' % (name, share.max()))
+    if name == 'noisy-psf':
+        assert share.max() >= MIN_VARIANCE_SHARE
+    _REFS[name] = dict(case=case, columns=columns, step=step, F=want_f, g=want_g, imgs=imgs, bounds=(bound_f, bound_g),
+                       share=share)
     return _REFS[name]
 
 
@@ -167,14 +202,28 @@ def test_entry_matches_the_definition_on_oracle_images(name, backend):
     assert err_f <= ref['bounds'][0] and err_g <= ref['bounds'][1]
     want_ll = ref['imgs']['ll'][0]
     assert abs(out['loglike'] - want_ll) <= 1e-9 * abs(want_ll)
-    # 4. the definition fed with the device's own sample images, within the same bound
+    # 4. the device's own sample images: the entry against the long-double definition of the SAME images, within
+    # the roundings that separate the two (mode_helpers.fisher_rounding_bound)
     vecs = mode.stencil(case['theta'], ref['step'], ref['columns'])[0]
-    dev = model.sample_images(vecs, ('residual', 'composite_ivm'))
-    own_f, own_g = mode.fisher_from_stencil(dev['residual'], dev['composite_ivm'], ~case['field'].bad_px,
-                                            0.5 / ref['step'][0])
-    err_f, err_g = mh.fisher_errors(out['F'], out['grad'], own_f, own_g)
-    assert err_f <= ref['bounds'][0] and err_g <= ref['bounds'][1]
+    held_to_own_images(model, vecs, out, 0.5 / ref['step'][0], '%s %s' % (name, backend))
     model.close()
+
+
+def held_to_own_images(model, vecs, out, inv2h, tag):
+    """Assert that `out` (F, grad of ONE stencil from the entry) lies within `fisher_rounding_bound` of
+    `fisher_reference_longdouble` on the model's own `sample_images` of the stencil's vectors; the science image and
+    the counted pixels are the model's.  -> the reference (F, g) as float64."""
+    dev = model.sample_images(vecs, ('convolved_model', 'composite_ivm'))
+    sci, good = np.asarray(model.config.obs_data, dtype=np.float64), ~np.asarray(model.config.bad_px, dtype=bool)
+    args = (dev['convolved_model'], dev['composite_ivm'], sci, good, inv2h)
+    want_f, want_g = mh.fisher_reference_longdouble(*args)
+    bound_f, bound_g = mh.fisher_rounding_bound(*args)
+    assert np.all(np.isfinite(want_f.astype(np.float64))) and np.all(np.isfinite(want_g.astype(np.float64)))
+    err_f, err_g = mh.fisher_errors(out['F'], out['grad'], want_f, want_g)
+    print('%s, own images, K = %d: rounding-level error F %.3g (bound %.3g), g %.3g (bound %.3g)' % (
+        tag, len(want_g), err_f, bound_f, err_g, bound_g))
+    assert err_f <= bound_f and err_g <= bound_g, (tag, err_f, bound_f, err_g, bound_g)
+    return want_f.astype(np.float64), want_g.astype(np.float64)
 
 
 # ---------------------------------------------------------------------------
