@@ -871,6 +871,49 @@ int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* base_col, c
 int psfmc_fisher_rows(psfmc_ctx* ctx, int field, int n_base, int K, const double* rows, const double* inv2h,
                       double* F, double* g, double* lnlike);
 /*
+ * psfmc_fisher_rows for stencils of DIFFERENT fields of a psfmc_ctx_create_fields context in one call (DESIGN.md
+ * section 31): stencil s is 2K + 1 walkers of field field[s]; every stencil of a call has the same K.
+ *   field   [n_stencils]                 the stencils' fields, in any order, a field as often as wanted
+ *   rows    [n_stencils][2K+1][row_len]  as psfmc_fisher_rows takes them (the PSF index counts within the field; a
+ *                                        context with an aux layout: psfmc_set_aux_rows for all n_stencils (2K+1)
+ *                                        walkers first)
+ *   inv2h   [n_stencils][K]
+ *   F [n_stencils][K][K], g [n_stencils][K], lnlike [n_stencils]   out
+ * Stencil s's F, g and lnlike are the bits psfmc_fisher_rows(ctx, field[s], 1, K, ...) gives for that stencil alone,
+ * whatever stands beside it, in whatever field order, and wherever a pass boundary falls.  The records are derived
+ * per run of equal field; the image passes run over the mixed records (a record's field is its kernel-spectrum
+ * index / PSFs per field, as in the log-posterior pipeline); then ONE Gram and ONE finish launch serve every stencil
+ * through a per-stencil device table.  1 <= K <= 63 and n_stencils (2K+1) <= max_walkers.  Fused back end and fp64
+ * storage only (PSFMC_EINVAL otherwise), as every shared context is.  Nothing is allocated or launched for it
+ * until the first call.
+ */
+int psfmc_fisher_rows_fields(psfmc_ctx* ctx, int n_stencils, int K, const int* field, const double* rows,
+                             const double* inv2h, double* F, double* g, double* lnlike);
+/*
+ * Fisher matrix and gradient of a JOINT fit (psfmc_eval_theta_joint's likelihood: the fields' sum) at n_base points.
+ * Field f of the context reads K_field of the K_joint differentiated joint columns: its column k is joint column
+ * col_of[f][k].  Stencil (b, f) holds field f's base row of point b and the +- rows of those K_field columns only.
+ *   col_of  [n_fields][K_field]                        injective per field, values in [0, K_joint)
+ *   rows    [n_base][n_fields][2 K_field + 1][row_len]
+ *   inv2h   [n_base][n_fields][K_field]                (the fields that share a joint column share its step)
+ *   F       [n_base][K_joint][K_joint]   out: element (r, c) starts at +0.0 and adds, for f = 0 ... n_fields - 1 in
+ *                                        that order, F_f[kr][kc] with col_of[f][kr] = r, col_of[f][kc] = c; a field
+ *                                        that does not read both is skipped.  Exactly symmetric.
+ *   g       [n_base][K_joint]            out: the same sum of g_f[kr]
+ *   lnlike  [n_base]                     out: ((ll_0 + ll_1) + ...) + ll_{F-1}, the sum psfmc_eval_theta_joint_split
+ *                                        defines, of the ROW-based ll_f (unguarded: not -inf'ed where it is not
+ *                                        finite).  The split entry forms its records from raw vectors on the device,
+ *                                        these rows come from the caller: the two values agree to rounding (2e-13
+ *                                        relative measured), not in their bits.
+ * F_f, g_f and ll_f are the bits psfmc_fisher_rows gives for field f's stencil alone.  A joint column no field reads
+ * is a zero row and column.  1 <= K_field <= 63; K_joint is limited by memory only (one thread per element of the
+ * result, no atomics); n_base n_fields (2 K_field + 1) <= max_walkers.  A col_of that is not injective or leaves
+ * [0, K_joint) is PSFMC_EINVAL.  Contexts with or without joint priors (the images do not read them).  Back end,
+ * storage and aux rows as psfmc_fisher_rows_fields.
+ */
+int psfmc_fisher_rows_joint(psfmc_ctx* ctx, int n_base, int K_joint, int K_field, const int* col_of,
+                            const double* rows, const double* inv2h, double* F, double* g, double* lnlike);
+/*
  * Diagnostic hook: the Gram and finish kernels of psfmc_fisher_rows alone, on caller-supplied per-pixel vectors
  * a, b [K][n_pix] and c, d [n_pix]:  F = sum_pix (a a^T + b b^T) [K][K],  g_k = sum_pix (a_k c + b_k d) [K].
  * Small-integer data make every product and sum exact in fp64, so a wrong lane map shows as a wrong integer.

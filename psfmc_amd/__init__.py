@@ -11,7 +11,7 @@ from .parallel import RankGroup, ShardedLogPosterior
 from .fitting import (model_galaxy_mcmc, model_fields_mcmc, model_joint_mcmc, model_galaxy_ptmcmc,
                       model_joint_ptmcmc, model_fields_ptmcmc)
 from .database import load_database
-from .mode import find_mode
+from .mode import find_mode, find_modes
 
 __version__ = '0.1.0'
 __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior', 'EnsembleSampler',
@@ -19,4 +19,4 @@ __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
            'model_joint_mcmc', 'model_galaxy_ptmcmc', 'model_joint_ptmcmc', 'load_database', 'Moffat', 'Ferrer',
            'StretchMove', 'DEMove', 'FieldSetTemperedSampler', 'model_fields_ptmcmc',
-           'find_mode']
+           'find_mode', 'find_modes']

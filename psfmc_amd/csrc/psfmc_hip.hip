@@ -33,6 +33,7 @@
 #include "psfmc_fused_path.h"
 #include "psfmc_rows3_path.h"
 #include "psfmc_theta.h"
+#include "psfmc_fisher_plan.h"   // (every part: the context holds a table of its records)
 #if PSFMC_PART == 0
 #include "psfmc_integrated.h"
 #include "psfmc_general.h"
@@ -316,9 +317,15 @@ struct psfmc_ctx {
     uint8_t* d_mean_flags = nullptr;
     // psfmc_fisher_rows (psfmc_fisher.h): the stencil walkers' stashed images, the Gram kernel's partial tiles and the
     // step reciprocals / results; grow-only, nothing is allocated until the first call
+    // psfmc_fisher_rows_fields / _joint add the stencils' table, the joint column map and the linked results, on
+    // their first call
     struct Fisher {
         double *stash = nullptr, *partial = nullptr, *io = nullptr;
         size_t cap_stash = 0, cap_partial = 0, cap_io = 0;
+        FisherFieldRec* recs = nullptr;
+        int* field_col = nullptr;
+        double* link = nullptr;
+        size_t cap_recs = 0, cap_field_col = 0, cap_link = 0;
     } fisher;
 };
 
@@ -1437,7 +1444,7 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
                     c->stretch.rand, c->stretch.chain, c->stretch.lnchain, c->stretch.partner, c->stretch.iter,
                     c->stretch.nacc, c->stretch.accflag, c->stretch.kind, c->stretch.partner_b, c->pt_blob, c->d_integ_flags, c->d_integ_par,
                     c->d_extra_img, c->d_gen_flags, c->d_gen_par, c->d_aux, c->d_mean_flags, c->fisher.stash, c->fisher.partial,
-                    c->fisher.io};
+                    c->fisher.io, c->fisher.recs, c->fisher.field_col, c->fisher.link};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (const psfmc_ctx::AuxBlockState& k : c->blk) {
@@ -4504,6 +4511,138 @@ extern "C" int psfmc_fisher_rows(psfmc_ctx* c, int field, int n_base, int K, con
     HIP_TRY(hipStreamSynchronize(st));
     for (int b = 0; b < n_base; ++b) lnlike[b] = like[(size_t)b * (2 * K + 1)];
     return PSFMC_OK;
+}
+
+// Stencils of different fields in one call (psfmc_fisher_rows_fields; with `joint`, psfmc_fisher_rows_joint): the
+// records derived per run of equal field (as fields_records_pass derives them from theta), the image passes over
+// the mixed records -- fused_forward / fused_inverse take a record's field from its kernel-spectrum index, as the
+// log-posterior pipeline's mixed passes do, and write walker w's images to image w of d_img0 / d_img1 whatever its
+// field -- each pass stashed through the stencils' table, then ONE Gram and ONE finish launch (and the link).
+struct FisherJointCall {
+    int n_base, K_joint;
+    const int* field_col;            // host [n_fields][K_joint] (fisher_joint_plan)
+    FisherJointPlan plan;
+};
+static int fisher_fields_impl(psfmc_ctx* c, const char* who, int n_stencils, int K, const int* field,
+                              const double* rows, const double* inv2h, double* F, double* g, double* lnlike,
+                              const FisherJointCall* joint) {
+    if (c->backend != PSFMC_BACKEND_FUSED)
+        return fail(PSFMC_EINVAL, "%s serves the fused back end (every shared context's)", who);
+    if (c->t_f32)
+        return fail(PSFMC_EINVAL, "%s needs fp64 storage: differences of complex64-stored images over a 1e-4 step are "
+                    "rounding noise", who);
+    std::vector<FisherFieldShape> shapes(c->n_fields);
+    for (int f = 0; f < c->n_fields; ++f) {
+        const WrapDesc& w = c->wraps[f];
+        shapes[f] = FisherFieldShape{(long long)((size_t)f * c->S), c->ny, c->nx, w.ly, w.lx, w.ay, w.ax};
+    }
+    std::vector<FisherFieldRec> recs(n_stencils > 0 ? n_stencils : 0);
+    FisherFieldsPlan plan;
+    if (const char* why = fisher_fields_plan(n_stencils, K, c->max_walkers, c->n_fields, field, shapes.data(),
+                                             recs.data(), &plan))
+        return fail(PSFMC_EINVAL, "%s: %s (n_stencils=%d, K=%d, max_walkers=%d)", who, why, n_stencils, K,
+                    c->max_walkers);
+    const int W = plan.W, n_st = 2 * K + 1;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    RC_TRY(take_aux_rows(c, W));
+    HIP_TRY(hipMemcpyAsync(c->d_rows, rows, (size_t)W * c->rlen * sizeof(double), hipMemcpyHostToDevice, st));
+    c->prep_tabs_valid = false;                       // d_prep is being rewritten
+    for (int s0 = 0; s0 < n_stencils;) {              // one record derivation per run of stencils of one field
+        int s1 = s0 + 1;
+        while (s1 < n_stencils && field[s1] == field[s0]) ++s1;
+        const int f = field[s0], w_lo = s0 * n_st, n = (s1 - s0) * n_st;
+        hipLaunchKernelGGL(k_prep, dim3((n + 127) / 128), dim3(128), 0, st, c->d_rows + (size_t)w_lo * c->rlen,
+                           c->d_prep + (size_t)w_lo * c->plen, n, c->n_ps, c->n_sersic, c->wraps[f].ly, c->wraps[f].lx,
+                           c->d_rho, c->n_psf_field, f * c->n_psf_field);
+        launch_pow_tables(c, n, w_lo, nullptr, st);
+        s0 = s1;
+    }
+    RC_TRY(ensure_image_staging(c));
+    psfmc_ctx::Fisher& fi = c->fisher;
+    RC_TRY(grow(&fi.stash, &fi.cap_stash, plan.stash_doubles));
+    RC_TRY(grow(&fi.partial, &fi.cap_partial, plan.partial_doubles));
+    RC_TRY(grow(&fi.io, &fi.cap_io, plan.io_doubles));
+    RC_TRY(grow(&fi.recs, &fi.cap_recs, (size_t)n_stencils));
+    if (joint) {
+        RC_TRY(grow(&fi.field_col, &fi.cap_field_col, (size_t)c->n_fields * joint->K_joint));
+        RC_TRY(grow(&fi.link, &fi.cap_link, joint->plan.link_doubles));
+    }
+    double* d_inv2h = fi.io;
+    double* d_F = fi.io + fisher_fields_F_at(n_stencils, K, 0);
+    double* d_g = fi.io + fisher_fields_g_at(n_stencils, K, 0);
+    HIP_TRY(hipMemcpyAsync(d_inv2h, inv2h, (size_t)n_stencils * K * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(fi.recs, recs.data(), (size_t)n_stencils * sizeof(FisherFieldRec), hipMemcpyHostToDevice, st));
+    for (int w0 = 0; w0 < W; w0 += c->chunk) {
+        const int n = W - w0 < c->chunk ? W - w0 : c->chunk;
+        const int rc = image_pass(c, n, c->d_prep + (size_t)w0 * c->plen, 0, nullptr,
+                                  c->d_partial + (size_t)w0 * c->nblk, st);
+        if (rc != PSFMC_OK) {                         // (the table's copy out of `recs` may still be in flight)
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        hipLaunchKernelGGL(k_fisher_stash_fields, dim3(16, n), dim3(256), 0, st, c->d_img0, c->d_img1, fi.stash, c->S,
+                           fi.recs, w0, n_st);
+    }
+    hipLaunchKernelGGL(k_finish, dim3(finish_blocks(W)), dim3(kFinishThreads), 0, st, c->d_partial,
+                       (const uint8_t*)nullptr, c->d_like, W, c->nblk);
+    const FisherFieldStencils src{fi.recs, fi.stash, d_inv2h, c->d_sci, c->d_var, c->d_bad};
+    launch_fisher_gram_fields(src, K, plan, fi.partial, d_F, d_g, st);
+    std::vector<double> like(W);
+    if (joint) {
+        const int nf = c->n_fields, Kj = joint->K_joint;
+        HIP_TRY(hipMemcpyAsync(fi.field_col, joint->field_col, (size_t)nf * Kj * sizeof(int), hipMemcpyHostToDevice, st));
+        const size_t n_el = joint->plan.link_elems;
+        hipLaunchKernelGGL(k_fisher_link, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, st, d_F, d_g, fi.field_col,
+                           joint->n_base, nf, Kj, K, n_el, fi.link);
+        HIP_TRY(hipGetLastError());
+        const size_t nF = (size_t)joint->n_base * Kj * Kj;
+        HIP_TRY(hipMemcpyAsync(F, fi.link, nF * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(g, fi.link + nF, (size_t)joint->n_base * Kj * sizeof(double), hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(F, d_F, (size_t)n_stencils * K * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(g, d_g, (size_t)n_stencils * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(like.data(), c->d_like, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (joint) {                                      // ((ll_0 + ll_1) + ...) + ll_{F-1}, psfmc_eval_theta_joint_split's sum
+        const int nf = c->n_fields;
+        for (int b = 0; b < joint->n_base; ++b) {
+            double ll = like[(size_t)b * nf * n_st];
+            for (int f = 1; f < nf; ++f) ll += like[((size_t)b * nf + f) * n_st];
+            lnlike[b] = ll;
+        }
+    } else {
+        for (int s = 0; s < n_stencils; ++s) lnlike[s] = like[(size_t)s * n_st];
+    }
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_fisher_rows_fields(psfmc_ctx* c, int n_stencils, int K, const int* field, const double* rows,
+                                        const double* inv2h, double* F, double* g, double* lnlike) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (!field || !rows || !inv2h || !F || !g || !lnlike) return fail(PSFMC_EINVAL, "NULL buffer");
+    return fisher_fields_impl(c, "psfmc_fisher_rows_fields", n_stencils, K, field, rows, inv2h, F, g, lnlike, nullptr);
+}
+
+extern "C" int psfmc_fisher_rows_joint(psfmc_ctx* c, int n_base, int K_joint, int K_field, const int* col_of,
+                                       const double* rows, const double* inv2h, double* F, double* g, double* lnlike) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (!col_of || !rows || !inv2h || !F || !g || !lnlike) return fail(PSFMC_EINVAL, "NULL buffer");
+    const int nf = c->n_fields;
+    FisherJointCall joint{n_base, K_joint, nullptr, FisherJointPlan{}};
+    std::vector<int> field_col;
+    if (K_joint >= 1 && K_joint <= (1 << 20)) field_col.resize((size_t)nf * K_joint);
+    if (const char* why = fisher_joint_plan(n_base, nf, K_joint, K_field, c->max_walkers, col_of,
+                                            field_col.empty() ? nullptr : field_col.data(), &joint.plan))
+        return fail(PSFMC_EINVAL, "psfmc_fisher_rows_joint: %s (n_base=%d, n_fields=%d, K_joint=%d, K_field=%d, "
+                    "max_walkers=%d)", why, n_base, nf, K_joint, K_field, c->max_walkers);
+    joint.field_col = field_col.data();
+    std::vector<int> field((size_t)joint.plan.n_stencils);
+    for (size_t s = 0; s < field.size(); ++s) field[s] = (int)(s % nf);
+    return fisher_fields_impl(c, "psfmc_fisher_rows_joint", joint.plan.n_stencils, K_field, field.data(), rows, inv2h,
+                              F, g, lnlike, &joint);
 }
 
 // the Gram and finish kernels alone on caller-supplied vectors: a, b [K][n_pix], c, d [n_pix] -> F [K][K], g [K]

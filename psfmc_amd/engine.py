@@ -316,6 +316,10 @@ def load_library():
                                                  [_c_double_p, ip, ip, ip, ip])
     lib.psfmc_fisher_rows.restype = ci
     lib.psfmc_fisher_rows.argtypes = [vp, ci, ci, ci] + [_c_double_p] * 5
+    lib.psfmc_fisher_rows_fields.restype = ci
+    lib.psfmc_fisher_rows_fields.argtypes = [vp, ci, ci, ip] + [_c_double_p] * 5
+    lib.psfmc_fisher_rows_joint.restype = ci
+    lib.psfmc_fisher_rows_joint.argtypes = [vp, ci, ci, ci, ip] + [_c_double_p] * 5
     lib.psfmc_debug_fisher_gram.restype = ci
     lib.psfmc_debug_fisher_gram.argtypes = [ci, ci, ci] + [_c_double_p] * 6
     lib.psfmc_debug_sweep.restype = ci
@@ -1402,6 +1406,67 @@ class FieldSetContext(object):
                             lambda n_w: _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w),
                                                        n_w, self._aux_width()))
 
+    def _stencil_rows(self, rows, inv2h, lead):
+        """The checked arrays of a several-stencil Fisher call: rows [*lead, 2K+1, row_len], inv2h [*lead, K] -> (rows,
+        inv2h, K); the walkers must fit max_walkers."""
+        rows, inv2h = _f64(rows), _f64(inv2h)
+        row_len = self._lib.psfmc_row_len(self._ctx)
+        if rows.ndim != len(lead) + 2 or rows.shape[:len(lead)] != tuple(lead) or rows.shape[-1] != row_len:
+            raise ValueError('rows must be [{}, 2K+1, {}], got {}'.format(
+                ', '.join(str(n) for n in lead), row_len, rows.shape))
+        n_st = rows.shape[-2]
+        k = (n_st - 1) // 2
+        if min(lead) < 1 or k < 1 or n_st != 2 * k + 1 or inv2h.shape != tuple(lead) + (k,):
+            raise ValueError('rows [..., 2K+1, row_len] need inv2h [..., K] with K >= 1; got {} and {}'.format(
+                rows.shape, inv2h.shape))
+        if k > FISHER_MAX_COLUMNS:
+            raise ValueError('K={} differentiated columns of a field exceed {}'.format(k, FISHER_MAX_COLUMNS))
+        n_w = int(np.prod(lead)) * n_st
+        if n_w > self.max_walkers:
+            raise ValueError('{} stencils of {} walkers exceed max_walkers={}'.format(
+                int(np.prod(lead)), n_st, self.max_walkers))
+        return rows, inv2h, k
+
+    def fisher_rows_fields(self, fields, rows, inv2h, aux=None):
+        """Stencils of several fields in ONE call (psfmc_fisher_rows_fields): fields [n] the stencils' fields (any
+        order, repeats allowed), rows [n, 2K+1, row_len], inv2h [n, K], aux [n (2K+1), n_aux] or None ->
+        (F [n, K, K], g [n, K], lnlike [n]); stencil s's values are the bits `fisher_rows(fields[s], ...)` gives for
+        it alone."""
+        fields = np.ascontiguousarray(fields, dtype=np.int32)
+        if fields.ndim != 1 or len(fields) < 1 or fields.min() < 0 or fields.max() >= self.n_fields:
+            raise ValueError('fields must be a non-empty list of fields of the context')
+        n = len(fields)
+        rows, inv2h, k = self._stencil_rows(rows, inv2h, (n,))
+        f_out, g_out, ll = np.empty((n, k, k)), np.empty((n, k)), np.empty(n)
+        n_w = n * (2 * k + 1)
+        _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w), n_w, self._aux_width())
+        self._check(self._lib.psfmc_fisher_rows_fields(
+            self._ctx, n, k, fields.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(rows), _dp(inv2h), _dp(f_out),
+            _dp(g_out), _dp(ll)))
+        return f_out, g_out, ll
+
+    def fisher_rows_joint(self, col_of, rows, inv2h, k_joint, aux=None):
+        """Fisher matrix and gradient of a joint fit (psfmc_fisher_rows_joint): col_of [n_fields, K_field] the joint
+        column of each field's differentiated columns, rows [n_base, n_fields, 2 K_field + 1, row_len], inv2h
+        [n_base, n_fields, K_field], aux [n_base n_fields (2 K_field + 1), n_aux] or None ->
+        (F [n_base, k_joint, k_joint], g [n_base, k_joint], lnlike [n_base])."""
+        col_of = np.ascontiguousarray(col_of, dtype=np.int32)
+        if col_of.ndim != 2 or col_of.shape[0] != self.n_fields:
+            raise ValueError('col_of must be [{}, K_field], got {}'.format(self.n_fields, col_of.shape))
+        k_joint = int(k_joint)
+        n_base = np.shape(rows)[0] if np.ndim(rows) else 0
+        rows, inv2h, k = self._stencil_rows(rows, inv2h, (n_base, self.n_fields))
+        if col_of.shape[1] != k or k_joint < k:
+            raise ValueError('col_of [n_fields, {}] must name K_field = {} of {} joint columns'.format(
+                col_of.shape[1], k, k_joint))
+        f_out, g_out, ll = np.empty((n_base, k_joint, k_joint)), np.empty((n_base, k_joint)), np.empty(n_base)
+        n_w = n_base * self.n_fields * (2 * k + 1)
+        _send_aux_rows(self._lib, self._ctx, self._check, self._field_aux(aux, n_w), n_w, self._aux_width())
+        self._check(self._lib.psfmc_fisher_rows_joint(
+            self._ctx, n_base, k_joint, k, col_of.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(rows), _dp(inv2h),
+            _dp(f_out), _dp(g_out), _dp(ll)))
+        return f_out, g_out, ll
+
 
 class FieldView(object):
     """One field of a `FieldSetContext` behind the interface of a one-field `Context`, so that a
@@ -1537,6 +1602,10 @@ class JointView(object):
         return self.owner.pt_run_joint(betas, pos, lnlike, lnprior, scal, lz, partner, log_u, swap_i, swap_j,
                                        swap_log_u, naccepted, nswap, store=store, accumulate=accumulate, kind=kind,
                                        partner_b=partner_b)
+
+    def fisher_rows(self, col_of, rows, inv2h, k_joint, aux=None):
+        """`FieldSetContext.fisher_rows_joint`: the joint fit's Fisher matrix, gradient and log-likelihood."""
+        return self.owner.fisher_rows_joint(col_of, rows, inv2h, k_joint, aux=aux)
 
     def accumulated(self, field):
         return self.owner.accumulated(field)

@@ -126,13 +126,46 @@ def _seed(sampler, state, default=None):
     sampler.random_state = state
 
 
+def _check_start(start, start_positions=None):
+    if start not in ('prior', 'mode'):
+        raise ValueError("start must be 'prior' or 'mode' (got {!r})".format(start))
+    if start == 'mode' and start_positions is not None:
+        raise ValueError("start='mode' draws the walkers around the mode it finds: it cannot be combined with "
+                         "start_positions")
+
+
 def _start_from_mode(sampler, model, chains):
-    """`start='mode'` of `model_galaxy_mcmc`: -> (start positions [chains, P], header keys).  The search's prior
-    draws and the walkers' normal deviates come from the sampler's random stream, which moves on past them."""
-    from .mode import find_mode, draw_about_mode, default_columns, _prior_draws
+    """`start='mode'` of `model_galaxy_mcmc` and `model_joint_mcmc` (a `JointModel`: the joint mode): -> (start
+    positions [chains, P], header keys).  The search's prior draws and the walkers' normal deviates come from the
+    sampler's random stream, which moves on past them."""
+    from .mode import find_mode
     random = np.random.RandomState()
     random.set_state(sampler.random_state)
-    found = find_mode(model, rng=random)
+    out = _walkers_about_mode(find_mode(model, rng=random), model, chains, random)
+    sampler.random_state = random.get_state()
+    return out
+
+
+def _start_fields_from_modes(sampler, fieldset, chains):
+    """`start='mode'` of `model_fields_mcmc`: one `find_modes` search for all fields, then `_start_from_mode`'s rule
+    per field, each field's draws from its own sampler's random stream -> (start positions [F][chains, P], header
+    keys per field)."""
+    from .mode import find_modes
+    randoms = []
+    for sub in sampler.fields:
+        randoms.append(np.random.RandomState())
+        randoms[-1].set_state(sub.random_state)
+    found = find_modes(fieldset, rng=randoms)
+    outs = [_walkers_about_mode(res, m, chains, random) for res, m, random in zip(found, fieldset.models, randoms)]
+    for sub, random in zip(sampler.fields, randoms):
+        sub.random_state = random.get_state()
+    return [o[0] for o in outs], [o[1] for o in outs]
+
+
+def _walkers_about_mode(found, model, chains, random):
+    """Walkers mode + L z around a `ModeResult` (discrete columns take prior draws; redrawn outside the support), or
+    prior draws with a warning where the curvature at the mode is not positive definite; all from `random`."""
+    from .mode import draw_about_mode, default_columns, _prior_draws
     if found.ok:
         others = None
         if len(default_columns(model)) < model.num_params:       # discrete columns take prior draws
@@ -144,7 +177,6 @@ def _start_from_mode(sampler, model, chains):
         warn('the curvature at the mode found (log-posterior {:.6g}) is not positive definite: the walkers start '
              'from prior draws'.format(found.lnpost))
         param_vec, meta = _prior_draws(model, chains, random), OrderedDict()
-    sampler.random_state = random.get_state()
     return param_vec, meta
 
 
@@ -253,8 +285,7 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
     discrete columns take prior draws); the database header then records MCSTART = 'mode' and MCMODELP, the mode's
     log-posterior.  Where the curvature at the mode is not positive definite the walkers are prior draws, with a
     warning."""
-    if start not in ('prior', 'mode'):
-        raise ValueError("start must be 'prior' or 'mode' (got {!r})".format(start))
+    _check_start(start)
     if output_name is None:
         output_name = 'out_' + model_file.replace('.py', '')
     output_name += '_{}'
@@ -337,7 +368,8 @@ def model_galaxy_mcmc(model_file, output_name=None, write_fits=default_filetypes
 
 def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetypes, iterations=0, burn=0,
                       chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
-                      device=0, random_states=None, start_positions=None, accumulate=True, quiet=False, moves=None):
+                      device=0, random_states=None, start_positions=None, accumulate=True, quiet=False, moves=None,
+                      start='prior'):
     """`model_galaxy_mcmc` for SEVERAL fields of one model structure at once (their image and PSF sizes may
     differ: each field's database and posterior images have its own shape), in
     one GPU context (`models.FieldSet`): every field is fitted exactly as its own `model_galaxy_mcmc`
@@ -354,8 +386,13 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
                      seeds them in field order)
     start_positions  optional [F][chains, P] start positions (default: drawn from each field's priors)
     moves            as `model_galaxy_mcmc`'s (`FieldSetSampler.set_moves`; recorded as MCMOVES)
+    start            'prior' (default; outputs byte for byte as without the keyword) or 'mode': ONE `mode.find_modes`
+                     search finds every field's posterior mode, and each field's walkers are drawn around its own as
+                     `model_galaxy_mcmc(start='mode')` draws them, from that field's random stream; each field's
+                     database header records MCSTART and MCMODELP.  Not together with `start_positions`.
     Returns a list of (model, database), one per field."""
     from .sampler import FieldSetSampler
+    _check_start(start, start_positions)
     fieldset, output_names, chains, db_names, have_db = _fields_arguments(
         model_files, output_names, random_states, start_positions, chains, device)
     models = fieldset.models
@@ -364,7 +401,10 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
     _seed_fields(sampler, random_states)
 
     if not have_db:
-        if start_positions is None:
+        start_meta = [OrderedDict() for _ in models]
+        if start == 'mode':
+            start_positions, start_meta = _start_fields_from_modes(sampler, fieldset, chains)
+        elif start_positions is None:
             start_positions = [m.init_params_from_priors(chains) for m in models]
         pos = np.array([np.asarray(p, dtype=np.float64) for p in start_positions])
         lnprob = None
@@ -387,8 +427,8 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
                 break
             warn('Not yet converged after {:d} iterations: fields {}'.format(
                 (sampling_iter + 1) * iterations, [f for f, ok in enumerate(converged) if not ok]))
-        databases = [save_database(sub, m, name, meta_dict=_chain_meta(sub, burn, chains, ok, moves))
-                     for sub, m, name, ok in zip(sampler.fields, models, db_names, converged)]
+        databases = [save_database(sub, m, name, meta_dict=_chain_meta(sub, burn, chains, ok, moves, **extra))
+                     for sub, m, name, ok, extra in zip(sampler.fields, models, db_names, converged, start_meta)]
     else:
         databases, _ = _load_existing(db_names, quiet, fields=True)
     for m, db, out in zip(models, databases, output_names):
@@ -398,7 +438,7 @@ def model_fields_mcmc(model_files, output_names=None, write_fits=default_filetyp
 
 def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=default_filetypes, iterations=0,
                      burn=0, chains=None, max_iterations=1, convergence_check=check_convergence_autocorr,
-                     device=0, random_state=None, accumulate=True, quiet=False, moves=None):
+                     device=0, random_state=None, accumulate=True, quiet=False, moves=None, start='prior'):
     """`model_galaxy_mcmc` for ONE model fitted jointly to several exposures of the same object
     (`models.JointModel`: each field its own data, PSFs, constants and zeropoint; the parameters not named
     in `per_field` shared).  The reference's flow -- burn-in, reset, sampling with posterior images
@@ -410,7 +450,10 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
     of fields), and each field's posterior images `<output_name>_f<k>_<type>.fits` at that field's shape
     (what `save_posterior_images` writes for the field's model and the database's rows mapped to the
     field's own parameter names).  An existing database skips sampling.  `moves`: as `model_galaxy_mcmc`'s
-    (recorded as MCMOVES).  Returns (JointModel, database)."""
+    (recorded as MCMOVES).  `start`: as `model_galaxy_mcmc`'s -- 'mode' searches the JOINT posterior mode
+    (`mode.find_mode` on the `JointModel`) and draws the walkers around it; the header then records MCSTART and
+    MCMODELP.  Returns (JointModel, database)."""
+    _check_start(start)
     if output_name is None:
         output_name = 'out_joint_' + str(model_files[0]).replace('.py', '')
     joint = model_files if isinstance(model_files, JointModel) else None
@@ -430,10 +473,14 @@ def model_joint_mcmc(model_files, per_field=(), output_name=None, write_fits=def
 
     db_name = output_name + '_db.fits'
     if not os.path.exists(db_name):
-        param_vec = joint.init_params_from_priors(chains)
+        start_meta = OrderedDict()
+        if start == 'mode':
+            param_vec, start_meta = _start_from_mode(sampler, joint, chains)
+        else:
+            param_vec = joint.init_params_from_priors(chains)
         converged = _burn_and_sample(sampler, joint, param_vec, burn, iterations, max_iterations,
                                      convergence_check, False, accumulate, quiet)
-        meta = _chain_meta(sampler, burn, chains, converged, moves, MCFIELDS=n_f)
+        meta = _chain_meta(sampler, burn, chains, converged, moves, MCFIELDS=n_f, **start_meta)
         database = save_database(sampler, joint, db_name, meta_dict=meta)
     else:
         (database,), _ = _load_existing([db_name], quiet)

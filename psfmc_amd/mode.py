@@ -59,6 +59,26 @@ def fisher_from_stencil(resid, ivm, good, inv2h):
     return fisher, grad
 
 
+def joint_fisher(f_list, g_list, col_of, k_joint):
+    """Fisher matrix and gradient of a JOINT fit -- the log-likelihood is the fields' sum -- from the fields' own: the
+    definition psfmc_fisher_rows_joint's link kernel is held to.
+
+    f_list, g_list  per field F_f [..., K_f, K_f] and g_f [..., K_f] over that field's differentiated columns
+    col_of          per field [K_f] the joint column of each of them (injective, in [0, k_joint))
+    Element (r, c) starts at +0.0 and adds, for f = 0, 1, ... in that order, F_f[kr, kc] with col_of[f][kr] = r and
+    col_of[f][kc] = c; a field that does not read both columns adds nothing.  A joint column no field reads is a zero
+    row and column.  -> (F [..., k_joint, k_joint], g [..., k_joint])."""
+    lead = np.shape(g_list[0])[:-1]
+    fisher, grad = np.zeros(lead + (k_joint, k_joint)), np.zeros(lead + (k_joint,))
+    for f_f, g_f, cols in zip(f_list, g_list, col_of):
+        cols = np.asarray(cols, dtype=np.int64)
+        if len(set(cols.tolist())) != len(cols) or (len(cols) and (cols.min() < 0 or cols.max() >= k_joint)):
+            raise ValueError('col_of must be injective per field with values in [0, {})'.format(k_joint))
+        fisher[..., cols[:, None], cols[None, :]] += np.asarray(f_f, dtype=np.float64)
+        grad[..., cols] += np.asarray(g_f, dtype=np.float64)
+    return fisher, grad
+
+
 def loglike_from_images(resid, ivm, good):
     """lnL of one vector's residual and weight images over the good pixels (NaN / inf preserved)."""
     good = np.asarray(good, dtype=bool)
@@ -169,12 +189,30 @@ def lm_search(curvature, lnpost, starts, columns, max_iter=50, lam0=1e-3, feasib
     search can reach and stop at.  A start stops when a step taken with lambda <= 1 is below 1e-2 sigma in every
     column (sigma from H^-1 over the columns that are free to move).
     Returns a list of `ModeResult`, one per start."""
+    steps = _lm_steps(starts, columns, max_iter, lam0, feasible)
+    try:
+        kind, thetas = next(steps)
+        while True:
+            if kind == 'curvature':
+                answer = curvature(thetas)
+            else:
+                with np.errstate(all='ignore'):
+                    answer = lnpost(thetas)
+            kind, thetas = steps.send(answer)
+    except StopIteration as done:
+        return done.value
+
+
+def _lm_steps(starts, columns, max_iter, lam0, feasible):
+    """`lm_search` as a generator, so that several searches can advance side by side with their device calls shared
+    (`find_modes`): it yields ('lnpost', thetas [m, P]) or ('curvature', thetas [m, P]), is sent what `lm_search`'s
+    callable of that name returns for them, and returns the list of `ModeResult`.  Per iteration at most one
+    'curvature' request, then one 'lnpost' request."""
     starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
     columns = np.asarray(columns, dtype=np.int64)
     n, k = starts.shape[0], len(columns)
     cur = starts.copy()
-    with np.errstate(all='ignore'):
-        f_cur = np.asarray(lnpost(cur), dtype=np.float64).copy()
+    f_cur = np.asarray((yield 'lnpost', cur), dtype=np.float64).copy()
     f_cur[~np.isfinite(f_cur)] = -np.inf
     hess, grad = np.full((n, k, k), np.nan), np.full((n, k), np.nan)
     stale = np.ones(n, dtype=bool)                   # H, grad are not those of `cur`
@@ -188,7 +226,7 @@ def lm_search(curvature, lnpost, starts, columns, max_iter=50, lam0=1e-3, feasib
             break
         need = np.flatnonzero(running & stale)
         if len(need):
-            h_new, g_new = curvature(cur[need])
+            h_new, g_new = yield 'curvature', cur[need]
             hess[need], grad[need] = h_new, g_new
             stale[need] = False
         idx = np.flatnonzero(running)
@@ -215,8 +253,7 @@ def lm_search(curvature, lnpost, starts, columns, max_iter=50, lam0=1e-3, feasib
             trial[j, columns] = cur[i][columns] + delta
             solved[j] = True
             small[j] = lam[i] <= 1.0 and size < CONVERGED_SIGMA
-        with np.errstate(all='ignore'):
-            f_trial = np.asarray(lnpost(trial), dtype=np.float64)
+        f_trial = np.asarray((yield 'lnpost', trial), dtype=np.float64)
         for j, i in enumerate(idx):
             iters[i] += 1
             if solved[j] and np.isfinite(f_trial[j]) and f_trial[j] > f_cur[i]:
@@ -231,7 +268,7 @@ def lm_search(curvature, lnpost, starts, columns, max_iter=50, lam0=1e-3, feasib
                 running[i] = False
     need = np.flatnonzero(stale & np.isfinite(f_cur))
     if len(need):                                    # the curvature AT the result
-        h_new, g_new = curvature(cur[need])
+        h_new, g_new = yield 'curvature', cur[need]
         hess[need], grad[need] = h_new, g_new
     return [ModeResult(cur[i], f_cur[i], columns, hess[i], iters[i], converged[i]) for i in range(n)]
 
@@ -240,8 +277,13 @@ def lm_search(curvature, lnpost, starts, columns, max_iter=50, lam0=1e-3, feasib
 # a model's columns, steps and priors
 # ---------------------------------------------------------------------------
 def _column_priors(model):
-    """[(prior, element)] per column of the model's parameter vector."""
+    """[(prior, element)] per column of the model's parameter vector; for a `JointModel`, of the joint vector (its
+    column blocks stand in joint column order)."""
     out = []
+    if hasattr(model, 'field_models'):
+        for prior, cols, _ in model._blocks:
+            out += [(prior, j) for j in range(cols.stop - cols.start)]
+        return out
     for comp in model.components:
         for name, width in zip(comp.free_names(), comp.stochastic_lens()):
             out += [(comp._priors[name], j) for j in range(width)]
@@ -304,9 +346,11 @@ def prior_derivatives(log_prior, theta, step, columns):
 
 
 def find_mode(model, start=None, n_draws=1024, n_starts=4, max_iter=50, rng=None):
-    """The posterior mode of a `MultiComponentModel` by Levenberg-Marquardt on the log-posterior, with the Fisher
-    matrix and gradient of the likelihood from the device (`model.fisher`) and the priors' derivatives from central
-    differences of `log_priors_batch` on the host.
+    """The posterior mode of a `MultiComponentModel` -- or of a `JointModel`, over its joint columns -- by
+    Levenberg-Marquardt on the log-posterior, with the Fisher matrix and gradient of the likelihood from the device
+    (`model.fisher`) and the priors' derivatives from central differences of `log_priors_batch` on the host.  A joint
+    result is in joint terms: `cov` and `laplace_log_evidence` over the continuous joint columns, the discrete ones
+    (every exposure's PSF index) left at their start values.
 
     start     [P] or [n, P] start vectors; None: `n_draws` prior draws are evaluated in one batch and the best
               `n_starts` run side by side (one `fisher` and one `log_posterior_batch` call per iteration for all)
@@ -340,6 +384,107 @@ def find_mode(model, start=None, n_draws=1024, n_starts=4, max_iter=50, rng=None
     inside = lambda thetas: np.isfinite(model.log_priors_batch(thetas))
     results = lm_search(curvature, model.log_posterior_batch, starts, columns, max_iter=max_iter, feasible=inside)
     return max(results, key=lambda r: (r.lnpost if np.isfinite(r.lnpost) else -np.inf))
+
+
+def _pack_fields(parts, capacity):
+    """Consecutive slices of several fields' rows in calls of at most `capacity` rows: parts [(field, n_rows)] ->
+    list of calls, each a list of (field, lo, hi)."""
+    calls, room = [[]], capacity
+    for f, n in parts:
+        lo = 0
+        while lo < n:
+            if room == 0:
+                calls.append([])
+                room = capacity
+            hi = min(n, lo + room)
+            calls[-1].append((f, lo, hi))
+            room -= hi - lo
+            lo = hi
+    return [c for c in calls if c]
+
+
+def _set_log_posteriors(fieldset, thetas):
+    """`FieldSet.log_posterior_batch` of {field: [m, P]} in as few calls as `max_walkers` allows -> {field: [m]}."""
+    out = {f: np.empty(len(t)) for f, t in thetas.items()}
+    for call in _pack_fields([(f, len(thetas[f])) for f in sorted(thetas)], fieldset.max_walkers):
+        batch = [None] * len(fieldset.models)
+        for f, lo, hi in call:
+            batch[f] = thetas[f][lo:hi]
+        got = fieldset.log_posterior_batch(batch)
+        for f, lo, hi in call:
+            out[f][lo:hi] = got[f]
+    return out
+
+
+def find_modes(fieldset, start=None, n_draws=1024, n_starts=4, max_iter=50, rng=None):
+    """`find_mode` for every field of a `FieldSet` at once: the fields' searches advance side by side under
+    `lm_search`'s rule, and one iteration is ONE `FieldSet.fisher` call and ONE `FieldSet.log_posterior_batch` call for
+    all fields and starts (split only where `max_walkers` is too small); the priors' derivatives and the edge
+    bisection stay on the host.  Field f's result is what `find_mode(fieldset.models[f], ...)` finds from the same
+    starts.
+
+    start   None, or one [n, P] (or [P]) array per field
+    rng     one RandomState or seed for all fields' prior draws (taken in field order), or a list of one per field
+    Returns a list of `ModeResult`, one per field."""
+    models = fieldset.models
+    n_f = len(models)
+    columns = [default_columns(m) for m in models]
+    if any(len(c) == 0 for c in columns):
+        raise ValueError('the model has no continuous free parameter')
+    if start is None:
+        rngs = list(rng) if isinstance(rng, (list, tuple)) else [rng] * n_f
+        if len(rngs) != n_f:
+            raise ValueError('rng: one generator, or one per field ({} given for {} fields)'.format(len(rngs), n_f))
+        if rng is not None and not isinstance(rng, (list, tuple, np.random.RandomState)):
+            rngs = [np.random.RandomState(rng)] * n_f          # one seed: one stream, the fields in order
+        draws = {f: _prior_draws(m, int(n_draws), rngs[f]) for f, m in enumerate(models)}
+        lps = _set_log_posteriors(fieldset, draws)
+        starts = []
+        for f in range(n_f):
+            lp = np.where(np.isfinite(lps[f]), lps[f], -np.inf)
+            order = np.argsort(-lp, kind='mergesort')[:max(int(n_starts), 1)]
+            order = order[np.isfinite(lp[order])]
+            if len(order) == 0:
+                raise ValueError('field {}: none of the {} prior draws has a finite log-posterior'.format(f, n_draws))
+            starts.append(draws[f][order])
+    else:
+        if len(start) != n_f:
+            raise ValueError('start: one [n, P] array per field ({} given for {} fields)'.format(len(start), n_f))
+        starts = [np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in start]
+
+    def curvatures(thetas):
+        fields = sorted(thetas)
+        steps = {f: default_steps(models[f], thetas[f], columns[f]) for f in fields}
+        fis = fieldset.fisher([thetas.get(f) for f in range(n_f)], step=[steps.get(f) for f in range(n_f)],
+                              columns=columns)
+        out = {}
+        for f in fields:
+            first, second = prior_derivatives(models[f].log_priors_batch, thetas[f], steps[f], columns[f])
+            hess = fis[f]['F'].copy()
+            hess[:, np.arange(len(columns[f])), np.arange(len(columns[f]))] -= second
+            out[f] = (hess, fis[f]['grad'] + first)
+        return out
+
+    def inside(model):
+        return lambda thetas: np.isfinite(model.log_priors_batch(thetas))
+
+    serve = (('curvature', curvatures), ('lnpost', lambda thetas: _set_log_posteriors(fieldset, thetas)))
+    searches = [_lm_steps(starts[f], columns[f], max_iter, 1e-3, inside(models[f])) for f in range(n_f)]
+    pending = [next(s) for s in searches]
+    results = [None] * n_f
+    while any(p is not None for p in pending):
+        for kind, call in serve:                     # every search asks for curvatures first, then log-posteriors
+            who = [f for f in range(n_f) if pending[f] is not None and pending[f][0] == kind]
+            if not who:
+                continue
+            with np.errstate(all='ignore'):
+                answers = call({f: pending[f][1] for f in who})
+            for f in who:
+                try:
+                    pending[f] = searches[f].send(answers[f])
+                except StopIteration as done:
+                    pending[f], results[f] = None, done.value
+    return [max(res, key=lambda r: (r.lnpost if np.isfinite(r.lnpost) else -np.inf)) for res in results]
 
 
 def _prior_draws(model, n, rng):

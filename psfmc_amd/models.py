@@ -806,10 +806,96 @@ class FieldSet(object):
         tempered samplers work with.  A member model's own `log_likelihood_and_prior_batch` gives its field's."""
         return self.context.eval_split(thetas)
 
+    def fisher(self, thetas, step=None, columns=None):
+        """`MultiComponentModel.fisher` for every field at once: thetas one [n_f, P] (or [P]) array per field, None
+        to leave a field out -> a list of the dicts `fs.models[f].fisher(thetas[f])` returns (None for a field left
+        out), the same bits.  The stencils of all fields go to the device together (psfmc_fisher_rows_fields): one
+        call per group of fields with the same number of differentiated columns, split only where `max_walkers` is
+        too small for the group.
+
+        step, columns  None, or one entry per field (an entry None: the defaults of that field's model,
+                       `mode.default_steps` / `mode.default_columns`); `columns` may also be one list for all fields"""
+        from . import mode
+        n_f = len(self.models)
+        if len(thetas) != n_f:
+            raise ValueError('one parameter array per field')
+        per_field = lambda arg: [None] * n_f if arg is None else list(arg)
+        if columns is not None and len(columns) and columns[0] is not None and np.ndim(columns[0]) == 0:
+            columns = [columns] * n_f
+        steps, cols = per_field(step), per_field(columns)
+        if len(steps) != n_f or len(cols) != n_f:
+            raise ValueError('step / columns: one entry per field')
+        jobs, outs = [], [None] * n_f
+        for f, (m, theta) in enumerate(zip(self.models, thetas)):
+            if theta is None:
+                continue
+            single = np.ndim(theta) == 1
+            theta = m._theta(theta)
+            col = mode.default_columns(m) if cols[f] is None else np.asarray(cols[f], dtype=np.int64)
+            if col.ndim != 1 or len(col) < 1 or col.min() < 0 or col.max() >= m.num_params:
+                raise ValueError('field {}: columns must be a non-empty list of columns of the parameter '
+                                 'vector'.format(f))
+            n, k = theta.shape[0], len(col)
+            if 2 * k + 1 > self.max_walkers:
+                raise ValueError('a stencil of {} columns is {} walkers; the set was built for max_walkers={}'.format(
+                    k, 2 * k + 1, self.max_walkers))
+            h = mode.default_steps(m, theta, col) if steps[f] is None else steps[f]
+            h = np.array(np.broadcast_to(np.asarray(h, dtype=np.float64), (n, k)))
+            if not np.all(np.isfinite(h) & (h > 0)):
+                raise ValueError('steps must be finite and positive')
+            vecs = mode.stencil(theta, h, col).reshape(-1, m.num_params)
+            rows, aux = m.derived_rows(vecs), m.aux_rows(vecs)
+            outs[f] = dict(F=np.empty((n, k, k)), grad=np.empty((n, k)), loglike=np.empty(n), columns=col, step=h)
+            jobs.append(dict(f=f, k=k, n=n, single=single, rows=rows.reshape(n, 2 * k + 1, -1),
+                             aux=None if aux is None else np.asarray(aux).reshape(n, 2 * k + 1, -1)))
+        for k in sorted({j['k'] for j in jobs}):
+            group = [j for j in jobs if j['k'] == k]
+            for call in mode._pack_fields([(i, j['n']) for i, j in enumerate(group)], self.max_walkers // (2 * k + 1)):
+                fields = np.concatenate([np.full(hi - lo, group[i]['f']) for i, lo, hi in call])
+                rows = np.concatenate([group[i]['rows'][lo:hi] for i, lo, hi in call])
+                inv2h = np.concatenate([0.5 / outs[group[i]['f']]['step'][lo:hi] for i, lo, hi in call])
+                aux = _stack_aux([None if group[i]['aux'] is None else group[i]['aux'][lo:hi] for i, lo, hi in call],
+                                 [hi - lo for _, lo, hi in call], 2 * k + 1)
+                fisher, grad, ll = self.context.fisher_rows_fields(fields, rows, inv2h, aux=aux)
+                at = 0
+                for i, lo, hi in call:
+                    out = outs[group[i]['f']]
+                    out['F'][lo:hi], out['grad'][lo:hi] = fisher[at:at + hi - lo], grad[at:at + hi - lo]
+                    out['loglike'][lo:hi] = ll[at:at + hi - lo]
+                    at += hi - lo
+        for j in jobs:
+            outs[j['f']] = _fisher_result(outs[j['f']], j['single'])
+        return outs
+
     def close(self):
         self.context.close()
         for m in self.models:
             m._engine = None               # (views of the context just closed)
+
+
+def _stack_aux(parts, counts, n_st):
+    """The auxiliary rows of a call whose stencils come from several models: parts[i] [counts[i], n_st, n_aux_i] or
+    None -> [sum(counts) n_st, widest n_aux] with zeros where a model has no (or shorter) rows; None if none has."""
+    if all(p is None for p in parts):
+        return None
+    width = max(p.shape[-1] for p in parts if p is not None)
+    out = np.zeros((sum(counts), n_st, width))
+    at = 0
+    for p, n in zip(parts, counts):
+        if p is not None:
+            out[at:at + n, :, :p.shape[-1]] = p
+        at += n
+    return out.reshape(-1, width)
+
+
+def _fisher_result(out, single):
+    """A fisher() result as it is returned: NaN F and grad for a base where either has a non-finite entry, -inf
+    for a non-finite log-likelihood, and no leading axis for a single vector."""
+    fisher, grad = out['F'], out['grad']
+    bad = ~(np.isfinite(fisher).all(axis=(1, 2)) & np.isfinite(grad).all(axis=1))
+    fisher[bad], grad[bad] = np.nan, np.nan
+    out['loglike'] = np.where(np.isfinite(out['loglike']), out['loglike'], -np.inf)
+    return {key: (val[0] if single and key != 'columns' else val) for key, val in out.items()}
 
 
 
@@ -1070,6 +1156,84 @@ class JointModel(object):
         if not parts:
             return np.zeros(0), np.zeros(0)
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+    # -- Fisher matrix and gradient ---------------------------------------------------------
+    def _check_columns(self, columns):
+        """The differentiated joint columns as an array, or ValueError (no device is touched)."""
+        from . import mode
+        columns = mode.default_columns(self) if columns is None else np.asarray(columns, dtype=np.int64)
+        if (columns.ndim != 1 or len(columns) < 1 or columns.min() < 0 or columns.max() >= self.num_params or
+                len(set(columns.tolist())) != len(columns)):
+            raise ValueError('columns must be a non-empty list of distinct joint columns in [0, {})'.format(
+                self.num_params))
+        return columns
+
+    def fisher(self, theta, step=None, columns=None):
+        """Fisher matrix and gradient of the JOINT log-likelihood (the fields' sum) at theta ([P_joint] or
+        [n, P_joint]) over joint columns, from central-difference stencils of device images
+        (psfmc_fisher_rows_joint; the definition: `mode.joint_fisher` of the fields' `mode.fisher_from_stencil`).
+
+        columns  the differentiated joint columns (default: every joint column whose prior is not discrete -- every
+                 exposure's PSF index stays at the base value)
+        step     [K] or [n, K] steps h_k (default: `mode.default_steps`' rule on the joint blocks' priors); the
+                 fields that share a column share its step
+        Field f's stencil holds the base and the +- vectors of only the joint columns it reads, so a per-field
+        column costs two images, not two per field.  Every field must read the same number of `columns` (the
+        default's always do), at most 63; their total is limited only by memory.
+        Returns dict(F [n, K, K], grad [n, K] (of lnL), loglike [n], columns [K], step [n, K]) in joint terms;
+        without the leading axis for a [P_joint] theta.  NaN F and grad where an image is not finite on a good
+        pixel, as `MultiComponentModel.fisher`.  `loglike` is `log_likelihood_and_prior_batch`'s lnL of theta, bit
+        for bit (one more evaluation of the n base vectors, from raw vectors as the samplers evaluate them): -inf
+        outside the priors, where F and grad -- the images do not care about supports -- are still the likelihood's."""
+        from . import mode
+        single = np.ndim(theta) == 1
+        theta = self._theta(theta)
+        columns = self._check_columns(columns)
+        n, k = theta.shape[0], len(columns)
+        if step is None:
+            step = mode.default_steps(self, theta, columns)
+        step = np.array(np.broadcast_to(np.asarray(step, dtype=np.float64), (n, k)))
+        if not np.all(np.isfinite(step) & (step > 0)):
+            raise ValueError('steps must be finite and positive')
+        place = np.full(self.num_params, -1, dtype=np.int64)       # a joint column's place among `columns`
+        place[columns] = np.arange(k)
+        own = [np.flatnonzero(place[jc] >= 0) for jc in self._columns]          # the field's own differentiated columns
+        col_of = [place[jc[o]] for jc, o in zip(self._columns, own)]
+        k_f = len(own[0])
+        if k_f < 1 or any(len(o) != k_f for o in own):
+            raise ValueError('every field must read the same number (>= 1) of the differentiated columns; the '
+                             'fields read {}'.format([len(o) for o in own]))
+        n_f, n_st = len(self.field_models), 2 * k_f + 1
+        eng = self.engine
+        per_call = self._max_walkers // (n_f * n_st)
+        if per_call < 1:
+            raise ValueError('{} field stencils of {} walkers exceed max_walkers={}'.format(n_f, n_st,
+                                                                                           self._max_walkers))
+        out = dict(F=np.empty((n, k, k)), grad=np.empty((n, k)), loglike=np.empty(n), columns=columns, step=step)
+        for lo in range(0, n, per_call):
+            hi = min(lo + per_call, n)
+            rows, inv2h, aux = [], [], []
+            for f, m in enumerate(self.field_models):
+                h = step[lo:hi][:, col_of[f]]
+                vecs = mode.stencil(theta[lo:hi][:, self._columns[f]], h, own[f]).reshape(-1, m.num_params)
+                rows.append(m.derived_rows(vecs).reshape(hi - lo, n_st, -1))
+                a = m.aux_rows(vecs)
+                aux.append(None if a is None else np.asarray(a).reshape(hi - lo, n_st, -1))
+                inv2h.append(0.5 / h)
+            aux_rows = None
+            if any(a is not None for a in aux):
+                width = max(a.shape[-1] for a in aux if a is not None)
+                aux_rows = np.zeros((hi - lo, n_f, n_st, width))
+                for f, a in enumerate(aux):
+                    if a is not None:
+                        aux_rows[:, f, :, :a.shape[-1]] = a
+                aux_rows = aux_rows.reshape(-1, width)
+            out['F'][lo:hi], out['grad'][lo:hi], _ = eng.fisher_rows(
+                np.stack(col_of), np.stack(rows, axis=1), np.stack(inv2h, axis=1), k, aux=aux_rows)
+        # (the entry's own lnlike is the sum of the fields' ROW-based log-likelihoods, whose rows the host derives: it
+        # sits a rounding apart -- 2e-13 relative, DESIGN.md section 31 -- from the lnL the samplers see)
+        out['loglike'] = self.log_likelihood_and_prior_batch(theta)[0]
+        return _fisher_result(out, single)
 
     # -- posterior-image bookkeeping: the device sampler counts samples on the model, every field's sums
     # get each of them -------------------------------------------------------------------
