@@ -355,6 +355,39 @@ int psfmc_set_radial_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* 
 int psfmc_set_truncation_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* flags, const int* col,
                                 const double* konst);
 /*
+ * BENDING MODES of general components (GALFIT's bending modes; not the reference's).  Definition:
+ * psfmc_amd/ModelComponents/Sersic.py Sersic.bend and Sersic.bent_image; kernels: csrc/psfmc_general.h.  mode_mask
+ * [n_sersic]: per Sersic slot (model-file order) bit m - 1 set where it has bending mode m, m = 1 ... PSFMC_BEND_MODES;
+ * col / konst [n_sersic][PSFMC_BEND_MODES] have the meaning of psfmc_set_layout's slot_col / slot_const, per slot the
+ * amplitudes a_1 ... a_4 in units of the semi-major radius; the entry of an absent mode is a finite constant (0 by
+ * convention) that no pixel reads.  With (u, v) the slot's coordinates in units of its semi-major and semi-minor radius
+ * (after the spiral's winding where there is one), r_a = 1 / hypot(m00, m01) and r_b = 1 / hypot(m10, m11),
+ *     v' = v + (r_a / r_b) sum_m a_m u^m
+ * and everything downstream -- the generalised radius, the angle of the Fourier modes, the centre, the laws and the
+ * truncation ramps -- reads (u, v').  In pixels along (x) and across (y) the major axis this is y' = y + sum_m a_m
+ * (x / r_a)^m r_a: the ridge lies at Y = -r_a sum_m a_m (X / r_a)^m.  The shear has unit Jacobian and leaves the centre
+ * where it is: mag stays the total magnitude, and psfmc_set_general_mean averages the bent law with its scheme
+ * unchanged.  The call APPENDS these 4 n_sersic entries to the field's auxiliary table BEHIND everything it holds.  A
+ * context with bending modes ALWAYS carries the Fourier, spiral, radial and truncation blocks: a field without them gets
+ * entries inside their supports that are never read (nothing more is launched for them), so that from the first such
+ * call on every walker's auxiliary vector of the context -- psfmc_set_aux_rows' rows included -- has 2 n_sky +
+ * 29 n_sersic doubles, the amplitudes of Sersic k at 2 n_sky + 25 n_sersic + 4 k, the entries of a field without
+ * bending modes unused.  An amplitude that is not finite gives log-posterior -inf (NaN through a row-based call without
+ * writable skip flags); the shear is a bijection for every finite value, so there is no further condition.  Call after
+ * the field's psfmc_set_aux_layout, which must flag the bent slots as general, after its psfmc_set_fourier_layout,
+ * psfmc_set_spiral_layout, psfmc_set_radial_layout and psfmc_set_truncation_layout where those are called (each of
+ * them, like a new layout or aux layout, drops the field's bending modes) and, in joint fits, before
+ * psfmc_set_joint_priors; psfmc_set_general_mean keeps them; all-zero masks remove them, and the slots are rendered as
+ * they were, bit for bit.  Refused (PSFMC_EINVAL) with nothing changed: a mask bit above 3, bending on a
+ * pixel-integrated slot or on one that is not flagged general, a field without an aux layout, a wrong n_sersic, a
+ * column outside the layout.  The fields of one context keep their own masks, registered in any order.  A context that
+ * never receives a nonzero mask allocates nothing, launches the kernels it launched and computes what it did without
+ * this call.
+ */
+#define PSFMC_BEND_MODES 4
+int psfmc_set_bending_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* mode_mask, const int* col,
+                             const double* konst);
+/*
  * General components rendered as the MEAN OF THEIR LAW OVER EACH PIXEL (Sersic(..., pixel_mean=True) with a boxiness,
  * modes or a spiral, Moffat(..., pixel_mean=True), Ferrer(..., pixel_mean=True); not the reference's).  Definition:
  * psfmc_amd/ModelComponents/Sersic.py Sersic.general_point and Sersic.general_mean_image; kernels:
@@ -738,6 +771,9 @@ int psfmc_group_set_spiral_layout(psfmc_group* group, int n_sersic, const int* f
 /* psfmc_set_truncation_layout (field 0) on every device of the group */
 int psfmc_group_set_truncation_layout(psfmc_group* group, int n_sersic, const int* flags, const int* col,
                                       const double* konst);
+/* psfmc_set_bending_layout (field 0) on every device of the group */
+int psfmc_group_set_bending_layout(psfmc_group* group, int n_sersic, const int* mode_mask, const int* col,
+                                   const double* konst);
 /* psfmc_set_radial_layout (field 0) on every device of the group */
 int psfmc_group_set_radial_layout(psfmc_group* group, int n_sersic, const int* kinds, const int* col,
                                   const double* konst);
@@ -848,6 +884,21 @@ int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* base_col, c
                                  const int* rad_kinds, const int* rad_col, const double* rad_const,
                                  const int* tru_flags, const int* tru_col, const double* tru_const,
                                  double* out_const, int* out_col, int* out_kinds, int* out_sides, int* counts);
+/*
+ * ... and with the bending block (psfmc_set_bending_layout's mode_mask, col and konst; NULL bnd_mask: never registered,
+ * and the call is psfmc_debug_aux_table_blocks).  out_const / out_col [2 n_sky + 29 n_sersic]; where bnd_mask is given,
+ * out_sides [n_sersic] is written where counts[4] > 0 (zeros for a field without truncations), out_bends [n_sersic]
+ * receives the bending masks (written where counts[5] > 0) and counts has six entries: n_aux, n_fou, n_spi, n_rad,
+ * n_tru, n_bnd.
+ */
+int psfmc_debug_aux_table_bending(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                                  const int* mode_mask, const int* fou_col, const double* fou_const,
+                                  const int* spi_flags, const int* spi_col, const double* spi_const,
+                                  const int* rad_kinds, const int* rad_col, const double* rad_const,
+                                  const int* tru_flags, const int* tru_col, const double* tru_const,
+                                  const int* bnd_mask, const int* bnd_col, const double* bnd_const,
+                                  double* out_const, int* out_col, int* out_kinds, int* out_sides, int* out_bends,
+                                  int* counts);
 
 /*
  * Fisher matrix and gradient of the Gaussian log-likelihood

@@ -1,7 +1,7 @@
 """
 Components whose RADIAL LAW is not the Sersic law: `Moffat` and `Ferrer` (GALFIT's component types and parameter
 names; not the reference's).  Both are functions of the generalised radius alone, so they take `boxiness`, `fourier`,
-`spiral` and `truncation` exactly as `Sersic` does, occupy a Sersic slot of the model (index fixed at 1, the two radii in the
+`spiral`, `truncation` and `bending` exactly as `Sersic` does, occupy a Sersic slot of the model (index fixed at 1, the two radii in the
 places of reff / reff_b) and always run the general kernels.  Definition: `Sersic.radial_image`.
 """
 import numpy as np
@@ -19,7 +19,8 @@ class _RadialLaw(Sersic):
     reff = property(lambda self: getattr(self, self.RADII[0]))
     reff_b = property(lambda self: getattr(self, self.RADII[1]))
 
-    def _init_law(self, xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean=False, truncation=None):
+    def _init_law(self, xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean=False, truncation=None,
+                  bending=None):
         ComponentBase.__init__(self)
         self.xy = xy
         self.mag = mag
@@ -27,7 +28,7 @@ class _RadialLaw(Sersic):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = False
-        self._init_shape(boxiness, fourier, spiral, pixel_mean, truncation)
+        self._init_shape(boxiness, fourier, spiral, pixel_mean, truncation, bending)
 
     @property
     def is_general(self):
@@ -71,8 +72,8 @@ class Moffat(_RadialLaw):
     `fwhm_b` are the FULL widths at half maximum along the major / minor axis (half the peak lies at rho = 1/2),
     `beta` the wing exponent, `mag` the total magnitude: Sigma_0 = F g (beta - 1) / (pi fwhm fwhm_b A(c) Q cos(incl)).
     Support: beta finite and > 1, fwhm_b <= fwhm (log-prior -inf otherwise).  `angle`, `angle_degrees`, `boxiness`,
-    `fourier`, `spiral` and `truncation` are `Sersic`'s (the truncation radii in pixels along the major axis; `mag`
-    stays the untruncated total).  The value is the law at the pixel centre -- no centroid term, the
+    `fourier`, `spiral`, `truncation` and `bending` are `Sersic`'s (the truncation radii in pixels along the major
+    axis; `mag` stays the untruncated total).  The value is the law at the pixel centre -- no centroid term, the
     reference's belongs to the Sersic law -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`;
     `pixel_mean=True` renders the mean of the law over each pixel instead (`Sersic.general_mean_image`), which is what
     a `fwhm` of a few pixels needs.  Definition: `Sersic.radial_image`."""
@@ -88,8 +89,8 @@ class Moffat(_RadialLaw):
     beta = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, fwhm=None, fwhm_b=None, beta=None, angle=None, angle_degrees=False,
-                 boxiness=None, fourier=None, spiral=None, pixel_mean=False, truncation=None):
-        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean, truncation)
+                 boxiness=None, fourier=None, spiral=None, pixel_mean=False, truncation=None, bending=None):
+        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean, truncation, bending)
         self.fwhm = fwhm
         self.fwhm_b = fwhm_b
         self.beta = beta
@@ -101,7 +102,7 @@ class Ferrer(_RadialLaw):
     truncation radii along the major / minor axis, `alpha` the sharpness of the truncation, `beta` the central
     slope, `mag` the total magnitude: Sigma_0 = F / (pi r_out r_out_b A(c) Q cos(incl) (2/k) B(2/k, alpha + 1)),
     k = 2 - beta.  Support: alpha, beta finite, alpha >= 0, beta < 2, r_out_b <= r_out (log-prior -inf otherwise).
-    `angle`, `angle_degrees`, `boxiness`, `fourier`, `spiral` and `truncation` are `Sersic`'s (the truncation radii
+    `angle`, `angle_degrees`, `boxiness`, `fourier`, `spiral`, `truncation` and `bending` are `Sersic`'s (the truncation radii
     in pixels along the major axis; `mag` stays the untruncated total).  The value is the law at the pixel
     centre -- no centroid term: the reference's belongs to the Sersic law, and this law's log-slope diverges at the
     edge -- and an on-pixel centre is finite (Sigma_0).  There is no `integrate`; `pixel_mean=True` renders the mean
@@ -120,8 +121,9 @@ class Ferrer(_RadialLaw):
     beta = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, r_out=None, r_out_b=None, alpha=None, beta=None, angle=None,
-                 angle_degrees=False, boxiness=None, fourier=None, spiral=None, pixel_mean=False, truncation=None):
-        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean, truncation)
+                 angle_degrees=False, boxiness=None, fourier=None, spiral=None, pixel_mean=False, truncation=None,
+                 bending=None):
+        self._init_law(xy, mag, angle, angle_degrees, boxiness, fourier, spiral, pixel_mean, truncation, bending)
         self.r_out = r_out
         self.r_out_b = r_out_b
         self.alpha = alpha

@@ -72,6 +72,20 @@ class Sersic(ComponentBase):
     either); `Sersic.truncation_flux_fraction` gives the fraction of it that survives.  The ramps are soft by
     construction, so `pixel_mean=True` averages the product with its scheme unchanged and adds no refinement at the
     radii.  A component with `truncation` alone is a general one with c = 0 and no modes; `truncation` with
+    `integrate=True` raises ValueError (use `pixel_mean=True`).
+
+    `bending={m: a_m, ...}` (m = 1 ... 4; numbers or priors; GALFIT's bending modes, not the reference's) displaces the
+    component's ridge across its major axis by a polynomial of the coordinate along it (`Sersic.bend`,
+    `Sersic.bent_image`): with (u, v) the coordinates in units of the semi-major and semi-minor radius r_a, r_b (after
+    the spiral's winding where there is one), v' = v + (r_a / r_b) sum_m a_m u^m, and everything downstream reads
+    (u, v') -- in pixels along and across the major axis y' = y + r_a sum_m a_m (x / r_a)^m, so that the ridge lies at
+    Y = -r_a sum_m a_m (X / r_a)^m: a banana (m = 2), an S-shaped tidal pair (m = 3), a sheared envelope (m = 1).  The
+    parameters are the attributes `bend1` ... `bend4`; an absent mode is the constant 0 and adds none.  The shear has
+    unit Jacobian and f(0) = 0, so `mag` stays the total magnitude and the centre the centre; boxiness, modes, spiral,
+    radial law and truncation act on the bent coordinates.  Support: every amplitude finite (log-prior -inf otherwise);
+    the shear is a bijection for any value.  m = 1 on a plain ellipse is another ellipse -- degenerate with `angle` and
+    the axis ratio; it is allowed, not refused (fix it or give it a narrow prior).  `pixel_mean=True` averages the bent
+    law with its scheme unchanged.  A component with `bending` alone is a general one with c = 0; `bending` with
     `integrate=True` raises ValueError (use `pixel_mean=True`)."""
     device_kind = 'sersic'
     # the radial law: None for the Sersic law, else a key of RADIAL_KINDS (the subclasses `Moffat` and `Ferrer`)
@@ -93,13 +107,17 @@ class Sersic(ComponentBase):
     TRUNC_ATTRS = ('trunc_in_lo', 'trunc_in_hi', 'trunc_out_lo', 'trunc_out_hi')
     TRUNC_PARAMS = 4
     TRUNC_ABSENT = (0.0, 1.0, 0.0, 1.0)
+    # the modes of `bending` (psfmc_set_bending_layout's mask bit m - 1; PSFMC_BEND_MODES) and their attributes
+    BEND_MODES = (1, 2, 3, 4)
+    BEND_ATTRS = tuple('bend%d' % m for m in BEND_MODES)
     _fits_abbrs = ([('trunc_in_lo', 'TIL'), ('trunc_in_hi', 'TIH'), ('trunc_out_lo', 'TOL'), ('trunc_out_hi', 'TOH'),
                     ('Sersic', 'SER'), ('spiral_r_in', 'SRI'), ('spiral_r_out', 'SRO'), ('spiral_wind', 'SWD'),
                     ('spiral_alpha', 'SAL'), ('spiral_incl', 'SIN'), ('spiral_sky', 'SPA'),
                     ('reff_b', 'REB'), ('reff', 'RE'),
                     ('index', 'N'), ('angle', 'ANG'), ('boxiness', 'BOX')] +
                    [('f%d_amp' % m, 'F%dA' % m) for m in FOURIER_MODES] +
-                   [('f%d_phase' % m, 'F%dP' % m) for m in FOURIER_MODES])
+                   [('f%d_phase' % m, 'F%dP' % m) for m in FOURIER_MODES] +
+                   [('bend%d' % m, 'BD%d' % m) for m in BEND_MODES])
 
     xy = StochasticProperty()
     mag = StochasticProperty()
@@ -130,10 +148,14 @@ class Sersic(ComponentBase):
     trunc_in_hi = StochasticProperty()
     trunc_out_lo = StochasticProperty()
     trunc_out_hi = StochasticProperty()
+    bend1 = StochasticProperty()
+    bend2 = StochasticProperty()
+    bend3 = StochasticProperty()
+    bend4 = StochasticProperty()
 
     def __init__(self, xy=None, mag=None, reff=None, reff_b=None, index=None,
                  angle=None, angle_degrees=False, integrate=False, boxiness=None, fourier=None, spiral=None,
-                 pixel_mean=False, truncation=None):
+                 pixel_mean=False, truncation=None, bending=None):
         super(Sersic, self).__init__()
         self.xy = xy
         self.mag = mag
@@ -143,19 +165,15 @@ class Sersic(ComponentBase):
         self.angle = angle
         self.angle_degrees = angle_degrees
         self.integrate = bool(integrate)
-        self._init_shape(boxiness, fourier, spiral, pixel_mean, truncation)
+        self._init_shape(boxiness, fourier, spiral, pixel_mean, truncation, bending)
 
-    def _init_shape(self, boxiness, fourier, spiral, pixel_mean=False, truncation=None):
-        """The isophote-shape keywords `boxiness`, `fourier` and `spiral`, the rendering keyword `pixel_mean` and
-        `truncation` (shared with the radial-law subclasses)."""
+    def _init_shape(self, boxiness, fourier, spiral, pixel_mean=False, truncation=None, bending=None):
+        """The isophote-shape keywords `boxiness`, `fourier` and `spiral`, the rendering keyword `pixel_mean`,
+        `truncation` and `bending` (shared with the radial-law subclasses)."""
         self.pixel_mean = bool(pixel_mean)
         if self.pixel_mean and self.integrate:
             raise ValueError('Sersic: pixel_mean=True together with integrate=True is not supported (integrate=True '
                              'is the plain profile\'s pixel integral, pixel_mean=True a general component\'s)')
-        if (self.pixel_mean and self.radial_law is None and boxiness is None and fourier is None and spiral is None
-                and truncation is None):
-            raise ValueError('Sersic: pixel_mean=True needs boxiness, fourier or spiral; the plain profile has '
-                             'integrate=True')
         self.truncation_sides = ()
         if truncation is not None:
             if self.integrate:
@@ -182,6 +200,31 @@ class Sersic(ComponentBase):
                 setattr(self, Sersic.TRUNC_ATTRS[2 * side + 1], hi)
             self.truncation_sides = tuple(k for k in Sersic.TRUNC_KEYS if k in truncation)
         self.has_truncation = bool(self.truncation_sides)
+        self.bending_modes = ()
+        if bending is not None:
+            if self.integrate:
+                raise ValueError('Sersic: bending together with integrate=True is not supported (the '
+                                 'pixel-integrated profile is defined for elliptical isophotes; use pixel_mean=True)')
+            modes = []
+            # (a mapping, or pairs (m, a_m): pairs can name a mode twice)
+            for m, amp in (bending.items() if hasattr(bending, 'items') else list(bending)):
+                try:
+                    whole = not isinstance(m, bool) and int(m) == m and int(m) in Sersic.BEND_MODES
+                except (TypeError, ValueError):
+                    whole = False
+                if not whole:
+                    raise ValueError('Sersic: bending mode numbers are integers in 1 ... 4, got {!r}'.format(m))
+                if int(m) in modes:
+                    raise ValueError('Sersic: bending mode {} given twice'.format(int(m)))
+                modes.append(int(m))
+                setattr(self, 'bend%d' % int(m), amp)
+            self.bending_modes = tuple(sorted(modes))
+        self.has_bending = bool(self.bending_modes)
+        # (asked of what was parsed: an empty `bending` names no mode and makes no general component)
+        if (self.pixel_mean and self.radial_law is None and boxiness is None and fourier is None and spiral is None
+                and not self.has_truncation and not self.has_bending):
+            raise ValueError('Sersic: pixel_mean=True needs boxiness, fourier or spiral; the plain profile has '
+                             'integrate=True')
         self.has_boxiness = boxiness is not None
         if self.has_boxiness:
             if self.integrate:
@@ -226,8 +269,14 @@ class Sersic(ComponentBase):
 
     @property
     def is_general(self):
-        """Does the component run the general kernels (a `boxiness`, `fourier`, `spiral` or `truncation` keyword)?"""
-        return self.has_boxiness or self.has_fourier or self.has_spiral or self.has_truncation
+        """Does the component run the general kernels (a `boxiness`, `fourier`, `spiral`, `truncation` or `bending`
+        keyword)?"""
+        return self.has_boxiness or self.has_fourier or self.has_spiral or self.has_truncation or self.has_bending
+
+    @property
+    def bending_mask(self):
+        """psfmc_set_bending_layout's mask of the slot: bit m - 1 set where the component has bending mode m; 0: none."""
+        return sum(1 << (m - 1) for m in self.bending_modes)
 
     @property
     def truncation_flags(self):
@@ -240,7 +289,8 @@ class Sersic(ComponentBase):
         comma-separated mode numbers when it has Fourier modes, `<count>SERSPI = T` when it has a spiral,
         `<count>SERLAW = 'moffat' | 'ferrer'` when its radial law is not the Sersic law (`Moffat`, `Ferrer`),
         `<count>SERAVG = T` when it is rendered as the mean over each pixel (`pixel_mean=True`), `<count>SERTRU =
-        'inner' | 'outer' | 'inner,outer'` when it is truncated, nothing otherwise."""
+        'inner' | 'outer' | 'inner,outer'` when it is truncated, `<count>SERBND` = the comma-separated mode numbers
+        when it has bending modes, nothing otherwise."""
         out = {'{:d}SERINT'.format(count): True} if self.integrate else {}
         if self.has_boxiness:
             out['{:d}SERBOX'.format(count)] = True
@@ -254,7 +304,29 @@ class Sersic(ComponentBase):
             out['{:d}SERAVG'.format(count)] = True
         if self.has_truncation:
             out['{:d}SERTRU'.format(count)] = ','.join(self.truncation_sides)
+        if self.has_bending:
+            out['{:d}SERBND'.format(count)] = ','.join(str(m) for m in self.bending_modes)
         return out
+
+    @staticmethod
+    def _bending_ok(amps):
+        """The support of the bending modes, amps [..., n_modes]: every amplitude finite (the shear is a bijection for
+        any value)."""
+        return np.all(np.isfinite(np.asarray(amps, dtype=np.float64)), axis=-1)
+
+    def _bending_values(self, vals, n_w=None):
+        """The amplitudes of the modes present, in mode order: [n_modes] (n_w None: current values) or
+        [n_w, n_modes]."""
+        shape = (len(self.bending_modes),) if n_w is None else (n_w, len(self.bending_modes))
+        get = (lambda k: np.reshape(vals[k], shape[:-1])) if n_w is not None else (lambda k: float(np.ravel(vals(k))[0]))
+        return np.stack([get('bend%d' % m) for m in self.bending_modes], axis=-1).reshape(shape).astype(np.float64)
+
+    def bending_list(self):
+        """The current values as the definition functions take them: [(m, a_m), ...] in mode order, or None for a
+        component without the keyword."""
+        if not self.has_bending:
+            return None
+        return list(zip(self.bending_modes, (float(a) for a in self._bending_values(lambda k: getattr(self, k)))))
 
     @staticmethod
     def _truncation_ok(trunc, flags):
@@ -341,6 +413,8 @@ class Sersic(ComponentBase):
         if self.has_truncation and not Sersic._truncation_ok(self._truncation_values(lambda k: getattr(self, k)),
                                                               self.truncation_flags):
             return -np.inf
+        if self.has_bending and not Sersic._bending_ok(self._bending_values(lambda k: getattr(self, k))):
+            return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
     def log_priors_batch(self, block):
@@ -356,6 +430,8 @@ class Sersic(ComponentBase):
         if self.has_truncation:
             logp = np.where(Sersic._truncation_ok(self._truncation_values(vals, len(logp)), self.truncation_flags),
                             logp, -np.inf)
+        if self.has_bending:
+            logp = np.where(Sersic._bending_ok(self._bending_values(vals, len(logp))), logp, -np.inf)
         return logp
 
     @staticmethod
@@ -389,16 +465,18 @@ class Sersic(ComponentBase):
         """Add this component (current values) to `arr` on the host: the reference's formula, or the
         pixel-integrated profile with `integrate=True`.  The GPU rasterisers compute the same."""
         row = self.derived_row(mag_zp)
-        if self.has_truncation:
+        if self.has_truncation or self.has_bending:
             amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
             args = (self.radial_law, row, self._radial_values(lambda k: getattr(self, k)) if self.radial_law else None,
                     float(np.ravel(self.boxiness)[0]) if self.has_boxiness else 0.0,
                     list(zip(self.fourier_modes, amps, phases)),
                     self._spiral_values(lambda k: getattr(self, k)) if self.has_spiral else None)
             if self.pixel_mean:
-                arr += Sersic.general_mean_image(*args, shape=arr.shape, truncation=self.truncation_tuple())
+                arr += Sersic.general_mean_image(*args, shape=arr.shape, truncation=self.truncation_tuple(),
+                                                 bending=self.bending_list())
             else:
-                arr += Sersic.truncated_image(*args, truncation=self.truncation_tuple(), shape=arr.shape)
+                arr += Sersic.bent_image(*args, truncation=self.truncation_tuple(), bending=self.bending_list(),
+                                         shape=arr.shape)
             return arr
         if self.pixel_mean:
             amps, phases = self._fourier_values(lambda k: getattr(self, k)) if self.has_fourier else ((), ())
@@ -442,7 +520,7 @@ class Sersic(ComponentBase):
         return 4.0 / np.pi * np.exp(2.0 * gammaln(1.0 + 1.0 / e) - gammaln(1.0 + 2.0 / e))
 
     @staticmethod
-    def general_image(row, boxiness, shape):
+    def general_image(row, boxiness, shape, bending=None):
         """The profile with boxy / disky isophotes on a `shape` image, from a derived row (`derived_row`: the plain
         component's) and c = `boxiness`.  This numpy text is the DEFINITION the device kernels
         (csrc/psfmc_general.h) are held to.  With e = c + 2,
@@ -459,6 +537,8 @@ class Sersic(ComponentBase):
         dx, dy = xx - x0, yy - y0
         u = m00 * dx + m01 * dy
         v = m10 * dx + m11 * dy
+        if bending:                                   # (`bend`; None or empty: the step is left out)
+            v = Sersic.bend(row, u, v, bending)
         with np.errstate(all='ignore'):
             rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
             q = rho2 / (dx ** 2 + dy ** 2)
@@ -498,7 +578,7 @@ class Sersic(ComponentBase):
         return np.sum(w * (1.0 + Sersic._fourier_eps(c, s, modes)) ** -2) / np.sum(w)
 
     @staticmethod
-    def fourier_image(row, boxiness, modes, shape):
+    def fourier_image(row, boxiness, modes, shape, bending=None):
         """The profile with azimuthal Fourier modes on the isophote radius on a `shape` image, from a derived row
         (`derived_row`: the plain component's), c = `boxiness` (0.0 for a component without the keyword) and
         `modes`, a list of (m, a_m, phi_m) with m distinct integers in 1 ... 6 and phi_m in radians.  This numpy
@@ -519,6 +599,8 @@ class Sersic(ComponentBase):
         dx, dy = xx - x0, yy - y0
         u = m00 * dx + m01 * dy
         v = m10 * dx + m11 * dy
+        if bending:                                   # (`bend`; None or empty: the step is left out)
+            v = Sersic.bend(row, u, v, bending)
         with np.errstate(all='ignore'):
             r = np.hypot(u, v)
             eps = Sersic._fourier_eps(u / r, v / r, modes)
@@ -530,7 +612,7 @@ class Sersic(ComponentBase):
             return sb * np.exp(-kappa * np.expm1(L * p)) * (1 + g * (q / 12 * g))
 
     @staticmethod
-    def spiral_image(row, boxiness, modes, spiral, shape):
+    def spiral_image(row, boxiness, modes, spiral, shape, bending=None):
         """The profile with its coordinates wound into arms on a `shape` image, from a derived row (`derived_row`:
         the plain component's), c = `boxiness` (0.0 without the keyword), `modes` as for `fourier_image` (may be
         empty) and `spiral` = (r_in, r_out, winding, alpha, inclination, sky_angle), angles in radians.  This numpy
@@ -572,6 +654,8 @@ class Sersic(ComponentBase):
             Yr = -st * X + ct * Y
             u = m00 * Xr + m01 * Yr
             v = m10 * Xr + m11 * Yr
+            if bending:                               # (`bend`; None or empty: the step is left out)
+                v = Sersic.bend(row, u, v, bending)
             rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
             area = Sersic.superellipse_area_ratio(boxiness)
             if modes:
@@ -619,7 +703,7 @@ class Sersic(ComponentBase):
         raise ValueError('radial law {!r}: one of moffat, ferrer'.format(law))
 
     @staticmethod
-    def radial_image(law, row, pars, boxiness, modes, spiral, shape):
+    def radial_image(law, row, pars, boxiness, modes, spiral, shape, bending=None):
         """A component whose RADIAL LAW is not the Sersic law (`Moffat`, `Ferrer`; GALFIT's component types, not the
         reference's) on a `shape` image.  This numpy text is the DEFINITION the device kernels
         (csrc/psfmc_general.h) are held to.  `row` is the derived row of the component's Sersic slot (index 1, the
@@ -643,7 +727,7 @@ class Sersic(ComponentBase):
         law's NaN.  Support: `_radial_ok`."""
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
         sigma0 = Sersic.radial_central(law, row, pars, boxiness, modes, spiral)
-        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape)
+        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape, bending)
         with np.errstate(all='ignore'):
             if law == 'moffat':
                 beta = float(pars[0])
@@ -656,9 +740,11 @@ class Sersic(ComponentBase):
             return np.where(centre, sigma0, img)
 
     @staticmethod
-    def radial_rho2(row, boxiness, modes, spiral, shape):
+    def radial_rho2(row, boxiness, modes, spiral, shape, bending=None):
         """(rho^2, centre) of `radial_image` on a `shape` image: the squared generalised radius in units of the
-        semi-major radius (NaN or 0 where u = v = 0) and the mask of the pixels where u = v = 0."""
+        semi-major radius (NaN or 0 where u = v = 0) and the mask of the pixels where u = v = 0.  `bending` (a list of
+        (m, a_m); None or empty: absent, the bits of the function without the argument) bends v ahead of everything that
+        reads it (`bend`)."""
         x0, y0, m00, m01, m10, m11 = row[:6]
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
         e = float(boxiness) + 2.0
@@ -678,11 +764,53 @@ class Sersic(ComponentBase):
                 dx, dy = ct * X + st * Y, -st * X + ct * Y
             u = m00 * dx + m01 * dy
             v = m10 * dx + m11 * dy
+            if bending:
+                v = Sersic.bend(row, u, v, bending)
             rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
             if modes:
                 ruv = np.hypot(u, v)
                 rho2 = rho2 * (1.0 + Sersic._fourier_eps(u / ruv, v / ruv, modes)) ** 2
             return rho2, (u == 0) & (v == 0)
+
+    # -- bending modes (`bending=...`) -----------------------------------------------------------------------------
+    @staticmethod
+    def bend(row, u, v, bending):
+        """v' of a bent component.  This numpy text is the DEFINITION the device kernels (csrc/psfmc_general.h,
+        psfmc_general_mean.h) are held to.  `u`, `v`: the coordinates in units of the semi-major and semi-minor radius,
+        exactly as the parent forms them (after the spiral's winding where there is one); `bending`: a list of
+        (m, a_m) with m distinct integers in 1 ... 4.
+
+            r_a = 1 / hypot(m00, m01),  r_b = 1 / hypot(m10, m11)        the row's two radii in pixels
+            v'  = v + (r_a / r_b) sum_m a_m u^m
+
+        In pixels along (x = r_a u) and across (y = r_b v) the major axis: y' = y + r_a sum_m a_m (x / r_a)^m, GALFIT's
+        bending modes with r_scale = r_a and a_m in units of r_a; the ridge v' = 0 lies at y = -r_a sum_m a_m
+        (x / r_a)^m.  A shear: unit Jacobian, a bijection for every finite amplitude, and f(0) = 0 keeps the centre.
+        Everything downstream reads (u, v'): |u|^e + |v'|^e, the angle of the Fourier eps, the u = v = 0 centre mask,
+        rho of the laws and of the truncation ramps.  The Sersic law's centroid term keeps q = rho^2 / (dx^2 + dy^2)
+        in the pixel plane, as under the spiral.  Support: `_bending_ok`."""
+        todo = {int(m): float(a) for m, a in bending}
+        if len(todo) != len(list(bending)) or any(m not in Sersic.BEND_MODES for m in todo):
+            raise ValueError('bending modes are distinct integers in 1 ... 4')
+        ratio = (1.0 / np.hypot(row[2], row[3])) / (1.0 / np.hypot(row[4], row[5]))
+        f, um = np.zeros(np.shape(u)), u
+        for m in range(1, max(todo) + 1 if todo else 1):       # u^m by repeated multiplication (no pow)
+            if m > 1:
+                um = um * u
+            if m in todo:
+                f = f + todo[m] * um
+        return v + ratio * f
+
+    @staticmethod
+    def bent_image(law, row, pars, boxiness, modes, spiral, truncation, bending, shape):
+        """A general component with bending modes on a `shape` image: `truncated_image`'s value -- the Sersic law
+        times the reference's centroid term (`law` None; NaN where the centre is a pixel centre) or `radial_image`'s
+        law ('moffat' / 'ferrer'; Sigma_0 at u = v' = 0), times the truncation's factors where `truncation` is given --
+        with v' of `bend` in the place of v: rho^2 and the centre mask are `radial_rho2(..., bending)`'s, the centroid
+        term's q = rho^2 / (dx^2 + dy^2) stays in the pixel plane, and sb = Sigma_e / (A(c) Q cos(incl)), Sigma_0 and
+        `mag` are the parent's (unit Jacobian).  `bending` None or empty gives `truncated_image`'s bits; all-zero
+        amplitudes give its values."""
+        return Sersic.truncated_image(law, row, pars, boxiness, modes, spiral, truncation, shape, bending)
 
     # -- truncation (`truncation=...`) ----------------------------------------------------------------------------
     @staticmethod
@@ -724,7 +852,7 @@ class Sersic(ComponentBase):
         return value
 
     @staticmethod
-    def truncated_image(law, row, pars, boxiness, modes, spiral, truncation, shape):
+    def truncated_image(law, row, pars, boxiness, modes, spiral, truncation, shape, bending=None):
         """A general component with an inner and / or outer truncation on a `shape` image: its PARENT VALUE -- what
         the component renders without the keyword: `general_image`, `fourier_image` or `spiral_image` for the Sersic
         law (`law` None; the law times the reference's centroid term, NaN where the centre is a pixel centre),
@@ -734,17 +862,18 @@ class Sersic(ComponentBase):
         (`truncation_flux_fraction`).  No refinement is added at the truncation radii: the ramps are soft by
         construction (`pixel_mean=True`, `general_mean_image`, averages the product over each pixel)."""
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
+        bending = bending or None                     # (`bend`: the parent and its radius with v' in the place of v)
         if law is not None:
-            parent = Sersic.radial_image(law, row, pars, boxiness, modes, spiral, shape)
+            parent = Sersic.radial_image(law, row, pars, boxiness, modes, spiral, shape, bending)
         elif spiral is not None:
-            parent = Sersic.spiral_image(row, boxiness, modes, spiral, shape)
+            parent = Sersic.spiral_image(row, boxiness, modes, spiral, shape, bending)
         elif modes:
-            parent = Sersic.fourier_image(row, boxiness, modes, shape)
+            parent = Sersic.fourier_image(row, boxiness, modes, shape, bending)
         else:
-            parent = Sersic.general_image(row, boxiness, shape)
+            parent = Sersic.general_image(row, boxiness, shape, bending)
         if truncation is None:
             return parent
-        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape)
+        rho2, centre = Sersic.radial_rho2(row, boxiness, modes, spiral, shape, bending)
         with np.errstate(all='ignore'):
             return Sersic._truncate(parent, row, rho2, centre, truncation)
 
@@ -884,7 +1013,7 @@ class Sersic(ComponentBase):
 
     # -- the pixel-averaged mode of the general components (`pixel_mean=True`) ------------------------------------
     @staticmethod
-    def _general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation=None):
+    def _general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation=None, bending=None):
         """(`general_point`'s value, Ferrer's x = rho^(2 - beta) with 0 at u = v = 0 -- None for the other laws)."""
         trunc = lambda val: Sersic._truncate(val, row, rho2, centre, truncation)
         x0, y0, m00, m01, m10, m11, kappa, p, sbeff = row
@@ -908,6 +1037,8 @@ class Sersic(ComponentBase):
                 dx, dy = ct * X + st * Y, -st * X + ct * Y
             u = m00 * dx + m01 * dy
             v = m10 * dx + m11 * dy
+            if bending:
+                v = Sersic.bend(row, u, v, bending)
             rho2 = (np.abs(u) ** e + np.abs(v) ** e) ** (2.0 / e)
             if modes:
                 ruv = np.hypot(u, v)
@@ -929,7 +1060,7 @@ class Sersic(ComponentBase):
             return trunc(np.where(xk < 1.0, sigma0 * np.abs(1.0 - xk) ** alpha, 0.0)), xk
 
     @staticmethod
-    def general_point(law, row, pars, boxiness, modes, spiral, x, y, truncation=None):
+    def general_point(law, row, pars, boxiness, modes, spiral, x, y, truncation=None, bending=None):
         """The law of a general component at ARBITRARY POINTS (x, y) (arrays of one shape, pixel coordinates): what
         `general_mean_image` averages.  `law` is None (the Sersic law), 'moffat' or 'ferrer'; `row`, `pars`
         (ignored for None), `boxiness`, `modes` and `spiral` as for `radial_image`.  The coordinate chain is
@@ -942,11 +1073,13 @@ class Sersic(ComponentBase):
         There is NO centroid term: the reference's is a correction for sampling the law at the pixel centre, and this
         is the law itself.  Where u = v = 0 the value is the finite peak, sb e^kappa or Sigma_0.  `truncation` (as for
         `truncation_weight`; None: absent, the bits of the function without the argument) multiplies the value by the
-        inner and outer factors at the point, the peak by the factors at s = 0."""
-        return Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation)[0]
+        inner and outer factors at the point, the peak by the factors at s = 0.  `bending` (a list of (m, a_m); None or
+        empty: absent, the bits of the function without the argument) bends v ahead of everything that reads it
+        (`bend`)."""
+        return Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation, bending)[0]
 
     @staticmethod
-    def general_mean_image(law, row, pars, boxiness, modes, spiral, shape, truncation=None):
+    def general_mean_image(law, row, pars, boxiness, modes, spiral, shape, truncation=None, bending=None):
         """A general component rendered as the MEAN OF ITS LAW OVER EACH PIXEL on a `shape` image (`pixel_mean=True`;
         not the reference's).  This numpy text is the DEFINITION the device kernels (csrc/psfmc_general_mean.h) are
         held to.  With g = `general_point` and the constants INTEG_* of `integrated_image`:
@@ -966,11 +1099,13 @@ class Sersic(ComponentBase):
         Parts 3 and 4 overwrite parts 1 and 2.  `mag` stays the total magnitude through the closed-form factors of
         `general_image`, `fourier_image`, `spiral_image` and `radial_image`.  With `truncation` every sample is
         `general_point(..., truncation)`, the product of the law and the truncation's factors: the scheme is applied
-        to the product unchanged, and no refinement is added at the truncation radii (the ramps are soft)."""
+        to the product unchanged, and no refinement is added at the truncation radii (the ramps are soft).  With
+        `bending` every sample is the bent law's (`general_point(..., bending)`); the scheme, its box around the centre
+        (which the bending leaves in place) and Ferrer's edge pixels are unchanged, and none is added along the ridge."""
         ny, nx = shape
         x0, y0 = row[0], row[1]
         modes = [(int(m), float(a), float(phi)) for m, a, phi in modes]
-        point = lambda x, y: Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation)
+        point = lambda x, y: Sersic._general_point_x(law, row, pars, boxiness, modes, spiral, x, y, truncation, bending)
         yy, xx = np.mgrid[0:ny, 0:nx].astype(np.float64)
         cyy, cxx = np.mgrid[0:ny + 1, 0:nx + 1].astype(np.float64) - 0.5
         mid, mid_x = point(xx, yy)

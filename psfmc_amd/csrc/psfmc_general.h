@@ -64,6 +64,19 @@
 // tpar[w][k][kTruPar] are formed by the TRU instantiation of k_general_split.  Such a context runs ONE further
 // instantiation of each of the two kernels (every flag set; the byte is a wave-uniform branch); contexts without
 // truncations run the kernels they ran.  `mag` stays the magnitude of the UNTRUNCATED component.
+//
+// BENDING MODES (`Sersic / Moffat / Ferrer(..., bending={m: a_m})`, m = 1 ... 4, GALFIT's bending modes; definition:
+// Sersic.py `Sersic.bend`): with (u, v) formed as ever (after the winding), r_a = 1 / hypot(m00, m01) and r_b =
+// 1 / hypot(m10, m11),
+//     v' = v + (r_a / r_b) sum_m a_m u^m
+// and everything downstream -- |u|^e + |v'|^e, the angle of eps, the centre, rho of the laws and of the truncation --
+// reads (u, v').  A shear with unit Jacobian and f(0) = 0: `mag`, A(c), Q, cos(incl), Sigma_0 and the centre stay.
+// psfmc_set_bending_layout appends kBndIn entries per Sersic -- a_1 ... a_4 -- BEHIND the truncations' entries.  A
+// context with bending ALWAYS carries the four blocks before it: a walker's auxiliary vector then has 2 n_sky +
+// 29 n_sersic doubles.  A per (field, Sersic) byte holds the modes (bit m - 1).  The per-walker constants
+// bpar[w][k][kBndPar] = a_m r_a / r_b are formed by the BND instantiation of k_general_split.  Such a context runs ONE
+// further instantiation of each kernel (every flag set; the byte is a wave-uniform branch); contexts without bending
+// run the kernels they ran.
 #pragma once
 #include "psfmc_device.h"
 #include "psfmc_integrated.h"
@@ -101,6 +114,13 @@ constexpr int kTruInner = 1, kTruOuter = 2;
 // the truncations' entries behind the laws': aux[base + fourier_len + spiral_len + radial_len + kTruIn k + j]
 __host__ __device__ inline int trunc_len(int n_sersic) { return kTruIn * n_sersic; }
 
+constexpr int kBndModes = 4;         // modes 1 ... 4 (PSFMC_BEND_MODES)
+constexpr int kBndIn = kBndModes;    // a_1 ... a_4
+constexpr int kBndPar = kBndModes;   // a_m r_a / r_b; zeros for an absent mode
+constexpr int kBndModeBits = (1 << kBndModes) - 1;
+// the bending entries behind the truncations': aux[base + fourier_len + ... + trunc_len + kBndIn k + (m - 1)]
+__host__ __device__ inline int bend_len(int n_sersic) { return kBndIn * n_sersic; }
+
 // skip: the context's own flags (writable) or nullptr (row-based calls without flags: a bad boxiness then makes the
 // component, and with it the walker's likelihood, NaN)
 // SPI: the context has spirals (spar, smasks set, aux_spi the offset of the spiral entries in a walker's vector); the
@@ -120,14 +140,20 @@ __host__ __device__ inline int trunc_len(int n_sersic) { return kTruIn * n_sersi
 // 1 / hypot(m00, m01) the slot's semi-major radius in pixels (zeros for an absent side), and 1 / e.  Outside the
 // support of a side present (a value not finite, lo < 0, hi <= lo) Sigma becomes NaN and the walker is skipped like a
 // bad boxiness.  The TRU = false instantiations are the kernels as they were.
-template <bool SPI, bool LAW = false, bool TRU = false>
+// BND: the context has bending modes (bpar, bmasks set, aux_bnd the offset of their entries); the thread of a slot with
+// a mode stores a_m r_a / r_b per mode present (zeros for an absent one), r_a = 1 / hypot(m00, m01), r_b =
+// 1 / hypot(m10, m11).  An amplitude of a mode present that is not finite makes Sigma NaN and the walker is skipped
+// like a bad boxiness.  The BND = false instantiations are the kernels as they were.
+template <bool SPI, bool LAW = false, bool TRU = false, bool BND = false>
 __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __restrict__ skip,
                                 double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
                                 const uint8_t* __restrict__ flags, int n_ps, int n_sersic, int n_psf, int n_psf_field,
                                 int n, double* __restrict__ spar, const uint8_t* __restrict__ smasks, int aux_spi,
                                 double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr,
                                 int aux_rad = 0, double* __restrict__ tpar = nullptr,
-                                const uint8_t* __restrict__ tmasks = nullptr, int aux_tru = 0) {
+                                const uint8_t* __restrict__ tmasks = nullptr, int aux_tru = 0,
+                                double* __restrict__ bpar = nullptr, const uint8_t* __restrict__ bmasks = nullptr,
+                                int aux_bnd = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * n_sersic) return;
     const int w = i / n_sersic, k = i - w * n_sersic;
@@ -218,6 +244,20 @@ __global__ void k_general_split(double* __restrict__ prep, int plen, uint8_t* __
             }
             tp[4] = 1.0 / e;
             tp[5] = 0.0;
+        }
+    }
+    if constexpr (BND) {
+        const int bm = bmasks[(idx / n_psf_field) * n_sersic + k];
+        if (bm) {
+            const double* a = aux + (size_t)w * aux_stride + aux_bnd + kBndIn * k;
+            const double r_a = 1.0 / hypot(b[2], b[3]), r_b = 1.0 / hypot(b[4], b[5]);
+            const double ratio = r_a / r_b;
+            double* bp = bpar + (size_t)i * kBndPar;
+            for (int m = 0; m < kBndModes; ++m) {
+                const bool on = (bm >> m) & 1;
+                if (on) bad = bad || !(fabs(a[m]) < INFINITY);                 // (true for a NaN)
+                bp[m] = on ? a[m] * ratio : 0.0;
+            }
         }
     }
     for (int j = 0; j < kPrepSersic - 1; ++j) o[j] = b[j];
@@ -427,10 +467,30 @@ __device__ __forceinline__ double trunc_apply(const TruPar& T, double val, doubl
     return val;
 }
 
-template <bool FOURIER, bool SPIRAL = false, bool LAW = false, bool TRU = false>
+// BND: the component is bent (file header; `Sersic.bend`): v' = v + u (b_1 + u (b_2 + u (b_3 + u b_4))) by Horner from
+// the highest mode present (`top`, wave-uniform, as FouPar::top), b_m = a_m r_a / r_b: top multiply-adds between
+// forming (u, v) and |u|^e + |v|^e.  The BND = false forms are the functions as they were.
+// (A NaN among the constants of the modes up to `top` makes v' NaN and so joins general_pixel's chk through u + v'.)
+struct BndPar { double b[kBndModes]; int top; };
+__device__ __forceinline__ BndPar load_bend(const double* __restrict__ bp, int modes) {
+    BndPar B;
+#pragma unroll
+    for (int m = 0; m < kBndModes; ++m) B.b[m] = bp[m];
+    B.top = 32 - __builtin_clz((unsigned)modes);                       // the highest mode present
+    return B;
+}
+__device__ __forceinline__ double bend_apply(const BndPar& B, double u, double v) {
+    double f = 0.0;
+#pragma unroll
+    for (int m = kBndModes - 1; m >= 0; --m)
+        if (m < B.top) f = __builtin_fma(f, u, B.b[m]);                // wave-uniform
+    return __builtin_fma(f, u, v);
+}
+
+template <bool FOURIER, bool SPIRAL = false, bool LAW = false, bool TRU = false, bool BND = false>
 __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F, double x, double y,
                                                 const SpiPar* SP = nullptr, const RadPar* RP = nullptr,
-                                                const TruPar* TP = nullptr) {
+                                                const TruPar* TP = nullptr, const BndPar* BP = nullptr) {
     const double dx = x - G.s.x0, dy = y - G.s.y0;
     double u, v, spi_chk = 0.0;
     if constexpr (SPIRAL) {
@@ -455,6 +515,7 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
         u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
         v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
     }
+    if constexpr (BND) v = bend_apply(*BP, u, v);
     const double au = fabs(u), av = fabs(v);
     // |u| = 0 gives the term exactly 0 (not log2(0) e)
     const double pu = au > 0.0 ? fast_exp2(G.e * fast_log2(au)) : 0.0;
@@ -525,7 +586,9 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
 // both blocks); a slot of kind != 0 runs the LAW pixel function, with or without modes and spiral.
 // TRU: the context has truncations (tpar, tmasks set; instantiated with every other flag set only, such a context
 // carries every block); a slot with a side runs the TRU pixel function of its law, with or without modes and spiral.
-template <bool FOU, bool SPI = false, bool LAW = false, bool TRU = false>
+// BND: the context has bending modes (bpar, bmasks set; instantiated with every other flag set only); a slot with a
+// mode runs the BND pixel function of its law, with or without modes, spiral and truncation.
+template <bool FOU, bool SPI = false, bool LAW = false, bool TRU = false, bool BND = false>
 __global__ void __launch_bounds__(256)
 k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                const double* __restrict__ gpar, const double* __restrict__ aux, int aux_stride, int n_sky,
@@ -534,7 +597,8 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
                int add, const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                const double* __restrict__ spar = nullptr, const uint8_t* __restrict__ smasks = nullptr,
                const double* __restrict__ rpar = nullptr, const uint8_t* __restrict__ rkinds = nullptr,
-               const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
+               const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr,
+               const double* __restrict__ bpar = nullptr, const uint8_t* __restrict__ bmasks = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -581,7 +645,40 @@ k_general_rows(const double* __restrict__ prep, int plen, const uint8_t* __restr
         }
         const int kind = LAW ? rkinds[field * n_sersic + k] : 0;                         // wave-uniform
         const int sides = TRU ? tmasks[field * n_sersic + k] : 0;                        // wave-uniform
-        if (TRU && sides) {
+        const int bends = BND ? bmasks[field * n_sersic + k] & kBndModeBits : 0;         // wave-uniform
+        if (BND && bends) {
+            const BndPar B = load_bend(bpar + ((size_t)w * n_sersic + k) * kBndPar, bends);
+            TruPar T{};
+            RadPar R{};
+            SpiPar S{};
+            if (sides) T = load_trunc(tpar + ((size_t)w * n_sersic + k) * kTruPar, sides);
+            if (kind) R = load_radial(rpar + ((size_t)w * n_sersic + k) * kRadPar);
+            if (wound) S = load_spiral(spar + ((size_t)w * n_sersic + k) * kSpiPar);
+            auto pass = [&](auto fou, auto spi, auto law, auto tru) {
+                for (int x0 = 0; x0 < xn; x0 += 64) {
+                    const int ix = x0 + lane;
+                    if (ix < xn)
+                        out[ix] = (first ? base(ix) : out[ix]) +
+                                  general_pixel<decltype(fou)::value, decltype(spi)::value, decltype(law)::value,
+                                                decltype(tru)::value, true>(G, F, (double)ix, y, &S, &R, &T, &B);
+                }
+            };
+            auto by_tru = [&](auto fou, auto spi, auto law) {
+                if (sides) pass(fou, spi, law, std::true_type{});
+                else pass(fou, spi, law, std::false_type{});
+            };
+            auto by_law = [&](auto fou, auto spi) {
+                if (kind) by_tru(fou, spi, std::true_type{});
+                else by_tru(fou, spi, std::false_type{});
+            };
+            if (wound) {
+                if (modes) by_law(std::true_type{}, std::true_type{});
+                else by_law(std::false_type{}, std::true_type{});
+            } else {
+                if (modes) by_law(std::true_type{}, std::false_type{});
+                else by_law(std::false_type{}, std::false_type{});
+            }
+        } else if (TRU && sides) {
             const TruPar T = load_trunc(tpar + ((size_t)w * n_sersic + k) * kTruPar, sides);
             RadPar R{};
             SpiPar S{};

@@ -24,7 +24,9 @@
 // one instantiation serves every context without truncations, and the instantiations of psfmc_general.h are the text
 // they were.  TRU: a context with truncations runs the second instantiation of the two kernels, whose g is
 // `general_point * inner * outer` (the sides a wave-uniform runtime branch): every scheme below averages the product.
-// The TRU = false instantiations are the kernels as they were, with their registers and occupancy.
+// The TRU = false instantiations are the kernels as they were, with their registers and occupancy.  BND: a context with
+// bending modes runs a third instantiation (TRU and BND set), whose g bends v ahead of |u|^e + |v|^e (the modes a
+// wave-uniform runtime branch); the BND = false instantiations are the kernels as they were.
 // The work per walker and component is fixed but for the Ferrer edge pixels, which depend on that walker's parameters
 // alone; every pixel is written by one lane in one fixed summation order (the xor butterfly of integ_wave_sum), there
 // are no atomics and no exchange through LDS: a walker's bits do not depend on its batch.
@@ -38,14 +40,15 @@ constexpr int kMeanChunk = 63;       // pixels of a row per pass of k_general_me
 static_assert(kMeanEdgeGrid * kMeanEdgeGrid == 64, "the 64 lanes of a wave are the samples of a Ferrer edge pixel");
 
 // a component's constants as the kernels of psfmc_general.h left them; F.top == 0: no modes; kind 0: the Sersic law;
-// T.sides == 0: not truncated
-struct MeanPar { GenPar G; FouPar F; SpiPar S; RadPar R; TruPar T; bool wound; int kind; };
+// T.sides == 0: not truncated; B.top == 0: not bent
+struct MeanPar { GenPar G; FouPar F; SpiPar S; RadPar R; TruPar T; BndPar B; bool wound; int kind; };
 __device__ __forceinline__ MeanPar load_mean(const double* __restrict__ gpar, const double* __restrict__ fpar,
                                              const uint8_t* __restrict__ fmasks, const double* __restrict__ spar,
                                              const uint8_t* __restrict__ smasks, const double* __restrict__ rpar,
                                              const uint8_t* __restrict__ rkinds, const double* __restrict__ tpar,
                                              const uint8_t* __restrict__ tmasks, int w, int k, int field,
-                                             int n_sersic) {
+                                             int n_sersic, const double* __restrict__ bpar = nullptr,
+                                             const uint8_t* __restrict__ bmasks = nullptr) {
     MeanPar M{};
     const size_t i = (size_t)w * n_sersic + k;
     M.G = load_general(gpar + i * kGenPar);
@@ -65,11 +68,13 @@ __device__ __forceinline__ MeanPar load_mean(const double* __restrict__ gpar, co
     if (M.kind) M.R = load_radial(rpar + i * kRadPar);
     const int sides = tmasks ? tmasks[field * n_sersic + k] : 0;                            // wave-uniform (TRU only)
     if (sides) M.T = load_trunc(tpar + i * kTruPar, sides);
+    const int bends = bmasks ? bmasks[field * n_sersic + k] & kBndModeBits : 0;             // wave-uniform (BND only)
+    if (bends) M.B = load_bend(bpar + i * kBndPar, bends);
     return M;
 }
 
 // g at the point (x, y); *inside: Ferrer's x < 1 (true at u = v = 0), true for the other laws
-template <bool TRU = false>
+template <bool TRU = false, bool BND = false>
 __device__ __forceinline__ double general_point(const MeanPar& M, double x, double y, bool* inside) {
     const GenPar& G = M.G;
     const double dx = x - G.s.x0, dy = y - G.s.y0;
@@ -94,6 +99,9 @@ __device__ __forceinline__ double general_point(const MeanPar& M, double x, doub
     } else {
         u = __builtin_fma(G.s.m00, dx, G.s.m01 * dy);
         v = __builtin_fma(G.s.m10, dx, G.s.m11 * dy);
+    }
+    if constexpr (BND) {
+        if (M.B.top > 0) v = bend_apply(M.B, u, v);                    // wave-uniform
     }
     const double au = fabs(u), av = fabs(v);
     // |u| = 0 gives the term exactly 0 (not log2(0) e)
@@ -150,8 +158,9 @@ __device__ __forceinline__ MeanBox mean_box(const SersicPar& s) {
 
 // parts 1 and 2; grid (ceil(ny / 4), n), 4 waves = 4 rows per workgroup.  Behind k_general_rows, which wrote or added
 // to every pixel of the row: this kernel ADDS.  mflags [n_fields][n_sersic]; fpar / fmasks, spar / smasks, rpar / rkinds
-// are nullptr in a context without modes, spirals or laws, tpar / tmasks in one without truncations.
-template <bool TRU = false>
+// are nullptr in a context without modes, spirals or laws, tpar / tmasks in one without truncations, bpar / bmasks in
+// one without bending modes.
+template <bool TRU = false, bool BND = false>
 __global__ void __launch_bounds__(256)
 k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                     const double* __restrict__ gpar, const uint8_t* __restrict__ mflags, int n_sersic, int n_psf,
@@ -159,7 +168,8 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
                     const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                     const double* __restrict__ spar, const uint8_t* __restrict__ smasks,
                     const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds,
-                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
+                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr,
+                    const double* __restrict__ bpar = nullptr, const uint8_t* __restrict__ bmasks = nullptr) {
     const int w = blockIdx.y;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x & 63;
@@ -175,7 +185,7 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
     for (int k = 0; k < n_sersic; ++k) {
         if (!fl[k]) continue;                                          // wave-uniform
         const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, tpar, tmasks, w, k, field,
-                                      n_sersic);
+                                      n_sersic, BND ? bpar : nullptr, BND ? bmasks : nullptr);
         const MeanBox box = mean_box(M.G.s);
         const bool row_boxed = box.any && abs(iy - box.py) <= kIntegHalfBox;
         // (every lane runs every chunk to its end, lane 63 and the ones beyond the row's last pixel included: they
@@ -184,9 +194,9 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
             const int ix = x0 + lane;
             const double x = (double)ix;
             bool ic, itl, ibl, itr, ibr;
-            const double c = general_point<TRU>(M, x, y, &ic);
-            const double tl = general_point<TRU>(M, x - 0.5, y - 0.5, &itl);
-            const double bl = general_point<TRU>(M, x - 0.5, y + 0.5, &ibl);
+            const double c = general_point<TRU, BND>(M, x, y, &ic);
+            const double tl = general_point<TRU, BND>(M, x - 0.5, y - 0.5, &itl);
+            const double bl = general_point<TRU, BND>(M, x - 0.5, y + 0.5, &ibl);
             const double tr = __shfl_down(tl, 1, 64), br = __shfl_down(bl, 1, 64);
             itr = __shfl_down((int)itl, 1, 64) != 0;
             ibr = __shfl_down((int)ibl, 1, 64) != 0;
@@ -203,7 +213,7 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
                     const int bit = __ffsll((long long)edge) - 1;
                     edge &= edge - 1;
                     bool unused;
-                    const double v = general_point<TRU>(M, (double)(x0 + bit) + ox, y + oy, &unused);
+                    const double v = general_point<TRU, BND>(M, (double)(x0 + bit) + ox, y + oy, &unused);
                     const double mean = integ_wave_sum(v) / (double)(kMeanEdgeGrid * kMeanEdgeGrid);
                     if (lane == bit) val = mean;
                 }
@@ -214,7 +224,7 @@ k_general_mean_rows(const double* __restrict__ prep, int plen, const uint8_t* __
 }
 
 // parts 3 and 4; grid (n), one wave per walker, its mean components one after the other (k_integ_core with g)
-template <bool TRU = false>
+template <bool TRU = false, bool BND = false>
 __global__ void __launch_bounds__(64)
 k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __restrict__ skip,
                     const double* __restrict__ gpar, const uint8_t* __restrict__ mflags, int n_sersic, int n_psf,
@@ -222,7 +232,8 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
                     const double* __restrict__ fpar, const uint8_t* __restrict__ fmasks,
                     const double* __restrict__ spar, const uint8_t* __restrict__ smasks,
                     const double* __restrict__ rpar, const uint8_t* __restrict__ rkinds,
-                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr) {
+                    const double* __restrict__ tpar = nullptr, const uint8_t* __restrict__ tmasks = nullptr,
+                    const double* __restrict__ bpar = nullptr, const uint8_t* __restrict__ bmasks = nullptr) {
     const int w = blockIdx.x;
     if (skip && skip[w]) return;
     const int lane = threadIdx.x;
@@ -237,7 +248,7 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
     for (int k = 0; k < n_sersic; ++k) {
         if (!fl[k]) continue;                                          // wave-uniform
         const MeanPar M = load_mean(gpar, fpar, fmasks, spar, smasks, rpar, rkinds, tpar, tmasks, w, k, field,
-                                      n_sersic);
+                                      n_sersic, BND ? bpar : nullptr, BND ? bmasks : nullptr);
         const double gx = M.G.s.x0 + 0.5, gy = M.G.s.y0 + 0.5;
         if (!(fabs(gx) <= kIntegMaxCentre && fabs(gy) <= kIntegMaxCentre)) continue;   // (NaN too)
         const double fx = floor(gx), fy = floor(gy);
@@ -256,7 +267,7 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
                 const int a = lane % g, b = lane / g;
                 const double sx = (double)X + (((double)a + 0.5) / (double)g - 0.5);
                 const double sy = (double)Y + (((double)b + 0.5) / (double)g - 0.5);
-                const double pv = general_point<TRU>(M, sx, sy, &unused);
+                const double pv = general_point<TRU, BND>(M, sx, sy, &unused);
                 const double v = lane < g * g ? pv : 0.0;
                 const double mean = integ_wave_sum(v) / (double)(g * g);
                 if (lane == 0) out[(size_t)Y * nx + X] += mean;
@@ -288,7 +299,7 @@ k_general_mean_core(const double* __restrict__ prep, int plen, const uint8_t* __
                 double sum = 0.0;
 #pragma unroll 1
                 for (int sx = 0; sx < kIntegSub; ++sx)
-                    sum += general_point<TRU>(M, bx + (((double)sx + 0.5) / (double)kIntegSub) * cw, sy, &unused);
+                    sum += general_point<TRU, BND>(M, bx + (((double)sx + 0.5) / (double)kIntegSub) * cw, sy, &unused);
                 const double part = deferred ? 0.0 : sum * (cw * cw * (1.0 / (kIntegSub * kIntegSub)));
                 const int dx = (int)(floor(cx / scale) - fx) + 1, dy = (int)(floor(cy / scale) - fy) + 1;   // its pixel
                 const int pix = (dy & 1) * 2 + (dx & 1);

@@ -280,8 +280,8 @@ struct psfmc_ctx {
     // nothing is allocated and no kernel changes until a field registers an aux layout with a flag set
     bool gen_any = false;
     // doubles per walker of d_aux, the same for every field: the longest table a field of the context ever had
-    // (apply_aux_record; 2 n_sky + n_sersic, + 12 / 18 / 20 / 24 n_sersic from the first modes / spiral / law /
-    // truncation on)
+    // (apply_aux_record; 2 n_sky + n_sersic, + 12 / 18 / 20 / 24 / 28 n_sersic from the first modes / spiral / law /
+    // truncation / bending on)
     int aux_stride = 0, aux_n_sky = 0;
     std::vector<uint8_t> gen_flags;      // [n_fields][n_sersic] general components, then [n_fields][n_sky] tilted skies
     uint8_t* d_gen_flags = nullptr;
@@ -294,11 +294,11 @@ struct psfmc_ctx {
     int aux_rows_w = -1;                 // walkers whose aux rows psfmc_set_aux_rows left in d_aux for the next row-based call
     int aux_base = 0;                    // 2 n_sky + n_sersic: the entries of psfmc_set_aux_layout, in front of the blocks
     // [kAuxBlocks] the blocks behind them, in table order (psfmc_aux_table.h kAuxBlock: Fourier modes, spiral arms,
-    // radial laws, truncations; psfmc_set_<name>_layout, psfmc_general.h).  Nothing is allocated and no kernel changes
+    // radial laws, truncations, bending modes; psfmc_set_<name>_layout, psfmc_general.h).  Nothing is allocated and no kernel changes
     // until a field registers a block.  The first registration of block b allocates the masks and per-walker
-    // constants, all clear, of blocks kAuxBlock[b].first ... b -- a law or a truncation those of every block before
-    // it, a spiral only its own -- and aux_stride grows to the end of block b in a walker's vector (aux_base + 12 /
-    // 18 / 20 / 24 n_sersic): a block's entries sit behind those of every block before it, zeros or padding where no
+    // constants, all clear, of blocks kAuxBlock[b].first ... b -- a law, a truncation or bending those of every block
+    // before it, a spiral only its own -- and aux_stride grows to the end of block b in a walker's vector (aux_base +
+    // 12 / 18 / 20 / 24 / 28 n_sersic): a block's entries sit behind those of every block before it, zeros or padding where no
     // field has them.  `any` follows the fields' registrations; general_launch reads what a launch carries from it.
     struct AuxBlockState {
         bool any = false;                // some field has the block registered now
@@ -1754,10 +1754,10 @@ __global__ void __launch_bounds__(256) k_pow_tables(double* __restrict__ prep, c
 // formed and the components' blocks made neutral for the rasterisers.  The integrated profile's kernels WRITE the
 // images, the general kernel then ADDS to them; alone it writes.
 // What a launch of the general kernels carries is decided ONCE, here, from the blocks' any-bits and the facts table:
-// block j is carried when some block b with `any` set has kAuxBlock[b].first <= j <= b.  So laws and truncations
+// block j is carried when some block b with `any` set has kAuxBlock[b].first <= j <= b.  So laws, truncations and bending
 // bring the masks and constants of every block before them, a context with only spirals does not carry the Fourier
 // buffers, and a context without modes and without spirals runs the kernels it always ran.
-enum GenLevel { GEN_PLAIN = 0, GEN_FOU = 1, GEN_SPI = 2, GEN_FOU_SPI = 3, GEN_RAD, GEN_TRU };
+enum GenLevel { GEN_PLAIN = 0, GEN_FOU = 1, GEN_SPI = 2, GEN_FOU_SPI = 3, GEN_RAD, GEN_TRU, GEN_BND };
 struct GenLaunch {
     double* par[kAuxBlocks];             // the block's per-walker constants from walker w_off on; nullptr: not carried
     const uint8_t* masks[kAuxBlocks];    // its mask bytes, or nullptr
@@ -1777,12 +1777,13 @@ static GenLaunch general_launch(const psfmc_ctx* c, int w_off) {
             g.masks[j] = c->blk[j].d_masks;
         }
     }
-    g.level = last == kBlkTru ? GEN_TRU : last == kBlkRad ? GEN_RAD
+    g.level = last == kBlkBnd ? GEN_BND : last == kBlkTru ? GEN_TRU : last == kBlkRad ? GEN_RAD
             : GenLevel((c->blk[kBlkFou].any ? GEN_FOU : 0) | (c->blk[kBlkSpi].any ? GEN_SPI : 0));
     return g;
 }
 static decltype(&k_general_rows<false, false>) general_rows_kernel(GenLevel level) {
     switch (level) {
+        case GEN_BND: return k_general_rows<true, true, true, true, true>;
         case GEN_TRU: return k_general_rows<true, true, true, true>;
         case GEN_RAD: return k_general_rows<true, true, true>;
         case GEN_FOU_SPI: return k_general_rows<true, true>;
@@ -1793,6 +1794,7 @@ static decltype(&k_general_rows<false, false>) general_rows_kernel(GenLevel leve
 }
 static decltype(&k_general_split<false, false>) general_split_kernel(GenLevel level) {
     switch (level) {
+        case GEN_BND: return k_general_split<true, true, true, true>;
         case GEN_TRU: return k_general_split<true, true, true>;
         case GEN_RAD: return k_general_split<true, true>;
         case GEN_FOU_SPI: case GEN_SPI: return k_general_split<true, false>;
@@ -1812,7 +1814,7 @@ static void launch_general_rows(psfmc_ctx* c, const GenLaunch& g, int n, int w_o
                        c->d_gen_flags + (size_t)c->n_fields * c->n_sersic, rows_flags, c->n_sersic, c->n_psf,
                        c->n_psf_field, c->d_wrap, c->ny, c->nx, c->d_extra_img + (size_t)w_off * c->S, add,
                        g.par[kBlkFou], g.masks[kBlkFou], g.par[kBlkSpi], g.masks[kBlkSpi], g.par[kBlkRad],
-                       g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru]);
+                       g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru], g.par[kBlkBnd], g.masks[kBlkBnd]);
 }
 
 // the mean components of a context that has some (psfmc_general_mean.h): behind k_general_rows, which left them out
@@ -1821,16 +1823,21 @@ static void launch_general_mean(psfmc_ctx* c, const GenLaunch& g, int n, int w_o
     const double* prep = c->d_prep + (size_t)w_off * c->plen;
     double* img = c->d_extra_img + (size_t)w_off * c->S;
     const double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
-    const bool tru = g.level == GEN_TRU;
-    hipLaunchKernelGGL(tru ? k_general_mean_rows<true> : k_general_mean_rows<false>, dim3((c->ny + 3) / 4, n),
+    const bool tru = g.level == GEN_TRU, bnd = g.level == GEN_BND;
+    const auto rows_kernel = bnd ? k_general_mean_rows<true, true>
+                           : tru ? k_general_mean_rows<true, false> : k_general_mean_rows<false, false>;
+    const auto core_kernel = bnd ? k_general_mean_core<true, true>
+                           : tru ? k_general_mean_core<true, false> : k_general_mean_core<false, false>;
+    hipLaunchKernelGGL(rows_kernel, dim3((c->ny + 3) / 4, n),
                        dim3(256), 0, st, prep, c->plen, skip, gpar, c->d_mean_flags, c->n_sersic, c->n_psf,
                        c->n_psf_field, c->d_wrap, c->ny, c->nx, img, g.par[kBlkFou], g.masks[kBlkFou],
                        g.par[kBlkSpi], g.masks[kBlkSpi], g.par[kBlkRad], g.masks[kBlkRad], g.par[kBlkTru],
-                       g.masks[kBlkTru]);
-    hipLaunchKernelGGL(tru ? k_general_mean_core<true> : k_general_mean_core<false>, dim3(n), dim3(64), 0, st, prep,
+                       g.masks[kBlkTru], g.par[kBlkBnd], g.masks[kBlkBnd]);
+    hipLaunchKernelGGL(core_kernel, dim3(n), dim3(64), 0, st, prep,
                        c->plen, skip, gpar, c->d_mean_flags, c->n_sersic, c->n_psf, c->n_psf_field, c->d_wrap, c->ny,
                        c->nx, img, g.par[kBlkFou], g.masks[kBlkFou], g.par[kBlkSpi], g.masks[kBlkSpi],
-                       g.par[kBlkRad], g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru]);
+                       g.par[kBlkRad], g.masks[kBlkRad], g.par[kBlkTru], g.masks[kBlkTru], g.par[kBlkBnd],
+                       g.masks[kBlkBnd]);
 }
 
 static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* skip, hipStream_t st) {
@@ -1844,13 +1851,15 @@ static void launch_extra_images(psfmc_ctx* c, int n, int w_off, const uint8_t* s
                                                                                            : nullptr;
         double* gpar = c->d_gen_par + (size_t)w_off * c->n_sersic * kGenPar;
         const double* aux = c->d_aux + (size_t)w_off * c->aux_stride;
-        // (the same launch also forms the per-walker constants of the spirals, laws and truncations the context carries)
+        // (the same launch also forms the per-walker constants of the spirals, laws, truncations and bending modes the
+        // context carries)
         if (items > 0)
             hipLaunchKernelGGL(general_split_kernel(g.level), dim3((items + 255) / 256), dim3(256), 0, st, prep,
                                c->plen, skip ? own_skip : nullptr, gpar, aux, c->aux_stride, c->aux_n_sky,
                                c->d_gen_flags, c->n_ps, c->n_sersic, c->n_psf, c->n_psf_field, n, g.par[kBlkSpi],
                                g.masks[kBlkSpi], g.off[kBlkSpi], g.par[kBlkRad], g.masks[kBlkRad], g.off[kBlkRad],
-                               g.par[kBlkTru], g.masks[kBlkTru], g.off[kBlkTru]);
+                               g.par[kBlkTru], g.masks[kBlkTru], g.off[kBlkTru], g.par[kBlkBnd], g.masks[kBlkBnd],
+                               g.off[kBlkBnd]);
         if (c->blk[kBlkFou].any && items > 0)
             hipLaunchKernelGGL(k_fourier_prep, dim3((items + 3) / 4), dim3(256), 0, st, prep, c->plen,
                                skip ? own_skip : nullptr, gpar, g.par[kBlkFou], aux, c->aux_stride, g.off[kBlkFou],
@@ -2213,6 +2222,7 @@ static int apply_aux_record(psfmc_ctx* c, int field, int touched = -1) {
     if (c->aux_blobs[field]) (void)hipFree(c->aux_blobs[field]);
     c->aux_blobs[field] = fresh;
     L.n_aux = t.n_aux; L.n_fou = t.n_fou; L.n_spi = t.n_spi; L.n_rad = t.n_rad; L.n_tru = t.n_tru;
+    L.n_bnd = t.n_bnd;
     L.aux_const = static_cast<const double*>(fresh);
     L.aux_col = fresh ? reinterpret_cast<const int*>(L.aux_const + t.n_aux) : nullptr;
     L.rad_kind = t.kinds.empty() ? nullptr : L.aux_col + t.n_aux;
@@ -2492,7 +2502,8 @@ extern "C" int psfmc_set_aux_rows(psfmc_ctx* c, int W, const double* aux) {
     return PSFMC_OK;
 }
 
-// psfmc_set_fourier_layout, _spiral_layout, _radial_layout and _truncation_layout: block b of field `field` with its per-Sersic tags.
+// psfmc_set_fourier_layout, _spiral_layout, _radial_layout, _truncation_layout and _bending_layout: block b of field
+// `field` with its per-Sersic tags.
 // Everything is checked before the record changes, so a refused call leaves the field as it was.
 static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const int* tags, const int* col,
                             const double* konst) {
@@ -2513,6 +2524,8 @@ static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const 
         if (b == kBlkTru && (tags[i] & ~(kTruInner | kTruOuter)))
             return fail(PSFMC_EINVAL, "Sersic %d: truncation flags %d outside 0 ... %d (bit 0 inner, bit 1 outer)", i,
                         tags[i], kTruInner | kTruOuter);
+        if (b == kBlkBnd && (tags[i] & ~kBndModeBits))
+            return fail(PSFMC_EINVAL, "Sersic %d: bending mask 0x%x names a mode outside 1 ... %d", i, tags[i], kBndModes);
         any_here = any_here || tags[i];
     }
     if (any_here && r.base_col.empty())
@@ -2560,6 +2573,11 @@ extern "C" int psfmc_set_truncation_layout(psfmc_ctx* c, int field, int n_sersic
     return set_block_layout(c, kBlkTru, field, n_sersic, flags, col, konst);
 }
 
+extern "C" int psfmc_set_bending_layout(psfmc_ctx* c, int field, int n_sersic, const int* mode_mask, const int* col,
+                                        const double* konst) {
+    return set_block_layout(c, kBlkBnd, field, n_sersic, mode_mask, col, konst);
+}
+
 extern "C" int psfmc_debug_aux_table(int n_sky, int n_sersic, const int* base_col, const double* base_const,
                                      const int* mode_mask, const int* fou_col, const double* fou_const,
                                      const int* spi_flags, const int* spi_col, const double* spi_const,
@@ -2578,16 +2596,33 @@ extern "C" int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* 
                                             const int* tru_flags, const int* tru_col, const double* tru_const,
                                             double* out_const, int* out_col, int* out_kinds, int* out_sides,
                                             int* counts) {
-    if (n_sky < 0 || n_sersic < 0 || !out_const || !out_col || !out_kinds || !counts || (tru_flags && !out_sides))
+    return psfmc_debug_aux_table_bending(n_sky, n_sersic, base_col, base_const, mode_mask, fou_col, fou_const, spi_flags,
+                                         spi_col, spi_const, rad_kinds, rad_col, rad_const, tru_flags, tru_col,
+                                         tru_const, nullptr, nullptr, nullptr, out_const, out_col, out_kinds, out_sides,
+                                         nullptr, counts);
+}
+
+// ... and with the bending block: out_bends and counts[5] are written where bnd_mask is given, out_sides and counts[4]
+// where tru_flags or bnd_mask is
+extern "C" int psfmc_debug_aux_table_bending(int n_sky, int n_sersic, const int* base_col, const double* base_const,
+                                             const int* mode_mask, const int* fou_col, const double* fou_const,
+                                             const int* spi_flags, const int* spi_col, const double* spi_const,
+                                             const int* rad_kinds, const int* rad_col, const double* rad_const,
+                                             const int* tru_flags, const int* tru_col, const double* tru_const,
+                                             const int* bnd_mask, const int* bnd_col, const double* bnd_const,
+                                             double* out_const, int* out_col, int* out_kinds, int* out_sides,
+                                             int* out_bends, int* counts) {
+    if (n_sky < 0 || n_sersic < 0 || !out_const || !out_col || !out_kinds || !counts ||
+        ((tru_flags || bnd_mask) && !out_sides) || (bnd_mask && !out_bends))
         return fail(PSFMC_EINVAL, "bad counts or NULL output");
     FieldAuxRecord r;
     if (base_col && base_const) {
         r.base_col.assign(base_col, base_col + aux_len(n_sky, n_sersic));
         r.base_const.assign(base_const, base_const + aux_len(n_sky, n_sersic));
     }
-    const int* tags[kAuxBlocks] = {mode_mask, spi_flags, rad_kinds, tru_flags};
-    const int* col[kAuxBlocks] = {fou_col, spi_col, rad_col, tru_col};
-    const double* konst[kAuxBlocks] = {fou_const, spi_const, rad_const, tru_const};
+    const int* tags[kAuxBlocks] = {mode_mask, spi_flags, rad_kinds, tru_flags, bnd_mask};
+    const int* col[kAuxBlocks] = {fou_col, spi_col, rad_col, tru_col, bnd_col};
+    const double* konst[kAuxBlocks] = {fou_const, spi_const, rad_const, tru_const, bnd_const};
     for (int b = 0; b < kAuxBlocks; ++b)
         if (tags[b] && col[b] && konst[b]) r.block[b].store(n_sersic, aux_block_len(b, n_sersic), tags[b], col[b], konst[b]);
     const AuxTable t = compose_aux_table(r, n_sky, n_sersic);
@@ -2595,9 +2630,13 @@ extern "C" int psfmc_debug_aux_table_blocks(int n_sky, int n_sersic, const int* 
     std::copy(t.col.begin(), t.col.end(), out_col);
     std::copy(t.kinds.begin(), t.kinds.end(), out_kinds);
     counts[0] = t.n_aux; counts[1] = t.n_fou; counts[2] = t.n_spi; counts[3] = t.n_rad;
-    if (tru_flags) {
+    if (tru_flags || bnd_mask) {
         std::copy(t.sides.begin(), t.sides.end(), out_sides);
         counts[4] = t.n_tru;
+    }
+    if (bnd_mask) {
+        std::copy(t.bends.begin(), t.bends.end(), out_bends);
+        counts[5] = t.n_bnd;
     }
     return PSFMC_OK;
 }
@@ -4376,6 +4415,11 @@ extern "C" int psfmc_group_set_radial_layout(psfmc_group* g, int n_sersic, const
 extern "C" int psfmc_group_set_truncation_layout(psfmc_group* g, int n_sersic, const int* flags, const int* col,
                                                  const double* konst) {
     return group_set_block_layout(g, kBlkTru, n_sersic, flags, col, konst);
+}
+
+extern "C" int psfmc_group_set_bending_layout(psfmc_group* g, int n_sersic, const int* mode_mask, const int* col,
+                                              const double* konst) {
+    return group_set_block_layout(g, kBlkBnd, n_sersic, mode_mask, col, konst);
 }
 
 extern "C" int psfmc_group_set_general_mean(psfmc_group* g, int n_sersic, const int* flags) {

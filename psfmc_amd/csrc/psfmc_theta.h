@@ -64,7 +64,12 @@ struct ThetaLayout {
     // (n_tru > 0 implies the three blocks before it, empty without the keywords); per Sersic slot in_lo, in_hi, out_lo,
     // out_hi; tru_side [n_sersic] in global memory: bit 0 inner, bit 1 outer; 0 / nullptr: none (every layout before
     // the call)
+    // bending modes (psfmc_set_bending_layout): the LAST n_bnd = 4 n_sersic of the n_aux entries, behind the
+    // truncations' (n_bnd > 0 implies the four blocks before it, empty without the keywords); per Sersic slot a_1 ... a_4,
+    // zeros for absent modes; 0: none (every layout before the call).  (Between n_tru and the pointer: the struct keeps
+    // its size.)
     int n_tru;
+    int n_bnd;
     const int* tru_side;
 };
 
@@ -638,7 +643,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 // the walker's auxiliary vector; a boxiness <= -2 or not finite is outside the support (as
                 // reff_b > reff is)
                 double* a = ax.aux + (size_t)w * ax.stride;
-                const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad - G.n_tru;
+                const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad - G.n_tru - G.n_bnd;
                 for (int j = 0; j < n_base; ++j) {
                     const int col = G.aux_col[j];
                     const double v = col >= 0 ? th[col] : G.aux_const[j];
@@ -685,7 +690,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // the radial laws' entries, per Sersic slot two; outside the support: a Moffat's beta not
                     // finite or <= 1; a Ferrer's alpha or beta not finite, alpha < 0 or beta >= 2
                     int k = 0;
-                    for (int j0 = G.n_aux - G.n_tru - G.n_rad; j0 < G.n_aux - G.n_tru; j0 += 2, ++k) {
+                    for (int j0 = G.n_aux - G.n_bnd - G.n_tru - G.n_rad; j0 < G.n_aux - G.n_bnd - G.n_tru; j0 += 2, ++k) {
                         const int c0 = G.aux_col[j0], c1 = G.aux_col[j0 + 1];
                         const double v0 = c0 >= 0 ? th[c0] : G.aux_const[j0];
                         const double v1 = c1 >= 0 ? th[c1] : G.aux_const[j0 + 1];
@@ -701,7 +706,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // the truncations' entries, per Sersic slot two pairs (lo, hi); outside the support of a side
                     // present: a value not finite, lo < 0 or hi <= lo
                     int k = 0;
-                    for (int j0 = G.n_aux - G.n_tru; j0 < G.n_aux; j0 += 4, ++k) {
+                    for (int j0 = G.n_aux - G.n_bnd - G.n_tru; j0 < G.n_aux - G.n_bnd; j0 += 4, ++k) {
                         const int sides = G.tru_side[k];
                         for (int j = 0; j < 4; j += 2) {
                             const int c0 = G.aux_col[j0 + j], c1 = G.aux_col[j0 + j + 1];
@@ -712,6 +717,16 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                             if (((sides >> (j >> 1)) & 1) && (!(lo >= 0.0) || !(hi > lo) || !(hi < INFINITY)))
                                 lp = -INFINITY;
                         }
+                    }
+                }
+                if (G.n_bnd > 0) {                                          // wave-uniform
+                    // the bending amplitudes, per Sersic slot four (zeros for absent modes); outside the support: a
+                    // value not finite
+                    for (int j = G.n_aux - G.n_bnd; j < G.n_aux; ++j) {
+                        const int col = G.aux_col[j];
+                        const double v = col >= 0 ? th[col] : G.aux_const[j];
+                        a[j] = v;
+                        if (!(fabs(v) < INFINITY)) lp = -INFINITY;
                     }
                 }
             }

@@ -28,7 +28,8 @@ _FLAG_COMMENTS = {'SERINT': _INTEGRATE_COMMENT, 'SERBOX': 'Sersic with boxy/disk
                   'SKYSLP': 'tilted sky (slope)', 'SERFOU': 'Sersic with azimuthal Fourier modes (fourier)',
                   'SERSPI': 'Sersic with spiral arms by coordinate rotation (spiral)',
                   'SERLAW': 'radial law of the component (Moffat, Ferrer)',
-                  'SERTRU': 'truncated sides of the component (truncation)'}
+                  'SERTRU': 'truncated sides of the component (truncation)',
+                  'SERBND': 'bending modes of the component (bending)'}
 
 
 class Table(object):

@@ -297,6 +297,10 @@ def load_library():
     lib.psfmc_set_truncation_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
     lib.psfmc_group_set_truncation_layout.restype = ci
     lib.psfmc_group_set_truncation_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
+    lib.psfmc_set_bending_layout.restype = ci
+    lib.psfmc_set_bending_layout.argtypes = [vp, ci, ci, ip, ip, _c_double_p]
+    lib.psfmc_group_set_bending_layout.restype = ci
+    lib.psfmc_group_set_bending_layout.argtypes = [vp, ci, ip, ip, _c_double_p]
     lib.psfmc_set_general_mean.restype = ci
     lib.psfmc_set_general_mean.argtypes = [vp, ci, ci, ip]
     lib.psfmc_group_set_general_mean.restype = ci
@@ -314,6 +318,9 @@ def load_library():
     lib.psfmc_debug_aux_table_blocks.restype = ci
     lib.psfmc_debug_aux_table_blocks.argtypes = ([ci, ci, ip, _c_double_p] + 4 * [ip, ip, _c_double_p] +
                                                  [_c_double_p, ip, ip, ip, ip])
+    lib.psfmc_debug_aux_table_bending.restype = ci
+    lib.psfmc_debug_aux_table_bending.argtypes = ([ci, ci, ip, _c_double_p] + 5 * [ip, ip, _c_double_p] +
+                                                  [_c_double_p, ip, ip, ip, ip, ip])
     lib.psfmc_fisher_rows.restype = ci
     lib.psfmc_fisher_rows.argtypes = [vp, ci, ci, ci] + [_c_double_p] * 5
     lib.psfmc_fisher_rows_fields.restype = ci
@@ -451,14 +458,15 @@ FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude an
 SPIRAL_PARAMS = 6          # PSFMC_SPIRAL_PARAMS: r_in, r_out, winding, alpha, inclination, sky angle
 RADIAL_PARAMS = 2          # PSFMC_RADIAL_PARAMS: (beta, unused) of a Moffat slot, (alpha, beta) of a Ferrer slot
 TRUNC_PARAMS = 4           # PSFMC_TRUNC_PARAMS: in_lo, in_hi, out_lo, out_hi of a slot (flag bit 0 inner, bit 1 outer)
+BEND_MODES = 4             # PSFMC_BEND_MODES: bending modes 1 ... 4, an amplitude entry each (mask bit m - 1)
 # the blocks behind the aux entries, in table order: name -> (entries per Sersic, the per-Sersic tags are flags)
 _BLOCKS = {'fourier': (2 * FOURIER_MODES, False), 'spiral': (SPIRAL_PARAMS, True), 'radial': (RADIAL_PARAMS, False),
-           'truncation': (TRUNC_PARAMS, False)}
+           'truncation': (TRUNC_PARAMS, False), 'bending': (BEND_MODES, False)}
 
 
 def _block_args(name, tags, col, const):
     """The arrays of psfmc_set_<name>_layout (kept alive by the caller's tuple) and their ctypes pointers: per
-    Sersic a tag -- mode mask, spiral flag, radial kind, truncation sides -- and the block's entries."""
+    Sersic a tag -- mode mask, spiral flag, radial kind, truncation sides, bending mask -- and the block's entries."""
     per_sersic, tags_are_flags = _BLOCKS[name]
     i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32), dtype=np.int32).ravel()
     tags = i32(np.asarray(tags, dtype=bool) if tags_are_flags else tags)
@@ -470,7 +478,7 @@ def _block_args(name, tags, col, const):
 
 
 class _BlockLayouts(object):
-    """The four block layout calls of a context, a field of a set and a group: each class has
+    """The five block layout calls of a context, a field of a set and a group: each class has
     `_set_block(name, tags, col, const)`, psfmc_[group_]set_<name>_layout on what it stands for."""
 
     def set_fourier_layout(self, mode_masks, col, const):
@@ -496,6 +504,12 @@ class _BlockLayouts(object):
         inner, bit 1 outer -- and four entries, in_lo, in_hi, out_lo, out_hi; column of theta or -1 and a constant.
         A context that never gets the call is what it was without it."""
         self._set_block('truncation', flags, col, const)
+
+    def set_bending_layout(self, mode_masks, col, const):
+        """Bending modes (psfmc_set_bending_layout; behind the truncation layout, the last block): per Sersic slot a
+        mask of its modes (bit m - 1: mode m) and four entries, a_1 ... a_4; column of theta or -1 and a constant.  A
+        context that never gets the call is what it was without it."""
+        self._set_block('bending', mode_masks, col, const)
 
 
 def _send_aux_rows(lib, ctx, check, aux, n_w, width=None):
@@ -577,31 +591,40 @@ def debug_pow_tab(values, p, device=0):
     return out.reshape(np.shape(values))
 
 
-def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radial=None, truncation=None):
+def debug_aux_table(n_sky, n_sersic, base=None, fourier=None, spiral=None, radial=None, truncation=None, bending=None):
     """The auxiliary table the library composes for one field (psfmc_debug_aux_table; host only, no device): base =
     (col, const) of the aux layout, each block (tags, col, const) as its layout call takes them, None where the
     field registered none -> (const, col, kinds, (n_aux, n_fou, n_spi, n_rad)).  With `truncation`
-    (psfmc_debug_aux_table_blocks) -> (const, col, kinds, sides, (n_aux, n_fou, n_spi, n_rad, n_tru))."""
+    (psfmc_debug_aux_table_blocks) -> (const, col, kinds, sides, (n_aux, n_fou, n_spi, n_rad, n_tru)).  With `bending`
+    (psfmc_debug_aux_table_bending; with or without `truncation`) -> (const, col, kinds, sides, bends, (n_aux, n_fou,
+    n_spi, n_rad, n_tru, n_bnd))."""
     lib = load_library()
     keep, args = [], [None, None]
     if base is not None:
         keep.append(_aux_layout_args(base[0], base[1], np.zeros(n_sky), np.zeros(n_sersic)))
         args = list(keep[-1][1][1:3])
-    for name, block in zip(_BLOCKS, (fourier, spiral, radial, truncation)):
+    for name, block in zip(_BLOCKS, (fourier, spiral, radial, truncation) + ((bending,) if bending is not None else ())):
         if block is not None:
             keep.append(_block_args(name, *block))
         args += [None, None, None] if block is None else list(keep[-1][1][1:])
     n_max = 2 * n_sky + (1 + sum(per for per, _ in _BLOCKS.values())) * n_sersic
     const, col = np.full(n_max, np.nan), np.full(n_max, -2, dtype=np.int32)
     kinds, sides = np.full(n_sersic, -2, dtype=np.int32), np.full(n_sersic, -2, dtype=np.int32)
-    counts = np.zeros(5, dtype=np.int32)
+    bends, counts = np.full(n_sersic, -2, dtype=np.int32), np.zeros(5 if bending is None else 6, dtype=np.int32)
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    rc = lib.psfmc_debug_aux_table_blocks(int(n_sky), int(n_sersic), *(
-        args + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(counts)]))
+    if bending is None:
+        rc = lib.psfmc_debug_aux_table_blocks(int(n_sky), int(n_sersic), *(
+            args + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(counts)]))
+    else:
+        rc = lib.psfmc_debug_aux_table_bending(int(n_sky), int(n_sersic), *(
+            args + [_dp(const), ipt(col), ipt(kinds), ipt(sides), ipt(bends), ipt(counts)]))
     if rc != 0:
         raise NativeError(rc, lib.psfmc_last_error().decode('utf-8', 'replace'))
     n_aux = int(counts[0])
     out = (const[:n_aux], col[:n_aux], kinds[:n_sersic if counts[3] else 0])
+    if bending is not None:
+        return out + (sides[:n_sersic if counts[4] else 0], bends[:n_sersic if counts[5] else 0],
+                      tuple(int(n) for n in counts))
     if truncation is None:
         return out + (tuple(int(n) for n in counts[:4]),)
     return out + (sides[:n_sersic if counts[4] else 0], tuple(int(n) for n in counts))

@@ -34,7 +34,7 @@ _DEVICE_FAMILIES = {
 # spiral entries (r_in, r_out, winding, alpha, inclination, sky angle) of a Sersic component without the keyword:
 # inside the support, never read
 _SPIRAL_ABSENT = (0.0, 1.0, 0.0, 0.0, 0.0, 0.0)
-# The four blocks behind the aux entries, in table order (engine._BLOCKS; include/psfmc_hip.h psfmc_set_<name>_layout):
+# The five blocks behind the aux entries, in table order (engine._BLOCKS; include/psfmc_hip.h psfmc_set_<name>_layout):
 # the model property with the per-Sersic tags, and a Sersic slot's entries -- each the name of a parameter as declared,
 # or the constant an absent one holds (neutral, or inside the support of what never reads it).  A block is registered,
 # after the aux layout and in this order, only by a model with a tag set; a block in a walker's auxiliary row forces
@@ -52,6 +52,9 @@ _AUX_BLOCKS = (
     ('truncation', 'sersic_truncation_flags', lambda c: [
         attr if (getattr(c, 'truncation_flags', 0) >> (j // 2)) & 1 else absent
         for j, (attr, absent) in enumerate(zip(Sersic.TRUNC_ATTRS, Sersic.TRUNC_ABSENT))]),
+    # a_1 ... a_4; mask bit m - 1 the mode m
+    ('bending', 'sersic_bending_masks', lambda c: [
+        attr if m in getattr(c, 'bending_modes', ()) else 0.0 for m, attr in zip(Sersic.BEND_MODES, Sersic.BEND_ATTRS)]),
 )
 _FIRST_NEW_FAMILY = 5           # psfmc_set_layout takes families 0-4; the rest go through psfmc_set_priors
 
@@ -320,8 +323,8 @@ class MultiComponentModel(object):
     @property
     def sersic_general_flags(self):
         """[n_sersic] which Sersic components (model-file order) run the general kernels: those given a `boxiness`
-        or `fourier` modes (a component with modes alone is a general one at c = 0), a `spiral` or a `truncation`, and
-        every `Moffat` and `Ferrer`."""
+        or `fourier` modes (a component with modes alone is a general one at c = 0), a `spiral`, a `truncation` or
+        `bending` modes, and every `Moffat` and `Ferrer`."""
         return [bool(getattr(c, 'is_general', False)) for c in self._sersic]
 
     @property
@@ -345,14 +348,19 @@ class MultiComponentModel(object):
         return [int(getattr(c, 'truncation_flags', 0)) for c in self._sersic]
 
     @property
+    def sersic_bending_masks(self):
+        """[n_sersic] bit m - 1 set where the Sersic slot (model-file order) has bending mode m; 0: none."""
+        return [int(getattr(c, 'bending_mask', 0)) for c in self._sersic]
+
+    @property
     def sersic_general_mean(self):
         """[n_sersic] which Sersic slots (model-file order) were given `pixel_mean=True`."""
         return [bool(getattr(c, 'pixel_mean', False)) for c in self._sersic]
 
     @property
     def has_aux(self):
-        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier`, `spiral` or
-        `truncation`, a `Moffat` or `Ferrer`)?"""
+        """Does a component carry an auxiliary parameter (Sky `slope`, Sersic `boxiness`, `fourier`, `spiral`,
+        `truncation` or `bending`, a `Moffat` or `Ferrer`)?"""
         return any(self.sky_slope_flags) or any(self.sersic_general_flags)
 
     def aux_rows(self, theta):
@@ -366,7 +374,9 @@ class MultiComponentModel(object):
         model with a `Moffat` or `Ferrer` carries both blocks and behind them psfmc_set_radial_layout's 2 n_sersic:
         per Sersic slot (beta, 0) or (alpha, beta), zeros for a slot with the Sersic law.  A model with a `truncation`
         carries the three blocks and behind them psfmc_set_truncation_layout's 4 n_sersic: per Sersic slot in_lo,
-        in_hi, out_lo, out_hi (constants inside the support for an absent side): 2 n_sky + 25 n_sersic in all."""
+        in_hi, out_lo, out_hi (constants inside the support for an absent side): 2 n_sky + 25 n_sersic in all.  A
+        model with `bending` modes carries the four blocks and behind them psfmc_set_bending_layout's 4 n_sersic: per
+        Sersic slot a_1 ... a_4 (zeros for absent modes): 2 n_sky + 29 n_sersic in all."""
         if not self.has_aux:
             return None
         theta = self._theta(theta)

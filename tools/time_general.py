@@ -12,7 +12,9 @@ boxy `Sersic`s.
 the same model without it.
 --truncation: the cost of a truncated component -- the `--radial` model with an inner and an outer truncation on the
 Ferrer and an outer one on the Moffat (all six radii free) against the same model untruncated.
-Usage: python tools/time_general.py [--fourier | --spiral | --radial | --mean | --truncation] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
+--bending: the cost of bending modes -- the `--radial` model with modes 2 and 3 on the Ferrer and mode 2 on the Moffat
+(all three amplitudes free) against the same model without bending.
+Usage: python tools/time_general.py [--fourier | --spiral | --radial | --mean | --truncation | --bending] [--shapes 256:4096 128:22] [--seconds 1.0] [--out FILE]"""
 import argparse
 import json
 import os
@@ -82,9 +84,10 @@ TRUNC_RANGE = {'trunc_in_lo': (0.0, 0.01), 'trunc_in_hi': (0.02, 0.04), 'trunc_o
                'trunc_out_hi': (0.10, 0.12)}                            # in units of the side
 
 
-def build_radial(side, directory, max_walkers, laws, mean=False, trunc=False):
+def build_radial(side, directory, max_walkers, laws, mean=False, trunc=False, bend=False):
     """Sky + PS + a boxy Ferrer and a Moffat (`laws`; with `mean` both have `pixel_mean=True`, with `trunc` the
-    Ferrer both truncations and the Moffat an outer one, every radius free), or two boxy Sersics with the same radii;
+    Ferrer both truncations and the Moffat an outer one, every radius free, with `bend` the Ferrer bending modes 2 and 3
+    and the Moffat mode 2, every amplitude free), or two boxy Sersics with the same radii;
     the model and a function drawing n_w vectors inside every support."""
     fld = synth_field.make_field(side, n_sersic=1, seed=0)
     for key, name in (('sci', 'sci.fits'), ('ivm', 'ivm.fits'), ('psf', 'psf.fits'), ('psf_ivm', 'psf_ivm.fits')):
@@ -97,15 +100,18 @@ def build_radial(side, directory, max_walkers, laws, mean=False, trunc=False):
     radius = 'Uniform(loc=0.0, scale=%r)' % float(side)
     cut = lambda sides: (", truncation={%s}" % ', '.join("'%s': (%s, %s)" % (k, radius, radius) for k in sides)
                          if trunc else '')
+    amp = 'Uniform(loc=-1.0, scale=2.0)'
+    cut_bend = lambda sides, modes: cut(sides) + (
+        ', bending={%s}' % ', '.join('%d: %s' % (m, amp) for m in modes) if bend else '')
     if laws:
         text += 'Ferrer(%s, r_out=%s, r_out_b=%s, alpha=Uniform(loc=0, scale=4), beta=Uniform(loc=-2, scale=3.95), %s%s)\n' % (
-            RADIAL_COMMON, big, small, box, cut(('inner', 'outer')))
+            RADIAL_COMMON, big, small, box, cut_bend(('inner', 'outer'), (2, 3)))
         text += 'Moffat(%s, fwhm=%s, fwhm_b=%s, beta=Uniform(loc=1.05, scale=8)%s%s)\n' % (
-            RADIAL_COMMON, big, small, ', pixel_mean=True' if mean else '', cut(('outer',)))
+            RADIAL_COMMON, big, small, ', pixel_mean=True' if mean else '', cut_bend(('outer',), (2,)))
     else:
         for _ in range(2):
             text += 'Sersic(%s, reff=%s, reff_b=%s, index=Uniform(loc=0.5, scale=6), %s)\n' % (RADIAL_COMMON, big, small, box)
-    path = os.path.join(directory, 'model_r%d%d%d.py' % (laws, mean, trunc))
+    path = os.path.join(directory, 'model_r%d%d%d%d.py' % (laws, mean, trunc, bend))
     with open(path, 'w') as f:
         f.write(text)
     model = MultiComponentModel(path, max_walkers=max_walkers)
@@ -123,6 +129,8 @@ def build_radial(side, directory, max_walkers, laws, mean=False, trunc=False):
                 cols.append(rng.uniform(2.0, side / 16.0, (n_w, 1)))
             elif attr in TRUNC_RANGE:
                 cols.append(side * rng.uniform(*TRUNC_RANGE[attr], size=(n_w, 1)))
+            elif attr.startswith('bend'):
+                cols.append(rng.uniform(-0.4, 0.4, (n_w, 1)))
             elif name.endswith('PointSource_mag'):
                 cols.append(rng.uniform(18.5, 19.5, (n_w, 1)))
             else:
@@ -164,18 +172,21 @@ def main():
     ap.add_argument('--mean', action='store_true', help='the --radial model with pixel_mean=True against the same without')
     ap.add_argument('--truncation', action='store_true',
                     help='the --radial model with truncated components against the same untruncated')
+    ap.add_argument('--bending', action='store_true',
+                    help='the --radial model with bending modes against the same without')
     args = ap.parse_args()
-    if args.fourier + args.spiral + args.radial + args.mean + args.truncation > 1:
-        ap.error('--fourier, --spiral, --radial, --mean and --truncation exclude each other')
+    if args.fourier + args.spiral + args.radial + args.mean + args.truncation + args.bending > 1:
+        ap.error('--fourier, --spiral, --radial, --mean, --truncation and --bending exclude each other')
     rows = []
     for shape in args.shapes:
         side, n_w = (int(v) for v in shape.split(':'))
         with tempfile.TemporaryDirectory() as tmp:
             rates = {}
             for general in (0, 1, 0, 1):                  # alternating, the better of two runs each
-                if args.radial or args.mean or args.truncation:
+                if args.radial or args.mean or args.truncation or args.bending:
                     model, draw = (build_radial(side, tmp, n_w, 1, mean=bool(general)) if args.mean else
                                    build_radial(side, tmp, n_w, 1, trunc=bool(general)) if args.truncation else
+                                   build_radial(side, tmp, n_w, 1, bend=bool(general)) if args.bending else
                                    build_radial(side, tmp, n_w, general))
                     rate, _ = evals_per_second(model, draw(n_w), args.seconds)
                     rates[general] = max(rates.get(general, 0.0), rate)
@@ -211,7 +222,8 @@ def main():
                        general_evals_per_s=round(rates[1], 1), ratio=round(rates[1] / rates[0], 4))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    lines = ['side     W untruncated evals/s  truncated evals/s  ratio' if args.truncation else
+    lines = ['side     W    unbent evals/s       bent evals/s  ratio' if args.bending else
+             'side     W untruncated evals/s  truncated evals/s  ratio' if args.truncation else
              'side     W   centres evals/s  pixel means evals/s  ratio' if args.mean else
              'side     W 2 Sersics evals/s Ferrer + Moffat evals/s ratio' if args.radial else
              'side     W  boxiness evals/s box + spiral evals/s  ratio' if args.spiral else
