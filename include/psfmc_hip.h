@@ -210,6 +210,28 @@ int psfmc_set_priors(psfmc_ctx* ctx, int field, int n_params, const int* family,
  */
 int psfmc_set_sersic_integrate(psfmc_ctx* ctx, int field, int n_sersic, const int* integrate);
 /*
+ * Ties: parameters of one model that are not independent (Tied(source, ratio, offset); GALFIT's constraints; not the
+ * reference's).  Tie t of observed field `field` (0 in an ordinary context) has the value
+ *     ratio * theta[src_col[t]] + offset,
+ * ratio = theta[ratio_col[t]] or, where ratio_col[t] = -1, ratio_const[t]; offset likewise.  The arithmetic is two
+ * separately rounded fp64 operations, product then sum, never a fused multiply-add: numpy's `ratio * source + offset`
+ * to the bit.  In every column table the library takes -- psfmc_set_layout[_field]'s slot_col, psfmc_set_aux_layout's
+ * aux_col and the col of psfmc_set_fourier / _spiral / _radial / _truncation / _bending_layout -- an entry <= -2
+ * names tie t = -2 - entry; -1 stays "the constant" and >= 0 "the column".  A tied entry has no prior of its own
+ * (the prior table stays over the n_params free columns); every support rule (reff_b > reff, boxiness <= -2,
+ * sum |a_m| >= 1, the spiral, law, truncation and bending rules) reads the resolved value.  The ties are resolved
+ * inside the kernels that derive the records and the joint log-priors: no launch is added, and a field without ties
+ * runs what it ran.  Call BEFORE the field's psfmc_set_layout[_field]: the ties take effect with that call, which
+ * checks them against its n_params, and a registered layout keeps the ties it was checked against until the field's
+ * next layout.  n_ties = 0 clears the field's ties (with its next layout).  PSFMC_EINVAL: n_ties outside
+ * [0, PSFMC_MAX_TIES], a source column < 0, a ratio / offset column < -1 or a constant that is not finite (here); a
+ * tie column >= n_params, a tie on the PSF-index slot (psfmc_set_layout[_field]); a table entry naming tie >= n_ties
+ * (the call that passes the table).  In joint fits the columns are the joint vector's.
+ */
+#define PSFMC_MAX_TIES 64
+int psfmc_set_ties(psfmc_ctx* ctx, int field, int n_ties, const int* src_col, const int* ratio_col,
+                   const double* ratio_const, const int* offset_col, const double* offset_const);
+/*
  * Auxiliary parameters: free parameters beyond the caller row, with the components that read them (not the
  * reference's): a tilted sky (Sky(..., slope=(sx, sy))) and boxy / disky Sersic isophotes (Sersic(..., boxiness=c),
  * GALFIT's C0).  Definitions: psfmc_amd/ModelComponents/Sky.py Sky.tilted_image and Sersic.py Sersic.general_image;
@@ -758,6 +780,9 @@ int psfmc_group_set_layout(psfmc_group* group, int n_sky, int n_params, const in
                            const double* p2);
 /* psfmc_set_priors on every device of the group */
 int psfmc_group_set_priors(psfmc_group* group, int n_params, const int* family, const double* params);
+/* psfmc_set_ties (field 0) on every device of the group; before psfmc_group_set_layout */
+int psfmc_group_set_ties(psfmc_group* group, int n_ties, const int* src_col, const int* ratio_col,
+                         const double* ratio_const, const int* offset_col, const double* offset_const);
 /* psfmc_set_aux_layout (field 0) on every device of the group (raw-vector entry points; the group's row-based
  * psfmc_group_eval_batch has no aux rows and is refused on such a group) */
 int psfmc_group_set_aux_layout(psfmc_group* group, int n_aux, const int* aux_col, const double* aux_const,

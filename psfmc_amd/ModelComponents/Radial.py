@@ -35,8 +35,8 @@ class _RadialLaw(Sersic):
         """Always: the laws live in the general kernels (boxiness 0 when absent)."""
         return True
 
-    def values_batch(self, block):
-        out = super(_RadialLaw, self).values_batch(block)
+    def values_batch(self, block, resolved=None):
+        out = super(_RadialLaw, self).values_batch(block, resolved)
         out['reff'], out['reff_b'] = out[self.RADII[0]], out[self.RADII[1]]
         return out
 
@@ -53,9 +53,9 @@ class _RadialLaw(Sersic):
             return -np.inf
         return logp
 
-    def log_priors_batch(self, block):
-        logp = super(_RadialLaw, self).log_priors_batch(block)
-        vals = self.values_batch(block)
+    def log_priors_batch(self, block, resolved=None):
+        logp = super(_RadialLaw, self).log_priors_batch(block, resolved)
+        vals = self.values_batch(block, resolved)
         return np.where(Sersic._radial_ok(self.radial_law, self._radial_values(vals, len(logp))), logp, -np.inf)
 
 

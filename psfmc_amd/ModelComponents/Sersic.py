@@ -417,9 +417,9 @@ class Sersic(ComponentBase):
             return -np.inf
         return logp + (-np.inf if self.reff_b > self.reff else 0)
 
-    def log_priors_batch(self, block):
+    def log_priors_batch(self, block, resolved=None):
         logp = super(Sersic, self).log_priors_batch(block)
-        vals = self.values_batch(block)
+        vals = self.values_batch(block, resolved)
         logp = np.where(vals['reff_b'] > vals['reff'], -np.inf, logp)
         if self.has_boxiness:
             logp = np.where(Sersic._boxiness_ok(np.reshape(vals['boxiness'], (len(logp),))), logp, -np.inf)

@@ -3,7 +3,7 @@ psfmc_amd -- MI355X-native batched log-posterior for psfMC-style MCMC surface
 brightness modelling.  Public names mirror the reference package `psfMC`.
 """
 from .models import MultiComponentModel, FieldSet, JointModel
-from .ModelComponents import Moffat, Ferrer
+from .ModelComponents import Moffat, Ferrer, Tied
 from .batch import BatchLogPosterior
 from .sampler import (EnsembleSampler, DeviceEnsembleSampler, FieldSetSampler, TemperedEnsembleSampler,
                       DeviceTemperedSampler, FieldSetTemperedSampler, default_betas, StretchMove, DEMove)
@@ -19,4 +19,4 @@ __all__ = ['MultiComponentModel', 'FieldSet', 'JointModel', 'BatchLogPosterior',
            'default_betas', 'RankGroup', 'ShardedLogPosterior', 'model_galaxy_mcmc', 'model_fields_mcmc',
            'model_joint_mcmc', 'model_galaxy_ptmcmc', 'model_joint_ptmcmc', 'load_database', 'Moffat', 'Ferrer',
            'StretchMove', 'DEMove', 'FieldSetTemperedSampler', 'model_fields_ptmcmc',
-           'find_mode', 'find_modes']
+           'find_mode', 'find_modes', 'Tied']

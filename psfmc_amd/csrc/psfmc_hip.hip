@@ -288,6 +288,18 @@ struct psfmc_ctx {
     double* d_gen_par = nullptr;         // [max_walkers][n_sersic][kGenPar] the general components' real blocks
     double* d_aux = nullptr;             // [max_walkers][aux_stride]
     std::vector<void*> aux_blobs;        // [n_fields] the allocations behind the layouts' aux_col / aux_const
+    // ties (psfmc_set_ties), [n_fields] each or empty (a context that never had a tie): src | ratio | offset columns,
+    // ratio | offset constants and their device copy (konst, then col).  ties_live: what the field's layout points to;
+    // ties_next: what psfmc_set_ties registered since (ties_dirty), made live by the field's next psfmc_set_layout --
+    // a layout and the tables behind it always stand on the ties they were checked against.
+    struct TieRecord {
+        std::vector<int> col;
+        std::vector<double> konst;
+        int n = 0;
+        void* blob = nullptr;
+    };
+    std::vector<TieRecord> ties_live, ties_next;
+    std::vector<char> ties_dirty;
     // [n_fields] what each field registered (psfmc_set_layout's degrees, the arguments of psfmc_set_aux_layout and
     // of the three block layouts): apply_aux_record composes the field's table and mask rows from it
     std::vector<psfmc::FieldAuxRecord> aux_records;
@@ -1453,6 +1465,9 @@ extern "C" int psfmc_ctx_destroy(psfmc_ctx* c) {
     }
     for (void* p : c->aux_blobs)
         if (p) (void)hipFree(p);
+    for (const std::vector<psfmc_ctx::TieRecord>* v : {&c->ties_live, &c->ties_next})
+        for (const psfmc_ctx::TieRecord& r : *v)
+            if (r.blob) (void)hipFree(r.blob);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     for (int i = 1; i < psfmc_ctx::kMaxStreams; ++i) {
         if (c->side[i]) {
@@ -2197,6 +2212,64 @@ static int write_block_masks(psfmc_ctx* c, int field, int touched = -1) {
     return PSFMC_OK;
 }
 
+// A column table's entries against the field's columns and ties: -1 a constant, >= 0 a column, <= -2 tie -2 - entry
+static int live_ties(const psfmc_ctx* c, int field) {
+    return (size_t)field < c->ties_live.size() ? c->ties_live[field].n : 0;
+}
+static int check_table_entries(const char* what, const int* col, int n, int n_params, int n_ties) {
+    for (int i = 0; i < n; ++i) {
+        if (col[i] >= n_params) return fail(PSFMC_EINVAL, "%s %d refers to column %d of %d", what, i, col[i], n_params);
+        if (col[i] <= -2 && -2 - (long long)col[i] >= n_ties)
+            return fail(PSFMC_EINVAL, "%s %d refers to tie %lld of %d (psfmc_set_ties)", what, i, -2 - (long long)col[i],
+                        n_ties);
+    }
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_set_ties(psfmc_ctx* c, int field, int n_ties, const int* src_col, const int* ratio_col,
+                              const double* ratio_const, const int* offset_col, const double* offset_const) {
+    if (!c) return fail(PSFMC_EINVAL, "ctx is NULL");
+    if (field < 0 || field >= c->n_fields) return fail(PSFMC_EINVAL, "field %d of %d", field, c->n_fields);
+    if (n_ties < 0 || n_ties > PSFMC_MAX_TIES)
+        return fail(PSFMC_EINVAL, "n_ties=%d outside [0, PSFMC_MAX_TIES=%d]", n_ties, PSFMC_MAX_TIES);
+    if (n_ties && (!src_col || !ratio_col || !ratio_const || !offset_col || !offset_const))
+        return fail(PSFMC_EINVAL, "NULL tie array");
+    for (int t = 0; t < n_ties; ++t) {
+        if (src_col[t] < 0) return fail(PSFMC_EINVAL, "tie %d: source column %d", t, src_col[t]);
+        if (ratio_col[t] < -1 || offset_col[t] < -1)
+            return fail(PSFMC_EINVAL, "tie %d: ratio column %d, offset column %d (-1: the constant)", t, ratio_col[t],
+                        offset_col[t]);
+        if (!std::isfinite(ratio_const[t]) || !std::isfinite(offset_const[t]))
+            return fail(PSFMC_EINVAL, "tie %d: ratio %g, offset %g: the constants must be finite", t, ratio_const[t],
+                        offset_const[t]);
+    }
+    if (c->ties_live.empty()) {
+        if (!n_ties) return PSFMC_OK;                  // (a context that never had a tie stays what it was)
+        c->ties_live.assign(c->n_fields, psfmc_ctx::TieRecord{});
+        c->ties_next.assign(c->n_fields, psfmc_ctx::TieRecord{});
+        c->ties_dirty.assign(c->n_fields, 0);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    psfmc_ctx::TieRecord& r = c->ties_next[field];     // (no layout points to it: no launch reads its blob)
+    if (r.blob) (void)hipFree(r.blob);
+    r = psfmc_ctx::TieRecord{};
+    c->ties_dirty[field] = 1;
+    if (!n_ties) return PSFMC_OK;
+    r.n = n_ties;
+    r.col.insert(r.col.end(), src_col, src_col + n_ties);
+    r.col.insert(r.col.end(), ratio_col, ratio_col + n_ties);
+    r.col.insert(r.col.end(), offset_col, offset_col + n_ties);
+    r.konst.insert(r.konst.end(), ratio_const, ratio_const + n_ties);
+    r.konst.insert(r.konst.end(), offset_const, offset_const + n_ties);
+    const size_t cb = r.konst.size() * sizeof(double), ib = r.col.size() * sizeof(int);
+    std::vector<unsigned char> blob(cb + ib);
+    memcpy(blob.data(), r.konst.data(), cb);
+    memcpy(blob.data() + cb, r.col.data(), ib);
+    HIP_TRY(hipMalloc(&r.blob, blob.size()));
+    HIP_TRY(hipMemcpy(r.blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    return PSFMC_OK;
+}
+
 // Make field `field`'s record live: its table composed afresh (psfmc_aux_table.h) in a new blob, the layout's counts
 // and pointers, the mask rows, and -- the first time the context needs them -- longer auxiliary vectors (the entries
 // they hold keep their places; aux_stride only grows) and the blocks' masks and parameter buffers, all clear.
@@ -2271,9 +2344,16 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     if (!slot_col || !slot_const || (c->n_ps && !ps_method) || (c->n_sersic && !sersic_degrees) ||
         (n_params && (!family || !p0 || !p1 || !p2)))
         return fail(PSFMC_EINVAL, "NULL layout array");
-    for (int i = 0; i < ns; ++i)
-        if (slot_col[i] < -1 || slot_col[i] >= n_params)
-            return fail(PSFMC_EINVAL, "slot %d refers to column %d of %d", i, slot_col[i], n_params);
+    // the ties this layout will stand on: those registered since the field's last layout, else the live ones
+    const bool new_ties = !c->ties_dirty.empty() && c->ties_dirty[field];
+    const psfmc_ctx::TieRecord none{};
+    const psfmc_ctx::TieRecord& tr = new_ties ? c->ties_next[field] : (c->ties_live.empty() ? none : c->ties_live[field]);
+    RC_TRY(check_table_entries("slot", slot_col, ns, n_params, tr.n));
+    if (slot_col[ns - 1] <= -2) return fail(PSFMC_EINVAL, "slot %d, the PSF index, cannot be tied", ns - 1);
+    for (int t = 0; t < tr.n; ++t)
+        if (tr.col[t] >= n_params || tr.col[tr.n + t] >= n_params || tr.col[2 * tr.n + t] >= n_params)
+            return fail(PSFMC_EINVAL, "tie %d: source column %d, ratio column %d, offset column %d of %d", t,
+                        tr.col[t], tr.col[tr.n + t], tr.col[2 * tr.n + t], n_params);
     for (int i = 0; i < n_params; ++i)
         if (family[i] < 0 || family[i] > PRIOR_RANDINT)
             return fail(PSFMC_EINVAL, "unknown prior family %d for column %d", family[i], i);
@@ -2314,6 +2394,17 @@ static int set_layout_impl(psfmc_ctx* c, int field, int n_sky, int n_params, con
     L.family = dip + ns + c->n_ps + c->n_sersic;
     L.slot_const = ddp; L.pa = ddp + ns; L.pb = ddp + ns + n_params; L.pc = ddp + ns + 2 * n_params;
     L.pd = ddp + ns + 3 * n_params; L.pk = ddp + ns + 4 * n_params;
+    if (new_ties) {                          // (after layout_sync: no launch reads the blob being freed)
+        if (c->ties_live[field].blob) (void)hipFree(c->ties_live[field].blob);
+        c->ties_live[field] = std::move(c->ties_next[field]);
+        c->ties_next[field] = psfmc_ctx::TieRecord{};
+        c->ties_dirty[field] = 0;
+    }
+    if (live_ties(c, field)) {
+        L.n_ties = c->ties_live[field].n;
+        L.tie_const = static_cast<const double*>(c->ties_live[field].blob);
+        L.tie_col = reinterpret_cast<const int*>(L.tie_const + 2 * L.n_ties);
+    }
     RC_TRY(write_block_masks(c, field));
     if (!c->d_aux) c->gen_flags.clear();     // (no flag was ever set; psfmc_set_aux_layout sizes them for its n_sky)
     if (!c->gen_flags.empty()) {
@@ -2427,9 +2518,7 @@ extern "C" int psfmc_set_aux_layout(psfmc_ctx* c, int field, int n_aux, const in
                     c->n_sersic, L.n_sky, c->n_sersic);
     if (n_aux && (!aux_col || !aux_const || (L.n_sky && !sky_slope_flags) || (c->n_sersic && !sersic_general_flags)))
         return fail(PSFMC_EINVAL, "NULL aux array");
-    for (int j = 0; j < n_aux; ++j)
-        if (aux_col[j] < -1 || aux_col[j] >= L.n_params)
-            return fail(PSFMC_EINVAL, "aux value %d refers to column %d of %d", j, aux_col[j], L.n_params);
+    RC_TRY(check_table_entries("aux value", aux_col, n_aux, L.n_params, live_ties(c, field)));
     for (int k = 0; n_aux && k < c->n_sersic; ++k)
         if (sersic_general_flags[k] && !c->integ_flags.empty() && c->integ_flags[(size_t)field * c->n_sersic + k])
             return fail(PSFMC_EINVAL, "Sersic %d of field %d is pixel-integrated: boxiness and integrate exclude each other",
@@ -2541,9 +2630,11 @@ static int set_block_layout(psfmc_ctx* c, int b, int field, int n_sersic, const 
                         i, field, k.what);
     }
     const int len = aux_block_len(b, n_sersic);
-    for (int j = 0; any_here && j < len; ++j)
-        if (col[j] < -1 || col[j] >= L.n_params)
-            return fail(PSFMC_EINVAL, "%s value %d refers to column %d of %d", k.name, j, col[j], L.n_params);
+    if (any_here) {
+        char what[32];
+        snprintf(what, sizeof(what), "%s value", k.name);
+        RC_TRY(check_table_entries(what, col, len, L.n_params, live_ties(c, field)));
+    }
     // (a field's blocks are registered in table order: a call drops the blocks behind its own with their entries)
     bool behind = false;
     for (int j = b + 1; j < kAuxBlocks; ++j) behind = behind || !r.block[j].empty();
@@ -4378,6 +4469,14 @@ extern "C" int psfmc_group_set_layout(psfmc_group* g, int n_sky, int n_params, c
 extern "C" int psfmc_group_set_priors(psfmc_group* g, int n_params, const int* family, const double* params) {
     if (!g) return fail(PSFMC_EINVAL, "group is NULL");
     for (psfmc_ctx* c : g->ctx) RC_TRY(psfmc_set_priors(c, 0, n_params, family, params));
+    return PSFMC_OK;
+}
+
+extern "C" int psfmc_group_set_ties(psfmc_group* g, int n_ties, const int* src_col, const int* ratio_col,
+                                    const double* ratio_const, const int* offset_col, const double* offset_const) {
+    if (!g) return fail(PSFMC_EINVAL, "group is NULL");
+    for (psfmc_ctx* c : g->ctx)
+        RC_TRY(psfmc_set_ties(c, 0, n_ties, src_col, ratio_col, ratio_const, offset_col, offset_const));
     return PSFMC_OK;
 }
 

@@ -71,6 +71,13 @@ struct ThetaLayout {
     int n_tru;
     int n_bnd;
     const int* tru_side;
+    // ties (psfmc_set_ties): an entry e <= -2 of slot_col, aux_col or a block's columns names tie t = -2 - e, whose
+    // value is ratio * theta[source] + offset (theta_value).  tie_col [3 n_ties]: the source columns, then the ratio
+    // columns, then the offset columns (-1: the constant); tie_const [2 n_ties]: the ratio constants, then the offset
+    // constants.  Both stay in global memory beside the aux tables; 0 / nullptr: none (a model without ties).
+    int n_ties;
+    const int* tie_col;
+    const double* tie_const;
 };
 
 // where k_theta_prep writes the walkers' auxiliary vectors: aux[w][stride] (stride: the context's, the same for
@@ -370,9 +377,29 @@ __device__ inline double prior_logp_more(int fam, double x, double a, double b, 
 // after a barrier one wave per Sersic forms Sigma_e and its prep block, and after another
 // task 0's wave writes the head of the prep record from the largest peak estimate.
 // Walkers outside the prior support get skip = 1; their prep record is scratch.
+// The value a table entry stands for in one walker's vector: column `entry` of theta, the constant (-1), or tie
+// t = -2 - entry: ratio * theta[source] + offset as two separately rounded operations, product then sum -- the
+// roundings of numpy's `ratio * source + offset`, so no FMA contraction.  Every reader of slot_col, aux_col and the
+// blocks' columns goes through here.
+__device__ inline double theta_value(const ThetaLayout& L, const double* __restrict__ theta, int entry, double konst) {
+#pragma clang fp contract(off)
+    // a layout without ties decides on a scalar (n_ties comes with the kernel's arguments): its readers do not wait
+    // for the table entry before they know that there is no tie to look for
+    const double plain = entry >= 0 ? theta[entry] : konst;
+    if (L.n_ties == 0 || entry >= -1) return plain;
+    // the five table entries are read unconditionally: independent loads, one round trip to global memory (the
+    // kernels that come here are chains of latencies)
+    const int t = -2 - entry, n = L.n_ties;
+    const int sc = L.tie_col[t], rc = L.tie_col[n + t], oc = L.tie_col[2 * n + t];
+    const double rk = L.tie_const[t], ok = L.tie_const[n + t];
+    const double r = rc >= 0 ? theta[rc] : rk;
+    const double o = oc >= 0 ? theta[oc] : ok;
+    const double prod = r * theta[sc];
+    return prod + o;
+}
+
 __device__ inline double theta_slot(const ThetaLayout& L, const double* __restrict__ theta, int s) {
-    const int col = L.slot_col[s];
-    return col >= 0 ? theta[col] : L.slot_const[s];
+    return theta_value(L, theta, L.slot_col[s], L.slot_const[s]);
 }
 
 // Sersic axis-ratio constraint (Sersic.py:41-45): -inf if some component has reff_b > reff, else lp
@@ -645,8 +672,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                 double* a = ax.aux + (size_t)w * ax.stride;
                 const int n_base = G.n_aux - G.n_fou - G.n_spi - G.n_rad - G.n_tru - G.n_bnd;
                 for (int j = 0; j < n_base; ++j) {
-                    const int col = G.aux_col[j];
-                    const double v = col >= 0 ? th[col] : G.aux_const[j];
+                    const double v = theta_value(L, th, G.aux_col[j], G.aux_const[j]);
                     a[j] = v;
                     if (j >= 2 * G.n_sky && (!(v > -2.0) || !(v < INFINITY))) lp = -INFINITY;
                 }
@@ -657,8 +683,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                         double sum_abs = 0.0;
                         bool fin = true;
                         for (int j = j0; j < j0 + 12; ++j) {
-                            const int col = G.aux_col[j];
-                            const double v = col >= 0 ? th[col] : G.aux_const[j];
+                            const double v = theta_value(L, th, G.aux_col[j], G.aux_const[j]);
                             a[j] = v;
                             fin = fin && fabs(v) < INFINITY;
                             if (!((j - j0) & 1)) sum_abs += fabs(v);
@@ -675,8 +700,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                         double v6[6];
                         bool fin = true;
                         for (int j = 0; j < 6; ++j) {
-                            const int col = G.aux_col[j0 + j];
-                            const double v = col >= 0 ? th[col] : G.aux_const[j0 + j];
+                            const double v = theta_value(L, th, G.aux_col[j0 + j], G.aux_const[j0 + j]);
                             a[j0 + j] = v;
                             v6[j] = v;
                             fin = fin && fabs(v) < INFINITY;
@@ -691,9 +715,8 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // finite or <= 1; a Ferrer's alpha or beta not finite, alpha < 0 or beta >= 2
                     int k = 0;
                     for (int j0 = G.n_aux - G.n_bnd - G.n_tru - G.n_rad; j0 < G.n_aux - G.n_bnd - G.n_tru; j0 += 2, ++k) {
-                        const int c0 = G.aux_col[j0], c1 = G.aux_col[j0 + 1];
-                        const double v0 = c0 >= 0 ? th[c0] : G.aux_const[j0];
-                        const double v1 = c1 >= 0 ? th[c1] : G.aux_const[j0 + 1];
+                        const double v0 = theta_value(L, th, G.aux_col[j0], G.aux_const[j0]);
+                        const double v1 = theta_value(L, th, G.aux_col[j0 + 1], G.aux_const[j0 + 1]);
                         a[j0] = v0;
                         a[j0 + 1] = v1;
                         const int kind = G.rad_kind[k];
@@ -709,9 +732,8 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     for (int j0 = G.n_aux - G.n_bnd - G.n_tru; j0 < G.n_aux - G.n_bnd; j0 += 4, ++k) {
                         const int sides = G.tru_side[k];
                         for (int j = 0; j < 4; j += 2) {
-                            const int c0 = G.aux_col[j0 + j], c1 = G.aux_col[j0 + j + 1];
-                            const double lo = c0 >= 0 ? th[c0] : G.aux_const[j0 + j];
-                            const double hi = c1 >= 0 ? th[c1] : G.aux_const[j0 + j + 1];
+                            const double lo = theta_value(L, th, G.aux_col[j0 + j], G.aux_const[j0 + j]);
+                            const double hi = theta_value(L, th, G.aux_col[j0 + j + 1], G.aux_const[j0 + j + 1]);
                             a[j0 + j] = lo;
                             a[j0 + j + 1] = hi;
                             if (((sides >> (j >> 1)) & 1) && (!(lo >= 0.0) || !(hi > lo) || !(hi < INFINITY)))
@@ -723,8 +745,7 @@ k_theta_prep(ThetaLayout G, const double* __restrict__ theta,
                     // the bending amplitudes, per Sersic slot four (zeros for absent modes); outside the support: a
                     // value not finite
                     for (int j = G.n_aux - G.n_bnd; j < G.n_aux; ++j) {
-                        const int col = G.aux_col[j];
-                        const double v = col >= 0 ? th[col] : G.aux_const[j];
+                        const double v = theta_value(L, th, G.aux_col[j], G.aux_const[j]);
                         a[j] = v;
                         if (!(fabs(v) < INFINITY)) lp = -INFINITY;
                     }

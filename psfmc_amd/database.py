@@ -101,8 +101,36 @@ def save_database(sampler, model, db_name, meta_dict=None, sample_index='referen
     # a model without the keyword writes the header it always wrote
     for key, val in getattr(model, 'header_flags', dict)().items():
         meta[key] = (val, _FLAG_COMMENTS.get(key.lstrip('0123456789'), _INTEGRATE_COMMENT))
+    # the ties of the model (`Tied`): the trace holds the free columns, the header how the tied attributes follow
+    # them; a model without ties writes the header it always wrote
+    ties = list(getattr(model, 'tie_records', ()))
+    if ties:
+        meta['MCTIES'] = (len(ties), 'number of tied attributes')
+        for k, (tied, source, ratio, offset) in enumerate(ties):
+            meta['MCTIE{}'.format(k)] = ('{} {}'.format(tied, source), 'tied attribute and its source')
+            # a scalar constant is a FITS float, a column its name, a vector constant its numbers in one string
+            text = lambda v: ','.join(repr(x) for x in v) if isinstance(v, tuple) else v
+            meta['MCTIR{}'.format(k)] = (text(ratio), 'ratio of the tie: a number or its column')
+            meta['MCTIO{}'.format(k)] = (text(offset), 'offset of the tie: a number or its column')
     fits_io.write_table(db_name, cols, annotate_metadata(meta))
     return load_database(db_name)
+
+
+def database_ties(database):
+    """The ties a database's header records (`save_database`): [(tied fitsname, source fitsname, ratio, offset)],
+    ratio and offset each a float, a tuple of floats (one per element of a vector attribute) or the fitsname of the
+    column that holds it; [] for a model without ties."""
+    def term(val):
+        if not isinstance(val, str):                   # a FITS number: a scalar constant
+            return float(val)
+        if ',' in val:                                 # no column name holds a comma: a vector constant
+            return tuple(float(v) for v in val.split(','))
+        return val.strip()
+    out = []
+    for k in range(int(database.meta.get('MCTIES', 0))):
+        tied, source = str(database.meta['MCTIE{}'.format(k)]).split()
+        out.append((tied, source, term(database.meta['MCTIR{}'.format(k)]), term(database.meta['MCTIO{}'.format(k)])))
+    return out
 
 
 def load_database(db_name):

@@ -279,6 +279,10 @@ def load_library():
     lib.psfmc_set_aux_layout.argtypes = [vp, ci, ci, ip, _c_double_p, ip, ip]
     lib.psfmc_set_aux_rows.restype = ci
     lib.psfmc_set_aux_rows.argtypes = [vp, ci, _c_double_p]
+    lib.psfmc_set_ties.restype = ci
+    lib.psfmc_set_ties.argtypes = [vp, ci, ci, ip, ip, _c_double_p, ip, _c_double_p]
+    lib.psfmc_group_set_ties.restype = ci
+    lib.psfmc_group_set_ties.argtypes = [vp, ci, ip, ip, _c_double_p, ip, _c_double_p]
     lib.psfmc_group_set_aux_layout.restype = ci
     lib.psfmc_group_set_aux_layout.argtypes = [vp, ci, ip, _c_double_p, ip, ip]
     lib.psfmc_set_fourier_layout.restype = ci
@@ -452,6 +456,21 @@ def _aux_layout_args(aux_col, aux_const, sky_flags, sersic_flags):
             len(col), len(sky), len(ser)))
     ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     return (col, const, sky, ser), (len(col), ipt(col), _dp(const), ipt(sky), ipt(ser))
+
+
+MAX_TIES = 64              # PSFMC_MAX_TIES: tied values per field (a tied `xy` is two)
+
+
+def _tie_args(src_col, ratio_col, ratio_const, offset_col, offset_const):
+    """The arrays of psfmc_set_ties (kept alive by the caller's tuple) and their ctypes pointers: per tie the source
+    column, the ratio's column or -1 and constant, the offset's column or -1 and constant."""
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int64).astype(np.int32), dtype=np.int32).ravel()
+    src, rcol, ocol = i32(src_col), i32(ratio_col), i32(offset_col)
+    rconst, oconst = _f64(ratio_const).ravel(), _f64(offset_const).ravel()
+    if not (len(src) == len(rcol) == len(ocol) == len(rconst) == len(oconst)):
+        raise ValueError('ties: five arrays of one length')
+    ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    return (src, rcol, ocol, rconst, oconst), (len(src), ipt(src), ipt(rcol), _dp(rconst), ipt(ocol), _dp(oconst))
 
 
 FOURIER_MODES = 6          # PSFMC_FOURIER_MODES: modes 1 ... 6, an amplitude and a phase entry each
@@ -656,6 +675,8 @@ def debug_valu_rate(waves_per_simd=2, iters=20000, device=0):
 class Context(_BlockLayouts):
     """One observed field resident on one GPU (wraps `psfmc_ctx`)."""
 
+    has_ties = False                  # does the registered layout have ties (`set_ties`)?
+
     IMAGE_KINDS = ('raw_model', 'convolved_model', 'residual', 'composite_ivm',
                    'point_source_subtracted')
 
@@ -780,6 +801,15 @@ class Context(_BlockLayouts):
                             lambda n_w: _send_aux_rows(self._lib, self._ctx, self._check, aux, n_w))
 
     # -- raw emcee vectors (device-side priors and derivation) ---------------
+    def set_ties(self, src_col, ratio_col, ratio_const, offset_col, offset_const):
+        """Ties (psfmc_set_ties; BEFORE `set_layout`, which they take effect with): tie t is
+        ratio * theta[src_col[t]] + offset, ratio / offset each a column of theta or -1 and a constant; an entry
+        -2 - t of a column table names it.  Empty arrays clear the ties.  A context that never gets the call is what
+        it was without it."""
+        keep, args = _tie_args(src_col, ratio_col, ratio_const, offset_col, offset_const)
+        self._check(self._lib.psfmc_set_ties(self._ctx, 0, *args))
+        self.has_ties = args[0] > 0
+
     def set_layout(self, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees,
                    mag_zeropoint, family, p0, p1, p2):
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
@@ -1079,6 +1109,7 @@ class FieldSetContext(object):
         self.n_ps, self.n_sersic = int(n_ps), int(n_sersic)
         self.max_walkers, self.device = int(max_walkers), int(device)
         self.n_params = None
+        self._tied_fields = set()                     # the fields whose registered layout has ties
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         ipt = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         ny, nx = i32([sh[0] for sh in self.shapes]), i32([sh[1] for sh in self.shapes])
@@ -1126,6 +1157,15 @@ class FieldSetContext(object):
         owner = self
 
         class _Proxy(_BlockLayouts):
+            @property
+            def has_ties(self):
+                return field in owner._tied_fields
+
+            def set_ties(self, src_col, ratio_col, ratio_const, offset_col, offset_const):
+                keep, args = _tie_args(src_col, ratio_col, ratio_const, offset_col, offset_const)
+                owner._check(owner._lib.psfmc_set_ties(owner._ctx, int(field), *args))
+                (owner._tied_fields.add if args[0] else owner._tied_fields.discard)(field)
+
             def set_layout(self, n_sky, n_params, slot_col, slot_const, ps_method, sersic_degrees,
                            mag_zeropoint, family, p0, p1, p2):
                 i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
@@ -1652,6 +1692,8 @@ class ContextGroup(_BlockLayouts):
     `psfmc_group`): walkers are split into contiguous blocks, one per listed device.
     The one-process-per-GPU form (torch.distributed / RCCL) is `psfmc_amd.parallel`."""
 
+    has_ties = False                  # as `Context.has_ties`
+
     def __init__(self, devices, sci, obs_var, bad_px, psfs, psf_vars, n_ps, n_sersic,
                  max_walkers=4096, backend='fused'):
         self._lib = load_library()
@@ -1698,6 +1740,12 @@ class ContextGroup(_BlockLayouts):
             self._grp, int(n_sky), int(n_params), ipt(slot_col), _dp(slot_const), ipt(ps_method),
             ipt(sersic_degrees), float(mag_zeropoint), ipt(family), _dp(p0), _dp(p1), _dp(p2)))
         self.n_params = int(n_params)
+
+    def set_ties(self, src_col, ratio_col, ratio_const, offset_col, offset_const):
+        """`Context.set_ties` on every device of the group."""
+        keep, args = _tie_args(src_col, ratio_col, ratio_const, offset_col, offset_const)
+        self._check(self._lib.psfmc_group_set_ties(self._grp, *args))
+        self.has_ties = args[0] > 0
 
     def set_priors(self, family, params):
         """`Context.set_priors` on every device of the group."""

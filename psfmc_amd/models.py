@@ -13,7 +13,7 @@ import copy
 import numpy as np
 
 from .ModelComponents import Configuration, PointSource, Sersic, Sky
-from .ModelComponents.ComponentBase import ComponentBase
+from .ModelComponents.ComponentBase import ComponentBase, Tied
 from .ModelComponents.PointSource import SHIFT_METHODS
 from .ModelComponents.PSFSelector import PSFSelector
 from .model_parser import component_list_from_file
@@ -114,6 +114,15 @@ def _device_prior(prior, width):
     return (code,) + tuple(params) + (0.0,) * (4 - len(params))
 
 
+def _tie_term(term, name_attr):
+    """A tie's ratio or offset as a header records it: the column's name for a prior, else the number -- a float, or
+    a tuple of floats for a vector constant."""
+    if hasattr(term, 'value'):
+        return getattr(term, name_attr)
+    vals = tuple(float(v) for v in np.ravel(term))
+    return vals[0] if len(vals) == 1 else vals
+
+
 class MultiComponentModel(object):
     """A 2-D surface-brightness model made of components (Sky, PointSource,
     Sersic) plus one Configuration, given as a model file or a list
@@ -167,6 +176,7 @@ class MultiComponentModel(object):
             pos += n
         self._num_params = pos
         self._param_vector = np.zeros(pos)
+        self._ties = self._collect_ties(components)
 
         self._sky = [c for c in components if isinstance(c, Sky)]
         self._ps = self.psf_comps
@@ -186,6 +196,105 @@ class MultiComponentModel(object):
         self.accumulated_samples = 0
         self._device_samples = 0
         self.reset_images()
+
+    # -- ties ------------------------------------------------------------------
+    @staticmethod
+    def _collect_ties(components):
+        """The model's ties in component and attribute order: [(component, attr, source component, source attr)],
+        checked -- ValueError, naming the attribute, for a tie on or to the PSF index, a source that is itself tied or
+        belongs to no component of this model, and widths that do not match."""
+        owner = {}                                    # id(prior) -> (component, attr) of every free attribute
+        for comp in components:
+            for attr in comp.free_names():
+                if id(comp._priors[attr]) in owner:
+                    first = owner[id(comp._priors[attr])]
+                    raise ValueError('{}.{}: the prior object is also given to {}.{}; one object is one parameter -- '
+                                     'to make the two equal give Tied(<the prior>) to one of them, to keep them '
+                                     'independent give each its own prior'.format(
+                                         type(comp).__name__, attr, type(first[0]).__name__, first[1]))
+                owner[id(comp._priors[attr])] = (comp, attr)
+        ties = []
+        for comp in components:
+            kind = type(comp).__name__
+            for attr in sorted(getattr(comp, '_ties', {})):
+                tie, what = comp._ties[attr], '{}.{}'.format(kind, attr)
+                if isinstance(comp, PSFSelector):
+                    raise ValueError('{}: the PSF index cannot be tied'.format(what))
+                if isinstance(tie.source, Tied):
+                    raise ValueError('{}: the source of a Tied is itself tied; chains of ties are not supported '
+                                     '(tie to its source)'.format(what))
+                if not hasattr(tie.source, 'value') or id(tie.source) not in owner:
+                    raise ValueError('{}: the source of the Tied is not a free parameter of a component of this '
+                                     'model (give the same prior object to the source attribute)'.format(what))
+                src_comp, src_attr = owner[id(tie.source)]
+                if isinstance(src_comp, PSFSelector):
+                    raise ValueError('{}: the PSF index cannot be the source of a Tied'.format(what))
+                if src_attr.endswith(tuple('_' + t for t in comp.TIE_TERMS)) and src_attr not in src_comp._declared:
+                    raise ValueError('{}: the source of the Tied is the ratio / offset of another tie'.format(what))
+                width = comp.attr_width(attr)
+                if tie.source.size != width:
+                    raise ValueError('{}: a {}-element attribute tied to a source of {} element(s)'.format(
+                        what, width, tie.source.size))
+                for term in comp.TIE_TERMS:
+                    val = getattr(tie, term)
+                    if isinstance(val, Tied):
+                        raise ValueError('{}: the {} of a Tied is a number or a prior'.format(what, term))
+                    size = val.size if hasattr(val, 'value') else np.size(val)
+                    if size not in (1, width):
+                        raise ValueError('{}: the {} has {} elements; one, or the attribute\'s {}'.format(
+                            what, term, size, width))
+                    if not hasattr(val, 'value') and not np.all(np.isfinite(np.asarray(val, dtype=np.float64))):
+                        raise ValueError('{}: the {} must be finite'.format(what, term))
+                ties.append((comp, attr, src_comp, src_attr))
+        if sum(c.attr_width(a) for c, a, _, _ in ties) > engine.MAX_TIES:
+            raise ValueError('a model holds at most {} tied values'.format(engine.MAX_TIES))
+        return ties
+
+    def _tie_terms(self, comp, attr, free, n_w):
+        """(ratio, offset) of a tie as arrays that broadcast against the source's [W] or [W, k] values."""
+        tie, width, out = comp._ties[attr], comp.attr_width(attr), []
+        for term in comp.TIE_TERMS:
+            key = '{}_{}'.format(attr, term)
+            if key in free:
+                val = free[key]                       # [W], or [W, k]
+                out.append(val[:, None] if width > 1 and val.ndim == 1 else val)
+            else:
+                out.append(np.asarray(getattr(tie, term), dtype=np.float64))
+        return out
+
+    def _resolved(self, theta):
+        """{id(component): {attr: [W] or [W, k]}} of the tied attributes at theta [W, P]: the numpy definition,
+        `ratio * source + offset`."""
+        if not self._ties:
+            return {}
+        free = {id(c): c.free_values_batch(theta[:, s]) for c, s in zip(self.components, self._spans)}
+        out = {}
+        for comp, attr, src_comp, src_attr in self._ties:
+            ratio, offset = self._tie_terms(comp, attr, free[id(comp)], theta.shape[0])
+            out.setdefault(id(comp), {})[attr] = Tied.resolve(free[id(src_comp)][src_attr], ratio, offset)
+        return out
+
+    def _values(self, theta):
+        """{id(component): its `values_batch`} at theta [W, P], tied attributes resolved."""
+        res = self._resolved(theta)
+        return {id(c): c.values_batch(theta[:, s], res.get(id(c))) for c, s in zip(self.components, self._spans)}
+
+    def tied_values(self, theta):
+        """{trace name of the tied attribute: [W] or [W, k]} at theta ([P] or [W, P]): ratio * source + offset."""
+        res = self._resolved(self._theta(theta))
+        return {comp._ties[attr].name: res[id(comp)][attr] for comp, attr, _, _ in self._ties}
+
+    @property
+    def tie_records(self):
+        """The ties as a database header records them: [(tied fitsname, source fitsname, ratio, offset)], ratio and
+        offset each the number (a float; a tuple of floats, one per element, for a vector constant) or the fitsname of
+        its column."""
+        out = []
+        for comp, attr, src_comp, src_attr in self._ties:
+            tie = comp._ties[attr]
+            terms = [_tie_term(getattr(tie, t), 'fitsname') for t in comp.TIE_TERMS]
+            out.append((tie.fitsname, src_comp._priors[src_attr].fitsname, terms[0], terms[1]))
+        return out
 
     # -- engine --------------------------------------------------------------
     @property
@@ -233,10 +342,27 @@ class MultiComponentModel(object):
                         params[pos + j] = [np.ravel(v)[j if np.size(v) > 1 else 0] for v in desc[1:]]
                 pos += width
         slot_col, slot_const = [], []
+        # the ties (psfmc_set_ties): one per tied element, named in the tables below by the entry -2 - t
+        tie_of, tie_rows = {}, []                     # (component id, attr, element) -> t; (src, ratio, offset) terms
+        for comp, attr, src_comp, src_attr in self._ties:
+            tie = comp._ties[attr]
+            for j in range(comp.attr_width(attr)):
+                row = [col_of[(id(src_comp), src_attr, j)]]
+                for term in comp.TIE_TERMS:
+                    val, key = getattr(tie, term), '{}_{}'.format(attr, term)
+                    if hasattr(val, 'value'):
+                        row += [col_of[(id(comp), key, j if val.size > 1 else 0)], 0.0]
+                    else:
+                        row += [-1, float(np.ravel(val)[j if np.size(val) > 1 else 0])]
+                tie_of[(id(comp), attr, j)] = len(tie_rows)
+                tie_rows.append(row)
 
         def add(comp, name, elem=0):
             key = (id(comp), name, elem)
-            if key in col_of:
+            if key in tie_of:
+                slot_col.append(-2 - tie_of[key])
+                slot_const.append(0.0)
+            elif key in col_of:
                 slot_col.append(col_of[key])
                 slot_const.append(0.0)
             else:
@@ -278,10 +404,16 @@ class MultiComponentModel(object):
                         slot_col.append(-1); slot_const.append(entry)
             blocks.append((name, getattr(self, tags), slot_col[n_before:], slot_const[n_before:]))
             del slot_col[n_before:], slot_const[n_before:]
-        if columns is not None:
-            aux_col = [int(columns[c]) if c >= 0 else -1 for c in aux_col]
-            blocks = [(name, tags, [int(columns[c]) if c >= 0 else -1 for c in col], const)
+        if columns is not None:                       # (constants and ties keep their entries)
+            aux_col = [int(columns[c]) if c >= 0 else c for c in aux_col]
+            blocks = [(name, tags, [int(columns[c]) if c >= 0 else c for c in col], const)
                       for name, tags, col, const in blocks]
+            tie_rows = [[int(columns[r[0]]), int(columns[r[1]]) if r[1] >= 0 else -1, r[2],
+                         int(columns[r[3]]) if r[3] >= 0 else -1, r[4]] for r in tie_rows]
+        # only a model with ties sends them (and one registered where a tied model stood clears them): every other
+        # model makes the calls it always made
+        if tie_rows or getattr(eng, 'has_ties', False):
+            eng.set_ties(*([list(v) for v in zip(*tie_rows)] if tie_rows else [[]] * 5))
 
         def register_aux():
             if self.has_aux:
@@ -294,7 +426,7 @@ class MultiComponentModel(object):
             if any(self.sersic_general_mean):
                 eng.set_general_mean(self.sersic_general_mean)
         if columns is not None:
-            slot_col = [int(columns[c]) if c >= 0 else -1 for c in slot_col]
+            slot_col = [int(columns[c]) if c >= 0 else c for c in slot_col]
             zero = np.zeros(n_params)
             eng.set_layout(len(self._sky), n_params, slot_col, slot_const,
                            [SHIFT_METHODS[c.shift_method] for c in self._ps],
@@ -382,21 +514,22 @@ class MultiComponentModel(object):
         theta = self._theta(theta)
         n_w = theta.shape[0]
         cols = []
+        all_vals = self._values(theta)
         for c, s in zip(self.components, self._spans):
             if isinstance(c, Sky):
-                sl = c.values_batch(theta[:, s])['slope'] if c.has_slope else np.zeros((n_w, 2))
+                sl = all_vals[id(c)]['slope'] if c.has_slope else np.zeros((n_w, 2))
                 sl = np.reshape(sl, (n_w, 2))
                 cols += [sl[:, 0], sl[:, 1]]
         for c, s in zip(self.components, self._spans):
             if isinstance(c, Sersic):
-                cols.append(np.reshape(c.values_batch(theta[:, s])['boxiness'], (n_w,)) if c.has_boxiness
+                cols.append(np.reshape(all_vals[id(c)]['boxiness'], (n_w,)) if c.has_boxiness
                             else np.zeros(n_w))
         present = [any(getattr(self, tags)) for _, tags, _ in _AUX_BLOCKS]
         for _, _, entries in _AUX_BLOCKS[:max([0] + [b + 1 for b, p in enumerate(present) if p])]:
             for c, s in zip(self.components, self._spans):
                 if isinstance(c, Sersic):
                     ents = entries(c)
-                    vals = c.values_batch(theta[:, s]) if any(isinstance(e, str) for e in ents) else {}
+                    vals = all_vals[id(c)]
                     cols += [np.reshape(vals[e], (n_w,)) if isinstance(e, str) else np.full(n_w, e) for e in ents]
         return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
 
@@ -505,8 +638,12 @@ class MultiComponentModel(object):
         theta = self._theta(theta)
         total = np.zeros(theta.shape[0])
         with np.errstate(all='ignore'):
+            res = self._resolved(theta)
             for comp, span in zip(self.components, self._spans):
-                total = total + comp.log_priors_batch(theta[:, span])
+                if id(comp) in res:
+                    total = total + comp.log_priors_batch(theta[:, span], res[id(comp)])
+                else:
+                    total = total + comp.log_priors_batch(theta[:, span])
         return total
 
     # -- host -> device rows ---------------------------------------------------
@@ -524,8 +661,7 @@ class MultiComponentModel(object):
         theta = self._theta(theta)
         n_w = theta.shape[0]
         zp = self.config.mag_zeropoint
-        vals = {id(c): c.values_batch(theta[:, s])
-                for c, s in zip(self.components, self._spans)}
+        vals = self._values(theta)
         cols = [sum((vals[id(c)]['adu'] for c in self._sky), np.zeros(n_w))]
         with np.errstate(all='ignore'):
             for c in self._ps:
@@ -966,6 +1102,25 @@ class JointModel(object):
                 raise ValueError('field {} has {} PSFs and field 0 has {}: every field needs the same number of '
                                  'PSFs'.format(f, len(m.config.psf_selector.psf_data), n_psf))
         per_field = set(per_field)
+        # ties: a tied attribute has no column to fit per field (its source may be per field), and -- as a shared
+        # parameter needs the same prior -- the ties are the same in every exposure
+        tie_names = {comp._ties[attr].name for comp, attr, _, _ in first._ties}
+        if per_field & tie_names:
+            raise ValueError('per_field names {} are tied attributes: a tied attribute follows its source (name the '
+                             'source in per_field)'.format(sorted(per_field & tie_names)))
+
+        def tie_key(m):
+            out = []
+            for comp, attr, src_comp, src_attr in m._ties:
+                tie = comp._ties[attr]
+                terms = tuple(getattr(tie, t).name if hasattr(getattr(tie, t), 'value') else
+                              tuple(float(v) for v in np.ravel(getattr(tie, t))) for t in comp.TIE_TERMS)
+                out.append((tie.name, src_comp._priors[src_attr].name) + terms)
+            return out
+        for f, m in enumerate(self.field_models):
+            if tie_key(m) != tie_key(first):
+                raise ValueError('field {}: the ties of a joint fit are the same in every field (same source, same '
+                                 'ratio and offset); got {} against field 0\'s {}'.format(f, tie_key(m), tie_key(first)))
         unknown = sorted(per_field - set(names))
         if unknown:
             raise ValueError('per_field names {} are not parameters of the model ({})'.format(unknown, names))
@@ -1102,6 +1257,19 @@ class JointModel(object):
             out[key] = same if 'F' not in marks else marks
         return out
 
+    @property
+    def tie_records(self):
+        """`MultiComponentModel.tie_records` of the joint fit (the ties are the same in every field), by the names
+        a joint database uses for its columns: [(tied name, source name, ratio, offset)]; a per-field source or
+        term stands for its `<name>_f<k>` blocks."""
+        first = self.field_models[0]
+        out = []
+        for comp, attr, src_comp, src_attr in first._ties:
+            tie = comp._ties[attr]
+            terms = [_tie_term(getattr(tie, t), 'name') for t in comp.TIE_TERMS]
+            out.append((tie.name, src_comp._priors[src_attr].name, terms[0], terms[1]))
+        return out
+
     def field_columns(self, f):
         """[P_f] joint column of each of field f's own columns."""
         return self._columns[f].copy()
@@ -1141,9 +1309,10 @@ class JointModel(object):
                 total = total + prior.logp_batch(theta[:, cols])
             for f, m in enumerate(self.field_models):
                 th = theta[:, self._columns[f]]
+                resolved = m._resolved(th)                     # once per field ({} for a model without ties)
                 for comp, span in zip(m.components, m._spans):
                     if isinstance(comp, Sersic):
-                        v = comp.values_batch(th[:, span])
+                        v = comp.values_batch(th[:, span], resolved.get(id(comp)))
                         total = np.where(v['reff_b'] > v['reff'], -np.inf, total)
         return total
 
