@@ -353,9 +353,9 @@ int psfmc_set_radial_layout(psfmc_ctx* ctx, int field, int n_sersic, const int* 
  * semi-major radius r_major = 1 / hypot(m00, m01) (boxiness, modes and winding included) and s = r_major rho, the
  * slot's value -- the Sersic law times its centroid term, a Moffat's or Ferrer's law, or with psfmc_set_general_mean
  * every sample of the pixel mean -- is multiplied by
- *     inner = (1 + tanh a(in_lo, in_hi)) / 2,  outer = (1 - tanh a(out_lo, out_hi)) / 2,
+ *     inner = 1 / (1 + exp(-2 a(in_lo, in_hi))),  outer = 1 / (1 + exp(+2 a(out_lo, out_hi))),
  *     a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo)
- * (0.018 / 0.982 at the two radii of a side; an absent side's factor is left out): the truncation follows the
+ * ((1 +- tanh a) / 2 without the cancellation; 0.018 / 0.982 at the two radii of a side; an absent side's factor is left out): the truncation follows the
  * component's own isophotes.  mag stays the total magnitude of the UNTRUNCATED component.  The call APPENDS these
  * 4 n_sersic entries to the field's auxiliary table BEHIND everything it holds.  A context with truncations ALWAYS
  * carries the Fourier, the spiral and the radial block: a field without them gets entries inside their supports that

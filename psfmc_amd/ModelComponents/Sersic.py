@@ -824,20 +824,24 @@ class Sersic(ComponentBase):
             r_major = 1 / hypot(m00, m01)            the row's semi-major radius in pixels (reff, fwhm, r_out)
             s     = r_major sqrt(rho2)               the generalised radius in pixels; 0 where u = v = 0
             a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo)          (the spiral ramp's argument)
-            inner = (1 + tanh(a(in_lo,  in_hi )))  / 2         0.018 at in_lo,  0.982 at in_hi
-            outer = (1 - tanh(a(out_lo, out_hi))) / 2          0.982 at out_lo, 0.018 at out_hi
+            inner = 1 / (1 + exp(-2 a(in_lo,  in_hi )))        0.018 at in_lo,  0.982 at in_hi
+            outer = 1 / (1 + exp(+2 a(out_lo, out_hi)))        0.982 at out_lo, 0.018 at out_hi
 
-        (outer is not 1 - ramp: no cancellation where it is small).  The truncation follows the component's own
-        isophotes; it has no centre or axis ratio of its own.  Support: `_truncation_ok`."""
+        These are (1 + tanh a) / 2 and (1 - tanh a) / 2 WRITTEN WITHOUT THEIR CANCELLATION: tanh saturates to -+1 at
+        |a| = 19, so the tanh forms are exactly 0 from there on, while the factor is e^(-2 |a|) -- 1e-17 at |a| = 19.6,
+        1e-280 at |a| = 322 -- and a component seen only through a ramp's tail (an inner ramp beyond the image, a ramp
+        a thousandth of a pixel wide) would be 0 in the definition and e^(-2 |a|) times its parent on the device.  An
+        exponent that overflows gives 1 / inf = 0.  The truncation follows the component's own isophotes; it has no
+        centre or axis ratio of its own.  Support: `_truncation_ok`."""
         in_lo, in_hi, out_lo, out_hi = truncation
         if (in_lo is None) != (in_hi is None) or (out_lo is None) != (out_hi is None):
             raise ValueError('truncation: a side is (lo, hi) or (None, None)')
         r_major = 1.0 / np.hypot(row[2], row[3])
         with np.errstate(all='ignore'):
             s = r_major * np.sqrt(np.where(centre, 0.0, rho2))
-            ramp = lambda lo, hi: np.tanh(2.0 * (2.0 * s - float(lo) - float(hi)) / (float(hi) - float(lo)))
-            inner = None if in_lo is None else 0.5 * (1.0 + ramp(in_lo, in_hi))
-            outer = None if out_lo is None else 0.5 * (1.0 - ramp(out_lo, out_hi))
+            arg = lambda lo, hi: 2.0 * (2.0 * s - float(lo) - float(hi)) / (float(hi) - float(lo))
+            inner = None if in_lo is None else 1.0 / (1.0 + np.exp(-2.0 * arg(in_lo, in_hi)))
+            outer = None if out_lo is None else 1.0 / (1.0 + np.exp(2.0 * arg(out_lo, out_hi)))
         return inner, outer
 
     @staticmethod
@@ -907,10 +911,11 @@ class Sersic(ComponentBase):
 
         def weight(r):
             w, s = 1.0, r_major * r
-            if in_lo is not None:
-                w *= 0.5 * (1.0 + np.tanh(2.0 * (2.0 * s - in_lo - in_hi) / (in_hi - in_lo)))
-            if out_lo is not None:
-                w *= 0.5 * (1.0 - np.tanh(2.0 * (2.0 * s - out_lo - out_hi) / (out_hi - out_lo)))
+            with np.errstate(over='ignore'):                 # (the factors as `truncation_weight` writes them)
+                if in_lo is not None:
+                    w *= 1.0 / (1.0 + np.exp(-4.0 * (2.0 * s - in_lo - in_hi) / (in_hi - in_lo)))
+                if out_lo is not None:
+                    w *= 1.0 / (1.0 + np.exp(4.0 * (2.0 * s - out_lo - out_hi) / (out_hi - out_lo)))
             return w
         cuts = sorted(set(v / r_major for v in truncation if v is not None and 0.0 < v / r_major < top))
         edges = [0.0] + cuts + [top]

@@ -54,8 +54,8 @@
 //
 // TRUNCATION (`Sersic / Moffat / Ferrer(..., truncation={'inner': (lo, hi), 'outer': (lo, hi)})`, GALFIT's truncation
 // function in spirit; definition: Sersic.py `Sersic.truncation_weight`): the component's value is multiplied by
-//     inner = (1 + tanh a(in_lo, in_hi)) / 2,  outer = (1 - tanh a(out_lo, out_hi)) / 2,
-//     a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo),  s = r_major rho
+//     inner = 1 / (1 + exp(-2 a(in_lo, in_hi))),  outer = 1 / (1 + exp(+2 a(out_lo, out_hi))),
+//     a(lo, hi) = 2 (2 s - lo - hi) / (hi - lo),  s = r_major rho        ((1 +- tanh a) / 2 without the cancellation)
 // with rho the component's own generalised radius (boxiness, modes and winding included) and r_major its semi-major
 // radius in pixels: the truncation follows the component's isophotes.  psfmc_set_truncation_layout appends kTruIn
 // entries per Sersic -- in_lo, in_hi, out_lo, out_hi -- BEHIND the laws' entries.  A context with truncations ALWAYS
@@ -396,6 +396,12 @@ __device__ __forceinline__ SpiPar load_spiral(const double* __restrict__ sp) {
     S.chk = ((S.cs + S.sn) + (S.icos + S.ek1)) + ((S.ek0 + S.alpha) + (S.l2ro + S.wind));
     return S;
 }
+// T at disk-plane radius r.  The exponent is capped at 1000 as in trunc_apply below: a ramp narrow against its radius
+// ((r_in + r_out) / (r_out - r_in) above ~177) has an exponent above 1024 inside r_in, where fast_exp2 returns inf and
+// the reciprocal's Newton step turns it into NaN; capped, T there is ~1e-301 and the winding angle 0 to every digit.
+__device__ __forceinline__ double spiral_ramp(const SpiPar& S, double r) {
+    return fast_rcp(1.0 + fast_exp2(__builtin_fmin(__builtin_fma(S.ek1, r, S.ek0), 1000.0)));
+}
 
 // sin and cos of t for the winding angle, |t| up to tens (thousands) of radians: t = n pi/2 + r by a two-constant
 // Cody-Waite reduction -- with fused multiply-adds the first step's error is one rounding of r, so r is good to
@@ -500,7 +506,7 @@ __device__ __forceinline__ double general_pixel(const GenPar& G, const FouPar& F
         const double r2 = __builtin_fma(X, X, Y * Y);
         const bool pos = r2 > 0.0;
         const double r = pos ? r2 * general_rsqrt(r2) : 0.0;
-        const double T = fast_rcp(1.0 + fast_exp2(__builtin_fma(S.ek1, r, S.ek0)));
+        const double T = spiral_ramp(S, r);
         double wt = S.wind * T;
         if (S.alpha != 0.0)                                            // wave-uniform; (r / r_out)^0 = 1 at r = 0 too
             wt *= pos ? fast_exp2(S.alpha * __builtin_fma(0.5, fast_log2(r2), -S.l2ro)) : 0.0;

@@ -86,7 +86,7 @@ __device__ __forceinline__ double general_point(const MeanPar& M, double x, doub
         const double r2 = __builtin_fma(X, X, Y * Y);
         const bool pos = r2 > 0.0;
         const double r = pos ? r2 * general_rsqrt(r2) : 0.0;
-        const double T = fast_rcp(1.0 + fast_exp2(__builtin_fma(S.ek1, r, S.ek0)));
+        const double T = spiral_ramp(S, r);
         double wt = S.wind * T;
         if (S.alpha != 0.0)                                            // wave-uniform; (r / r_out)^0 = 1 at r = 0 too
             wt *= pos ? fast_exp2(S.alpha * __builtin_fma(0.5, fast_log2(r2), -S.l2ro)) : 0.0;

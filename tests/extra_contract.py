@@ -24,7 +24,7 @@ MAG_ZP = 25.0
 PSF_SHAPE = (15, 13)
 FREE = object()
 ABSENT = object()
-KEYWORDS = ('integrate', 'boxiness', 'fourier', 'spiral', 'law', 'fixed', 'truncation')
+KEYWORDS = ('integrate', 'boxiness', 'fourier', 'spiral', 'law', 'fixed', 'truncation', 'bending')
 THREE = {1: (FREE, FREE), 3: (FREE, 25.0), 4: (FREE, FREE)}          # one constant phase among free ones
 MODES_1_4 = {1: (FREE, FREE), 4: (FREE, FREE)}
 
@@ -115,7 +115,7 @@ def make_model(case, sersics, slope=ABSENT, backend='fused', max_walkers=8, lean
     """Configuration (the case's PSFs, mask and zeropoint) + Sky (`slope`: FREE, two values or ABSENT) + PointSource +
     one Sersic per entry of `sersics`, a dict with any of `integrate`, `boxiness` (FREE or a value), `fourier`
     ({m: (amplitude, phase)}, FREE or values), `spiral` ({key: FREE or a value}, `Sersic`'s keys), `truncation`
-    ({side: (lo, hi)}, FREE or values) and `law`: 'moffat'
+    ({side: (lo, hi)}, FREE or values), `bending` ({m: a_m}, FREE or values) and `law`: 'moffat'
     or 'ferrer' -- a `Moffat` / `Ferrer` with its own argument names in the Sersic's place -- or (law, {argument: a
     constant}) for constants among the law's own arguments; `fixed`: {argument: a constant} among a plain Sersic's
     own (`xy`, `mag`, `reff`, `reff_b`, `index`).  FREE: the test's prior, a fresh object per model; those of
@@ -153,6 +153,8 @@ def make_model(case, sersics, slope=ABSENT, backend='fused', max_walkers=8, lean
         if 'truncation' in spec:
             kw['truncation'] = {k: tuple(Uniform(loc=-5.0, scale=95.0) if v is FREE else v for v in pair)
                                 for k, pair in spec['truncation'].items()}
+        if 'bending' in spec:
+            kw['bending'] = {m: Uniform(loc=-3.0, scale=6.0) if a is FREE else a for m, a in spec['bending'].items()}
         kw.update(xy=wide(), mag=Uniform(loc=15.0, scale=10.0), angle=30.0 if lean else Uniform(loc=-360, scale=720),
                   angle_degrees=True)
         if 'law' in spec:

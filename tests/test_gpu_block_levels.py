@@ -1,5 +1,5 @@
-"""The six forms a context's general launches take -- no block, modes only, a spiral only, modes and a spiral, a radial
-law, a truncation -- each registered on FIELD 1 ALONE of a two-field context (fused back end, 64 x 64, two Sersic
+"""The seven forms a context's general launches take -- no block, modes only, a spiral only, modes and a spiral, a radial
+law, a truncation, bending modes -- each registered on FIELD 1 ALONE of a two-field context (fused back end, 64 x 64, two Sersic
 slots, 8 walkers per field), so that the per-field state is read at an index above 0 and the context carries exactly
 the level's blocks.  Field 0 keeps a plain boxy Sersic.
 
@@ -30,8 +30,10 @@ LEVELS = {
     'modes+spiral': dict(boxiness=xc.FREE, fourier=MODES, spiral=ARMS),
     'law': dict(boxiness=xc.FREE, law='moffat'),
     'truncation': dict(boxiness=xc.FREE, truncation={'outer': (9.0, 14.0)}),
+    'bending': dict(boxiness=xc.FREE, bending={2: 0.2, 3: -0.1}),
 }
-BLOCK_CALLS = ('set_fourier_layout', 'set_spiral_layout', 'set_radial_layout', 'set_truncation_layout')
+BLOCK_CALLS = ('set_fourier_layout', 'set_spiral_layout', 'set_radial_layout', 'set_truncation_layout',
+               'set_bending_layout')
 
 
 class WithoutBlocks(object):

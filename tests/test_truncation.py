@@ -75,7 +75,9 @@ def test_the_ramps_at_their_four_radii():
     got = Sersic.truncated_image('moffat', row, (2.5, 0.0), 0.8, MODES, SPIRAL, (4.0, 8.0, None, None), (64, 64))
     par = Sersic.radial_image('moffat', row, (2.5, 0.0), 0.8, MODES, SPIRAL, (64, 64))
     s = 12.0 * np.sqrt(np.where(centre, 0.0, rho2))
-    assert np.allclose(got, par * 0.5 * (1 + np.tanh(2 * (2 * s - 12.0) / 4.0)), rtol=1e-15, atol=0.0)
+    # ((1 + tanh a) / 2 without its cancellation: 6e-6 at a = -6, where the tanh form has five digits fewer)
+    assert np.allclose(got, par * (1 / (1 + np.exp(-2 * (2 * (2 * s - 12.0) / 4.0)))), rtol=1e-15, atol=0.0)
+    assert np.allclose(got, par * 0.5 * (1 + np.tanh(2 * (2 * s - 12.0) / 4.0)), rtol=0.0, atol=1e-15 * par)
 
 
 def test_a_side_far_outside_the_image_is_one_while_the_other_acts():
@@ -84,7 +86,8 @@ def test_a_side_far_outside_the_image_is_one_while_the_other_acts():
     assert np.all(np.abs(far_out - inner) <= 1e-15 * inner) and np.nanmin(inner / image(sersic(boxiness=0.0))) < 0.02
     outer = image(sersic(truncation={'outer': (14.0, 20.0)}))
     far_in = image(sersic(truncation={'inner': (0.0, 1e-3), 'outer': (14.0, 20.0)}))
-    assert np.all(np.abs(far_in - outer) <= 1e-15 * outer) and outer.min() == 0.0 and outer.max() > 0
+    # (the factor in its tail is e^(-2 a), not the 0 of a saturated tanh: 3e-34 of the parent at the far corner)
+    assert np.all(np.abs(far_in - outer) <= 1e-15 * outer) and 0.0 < outer.min() < 1e-30 * outer.max()
     parent = image(sersic(boxiness=0.0))
     assert outer[32, 31] / parent[32, 31] > 0.999 and outer[60, 60] / parent[60, 60] < 1e-3
 
@@ -96,7 +99,8 @@ def test_the_centre_pixel_of_each_law():
     m = image(tr.moffat(xy=(30.0, 32.0), truncation=cut))
     row = tr.moffat(xy=(30.0, 32.0)).derived_row(ZP)
     s0 = Sersic.radial_central('moffat', row, (3.5, 0.0))
-    assert np.all(np.isfinite(m)) and m[32, 30] == s0 * (0.5 * (1.0 + np.tanh(-6.0)))
+    assert np.all(np.isfinite(m)) and m[32, 30] == s0 * (1.0 / (1.0 + np.exp(12.0)))
+    assert abs(m[32, 30] - s0 * (0.5 * (1.0 + np.tanh(-6.0)))) <= 1e-15 * s0
     f = image(tr.ferrer(xy=(30.0, 32.0), r_out=25.0, r_out_b=12.0, fourier={2: (0.1, 0.3)}, truncation=cut))
     assert np.all(np.isfinite(f)) and f[32, 30] > 0
     s = image(sersic(xy=(30.0, 32.0), truncation=cut))
@@ -110,10 +114,15 @@ def test_pixel_mean_applies_its_scheme_to_the_product():
     comp = sersic(boxiness=0.4, truncation=BOTH, pixel_mean=True)
     row, t = comp.derived_row(ZP), (4.0, 8.0, 14.0, 20.0)
     got = image(comp)
-    g = lambda x, y: Sersic.general_point(None, row, None, 0.4, [], None, np.float64(x), np.float64(y), t)
+    # (the samples on whole grids, as the definition takes them: numpy's array and scalar `**` differ in the last bit
+    # at one point in twenty, with or without a truncation)
+    g = lambda x, y: Sersic.general_point(None, row, None, 0.4, [], None, x, y, t)
+    yy, xx = np.mgrid[0:64, 0:64].astype(np.float64)
+    cyy, cxx = np.mgrid[0:65, 0:65].astype(np.float64) - 0.5
+    mid, cor = g(xx, yy), g(cxx, cyy)
     for py, px in ((20, 45), (32, 40), (50, 22)):
-        corners = 0.25 * ((g(px - 0.5, py - 0.5) + g(px + 0.5, py - 0.5)) + (g(px - 0.5, py + 0.5) + g(px + 0.5, py + 0.5)))
-        assert got[py, px] == (2.0 * g(px, py) + corners) / 3.0
+        corners = 0.25 * ((cor[py, px] + cor[py, px + 1]) + (cor[py + 1, px] + cor[py + 1, px + 1]))
+        assert got[py, px] == (2.0 * mid[py, px] + corners) / 3.0
     assert np.array_equal(got, Sersic.general_mean_image(None, row, None, 0.4, [], None, (64, 64), truncation=t))
 
 
